@@ -8,15 +8,19 @@ Termination / Command manager stack (6 reward terms, 2 termination terms, veloci
 data.  The path shards by env: every rank owns its own envs, the only cross-rank traffic is the logging all-reduce (RCCL).
 
     python bench.py                                   # 1 GPU, 65 536 envs
+    python bench.py --full                            # ... and every side measurement (sweep, roofline, CPU baseline, ...)
     python bench.py --gpus 8                          # starts 8 ranks itself (one per GPU), weak scaling: 65 536 envs per GPU
     python bench.py --gpus 8 --scaling strong --global-envs 65536 --config gait     # BASELINE config 5 sharded over 8 GPUs
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Timing: W warm-up steps, then BATCHES of exactly K steps, each bracketed by barrier + synchronize on both sides and taken as
-the max over ranks, repeated until at least 0.3 s has been timed; the MEDIAN batch is reported (``ms_per_step`` = median / K).
-Nothing else runs inside a timed batch: the HIP-event stamping of the dominant kernel (``roofline``) is a separate loop after
-the timed batches, and every figure in the JSON line is measured by this run (committed rocprofv3 / PMC summaries live under
-profiles/ and are quoted in DESIGN.md, not here).
+Timing: W warm-up steps, then ONE batch of exactly K = --steps steps, bracketed by barrier + synchronize on both sides and
+taken as the max over ranks: ``ms_per_step`` = batch / K, ``value`` = envs x K / batch.  --dump-outputs DIR then writes what
+the last timed step returned (dump_outputs).  That is all a plain run does.  --full adds the side measurements, each after the
+headline batch: further batches of K steps until at least 0.3 s has been timed (``timing``: median / min / max batch), the
+4 096 / 16 384-env ``sweep``, ``roofline``, ``roofline_hbm``, PMC ``traffic`` and ``cpu_baseline``.  Nothing else runs inside
+a timed batch: the HIP-event stamping of the dominant kernel (``roofline``) is a separate loop after the timed batches, and
+every figure in the JSON line is measured by this run (committed rocprofv3 / PMC summaries live under profiles/ and are
+quoted in DESIGN.md, not here).
 
 Prints ONE JSON line (rank 0).  ``roofline``: the fused post-physics launch that contains the reward fold (566 algorithmic
 B/env for this config), bytes ÷ its average duration from dispatch-timestamp HIP events on the launch stream.
@@ -27,6 +31,7 @@ cores of the same box over the N x D grid of BASELINE.md §3 (plan B2).
 import argparse
 import json
 import os
+import re
 import statistics
 import subprocess
 import sys
@@ -42,6 +47,7 @@ PRIMING_STEPS = 8      # setup, not warm-up: an env records its step over its fi
 HBM_POINT_ENVS = 1 << 20
 GRID_N = (64, 4096, 16384, 65536)
 GRID_D = (12, 28)
+DUMP_BYTES_MAX = 64 << 20
 # the package's default output contract (the reference's: every step returns a tensor of the caller's own — the fused launch writes
 # straight into it); GF_OBS_OUTPUT=static selects the persistent output slots instead (same step time within the box-to-box noise)
 OBS_OUTPUT = os.environ.get("GF_OBS_OUTPUT", "fresh")
@@ -124,6 +130,30 @@ def make_env(num_envs: int, config: str = "go2_cmd", dofs: int = 12):
         env = tasks.BASELINE_CONFIGS[config][1](num_envs)
     env.build()
     return env
+
+
+def dump_outputs(out_dir: str, step_out, log: dict) -> None:
+    """What one env.step() returned, as ``out_dir/<name>.npy``: obs, reward, terminated / truncated (0 / 1), every other observation
+    group, and the episode log (``log``, read from the same step) as float64 scalars.  When the per-env arrays exceed DUMP_BYTES_MAX
+    in all, every one of them keeps the same fixed, seeded sample of env rows (``env_index.npy``)."""
+    import numpy as np
+    import torch
+
+    obs, rew, term, trunc, extras = step_out
+    per_env = {"obs": obs, "reward": rew, "terminated": term, "truncated": trunc}
+    per_env.update({"obs_" + k: v for k, v in extras["observations"].items() if k != "policy"})
+    per_env = {k: (v.double() if v.dtype == torch.float64 else v.float()).cpu().numpy() for k, v in per_env.items()}
+    n = obs.shape[0]
+    row_bytes = sum(a.nbytes for a in per_env.values()) // n
+    if row_bytes * n > DUMP_BYTES_MAX:
+        keep = (DUMP_BYTES_MAX - (1 << 20)) // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        per_env = {k: a[idx] for k, a in per_env.items()}
+        per_env["env_index"] = idx.astype(np.float64)
+    scalars = {"episode_" + re.sub(r"[^A-Za-z0-9_.-]", "_", k): np.asarray(torch.as_tensor(v).double().cpu().numpy()) for k, v in log.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in {**per_env, **scalars}.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -271,6 +301,13 @@ def parse_args(argv):
                     help="recorded steps per logging all-reduce (world > 1): the statistics rows of K consecutive steps travel as ONE all-reduce "
                          "(K x 392 B).  0 (default) = 32 — the benchmark loop is lock-step on every rank, which is what K > 1 asks for "
                          "(distributed.attach); 1 = one asynchronous all-reduce per step, log reads rank-local (the library default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's envs) as DIR/<name>.npy, float32 / float64, at most 64 MB in "
+                         "all (above that, the same seeded sample of env rows in every per-env array; env_index.npy names the rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything besides the headline: more timed batches until >= 0.3 s (timing), the 4096 / 16384-env sweep, "
+                         "the stamping pass (roofline), roofline_hbm, PMC traffic and the CPU baseline; the --no-* options below "
+                         "leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true", help="skip the 4096 / 16384-env side measurements")
     ap.add_argument("--no-hbm-point", action="store_true", help="skip the 1 048 576-env roofline_hbm measurement")
@@ -285,7 +322,10 @@ def parse_args(argv):
     ap.add_argument("--profile-presleep-cycles", type=int, default=150000,
                     help="GPU spin (torch.cuda._sleep) enqueued in front of every stamped step of the stamping pass so that the stamped "
                          "kernel runs behind queued work as in the timed loop; 0 = off")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -461,27 +501,30 @@ def run_rank(args):
             dist.barrier()
         sync()
 
-    def timed_batches(e, a, steps):
-        """Batches of exactly `steps` steps, barrier + synchronize on both sides, max over ranks, until MIN_TIMED_S is covered."""
-        times = []
-        while True:
-            barrier()
-            t0 = time.perf_counter()
-            for i in range(steps):
-                e.step(a[i % len(a)])
-            host_dt = time.perf_counter() - t0
-            sync()
-            dt = time.perf_counter() - t0
-            barrier()
-            local_times.append(dt)   # this rank's own clock, before the max over ranks (reported per rank)
-            host_times.append(host_dt / steps)
-            if dist_on:
-                t = torch.tensor([dt], device=gs.device, dtype=torch.float64)
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-                dt = float(t.item())
-            times.append(dt)
-            if sum(times) >= MIN_TIMED_S or len(times) >= 1000:
-                return times
+    def timed_batch(e, a, steps):
+        """One batch of exactly `steps` steps, barrier + synchronize on both sides, max over ranks: (seconds, last step's return)."""
+        barrier()
+        t0 = time.perf_counter()
+        for i in range(steps):
+            last = e.step(a[i % len(a)])
+        host_dt = time.perf_counter() - t0
+        sync()
+        dt = time.perf_counter() - t0
+        barrier()
+        local_times.append(dt)   # this rank's own clock, before the max over ranks (reported per rank)
+        host_times.append(host_dt / steps)
+        if dist_on:
+            t = torch.tensor([dt], device=gs.device, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
+        return dt, last
+
+    def timed_batches(e, a, steps, times=()):
+        """Batches of exactly `steps` steps after the ones already in `times`, until MIN_TIMED_S is covered."""
+        times = list(times)
+        while sum(times) < MIN_TIMED_S:
+            times.append(timed_batch(e, a, steps)[0])
+        return times
 
     def stamp_pass(e, a, bytes_per_launch):
         """HIP-event (dispatch timestamp) durations of the dominant kernel, in a loop of its own after the timed batches."""
@@ -510,8 +553,14 @@ def run_rank(args):
         env.step(acts[i % 8])
     for i in range(args.warmup):
         env.step(acts[i % 8])
-    times = timed_batches(env, acts, args.steps)
-    batch = statistics.median(times)
+    batch, last = timed_batch(env, acts, args.steps)   # the headline: exactly --steps timed steps
+    log = dict(last[4]["episode"])   # keep the logging path honest: read the last step's global statistics (on every rank)
+    tm_ = env.managers["termination"]
+    reset_frac = float((tm_._terminated_buf | tm_._truncated_buf).float().mean()) if tm_ is not None else 0.0   # (after the timed region)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, log)
+    del last
+    times = timed_batches(env, acts, args.steps, [batch]) if args.full else [batch]
     # what each rank ran on and measured by its own clock: makes the one line checkable against the launcher's view of the node
     mine = {"rank": rank, "device": ("cpu (rehearsal)" if rehearsal else torch.cuda.get_device_name(gs.device)), "device_index": (None if rehearsal else gs.device.index),
             "num_envs": N, "env_offset": env.env_offset, "batch_ms_median": statistics.median(local_times) * 1e3, "batch_ms_max": max(local_times) * 1e3,
@@ -520,9 +569,6 @@ def run_rank(args):
     if dist_on:
         per_rank = [None] * dist.get_world_size()
         dist.all_gather_object(per_rank, mine)
-    _ = dict(env.extras["episode"])   # keep the logging path honest: read one step's global statistics (on every rank)
-    tm_ = env.managers["termination"]
-    reset_frac = float((tm_._terminated_buf | tm_._truncated_buf).float().mean()) if tm_ is not None else 0.0   # (after the timed region)
 
     fused = env._trace is not None and env._trace.post_refs is not None
     rm = env.managers["reward"]
@@ -535,7 +581,7 @@ def run_rank(args):
         what = backend.post_describe(env._trace.post_refs).split(":")[0]   # "program <id> (<name>)"
         kernel = f"gf::post_ws_kernel, {what} (termination+reward+command+reset+observe fused)"
     roof = None
-    if not args.no_profile and not rehearsal and per_env is not None:
+    if args.full and not args.no_profile and not rehearsal and per_env is not None:
         m = stamp_pass(env, acts, per_env * N)   # on every rank (the steps contain the logging collective); rank 0 reports its own
         if m is not None:
             roof = dict({"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": None, "kernel": kernel,
@@ -564,18 +610,19 @@ def run_rank(args):
                        "resets_last_step_frac": reset_frac,
                        "setup_steps_before_warmup": PRIMING_STEPS, "fused_post_physics": fused, "observation_output": OBS_OUTPUT,
                        "launches_per_step": env._trace.n_ops if env._trace is not None else None},
-            "timing": {"batches": len(times), "timed_s": sum(times), "batch_ms_median": batch * 1e3, "batch_ms_min": min(times) * 1e3,
-                       "batch_ms_max": max(times) * 1e3, "rule": f"batches of exactly {args.steps} steps (barrier + synchronize both sides, max over ranks) "
-                                                                  f"until >= {MIN_TIMED_S} s are timed; median batch reported"},
+            "timing": {"batches": len(times), "timed_s": sum(times), "batch_ms_median": statistics.median(times) * 1e3, "batch_ms_min": min(times) * 1e3,
+                       "batch_ms_max": max(times) * 1e3, "rule": f"value / ms_per_step: the first batch, exactly {args.steps} steps (barrier + synchronize "
+                                                                  f"both sides, max over ranks)" + (f"; --full: further batches of {args.steps} until "
+                                                                  f">= {MIN_TIMED_S} s are timed, batch_ms_* over all of them" if args.full else "")},
             "roofline": roof,
             "rccl_ranks": (dist.get_world_size() if dist_on else 1),   # read back from the process group, not from --gpus
             "ranks": per_rank,
         }
     del env
-    if world == 1 and not rehearsal:
+    if args.full and world == 1 and not rehearsal:
         if not args.no_sweep and go2:
-            # BASELINE.json quotes the metric "@ 4096–65536 envs": the other end of the range and the middle, same workload, same
-            # timing rule (informational; `value` is the 65 536-env figure unless --num-envs says otherwise)
+            # BASELINE.json quotes the metric "@ 4096–65536 envs": the other end of the range and the middle, same workload, median
+            # of batches of K steps until >= 0.3 s (informational; `value` is the 65 536-env figure unless --num-envs says otherwise)
             out["sweep"] = []
             for n_s in (4096, 16384):
                 if n_s == N:

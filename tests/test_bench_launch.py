@@ -27,7 +27,7 @@ def _bench(*argv, timeout=240):
 
 @pytest.mark.timeout(300)
 def test_gpus_2_self_launch_weak():
-    out = _bench("--gpus", "2", "--steps", "6", "--warmup", "2", "--num-envs", "96", "--no-cpu-baseline")
+    out = _bench("--gpus", "2", "--steps", "6", "--warmup", "2", "--num-envs", "96", "--no-cpu-baseline", "--full")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["steps"] == 6
     assert out["config"]["num_envs_per_gpu"] == 96 and out["config"]["global_num_envs"] == 192
     assert out["config"]["parallelism"] == "env-shard x2" and out["config"]["dist_backend"] == "gloo"
@@ -94,6 +94,73 @@ def test_single_rank_line_and_torchrun_env():
     assert out["rccl_ranks"] == 1 and len(out["ranks"]) == 1 and out["ranks"][0]["num_envs"] == 64
 
 
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("_bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_times_exactly_steps_and_dumps_the_last_timed_step(tmp_path, oracle_backend):
+    """A plain run times one batch of exactly --steps steps, and --dump-outputs writes what the last of them returned: the same
+    arrays from two runs with the same arguments, and the same as this process's own run of the trajectory (setup steps, warm-up,
+    timed steps) on the oracle."""
+    import numpy as np
+    import torch
+
+    for d in ("a", "b"):
+        out = _bench("--steps", "5", "--warmup", "3", "--num-envs", "64", "--dump-outputs", str(tmp_path / d))
+        assert out["steps"] == 5 and out["timing"]["batches"] == 1 and out["roofline"] is None and "sweep" not in out
+        assert out["ms_per_step"] * 5 == pytest.approx(out["timing"]["batch_ms_median"])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and {"obs.npy", "reward.npy", "terminated.npy", "truncated.npy"} <= set(names)
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+
+    bench = _bench_module()
+    env = bench.make_env(64)
+    env.seed(1234)
+    env.reset()
+    g = torch.Generator().manual_seed(1234)
+    acts = [torch.randn(64, 12, generator=g) for _ in range(8)]
+    for i in list(range(bench.PRIMING_STEPS)) + list(range(3)) + list(range(5)):
+        last = env.step(acts[i % 8])
+    for k, v in {"obs": last[0], "reward": last[1], "terminated": last[2], "truncated": last[3]}.items():
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), v.float().numpy()), k
+
+
+def test_dump_outputs_samples_rows_above_the_size_cap(tmp_path, monkeypatch):
+    """Above DUMP_BYTES_MAX every per-env array keeps the same seeded rows (env_index.npy); episode log entries are float64 scalars."""
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", (1 << 20) + 40000)
+    n = 8000   # 236 B per env row: 1.9 MB in all
+    obs = torch.arange(n * 48, dtype=torch.float32).reshape(n, 48)
+    step = (obs, obs[:, 0] * 2, obs[:, 0] > 500, torch.zeros(n, dtype=torch.bool),
+            {"observations": {"policy": obs, "critic": obs[:, :4].double()}})
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), step, {"Episode_Reward/track": torch.tensor(0.25), "length": 3.0})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["env_index.npy", "episode_Episode_Reward_track.npy", "episode_length.npy", "obs.npy", "obs_critic.npy", "reward.npy",
+                     "terminated.npy", "truncated.npy"]
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "b" / "env_index.npy"))
+    rows = idx.astype(np.int64)
+    assert 0 < len(rows) < n and np.all(np.diff(rows) > 0)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BYTES_MAX
+    assert np.array_equal(np.load(tmp_path / "a" / "obs.npy"), obs.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "reward.npy"), obs.numpy()[rows, 0] * 2)
+    assert np.array_equal(np.load(tmp_path / "a" / "terminated.npy"), (obs.numpy()[rows, 0] > 500).astype(np.float32))
+    assert np.load(tmp_path / "a" / "obs_critic.npy").dtype == np.float64
+    assert float(np.load(tmp_path / "a" / "episode_Episode_Reward_track.npy")) == 0.25
+
+
 def test_spawn_ranks_propagates_failure_and_environment(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "genesis-forge_amd"))
     from genesis_forge_amd.launch import spawn_ranks
@@ -111,11 +178,7 @@ def test_rank_pinning_plan_is_numa_local_when_the_box_says_so():
     """bench.py:pin_plan — on an 8-GPU node (two sockets, SMT siblings numbered behind the physical cores) a contiguous split would give
     ranks 2 and 3 the other socket's cores and make ranks 0 and 4 SMT siblings; with the GPUs' NUMA nodes from sysfs the ranks of a socket
     split that socket's cores.  Without the information (or with an unusable node) it is the contiguous split."""
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location("_bench_mod", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
+    bench = _bench_module()
     avail = list(range(256))
     node_cpus = {0: list(range(0, 64)) + list(range(128, 192)), 1: list(range(64, 128)) + list(range(192, 256))}
     gpu_nodes = [0, 0, 0, 0, 1, 1, 1, 1]

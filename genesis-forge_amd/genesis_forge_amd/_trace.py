@@ -35,6 +35,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from functools import partial
 from typing import Callable, Optional
 
 from . import _native as nat
@@ -116,6 +117,14 @@ class StepTrace:
                 plain.append(c)
         calls = plain
         self.py_marks = marks
+        #: (reward, terminated, truncated) of the step: the managers' buffers — or, for a user RewardManager / TerminationManager class
+        #: whose step() is a python phase, the env's copies of what that step() returned (ManagedEnvironment._phase_step): the recorded
+        #: reset and rollout launches read them, the step returns them
+        tm, rm = env.managers["termination"], env.managers["reward"]
+        staged = {f.args[0] for _at, f in marks if getattr(f, "func", None) == env._phase_step}
+        po = env._phase_out
+        self.outputs = (po["reward"] if rm in staged else rm._reward_buf if rm is not None else env._reward_buf,
+                        *((po["terminated"], po["truncated"]) if tm in staged else (tm._terminated_buf, tm._truncated_buf)))
         self._term_call = next((c for c in calls if c[0] == "termination_step"), None)   # (its masks: inputs of a fused tail observation launch)
         self._tail_refs = None
         self.patches: list[Callable] = []   # Python-side per-step work that has Python semantics (live ranges, log registration)
@@ -663,7 +672,7 @@ class StepTrace:
                     if rm.enabled and rm.logging_enabled:
                         rm._register_log()
                 self.patches.append(patch)
-            self.afters.append((self._cur_op, env._after_masked_reset_traced))
+            self.afters.append((self._cur_op, partial(env._after_masked_reset_traced, *self.outputs[1:])))
         elif fn == "observe":
             self.native.extend(owner._trace_native(args))
             fresh = owner._trace_fresh_patch(args)
@@ -754,7 +763,7 @@ class StepTrace:
             env._tick += 1  # scene advanced
         for _, f in self.afters[done:]:
             f()
-        tm, rm = env.managers["termination"], env.managers["reward"]
+        rew, terminated, truncated = self.outputs
         obs_tail = None
         if self.tail_python:
             # reset (the user's override, by index list, behind the same nonzero() sync the reference pays) and observations,
@@ -768,13 +777,12 @@ class StepTrace:
                 rec.tail_python = True
                 self.backend.tracer = rec
             try:
-                env._reset_done(tm._terminated_buf, tm._truncated_buf)
+                env._reset_done(terminated, truncated)
                 obs_tail = env.get_observations()
                 ro = getattr(env, "_rollout", None)
                 if ro is not None:
                     pol = next((m for m in env.managers["observation"] if m.name == ro.obs_name), None)
-                    ro.write(pol._last_out if pol is not None else obs_tail, rm._reward_buf if rm is not None else env._reward_buf,
-                             tm._terminated_buf, tm._truncated_buf)
+                    ro.write(pol._last_out if pol is not None else obs_tail, rew, terminated, truncated)
             finally:
                 env.stats.ptr_override, env._in_step, env._tail_trace = None, False, None
                 if rec is not None:
@@ -789,7 +797,7 @@ class StepTrace:
             obs = env._step_obs   # what the env's own get_observations() returned (a python phase behind the last launch)
         elif self._env_obs_tail:
             obs = obs_tail
-        return obs, rm._reward_buf if rm is not None else env._reward_buf, tm._terminated_buf, tm._truncated_buf, extras
+        return obs, rew, terminated, truncated, extras
 
 
 def traceable(env, tail_python: bool = False) -> bool:
@@ -818,9 +826,11 @@ def traceable(env, tail_python: bool = False) -> bool:
     # Overrides that produce the step's native outputs themselves (action, termination, reward, observation managers) are not
     # something a recording can stand in for.
     between = set(map(id, env.managers["entity"] + env.managers["contact"] + env.managers["command"]))
-    # Round 4: the step() of a user TerminationManager / RewardManager class as well — `super().step()` + torch on the manager's buffers
-    # is user code at the place of its phase; the launches it makes itself are its own (pointed at the step's statistics slot by the
-    # replay) and the native phases behind it read the manager's buffers as they find them.  (A reset() override of these two stays out:
+    # Round 4: the step() of a user TerminationManager / RewardManager class as well — `super().step()` + torch is user code at the place
+    # of its phase; the launches it makes itself are its own (pointed at the step's statistics slot by the replay).  Every such override
+    # stays recorded: in place on the manager's buffers or returning new tensors (`super().step() * 2`, `t | extra, tr`), on every step
+    # or only on some.  What it RETURNS is what the step resets from, writes into the rollout rows and returns: the recorded launches
+    # read the env's copies of it (ManagedEnvironment._phase_step, StepTrace.outputs).  (A reset() override of these two stays out:
     # their reset is a section of the masked reset.)
     phase_step = set(map(id, [m for m in (tm, rm) if m is not None]))
     # … and the get_observations() / _perform_observation() of a user ObservationManager class: user code at the manager's place

@@ -76,6 +76,8 @@ class ManagedEnvironment(GenesisEnv):
         self._terminated_buf = torch.zeros((self.num_envs,), device=gs.device, dtype=gs.tc_bool)
         self._truncated_buf = torch.zeros((self.num_envs,), device=gs.device, dtype=gs.tc_bool)
         self._reset_args = nat.GfResetArgs()
+        #: a recorded step's copies of what the step() of a user RewardManager / TerminationManager class returned (_phase_step)
+        self._phase_out: dict = {}
         self._last_images = None  # descriptor images of the previous recorded ordinary step (Genesis-shaped scene)
         self._untraceable: Optional[str] = None   # why the last attempt to record the step was refused
         self._no_trace_epoch = -1
@@ -88,6 +90,7 @@ class ManagedEnvironment(GenesisEnv):
         #: built-in one matches (None: by size, see _programs.mode_for; GF_JIT overrides)
         self.jit_programs: Optional[str] = None
         self._done_ids = None     # the index list of this step's done envs while a user reset() override holds it (reset() recognises it)
+        self._done_masks = None   # … and the step's (terminated, truncated) it was made from: what the masked reset of those envs reads
         self._tail_trace = None   # the recorded step whose Python tail is running (its reset / observation segments replay natively)
         #: record the step and replay it through gf_run_ops when possible (see _trace.py); GF_NO_TRACE=1 disables
         self.trace_enabled = os.environ.get("GF_NO_TRACE", "0") != "1"
@@ -246,17 +249,16 @@ class ManagedEnvironment(GenesisEnv):
         if rm is not None:
             rm._note_snapshot(snap)
 
-    def _after_masked_reset_traced(self) -> None:
-        tm = self.managers["termination"]
+    def _after_masked_reset_traced(self, terminated: torch.Tensor, truncated: torch.Tensor) -> None:
         for em in self.managers["entity"]:
-            em._after_fused_reset(tm._terminated_buf, tm._truncated_buf)
+            em._after_fused_reset(terminated, truncated)
         self.invalidate_views()
         ad = self._adapter
         if ad is not None:   # Genesis-shaped scene: the simulator learns the reset rows through its envs_idx setters
             if self._done_ids is not None:
                 ad.push(self._done_ids)   # (a reset() override already paid for the index list)
             else:
-                ad.push_done(tm._terminated_buf, tm._truncated_buf)
+                ad.push_done(terminated, truncated)
 
     def _step_ordinary(self, actions: torch.Tensor):
         self._begin_step()
@@ -328,11 +330,57 @@ class ManagedEnvironment(GenesisEnv):
         """``m.step()`` — for a user-defined manager class while the step is being recorded: as user code between native phases
         (the recording keeps its place and calls it again there; launches it makes itself belong to it, not to the recording)."""
         rec = self.backend.tracer
-        if rec is None or _most_derived_is_ours(m, "step"):
+        if rec is None:
+            out = m.step()
+            if (m is self.managers["termination"] or m is self.managers["reward"]) and not _most_derived_is_ours(m, "step"):
+                self._check_step_out(m, out)
+            return out
+        if _most_derived_is_ours(m, "step"):
             return m.step()
         from .managers._program import call_untraced
-        rec.python(m.step)
-        return call_untraced(self, m.step)
+        fn = partial(self._phase_step, m) if m is self.managers["termination"] or m is self.managers["reward"] else m.step
+        rec.python(fn)
+        return call_untraced(self, fn)
+
+    def _check_step_out(self, m, out) -> None:
+        """What the step() of a user RewardManager / TerminationManager class returns is read by address — by the masked reset, the
+        rollout rows, a recorded step's copies of it (_phase_step) — so it must be what the manager's own buffers are: one contiguous
+        row of ``num_envs`` on the env's device, float32 rewards, bool masks.  Anything else is an error, not a silent cast."""
+        if m is self.managers["termination"]:
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise TypeError(f"{type(m).__name__}.step() must return (terminated, truncated), got {type(out).__name__}")
+            pairs = (("terminated", out[0], m._terminated_buf), ("truncated", out[1], m._truncated_buf))
+        else:
+            pairs = (("reward", out, m._reward_buf),)
+        for name, t, like in pairs:
+            if not (isinstance(t, torch.Tensor) and t.dtype == like.dtype and t.shape == like.shape and t.device == like.device and t.is_contiguous()):
+                got = f"{t.dtype} tensor of shape {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else " (strided)") \
+                    if isinstance(t, torch.Tensor) else type(t).__name__
+                raise TypeError(f"{type(m).__name__}.step() returned a {name} {got}; the step takes a contiguous {like.dtype} tensor "
+                                f"of shape {tuple(like.shape)} on {like.device}, like the manager's own buffer")
+
+    def _phase_step(self, m):
+        """``m.step()`` of a user RewardManager / TerminationManager class in a recorded step.  What it RETURNS is what the step resets
+        from, writes into the rollout rows and returns (managed_env.py:303-315 of the reference): the manager's own buffers, or new
+        tensors — ``super().step() * 2``, ``t | extra`` — on every step or only on some.  The recorded launches read fixed addresses, so
+        the returned values are copied into buffers of the env's own (``_phase_out``) that the recording is made with and the replay
+        returns (StepTrace.outputs); the manager's buffers keep what the manager left in them, as in the ordinary step.  So a recorded
+        step returns the same reward / mask tensors on every step and the next step overwrites them — as the library managers' buffers
+        are — where the ordinary step hands back whatever the user's step() made: keep a copy (``clone()``) of what must outlive a step."""
+        out = m.step()
+        self._check_step_out(m, out)
+        po = self._phase_out
+        if m is self.managers["termination"]:
+            if "terminated" not in po:
+                po["terminated"] = torch.zeros(self.num_envs, device=gs.device, dtype=torch.bool)
+                po["truncated"] = torch.zeros(self.num_envs, device=gs.device, dtype=torch.bool)
+            po["terminated"].copy_(out[0])
+            po["truncated"].copy_(out[1])
+            return po["terminated"], po["truncated"]
+        if "reward" not in po:
+            po["reward"] = torch.zeros(self.num_envs, device=gs.device, dtype=gs.tc_float)
+        po["reward"].copy_(out)
+        return po["reward"]
 
     def _indexed_reset(self, indexed: list, mask: torch.Tensor, mask2: Optional[torch.Tensor]) -> None:
         """``reset(ids)`` of the managers that need an index list (user-defined classes, Python on_reset entries), for the done
@@ -366,10 +414,11 @@ class ManagedEnvironment(GenesisEnv):
             ids = self.done_ids(terminated, truncated, own=True)
             if ids.numel() > 0:
                 self._done_ids = ids   # (reset() recognises THIS index list: the done envs, i.e. the termination masks)
+                self._done_masks = (terminated, truncated)   # (the step's masks: what a user TerminationManager's step() returned)
                 try:
                     self.reset(ids)
                 finally:
-                    self._done_ids = None
+                    self._done_ids = self._done_masks = None
             return
         self._reset_with_mask(terminated, truncated, ids=None)
 
@@ -460,12 +509,11 @@ class ManagedEnvironment(GenesisEnv):
             # so the launches are the mask path's (persistent descriptors: a recorded step replays them with one native call)
             tr = self._tail_trace
             if tr is None or not tr.run_tail_segment("reset"):
-                tm = self.managers["termination"]
                 rec = self.backend.tracer
                 if rec is not None:
                     rec.part = "reset"
                 try:
-                    self._reset_with_mask(tm._terminated_buf, tm._truncated_buf, ids=env_ids)
+                    self._reset_with_mask(*self._done_masks, ids=env_ids)
                 finally:
                     if rec is not None:
                         rec.part = None

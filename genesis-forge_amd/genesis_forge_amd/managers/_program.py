@@ -304,12 +304,18 @@ def same_structure(old, new) -> bool:
 
 
 def refresh_terms(old, new) -> None:
-    """``new``'s numbers into ``old``'s descriptor (same_structure holds): the term table, entry by entry."""
+    """``new``'s numbers into ``old``'s descriptor (same_structure holds): the term table, entry by entry — and ``new``'s Python side.
+    Its Python-level terms (an opaque fn, a class-style fn, a native term of a second entity) are closures over the params they were
+    compiled with: a replaced ``params`` dict reaches them only through the new closures.  A recorded step picks them up by itself
+    (_program_trace_pre reads ``prog.slots.exts`` when it runs)."""
     for k in range(old.n):
         a, b = old.args.terms[k], new.args.terms[k]
         a.w = b.w
         for j in range(4):
             a.p[j] = b.p[j]
+    old.slots.exts = new.slots.exts
+    if hasattr(new, "after"):
+        old.after = new.after
 
 
 def _program_trace_pre(prog, ext_dtype):

@@ -21,7 +21,10 @@ from helpers import FLOAT_TOL
 # (termination done by a launch of its own; the body-frame items in a manager that observes behind the fused launch)
 # 57 / 132 (round 3): a late observation manager's launch in front of a manager that is part of the fused launch, in call order — the
 # per-piece patch tables applied the fused manager's output rotation / stream id one piece too late
-SEEDS = list(range(*map(int, os.environ["GF_FUZZ_SEEDS"].split(":")))) if os.environ.get("GF_FUZZ_SEEDS") else list(range(28)) + [57, 123, 132, 140]
+# 288 / 300 (round 5): a user RewardManager (288) / TerminationManager (300) class whose step() returns a NEW tensor — the recorded step
+# reset from and returned the manager's buffers instead.  333: an opaque reward term's params replaced and put back (A -> B -> A) — the
+# compiled table kept the closure over the old params
+SEEDS = list(range(*map(int, os.environ["GF_FUZZ_SEEDS"].split(":")))) if os.environ.get("GF_FUZZ_SEEDS") else list(range(28)) + [57, 123, 132, 140, 288, 300, 333]
 STEPS = 48
 
 
@@ -61,6 +64,7 @@ def make_fuzz_env(seed: int):
                                                            contact_prob=uni(0.05, 0.3), contact_force=uni(10.0, 60.0))
             self.terrain = self.scene.add_entity(morphs.Plane())
             self.robot = self.scene.add_entity(morphs.URDF(file="urdf/go2/urdf/go2.urdf", pos=[0.0, 0.0, 0.4], quat=[1.0, 0.0, 0.0, 0.0]))
+            self.seen_params = {}   # (the params an opaque term was last called with: _seen)
 
         def config(self):
             em = self.robot_manager = EntityManager(self, entity_attr="robot", on_reset={
@@ -160,7 +164,8 @@ def make_fuzz_env(seed: int):
             self.has_user_term = pick(0.3)
             self.has_user_obs = False   # a Python-level OBSERVATION item (sees the post-reset state: nothing behind it can be fused)
             if self.has_user_term:  # a user-level Python term: evaluated in torch on both sides, in the middle of the recorded step
-                rcfg["user_height"] = {"weight": 0.3, "fn": lambda env: torch.tanh(env.robot.get_pos()[:, 2])}
+                # (`scale`: what a params replacement edits, _replacements; 1.0 leaves every bit of the term as it was)
+                rcfg["user_height"] = {"weight": 0.3, "fn": lambda env, scale=1.0: _seen(env, "user_height", scale, torch.tanh(env.robot.get_pos()[:, 2]) * scale)}
             if self.user_manager:
                 rcfg["in_phase"] = {"weight": 0.2, "fn": lambda env: torch.cos(6.2831853 * self.clock.phase)}
             # user-defined RewardManager / TerminationManager CLASSES (their own step() around the library's, torch on the manager's
@@ -168,16 +173,25 @@ def make_fuzz_env(seed: int):
             rnd_cls = random.Random(77000 + seed)
             self.user_reward_cls, self.user_term_cls = rnd_cls.random() < 0.2, rnd_cls.random() < 0.2
             floor, grace = -round(rnd_cls.uniform(0.05, 0.5), 3), rnd_cls.choice([1, 2, 4])
+            # round 5: their OUT-OF-PLACE variant — step() returns new tensors, which the env resets from, stores and returns while the
+            # managers' buffers keep what super().step() left.  A stream of its own, chosen so that no seed committed before it draws it
+            # (0-27, 57, 123, 132, 140 build what they built; of the seeds below 141, 29 52 66 76 77 80 81 87 88 102 130 would).
+            oop = (self.user_reward_cls or self.user_term_cls) and random.Random(690000 + seed).random() < 0.25
+            self.out_of_place = oop
 
             class CappedRewards(RewardManager):
                 def step(s):
                     r = super().step()
+                    if oop:
+                        return torch.clamp(r, min=floor) * 2
                     r.clamp_(min=floor)
                     return r
 
             class GracefulTerminations(TerminationManager):
                 def step(s):
                     te, tr = super().step()
+                    if oop:   # (… and a few terminations of its own, so that the returned mask surely differs from the manager's)
+                        return (te & (s.env.episode_length > grace)) | (s.env.episode_length % 29 == 11), tr
                     te &= s.env.episode_length > grace
                     return te, tr
 
@@ -219,7 +233,7 @@ def make_fuzz_env(seed: int):
                                             "params": {"contact_manager": body, "threshold": uni(20.0, 50.0), "grace_steps": rnd.choice([3, 10])}}
             if pick(0.15):  # a user-level termination term (evaluated in front of the termination op)
                 self.has_user_term = True
-                tcfg["user_far"] = {"fn": lambda env: env.robot.get_pos()[:, :2].abs().sum(dim=1) > 0.35}
+                tcfg["user_far"] = {"fn": lambda env, reach=0.35: _seen(env, "user_far", reach, env.robot.get_pos()[:, :2].abs().sum(dim=1) > reach)}
             self.termination_manager = with_reset(GracefulTerminations if self.user_term_cls else TerminationManager, "termination" in self.user_reset_cls)(
                 self, logging_enabled=True, term_cfg=tcfg)
 
@@ -326,6 +340,36 @@ def _mutations(env, seed):
     return out
 
 
+def _seen(env, name, value, out):
+    """An opaque term's record of the param it was last called with (checked against its cfg after every step, _run)."""
+    env.seen_params[name] = value
+    return out
+
+
+def _replacements(env, seed):
+    """Round 5: a term's params REPLACED (``cfg[name].params = {...}``, a curriculum's other idiom), from a stream of its own chosen so
+    that no seed committed before it draws it (of the seeds below 141, 31 34 53 55 72 82 87 92 94 130 would): [(step, callable)].  An
+    opaque term is the target where there is one — its closure holds the params — and half of the draws put the old params back later
+    (A -> B -> A)."""
+    r = random.Random(660000 + seed)
+    if r.random() >= 0.08:
+        return []
+    rm, tm = env.reward_manager.cfg, env.termination_manager.term_cfg
+    opaque = [(c, n, k) for c, n, k in ((rm, "user_height", "scale"), (tm, "user_far", "reach")) if n in c]
+    cands = opaque or [(c, n, k) for c in (rm, tm) for n in sorted(c) for k, v in c[n].params.items() if isinstance(v, float)]
+    if not cands:
+        return []
+    cfg, name, key = r.choice(cands)
+    old = dict(cfg[name].params)
+    f = round(r.uniform(0.5, 1.5), 3)
+    new = dict(old, **{key: f * old.get(key, 1.0 if key == "scale" else 0.35)})
+    at = r.randint(3, 24)
+    out = [(at, lambda: setattr(cfg[name], "params", dict(new)))]
+    if r.random() < 0.5:
+        out.append((at + r.randint(2, 10), lambda: setattr(cfg[name], "params", dict(old))))
+    return out
+
+
 def _run(seed, dev, steps=STEPS):
     env = make_fuzz_env(seed)
     env.build()
@@ -335,13 +379,16 @@ def _run(seed, dev, steps=STEPS):
     g = torch.Generator().manual_seed(seed)
     f = lambda t: t.detach().cpu().clone()
     out = [({"obs": f(obs)}, {})]
-    edits = _mutations(env, seed)
+    edits = _mutations(env, seed) + _replacements(env, seed)
     for t in range(steps):
         for at, edit in edits:
             if at == t:
                 edit()
         act = torch.randn(n, 12, generator=g)
         obs, rew, term, trunc, extras = env.step(act.to(dev))
+        for name, cfg, key, dflt in (("user_height", env.reward_manager.cfg, "scale", 1.0), ("user_far", env.termination_manager.term_cfg, "reach", 0.35)):
+            if name in cfg and getattr(cfg[name], "weight", 1.0) != 0:
+                assert env.seen_params[name] == cfg[name].params.get(key, dflt), f"step {t}: '{name}' called with stale params"
         state = {"obs": obs, "reward": rew, "terminated": term, "truncated": trunc, "command": env.velocity_command.command,
                  "episode_length": env.episode_length, "max_episode_length": env.max_episode_length,
                  "episode_sums": env.reward_manager._episode_sums, "episode_seconds": env.reward_manager._episode_seconds,

@@ -10,6 +10,9 @@
 //   random walk driven by Philox draws, contacts are sampled per slot.  What matters is that the
 //   update is deterministic and integer-RNG driven with f32 ops in a fixed order, so this kernel, the
 //   C oracle and the numpy model that drives the reference produce the same bits.
+#include <stdlib.h>
+#include <string.h>
+
 #include "gf_launch.h"
 
 namespace gf {
@@ -40,52 +43,23 @@ struct SynthBase {
     float p[3], q[4], v[3], w[3];
 };
 
-template <int DV>
-__device__ __forceinline__ void synth_state_body(const GfSynthSceneArgs& a, const int64_t n, SynthBase& out) {
-    const int D = a.num_dofs;
+// The two Philox blocks of an env's tick: columns 0..5 (block 0: x,y,z,w, block 1: x,y) are its six base-motion draws
+struct SynthDraws {
+    U4 b0, b1;
+};
+__device__ __forceinline__ SynthDraws synth_draws(const GfSynthSceneArgs& a, const uint32_t genv) {
+    return SynthDraws{philox4x32_10(genv, 0u, (uint32_t)a.tick, (uint32_t)(a.tick >> 32), (uint32_t)a.seed, (uint32_t)(a.seed >> 32)),
+                      philox4x32_10(genv, 1u, (uint32_t)a.tick, (uint32_t)(a.tick >> 32), (uint32_t)a.seed, (uint32_t)(a.seed >> 32))};
+}
+
+// The base part of one env's tick: damped random walk of the velocities, position and quaternion integration.  Every kernel
+// that ticks the base goes through this one copy of the statements, so they all give the oracle's bits.
+__device__ __forceinline__ void synth_base_math(const GfSynthSceneArgs& a, const float4 q4, const V3 w0, const V3 v0, const V3 p0,
+                                                const SynthDraws& r, SynthBase& out) {
     const float dt = a.dt;
-    const uint32_t genv = (uint32_t)n + a.env_offset;
-    // all loads first: joint rows as float4 (DV = D/4 when the rows are 16-byte tiles), base state, then one wait
-    float4 tg[DV > 0 ? DV : 1], dp[DV > 0 ? DV : 1];
-    if (DV > 0) {
-        const float4* t4 = reinterpret_cast<const float4*>(a.targets + n * D);
-        const float4* p4 = reinterpret_cast<const float4*>(a.dof_pos + n * D);
-#pragma unroll
-        for (int c = 0; c < DV; ++c) { tg[c] = t4[c]; dp[c] = p4[c]; }
-    }
-    const float4 q4 = load_quat(a.quat, n);
-    const V3 w0 = load3(a.ang_vel, n), v0 = load3(a.lin_vel, n), p0 = load3(a.pos, n);
-    // six base-motion draws = Philox columns 0..5 = block 0 (x,y,z,w) + block 1 (x,y)
-    const U4 b0 = philox4x32_10(genv, 0u, (uint32_t)a.tick, (uint32_t)(a.tick >> 32), (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-    const U4 b1 = philox4x32_10(genv, 1u, (uint32_t)a.tick, (uint32_t)(a.tick >> 32), (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+    const U4 b0 = r.b0, b1 = r.b1;
     const float s[6] = {u24_to_unit(b0.x) * 2.0f - 1.0f, u24_to_unit(b0.y) * 2.0f - 1.0f, u24_to_unit(b0.z) * 2.0f - 1.0f,
                         u24_to_unit(b0.w) * 2.0f - 1.0f, u24_to_unit(b1.x) * 2.0f - 1.0f, u24_to_unit(b1.y) * 2.0f - 1.0f};
-    if (DV > 0) {
-        float4* v4 = reinterpret_cast<float4*>(a.dof_vel + n * D);
-        float4* p4 = reinterpret_cast<float4*>(a.dof_pos + n * D);
-#pragma unroll
-        for (int c = 0; c < DV; ++c) {
-            float4 v, p;
-            v.x = (tg[c].x - dp[c].x) * a.joint_rate; p.x = dp[c].x + v.x * dt;
-            v.y = (tg[c].y - dp[c].y) * a.joint_rate; p.y = dp[c].y + v.y * dt;
-            v.z = (tg[c].z - dp[c].z) * a.joint_rate; p.z = dp[c].z + v.z * dt;
-            v.w = (tg[c].w - dp[c].w) * a.joint_rate; p.w = dp[c].w + v.w * dt;
-            v4[c] = v;
-            p4[c] = p;
-        }
-    } else {
-        for (int d = 0; d < D; ++d) {
-            const float cur = a.dof_pos[n * D + d];
-            const float err = a.targets[n * D + d] - cur;
-            const float v = err * a.joint_rate;
-            a.dof_vel[n * D + d] = v;
-            a.dof_pos[n * D + d] = cur + v * dt;
-        }
-    }
-    float* wp = a.ang_vel + 3 * n;
-    float* vp = a.lin_vel + 3 * n;
-    float* pp = a.pos + 3 * n;
-    float* qp = a.quat + 4 * n;
     float w[3] = {w0.x, w0.y, w0.z}, v[3] = {v0.x, v0.y, v0.z}, p[3] = {p0.x, p0.y, p0.z};
 #pragma unroll
     for (int j = 0; j < 3; ++j) w[j] = w[j] * 0.9f + s[j] * a.ang_noise;
@@ -105,9 +79,170 @@ __device__ __forceinline__ void synth_state_body(const GfSynthSceneArgs& a, cons
 #pragma unroll
     for (int j = 0; j < 4; ++j) nq[j] = nq[j] / nrm;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) { wp[j] = w[j]; vp[j] = v[j]; pp[j] = p[j]; out.w[j] = w[j]; out.v[j] = v[j]; out.p[j] = p[j]; }
+    for (int j = 0; j < 3; ++j) { out.w[j] = w[j]; out.v[j] = v[j]; out.p[j] = p[j]; }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { qp[j] = nq[j]; out.q[j] = nq[j]; }
+    for (int j = 0; j < 4; ++j) out.q[j] = nq[j];
+}
+
+// One joint of the first-order tracking lag: v = (target - pos) * rate, pos += v * dt
+__device__ __forceinline__ void synth_joint(float t, float& p, float& v, float rate, float dt) {
+    v = (t - p) * rate;
+    p = p + v * dt;
+}
+
+// The legacy lane-per-env tick (GF_SCENE_LEGACY=1): every load of the env first, then the joints, then the base.
+template <int DV>
+__device__ __forceinline__ void synth_state_body(const GfSynthSceneArgs& a, const int64_t n, SynthBase& out) {
+    const int D = a.num_dofs;
+    const float dt = a.dt;
+    const uint32_t genv = (uint32_t)n + a.env_offset;
+    // all loads first: joint rows as float4 (DV = D/4 when the rows are 16-byte tiles), base state, then one wait
+    float4 tg[DV > 0 ? DV : 1], dp[DV > 0 ? DV : 1];
+    if (DV > 0) {
+        const float4* t4 = reinterpret_cast<const float4*>(a.targets + n * D);
+        const float4* p4 = reinterpret_cast<const float4*>(a.dof_pos + n * D);
+#pragma unroll
+        for (int c = 0; c < DV; ++c) { tg[c] = t4[c]; dp[c] = p4[c]; }
+    }
+    const float4 q4 = load_quat(a.quat, n);
+    const V3 w0 = load3(a.ang_vel, n), v0 = load3(a.lin_vel, n), p0 = load3(a.pos, n);
+    const SynthDraws r = synth_draws(a, genv);
+    if (DV > 0) {
+        float4* v4 = reinterpret_cast<float4*>(a.dof_vel + n * D);
+        float4* p4 = reinterpret_cast<float4*>(a.dof_pos + n * D);
+#pragma unroll
+        for (int c = 0; c < DV; ++c) {
+            float4 v, p = dp[c];
+            synth_joint(tg[c].x, p.x, v.x, a.joint_rate, dt);
+            synth_joint(tg[c].y, p.y, v.y, a.joint_rate, dt);
+            synth_joint(tg[c].z, p.z, v.z, a.joint_rate, dt);
+            synth_joint(tg[c].w, p.w, v.w, a.joint_rate, dt);
+            v4[c] = v;
+            p4[c] = p;
+        }
+    } else {
+        for (int d = 0; d < D; ++d) {
+            float p = a.dof_pos[n * D + d], v;
+            synth_joint(a.targets[n * D + d], p, v, a.joint_rate, dt);
+            a.dof_vel[n * D + d] = v;
+            a.dof_pos[n * D + d] = p;
+        }
+    }
+    synth_base_math(a, q4, w0, v0, p0, r, out);
+    float* wp = a.ang_vel + 3 * n;
+    float* vp = a.lin_vel + 3 * n;
+    float* pp = a.pos + 3 * n;
+    float* qp = a.quat + 4 * n;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { wp[j] = out.w[j]; vp[j] = out.v[j]; pp[j] = out.p[j]; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) qp[j] = out.q[j];
+}
+
+// ---------------------------------------------------------------------------------------------
+// The tick of a tile of TE envs [n0, n0 + rows) by a 256-lane workgroup, split by wave:
+//  * waves 1-3 stream the tile's joint rows.  targets / dof_pos / dof_vel of the tile are one contiguous block of rows·D floats
+//    each, so lane t takes float4 t, t + 192, … (DV > 0) or float t, t + 192, … (DV = 0): every access is a whole 1 KiB (float4)
+//    per wave instruction, where the lane-per-env tick read 48 B-strided records and kept the stream waiting behind the Philox work;
+//  * wave 0 ticks the base with lane = env.  The tile's pos / lin_vel / ang_vel are contiguous blocks of rows·3 floats: they are
+//    read and written as consecutive floats by consecutive lanes and transposed through LDS, the quaternions are one float4 per
+//    lane already.  The Philox blocks are computed while those loads are in flight.
+// The statements per element are the lane-per-env tick's, so the outputs are bit-identical to it and to the oracle.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSynthTileBlock = 256;
+constexpr int kSynthDofLanes = kSynthTileBlock - GF_WAVE;
+
+// orders one wave's LDS accesses across lanes: LDS serves a wave's instructions in order, so it is enough that the compiler moves
+// no LDS access across this point
+__device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_wave_barrier(); }
+
+template <int DV, int TE>
+__device__ __forceinline__ void synth_dof_tile(const GfSynthSceneArgs& a, const int64_t n0, const int rows, const int t) {
+    const float dt = a.dt, rate = a.joint_rate;
+    if (DV > 0) {
+        constexpr int kIt = DV > 0 ? (TE * DV + kSynthDofLanes - 1) / kSynthDofLanes : 1;
+        const int cnt = rows * DV;
+        const float4* t4 = reinterpret_cast<const float4*>(a.targets) + n0 * DV;
+        float4* p4 = reinterpret_cast<float4*>(a.dof_pos) + n0 * DV;
+        float4* v4 = reinterpret_cast<float4*>(a.dof_vel) + n0 * DV;
+        float4 tg[kIt], dp[kIt];
+#pragma unroll
+        for (int k = 0; k < kIt; ++k) {
+            const int i = t + k * kSynthDofLanes;
+            if (i < cnt) { tg[k] = t4[i]; dp[k] = p4[i]; }
+        }
+#pragma unroll
+        for (int k = 0; k < kIt; ++k) {
+            const int i = t + k * kSynthDofLanes;
+            if (i < cnt) {
+                float4 v, p = dp[k];
+                synth_joint(tg[k].x, p.x, v.x, rate, dt);
+                synth_joint(tg[k].y, p.y, v.y, rate, dt);
+                synth_joint(tg[k].z, p.z, v.z, rate, dt);
+                synth_joint(tg[k].w, p.w, v.w, rate, dt);
+                v4[i] = v;
+                p4[i] = p;
+            }
+        }
+    } else {
+        const int64_t base = n0 * a.num_dofs;
+        const int cnt = rows * a.num_dofs;
+        for (int i = t; i < cnt; i += kSynthDofLanes) {
+            float p = a.dof_pos[base + i], v;
+            synth_joint(a.targets[base + i], p, v, rate, dt);
+            a.dof_vel[base + i] = v;
+            a.dof_pos[base + i] = p;
+        }
+    }
+}
+
+// wave 0: lane = env of the tile; s3 is this wave's LDS, 3 × [TE·3] floats.  Returns the lane's new base state (lane < rows).
+template <int TE>
+__device__ __forceinline__ void synth_base_tile(const GfSynthSceneArgs& a, const int64_t n0, const int rows, const int lane,
+                                                float (&s3)[3][TE * 3], SynthBase& out) {
+    constexpr int kJ = (TE * 3 + GF_WAVE - 1) / GF_WAVE;
+    const int cnt = rows * 3;
+    float* const pos = a.pos + n0 * 3;
+    float* const lin = a.lin_vel + n0 * 3;
+    float* const ang = a.ang_vel + n0 * 3;
+    // float i of each block, i = lane + 64 j; a lane past the tile re-reads its last float (no branch around the loads)
+    float xp[kJ], xv[kJ], xw[kJ];
+#pragma unroll
+    for (int j = 0; j < kJ; ++j) {
+        const int i = lane + j * GF_WAVE < cnt ? lane + j * GF_WAVE : cnt - 1;
+        xp[j] = pos[i]; xv[j] = lin[i]; xw[j] = ang[i];
+    }
+    const bool mine = lane < rows;
+    const float4 q4 = load_quat(a.quat, n0 + (mine ? lane : rows - 1));
+    const SynthDraws r = synth_draws(a, (uint32_t)(n0 + lane) + a.env_offset);
+    // the Philox rounds run while the loads are in flight: the draws are pinned here, ahead of the first LDS write (which waits
+    // for the loads); left alone, the compiler sinks the rounds to their first use behind that wait
+    asm volatile("" ::"v"(r.b0.x), "v"(r.b0.y), "v"(r.b0.z), "v"(r.b0.w), "v"(r.b1.x), "v"(r.b1.y));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < kJ; ++j) {
+        const int i = lane + j * GF_WAVE;
+        if (i < TE * 3) { s3[0][i] = xp[j]; s3[1][i] = xv[j]; s3[2][i] = xw[j]; }
+    }
+    wave_lds_sync();
+    const int e = mine ? lane : 0;
+    const V3 p0{s3[0][3 * e], s3[0][3 * e + 1], s3[0][3 * e + 2]};
+    const V3 v0{s3[1][3 * e], s3[1][3 * e + 1], s3[1][3 * e + 2]};
+    const V3 w0{s3[2][3 * e], s3[2][3 * e + 1], s3[2][3 * e + 2]};
+    synth_base_math(a, q4, w0, v0, p0, r, out);
+    wave_lds_sync();
+    if (mine) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { s3[0][3 * lane + j] = out.p[j]; s3[1][3 * lane + j] = out.v[j]; s3[2][3 * lane + j] = out.w[j]; }
+    }
+    wave_lds_sync();
+#pragma unroll
+    for (int j = 0; j < kJ; ++j) {
+        const int i = lane + j * GF_WAVE;
+        const float yp = s3[0][i < TE * 3 ? i : 0], yv = s3[1][i < TE * 3 ? i : 0], yw = s3[2][i < TE * 3 ? i : 0];
+        if (i < cnt) { pos[i] = yp; lin[i] = yv; ang[i] = yw; }
+    }
+    if (mine) reinterpret_cast<float4*>(a.quat)[n0 + lane] = make_float4(out.q[0], out.q[1], out.q[2], out.q[3]);
 }
 
 template <int DV>
@@ -116,6 +251,25 @@ __global__ __launch_bounds__(kEnvBlock) void synth_scene_kernel(const GfSynthSce
     if (n >= a.num_envs) return;
     SynthBase b;
     synth_state_body<DV>(a, n, b);
+}
+
+// The tick of tile [n0, n0 + rows) by a whole workgroup (see above): wave 0 returns the base state of env n0 + lane in `b`.
+template <int DV, int TE>
+__device__ __forceinline__ void synth_tick_tile(const GfSynthSceneArgs& a, const int64_t n0, const int rows, float (&s3)[3][TE * 3], SynthBase& b) {
+    const int tid = threadIdx.x;
+    if (tid >= GF_WAVE) synth_dof_tile<DV, TE>(a, n0, rows, tid - GF_WAVE);
+    else synth_base_tile<TE>(a, n0, rows, tid, s3, b);
+}
+
+// A scene without per-link outputs or contacts (the benchmark's): workgroup b ticks envs [64b, 64b+64), the tile workgroup b of
+// the action and post-physics kernels owns, so with round-robin workgroup → XCD placement a tile stays on one XCD across the step.
+template <int DV>
+__global__ __launch_bounds__(kSynthTileBlock) void synth_scene_tile_kernel(const GfSynthSceneArgs a) {
+    __shared__ float s3[3][GF_WAVE * 3];
+    const int64_t n0 = (int64_t)blockIdx.x * GF_WAVE;
+    const int rows = (int)((int64_t)a.num_envs - n0 < GF_WAVE ? (int64_t)a.num_envs - n0 : GF_WAVE);
+    SynthBase b;
+    synth_tick_tile<DV, GF_WAVE>(a, n0, rows, s3, b);
 }
 
 // Per-link outputs (orientation, velocity, position of scene link l of env n; flat index gid = n·NL + l) from the base state the
@@ -195,21 +349,23 @@ __device__ __forceinline__ void synth_contact_one(const GfSynthSceneArgs& a, con
 }
 
 // A scene with per-link outputs and / or contacts, as ONE launch (two until round 2: the state tick, then a flat kernel over
-// (env, link) and (env, slot) pairs that read the new base state back): workgroup b owns envs [64b, 64b+64) — wave 0 ticks them
-// (lane = env) and leaves their new base state in LDS, then all four waves write the tile's link rows and contact slots, which are
-// contiguous in memory.  Same statements per element, so the outputs are bit-identical to the two-launch version and the oracle.
+// (env, link) and (env, slot) pairs that read the new base state back): workgroup b owns envs [64b, 64b+64) — the tick of
+// synth_tick_tile (SPLIT; wave 0 alone with the lane-per-env body otherwise, GF_SCENE_LEGACY=1) leaves their new base state in
+// LDS, then all four waves write the tile's link rows and contact slots, which are contiguous in memory.  Same statements per
+// element, so the outputs are bit-identical to the two-launch version and the oracle.
 // TE = envs per workgroup: 64 (the tile of the action / post-physics kernels, same XCD) when that still fills the chip, 16 below
 // ~32 k envs (4 096 envs are 64 tiles of 64 — a quarter of the CUs — but 256 tiles of 16).
-constexpr int kSynthTileBlock = 256;
-template <int DV, int TE>
+template <int DV, int TE, bool SPLIT>
 __global__ __launch_bounds__(kSynthTileBlock) void synth_tile_kernel(const GfSynthSceneArgs a, const int links, const int contacts) {
     __shared__ float s_base[TE][13];   // p(3) q(4) v(3) w(3)
+    __shared__ float s3[3][SPLIT ? TE * 3 : 1];
     const int64_t n0 = (int64_t)blockIdx.x * TE;
     const int rows = (int)((int64_t)a.num_envs - n0 < TE ? (int64_t)a.num_envs - n0 : TE);
     const int tid = threadIdx.x;
+    SynthBase b;
+    if constexpr (SPLIT) synth_tick_tile<DV, TE>(a, n0, rows, s3, b);
+    else if (tid < rows) synth_state_body<DV>(a, n0 + tid, b);
     if (tid < rows) {
-        SynthBase b;
-        synth_state_body<DV>(a, n0 + tid, b);
         float* r = s_base[tid];
         r[0] = b.p[0]; r[1] = b.p[1]; r[2] = b.p[2];
         r[3] = b.q[0]; r[4] = b.q[1]; r[5] = b.q[2]; r[6] = b.q[3];
@@ -264,18 +420,32 @@ extern "C" __attribute__((visibility("default"))) int gf_synth_scene_step(const 
     const unsigned grid = gf::env_grid(a->num_envs);
     const bool links = (a->links_quat_out || a->links_vel_out || a->links_pos_out) && a->num_scene_links > 0;
     const bool contacts = a->num_contacts > 0 && a->contact_force_out;
+    const int dv = !rows16 ? 0 : (a->num_dofs == 12 ? 3 : (a->num_dofs == 28 ? 7 : 0));
+    // GF_SCENE_LEGACY=1: the lane-per-env tick (A/B runs and tests/test_scene_tile.py); read per call so one process can run both
+    const char* legacy_env = getenv("GF_SCENE_LEGACY");
+    const bool legacy = legacy_env && legacy_env[0] && strcmp(legacy_env, "0") != 0;
     if (links || contacts) {   // tick + per-link rows + contact slots of a 64-env tile in one launch
         const dim3 tb(gf::kSynthTileBlock);
         const bool small = a->num_envs < 32768;
         const dim3 tg(small ? gf::env_grid(a->num_envs, 16) : grid);
-        const int dv = !rows16 ? 0 : (a->num_dofs == 12 ? 3 : (a->num_dofs == 28 ? 7 : 0));
-#define GF_SYNTH_TILE(DVV)                                                                                              \
-        if (small) gf::klaunch(gf::synth_tile_kernel<DVV, 16>, tg, tb, 0, s, *a, (int)links, (int)contacts);          \
-        else gf::klaunch(gf::synth_tile_kernel<DVV, 64>, tg, tb, 0, s, *a, (int)links, (int)contacts)
-        if (dv == 3) { GF_SYNTH_TILE(3); } else if (dv == 7) { GF_SYNTH_TILE(7); } else { GF_SYNTH_TILE(0); }
+#define GF_SYNTH_TILE(DVV, SPLIT)                                                                                      \
+        if (small) gf::klaunch(gf::synth_tile_kernel<DVV, 16, SPLIT>, tg, tb, 0, s, *a, (int)links, (int)contacts);   \
+        else gf::klaunch(gf::synth_tile_kernel<DVV, 64, SPLIT>, tg, tb, 0, s, *a, (int)links, (int)contacts)
+        if (legacy) {
+            if (dv == 3) { GF_SYNTH_TILE(3, false); } else if (dv == 7) { GF_SYNTH_TILE(7, false); } else { GF_SYNTH_TILE(0, false); }
+        } else {
+            if (dv == 3) { GF_SYNTH_TILE(3, true); } else if (dv == 7) { GF_SYNTH_TILE(7, true); } else { GF_SYNTH_TILE(0, true); }
+        }
 #undef GF_SYNTH_TILE
-    } else if (rows16 && a->num_dofs == 12) gf::klaunch(gf::synth_scene_kernel<3>, dim3(grid), dim3(gf::kEnvBlock), 0, s, *a);
-    else if (rows16 && a->num_dofs == 28) gf::klaunch(gf::synth_scene_kernel<7>, dim3(grid), dim3(gf::kEnvBlock), 0, s, *a);
-    else gf::klaunch(gf::synth_scene_kernel<0>, dim3(grid), dim3(gf::kEnvBlock), 0, s, *a);
+    } else if (legacy) {
+        if (dv == 3) gf::klaunch(gf::synth_scene_kernel<3>, dim3(grid), dim3(gf::kEnvBlock), 0, s, *a);
+        else if (dv == 7) gf::klaunch(gf::synth_scene_kernel<7>, dim3(grid), dim3(gf::kEnvBlock), 0, s, *a);
+        else gf::klaunch(gf::synth_scene_kernel<0>, dim3(grid), dim3(gf::kEnvBlock), 0, s, *a);
+    } else {   // one 64-env tile per 256-lane workgroup
+        const dim3 tb(gf::kSynthTileBlock);
+        if (dv == 3) gf::klaunch(gf::synth_scene_tile_kernel<3>, dim3(grid), tb, 0, s, *a);
+        else if (dv == 7) gf::klaunch(gf::synth_scene_tile_kernel<7>, dim3(grid), tb, 0, s, *a);
+        else gf::klaunch(gf::synth_scene_tile_kernel<0>, dim3(grid), tb, 0, s, *a);
+    }
     return gf::launch_status();
 }

@@ -69,6 +69,7 @@ GF_EXPORT int gf_sizeof(int which) {
         case 20: return (int)sizeof(GfRolloutPolicyArgs);
         case 21: return (int)sizeof(GfGaeArgs);
         case 22: return (int)sizeof(GfCompactArgs);
+        case 23: return (int)sizeof(GfMinibatchArgs);
         default: return -1;
     }
 }

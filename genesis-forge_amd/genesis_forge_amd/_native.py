@@ -307,6 +307,19 @@ class GfPostRefs(C.Structure):
                 ("num_gait", C.c_int32), ("flags", C.c_int32), ("gait_step", P * GF_POST_MAX_GAIT), ("gait_reset", P * GF_POST_MAX_GAIT),
                 ("gait_flags_next", P * GF_POST_MAX_GAIT), ("rollout", P)]
 
+GF_MINIBATCH_MAX_FIELDS = 12
+GF_SIZEOF_MINIBATCH = 23   # gf_sizeof index of GfMinibatchArgs (not in ABI_STRUCTS: the oracle twin has no minibatch gather)
+
+
+class GfMinibatchField(C.Structure):
+    _fields_ = [("src", P), ("dst", P), ("src_width", C.c_int32), ("dst_width", C.c_int32), ("dst_col", C.c_int32), ("_pad", C.c_int32)]
+
+
+class GfMinibatchArgs(C.Structure):
+    _fields_ = [("num_rows", C.c_int64), ("num_src_rows", C.c_int64), ("indices", P), ("num_fields", C.c_int32), ("_pad", C.c_int32),
+                ("fields", GfMinibatchField * GF_MINIBATCH_MAX_FIELDS)]
+
+
 ABI_STRUCTS = [GfStepStats, GfActionArgs, GfContactArgs, GfTerminationArgs, GfRewardArgs, GfCommandArgs,
                GfResetArgs, GfObservationArgs, GfRotateArgs, GfSynthSceneArgs, GfTerm, GfObsItem, GfTerrainView, GfTerrainHeightArgs, GfGaitArgs, GfContactView, GfCommandView,
                GfPostRefs, GfRolloutArgs, GfHistoryUnrollArgs, GfRolloutPolicyArgs, GfGaeArgs, GfCompactArgs]
@@ -495,6 +508,12 @@ class HipBackend(Backend):
             self.set_option(GF_OPT_POST_VARIANT, int(variant))
         self.lib.gf_profile_end.restype = C.c_int
         self.lib.gf_profile_end.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        # the PPO minibatch gather: not a phase of the step (no PHASE_FUNCS entry, never recorded), checked on its own
+        n = self.lib.gf_sizeof(GF_SIZEOF_MINIBATCH)
+        if n != C.sizeof(GfMinibatchArgs):
+            raise GfError(f"ABI drift: sizeof(GfMinibatchArgs) is {n} in the library, {C.sizeof(GfMinibatchArgs)} in the binding")
+        self.lib.gf_minibatch_gather.restype = C.c_int
+        self.lib.gf_minibatch_gather.argtypes = [C.POINTER(GfMinibatchArgs), C.c_void_p]
 
     def _stream(self) -> int:
         torch = self._torch
@@ -521,6 +540,12 @@ class HipBackend(Backend):
         rc = self._fn[fn](C.byref(args), self._stream())
         if rc != 0:
             self._raise(fn, rc)
+
+    def minibatch_gather(self, args) -> None:
+        """gf_minibatch_gather on the current stream (learner.RolloutStorage.mini_batch_generator)."""
+        rc = self.lib.gf_minibatch_gather(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("minibatch_gather", rc)
 
     def run_ops(self, ops, n: int) -> None:
         failed = C.c_int(-1)

@@ -142,6 +142,7 @@ class StepTrace:
         k += 1
         self._gait_swaps: list = []
         self._late: set = set()
+        self._rows_via_unroll: set = set()   # group-row descriptors a fused step's history gathers store instead (_fuse_post)
         first_post0 = self._post_start(calls)
         # (user code in the middle of the post-physics phases — a user manager's step() between reward and reset — keeps them off
         # the single fused launch: the phases on either side of it run as phase chains, gf_run_ops)
@@ -150,6 +151,7 @@ class StepTrace:
         if self.post_refs is None:
             self._gait_swaps = []
             self._late = set()
+            self._rows_via_unroll = set()
         first_post = self._post_start(calls) if self.post_refs is not None else len(calls)
         self.post_split = self.post_refs is not None and bool(self.post_refs.flags & nat.GF_POST_TERMINATION_DONE)
         mark_i = 0
@@ -614,6 +616,14 @@ class StepTrace:
             if pol is not None and pol._unrolled:
                 tail[j][1].obs_out = None   # … except the observation row of a ring-kept history: its gather writes it (learner.py)
             j += 1
+            # the rows of the storage's other observation-group members (learner._GroupRows): a ring-kept history's gather stores its
+            # row as second destination (no op); any other row is a rollout_write op of its own behind the fused launch
+            while j < len(fns) and fns[j] == "rollout_write" and getattr(tail[j][2], "group_row", False):
+                if tail[j][2].unroll_ok():
+                    self._rows_via_unroll.add(C.addressof(tail[j][1]))
+                else:
+                    self._late.add(i + j)
+                j += 1
         if j != len(fns) or len(steps) != len(resets) or len(steps) > nat.GF_POST_MAX_CMD or len(obs) > nat.GF_POST_MAX_OBS:
             return None
         if len(gsteps) != len(gresets) or len(gsteps) > nat.GF_POST_MAX_GAIT:
@@ -691,6 +701,11 @@ class StepTrace:
             if not hasattr(self, "_contact_args"):
                 self._contact_args = []
             self._contact_args.append(args)
+        elif fn == "rollout_write" and getattr(owner, "group_row", False):
+            patch, native = owner._trace(args, C.addressof(args) in self._rows_via_unroll)
+            if patch is not None:
+                self.patches.append(patch)
+            self.native.extend(native)
         elif fn == "rollout_write":
             pol = next(m for m in env.managers["observation"] if m.name == owner.obs_name)
             fused = self.post_refs is not None and bool(self.post_refs.rollout)

@@ -12,6 +12,9 @@ dependency and stays one; this module provides the two pieces of it that touch t
   (``add_policy``), and the end-of-rollout return computation (rsl_rl ``compute_returns``: a backwards loop of eight
   elementwise launches per step, then the advantage normalisation) is ``gf_gae`` (``compute_returns``): one lane per env
   walks its T steps, rows are coalesced, the recurrence is the torch loop's arithmetic operation for operation.
+  ``obs_groups`` (rsl_rl's dict form) adds the rows of further ObservationManagers — the gait trainer's asymmetric critic —
+  stored by the step's own launches too, and ``mini_batch_generator`` reads the rollout back as PPO minibatches: rsl_rl's nine
+  per-field index launches per minibatch are one ``gf_minibatch_gather`` launch.
 * :class:`GradientAllReduce` — the multi-GPU half: every rank owns a shard of envs and a replica of the policy; after
   ``backward()`` the gradients of all parameters are averaged with ONE all-reduce over a flat bucket (RCCL over xGMI on GPUs;
   the 512-256-128 actor + critic MLPs of the reference configs are 1.5 MB), overlapped with nothing because nothing follows
@@ -22,12 +25,69 @@ dependency and stays one; this module provides the two pieces of it that touch t
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable, Optional, Sequence
+from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequence
 
 import torch
 
 from . import _native as nat
 from . import gs
+
+
+class MiniBatch(NamedTuple):
+    """One PPO minibatch (rsl_rl ``mini_batch_generator``): rows ``indices`` of the flattened ``[T·N, …]`` storage, fresh tensors."""
+    obs: torch.Tensor            # [mb, W_policy group]
+    critic_obs: torch.Tensor     # [mb, W_critic group] (``obs`` itself when the two groups are the same)
+    actions: torch.Tensor        # [mb, A]
+    values: torch.Tensor         # [mb]
+    advantages: torch.Tensor     # [mb]
+    returns: torch.Tensor        # [mb]
+    old_log_prob: torch.Tensor   # [mb]
+    old_mu: torch.Tensor         # [mb, A]
+    old_sigma: torch.Tensor      # [mb, A]
+    indices: torch.Tensor        # [mb] int64: transition (t, n) = divmod(index, N)
+
+
+_MB_FIELDS = ("actions", "values", "advantages", "returns", "actions_log_prob", "mu", "sigma")   # MiniBatch fields after the observations
+
+
+class _GroupRows:
+    """The time-major rows ``[T+1, N, W]`` of one observation-group member other than the storage's ``obs_name`` manager, and the
+    descriptor that stores them: a ``gf_rollout_write`` with only the observation row set — or, in a fused recorded step, the second
+    destination of the manager's own history gather (no launch of its own)."""
+
+    group_row = True   # (_trace.StepTrace tells these rollout_write calls from the storage's own by it)
+
+    def __init__(self, om, rows: torch.Tensor):
+        self.om, self.rows = om, rows
+        self.args = nat.GfRolloutArgs()
+        self.args.num_envs, self.args.obs_width = rows.shape[1], rows.shape[2]
+
+    def unroll_ok(self) -> bool:
+        """The manager's gather can store the row itself: its history is a ring, and every row start is 16-byte aligned."""
+        return bool(self.om._unrolled) and (self.rows.stride(0) * 4) % 16 == 0 and self.rows.data_ptr() % 16 == 0
+
+    def write(self, backend) -> None:
+        out = self.om._last_out
+        if not out.is_contiguous():
+            raise ValueError(f"RolloutStorage copies contiguous observation rows: '{self.om.name}' is a strided view (output='window')")
+        self.args.obs = out.data_ptr()
+        self._keep = out
+        backend.call("rollout_write", self.args, owner=self)
+
+    def _trace(self, args, via_unroll: bool):
+        """Recorded step: (Python patch or None, native patches).  The row address is advanced by the storage's own patch, which runs
+        first (its rollout_write comes first); ``via_unroll``: the fused launch's gather writes the row as its second destination."""
+        om, P = self.om, nat.GfReplayPatch
+        if om._window:
+            from ._trace import Untraceable
+            raise Untraceable("the rollout rows of a window-mode observation (a strided view) cannot be copied by the step's launch")
+        if via_unroll:
+            def patch(_actions, a=args, u=om._unroll_args):
+                u.out2 = a.obs_out
+
+            return patch, []
+        src = nat.field_addr(om._unroll_args, "out") if om._unrolled else nat.field_addr(om._args, "obs")
+        return None, [P(nat.GF_PATCH_COPY, 0, nat.field_addr(args, "obs"), None, src)]
 
 
 class RolloutStorage:
@@ -36,20 +96,48 @@ class RolloutStorage:
     ``observations[t]`` is the policy input of transition ``t`` (row 0: the observation the rollout starts from; row
     ``num_steps``: the bootstrap observation), ``rewards[t]`` / ``dones[t]`` its outcome.  ``attach()`` makes every
     ``env.step()`` write transition ``step``'s rows and advance; after ``num_steps`` steps ``full`` is true and the next step
-    starts the next rollout (its row 0 is the previous rollout's row ``num_steps``)."""
+    starts the next rollout (its row 0 is the previous rollout's row ``num_steps``).
 
-    def __init__(self, env, num_steps: int, obs_name: str = "policy"):
+    ``obs_groups`` is rsl_rl's dict form (``{"policy": ["policy"], "critic": ["policy", "critic"]}``): a group's input is the
+    concatenation of the named ObservationManagers' rows in list order.  Rows are kept once per distinct manager, not per group:
+    ``observations`` for ``obs_name``, ``group_rows[name]`` for every member (the ``obs_name`` entry is ``observations``
+    itself).  ``None``: both groups are ``[obs_name]`` — nothing beyond ``observations`` is stored.
+    ``mini_batch_generator`` reads the rollout back as PPO minibatches."""
+
+    def __init__(self, env, num_steps: int, obs_name: str = "policy", obs_groups: Optional[Dict[str, Sequence[str]]] = None):
         self.env, self.num_steps, self.obs_name = env, int(num_steps), obs_name
         n = env.num_envs
-        om = next((m for m in env.managers["observation"] if m.name == obs_name), None)
+        managers = {m.name: m for m in env.managers["observation"]}
+        om = managers.get(obs_name)
         if om is None:
             raise ValueError(f"no ObservationManager named '{obs_name}'")
         self._om = om
-        if getattr(om, "output", None) == "window" and om._history_len > 1:
-            raise ValueError("RolloutStorage copies contiguous observation rows: an ObservationManager with output='window' hands out a "
-                             "strided view — use output='fresh' / 'static' for the manager the storage follows")
+        self._refuse_window(om)
         self.obs_width = int(om.observation_space.shape[0])
         self.observations = torch.zeros((self.num_steps + 1, n, self.obs_width), device=gs.device, dtype=torch.float32)
+        groups = {"policy": [obs_name], "critic": [obs_name]} if obs_groups is None else {k: list(v) for k, v in obs_groups.items()}
+        if "policy" not in groups:
+            raise ValueError("obs_groups needs a 'policy' group")
+        groups.setdefault("critic", list(groups["policy"]))
+        self.obs_groups = groups
+        self.group_rows: Dict[str, torch.Tensor] = {}
+        self._group_writers: List[_GroupRows] = []
+        for members in groups.values():
+            if not members:
+                raise ValueError("an observation group needs at least one ObservationManager")
+            for name in members:
+                if name in self.group_rows:
+                    continue
+                m = managers.get(name)
+                if m is None:
+                    raise ValueError(f"obs_groups names '{name}', but the env has no ObservationManager of that name")
+                self._refuse_window(m)
+                if name == obs_name:
+                    self.group_rows[name] = self.observations
+                    continue
+                rows = torch.zeros((self.num_steps + 1, n, int(m.observation_space.shape[0])), device=gs.device, dtype=torch.float32)
+                self.group_rows[name] = rows
+                self._group_writers.append(_GroupRows(m, rows))
         self.rewards = torch.zeros((self.num_steps, n), device=gs.device, dtype=torch.float32)
         self.dones = torch.zeros((self.num_steps, n), device=gs.device, dtype=torch.bool)
         self.step = 0            # transitions written in the current rollout
@@ -61,6 +149,14 @@ class RolloutStorage:
         self._pol_args = nat.GfRolloutPolicyArgs()
         self._gae_args = nat.GfGaeArgs()
         self._moments = None
+        self._returns_ready = False
+        self._mb_args = nat.GfMinibatchArgs()
+
+    @staticmethod
+    def _refuse_window(om) -> None:
+        if getattr(om, "output", None) == "window" and om._history_len > 1:
+            raise ValueError(f"RolloutStorage copies contiguous observation rows: ObservationManager '{om.name}' has output='window' and "
+                             "hands out a strided view — use output='fresh' / 'static' for the managers the storage follows")
 
     @property
     def full(self) -> bool:
@@ -76,8 +172,14 @@ class RolloutStorage:
             self.env._rollout = None
             self.env.invalidate_trace()
 
-    def begin(self, obs: torch.Tensor) -> None:
-        """Start a rollout from ``obs`` (what ``env.reset()`` returned)."""
+    def begin(self, obs: torch.Tensor, extras: Optional[dict] = None) -> None:
+        """Start a rollout from ``obs`` and ``extras`` (what ``env.reset()`` returned; the group members' starting rows are read from
+        ``extras["observations"]``, so ``extras`` is required when ``obs_groups`` names a manager other than ``obs_name``)."""
+        if self._group_writers:
+            if extras is None or "observations" not in extras:
+                raise ValueError("begin(obs, extras): the observation groups need every member's starting rows — pass what env.reset() returned")
+            for w in self._group_writers:
+                w.rows[0].copy_(extras["observations"][w.om.name])
         self.observations[0].copy_(obs)
         self.step = 0
 
@@ -85,11 +187,15 @@ class RolloutStorage:
         """Point the descriptor at transition ``step``'s rows and advance (wrapping into the next rollout)."""
         if self.step >= self.num_steps:
             self.observations[0].copy_(self.observations[self.num_steps])
+            for w in self._group_writers:
+                w.rows[0].copy_(w.rows[self.num_steps])
             self.step = 0
         t = self.step
         a.obs_out = self.observations.data_ptr() + (t + 1) * self.observations.stride(0) * 4
         a.reward_out = self.rewards.data_ptr() + t * self.rewards.stride(0) * 4
         a.done_out = self.dones.data_ptr() + t * self.dones.stride(0)
+        for w in self._group_writers:
+            w.args.obs_out = w.rows.data_ptr() + (t + 1) * w.rows.stride(0) * 4
         self.step = t + 1
 
     def write(self, obs: torch.Tensor, reward: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor) -> None:
@@ -102,6 +208,8 @@ class RolloutStorage:
         self._next_rows(a)
         self._keep = (obs, reward, terminated, truncated)
         self.env.backend.call("rollout_write", a, owner=self)
+        for w in self._group_writers:   # (behind the storage's own launch: a recorded step advances the rows in that order)
+            w.write(self.env.backend)
 
     # -- the policy's half of a transition, returns ---------------------------------------------------------------------------
     def _ensure_policy_rows(self, num_actions: int) -> None:
@@ -154,6 +262,80 @@ class RolloutStorage:
         g.normalize = 1 if normalize else 0
         self._keep_gae = last_values
         self.env.backend.call("gae", g, owner=None)
+        self._returns_ready = True
+
+    # -- PPO minibatches ------------------------------------------------------------------------------------------------------------
+    def mini_batch_generator(self, num_mini_batches: int, num_epochs: int = 1, generator: Optional[torch.Generator] = None) -> Iterator[MiniBatch]:
+        """rsl_rl's ``RolloutStorage.mini_batch_generator``: ONE ``torch.randperm(num_mini_batches * mb)`` (``mb = T·N //
+        num_mini_batches``; the remainder rows are never drawn) shared by all ``num_epochs`` epochs; minibatch ``i`` is rows
+        ``indices[i·mb:(i+1)·mb]`` of every flattened ``[T·N, …]`` array, source row ``k`` being transition ``divmod(k, N)``.
+        Each batch is gathered by one ``gf_minibatch_gather`` launch into fresh tensors (a consumer may keep a batch); the
+        critic input is the concatenation of its group's members, written side by side by the same launch, and is ``obs`` itself
+        when the two groups are the same."""
+        if not self._returns_ready:
+            raise RuntimeError("mini_batch_generator() reads returns and advantages: call compute_returns() first")
+        num_mini_batches, num_epochs = int(num_mini_batches), int(num_epochs)
+        T, n = self.num_steps, self.env.num_envs
+        if num_mini_batches < 1 or num_epochs < 0:
+            raise ValueError("num_mini_batches must be >= 1 and num_epochs >= 0")
+        mb = (T * n) // num_mini_batches
+        if mb < 1:
+            raise ValueError(f"{T * n} transitions cannot fill {num_mini_batches} minibatches")
+        indices = torch.randperm(num_mini_batches * mb, device=gs.device, generator=generator)
+        return self._mini_batches(indices, num_mini_batches, num_epochs, mb)
+
+    def _mini_batches(self, indices: torch.Tensor, num_mini_batches: int, num_epochs: int, mb: int) -> Iterator[MiniBatch]:
+        for _epoch in range(num_epochs):
+            for i in range(num_mini_batches):
+                yield self._gather(indices[i * mb:(i + 1) * mb])
+
+    def _flat(self) -> dict:
+        """Every stored array as its ``[T·N, w]`` source rows (views)."""
+        T, n = self.num_steps, self.env.num_envs
+        rows = {name: r[:T].view(T * n, r.shape[2]) for name, r in self.group_rows.items()}
+        if self.obs_name not in rows:
+            rows[self.obs_name] = self.observations[:T].view(T * n, self.obs_width)
+        per = {k: getattr(self, k).flatten(0, 1) for k in _MB_FIELDS}   # ([T·N] or [T·N, A])
+        return rows, per
+
+    def _gather(self, idx: torch.Tensor) -> MiniBatch:
+        rows, per = self._flat()
+        policy, critic = self.obs_groups["policy"], self.obs_groups["critic"]
+        same = list(critic) == list(policy)
+        gather = getattr(self.env.backend, "minibatch_gather", None)
+        if gather is None:   # (the test-only oracle backend) rsl_rl's expression itself
+            cat = lambda names: rows[names[0]][idx] if len(names) == 1 else torch.cat([rows[m][idx] for m in names], dim=-1)
+            obs = cat(policy)
+            return MiniBatch(obs, obs if same else cat(critic), *(per[k][idx] for k in _MB_FIELDS), idx)
+        m = idx.shape[0]
+        dev = self.observations.device
+        empty = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+        fields = []   # (source rows [T·N, w], destination, its width, first column)
+
+        def group(names):
+            w = sum(rows[k].shape[1] for k in names)
+            out, col = empty(m, w), 0
+            for k in names:
+                fields.append((rows[k], out, w, col))
+                col += rows[k].shape[1]
+            return out
+
+        obs = group(policy)
+        critic_obs = obs if same else group(critic)
+        outs = []
+        for k in _MB_FIELDS:
+            src = per[k]
+            outs.append(empty(m, *src.shape[1:]))
+            fields.append((src, outs[-1], src.shape[1] if src.dim() == 2 else 1, 0))
+        a = self._mb_args
+        a.num_rows, a.num_src_rows, a.indices = m, self.num_steps * self.env.num_envs, idx.data_ptr()
+        for at in range(0, len(fields), nat.GF_MINIBATCH_MAX_FIELDS):   # (more members than one launch holds: a further launch)
+            part = fields[at:at + nat.GF_MINIBATCH_MAX_FIELDS]
+            a.num_fields = len(part)
+            for f, (src, dst, w, col) in zip(a.fields, part):
+                f.src, f.dst, f.src_width, f.dst_width, f.dst_col = src.data_ptr(), dst.data_ptr(), src.numel() // src.shape[0], w, col
+            gather(a)
+        return MiniBatch(obs, critic_obs, *outs, idx)
 
     def _trace_patch(self, args, via_unroll=None):
         """Recorded step: advance the rows.  ``via_unroll`` = the policy ObservationManager when it keeps its history as a ring and

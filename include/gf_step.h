@@ -679,6 +679,36 @@ typedef struct GfCompactArgs {
 } GfCompactArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * PPO minibatches of a finished rollout (rsl_rl RolloutStorage.mini_batch_generator).  rsl_rl draws one permutation of the
+ * T·N transitions per call and builds each minibatch by indexing every flattened [T·N, …] array with a slice of it — obs,
+ * critic obs, actions, values, advantages, returns, log-prob, mu, sigma: nine index launches that read and write every stored
+ * byte once per epoch.  gf_minibatch_gather copies every field of the selected rows in ONE launch:
+ *     fields[f].dst[i * dst_width + dst_col + c] = fields[f].src[indices[i] * src_width + c]   (i < num_rows, c < src_width)
+ * `dst_col` lets the members of a concatenated observation group land side by side in one [num_rows, dst_width] output.
+ * An index outside [0, num_src_rows) is never dereferenced: its row is written as quiet NaN in every field.  Pure copy:
+ * bit-identical to `src[indices]`.  Not a phase of the step: it never enters a recorded step's op table.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_MINIBATCH_MAX_FIELDS 12
+
+typedef struct GfMinibatchField {
+    const float* src;           /* [num_src_rows, src_width] f32, row-major */
+    float* dst;                 /* [num_rows, dst_width] f32, row-major */
+    int32_t src_width;          /* >= 1 */
+    int32_t dst_width;          /* >= dst_col + src_width */
+    int32_t dst_col;            /* first destination column of this field */
+    int32_t _pad;
+} GfMinibatchField;
+
+typedef struct GfMinibatchArgs {
+    int64_t num_rows;           /* rows of the minibatch; 0: nothing is launched */
+    int64_t num_src_rows;       /* T·N >= 1: indices at or past it (or negative) give NaN rows */
+    const int64_t* indices;     /* [num_rows] source rows (a slice of torch.randperm) */
+    int32_t num_fields;         /* 1 … GF_MINIBATCH_MAX_FIELDS */
+    int32_t _pad;
+    GfMinibatchField fields[GF_MINIBATCH_MAX_FIELDS];
+} GfMinibatchArgs;
+
+/* ------------------------------------------------------------------------------------------
  * History ring -> the reference's observation layout.  The reference keeps a list of H frames, pops the oldest, inserts the new
  * one in front and returns `torch.cat(self._history, dim=-1)` (observation_manager.py:219-226): every call writes a NEW
  * [N, H*O] tensor, newest frame first.  With the history kept as an in-place ring (GfObservationArgs.history_ring: the step
@@ -719,7 +749,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -741,6 +771,7 @@ int gf_history_unroll(const GfHistoryUnrollArgs* a, void* stream);/* replaces th
 int gf_rollout_policy_write(const GfRolloutPolicyArgs* a, void* stream);   /* the policy's rows of a transition + time-out bootstrap (rsl_rl add_transitions; call site examples/simple/train.py:125-129) */
 int gf_done_compact(const GfCompactArgs* a, void* stream);       /* replaces the nonzero() of managed_env.py:308-310 where an index list is still needed */
 int gf_gae(const GfGaeArgs* a, void* stream);                     /* returns and advantages of a finished rollout (rsl_rl compute_returns; gamma / lam: examples/simple/train.py:41-47) */
+int gf_minibatch_gather(const GfMinibatchArgs* a, void* stream);  /* every field of one PPO minibatch in one launch (rsl_rl mini_batch_generator) */
 
 /* ------------------------------------------------------------------------------------------
  * Fused post-physics step: everything ManagedEnvironment.step() does after scene.step() and the

@@ -70,6 +70,8 @@ GF_EXPORT int gf_sizeof(int which) {
         case 21: return (int)sizeof(GfGaeArgs);
         case 22: return (int)sizeof(GfCompactArgs);
         case 23: return (int)sizeof(GfMinibatchArgs);
+        case 24: return (int)sizeof(GfPolicyActArgs);
+        case 25: return (int)sizeof(GfEpisodeArgs);
         default: return -1;
     }
 }

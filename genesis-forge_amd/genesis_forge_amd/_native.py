@@ -320,6 +320,27 @@ class GfMinibatchArgs(C.Structure):
                 ("fields", GfMinibatchField * GF_MINIBATCH_MAX_FIELDS)]
 
 
+# the collection loop around env.step() (learner.RolloutStorage.act / process_env_step, learner.EpisodeStatistics): like the
+# minibatch gather, not in ABI_STRUCTS — the oracle twin has neither
+GF_SIZEOF_POLICY_ACT = 24
+GF_SIZEOF_EPISODE = 25
+GF_POLICY_SEED_TAG = 0xAC7105A3C7105EED   # the kernel keys the action noise with seed ^ this tag (gf_step.h)
+GF_EPISODE_BLOCK_ENVS = 1024
+GF_EPISODE_SINGLE_MAX = 65536
+
+
+class GfPolicyActArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("num_actions", C.c_int32), ("std_per_env", C.c_int32), ("mean", P), ("std", P), ("values", P),
+                ("noise", P), ("seed", C.c_uint64), ("stream", C.c_uint64), ("env_offset", C.c_uint32), ("_pad", C.c_uint32),
+                ("actions", P), ("actions_out", P), ("mu_out", P), ("sigma_out", P), ("values_out", P), ("log_prob_out", P)]
+
+
+class GfEpisodeArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("rewards", P), ("dones", P), ("time_outs", P), ("values", P), ("cur_reward_sum", P),
+                ("cur_episode_length", P), ("ring_reward", P), ("ring_length", P), ("ring_state", P), ("block_counts", P),
+                ("gamma", C.c_float), ("window", C.c_int32), ("parity", C.c_int32), ("_pad", C.c_int32)]
+
+
 ABI_STRUCTS = [GfStepStats, GfActionArgs, GfContactArgs, GfTerminationArgs, GfRewardArgs, GfCommandArgs,
                GfResetArgs, GfObservationArgs, GfRotateArgs, GfSynthSceneArgs, GfTerm, GfObsItem, GfTerrainView, GfTerrainHeightArgs, GfGaitArgs, GfContactView, GfCommandView,
                GfPostRefs, GfRolloutArgs, GfHistoryUnrollArgs, GfRolloutPolicyArgs, GfGaeArgs, GfCompactArgs]
@@ -514,6 +535,13 @@ class HipBackend(Backend):
             raise GfError(f"ABI drift: sizeof(GfMinibatchArgs) is {n} in the library, {C.sizeof(GfMinibatchArgs)} in the binding")
         self.lib.gf_minibatch_gather.restype = C.c_int
         self.lib.gf_minibatch_gather.argtypes = [C.POINTER(GfMinibatchArgs), C.c_void_p]
+        # the two pieces of the collection loop (RolloutStorage.act / process_env_step): the same kind of entry points
+        for fn, idx, st in (("gf_policy_act", GF_SIZEOF_POLICY_ACT, GfPolicyActArgs), ("gf_episode_step", GF_SIZEOF_EPISODE, GfEpisodeArgs)):
+            n = self.lib.gf_sizeof(idx)
+            if n != C.sizeof(st):
+                raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")
+            getattr(self.lib, fn).restype = C.c_int
+            getattr(self.lib, fn).argtypes = [C.POINTER(st), C.c_void_p]
 
     def _stream(self) -> int:
         torch = self._torch
@@ -546,6 +574,18 @@ class HipBackend(Backend):
         rc = self.lib.gf_minibatch_gather(C.byref(args), self._stream())
         if rc != 0:
             self._raise("minibatch_gather", rc)
+
+    def policy_act(self, args) -> None:
+        """gf_policy_act on the current stream (learner.RolloutStorage.act)."""
+        rc = self.lib.gf_policy_act(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("policy_act", rc)
+
+    def episode_step(self, args) -> None:
+        """gf_episode_step on the current stream (learner.RolloutStorage.process_env_step, learner.EpisodeStatistics.update)."""
+        rc = self.lib.gf_episode_step(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("episode_step", rc)
 
     def run_ops(self, ops, n: int) -> None:
         failed = C.c_int(-1)

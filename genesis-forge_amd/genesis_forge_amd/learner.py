@@ -15,6 +15,11 @@ dependency and stays one; this module provides the two pieces of it that touch t
   ``obs_groups`` (rsl_rl's dict form) adds the rows of further ObservationManagers — the gait trainer's asymmetric critic —
   stored by the step's own launches too, and ``mini_batch_generator`` reads the rollout back as PPO minibatches: rsl_rl's nine
   per-field index launches per minibatch are one ``gf_minibatch_gather`` launch.
+  The two per-step pieces of rsl_rl's collection loop around ``env.step()`` are one launch each: ``act`` samples the Gaussian
+  actions, their log-probability and the policy's rows (``PPO.act``: ~ten elementwise launches, then five ``copy_``) with
+  ``gf_policy_act``, and ``process_env_step`` bootstraps the time-outs and keeps the runner's episode statistics
+  (:class:`EpisodeStatistics`: ``rewbuffer`` / ``lenbuffer`` without the per-step ``nonzero()`` and ``.cpu()``) with
+  ``gf_episode_step``.
 * :class:`GradientAllReduce` — the multi-GPU half: every rank owns a shard of envs and a replica of the policy; after
   ``backward()`` the gradients of all parameters are averaged with ONE all-reduce over a flat bucket (RCCL over xGMI on GPUs;
   the 512-256-128 actor + critic MLPs of the reference configs are 1.5 MB), overlapped with nothing because nothing follows
@@ -25,6 +30,8 @@ dependency and stays one; this module provides the two pieces of it that touch t
 from __future__ import annotations
 
 import ctypes as C
+import math
+import statistics
 from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequence
 
 import torch
@@ -48,6 +55,31 @@ class MiniBatch(NamedTuple):
 
 
 _MB_FIELDS = ("actions", "values", "advantages", "returns", "actions_log_prob", "mu", "sigma")   # MiniBatch fields after the observations
+_LOG_SQRT_2PI = math.log(math.sqrt(2 * math.pi))   # the constant of torch's Normal.log_prob
+
+
+def _check_f32(x, name: str, shapes, device) -> None:
+    """``act``'s inputs are taken as they are: float32, contiguous, on the storage's device, one of ``shapes`` — nothing is cast."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, not {x.dtype}")
+    if x.device != device:
+        raise ValueError(f"{name} lives on {x.device}, the storage on {device}")
+    if tuple(x.shape) not in shapes:
+        raise ValueError(f"{name} has shape {tuple(x.shape)}; expected one of {sorted(shapes)}")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _check_mask(x, name: str, n: int, device) -> torch.Tensor:
+    """A ``[N]`` done / time-out mask on ``device`` as the bytes the kernel reads (bool or uint8; anything else is compared with 0)."""
+    if not isinstance(x, torch.Tensor) or x.device != device or x.numel() != n or (x.dim() == 2 and x.shape[1] != 1) or x.dim() > 2:
+        raise ValueError(f"{name} must be a [{n}] tensor on {device}")
+    x = x.reshape(n)
+    if x.dtype != torch.bool and x.dtype != torch.uint8:
+        x = x != 0
+    return x.contiguous()
 
 
 class _GroupRows:
@@ -151,6 +183,15 @@ class RolloutStorage:
         self._moments = None
         self._returns_ready = False
         self._mb_args = nat.GfMinibatchArgs()
+        # the collection loop around env.step() (act / process_env_step).  `_serial` counts the transitions written; the policy rows
+        # and the bootstrap are tracked as the serial of the transition they belong to.  The action noise has a Philox seed and
+        # stream of its own (``seed()``): never the env's draws.
+        self._serial = 0
+        self._pol_serial = self._boot_serial = -1
+        self._act_seed: Optional[int] = None   # None: the env's seed (the kernel XORs GF_POLICY_SEED_TAG into it either way)
+        self._act_stream = 0
+        self._act_args = nat.GfPolicyActArgs()
+        self._ep_args = nat.GfEpisodeArgs()
 
     @staticmethod
     def _refuse_window(om) -> None:
@@ -182,6 +223,7 @@ class RolloutStorage:
                 w.rows[0].copy_(extras["observations"][w.om.name])
         self.observations[0].copy_(obs)
         self.step = 0
+        self._pol_serial = self._boot_serial = -1
 
     def _next_rows(self, a: nat.GfRolloutArgs) -> None:
         """Point the descriptor at transition ``step``'s rows and advance (wrapping into the next rollout)."""
@@ -197,6 +239,7 @@ class RolloutStorage:
         for w in self._group_writers:
             w.args.obs_out = w.rows.data_ptr() + (t + 1) * w.rows.stride(0) * 4
         self.step = t + 1
+        self._serial += 1
 
     def write(self, obs: torch.Tensor, reward: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor) -> None:
         """One transition through ``gf_rollout_write`` (the phase-by-phase path; a recorded step fuses it, _trace.py)."""
@@ -247,6 +290,119 @@ class RolloutStorage:
             a.time_outs, a.reward_row, a.gamma = None, None, 0.0
         self._keep_pol = (actions, values, log_prob, mu, sigma, time_outs)
         self.env.backend.call("rollout_policy_write", a, owner=None)
+        self._pol_serial = self._serial
+        if time_outs is not None:
+            self._boot_serial = self._serial
+
+    # -- the collection loop around env.step(): act -> env.step -> process_env_step ---------------------------------------------
+    def seed(self, seed: int) -> None:
+        """Seed of the action noise of ``act`` (Philox key ``seed ^ GF_POLICY_SEED_TAG``); its stream starts again at 0.  Until
+        this is called the env's seed is used — with the tag, so the draws never repeat one of the env's."""
+        self._act_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._act_stream = 0
+
+    def act(self, mean: torch.Tensor, std: torch.Tensor, values: torch.Tensor, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """rsl_rl's ``PPO.act`` from the actor's ``mean`` ``[N, A]``, the action ``std`` (``[A]``, rsl_rl's ``noise_std_type=
+        "scalar"``; pass ``log_std.exp()`` for ``"log"``; or ``[N, A]``) and the critic's ``values`` (``[N]`` or ``[N, 1]``):
+        returns ``Normal(mean, std).sample()`` as a fresh ``[N, A]`` tensor and writes the policy's rows of the transition the next
+        ``env.step()`` writes (row ``step``, 0 once the storage is ``full``): actions, mu, sigma (``std`` expanded), values and
+        ``log_prob(actions).sum(-1)``.  One ``gf_policy_act`` launch; the draws are Philox + Box–Muller keyed by (seed, stream,
+        global env id, column) — the stream advances once per call, the env's own stream is never touched.
+        ``noise``: ``[N, A]`` standard normals used instead of the draws (parity tests; the only mode of the CPU oracle backend).
+        Inputs must be float32, contiguous and on the storage's device: nothing is cast (``ValueError``)."""
+        n, dev = self.env.num_envs, self.observations.device
+        if not isinstance(mean, torch.Tensor) or mean.dim() != 2 or mean.shape[0] != n or mean.shape[1] < 1:
+            raise ValueError(f"mean must be a [{n}, A] tensor")
+        A = int(mean.shape[1])
+        _check_f32(mean, "mean", {(n, A)}, dev)
+        _check_f32(std, "std", {(A,), (n, A)}, dev)
+        _check_f32(values, "values", {(n,), (n, 1)}, dev)
+        if noise is not None:
+            _check_f32(noise, "noise", {(n, A)}, dev)
+        t = 0 if self.full else self.step   # (env.step() does the wrap's row copies; only the row index is needed here)
+        self._ensure_policy_rows(A)
+        actions = torch.empty((n, A), device=dev, dtype=torch.float32)
+        stream = self._act_stream
+        self._act_stream += 1
+        fn = getattr(self.env.backend, "policy_act", None)
+        if fn is None:   # (the test-only oracle backend) the same expression in torch, from the given draws
+            if noise is None:
+                raise RuntimeError("act() draws its noise in the HIP kernel: on a backend without gf_policy_act pass noise=")
+            self._act_torch(mean, std, values, noise, actions, t)
+        else:
+            a = self._act_args
+            a.num_envs, a.num_actions, a.std_per_env = n, A, 1 if std.dim() == 2 else 0
+            a.mean, a.std, a.values = mean.data_ptr(), std.data_ptr(), values.data_ptr()
+            a.noise = None if noise is None else noise.data_ptr()
+            a.seed = self.env._rng_seed if self._act_seed is None else self._act_seed
+            a.stream, a.env_offset = stream, int(getattr(self.env, "env_offset", 0))
+            a.actions = actions.data_ptr()
+            a.actions_out, a.mu_out, a.sigma_out = (x.data_ptr() + t * x.stride(0) * 4 for x in (self.actions, self.mu, self.sigma))
+            a.values_out, a.log_prob_out = (x.data_ptr() + t * x.stride(0) * 4 for x in (self.values, self.actions_log_prob))
+            self._keep_act = (mean, std, values, noise)
+            fn(a)
+        self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
+        return actions
+
+    def _act_torch(self, mean, std, values, noise, actions, t) -> None:
+        with torch.no_grad():
+            sd = std.expand_as(mean)
+            actions.copy_(mean + sd * noise)
+            d = actions - mean
+            term = -(d * d) / (2 * (sd * sd)) - sd.log() - _LOG_SQRT_2PI
+            lp = term[:, 0].clone()
+            for c in range(1, term.shape[1]):   # (a left fold, as the kernel)
+                lp = lp + term[:, c]
+            self.actions[t].copy_(actions)
+            self.mu[t].copy_(mean)
+            self.sigma[t].copy_(sd)
+            self.values[t].copy_(values.reshape(-1))
+            self.actions_log_prob[t].copy_(lp)
+
+    def process_env_step(self, time_outs: Optional[torch.Tensor], gamma: float = 0.99, episodes: Optional["EpisodeStatistics"] = None) -> None:
+        """After ``env.step()``: for the transition it wrote (row ``step - 1``) update ``episodes`` from the raw ``rewards`` / ``dones``
+        rows as rsl_rl's runner does, then bootstrap ``rewards[t] += (gamma * values[t]) * time_outs`` (PPO.process_env_step) —
+        one ``gf_episode_step`` launch.  ``time_outs=None``: the statistics only.  The transition's policy rows must be in (``act``
+        before the step or ``add_policy`` after it), and a row is bootstrapped once: after ``add_policy(..., time_outs=…)`` pass
+        ``time_outs=None``."""
+        if self.step < 1 or self._serial == 0:
+            raise RuntimeError("process_env_step() follows the env.step() whose transition it completes")
+        t = self.step - 1
+        if self._pol_serial != self._serial:
+            raise RuntimeError(f"process_env_step() needs the policy rows of transition {t}: call act() before env.step() or add_policy() after it")
+        n, dev = self.env.num_envs, self.observations.device
+        if time_outs is not None:
+            if self._boot_serial == self._serial:
+                raise RuntimeError(f"the rewards of transition {t} are already bootstrapped (add_policy(time_outs=...) or process_env_step)")
+            time_outs = _check_mask(time_outs, "time_outs", n, dev)
+        if episodes is not None and episodes.num_envs != n:
+            raise ValueError(f"episodes keeps {episodes.num_envs} envs, the storage {n}")
+        if time_outs is None and episodes is None:
+            return
+        rewards, dones, values = self.rewards[t], self.dones[t], self.values[t]
+        fn = getattr(self.env.backend, "episode_step", None)
+        if fn is None:   # (the test-only oracle backend) the runner's and PPO's torch expressions
+            if episodes is not None:
+                episodes._update_torch(rewards, dones)
+            if time_outs is not None:
+                with torch.no_grad():
+                    rewards.copy_(rewards + (float(gamma) * values) * time_outs.to(torch.float32))
+        else:
+            a = self._ep_args
+            a.num_envs, a.rewards, a.dones = n, rewards.data_ptr(), dones.data_ptr()
+            a.time_outs = None if time_outs is None else time_outs.data_ptr()
+            a.values = None if time_outs is None else values.data_ptr()
+            a.gamma = float(gamma)
+            if episodes is not None:
+                episodes._fill(a)
+            else:
+                a.cur_reward_sum = a.cur_episode_length = a.ring_reward = a.ring_length = a.ring_state = a.block_counts = None
+            self._keep_ep = time_outs
+            fn(a)
+            if episodes is not None:
+                episodes._calls += 1
+        if time_outs is not None:
+            self._boot_serial = self._serial
 
     def compute_returns(self, last_values: torch.Tensor, gamma: float = 0.99, lam: float = 0.95, normalize: bool = True) -> None:
         """``returns`` / ``advantages`` of the finished rollout (rsl_rl ``RolloutStorage.compute_returns``; gamma / lam as
@@ -358,6 +514,117 @@ class RolloutStorage:
         if getattr(pol, "_unrolled", False):
             return [] if fused else [P(nat.GF_PATCH_COPY, 0, nat.field_addr(args, "obs"), None, nat.field_addr(pol._unroll_args, "out"))]
         return [P(nat.GF_PATCH_COPY, 0, nat.field_addr(args, "obs"), None, nat.field_addr(pol._args, "obs"))]
+
+
+class EpisodeStatistics:
+    """rsl_rl ``OnPolicyRunner.learn``'s episode bookkeeping, kept on the device: ``cur_reward_sum`` / ``cur_episode_length``
+    (``[N]`` float32) and the last ``window`` finished returns and lengths (``rewbuffer`` / ``lenbuffer``, ``deque(maxlen=
+    window)``) as a ring.  Every step: ``cur_reward_sum += rewards``, ``cur_episode_length += 1``; every done env appends its two
+    values in ascending env order, then both are zeroed.  ``update`` (or ``RolloutStorage.process_env_step(..., episodes=)``)
+    is one ``gf_episode_step`` launch with no host synchronisation; the reads below synchronise — once per log interval."""
+
+    def __init__(self, num_envs: int, window: int = 100, device=None):
+        if int(num_envs) < 1 or int(window) < 1:
+            raise ValueError("EpisodeStatistics needs num_envs >= 1 and window >= 1")
+        self.num_envs, self.window = int(num_envs), int(window)
+        dev = torch.device(gs.device if device is None else device)
+        z = lambda k, dt=torch.float32: torch.zeros(k, device=dev, dtype=dt)
+        self.cur_reward_sum, self.cur_episode_length = z(self.num_envs), z(self.num_envs)
+        self.ring_reward, self.ring_length = z(self.window), z(self.window)
+        self.ring_state = z(4, torch.int32)   # [2][2] {head, fill}: a launch reads slot _calls & 1 and writes the other
+        big = self.num_envs > nat.GF_EPISODE_SINGLE_MAX
+        self._block_counts = z(-(-self.num_envs // nat.GF_EPISODE_BLOCK_ENVS), torch.int32) if big else None
+        self._calls = 0
+        self._args = nat.GfEpisodeArgs()
+
+    @property
+    def device(self) -> torch.device:
+        return self.cur_reward_sum.device
+
+    def _fill(self, a) -> None:
+        """Point the statistics fields of a GfEpisodeArgs at these tensors."""
+        a.cur_reward_sum, a.cur_episode_length = self.cur_reward_sum.data_ptr(), self.cur_episode_length.data_ptr()
+        a.ring_reward, a.ring_length, a.ring_state = self.ring_reward.data_ptr(), self.ring_length.data_ptr(), self.ring_state.data_ptr()
+        a.block_counts = None if self._block_counts is None else self._block_counts.data_ptr()
+        a.window, a.parity = self.window, self._calls & 1
+
+    def update(self, rewards: torch.Tensor, dones: torch.Tensor) -> None:
+        """One step of the runner's bookkeeping from this step's ``rewards`` (``[N]`` float32, before any bootstrap) and ``dones``
+        (``[N]``; bool / uint8, anything else is compared with 0), for loops without a :class:`RolloutStorage`.  One launch."""
+        n, dev = self.num_envs, self.device
+        if not isinstance(rewards, torch.Tensor) or rewards.dtype != torch.float32 or rewards.device != dev or rewards.numel() != n:
+            raise ValueError(f"rewards must be a [{n}] float32 tensor on {dev}")
+        rewards = rewards.reshape(n)
+        if not rewards.is_contiguous():
+            raise ValueError("rewards must be contiguous")
+        dones = _check_mask(dones, "dones", n, dev)
+        fn = getattr(nat.get_backend(), "episode_step", None)
+        if fn is None:   # (the test-only oracle backend)
+            self._update_torch(rewards, dones)
+            return
+        a = self._args
+        a.num_envs, a.rewards, a.dones, a.time_outs, a.values, a.gamma = n, rewards.data_ptr(), dones.data_ptr(), None, None, 0.0
+        self._fill(a)
+        self._keep = (rewards, dones)
+        fn(a)
+        self._calls += 1
+
+    def _update_torch(self, rewards: torch.Tensor, dones: torch.Tensor) -> None:
+        """The runner's lines themselves (``nonzero`` and a host copy per step), for the CPU oracle backend."""
+        with torch.no_grad():
+            self.cur_reward_sum += rewards
+            self.cur_episode_length += 1
+            ids = (dones != 0).nonzero()[:, 0]
+            k, W = int(ids.numel()), self.window
+            head, fill = self._state()
+            if k:
+                keep = ids[max(0, k - W):]
+                pos = (head + torch.arange(k - keep.numel(), k, device=ids.device)) % W
+                self.ring_reward[pos] = self.cur_reward_sum[keep]
+                self.ring_length[pos] = self.cur_episode_length[keep]
+                self.cur_reward_sum[ids] = 0
+                self.cur_episode_length[ids] = 0
+            nxt = 1 - (self._calls & 1)
+            self.ring_state[2 * nxt] = (head + k) % W
+            self.ring_state[2 * nxt + 1] = min(fill + k, W)
+        self._calls += 1
+
+    def _state(self):
+        head, fill = self.ring_state[2 * (self._calls & 1):2 * (self._calls & 1) + 2].tolist()
+        return int(head), int(fill)
+
+    def _ring(self, ring: torch.Tensor) -> List[float]:
+        head, fill = self._state()
+        if fill == 0:
+            return []
+        vals = ring.tolist()
+        start = (head - fill) % self.window
+        return [vals[(start + i) % self.window] for i in range(fill)]
+
+    @property
+    def rewbuffer(self) -> List[float]:
+        """The finished returns, oldest first (rsl_rl's ``rewbuffer`` deque as a list)."""
+        return self._ring(self.ring_reward)
+
+    @property
+    def lenbuffer(self) -> List[float]:
+        """The matching episode lengths, oldest first (rsl_rl's ``lenbuffer``)."""
+        return self._ring(self.ring_length)
+
+    def mean_reward(self) -> Optional[float]:
+        """``statistics.mean(rewbuffer)`` — the runner's "Mean reward" — or None while no episode has finished."""
+        buf = self.rewbuffer
+        return statistics.mean(buf) if buf else None
+
+    def mean_episode_length(self) -> Optional[float]:
+        """``statistics.mean(lenbuffer)`` — "Mean episode length" — or None while no episode has finished."""
+        buf = self.lenbuffer
+        return statistics.mean(buf) if buf else None
+
+    def reset(self) -> None:
+        for x in (self.cur_reward_sum, self.cur_episode_length, self.ring_reward, self.ring_length, self.ring_state):
+            x.zero_()
+        self._calls = 0
 
 
 class ActorCriticMLP(torch.nn.Module):

@@ -709,6 +709,84 @@ typedef struct GfMinibatchArgs {
 } GfMinibatchArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * Gaussian action sampling of a PPO collection step (rsl_rl PPO.act -> ActorCritic.act / get_actions_log_prob).  rsl_rl builds
+ * Normal(mean, std), samples with torch.normal, computes log_prob(actions).sum(-1) — about ten elementwise launches on [N, A] —
+ * and add_transitions then copies the results into the storage.  gf_policy_act does all of it in ONE launch, one lane per env:
+ *     eps     = noise[n, a]  or  Philox4x32-10 + Box–Muller (below)
+ *     actions = mean + std * eps                                        (one product, one sum: torch.normal's order)
+ *     log_prob[n] = left fold over a of  -((act - mean)^2) / (2 * std^2) - log(std) - c,   c = (float)log(sqrt(2π))
+ *                                                                       (the operation order of torch's Normal.log_prob)
+ * and stores actions into the fresh `actions` tensor and, where given, the storage rows of transition t (actions, mu = mean,
+ * sigma = std expanded to [N, A], values, actions_log_prob).
+ * Draws: Philox block (env_offset + n, a / 4, stream_lo, stream_hi) keyed by seed ^ GF_POLICY_SEED_TAG (never the env's own key,
+ * so no env draw is ever repeated) gives the normals of columns 4k … 4k+3: words (x, y) -> columns 4k, 4k+1 and (z, w) -> 4k+2, 4k+3,
+ *     u1 = ((word1 >> 8) + 1) · 2^-24 ∈ (0, 1],  u2 = (word2 >> 8) · 2^-24,  r = sqrt(-2 · log(u1)),
+ *     first = r · cospi(2 · u2),  second = r · sinpi(2 · u2).
+ * Not a phase of the step: it never enters a recorded step's op table.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_POLICY_SEED_TAG 0xAC7105A3C7105EEDull   /* XOR-ed into the seed of the action noise: a key of its own */
+
+typedef struct GfPolicyActArgs {
+    int64_t num_envs;           /* N >= 0; 0: nothing is launched */
+    int32_t num_actions;        /* A >= 1 */
+    int32_t std_per_env;        /* 0: std is [A] (shared by every env), 1: std is [N, A] */
+    const float* mean;          /* [N, A] actor output */
+    const float* std;           /* [A] or [N, A] */
+    const float* values;        /* [N] critic output, or NULL (then values_out must be NULL) */
+    const float* noise;         /* [N, A] standard normals (parity mode), or NULL: Philox + Box–Muller */
+    uint64_t seed;              /* Philox key = seed ^ GF_POLICY_SEED_TAG */
+    uint64_t stream;            /* Philox counter words 2-3 */
+    uint32_t env_offset;        /* global index of local env 0 (env sharding) */
+    uint32_t _pad;
+    float* actions;             /* [N, A] out (required) */
+    float* actions_out;         /* [N, A] storage row, or NULL */
+    float* mu_out;              /* [N, A] storage row, or NULL */
+    float* sigma_out;           /* [N, A] storage row, or NULL */
+    float* values_out;          /* [N] storage row, or NULL */
+    float* log_prob_out;        /* [N] storage row, or NULL */
+} GfPolicyActArgs;
+
+/* ------------------------------------------------------------------------------------------
+ * Time-out bootstrap and the episode statistics of rsl_rl's OnPolicyRunner.learn.  Every step the runner does
+ *     cur_reward_sum += rewards; cur_episode_length += 1; new_ids = (dones > 0).nonzero()
+ *     rewbuffer.extend(cur_reward_sum[new_ids].cpu()...); lenbuffer.extend(cur_episode_length[new_ids].cpu()...)
+ *     cur_reward_sum[new_ids] = 0; cur_episode_length[new_ids] = 0
+ * (about eight launches and two or three host synchronisations; rewbuffer / lenbuffer are deque(maxlen=window)), and
+ * PPO.process_env_step bootstraps the rewards of timed-out envs.  gf_episode_step does both in ONE launch up to
+ * GF_EPISODE_SINGLE_MAX envs and in two above (a per-block count of the done envs, then everything else), as gf_done_compact:
+ *   * cur_reward_sum[n] += rewards[n] (one f32 add), cur_episode_length[n] += 1;
+ *   * every done env appends (cur_reward_sum, cur_episode_length) to the ring in ascending env order, then both are zeroed; the
+ *     ring keeps the last `window` entries, like deque.extend: of a step's `count` finished envs, rank k survives iff
+ *     k >= count - window, at slot (head + k) mod window.  A block finds the done envs in front of it by counting the masks itself
+ *     (one launch) or from the per-block counts (two launches) — no inter-workgroup wait;
+ *   * ring_state holds {head, fill} twice: the launch reads slot `parity` and writes slot 1 - parity (a host-side call counter's
+ *     parity), so no block ever reads a word another block of the same launch writes;
+ *   * with time_outs: rewards[n] = rewards[n] + (gamma * values[n]) * time_out — after the statistics read the raw reward (the
+ *     runner counts the reward before the bootstrap), the same expression as gf_rollout_policy_write.
+ * Not a phase of the step: it never enters a recorded step's op table.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_EPISODE_BLOCK_ENVS 1024      /* envs per workgroup (256 lanes x 4) */
+#define GF_EPISODE_SINGLE_MAX 65536     /* one launch up to this many envs; above it, two (block_counts required) */
+
+typedef struct GfEpisodeArgs {
+    int64_t num_envs;           /* N, 0 <= N < 2^31; 0: nothing is launched */
+    float* rewards;             /* [N] raw rewards of the step (required); rewritten in place by the bootstrap */
+    const uint8_t* dones;       /* [N] nonzero = done (required with statistics) */
+    const uint8_t* time_outs;   /* [N] nonzero = timed out, or NULL: no bootstrap */
+    const float* values;        /* [N] value estimates of the transition (required with time_outs) */
+    float* cur_reward_sum;      /* [N], or NULL: no statistics (then every statistics pointer is NULL) */
+    float* cur_episode_length;  /* [N] */
+    float* ring_reward;         /* [window] finished returns */
+    float* ring_length;         /* [window] finished lengths */
+    int32_t* ring_state;        /* [2][2] {head, fill}: slot `parity` is read, slot 1 - parity written */
+    int32_t* block_counts;      /* scratch, ceil(N / GF_EPISODE_BLOCK_ENVS) words: required above GF_EPISODE_SINGLE_MAX envs */
+    float gamma;
+    int32_t window;             /* ring capacity >= 1 (with statistics) */
+    int32_t parity;             /* 0 or 1 */
+    int32_t _pad;
+} GfEpisodeArgs;
+
+/* ------------------------------------------------------------------------------------------
  * History ring -> the reference's observation layout.  The reference keeps a list of H frames, pops the oldest, inserts the new
  * one in front and returns `torch.cat(self._history, dim=-1)` (observation_manager.py:219-226): every call writes a NEW
  * [N, H*O] tensor, newest frame first.  With the history kept as an in-place ring (GfObservationArgs.history_ring: the step
@@ -749,7 +827,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -772,6 +850,8 @@ int gf_rollout_policy_write(const GfRolloutPolicyArgs* a, void* stream);   /* th
 int gf_done_compact(const GfCompactArgs* a, void* stream);       /* replaces the nonzero() of managed_env.py:308-310 where an index list is still needed */
 int gf_gae(const GfGaeArgs* a, void* stream);                     /* returns and advantages of a finished rollout (rsl_rl compute_returns; gamma / lam: examples/simple/train.py:41-47) */
 int gf_minibatch_gather(const GfMinibatchArgs* a, void* stream);  /* every field of one PPO minibatch in one launch (rsl_rl mini_batch_generator) */
+int gf_policy_act(const GfPolicyActArgs* a, void* stream);       /* Normal sample + log_prob + the policy's storage rows in one launch (rsl_rl PPO.act) */
+int gf_episode_step(const GfEpisodeArgs* a, void* stream);       /* time-out bootstrap + the runner's rewbuffer / lenbuffer upkeep (rsl_rl OnPolicyRunner.learn) */
 
 /* ------------------------------------------------------------------------------------------
  * Fused post-physics step: everything ManagedEnvironment.step() does after scene.step() and the

@@ -72,6 +72,8 @@ GF_EXPORT int gf_sizeof(int which) {
         case 23: return (int)sizeof(GfMinibatchArgs);
         case 24: return (int)sizeof(GfPolicyActArgs);
         case 25: return (int)sizeof(GfEpisodeArgs);
+        case 26: return (int)sizeof(GfPpoLossArgs);
+        case 27: return (int)sizeof(GfAdamArgs);
         default: return -1;
     }
 }

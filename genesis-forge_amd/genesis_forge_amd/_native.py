@@ -341,6 +341,40 @@ class GfEpisodeArgs(C.Structure):
                 ("gamma", C.c_float), ("window", C.c_int32), ("parity", C.c_int32), ("_pad", C.c_int32)]
 
 
+# the PPO update (learner.PPO): gf_ppo_loss / gf_adam_step, not in ABI_STRUCTS either
+GF_SIZEOF_PPO_LOSS = 26
+GF_SIZEOF_ADAM = 27
+GF_PPO_BLOCK_ROWS = 256
+GF_PPO_OUT_COUNT = 5        # out[]: surrogate, value_loss, entropy, kl_mean, loss
+GF_ADAM_BLOCK_ELEMS = 1024
+GF_ADAM_MAX_PARTIALS = 1024
+GF_ADAM_SCHEDULE_FIXED = 0
+GF_ADAM_SCHEDULE_ADAPTIVE = 1
+
+
+def ppo_loss_workspace_bytes(mb: int, num_actions: int) -> int:
+    """GF_PPO_LOSS_WORKSPACE_BYTES: (3 + A) doubles per workgroup of GF_PPO_BLOCK_ROWS rows."""
+    return -(-int(mb) // GF_PPO_BLOCK_ROWS) * (3 + int(num_actions)) * 8
+
+
+def adam_workspace_bytes(numel: int) -> int:
+    """GF_ADAM_WORKSPACE_BYTES: one double per norm workgroup."""
+    return min(-(-int(numel) // GF_ADAM_BLOCK_ELEMS), GF_ADAM_MAX_PARTIALS) * 8
+
+
+class GfPpoLossArgs(C.Structure):
+    _fields_ = [("num_rows", C.c_int64), ("num_actions", C.c_int32), ("use_clipped_value_loss", C.c_int32), ("mu", P), ("sigma", P),
+                ("value", P), ("actions", P), ("old_log_prob", P), ("advantages", P), ("target_values", P), ("returns", P), ("old_mu", P),
+                ("old_sigma", P), ("clip_param", C.c_float), ("value_loss_coef", C.c_float), ("entropy_coef", C.c_float), ("_pad", C.c_float),
+                ("grad_mu", P), ("grad_value", P), ("grad_sigma", P), ("out", P), ("sums", P), ("workspace", P), ("workspace_bytes", C.c_int64)]
+
+
+class GfAdamArgs(C.Structure):
+    _fields_ = [("numel", C.c_int64), ("params", P), ("grads", P), ("exp_avg", P), ("exp_avg_sq", P), ("state", P), ("kl_mean", P),
+                ("workspace", P), ("workspace_bytes", C.c_int64), ("desired_kl", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("max_grad_norm", C.c_float), ("schedule", C.c_int32), ("parity", C.c_int32), ("_pad", C.c_int32)]
+
+
 ABI_STRUCTS = [GfStepStats, GfActionArgs, GfContactArgs, GfTerminationArgs, GfRewardArgs, GfCommandArgs,
                GfResetArgs, GfObservationArgs, GfRotateArgs, GfSynthSceneArgs, GfTerm, GfObsItem, GfTerrainView, GfTerrainHeightArgs, GfGaitArgs, GfContactView, GfCommandView,
                GfPostRefs, GfRolloutArgs, GfHistoryUnrollArgs, GfRolloutPolicyArgs, GfGaeArgs, GfCompactArgs]
@@ -536,7 +570,8 @@ class HipBackend(Backend):
         self.lib.gf_minibatch_gather.restype = C.c_int
         self.lib.gf_minibatch_gather.argtypes = [C.POINTER(GfMinibatchArgs), C.c_void_p]
         # the two pieces of the collection loop (RolloutStorage.act / process_env_step): the same kind of entry points
-        for fn, idx, st in (("gf_policy_act", GF_SIZEOF_POLICY_ACT, GfPolicyActArgs), ("gf_episode_step", GF_SIZEOF_EPISODE, GfEpisodeArgs)):
+        for fn, idx, st in (("gf_policy_act", GF_SIZEOF_POLICY_ACT, GfPolicyActArgs), ("gf_episode_step", GF_SIZEOF_EPISODE, GfEpisodeArgs),
+                            ("gf_ppo_loss", GF_SIZEOF_PPO_LOSS, GfPpoLossArgs), ("gf_adam_step", GF_SIZEOF_ADAM, GfAdamArgs)):
             n = self.lib.gf_sizeof(idx)
             if n != C.sizeof(st):
                 raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")
@@ -586,6 +621,18 @@ class HipBackend(Backend):
         rc = self.lib.gf_episode_step(C.byref(args), self._stream())
         if rc != 0:
             self._raise("episode_step", rc)
+
+    def ppo_loss(self, args) -> None:
+        """gf_ppo_loss on the current stream (learner.PPO.update)."""
+        rc = self.lib.gf_ppo_loss(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("ppo_loss", rc)
+
+    def adam_step(self, args) -> None:
+        """gf_adam_step on the current stream (learner.PPO.update)."""
+        rc = self.lib.gf_adam_step(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("adam_step", rc)
 
     def run_ops(self, ops, n: int) -> None:
         failed = C.c_int(-1)

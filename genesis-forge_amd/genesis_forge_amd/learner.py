@@ -26,6 +26,10 @@ dependency and stays one; this module provides the two pieces of it that touch t
   it but the optimizer step.  This is the first place of the pipeline where xGMI bandwidth rather than latency matters.
 * :class:`ActorCriticMLP` — the policy of ``examples/*/train.py`` (ELU, hidden dims 512-256-128, learnable action std) as a
   plain torch module, so the two pieces above can be exercised without rsl_rl.
+* :class:`PPO` — rsl_rl's ``PPO.update`` for the ``"algorithm"`` dict of ``examples/*/train.py``: per minibatch the MLP forward /
+  backward stay in torch, the loss and its gradient w.r.t. the policy outputs are one ``gf_ppo_loss`` (two launches), the adaptive
+  learning rate, ``clip_grad_norm_`` and Adam over the flat gradient bucket are one ``gf_adam_step`` (two launches) — no host
+  synchronisation per minibatch; the three logged means are read once per update.
 """
 from __future__ import annotations
 
@@ -715,3 +719,237 @@ class GradientAllReduce:
 
         for p in self.params:
             dist.broadcast(p.data, src=src, group=self.group)
+
+
+# ---- the update: rsl_rl PPO.update ---------------------------------------------------------------------------------------------------
+_PPO_KEYS = ("clip_param", "desired_kl", "entropy_coef", "gamma", "lam", "learning_rate", "max_grad_norm", "num_learning_epochs",
+             "num_mini_batches", "schedule", "use_clipped_value_loss", "value_loss_coef")
+_PPO_DEFAULTS = dict(clip_param=0.2, desired_kl=0.01, entropy_coef=0.01, gamma=0.99, lam=0.95, learning_rate=0.001, max_grad_norm=1.0,
+                     num_learning_epochs=5, num_mini_batches=4, schedule="adaptive", use_clipped_value_loss=True, value_loss_coef=1.0)
+# rsl_rl keys whose default is all this class does: accepted with that value only
+_PPO_ONLY_DEFAULT = {"normalize_advantage_per_mini_batch": False, "rnd_cfg": None, "symmetry_cfg": None}
+_ADAM_BETAS, _ADAM_EPS = (0.9, 0.999), 1e-8   # torch.optim.Adam's defaults, as rsl_rl constructs it
+
+
+class PPO:
+    """rsl_rl's ``PPO`` (non-recurrent, no RND, no symmetry) over a :class:`RolloutStorage` and an :class:`ActorCriticMLP`.
+
+    ``PPO(policy, storage, **train_cfg["algorithm"])`` takes the dict of ``examples/*/train.py`` as written (``class_name`` is
+    ignored); unknown keys and unsupported values raise ``ValueError``.  ``grad_sync``: the :class:`GradientAllReduce` of a multi-rank
+    run (a one-rank bucket is made otherwise).  At construction the policy's trainable parameters move into ONE flat buffer in the
+    bucket's order (each ``p.data`` becomes a view of it) and the Adam state, the workspaces and the device control block (lr as a
+    double, the step) are allocated once.
+
+    Per minibatch ``update()`` zeroes the bucket, runs the actor / critic forward, ``gf_ppo_loss`` (the loss, its gradient w.r.t.
+    mu / value / std), back-propagates the kernel's gradients, all-reduces ``kl_mean`` over the ranks when there are several,
+    averages the bucket, and ``gf_adam_step`` (schedule, clipping, Adam) — no host synchronisation; the returned means are one read
+    at the end.  On a backend without these entry points (the test-only CPU oracle) the same arithmetic runs in torch."""
+
+    def __init__(self, policy: "ActorCriticMLP", storage: RolloutStorage, grad_sync: Optional[GradientAllReduce] = None, **algorithm):
+        algorithm = dict(algorithm)
+        algorithm.pop("class_name", None)
+        bad = [k for k in algorithm if k not in _PPO_KEYS and k not in _PPO_ONLY_DEFAULT]
+        if bad:
+            raise ValueError(f"PPO: unsupported algorithm keys {sorted(bad)}")
+        for k, want in _PPO_ONLY_DEFAULT.items():
+            if k in algorithm and algorithm[k] != want:
+                raise ValueError(f"PPO: {k}={algorithm[k]!r} is not supported (only {want!r})")
+        cfg = dict(_PPO_DEFAULTS, **{k: v for k, v in algorithm.items() if k in _PPO_KEYS})
+        if cfg["schedule"] not in ("adaptive", "fixed"):
+            raise ValueError(f"PPO: schedule={cfg['schedule']!r} is not supported ('adaptive' or 'fixed')")
+        if int(cfg["num_learning_epochs"]) < 1 or int(cfg["num_mini_batches"]) < 1:
+            raise ValueError("PPO: num_learning_epochs and num_mini_batches must be >= 1")
+        if not float(cfg["max_grad_norm"]) > 0.0:
+            raise ValueError(f"PPO: max_grad_norm={cfg['max_grad_norm']!r} must be > 0")
+        if cfg["schedule"] == "adaptive" and cfg["desired_kl"] is not None and not float(cfg["desired_kl"]) > 0.0:
+            raise ValueError(f"PPO: desired_kl={cfg['desired_kl']!r} must be > 0")
+        self.policy, self.storage = policy, storage
+        self.clip_param, self.entropy_coef, self.value_loss_coef = float(cfg["clip_param"]), float(cfg["entropy_coef"]), float(cfg["value_loss_coef"])
+        self.gamma, self.lam, self.max_grad_norm = float(cfg["gamma"]), float(cfg["lam"]), float(cfg["max_grad_norm"])
+        self.num_learning_epochs, self.num_mini_batches = int(cfg["num_learning_epochs"]), int(cfg["num_mini_batches"])
+        self.use_clipped_value_loss = bool(cfg["use_clipped_value_loss"])
+        self.schedule = cfg["schedule"]
+        self.desired_kl = None if cfg["desired_kl"] is None else float(cfg["desired_kl"])
+        self.adaptive = self.schedule == "adaptive" and self.desired_kl is not None   # (rsl_rl: `if desired_kl is not None and schedule == "adaptive"`)
+        std = getattr(policy, "std", None)
+        if not isinstance(std, torch.Tensor) or std.dim() != 1:
+            raise ValueError("PPO needs a policy with act_mean(), evaluate() and a [A] std parameter (ActorCriticMLP)")
+        self.num_actions = int(std.numel())
+        self.grad_sync = grad_sync if grad_sync is not None else GradientAllReduce(policy.parameters())
+        sync = self.grad_sync
+        ids = {id(p) for p in sync.params}
+        if any(p.requires_grad and id(p) not in ids for p in policy.parameters()) or id(std) not in ids:
+            raise ValueError("grad_sync must hold every trainable parameter of the policy")
+        # the parameters as views of one flat buffer, in the bucket's order
+        self.params = torch.empty_like(sync.bucket)
+        off = 0
+        with torch.no_grad():
+            for p in sync.params:
+                k = p.numel()
+                self.params[off:off + k].copy_(p.data.reshape(-1))
+                p.data = self.params[off:off + k].view_as(p)
+                off += k
+        dev = self.params.device
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        # device control block: GfAdamState[2] = {lr (double), step (int64)} x 2, read at parity, written at 1 - parity
+        self._state = torch.zeros(4, device=dev, dtype=torch.int64)
+        self._state_lr = self._state.view(torch.float64)
+        self._state_lr[0] = float(cfg["learning_rate"])
+        self._calls = 0
+        self._adam_ws = torch.zeros(max(1, nat.adam_workspace_bytes(self.params.numel()) // 8), device=dev, dtype=torch.float64)
+        self._out = torch.zeros(nat.GF_PPO_OUT_COUNT, device=dev, dtype=torch.float32)   # surrogate, value_loss, entropy, kl_mean, loss
+        self._sums = torch.zeros(3, device=dev, dtype=torch.float64)                      # value_function, surrogate, entropy
+        self._mb_key = None
+        self._loss_args, self._adam_args = nat.GfPpoLossArgs(), nat.GfAdamArgs()
+
+    @property
+    def learning_rate(self) -> float:
+        """The current learning rate (one host read)."""
+        return float(self._state_lr[2 * (self._calls & 1)])
+
+    def compute_returns(self, last_critic_obs: torch.Tensor) -> None:
+        """rsl_rl ``PPO.compute_returns``: the critic's value of the bootstrap observation, then GAE over the storage."""
+        with torch.no_grad():
+            last_values = self.policy.evaluate(last_critic_obs)
+        self.storage.compute_returns(last_values, gamma=self.gamma, lam=self.lam)
+
+    def update(self, generator: Optional[torch.Generator] = None) -> Dict[str, float]:
+        """``num_learning_epochs x num_mini_batches`` minibatches of ``storage.mini_batch_generator`` (``generator``: its randperm's);
+        returns rsl_rl 3.x's ``{"value_function", "surrogate", "entropy"}`` means — the one host read of the update."""
+        self._sums.zero_()
+        for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, generator=generator):
+            self._minibatch(batch)
+        vf, surr, ent = self._sums.tolist()
+        k = self.num_learning_epochs * self.num_mini_batches
+        return {"value_function": vf / k, "surrogate": surr / k, "entropy": ent / k}
+
+    # -- one minibatch ------------------------------------------------------------------------------------------------------------
+    def _minibatch(self, b: MiniBatch) -> None:
+        sync, policy = self.grad_sync, self.policy
+        sync.zero_grad()
+        mu = policy.act_mean(b.obs)
+        value = policy.evaluate(b.critic_obs)
+        backend = self.storage.env.backend
+        hip = getattr(backend, "ppo_loss", None) is not None   # (else the test-only oracle backend: rsl_rl's expression, autograd, torch Adam)
+        if hip:
+            gmu, gval = self._loss_hip(backend, mu, value, b)
+            torch.autograd.backward((mu, value), (gmu, gval.view_as(value)))
+        else:
+            self._loss_torch(mu, value, b)
+        self._reduce_kl()
+        sync.average()
+        sync.wait()
+        if hip:
+            self._adam_hip(backend)
+        else:
+            self._adam_torch()
+
+    def _reduce_kl(self) -> None:
+        """rsl_rl: with several ranks, ``all_reduce(kl_mean, SUM)`` then ``kl_mean /= world_size`` (every rank then takes the same lr)."""
+        sync = self.grad_sync
+        if not self.adaptive or (sync.world == 1 and not sync.force):
+            return
+        import torch.distributed as dist
+
+        kl = self._out[3:4]
+        dist.all_reduce(kl, op=dist.ReduceOp.SUM, group=sync.group)
+        kl.div_(sync.world)
+
+    def _buffers(self, mb: int):
+        key = (mb, self.num_actions)
+        if self._mb_key != key:
+            dev, A = self.params.device, self.num_actions
+            self._grad_mu = torch.empty((mb, A), device=dev, dtype=torch.float32)
+            self._grad_value = torch.empty((mb, 1), device=dev, dtype=torch.float32)
+            self._loss_ws = torch.empty(max(1, nat.ppo_loss_workspace_bytes(mb, A) // 8), device=dev, dtype=torch.float64)
+            self._mb_key = key
+        return self._grad_mu, self._grad_value
+
+    def _loss_hip(self, backend, mu, value, b: MiniBatch):
+        mb, A = int(b.actions.shape[0]), self.num_actions
+        std = self.policy.std
+        for name, t, shape in (("mu", mu, (mb, A)), ("value", value, (mb, 1))):
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"PPO: the policy's {name} must be a contiguous float32 {shape} tensor, not {tuple(t.shape)} {t.dtype}")
+        gmu, gval = self._buffers(mb)
+        a = self._loss_args
+        a.num_rows, a.num_actions, a.use_clipped_value_loss = mb, A, 1 if self.use_clipped_value_loss else 0
+        a.mu, a.sigma, a.value = mu.data_ptr(), std.data_ptr(), value.data_ptr()
+        a.actions, a.old_log_prob, a.advantages = b.actions.data_ptr(), b.old_log_prob.data_ptr(), b.advantages.data_ptr()
+        a.target_values, a.returns, a.old_mu, a.old_sigma = b.values.data_ptr(), b.returns.data_ptr(), b.old_mu.data_ptr(), b.old_sigma.data_ptr()
+        a.clip_param, a.value_loss_coef, a.entropy_coef = self.clip_param, self.value_loss_coef, self.entropy_coef
+        # d loss / d std goes straight into its slot of the (just zeroed) bucket: nothing in the graph of mu / value reaches std
+        a.grad_mu, a.grad_value, a.grad_sigma = gmu.data_ptr(), gval.data_ptr(), std.grad.data_ptr()
+        a.out, a.sums = self._out.data_ptr(), self._sums.data_ptr()
+        a.workspace, a.workspace_bytes = self._loss_ws.data_ptr(), self._loss_ws.numel() * 8
+        self._keep = (mu, value, b)
+        backend.ppo_loss(a)
+        return gmu, gval
+
+    def _adam_hip(self, backend) -> None:
+        a, par = self._adam_args, self._calls & 1
+        a.numel = self.params.numel()
+        a.params, a.grads, a.exp_avg, a.exp_avg_sq = (t.data_ptr() for t in (self.params, self.grad_sync.bucket, self.exp_avg, self.exp_avg_sq))
+        a.state = self._state.data_ptr()
+        a.kl_mean = self._out.data_ptr() + 3 * 4 if self.adaptive else None
+        a.workspace, a.workspace_bytes = self._adam_ws.data_ptr(), self._adam_ws.numel() * 8
+        a.desired_kl = self.desired_kl if self.adaptive else 0.0
+        a.beta1, a.beta2, a.eps = _ADAM_BETAS[0], _ADAM_BETAS[1], _ADAM_EPS
+        a.max_grad_norm = self.max_grad_norm
+        a.schedule = nat.GF_ADAM_SCHEDULE_ADAPTIVE if self.adaptive else nat.GF_ADAM_SCHEDULE_FIXED
+        a.parity = par
+        backend.adam_step(a)
+        self._calls += 1
+
+    # -- the same arithmetic in torch (backends without gf_ppo_loss / gf_adam_step) -------------------------------------------------
+    def _loss_torch(self, mu, value, b: MiniBatch) -> None:
+        """rsl_rl PPO.update's loss lines, ``loss.backward()``, and the values gf_ppo_loss leaves in ``out`` / ``sums``."""
+        std = self.policy.std
+        sigma = std.expand_as(mu)
+        dist = torch.distributions.Normal(mu, sigma, validate_args=False)   # (rsl_rl's ActorCritic turns validation off: no host read)
+        logp = dist.log_prob(b.actions).sum(dim=-1)
+        entropy = dist.entropy().sum(dim=-1)
+        with torch.no_grad():
+            kl = torch.sum(torch.log(sigma / b.old_sigma + 1.0e-5) + (torch.square(b.old_sigma) + torch.square(b.old_mu - mu))
+                           / (2.0 * torch.square(sigma)) - 0.5, dim=-1)
+            kl_mean = torch.mean(kl)
+        ratio = torch.exp(logp - torch.squeeze(b.old_log_prob))
+        surrogate = -torch.squeeze(b.advantages) * ratio
+        surrogate_clipped = -torch.squeeze(b.advantages) * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)
+        surrogate_loss = torch.max(surrogate, surrogate_clipped).mean()
+        v, tv, ret = value.reshape(-1), b.values, b.returns
+        if self.use_clipped_value_loss:
+            value_clipped = tv + (v - tv).clamp(-self.clip_param, self.clip_param)
+            value_loss = torch.max((v - ret).pow(2), (value_clipped - ret).pow(2)).mean()
+        else:
+            value_loss = (ret - v).pow(2).mean()
+        ent_mean = entropy.mean()
+        loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * ent_mean
+        loss.backward()
+        with torch.no_grad():
+            self._out.copy_(torch.stack([surrogate_loss, value_loss, ent_mean, kl_mean, loss]).to(torch.float32))
+            self._sums.add_(torch.stack([value_loss, surrogate_loss, ent_mean]).to(torch.float64))
+
+    def _adam_torch(self) -> None:
+        """The schedule, ``clip_grad_norm_`` and torch.optim.Adam's foreach arithmetic as tensor operations (no host read)."""
+        par = self._calls & 1
+        with torch.no_grad():
+            lr = self._state_lr[2 * par].clone()
+            if self.adaptive:
+                kl = self._out[3]   # (float32 against a Python float: compared in float32, as rsl_rl's `kl_mean > desired_kl * 2.0`)
+                down = torch.clamp(lr / 1.5, min=1e-5)
+                up = torch.clamp(lr * 1.5, max=1e-2)
+                lr = torch.where(kl > self.desired_kl * 2.0, down, torch.where((kl < self.desired_kl / 2.0) & (kl > 0.0), up, lr))
+            step = self._calls + 1
+            g = self.grad_sync.bucket
+            torch.nn.utils.clip_grad_norm_(self.grad_sync.params, self.max_grad_norm)
+            b1, b2 = _ADAM_BETAS
+            bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+            step_size = ((lr / bc1) * -1).to(torch.float32)
+            self.exp_avg.lerp_(g, 1 - b1)
+            self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
+            denom = (self.exp_avg_sq.sqrt() / (bc2 ** 0.5)).add_(_ADAM_EPS)
+            self.params.add_(step_size * (self.exp_avg / denom))
+            self._state_lr[2 * (1 - par)] = lr
+            self._state[2 * (1 - par) + 1] = step
+        self._calls += 1

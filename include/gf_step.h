@@ -787,6 +787,104 @@ typedef struct GfEpisodeArgs {
 } GfEpisodeArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * The PPO update (rsl_rl PPO.update, non-recurrent path without RND / symmetry).  Per minibatch rsl_rl evaluates the policy,
+ * builds the loss from a few dozen elementwise and reduction launches (and as many for their backward), clips the gradient
+ * norm, takes an Adam step and reads four scalars back to the host (the KL test of the adaptive schedule, three .item()).
+ * The MLP forward / backward stay in torch; the rest is two entry points that never synchronise:
+ *
+ * gf_ppo_loss — value and gradient of the minibatch loss for mb rows and A actions (sigma [A] shared by all rows):
+ *     logp_i   = left fold over a of  -((x - mu)^2) / (2 sigma^2) - log(sigma) - c       (Normal.log_prob order, as gf_policy_act)
+ *     entropy  = sum_a (0.5 + 0.5 log 2π + log sigma_a)                                  (identical for every row)
+ *     kl_i     = sum_a [log(sigma / old_sigma + 1e-5) + (old_sigma^2 + (old_mu - mu)^2) / (2 sigma^2) - 0.5]
+ *     ratio_i  = exp(logp_i - old_log_prob_i)
+ *     surrogate  = mean_i max(-adv·ratio, -adv·clamp(ratio, 1 - eps, 1 + eps))
+ *     value_loss = mean_i max((v - R)^2, (v_c - R)^2),  v_c = target + clamp(v - target, -eps, eps)   (clipped)
+ *                  mean_i (R - v)^2                                                                     (otherwise)
+ *     loss     = surrogate + value_loss_coef · value_loss - entropy_coef · entropy
+ * and d loss / d (mu, value, sigma) as torch autograd gives them (clamp passes the gradient at its bounds, a max tie sends half
+ * to each side, the KL carries none).  One lane per row, columns in groups of four (16-byte loads where A % 4 == 0 and every
+ * row is 16-byte aligned).  Every workgroup leaves 3 + A double partials (surrogate, value loss and KL sums, then the
+ * column sums of grad_sigma) in the caller's workspace; a second, one-workgroup launch sums them in a fixed order and writes
+ * grad_sigma, out[] and the running sums.  No float atomics, no hand-off between workgroups: bitwise reproducible.
+ *
+ * gf_adam_step — torch.nn.utils.clip_grad_norm_ then torch.optim.Adam (defaults: no weight decay, no amsgrad; foreach order)
+ * over one flat float32 parameter buffer and its flat gradient (the GradientAllReduce bucket):
+ *     adaptive schedule: kl > (float)(2·desired) -> lr = max(1e-5, lr / 1.5);  kl < (float)(desired / 2) and kl > 0 -> lr =
+ *                        min(1e-2, lr · 1.5)   (kl the float32 kl_mean; lr in double, as Python)
+ *     coef = min(1, max_norm / (||g||_2 + 1e-6));  g *= coef (written back, as clip_grad_norm_ leaves it)
+ *     m += (1 - b1)(g - m);  v = v·b2 + (1 - b2)·g·g;  p += (float)(-lr / bc1) · (m / (sqrt(v) / (float)sqrt(bc2) + eps))
+ *     with bc1 = 1 - b1^step, bc2 = 1 - b2^step in double.
+ * Launch 1 leaves per-workgroup partial sums of g^2 (double) in the workspace; launch 2 has every workgroup sum them in the
+ * same order (no hand-off), apply the schedule to state[parity] and update its elements; workgroup 0 writes state[1 - parity]
+ * (double-buffered by call parity, as GfEpisodeArgs.ring_state).
+ *
+ * Neither is a phase of the step.  Refusals (GF_E_NULL / GF_E_RANGE) launch nothing; mb == 0 / numel == 0 is a no-op.  No
+ * allocation, no copy, no synchronisation inside either entry point.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_PPO_BLOCK_ROWS 256          /* rows per workgroup of gf_ppo_loss: one partial record per workgroup */
+#define GF_PPO_OUT_COUNT 5             /* out[]: surrogate, value_loss, entropy, kl_mean, loss */
+/* workspace of gf_ppo_loss: (3 + A) doubles per workgroup of rows, 8-byte aligned */
+#define GF_PPO_LOSS_WORKSPACE_BYTES(mb, A) ((int64_t)(((mb) + GF_PPO_BLOCK_ROWS - 1) / GF_PPO_BLOCK_ROWS) * (3 + (int64_t)(A)) * 8)
+#define GF_ADAM_BLOCK_ELEMS 1024       /* elements per workgroup and pass of gf_adam_step (256 lanes x 4) */
+#define GF_ADAM_MAX_PARTIALS 1024      /* norm partials (workgroups of launch 1) at most */
+/* workspace of gf_adam_step: one double per launch-1 workgroup, 8-byte aligned */
+#define GF_ADAM_WORKSPACE_BYTES(numel) \
+    ((int64_t)((((numel) + GF_ADAM_BLOCK_ELEMS - 1) / GF_ADAM_BLOCK_ELEMS) < GF_ADAM_MAX_PARTIALS ? \
+               (((numel) + GF_ADAM_BLOCK_ELEMS - 1) / GF_ADAM_BLOCK_ELEMS) : GF_ADAM_MAX_PARTIALS) * 8)
+#define GF_ADAM_SCHEDULE_FIXED 0
+#define GF_ADAM_SCHEDULE_ADAPTIVE 1
+
+typedef struct GfPpoLossArgs {
+    int64_t num_rows;           /* mb >= 0; 0: nothing is launched */
+    int32_t num_actions;        /* A >= 1 */
+    int32_t use_clipped_value_loss;   /* 0 or 1 */
+    const float* mu;            /* [mb, A] actor mean of this update */
+    const float* sigma;         /* [A] action std (shared by every row) */
+    const float* value;         /* [mb] critic output of this update */
+    const float* actions;       /* [mb, A] minibatch actions */
+    const float* old_log_prob;  /* [mb] */
+    const float* advantages;    /* [mb] */
+    const float* target_values; /* [mb] values stored with the rollout */
+    const float* returns;       /* [mb] */
+    const float* old_mu;        /* [mb, A] */
+    const float* old_sigma;     /* [mb, A] */
+    float clip_param;
+    float value_loss_coef;
+    float entropy_coef;
+    float _pad;
+    float* grad_mu;             /* [mb, A] d loss / d mu, or NULL: no gradients (then all three are NULL) */
+    float* grad_value;          /* [mb] */
+    float* grad_sigma;          /* [A] */
+    float* out;                 /* [GF_PPO_OUT_COUNT] (required) */
+    double* sums;               /* [3] += value_loss, surrogate, entropy (rsl_rl's loss-dict order), or NULL */
+    void* workspace;            /* GF_PPO_LOSS_WORKSPACE_BYTES(mb, A) bytes, 8-byte aligned */
+    int64_t workspace_bytes;
+} GfPpoLossArgs;
+
+typedef struct GfAdamState {    /* device control block; GfAdamArgs.state points at two of them */
+    double lr;                  /* learning rate (double, as Python keeps it) */
+    int64_t step;               /* Adam steps taken */
+} GfAdamState;
+
+typedef struct GfAdamArgs {
+    int64_t numel;              /* >= 0; 0: nothing is launched */
+    float* params;              /* [numel] flat parameters, updated in place */
+    float* grads;               /* [numel] flat gradient; the clipped gradient is written back */
+    float* exp_avg;             /* [numel] */
+    float* exp_avg_sq;          /* [numel] */
+    GfAdamState* state;         /* [2]: slot `parity` is read, slot 1 - parity written */
+    const float* kl_mean;       /* the KL of the adaptive schedule (required with it, NULL with the fixed one) */
+    void* workspace;            /* GF_ADAM_WORKSPACE_BYTES(numel) bytes, 8-byte aligned */
+    int64_t workspace_bytes;
+    double desired_kl;          /* > 0 with the adaptive schedule */
+    double beta1, beta2, eps;   /* as Python holds them (torch defaults 0.9, 0.999, 1e-8): b^step in double, the rest rounded to f32 */
+    float max_grad_norm;        /* > 0 */
+    int32_t schedule;           /* GF_ADAM_SCHEDULE_FIXED / _ADAPTIVE */
+    int32_t parity;             /* 0 or 1 */
+    int32_t _pad;
+} GfAdamArgs;
+
+/* ------------------------------------------------------------------------------------------
  * History ring -> the reference's observation layout.  The reference keeps a list of H frames, pops the oldest, inserts the new
  * one in front and returns `torch.cat(self._history, dim=-1)` (observation_manager.py:219-226): every call writes a NEW
  * [N, H*O] tensor, newest frame first.  With the history kept as an in-place ring (GfObservationArgs.history_ring: the step
@@ -827,7 +925,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -852,6 +950,8 @@ int gf_gae(const GfGaeArgs* a, void* stream);                     /* returns and
 int gf_minibatch_gather(const GfMinibatchArgs* a, void* stream);  /* every field of one PPO minibatch in one launch (rsl_rl mini_batch_generator) */
 int gf_policy_act(const GfPolicyActArgs* a, void* stream);       /* Normal sample + log_prob + the policy's storage rows in one launch (rsl_rl PPO.act) */
 int gf_episode_step(const GfEpisodeArgs* a, void* stream);       /* time-out bootstrap + the runner's rewbuffer / lenbuffer upkeep (rsl_rl OnPolicyRunner.learn) */
+int gf_ppo_loss(const GfPpoLossArgs* a, void* stream);           /* minibatch loss + its gradient w.r.t. mu / value / sigma (rsl_rl PPO.update: the KL block, surrogate, value loss, loss, loss.backward() down to the policy outputs, the three .item()) */
+int gf_adam_step(const GfAdamArgs* a, void* stream);             /* adaptive lr + clip_grad_norm_ + Adam.step over the flat bucket (rsl_rl PPO.update: the lr schedule, nn.utils.clip_grad_norm_, optimizer.step()) */
 
 /* ------------------------------------------------------------------------------------------
  * Fused post-physics step: everything ManagedEnvironment.step() does after scene.step() and the

@@ -1,0 +1,144 @@
+"""One PPO update (num_learning_epochs x num_mini_batches = 5 x 4 minibatches) of the reference's training configs: rsl_rl's
+PPO.update restated in torch (tests/rsl_rl_ppo.py: torch.optim.Adam, clip_grad_norm_, the .item() calls) against learner.PPO
+(gf_ppo_loss + gf_adam_step, one host read per update).
+
+usage: python tools/bench_update.py [--sizes go2_cmd:4096,go2_cmd:16384,go2_cmd:65536,gait:4096] [--steps 24] [--reps 7]
+                                    [--forms rsl_rl,fused] [--out FILE]
+
+Per size: one rollout of T steps is collected with act / process_env_step by the reference policy (ELU MLPs 512-256-128, as
+examples/*/train.py) and its returns computed; then every rep runs each form once, alternating, from the same initial weights,
+a fresh optimizer state and the same minibatch stream (the generator's seed), so only the update differs.  A rep is timed with
+the host clock from a device synchronise to the device synchronise that ends it.  ``gait`` uses the gait trainer's asymmetric
+critic (obs_groups {"policy": ["policy"], "critic": ["policy", "critic"]}).  Prints one JSON line per size and form: best and
+median ms per update over the reps (after one warm-up update per form), and the losses of the last rep.
+``--synthetic``: random storage rows instead of a rollout — two such runs of one form under ``rocprofv3 --kernel-trace --stats``
+that differ only in ``--reps`` differ by exactly that many updates, which gives the dispatches per minibatch."""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "genesis-forge_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))   # the torch restatement of rsl_rl's update is test infrastructure
+
+import torch  # noqa: E402
+
+ALGO = dict(class_name="PPO", clip_param=0.2, desired_kl=0.01, entropy_coef=0.01, gamma=0.99, lam=0.95, learning_rate=0.001, max_grad_norm=1.0,
+            num_learning_epochs=5, num_mini_batches=4, schedule="adaptive", use_clipped_value_loss=True, value_loss_coef=1.0)
+GAIT_GROUPS = {"policy": ["policy"], "critic": ["policy", "critic"]}
+
+
+def rollout(config: str, n: int, T: int):
+    from genesis_forge_amd.learner import ActorCriticMLP, RolloutStorage
+    from genesis_forge_amd.tasks import BASELINE_CONFIGS
+
+    env = BASELINE_CONFIGS[config][1](n)
+    env.build()
+    env.seed(1)
+    obs, extras = env.reset()
+    groups = GAIT_GROUPS if config == "gait" else None
+    st = RolloutStorage(env, T, obs_groups=groups).attach()
+    st.begin(obs, extras)
+    st.seed(2)
+    A = env.action_space.shape[0]
+    critic = st.obs_groups["critic"]
+    critic_w = sum(st.group_rows[m].shape[2] for m in critic)
+    torch.manual_seed(0)
+    policy = ActorCriticMLP(st.obs_width, A).cuda()
+    if critic_w != st.obs_width:
+        policy.critic = ActorCriticMLP(critic_w, A).critic.cuda()
+    cat = lambda o, ex: o if critic == st.obs_groups["policy"] else torch.cat([ex["observations"][m] for m in critic], dim=-1)
+    for _ in range(T):
+        with torch.no_grad():
+            mean, values = policy.act_mean(obs), policy.evaluate(cat(obs, extras))
+        actions = st.act(mean, policy.std.detach(), values)
+        obs, _r, _te, tr, extras = env.step(actions)
+        st.process_env_step(tr)
+    with torch.no_grad():
+        st.compute_returns(policy.evaluate(cat(obs, extras)), gamma=ALGO["gamma"], lam=ALGO["lam"])
+    return env, st, policy
+
+
+def synthetic(config: str, n: int, T: int):
+    """A storage of random rows with the shapes of ``config`` and no env behind it (the dispatch-count runs: every launch of the
+    process then belongs to the set-up or to an update)."""
+    from types import SimpleNamespace
+
+    from genesis_forge_amd import _native as nat
+    from genesis_forge_amd.learner import ActorCriticMLP, RolloutStorage
+
+    obs_w, critic_w, A = (48, 0, 12) if config == "go2_cmd" else (52, 12, 12)   # (widths of the go2_cmd and gait configs' managers)
+    mk = lambda name, w: SimpleNamespace(name=name, observation_space=SimpleNamespace(shape=(w,)), output="fresh", _history_len=1, _unrolled=False)
+    mgrs = [mk("policy", obs_w)] + ([mk("critic", critic_w)] if critic_w else [])
+    env = SimpleNamespace(num_envs=n, managers={"observation": mgrs}, backend=nat.get_backend())
+    st = RolloutStorage(env, T, obs_groups=GAIT_GROUPS if critic_w else None)
+    st._ensure_policy_rows(A)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for t in [st.observations, *st.group_rows.values(), st.actions, st.values, st.advantages, st.returns, st.actions_log_prob, st.mu]:
+        t.copy_(torch.randn(t.shape, device="cuda", generator=g))
+    st.sigma.fill_(1.0)
+    st._returns_ready = True
+    torch.manual_seed(0)
+    policy = ActorCriticMLP(obs_w, A).cuda()
+    if critic_w:
+        policy.critic = ActorCriticMLP(obs_w + critic_w, A).critic.cuda()
+    return env, st, policy
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="go2_cmd:4096,go2_cmd:16384,go2_cmd:65536,gait:4096")
+    ap.add_argument("--steps", type=int, default=24)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--forms", default="rsl_rl,fused")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--synthetic", action="store_true", help="random storage rows, no env (dispatch counts under rocprofv3)")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_update.py measures on a ROCm GPU: none is visible")
+    from genesis_forge_amd.learner import PPO
+    from rsl_rl_ppo import RslRlPPO
+
+    forms = args.forms.split(",")
+    lines = []
+    for spec in args.sizes.split(","):
+        config, n = spec.split(":")
+        env, st, policy0 = (synthetic if args.synthetic else rollout)(config, int(n), args.steps)
+        init = copy.deepcopy(policy0.state_dict())
+        times = {f: [] for f in forms}
+        last = {}
+        for rep in range(args.reps + 1):   # rep 0: warm-up
+            for form in forms:
+                policy = copy.deepcopy(policy0)
+                policy.load_state_dict(init)
+                algo = PPO(policy, st, **ALGO) if form == "fused" else RslRlPPO(policy, st, **ALGO)
+                gen = torch.Generator(device="cuda").manual_seed(rep)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                losses = algo.update(generator=gen)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                if rep:
+                    times[form].append(dt * 1e3)
+                last[form] = (losses, algo.learning_rate)
+        mb = st.num_steps * st.env.num_envs // ALGO["num_mini_batches"]
+        for form in forms:
+            row = dict(config=config, num_envs=int(n), steps=args.steps, minibatch=mb, form=form, reps=args.reps,
+                       best_ms=round(min(times[form]), 3) if times[form] else None,
+                       median_ms=round(statistics.median(times[form]), 3) if times[form] else None,
+                       losses=last[form][0], lr=last[form][1], device=torch.cuda.get_device_name(0))
+            lines.append(row)
+            print(json.dumps(row), flush=True)
+        del env, st, policy0
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("".join(json.dumps(r) + "\n" for r in lines))
+
+
+if __name__ == "__main__":
+    main()

@@ -74,6 +74,7 @@ GF_EXPORT int gf_sizeof(int which) {
         case 25: return (int)sizeof(GfEpisodeArgs);
         case 26: return (int)sizeof(GfPpoLossArgs);
         case 27: return (int)sizeof(GfAdamArgs);
+        case 28: return (int)sizeof(GfMlpActArgs);
         default: return -1;
     }
 }

@@ -1,0 +1,337 @@
+// gf_mlp.hip — gf_mlp_act: the actor and critic MLPs of a collection step and gf_policy_act's sampling in one launch
+// (include/gf_step.h has the contract).  The first kernel of the library on the matrix cores: every other one is bandwidth- or
+// latency-bound, this one is 0.76 MFLOP per env.
+//
+// A workgroup of four waves owns kMlpRows = 32 rows of ONE net (blockIdx.y) and walks its layers.  Per layer y = x · Wᵀ + b runs on
+// v_mfma_f32_32x32x2_f32: A operand = the tile's activations (lane l holds x[l & 31][k + (l >> 5)]), B operand = Wᵀ (lane l holds
+// W[j0 + (l & 31)][k + (l >> 5)]), D = 32 rows x 32 output columns with the column on the lane.  Wave w owns the 32-column blocks
+// w, w + 4, w + 8, w + 12 of the layer — up to four independent accumulators, each started from the bias — and issues the k steps in
+// ascending order, so an output element is one k-ascending fma chain.
+//   * Activations stay in LDS (x: 32 rows x 513 floats; the odd stride keeps the 32 rows of a k column on 32 banks).  A layer reads
+//     x through its whole k loop into registers (the accumulators), the workgroup meets, and the ELU-ed outputs overwrite x: one
+//     buffer, never written to memory.  The first layer's input is copied from the segments into x, 512 columns at a time (the
+//     accumulators live through the passes).
+//   * Weights never touch LDS: a lane reads its own row of W along k — torch's layout is contiguous there — 16 bytes at a time, a
+//     whole chunk of k (32 … 128 columns, 64 registers per wave) ahead of its multiplications; where a wave has one or two output
+//     blocks a second chunk is in flight meanwhile.  The two lane halves of a wave read the two halves of a chunk, so a register
+//     holds column k in lanes 0–31 and column k + chunk / 2 in lanes 32–63; the MFMA wants k and k + 1 there: one v_permlane32_swap
+//     per register pair turns (k | k + c/2), (k + 1 | k + 1 + c/2) into (k | k + 1), (k + c/2 | k + 1 + c/2).  No barrier inside a
+//     layer: the waves only meet where x changes.  Rows whose start is not 16-byte aligned (in % 4 != 0) load by element.
+//   * Tails — rows past num_envs, k past `in`, output columns past `out` — are zeros (in x, or selected into the weight registers of
+//     the last chunk), never a branch around an MFMA.
+//   * The last layer's outputs land in x like any other; lane r < 32 of the workgroup then finishes row r: the actor workgroup stores
+//     `mean` and runs gf_policy_act's row (gf_policy_row.h) with the mean read from LDS, the critic workgroup stores the value.
+// LDS: 65 664 B, registers <= 256: two workgroups per CU, so one's barriers, ELU and load latency hide behind the other's MFMAs.
+#include "gf_launch.h"
+#include "gf_policy_row.h"
+
+namespace gf {
+
+constexpr int kMlpBlock = 256;
+constexpr int kMlpWaves = kMlpBlock / GF_WAVE;
+constexpr int kMlpRows = GF_MLP_TILE_ROWS;
+constexpr int kMlpXS = GF_MLP_MAX_HIDDEN + 1;   // row stride of the activations
+constexpr int kMlpMaxNB = GF_MLP_MAX_HIDDEN / 32 / kMlpWaves;   // 32-column blocks per wave at most
+// k columns per chunk for NB 32-column blocks per wave: a lane holds chunk / 2 of them per block — 64 registers (48 for NB = 3) — and a
+// chunk is 4 096 MFMA cycles per wave, which is what the next chunk's loads hide behind.  At least 32: a lane then reads 64 contiguous
+// bytes and a wave-instruction pair whole 128-byte lines.
+constexpr int mlp_kc(int nb) { return nb == 1 ? 128 : nb == 2 ? 64 : 32; }
+static_assert(kMlpRows == 32 && kMlpMaxNB == 4, "tile shape");
+static_assert(GF_MLP_MAX_ACTIONS <= GF_MLP_MAX_HIDDEN, "the last layer's outputs are kept like a hidden layer's");
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct MlpSmem {
+    float x[kMlpRows * kMlpXS];
+};
+
+// This lane's weights of a chunk: for block b, row j_b (rowoff = j_b · K), columns kl + (0 … KC / 2 - 1), kl = the chunk's first column
+// + lh · KC / 2.  FULL: the chunk lies inside `in`; otherwise an element past it loads the row's first and is zeroed (with VEC, K % 4
+// == 0, a quad is inside or outside as a whole).  Straight-line either way.  Rows past `out` read row 0: their columns are never stored.
+template <int NB, bool VEC, bool FULL>
+__device__ __forceinline__ void mlp_load_w(const GF_GLOBAL float* W, const uint32_t (&rowoff)[NB], int K, int kl, float (&r)[NB][mlp_kc(NB) / 2]) {
+    constexpr int H = mlp_kc(NB) / 2;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        if (VEC) {
+#pragma unroll
+            for (int e = 0; e < H; e += 4) {
+                const bool in = FULL || kl + e < K;
+                const f32x4 v = *reinterpret_cast<const GF_GLOBAL f32x4*>(W + (rowoff[b] + (uint32_t)(in ? kl + e : 0)));
+                r[b][e] = in ? v.x : 0.0f; r[b][e + 1] = in ? v.y : 0.0f; r[b][e + 2] = in ? v.z : 0.0f; r[b][e + 3] = in ? v.w : 0.0f;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < H; ++e) {
+                const bool in = FULL || kl + e < K;
+                const float v = W[rowoff[b] + (uint32_t)(in ? kl + e : 0)];
+                r[b][e] = in ? v : 0.0f;
+            }
+        }
+    }
+}
+
+template <int NB, bool VEC>
+__device__ __forceinline__ void mlp_load_chunk(const GF_GLOBAL float* W, const uint32_t (&rowoff)[NB], int K, int k, int lh, float (&r)[NB][mlp_kc(NB) / 2]) {
+    constexpr int KC = mlp_kc(NB);
+    if (k + KC <= K) mlp_load_w<NB, VEC, true>(W, rowoff, K, k + lh * (KC / 2), r);
+    else mlp_load_w<NB, VEC, false>(W, rowoff, K, k + lh * (KC / 2), r);
+}
+
+// the chunk's MFMAs: after the swap register 2m holds columns (2m | 2m + 1) of the chunk's first half, register 2m + 1 those of the second
+template <int NB>
+__device__ __forceinline__ void mlp_multiply(const float* ap, float (&r)[NB][mlp_kc(NB) / 2], f32x16 (&acc)[NB]) {
+    constexpr int H = mlp_kc(NB) / 2;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int m = 0; m < H; m += 2) {
+            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(r[b][m]), __float_as_uint(r[b][m + 1]), false, false);
+            r[b][m] = __uint_as_float(sw[0]);
+            r[b][m + 1] = __uint_as_float(sw[1]);
+        }
+    }
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+        for (int m = 0; m < H; m += 2) {
+            const float av = ap[half * H + m];   // x[li][k0 + half · H + m + lh]
+#pragma unroll
+            for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, r[b][m + half], acc[b], 0, 0, 0);
+        }
+    }
+}
+
+// columns [k0, k1) of the layer's k loop, x holding column k at x[row][k - xk0]
+template <int NB, bool VEC>
+__device__ __forceinline__ void mlp_k_loop(const MlpSmem& sm, const GF_GLOBAL float* W, const uint32_t (&rowoff)[NB], int K, int k0, int k1, int xk0, int li, int lh,
+                                           f32x16 (&acc)[NB]) {
+    constexpr int KC = mlp_kc(NB), H = KC / 2;
+    const float* ap = sm.x + li * kMlpXS + lh - xk0;
+    if constexpr (NB <= 2) {   // registers for two chunks: the one being multiplied and the one in flight, by turns
+        float ra[NB][H], rb[NB][H];
+        int k = k0;
+        mlp_load_chunk<NB, VEC>(W, rowoff, K, k, lh, ra);
+        for (;;) {
+            if (k + KC < k1) mlp_load_chunk<NB, VEC>(W, rowoff, K, k + KC, lh, rb);
+            mlp_multiply<NB>(ap + k, ra, acc);
+            k += KC;
+            if (k >= k1) break;
+            if (k + KC < k1) mlp_load_chunk<NB, VEC>(W, rowoff, K, k + KC, lh, ra);
+            mlp_multiply<NB>(ap + k, rb, acc);
+            k += KC;
+            if (k >= k1) break;
+        }
+    } else {   // one chunk (three or four accumulator tiles leave no room for two under 256 registers): its loads are issued as soon
+               // as the last MFMA of the previous chunk has read them, and the other workgroup of the CU multiplies meanwhile
+        float r[NB][H];
+        for (int k = k0; k < k1; k += KC) {
+            mlp_load_chunk<NB, VEC>(W, rowoff, K, k, lh, r);
+            mlp_multiply<NB>(ap + k, r, acc);
+        }
+    }
+}
+
+// One Linear layer (+ ELU unless `last`) of the tile: x (LDS, K columns; the segments when `first`) -> x (O columns, zeros up to the
+// next multiple of 32).  NB = 32-column blocks per wave: every wave multiplies NB blocks (the ones past `out` are not stored).
+template <int NB>
+__device__ __forceinline__ void mlp_layer(MlpSmem& sm, const GfMlpNet& net, const GfMlpLayer& L, const int K, const bool first, const bool last,
+                                          const int64_t row0, const int64_t N) {
+    constexpr int KC = mlp_kc(NB);
+    const int O = L.out_width;
+    const int CB = (O + 31) >> 5;
+    const bool vec = (K & 3) == 0 && (reinterpret_cast<uintptr_t>(L.weight) & 15u) == 0;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+
+    f32x16 acc[NB];
+    const GF_GLOBAL float* W = G(L.weight);
+    uint32_t rowoff[NB];   // (out · in <= 512 · 1 024: 32 bits)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int j = (wave + kMlpWaves * b) * 32 + li;
+        rowoff[b] = (uint32_t)(j < O ? j : 0) * (uint32_t)K;
+        const float bv = G(L.bias)[j < O ? j : 0];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[b][r] = j < O ? bv : 0.0f;   // (the column is on the lane: all 16 rows of it start from bias[j])
+    }
+
+    // the k loop, GF_MLP_MAX_HIDDEN columns of x at a time (a multiple of every chunk length; only a first layer has more)
+    for (int p0 = 0; p0 < K; p0 += GF_MLP_MAX_HIDDEN) {
+        const int cols = K - p0 < GF_MLP_MAX_HIDDEN ? K - p0 : GF_MLP_MAX_HIDDEN;
+        if (first) {   // the input from its segments: zeros past num_envs and past K up to the chunk's end
+            const int padded = (cols + KC - 1) / KC * KC;
+            if (p0) __syncthreads();   // (the previous pass is multiplied)
+            for (int e = (int)threadIdx.x; e < kMlpRows * padded; e += kMlpBlock) {
+                const int row = e / padded, col = e - row * padded;
+                const int64_t n = row0 + row;
+                int k = p0 + col;
+                const bool in = n < N && col < cols;
+                const float* rows = net.inputs[0].rows;
+                int64_t off = 0;
+#pragma unroll
+                for (int s = 0; s < GF_MLP_MAX_INPUTS; ++s) {
+                    const int w = s < net.num_inputs ? net.inputs[s].width : 0;
+                    const bool hit = in && k >= 0 && k < w;
+                    rows = hit ? net.inputs[s].rows : rows;
+                    off = hit ? n * w + k : off;
+                    k -= w;
+                }
+                const float v = G(rows)[off];
+                sm.x[row * kMlpXS + col] = in ? v : 0.0f;
+            }
+            __syncthreads();
+        }
+        if (vec) mlp_k_loop<NB, true>(sm, W, rowoff, K, p0, p0 + cols, p0, li, lh, acc);
+        else mlp_k_loop<NB, false>(sm, W, rowoff, K, p0, p0 + cols, p0, li, lh, acc);
+    }
+    __syncthreads();   // every wave is done reading x
+
+    // out columns, then zeros up to the longest chunk the next layer may read to (its k tail multiplies them by zero weights)
+    const int padded = (O + 127) / 128 * 128 < GF_MLP_MAX_HIDDEN ? (O + 127) / 128 * 128 : GF_MLP_MAX_HIDDEN;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int cb = wave + kMlpWaves * b;
+        if (cb >= CB) continue;   // (wave-uniform)
+        const bool real = cb * 32 + li < O;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            float v = acc[b][r];
+            if (!last) v = v > 0.0f ? v : expm1f(v);
+            sm.x[row * kMlpXS + cb * 32 + li] = real ? v : 0.0f;
+        }
+    }
+    for (int e = (int)threadIdx.x; e < kMlpRows * (padded - CB * 32); e += kMlpBlock) {
+        const int w = padded - CB * 32, row = e / w;
+        sm.x[row * kMlpXS + CB * 32 + (e - row * w)] = 0.0f;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArgs a, const int first_net, const int vec_rows) {
+    __shared__ MlpSmem sm;
+    const bool is_critic = (int)blockIdx.y + first_net == 1;
+    const GfMlpNet& net = is_critic ? a.critic : a.actor;
+    const int64_t N = a.num_envs;
+    const int64_t row0 = (int64_t)blockIdx.x * kMlpRows;
+
+    int K = 0;
+    for (int s = 0; s < net.num_inputs; ++s) K += net.inputs[s].width;
+    const int layers = net.num_layers;
+    for (int l = 0; l < layers; ++l) {
+        const GfMlpLayer& L = net.layers[l];
+        const int nb = (((L.out_width + 31) >> 5) + kMlpWaves - 1) / kMlpWaves;
+        const bool first = l == 0, last = l == layers - 1;
+        if (nb == 1) mlp_layer<1>(sm, net, L, K, first, last, row0, N);
+        else if (nb == 2) mlp_layer<2>(sm, net, L, K, first, last, row0, N);
+        else if (nb == 3) mlp_layer<3>(sm, net, L, K, first, last, row0, N);
+        else mlp_layer<4>(sm, net, L, K, first, last, row0, N);
+        K = L.out_width;
+    }
+
+    // one lane per row finishes it from the outputs in x
+    const int r = (int)threadIdx.x;
+    const int64_t n = row0 + r;
+    if (r >= kMlpRows || n >= N) return;
+    const float* out = sm.x + r * kMlpXS;
+    if (is_critic) {
+        const float v = out[0];
+        if (a.values) G(a.values)[n] = v;
+        if (a.values_out) G(a.values_out)[n] = v;
+        return;
+    }
+    const int A = K;
+    if (a.mean) {
+        GF_GLOBAL float* m = G(a.mean) + n * A;
+        for (int c = 0; c < A; ++c) m[c] = out[c];
+    }
+    if (!a.actions) return;
+    GfPolicyActArgs p;
+    p.num_envs = N;
+    p.num_actions = A;
+    p.std_per_env = a.std_per_env;
+    p.mean = nullptr;
+    p.std = a.std;
+    p.values = nullptr;
+    p.noise = a.noise;
+    p.seed = a.seed;
+    p.stream = a.stream;
+    p.env_offset = a.env_offset;
+    p._pad = 0;
+    p.actions = a.actions;
+    p.actions_out = a.actions_out;
+    p.mu_out = a.mu_out;
+    p.sigma_out = a.sigma_out;
+    p.values_out = nullptr;   // (the critic workgroup's)
+    p.log_prob_out = a.log_prob_out;
+    const auto load_mean = [&](int c0, float (&m)[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m[k] = out[c0 + k];   // (columns past A: zeros, or x's finite leftovers — never folded or stored)
+    };
+    if (vec_rows) policy_act_row<true>(p, n, load_mean);
+    else policy_act_row<false>(p, n, load_mean);
+}
+
+// GF_OK and the net's widths, or the refusal
+static int mlp_check_net(const GfMlpNet& net, bool critic, int* out_width) {
+    if (net.num_layers < 0 || net.num_layers > GF_MLP_MAX_LAYERS) return GF_E_RANGE;
+    if (net.num_layers == 0) return GF_OK;
+    if (net.num_inputs < 1 || net.num_inputs > GF_MLP_MAX_INPUTS) return GF_E_RANGE;
+    int64_t in = 0;
+    for (int s = 0; s < net.num_inputs; ++s) {
+        if (!net.inputs[s].rows) return GF_E_NULL;
+        if (net.inputs[s].width < 1) return GF_E_RANGE;
+        in += net.inputs[s].width;
+    }
+    if (in > GF_MLP_MAX_INPUT_WIDTH) return GF_E_RANGE;
+    for (int l = 0; l < net.num_layers; ++l) {
+        const GfMlpLayer& L = net.layers[l];
+        if (!L.weight || !L.bias) return GF_E_NULL;
+        if (L.out_width < 1) return GF_E_RANGE;
+        if (l < net.num_layers - 1) {
+            if (L.out_width > GF_MLP_MAX_HIDDEN) return GF_E_RANGE;
+        } else if (critic) {
+            if (L.out_width != 1) return GF_E_UNSUPPORTED;
+        } else if (L.out_width > GF_MLP_MAX_ACTIONS) {
+            return GF_E_RANGE;
+        }
+    }
+    *out_width = net.layers[net.num_layers - 1].out_width;
+    return GF_OK;
+}
+
+}  // namespace gf
+
+extern "C" __attribute__((visibility("default"))) int gf_mlp_act(const GfMlpActArgs* a, void* stream) {
+    if (!a) return GF_E_NULL;
+    if (a->num_envs < 0 || (a->std_per_env != 0 && a->std_per_env != 1)) return GF_E_RANGE;
+    int A = 0, one = 0;
+    int rc = gf::mlp_check_net(a->actor, false, &A);
+    if (rc != GF_OK) return rc;
+    rc = gf::mlp_check_net(a->critic, true, &one);
+    if (rc != GF_OK) return rc;
+    const bool actor = a->actor.num_layers > 0, critic = a->critic.num_layers > 0;
+    if (!actor && !critic) return GF_E_UNSUPPORTED;
+    if (actor) {
+        if (!a->mean && !a->actions) return GF_E_NULL;
+        if (a->actions && !a->std) return GF_E_NULL;
+        if (!a->actions && (a->actions_out || a->mu_out || a->sigma_out || a->log_prob_out)) return GF_E_NULL;
+    } else if (a->mean || a->actions || a->actions_out || a->mu_out || a->sigma_out || a->log_prob_out) {
+        return GF_E_NULL;
+    }
+    if (critic) {
+        if (!a->values && !a->values_out) return GF_E_NULL;
+    } else if (a->values || a->values_out) {
+        return GF_E_NULL;
+    }
+    if (a->num_envs == 0) return GF_OK;
+    const int64_t tiles = (a->num_envs + gf::kMlpRows - 1) / gf::kMlpRows;
+    if (tiles > 0x7fffffff) return GF_E_RANGE;
+    uintptr_t bits = 0;
+    const void* rows[] = {a->noise, a->actions, a->actions_out, a->mu_out, a->sigma_out, a->std};
+    for (const void* p : rows) bits |= reinterpret_cast<uintptr_t>(p);
+    const int vec_rows = (bits & 15u) == 0 && (A & 3) == 0;
+    gf::klaunch(gf::mlp_act_kernel, dim3((unsigned)tiles, actor && critic ? 2u : 1u), dim3(gf::kMlpBlock), 0, (hipStream_t)stream, *a,
+                actor ? 0 : 1, vec_rows);
+    return gf::launch_status();
+}

@@ -375,6 +375,35 @@ class GfAdamArgs(C.Structure):
                 ("eps", C.c_double), ("max_grad_norm", C.c_float), ("schedule", C.c_int32), ("parity", C.c_int32), ("_pad", C.c_int32)]
 
 
+# the actor-critic forward of a collection step (learner.PolicyForward / RolloutStorage.act_policy): gf_mlp_act, not in ABI_STRUCTS either
+GF_SIZEOF_MLP_ACT = 28
+GF_MLP_MAX_LAYERS = 6
+GF_MLP_MAX_INPUTS = 4
+GF_MLP_MAX_HIDDEN = 512
+GF_MLP_MAX_INPUT_WIDTH = 1024
+GF_MLP_MAX_ACTIONS = 64
+GF_MLP_TILE_ROWS = 32
+
+
+class GfMlpSegment(C.Structure):
+    _fields_ = [("rows", P), ("width", C.c_int32), ("_pad", C.c_int32)]
+
+
+class GfMlpLayer(C.Structure):
+    _fields_ = [("weight", P), ("bias", P), ("out_width", C.c_int32), ("_pad", C.c_int32)]
+
+
+class GfMlpNet(C.Structure):
+    _fields_ = [("num_layers", C.c_int32), ("num_inputs", C.c_int32), ("inputs", GfMlpSegment * GF_MLP_MAX_INPUTS),
+                ("layers", GfMlpLayer * GF_MLP_MAX_LAYERS)]
+
+
+class GfMlpActArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("actor", GfMlpNet), ("critic", GfMlpNet), ("std", P), ("noise", P), ("seed", C.c_uint64),
+                ("stream", C.c_uint64), ("env_offset", C.c_uint32), ("std_per_env", C.c_int32), ("mean", P), ("values", P), ("actions", P),
+                ("actions_out", P), ("mu_out", P), ("sigma_out", P), ("values_out", P), ("log_prob_out", P)]
+
+
 ABI_STRUCTS = [GfStepStats, GfActionArgs, GfContactArgs, GfTerminationArgs, GfRewardArgs, GfCommandArgs,
                GfResetArgs, GfObservationArgs, GfRotateArgs, GfSynthSceneArgs, GfTerm, GfObsItem, GfTerrainView, GfTerrainHeightArgs, GfGaitArgs, GfContactView, GfCommandView,
                GfPostRefs, GfRolloutArgs, GfHistoryUnrollArgs, GfRolloutPolicyArgs, GfGaeArgs, GfCompactArgs]
@@ -571,7 +600,8 @@ class HipBackend(Backend):
         self.lib.gf_minibatch_gather.argtypes = [C.POINTER(GfMinibatchArgs), C.c_void_p]
         # the two pieces of the collection loop (RolloutStorage.act / process_env_step): the same kind of entry points
         for fn, idx, st in (("gf_policy_act", GF_SIZEOF_POLICY_ACT, GfPolicyActArgs), ("gf_episode_step", GF_SIZEOF_EPISODE, GfEpisodeArgs),
-                            ("gf_ppo_loss", GF_SIZEOF_PPO_LOSS, GfPpoLossArgs), ("gf_adam_step", GF_SIZEOF_ADAM, GfAdamArgs)):
+                            ("gf_ppo_loss", GF_SIZEOF_PPO_LOSS, GfPpoLossArgs), ("gf_adam_step", GF_SIZEOF_ADAM, GfAdamArgs),
+                            ("gf_mlp_act", GF_SIZEOF_MLP_ACT, GfMlpActArgs)):
             n = self.lib.gf_sizeof(idx)
             if n != C.sizeof(st):
                 raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")
@@ -633,6 +663,12 @@ class HipBackend(Backend):
         rc = self.lib.gf_adam_step(C.byref(args), self._stream())
         if rc != 0:
             self._raise("adam_step", rc)
+
+    def mlp_act(self, args) -> None:
+        """gf_mlp_act on the current stream (learner.PolicyForward, learner.RolloutStorage.act_policy)."""
+        rc = self.lib.gf_mlp_act(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("mlp_act", rc)
 
     def run_ops(self, ops, n: int) -> None:
         failed = C.c_int(-1)

@@ -20,6 +20,8 @@ dependency and stays one; this module provides the two pieces of it that touch t
   ``gf_policy_act``, and ``process_env_step`` bootstraps the time-outs and keeps the runner's episode statistics
   (:class:`EpisodeStatistics`: ``rewbuffer`` / ``lenbuffer`` without the per-step ``nonzero()`` and ``.cpu()``) with
   ``gf_episode_step``.
+  ``act_policy`` takes the observations instead of the network outputs: the actor and critic forward passes of a
+  :class:`PolicyForward` run inside the same launch (``gf_mlp_act``: f32 MFMA, activations in LDS, weights read in place).
 * :class:`GradientAllReduce` — the multi-GPU half: every rank owns a shard of envs and a replica of the policy; after
   ``backward()`` the gradients of all parameters are averaged with ONE all-reduce over a flat bucket (RCCL over xGMI on GPUs;
   the 512-256-128 actor + critic MLPs of the reference configs are 1.5 MB), overlapped with nothing because nothing follows
@@ -348,6 +350,55 @@ class RolloutStorage:
         self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
         return actions
 
+    def act_policy(self, forward: "PolicyForward", obs, critic_obs=None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``act(policy.act_mean(obs), policy.std, policy.evaluate(critic_obs), noise)`` with the two forward passes inside the launch:
+        ONE ``gf_mlp_act`` runs the actor and the critic MLP of ``forward`` (a :class:`PolicyForward`) on the f32 matrix cores, samples
+        and writes the policy's rows — instead of torch's GEMM and ELU launch per layer and ``gf_policy_act`` behind them.  The row, the
+        noise stream and seed, and the input rules are ``act``'s: a loop that replaces ``store.act(policy.act_mean(obs), policy.std,
+        policy.evaluate(obs))`` by ``store.act_policy(fwd, obs)`` draws the same noise.  ``obs`` / ``critic_obs``: a ``[N, W]`` tensor
+        or a sequence of up to four (the members of an observation group side by side — no ``torch.cat``); ``critic_obs=None``: the
+        critic reads ``obs``.  The mean and the value are k-ascending f32 fma chains (``gf_step.h``), not torch's GEMM bits: within
+        f32 rounding of ``policy.act_mean`` / ``evaluate``, and the same for a row whatever ``num_envs`` is.
+        Measured per collection step (profiles/r09_mlp_act.md): 3.5 x faster than ``act()`` on torch's forward at 4 096 envs, 1.4 x
+        at 16 384, but 7 % SLOWER at 65 536 envs, where the large GEMMs win: there ``act()`` with the torch forward is the call to use.
+        On a backend without ``gf_mlp_act`` (the test-only CPU oracle) this is exactly the ``act`` call above under ``no_grad``, and
+        ``noise`` is required."""
+        if not isinstance(forward, PolicyForward):
+            raise ValueError("act_policy(forward, ...) takes a PolicyForward")
+        n, dev = self.env.num_envs, self.observations.device
+        if forward.actor is None or forward.critic is None or forward.num_actions is None:
+            raise ValueError("act_policy needs a policy with an actor, a critic and a [A] std")
+        segs = forward._segments(obs, forward.actor, "obs", n, dev)
+        csegs = forward._segments(obs if critic_obs is None else critic_obs, forward.critic, "obs (the critic's input)" if critic_obs is None else "critic_obs", n, dev)
+        A = forward.num_actions
+        std = forward.policy.std
+        fn = getattr(self.env.backend, "mlp_act", None)
+        if fn is None:   # (the test-only oracle backend) today's path, bit for bit
+            cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+            with torch.no_grad():
+                return self.act(forward.policy.act_mean(cat(segs)), std.detach(), forward.policy.evaluate(cat(csegs)), noise)
+        _check_f32(std, "policy.std", {(A,)}, dev)
+        if noise is not None:
+            _check_f32(noise, "noise", {(n, A)}, dev)
+        t = 0 if self.full else self.step
+        self._ensure_policy_rows(A)
+        actions = torch.empty((n, A), device=dev, dtype=torch.float32)
+        stream = self._act_stream
+        self._act_stream += 1
+        a = forward._fill(n, segs, csegs)
+        a.std, a.std_per_env = std.data_ptr(), 0
+        a.noise = None if noise is None else noise.data_ptr()
+        a.seed = self.env._rng_seed if self._act_seed is None else self._act_seed
+        a.stream, a.env_offset = stream, int(getattr(self.env, "env_offset", 0))
+        a.mean = a.values = None
+        a.actions = actions.data_ptr()
+        a.actions_out, a.mu_out, a.sigma_out = (x.data_ptr() + t * x.stride(0) * 4 for x in (self.actions, self.mu, self.sigma))
+        a.values_out, a.log_prob_out = (x.data_ptr() + t * x.stride(0) * 4 for x in (self.values, self.actions_log_prob))
+        self._keep_act = (segs, csegs, noise)
+        fn(a)
+        self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
+        return actions
+
     def _act_torch(self, mean, std, values, noise, actions, t) -> None:
         with torch.no_grad():
             sd = std.expand_as(mean)
@@ -410,7 +461,9 @@ class RolloutStorage:
 
     def compute_returns(self, last_values: torch.Tensor, gamma: float = 0.99, lam: float = 0.95, normalize: bool = True) -> None:
         """``returns`` / ``advantages`` of the finished rollout (rsl_rl ``RolloutStorage.compute_returns``; gamma / lam as
-        examples/simple/train.py:41-47) — GAE over the T steps, then ``(adv - mean) / (std + 1e-8)`` over all T*N entries."""
+        examples/simple/train.py:41-47) — GAE over the T steps, then ``(adv - mean) / (std + 1e-8)`` over all T*N entries.
+        ``last_values``: the critic's value of the bootstrap observation — ``policy.evaluate(last_obs)``, or one launch with
+        ``PolicyForward(policy).value(last_obs)``."""
         if self.values is None:
             raise RuntimeError("compute_returns() needs the value estimates: call add_policy() for every transition")
         last_values = last_values.reshape(-1).to(torch.float32).contiguous()
@@ -657,6 +710,137 @@ class ActorCriticMLP(torch.nn.Module):
         return self.critic(obs)
 
 
+class PolicyForward:
+    """The actor and critic of a policy as ``gf_mlp_act`` reads them: one launch per forward pass, weights read in place.
+
+    ``policy.actor`` / ``policy.critic`` (either may be missing or ``None``) must be ``nn.Sequential`` of ``Linear`` layers with
+    ``ELU(alpha=1)`` between them and nothing after the last, float32, contiguous, within the kernel's limits (hidden widths <= 512,
+    input <= 1 024, actor output <= 64, critic output 1, at most 6 ``Linear``): anything else raises ``ValueError`` naming it.  Only the
+    structure is kept: the weight addresses are read from the parameters at every call, so a ``PolicyForward`` made before a
+    :class:`PPO` (which re-seats every ``p.data`` into its flat buffer and updates it in place) sees the current weights.
+
+    ``mean(obs)`` / ``value(critic_obs)``: play-time inference and the bootstrap value, one launch each, fresh tensors;
+    ``RolloutStorage.act_policy(forward, obs)``: the collection step.  An observation is a ``[N, W]`` tensor or a sequence of up to
+    four whose widths add up to the first layer's input (an observation group's members, no ``torch.cat``)."""
+
+    def __init__(self, policy):
+        self.policy = policy
+        self.actor = self._walk(getattr(policy, "actor", None), "actor", nat.GF_MLP_MAX_ACTIONS)
+        self.critic = self._walk(getattr(policy, "critic", None), "critic", 1)
+        if self.actor is None and self.critic is None:
+            raise ValueError("PolicyForward: the policy has neither an actor nor a critic")
+        std = getattr(policy, "std", None)
+        self.num_actions = None
+        if self.actor is not None and isinstance(std, torch.Tensor):
+            A = self.actor[-1][0].shape[0]
+            if std.dtype != torch.float32 or tuple(std.shape) != (A,):
+                raise ValueError(f"PolicyForward: policy.std must be a float32 [{A}] tensor, not {std.dtype} {tuple(std.shape)}")
+            self.num_actions = int(A)
+        self._args = nat.GfMlpActArgs()
+
+    @staticmethod
+    def _walk(net, name: str, max_out: int):
+        """[(weight, bias)] of the net's Linear layers (the Parameter objects: their storage may be re-seated later), or None."""
+        if net is None:
+            return None
+        if not isinstance(net, torch.nn.Sequential) or len(net) == 0:
+            raise ValueError(f"PolicyForward: policy.{name} must be a non-empty nn.Sequential of Linear and ELU")
+        layers = []
+        for i, m in enumerate(net):
+            if i % 2 == 0:
+                if not isinstance(m, torch.nn.Linear):
+                    raise ValueError(f"PolicyForward: policy.{name}[{i}] is {type(m).__name__}; expected Linear")
+                if m.bias is None:
+                    raise ValueError(f"PolicyForward: policy.{name}[{i}] has no bias")
+                for p, what in ((m.weight, "weight"), (m.bias, "bias")):
+                    if p.dtype != torch.float32:
+                        raise ValueError(f"PolicyForward: policy.{name}[{i}].{what} is {p.dtype}; the kernel reads float32")
+                    if not p.is_contiguous():
+                        raise ValueError(f"PolicyForward: policy.{name}[{i}].{what} is not contiguous")
+                layers.append((m.weight, m.bias))
+            elif not isinstance(m, torch.nn.ELU) or float(m.alpha) != 1.0:
+                what = f"ELU(alpha={m.alpha})" if isinstance(m, torch.nn.ELU) else type(m).__name__
+                raise ValueError(f"PolicyForward: policy.{name}[{i}] is {what}; only ELU(alpha=1) between Linear layers is supported")
+        if len(net) % 2 == 0:
+            raise ValueError(f"PolicyForward: policy.{name} ends in an activation; the last module must be a Linear")
+        if len(layers) > nat.GF_MLP_MAX_LAYERS:
+            raise ValueError(f"PolicyForward: policy.{name} has {len(layers)} Linear layers; at most {nat.GF_MLP_MAX_LAYERS}")
+        if layers[0][0].shape[1] > nat.GF_MLP_MAX_INPUT_WIDTH:
+            raise ValueError(f"PolicyForward: policy.{name} reads {layers[0][0].shape[1]} inputs; at most {nat.GF_MLP_MAX_INPUT_WIDTH}")
+        for i, (w, _b) in enumerate(layers[:-1]):
+            if w.shape[0] > nat.GF_MLP_MAX_HIDDEN:
+                raise ValueError(f"PolicyForward: policy.{name} has a hidden layer of width {w.shape[0]}; at most {nat.GF_MLP_MAX_HIDDEN}")
+        out = layers[-1][0].shape[0]
+        if name == "critic" and out != 1:
+            raise ValueError(f"PolicyForward: policy.critic has {out} outputs; the value is one")
+        if out > max_out:
+            raise ValueError(f"PolicyForward: policy.{name} has {out} outputs; at most {max_out}")
+        return layers
+
+    @staticmethod
+    def _segments(obs, layers, name: str, n: Optional[int], dev) -> tuple:
+        """``obs`` as the tuple of ``[n, w]`` float32 contiguous segments the first layer of ``layers`` reads side by side."""
+        parts = (obs,) if isinstance(obs, torch.Tensor) else tuple(obs) if isinstance(obs, (list, tuple)) else None
+        if not parts or len(parts) > nat.GF_MLP_MAX_INPUTS:
+            raise ValueError(f"{name} must be a tensor or a sequence of 1 to {nat.GF_MLP_MAX_INPUTS} tensors")
+        for i, x in enumerate(parts):
+            if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] < 1:
+                raise ValueError(f"{name}[{i}] must be a [N, W] tensor" if len(parts) > 1 else f"{name} must be a [N, W] tensor")
+            if n is None:
+                n, dev = int(x.shape[0]), x.device
+            _check_f32(x, f"{name}[{i}]" if len(parts) > 1 else name, {(n, int(x.shape[1]))}, dev)
+        want = int(layers[0][0].shape[1])
+        if sum(int(x.shape[1]) for x in parts) != want:
+            raise ValueError(f"{name} is {' + '.join(str(int(x.shape[1])) for x in parts)} wide; the first layer reads {want}")
+        if layers[0][0].device != parts[0].device:
+            raise ValueError(f"{name} lives on {parts[0].device}, the policy on {layers[0][0].device}")
+        return parts
+
+    @staticmethod
+    def _fill_net(net, layers, parts) -> None:
+        if layers is None or parts is None:
+            net.num_layers = 0
+            return
+        net.num_layers, net.num_inputs = len(layers), len(parts)
+        for seg, x in zip(net.inputs, parts):
+            seg.rows, seg.width = x.data_ptr(), x.shape[1]
+        for lay, (w, b) in zip(net.layers, layers):
+            lay.weight, lay.bias, lay.out_width = w.data_ptr(), b.data_ptr(), w.shape[0]
+
+    def _fill(self, n: int, actor_parts, critic_parts):
+        """The descriptor with both nets pointed at the current weights and the given inputs (None: that net is left out)."""
+        a = self._args
+        a.num_envs = n
+        self._fill_net(a.actor, self.actor, actor_parts)
+        self._fill_net(a.critic, self.critic, critic_parts)
+        return a
+
+    def _one(self, obs, layers, name: str, torch_fn) -> torch.Tensor:
+        if layers is None:
+            raise ValueError(f"PolicyForward: the policy has no {name}")
+        parts = self._segments(obs, layers, "obs", None, None)
+        fn = getattr(nat.get_backend(), "mlp_act", None)
+        if fn is None:   # (the test-only oracle backend)
+            with torch.no_grad():
+                return torch_fn(parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1))
+        n = int(parts[0].shape[0])
+        out = torch.empty((n, int(layers[-1][0].shape[0])), device=parts[0].device, dtype=torch.float32)
+        a = self._fill(n, parts if name == "actor" else None, parts if name == "critic" else None)
+        a.std = a.noise = a.actions = a.actions_out = a.mu_out = a.sigma_out = a.values_out = a.log_prob_out = None
+        a.mean, a.values = (out.data_ptr(), None) if name == "actor" else (None, out.data_ptr())
+        self._keep = (parts, out)
+        fn(a)
+        return out
+
+    def mean(self, obs) -> torch.Tensor:
+        """The actor's output ``[N, A]`` (``policy.act_mean(obs)``): one launch, a fresh tensor."""
+        return self._one(obs, self.actor, "actor", self.policy.actor)
+
+    def value(self, critic_obs) -> torch.Tensor:
+        """The critic's output ``[N, 1]`` (``policy.evaluate(critic_obs)``): one launch, a fresh tensor."""
+        return self._one(critic_obs, self.critic, "critic", self.policy.critic)
+
+
 class GradientAllReduce:
     """Average the gradients of ``params`` over the ranks of ``group`` with one collective.
 
@@ -808,7 +992,9 @@ class PPO:
         return float(self._state_lr[2 * (self._calls & 1)])
 
     def compute_returns(self, last_critic_obs: torch.Tensor) -> None:
-        """rsl_rl ``PPO.compute_returns``: the critic's value of the bootstrap observation, then GAE over the storage."""
+        """rsl_rl ``PPO.compute_returns``: the critic's value of the bootstrap observation, then GAE over the storage.  The value is
+        torch's forward (so results stay what they were); a loop that wants the one-launch forward passes
+        ``PolicyForward(policy).value(last_critic_obs)`` to ``storage.compute_returns`` itself."""
         with torch.no_grad():
             last_values = self.policy.evaluate(last_critic_obs)
         self.storage.compute_returns(last_values, gamma=self.gamma, lam=self.lam)

@@ -885,6 +885,81 @@ typedef struct GfAdamArgs {
 } GfAdamArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * The actor-critic forward of a collection step (rsl_rl ActorCritic.act / evaluate inside PPO.act): torch runs each MLP as one GEMM
+ * and one ELU launch per layer — 14 launches for the obs -> 512 -> 256 -> 128 -> A / 1 nets of the reference configs — and every
+ * activation makes a round trip through memory.  gf_mlp_act runs both nets AND the whole of gf_policy_act in ONE launch:
+ *     observations        -> actor MLP  -> mean  -> sample, log_prob, the policy's storage rows (gf_policy_act's contract, word for word)
+ *     critic observations -> critic MLP -> value -> storage row
+ * A workgroup owns GF_MLP_TILE_ROWS rows of ONE net (grid y: actor / critic; the two have no data dependency), walks its layers on
+ * the f32 matrix cores (v_mfma_f32_32x32x2_f32) and keeps the tile's activations in LDS; only mean, values, actions and the storage
+ * rows are written to memory.  Weights are read in place, `[out, in]` row-major f32 exactly as torch.nn.Linear stores them; the first
+ * layer reads its input as up to GF_MLP_MAX_INPUTS segments `[N, width]` side by side (an observation group of several managers
+ * needs no torch.cat).  Layers are Linear with ELU(alpha = 1) between them and none after the last.
+ *
+ * Arithmetic (the one exception to "a left fold of separately rounded operations"):
+ *     y[n, j] = chain over k = 0 … K-1, ascending, of fma(x[n, k], W[j, k], acc),  acc starting from bias[j];
+ *     hidden layers then  v > 0 ? v : expm1f(v).
+ * One chain per output element, no split-K, no atomics: row n's results depend on row n's inputs only — not on num_envs, the tile it
+ * falls in, env_offset or the run.  The f32 MFMA is bit for bit such a chain (one rounding per fma, f32 accumulator).
+ *
+ * Either net may be absent (num_layers == 0): actor only = play-time inference, critic only = the bootstrap value.  With an actor,
+ * `actions == NULL` computes the mean only and draws nothing (then `mean` is required and actions_out / mu_out / sigma_out /
+ * log_prob_out must be NULL).  `mean` / `values` are optional fresh outputs.
+ * Refusals, before anything is launched: GF_E_NULL — args, a weight / bias / segment pointer, std with actions, an actor without
+ * mean and actions, a critic without values and values_out, an actor's or critic's output pointer with that net absent;
+ * GF_E_RANGE — num_envs < 0, more than GF_MLP_MAX_LAYERS layers, a segment count outside 1 … GF_MLP_MAX_INPUTS, a width < 1, a
+ * hidden width > GF_MLP_MAX_HIDDEN, a total input width > GF_MLP_MAX_INPUT_WIDTH, an actor output > GF_MLP_MAX_ACTIONS,
+ * std_per_env outside {0, 1}; GF_E_UNSUPPORTED — both nets absent, a critic output other than 1.  num_envs == 0 is a no-op.
+ * No allocation, no copy, no synchronisation inside.  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_MLP_MAX_LAYERS 6            /* Linear layers per net */
+#define GF_MLP_MAX_INPUTS 4            /* input segments per net */
+#define GF_MLP_MAX_HIDDEN 512          /* widest hidden layer */
+#define GF_MLP_MAX_INPUT_WIDTH 1024    /* sum of the segment widths */
+#define GF_MLP_MAX_ACTIONS 64          /* widest actor output */
+#define GF_MLP_TILE_ROWS 32            /* rows per workgroup */
+
+typedef struct GfMlpSegment {
+    const float* rows;          /* [N, width] contiguous */
+    int32_t width;              /* >= 1 */
+    int32_t _pad;
+} GfMlpSegment;
+
+typedef struct GfMlpLayer {
+    const float* weight;        /* [out_width, in] row-major, torch.nn.Linear.weight read in place */
+    const float* bias;          /* [out_width] */
+    int32_t out_width;          /* >= 1; `in` is the previous layer's out_width (layer 0: the sum of the segment widths) */
+    int32_t _pad;
+} GfMlpLayer;
+
+typedef struct GfMlpNet {
+    int32_t num_layers;         /* 1 … GF_MLP_MAX_LAYERS; 0: the net is absent */
+    int32_t num_inputs;         /* 1 … GF_MLP_MAX_INPUTS */
+    GfMlpSegment inputs[GF_MLP_MAX_INPUTS];
+    GfMlpLayer layers[GF_MLP_MAX_LAYERS];
+} GfMlpNet;
+
+typedef struct GfMlpActArgs {
+    int64_t num_envs;           /* N >= 0; 0: nothing is launched */
+    GfMlpNet actor;             /* output width A <= GF_MLP_MAX_ACTIONS */
+    GfMlpNet critic;            /* output width 1 */
+    const float* std;           /* [A] or [N, A] (required with actions) */
+    const float* noise;         /* [N, A] standard normals (parity mode), or NULL: Philox + Box–Muller */
+    uint64_t seed;              /* as GfPolicyActArgs */
+    uint64_t stream;
+    uint32_t env_offset;
+    int32_t std_per_env;        /* 0: std is [A], 1: [N, A] */
+    float* mean;                /* [N, A] out: the actor's output, or NULL */
+    float* values;              /* [N] out: the critic's output, or NULL */
+    float* actions;             /* [N, A] out: the sample, or NULL: mean only */
+    float* actions_out;         /* storage rows, as GfPolicyActArgs; each may be NULL */
+    float* mu_out;
+    float* sigma_out;
+    float* values_out;
+    float* log_prob_out;
+} GfMlpActArgs;
+
+/* ------------------------------------------------------------------------------------------
  * History ring -> the reference's observation layout.  The reference keeps a list of H frames, pops the oldest, inserts the new
  * one in front and returns `torch.cat(self._history, dim=-1)` (observation_manager.py:219-226): every call writes a NEW
  * [N, H*O] tensor, newest frame first.  With the history kept as an in-place ring (GfObservationArgs.history_ring: the step
@@ -925,7 +1000,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -951,6 +1026,7 @@ int gf_minibatch_gather(const GfMinibatchArgs* a, void* stream);  /* every field
 int gf_policy_act(const GfPolicyActArgs* a, void* stream);       /* Normal sample + log_prob + the policy's storage rows in one launch (rsl_rl PPO.act) */
 int gf_episode_step(const GfEpisodeArgs* a, void* stream);       /* time-out bootstrap + the runner's rewbuffer / lenbuffer upkeep (rsl_rl OnPolicyRunner.learn) */
 int gf_ppo_loss(const GfPpoLossArgs* a, void* stream);           /* minibatch loss + its gradient w.r.t. mu / value / sigma (rsl_rl PPO.update: the KL block, surrogate, value loss, loss, loss.backward() down to the policy outputs, the three .item()) */
+int gf_mlp_act(const GfMlpActArgs* a, void* stream);             /* actor + critic MLP forward on the f32 matrix cores, then gf_policy_act's sampling and rows, in one launch (rsl_rl ActorCritic.act / evaluate inside PPO.act) */
 int gf_adam_step(const GfAdamArgs* a, void* stream);             /* adaptive lr + clip_grad_norm_ + Adam.step over the flat bucket (rsl_rl PPO.update: the lr schedule, nn.utils.clip_grad_norm_, optimizer.step()) */
 
 /* ------------------------------------------------------------------------------------------

@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
-"""One PPO collection step (Go2 ``go2_cmd``) with the actor and critic forward passes, in two forms:
+"""One PPO collection step (Go2 ``go2_cmd``) with the actor and critic forward passes, in three forms:
 
 * ``rsl_rl``: rsl_rl's PPO.act (torch ``Normal``: sample, log_prob(...).sum(-1), mean, stddev), env.step, ``add_policy(...,
   time_outs=…)``, then OnPolicyRunner.learn's episode bookkeeping verbatim — ``nonzero()`` and two ``.cpu()`` copies per step;
 * ``fused``: ``RolloutStorage.act`` → env.step → ``process_env_step(episodes=…)`` (one gf_policy_act and one gf_episode_step launch
-  around the step, no host synchronisation).
+  around the step, no host synchronisation);
+* ``fused_mlp``: ``RolloutStorage.act_policy(PolicyForward(policy), obs)`` → env.step → ``process_env_step(episodes=…)``: the two forward
+  passes and the sampling are one gf_mlp_act launch (not in the default ``--forms``).
 
 Prints one JSON line per (num_envs, form): µs per step (best and median of --reps batches of --steps steps, each batch ending in a
 device synchronise).  HipBackend keeps no launch counter: count the kernels of a step in a separate run,
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_collect.py --sizes 4096 --forms fused --steps 100 --warmup 24 --reps 1
 and divide the kernel count by the steps run (warm-up + timed).
-    python tools/bench_collect.py [--sizes 4096,16384,65536] [--forms rsl_rl,fused] [--steps 240] [--warmup 48] [--reps 5]"""
+    python tools/bench_collect.py [--sizes 4096,16384,65536] [--forms rsl_rl,fused,fused_mlp] [--steps 240] [--warmup 48] [--reps 5]"""
 import argparse
 import json
 import os
@@ -23,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "genesis-forge_amd"))
 import torch
 from genesis_forge_amd import gs, tasks
-from genesis_forge_amd.learner import ActorCriticMLP, EpisodeStatistics, RolloutStorage
+from genesis_forge_amd.learner import ActorCriticMLP, EpisodeStatistics, PolicyForward, RolloutStorage
 
 T = 24   # num_steps_per_env of examples/simple/train.py
 torch.distributions.Normal.set_default_validate_args(False)   # as rsl_rl's ActorCritic.__init__ does (no per-step support checks)
@@ -45,6 +47,15 @@ def run(n: int, form: str, steps: int, warmup: int, reps: int) -> dict:
 
         def step(obs):
             actions = store.act(policy.act_mean(obs), policy.std, policy.evaluate(obs))
+            obs, _rew, _term, trunc, _ = env.step(actions)
+            store.process_env_step(trunc, gamma=gamma, episodes=stats)
+            return obs
+    elif form == "fused_mlp":
+        stats = EpisodeStatistics(n)
+        fwd = PolicyForward(policy)
+
+        def step(obs):
+            actions = store.act_policy(fwd, obs)
             obs, _rew, _term, trunc, _ = env.step(actions)
             store.process_env_step(trunc, gamma=gamma, episodes=stats)
             return obs
@@ -84,7 +95,7 @@ def run(n: int, form: str, steps: int, warmup: int, reps: int) -> dict:
     out = {"tool": "bench_collect", "config": "go2_cmd", "num_envs": n, "form": form, "steps": steps, "warmup": warmup, "reps": reps,
            "us_per_step_best": round(min(times), 2), "us_per_step_median": round(statistics.median(times), 2),
            "recorded_step": env._trace is not None}
-    if form == "fused":
+    if form in ("fused", "fused_mlp"):
         out["mean_reward"] = stats.mean_reward()
     else:
         out["mean_reward"] = statistics.mean(rewbuffer) if rewbuffer else None
@@ -105,7 +116,7 @@ def main() -> None:
     gs.set_device("cuda:0")
     for n in (int(x) for x in a.sizes.split(",")):
         for form in a.forms.split(","):
-            if form not in ("rsl_rl", "fused"):
+            if form not in ("rsl_rl", "fused", "fused_mlp"):
                 raise SystemExit(f"unknown form {form!r}")
             print(json.dumps(run(n, form, a.steps, a.warmup, a.reps)), flush=True)
 

@@ -475,16 +475,37 @@ class Backend:
     tracer = None  # set by _trace.StepTrace while it records a step
     graph_enabled = False   # GF_GRAPH=1 (HipBackend): recorded steps replay as one hipGraphLaunch (measured slower, see gf_step.h)
 
+    def __new__(cls, *args, **kwargs):
+        self = super().__new__(cls)   # (here, not in __init__: a backend class with a constructor of its own need not chain to this one)
+        self.watched: set = set()     # descriptor addresses of the live recorded steps (StepTrace.arg_set)
+        self.dirty: set = set()       # … those of them a phase call outside a replay has gone through since
+        return self
+
+    def watch(self, addrs) -> None:
+        """A recorded step froze the descriptors at ``addrs``: whatever went through them before does not concern it."""
+        self.dirty.difference_update(addrs)
+        self.watched.update(addrs)
+
+    def forget(self, addrs) -> None:
+        """The recorded step that watched ``addrs`` is gone."""
+        self.watched.difference_update(addrs)
+        self.dirty.difference_update(addrs)
+
+    def stale(self, addrs) -> bool:
+        """A phase call outside a replay has gone through one of ``addrs`` since they were last watched."""
+        d = self.dirty
+        return bool(d) and not d.isdisjoint(addrs)
+
     def _note_call(self, args) -> None:
         """A phase call outside a recorded step's replay.  If its descriptor belongs to a live recorded step (`watched`), that
         step's frozen copy of it is no longer what the ordinary path would launch — a manager method called between steps
         (``resample_command([…])``, ``reset([…])``) has refilled it — and the recording must go (`dirty`, checked by
         StepTrace.fresh before every replay)."""
-        w = self.__dict__.get("watched")
+        w = self.watched
         if w:
             a = C.addressof(args)
             if a in w:
-                self.__dict__.setdefault("dirty", set()).add(a)
+                self.dirty.add(a)
 
     def call(self, fn: str, args, owner=None) -> None:  # pragma: no cover - interface
         raise NotImplementedError

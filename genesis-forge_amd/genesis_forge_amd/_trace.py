@@ -85,234 +85,257 @@ class Untraceable(Exception):
     """The step cannot be recorded (the reason is kept on the env: ``env._untraceable``)."""
 
 
+class _OpTables:
+    """The per-step work of ONE op list, collected while its calls are walked (``StepTrace._hooks``): the main step has one, every
+    native tail segment its own."""
+
+    def __init__(self):
+        self.patches: list[Callable] = []   # Python-side per-step work that has Python semantics (live ranges, log registration)
+        self.native: list = []              # GfReplayPatch entries: every per-step descriptor field, applied by gf_replay_step
+        self.native_op: list = []           # … and the index of the op each entry belongs to (-1: none, applied first)
+        self.afters: list = []              # (index of the op it follows, callable)
+        self.op = 0                         # index of the op the entries and afters collected next belong to
+
+    def add(self, entries, patch: Optional[Callable] = None) -> None:
+        """Native entries — and the Python patch that goes with them, where there is one — of the op ``self.op``."""
+        if patch is not None:
+            self.patches.append(patch)
+        self.native.extend(entries)
+        self.native_op.extend([self.op] * (len(self.native) - len(self.native_op)))
+
+
+def _split_marks(calls: list) -> tuple:
+    """Stage 1.  Returns ``(calls, marks)``: the recorded launches without the user-code entries (Recorder.python), and those as
+    ``(index of the recorded call it precedes, callable)`` — replayed as splits."""
+    marks, plain = [], []
+    for c in calls:
+        if c[0] == "__python__":
+            marks.append((len(plain), c[1]))
+        else:
+            plain.append(c)
+    return plain, marks
+
+
+def _post_start(calls) -> int:
+    """Index of the first post-physics call (the termination launch); ``len(calls)`` without one."""
+    return next((i for i, c in enumerate(calls) if c[0] == "termination_step"), len(calls))
+
+
+def _cut_pieces(ops, n_ops: int, splits: list, native: list, native_op: list, scene_tab: list, scene_pre, rng_addr: int) -> list:
+    """Stage 6.  Returns the op list cut at the splits, piece by piece: ``(first op, count, callable to run before it or None,
+    GfReplay of the piece, its patch table)``.  Each piece of the op list goes out with its patches (one native call per piece).
+    The table stays in CALL order — stream ids are handed out in the order the ordinary step draws them — and a piece applies the
+    not yet applied PREFIX of it up to the last entry one of its own ops needs: user code that runs between two pieces may draw
+    Philox streams itself (a user manager's step() calling the base class' resample), so the entries of the calls behind it must
+    not run before it; but an observation manager that is part of the fused launch can sit BEHIND a late manager's launch in call
+    order, and then the late manager's entries go out early with it (fuzz seeds 57 / 115 / 132: its stream id comes first).  The
+    statistics slots (call parameters, no order) go with the first piece; on a Genesis-shaped scene the piece behind the scene
+    split (``scene_pre``) also carries every descriptor's snapshot pointers (``scene_tab``)."""
+    cuts = [0] + [i for i, _ in splits] + [n_ops]
+    pres = [None] + [f for _, f in splits]
+    ordered = [i for i, at in enumerate(native_op) if at >= 0]
+    unordered = [native[i] for i, at in enumerate(native_op) if at < 0]
+    done_upto = 0
+    pieces = []
+    for j, (a0, a1, pre) in enumerate(zip(cuts[:-1], cuts[1:], pres)):
+        cnt = a1 - a0
+        mine = list(scene_tab) if pre == scene_pre else []
+        if j == 0:
+            mine += unordered
+        need = [pos for pos, i in enumerate(ordered) if a0 <= native_op[i] < a1]
+        end = len(ordered) if j == len(pres) - 1 else max([done_upto] + [pos + 1 for pos in need])
+        mine += [native[i] for i in ordered[done_upto:end]]
+        done_upto = end
+        table = (nat.GfReplayPatch * max(1, len(mine)))(*mine)
+        desc = nat.GfReplay(C.addressof(ops) + a0 * C.sizeof(nat.GfOp) if cnt else None, cnt, len(mine), C.addressof(table), rng_addr)
+        pieces.append((a0, cnt, pre, desc, table))
+    assert sum(d.num_patches for *_x, d, _t in pieces) == len(native) + len(scene_tab)
+    return pieces
+
+
 class StepTrace:
+    """One recorded step.  The constructor builds it in stages — split the user-code marks from the calls (``_split_marks``) →
+    decide the fused launch (``_fuse_post``) → lay out ops, hooks and splits (``_lay_out``) → statistics parameters
+    (``_wire_statistics``) → freeze the tables (``_freeze``) → cut the step into pieces (``_cut_pieces``); ``replay`` runs it."""
+
+    graph = None   # (what __del__ finds when the constructor raised Untraceable before the step was laid out)
+
     def __init__(self, env, calls: list, tail_python: bool = False, tail_calls: Optional[dict] = None, images: Optional[tuple] = None):
+        self.backend = env.backend
+        calls, self.py_marks = _split_marks(calls)   # (index of the recorded call it precedes, user callable): replayed as splits
+        #: the descriptors this recording froze: a phase call that goes through one of them from now on (a manager method the
+        #: training script calls between steps) makes the recording stale (Backend._note_call, fresh())
+        self.arg_set = {C.addressof(c[1]) for c in calls}
         self.env = env
         #: a scene with Genesis' public surface only (fresh getter tensors, envs_idx setters): the scene step and the state fetch
         #: run in Python in the middle of the replay, the snapshot's addresses reach the descriptors as call parameters
         self.adapter = env._adapter
         self.scene_plan: list = []
         self._scene_shapes: list = []     # the plan's tensor shapes in the recorded steps (checked every replayed tick)
+        self._scene_covered: set = set()  # pointer fields of the descriptors that a patch of this recording writes (_scene_patches)
+        self._contact_args: list = []     # ContactManager descriptors (an adapter scene re-checks their shapes every tick: _scene_pre)
         self._null_stub = None
         if env._adapter is not None:
             import torch
             from . import gs
             self._null_stub = torch.zeros(16, dtype=torch.int32, device=gs.device)
-        self._images = images
         from .managed_env import ManagedEnvironment
         env_obs = type(env).get_observations is not ManagedEnvironment.get_observations
         self._env_obs_python = env_obs and not tail_python
         self._env_obs_tail = env_obs and tail_python   # (with a reset() override too: the Python tail calls it, the step returns ITS value)
         self.tail_python = tail_python
         self.tail_seg: dict = {}   # "reset" / "obs" → native segment of the Python tail (see _build_tail_segment)
-        self.backend = env.backend
+        self._tail_refs = None     # the fused observation launch of the tail's "obs" segment (_fuse_tail_obs)
+        self._tail_tries = 0
         self.epoch = env._trace_epoch
-        #: user code between native phases (Recorder.python): (index of the recorded call it precedes, callable) — replayed as splits
-        marks = []
-        plain = []
-        for c in calls:
-            if c[0] == "__python__":
-                marks.append((len(plain), c[1]))
-            else:
-                plain.append(c)
-        calls = plain
-        self.py_marks = marks
-        #: (reward, terminated, truncated) of the step: the managers' buffers — or, for a user RewardManager / TerminationManager class
-        #: whose step() is a python phase, the env's copies of what that step() returned (ManagedEnvironment._phase_step): the recorded
-        #: reset and rollout launches read them, the step returns them
-        tm, rm = env.managers["termination"], env.managers["reward"]
-        staged = {f.args[0] for _at, f in marks if getattr(f, "func", None) == env._phase_step}
-        po = env._phase_out
-        self.outputs = (po["reward"] if rm in staged else rm._reward_buf if rm is not None else env._reward_buf,
-                        *((po["terminated"], po["truncated"]) if tm in staged else (tm._terminated_buf, tm._truncated_buf)))
-        self._term_call = next((c for c in calls if c[0] == "termination_step"), None)   # (its masks: inputs of a fused tail observation launch)
-        self._tail_refs = None
-        self.patches: list[Callable] = []   # Python-side per-step work that has Python semantics (live ranges, log registration)
-        self.native: list = []              # GfReplayPatch entries: every per-step descriptor field, applied by gf_replay_step
-        self.native_op: list = []           # … and the index of the op each entry belongs to (-1: none, applied first)
-        self.afters: list = []   # (index of the op it follows, callable)
-        self.splits: list = []   # (index of the op it precedes, callable): Python that must run in the middle of the step
-        self._cur_op = 0
-        n = len(calls) + 2
-        self.ops = (nat.GfOp * n)()
         self.keep = [c[1] for c in calls]
-        stats = env.stats
-        k = 0
-        self.ops[k].phase, self.ops[k].args = nat.GF_OP_STATS_CLEAR, stats.ptr
-        k += 1
-        self._gait_swaps: list = []
-        self._late: set = set()
-        self._rows_via_unroll: set = set()   # group-row descriptors a fused step's history gathers store instead (_fuse_post)
-        first_post0 = self._post_start(calls)
+        self.outputs = self._step_outputs(self.py_marks)
+        self._term_call = next((c for c in calls if c[0] == "termination_step"), None)   # (its masks: inputs of a fused tail observation launch)
+        self.action_args, self.action_owner = next((c[1], c[2]) for c in calls if c[0] == "action_step")
         # (user code in the middle of the post-physics phases — a user manager's step() between reward and reset — keeps them off
         # the single fused launch: the phases on either side of it run as phase chains, gf_run_ops)
-        marks_in_post = any(first_post0 < at < len(calls) for at, _ in marks)   # (user code BEHIND the last launch leaves the fused launch alone)
-        self.post_refs = self._fuse_post(calls) if env.fuse_post_physics and not marks_in_post else None
-        if self.post_refs is None:
-            self._gait_swaps = []
-            self._late = set()
-            self._rows_via_unroll = set()
-        first_post = self._post_start(calls) if self.post_refs is not None else len(calls)
-        self.post_split = self.post_refs is not None and bool(self.post_refs.flags & nat.GF_POST_TERMINATION_DONE)
-        mark_i = 0
-        post_index = -1   # final index of the fused launch's op
-        scene_pre_at = None
-        for idx, (fn, args, owner) in enumerate(calls):
-            k_before = k
-            while mark_i < len(marks) and marks[mark_i][0] <= idx:   # user code that ran before this call: a split in front of its op
-                assert idx <= first_post or self.post_refs is None
-                self.splits.append((k - 1, marks[mark_i][1]))
-                mark_i += 1
-                if scene_pre_at is not None:   # right behind the step() of a user-defined action manager class (the FIRST mark: it sends
-                    self.splits.append((scene_pre_at, self._scene_pre))   # the targets itself) and in front of any other user code —
-                    scene_pre_at = None                                    # a user termination manager's step() reads this tick's state
-            if scene_pre_at is not None:
-                self.splits.append((scene_pre_at, self._scene_pre))
-                scene_pre_at = None
-            if idx < first_post:
-                self.ops[k].phase = nat.PHASE_OF_FN[fn]
-                self.ops[k].args = C.addressof(args)
-                k += 1
-            elif idx == first_post and self.post_split:   # termination as a launch of its own, the fused launch behind it (Python between)
-                self.ops[k].phase = nat.PHASE_OF_FN[fn]
-                self.ops[k].args = C.addressof(args)
-                k += 1
-            elif idx == first_post + (1 if self.post_split else 0):
-                self.ops[k].phase = nat.GF_OP_POST_PHYSICS
-                self.ops[k].args = C.addressof(self.post_refs)
-                k += 1
-                post_index = k - 2
-            elif fn == "history_unroll" or idx in self._late:   # the gather of a ring-kept history — and an observation manager with a
-                self.ops[k].phase = nat.PHASE_OF_FN[fn]         # Python-level item — follow the fused launch as ops of their own
-                self.ops[k].args = C.addressof(args)
-                k += 1
-            # index of this call's op once the leading STATS_CLEAR op is dropped (below).  A call that is PART of the fused launch has
-            # no op of its own: its per-step fields belong to the fused launch's op — not to whatever op was assigned last (a late
-            # observation manager's launch can sit between two fused calls in the recorded order, and with per-piece patch tables its
-            # output rotation would then be applied one piece too late: fuzz seeds 57 / 115 / 132 / 139)
-            self._cur_op = k - 2 if (k != k_before or post_index < 0) else post_index
-            self._hooks(fn, args, owner)
-            self.native_op.extend([self._cur_op] * (len(self.native) - len(self.native_op)))
-            if fn == "action_step" and self.adapter is not None:
-                if owner is not None:
-                    self.splits.append((self._cur_op + 1, self._scene_pre))   # control_dofs_position → scene.step() → state fetch
-                else:
-                    scene_pre_at = self._cur_op + 1
-            pre = owner._trace_pre(args) if hasattr(owner, "_trace_pre") else None
-            if pre is not None:
-                assert idx < first_post + (2 if self.post_split else 0) or idx in self._late, "a phase with Python-level terms cannot be part of the fused launch"
-                self.splits.append((self._cur_op, pre))
-        for _at, f in marks[mark_i:]:   # user code behind the last launch
-            self.splits.append((k - 1, f))
-            if scene_pre_at is not None:
-                self.splits.append((scene_pre_at, self._scene_pre))
-                scene_pre_at = None
-        if scene_pre_at is not None:
-            self.splits.append((scene_pre_at, self._scene_pre))
-        self.native.extend(self._gait_swaps)   # after the gait managers' own patches (those refill the descriptors)
-        post_at = next((i - 1 for i in range(k) if self.ops[i].phase == nat.GF_OP_POST_PHYSICS), -1)
-        self.native_op.extend([post_at] * (len(self.native) - len(self.native_op)))   # (they serve the fused launch)
-        # single process: statistics go to a device ring slot per step (no memset, no copy); with a process group the
-        # per-step all-reduce path is kept (clear op here, packed + reduced + copied by StepStats.snapshot)
+        marks_in_post = any(_post_start(calls) < at < len(calls) for at, _ in self.py_marks)   # (user code BEHIND the last launch leaves the fused launch alone)
+        fused = self._fuse_post(calls) if env.fuse_post_physics and not marks_in_post else None
+        #: the fused launch's descriptor (None: phase chains) … the group-row descriptors its history gathers store instead
+        self.post_refs, late, gait_swaps, self._rows_via_unroll = fused or (None, frozenset(), [], frozenset())
+        #: ``splits``: (index of the op it precedes, callable) — Python that must run in the middle of the step
+        self.ops, n_ops, tables, self.splits = self._lay_out(calls, self.py_marks, late, gait_swaps)
+        # single process: statistics go to a device ring slot per step (no memset, no copy; ring slots are zeroed by the previous
+        # step's action kernel); with a process group the per-step all-reduce path is kept (packed + reduced + copied by
+        # StepStats.snapshot)
+        stats = env.stats
         self.use_ring = stats.group is None
-        self.stat_fields = [c[1] for c in calls if hasattr(c[1], "stats") and c[1].stats]
-        self.action_args = next(c[1] for c in calls if c[0] == "action_step")
-        for i in range(k - 1):  # drop the leading STATS_CLEAR op: ring slots are zeroed by the previous step's action kernel
-            self.ops[i].phase, self.ops[i].args = self.ops[i + 1].phase, self.ops[i + 1].args
-        k -= 1
         #: process group + batched reduction: the previous step's statistics are folded by this step's action kernel (as in the
         #: single-process ring) instead of a pack launch per step; rows are all-reduced K at a time (StepStats.vec_ring_reduce)
         self.fold_mode = (not self.use_ring) and stats.reduce_every > 1
+        self.stat_fields = [c[1] for c in calls if hasattr(c[1], "stats") and c[1].stats]
+        self.pack_args = None if self.use_ring or self.fold_mode else nat.GfStatsPackArgs()
+        # the statistics ring slots of a step arrive as call parameters (cur, next-to-zero, previous, its vector row, last_reset);
+        # behind them, on a Genesis-shaped scene, the addresses of this tick's state tensors (_init_scene)
+        self.params = (C.c_void_p * 5)()
+        self.n_params = 5
+        self.n_ops = self._wire_statistics(stats, self.ops, n_ops, tables)
+        self._last_reset_ptr = stats.last_reset.data_ptr() if self.use_ring else None   # (group ring: gf_stats_last_reset)
+        self.patches, self.native, self.native_op, self.afters = tables.patches, tables.native, tables.native_op, tables.afters
+        self.patch_table, self.replay_desc, self.patch_desc = self._freeze(self.native, self.n_ops)
+        self._scene_tab = self._init_scene(self.keep, images) if self.adapter is not None else []
+        # (both parts or none: the observation descriptors of a step WITH a reset carry the stale-quaternion stash and the termination
+        # masks — with all-false masks they also describe a step without one; the descriptors of a step without a reset do not)
+        if tail_python:
+            self._adopt_tail(tail_calls)
+        self.backend.watch(self.arg_set)
+        #: hipGraph of this step's launches (built by the library on first replay; HIP backend only)
+        self.graph = C.c_void_p() if hasattr(self.backend, "run_ops_graph") and not self.splits and not tail_python else None
+        #: the op list cut at the splits (_cut_pieces); empty: the step is one native call
+        self.segments = _cut_pieces(self.ops, self.n_ops, self.splits, self.native, self.native_op, self._scene_tab, self._scene_pre,
+                                    C.addressof(env._rng_c)) if self.splits else []
+
+    def _step_outputs(self, marks: list) -> tuple:
+        """Returns (reward, terminated, truncated) of the step: the managers' buffers — or, for a user RewardManager /
+        TerminationManager class whose step() is a python phase, the env's copies of what that step() returned
+        (ManagedEnvironment._phase_step): the recorded reset and rollout launches read them, the step returns them."""
+        env = self.env
+        tm, rm = env.managers["termination"], env.managers["reward"]
+        staged = {f.args[0] for _at, f in marks if getattr(f, "func", None) == env._phase_step}
+        po = env._phase_out
+        return (po["reward"] if rm in staged else rm._reward_buf if rm is not None else env._reward_buf,
+                *((po["terminated"], po["truncated"]) if tm in staged else (tm._terminated_buf, tm._truncated_buf)))
+
+    def _lay_out(self, calls: list, marks: list, late, gait_swaps: list) -> tuple:
+        """Stage 3.  Returns ``(ops, number of ops, tables, splits)``: the op list as it is replayed (every index below is a final
+        one), what every call needs per step (``_hooks``) with the op it belongs to, and where Python runs in the middle of the
+        step (user-code marks, Python-level terms, the scene step of a Genesis-shaped scene)."""
+        refs = self.post_refs
+        first_post = _post_start(calls) if refs is not None else len(calls)
+        post_split = refs is not None and bool(refs.flags & nat.GF_POST_TERMINATION_DONE)
+        post_call = first_post + (1 if post_split else 0)   # the call whose place the fused launch's op takes
+        ops = (nat.GfOp * (len(calls) + 1))()               # (+ 1: the statistics pack op of a process group, _wire_statistics)
+        tables = _OpTables()
+        splits: list = []
+        k = 0
+        post_index = -1   # index of the fused launch's op
+        scene_pre_at = None
+
+        def scene_split():
+            nonlocal scene_pre_at
+            if scene_pre_at is not None:
+                splits.append((scene_pre_at, self._scene_pre))
+                scene_pre_at = None
+
+        mark_i = 0
+        for idx, (fn, args, owner) in enumerate(calls):
+            k_before = k
+            while mark_i < len(marks) and marks[mark_i][0] <= idx:   # user code that ran before this call: a split in front of its op
+                assert idx <= first_post or refs is None
+                splits.append((k, marks[mark_i][1]))
+                mark_i += 1
+                # right behind the step() of a user-defined action manager class (the FIRST mark: it sends the targets itself) and in
+                # front of any other user code — a user termination manager's step() reads this tick's state
+                scene_split()
+            scene_split()
+            if idx == post_call:   # (with GF_POST_TERMINATION_DONE: termination is a launch of its own in front, Python between)
+                ops[k].phase, ops[k].args = nat.GF_OP_POST_PHYSICS, C.addressof(refs)
+                post_index = k
+                k += 1
+            elif idx < post_call or fn == "history_unroll" or idx in late:   # behind the fused launch: the gather of a ring-kept
+                ops[k].phase, ops[k].args = nat.PHASE_OF_FN[fn], C.addressof(args)   # history — and an observation manager with a
+                k += 1                                                               # Python-level item — stay ops of their own
+            # A call that is PART of the fused launch has no op of its own: its per-step fields belong to the fused launch's op — not
+            # to whatever op was assigned last (a late observation manager's launch can sit between two fused calls in the recorded
+            # order, and with per-piece patch tables its output rotation would then be applied one piece too late: fuzz seeds 57 /
+            # 115 / 132 / 139)
+            tables.op = k - 1 if (k != k_before or post_index < 0) else post_index
+            self._hooks(tables, fn, args, owner)
+            if fn == "action_step" and self.adapter is not None:
+                if owner is not None:
+                    splits.append((tables.op + 1, self._scene_pre))   # control_dofs_position → scene.step() → state fetch
+                else:
+                    scene_pre_at = tables.op + 1
+            pre = owner._trace_pre(args) if hasattr(owner, "_trace_pre") else None
+            if pre is not None:
+                assert idx < first_post + (2 if post_split else 0) or idx in late, "a phase with Python-level terms cannot be part of the fused launch"
+                splits.append((tables.op, pre))
+        for _at, f in marks[mark_i:]:   # user code behind the last launch
+            splits.append((k, f))
+            scene_split()
+        scene_split()
+        tables.op = post_index   # (they serve the fused launch)
+        tables.add(gait_swaps)   # after the gait managers' own patches (those refill the descriptors)
+        return ops, k, tables, splits
+
+    def _wire_statistics(self, stats, ops, n_ops: int, tables: _OpTables) -> int:
+        """Stage 4.  Adds the entries that hand the step's statistics slots (call parameters, no order: op -1) to the descriptors
+        that count, or — process group without batched reduction — the pack op behind the last op.  Returns the number of ops."""
+        tables.op = -1
         if self.use_ring:
             stats.ensure_ring()
         else:
             stats.ensure_vec_ring()
             if not self.fold_mode:
-                self.pack_args = nat.GfStatsPackArgs()
-                self.ops[k].phase, self.ops[k].args = nat.GF_OP_STATS_PACK, C.addressof(self.pack_args)
-                k += 1
-        self.n_ops = k
-        # the statistics ring slots of a step arrive as call parameters (cur, next-to-zero, previous, its vector row, last_reset);
-        # behind them, on a Genesis-shaped scene, the addresses of this tick's state tensors (_init_scene)
-        self.params = (C.c_void_p * 5)()
-        self.n_params = 5
-        if self.use_ring or self.fold_mode:
-            P = nat.GfReplayPatch
-            for a in self.stat_fields:
-                self.native.append(P(nat.GF_PATCH_PARAM, 0, nat.field_addr(a, "stats"), None, None))
-            aa = self.action_args
-            for idx, name in ((1, "stats_zero"), (2, "stats_fold_src"), (3, "stats_fold_dst"), (4, "stats_last_reset")):
-                self.native.append(P(nat.GF_PATCH_PARAM, idx, nat.field_addr(aa, name), None, None))
-            self._last_reset_ptr = stats.last_reset.data_ptr() if self.use_ring else None   # (group ring: gf_stats_last_reset)
-        # gf_replay_step: the whole table, then the ops, in ONE native call (the patch-only variant serves steps whose ops are
-        # replayed in pieces around Python-level terms, or as a hipGraph)
-        self.native_op.extend([-1] * (len(self.native) - len(self.native_op)))   # statistics slots: call parameters, no order
-        self.patch_table = (nat.GfReplayPatch * max(1, len(self.native)))(*self.native)
-        self.replay_desc = nat.GfReplay(C.addressof(self.ops), k, len(self.native), C.addressof(self.patch_table), C.addressof(env._rng_c))
-        self.patch_desc = nat.GfReplay(None, 0, len(self.native), C.addressof(self.patch_table), C.addressof(env._rng_c))
-        #: the descriptors this recording froze: a phase call that goes through one of them from now on (a manager method the
-        #: training script calls between steps) makes the recording stale (Backend._note_call, fresh())
-        self.arg_set = {C.addressof(c[1]) for c in calls}
-        if self.adapter is not None:
-            self._init_scene([c[1] for c in calls])
-        # (both parts or none: the observation descriptors of a step WITH a reset carry the stale-quaternion stash and the termination
-        # masks — with all-false masks they also describe a step without one; the descriptors of a step without a reset do not)
-        self._tail_tries = 0
-        if tail_python:
-            self._adopt_tail(tail_calls)
-        b = self.backend
-        b.__dict__.setdefault("dirty", set()).difference_update(self.arg_set)
-        b.__dict__.setdefault("watched", set()).update(self.arg_set)
-        #: hipGraph of this step's launches (built by the library on first replay; HIP backend only)
-        self.graph = C.c_void_p() if hasattr(self.backend, "run_ops_graph") and not self.splits and not tail_python else None
-        #: the op list cut at the splits: (first op, count, callable to run before it or None)
-        self.segments = []
-        if self.splits:
-            cuts = [0] + [i for i, _ in self.splits] + [k]
-            pres = [None] + [f for _, f in self.splits]
-            for (a0, a1), pre in zip(zip(cuts[:-1], cuts[1:]), pres):
-                sub = (nat.GfOp * (a1 - a0)).from_buffer(self.ops, a0 * C.sizeof(nat.GfOp)) if a1 > a0 else None
-                self.segments.append((a0, a1 - a0, sub, pre))
-            # Each piece of the op list goes out with its patches (one native call per piece).  The table stays in CALL order — stream
-            # ids are handed out in the order the ordinary step draws them — and a piece applies the not yet applied PREFIX of it up
-            # to the last entry one of its own ops needs: user code that runs between two pieces may draw Philox streams itself (a
-            # user manager's step() calling the base class' resample), so the entries of the calls behind it must not run before it;
-            # but an observation manager that is part of the fused launch can sit BEHIND a late manager's launch in call order, and
-            # then the late manager's entries go out early with it (fuzz seeds 57 / 115 / 132: its stream id comes first).  The
-            # statistics slots (call parameters, no order) go with the first piece; on a Genesis-shaped scene the piece behind the
-            # scene split also carries every descriptor's snapshot pointers.
-            scene_tab = list(getattr(self, "_scene_tab", []))
-            ordered = [i for i, at in enumerate(self.native_op) if at >= 0]
-            unordered = [self.native[i] for i, at in enumerate(self.native_op) if at < 0]
-            done_upto = 0
-            segs = []
-            for j, (a0, cnt, sub, pre) in enumerate(self.segments):
-                mine = list(scene_tab) if (self.adapter is not None and pre == self._scene_pre) else []
-                if j == 0:
-                    mine += unordered
-                need = [pos for pos, i in enumerate(ordered) if a0 <= self.native_op[i] < a0 + cnt]
-                end = len(ordered) if j == len(self.segments) - 1 else max([done_upto] + [pos + 1 for pos in need])
-                mine += [self.native[i] for i in ordered[done_upto:end]]
-                done_upto = max(done_upto, end)
-                table = (nat.GfReplayPatch * max(1, len(mine)))(*mine)
-                desc = nat.GfReplay(C.addressof(self.ops) + a0 * C.sizeof(nat.GfOp) if cnt else None, cnt, len(mine), C.addressof(table), C.addressof(env._rng_c))
-                segs.append((a0, cnt, pre, desc, table))
-            self.segments = segs
-            assert sum(d.num_patches for *_x, d, _t in segs) == len(self.native) + len(scene_tab)
+                ops[n_ops].phase, ops[n_ops].args = nat.GF_OP_STATS_PACK, C.addressof(self.pack_args)
+                return n_ops + 1
+        P = nat.GfReplayPatch
+        tables.add(P(nat.GF_PATCH_PARAM, 0, nat.field_addr(a, "stats"), None, None) for a in self.stat_fields)
+        aa = self.action_args
+        tables.add(P(nat.GF_PATCH_PARAM, idx, nat.field_addr(aa, name), None, None)
+                   for idx, name in ((1, "stats_zero"), (2, "stats_fold_src"), (3, "stats_fold_dst"), (4, "stats_last_reset")))
+        return n_ops
+
+    def _freeze(self, native: list, n_ops: int) -> tuple:
+        """Stage 5.  Returns ``(patch_table, replay_desc, patch_desc)``.  gf_replay_step: the whole table, then the ops, in ONE
+        native call (``replay_desc``); the patch-only variant (``patch_desc``) serves a step replayed as a hipGraph."""
+        table = (nat.GfReplayPatch * max(1, len(native)))(*native)
+        rng = C.addressof(self.env._rng_c)
+        return (table, nat.GfReplay(C.addressof(self.ops), n_ops, len(native), C.addressof(table), rng),
+                nat.GfReplay(None, 0, len(native), C.addressof(table), rng))
 
     def fresh(self) -> bool:
         """No descriptor of this recording has been used by a phase call outside its replay since it was made."""
-        d = self.backend.__dict__.get("dirty")
-        return not d or d.isdisjoint(self.arg_set)
+        return not self.backend.stale(self.arg_set)
 
     def __del__(self):
-        b, mine = getattr(self, "backend", None), getattr(self, "arg_set", None)
-        if b is not None and mine:
-            for name in ("watched", "dirty"):
-                st = b.__dict__.get(name)
-                if st:
-                    st.difference_update(mine)
-        g = getattr(self, "graph", None)
+        self.backend.forget(self.arg_set)
+        g = self.graph
         if g is not None and g.value:
             try:
                 self.backend.graph_destroy(g)
@@ -320,9 +343,9 @@ class StepTrace:
                 pass
 
     # -- a scene with Genesis' public surface only --------------------------------------------------------------------------
-    def _scene_patches(self, descs: list) -> list:
-        """GF_PATCH_PARAM_OFFSET entries for every pointer field of ``descs`` that addresses a tensor of this tick's snapshot.
-        The fetch plan only ever grows (a tail adopted later may read state the main part does not): parameter indices stay."""
+    def _scene_patches(self, descs: list, native: list) -> list:
+        """GF_PATCH_PARAM_OFFSET entries for every pointer field of ``descs`` that addresses a tensor of this tick's snapshot and
+        that no entry of ``native`` (the table of the same op list) writes.  The fetch plan only ever grows (a tail adopted later may read state the main part does not): parameter indices stay."""
         ad = self.adapter
         plan = ad.plan()
         if [k for k, _ in plan[:len(self.scene_plan)]] != [k for k, _ in self.scene_plan]:
@@ -337,29 +360,30 @@ class StepTrace:
                 params[5 + i] = ad.peek(key).data_ptr()
             self.params, self.n_params = params, 5 + len(plan)
         skip = set()
-        for p in self.native:
+        for p in native:
             skip.update(t for t in (p.target, p.target2) if t)
         patches, covered = ad.attribute(descs, self.scene_plan, skip)
-        self._scene_covered = getattr(self, "_scene_covered", set()) | covered | skip
+        self._scene_covered = self._scene_covered | covered | skip
         P = nat.GfReplayPatch
         return [P(nat.GF_PATCH_PARAM_OFFSET, 5 + i, addr, None, off if off else None) for addr, i, off in patches]
 
-    def _init_scene(self, descs: list) -> None:
+    def _init_scene(self, descs: list, images: Optional[tuple]) -> list:
+        """Returns the snapshot-pointer entries of the main step's descriptors (they go out with the piece behind the scene split,
+        _cut_pieces).  ``images``: the descriptors' byte images in the two recorded steps (Recorder.images)."""
         from ._scene_adapter import PER_STEP_FIELDS, changed_pointer_fields
-        tab = self._scene_patches(descs)
+        tab = self._scene_patches(descs, self.native)
         if not tab:
             raise Untraceable("no descriptor reads the scene snapshot")
         # every pointer field that differed between the two recorded steps must be explained: a snapshot tensor (patched above),
         # a field another patch writes, or one of the per-step fields the step's own bookkeeping sets
-        if self._images is not None and self._images[0] is not None:
-            before, now = self._images
+        if images is not None and images[0] is not None:
+            before, now = images
             for addr, name in changed_pointer_fields(descs, [before.get(C.addressof(d)) for d in descs], [now.get(C.addressof(d)) for d in descs]):
                 leaf = name.rsplit(".", 1)[-1]
                 if addr in self._scene_covered or leaf in PER_STEP_FIELDS or leaf.startswith("ext["):
                     continue
                 raise Untraceable(f"{name} changes from step to step and is neither scene state nor a per-step field")
-        self._scene_tab = tab
-        self.scene_table = (nat.GfReplayPatch * len(tab))(*tab)
+        return tab
 
     def _scene_pre(self) -> None:
         """What the ordinary step does between the action phase and the first post-physics phase (managed_env.py:290-292,
@@ -386,7 +410,7 @@ class StepTrace:
         old = self._scene_shapes[i]
         if key and key[0] == "contacts" and t.dim() == len(old) and tuple(t.shape)[:1] == old[:1]:
             c = int(t.shape[1]) if t.dim() > 1 else 0
-            for a in getattr(self, "_contact_args", []):
+            for a in self._contact_args:
                 a.num_contacts = c
             self._scene_shapes[i] = tuple(t.shape)
             return
@@ -435,31 +459,28 @@ class StepTrace:
         described = [c[1] for c in calls]   # every descriptor a launch reads, fused or not
         if reset_args is not None:
             calls = self._fuse_tail_obs(calls, reset_args)
-        saved = (self.native, self.patches, self.afters, self._cur_op)
-        self.native, self.patches, self.afters = [], [], []
-        try:
-            ops = (nat.GfOp * len(calls))()
-            P = nat.GfReplayPatch
-            for k, (fn, args, owner) in enumerate(calls):
-                self._cur_op = k
-                if fn == "post_obs":   # the fused observation launch: the hooks and patches are the member launches' own
-                    ops[k].phase, ops[k].args = nat.GF_OP_POST_PHYSICS, C.addressof(args)
-                    members = owner
-                else:
-                    ops[k].phase, ops[k].args = nat.PHASE_OF_FN[fn], C.addressof(args)
-                    members = [(fn, args, owner)]
-                for mfn, margs, mowner in members:
-                    self._hooks(mfn, margs, mowner)
-                    if hasattr(margs, "stats") and margs.stats:
-                        self.native.append(P(nat.GF_PATCH_PARAM, 0, nat.field_addr(margs, "stats"), None, None))
-            if self.adapter is not None:
-                self.native.extend(self._scene_patches(described))
-            table = (nat.GfReplayPatch * max(1, len(self.native)))(*self.native)
-            desc = nat.GfReplay(C.addressof(ops), len(calls), len(self.native), C.addressof(table), C.addressof(self.env._rng_c))
-            return {"ops": ops, "table": table, "desc": desc, "patches": self.patches, "afters": [f for _, f in self.afters],
-                    "keep": [c[1] for c in calls] + described, "fused_obs": any(c[0] == "post_obs" for c in calls)}
-        finally:
-            self.native, self.patches, self.afters, self._cur_op = saved
+        tables = _OpTables()
+        ops = (nat.GfOp * len(calls))()
+        P = nat.GfReplayPatch
+        for k, (fn, args, owner) in enumerate(calls):
+            tables.op = k
+            if fn == "post_obs":   # the fused observation launch: the hooks and patches are the member launches' own
+                ops[k].phase, ops[k].args = nat.GF_OP_POST_PHYSICS, C.addressof(args)
+                members = owner
+            else:
+                ops[k].phase, ops[k].args = nat.PHASE_OF_FN[fn], C.addressof(args)
+                members = [(fn, args, owner)]
+            for mfn, margs, mowner in members:
+                self._hooks(tables, mfn, margs, mowner)
+                if hasattr(margs, "stats") and margs.stats:
+                    tables.add([P(nat.GF_PATCH_PARAM, 0, nat.field_addr(margs, "stats"), None, None)])
+        native = tables.native
+        if self.adapter is not None:
+            native.extend(self._scene_patches(described, native))
+        table = (nat.GfReplayPatch * max(1, len(native)))(*native)
+        desc = nat.GfReplay(C.addressof(ops), len(calls), len(native), C.addressof(table), C.addressof(self.env._rng_c))
+        return {"ops": ops, "table": table, "desc": desc, "patches": tables.patches, "afters": [f for _, f in tables.afters],
+                "keep": [c[1] for c in calls] + described, "fused_obs": any(c[0] == "post_obs" for c in calls)}
 
     def _tail_native_ok(self) -> bool:
         """The native tail replays only what went through ``backend.call``: every manager's reset must be a section of the masked
@@ -497,9 +518,7 @@ class StepTrace:
             _programs.on_recorded(self.env, self._tail_refs)   # (a structure no built-in program matches gets its own: GF_JIT)
         mine = {C.addressof(c[1]) for part in ("reset", "obs") for c in tail_calls[part]}
         self.arg_set.update(mine)
-        b = self.backend
-        b.__dict__.setdefault("dirty", set()).difference_update(mine)
-        b.__dict__.setdefault("watched", set()).update(mine)
+        self.backend.watch(mine)
 
     def run_tail_segment(self, part: str) -> bool:
         """Replay one part of the Python tail natively; False when that part was not recorded (the caller walks the managers)."""
@@ -523,16 +542,30 @@ class StepTrace:
 
     # -- fused post-physics launch -----------------------------------------------------------------------
     @staticmethod
-    def _post_start(calls) -> int:
-        for i, (fn, _, _) in enumerate(calls):
-            if fn == "termination_step":
-                return i
-        return len(calls)
+    def _gait_swaps(refs, g: int, mgr, step_args, reset_args, reward_args) -> list:
+        """Enters gait manager ``g`` into ``refs`` and returns its per-step entries.  One launch reads the swing / stance bytes the
+        previous step left and writes the bytes of the state it leaves into the manager's OTHER buffer (GfPostRefs): rotate the
+        manager's two buffers, the other descriptors follow.  ``reset_args`` None (GF_POST_NO_RESET): the masked gait launch of the
+        tail then finds the manager's CURRENT buffer (the rotor has advanced) and updates the reset blocks' bytes in place."""
+        P = nat.GfReplayPatch
+        refs.gait_step[g] = C.addressof(step_args)
+        refs.gait_flags_next[g] = mgr._wave_flags_next.data_ptr()
+        flags = nat.field_addr(step_args, "wave_flags")
+        sw = [P(nat.GF_PATCH_ROTATE, 0, flags, C.addressof(refs) + nat.GfPostRefs.gait_flags_next.offset + 8 * g, C.addressof(mgr._flags_rotor))]
+        if reset_args is not None:
+            refs.gait_reset[g] = C.addressof(reset_args)
+            sw.append(P(nat.GF_PATCH_COPY, 0, nat.field_addr(reset_args, "wave_flags"), None, flags))
+        if reward_args is not None and reward_args.gait_wave_flags:
+            sw.append(P(nat.GF_PATCH_COPY, 0, nat.field_addr(reward_args, "gait_wave_flags"), None, flags))
+        return sw
 
-    def _fuse_post(self, calls):
-        """If the tail of the step is [termination, reward?, command.step*, reset, command.reset*, observe*], describe it
-        to gf_post_physics_step (one launch) — provided the library agrees the combination is fusable."""
-        i = self._post_start(calls)
+    def _fuse_post(self, calls) -> Optional[tuple]:
+        """Stage 2.  If the tail of the step is [termination, reward?, command.step*, reset, command.reset*, observe*], describe it
+        to gf_post_physics_step (one launch) — provided the library agrees the combination is fusable.  Returns None (the phases
+        stay phase chains) or what the caller has to apply: ``(the GfPostRefs, indices into calls of the launches that stay ops of
+        their own behind the fused one, the gait managers' buffer-swap entries, addresses of the group-row descriptors a history
+        gather stores instead)``.  Assigns nothing on ``self``."""
+        i = _post_start(calls)
         tail = calls[i:]
         fns = [c[0] for c in tail]
         if not fns or fns[0] != "termination_step":
@@ -545,18 +578,19 @@ class StepTrace:
             # the callables run where the reference calls them (before their phase, after the earlier ones: a reward callable may
             # read this step's termination buffers), and ONE launch does reward … observation with the termination masks as inputs
             # (GF_POST_TERMINATION_DONE).  A Python-level OBSERVATION item sees the post-reset state: the manager that owns it is left
-            # out of the fused launch and observes behind it, after its callables, as a launch of its own (self._late).
+            # out of the fused launch and observes behind it, after its callables, as a launch of its own (`late`).
             if any(fns[i] not in ("termination_step", "reward_step", "observe") for i in py) or len(fns) < 2:
                 return None
             if any(fns[i] in ("termination_step", "reward_step") for i in py):
                 refs.flags = nat.GF_POST_TERMINATION_DONE
         late_obs = {k for k in py if fns[k] == "observe"}
-        self._late = set()
+        late, rows_via_unroll, gait_swaps = set(), set(), []
         refs.termination = C.addressof(tail[0][1])
         j = 1
         if j < len(fns) and fns[j] == "reward_step":
             refs.reward = C.addressof(tail[j][1])
             j += 1
+        reward_args = tail[1][1] if refs.reward else None
         steps, gsteps = [], []
         while j < len(fns) and fns[j] in ("command_step", "gait_step") and tail[j][1].mode == nat.GF_CMD_STEP:
             (steps if fns[j] == "command_step" else gsteps).append(tail[j])
@@ -571,26 +605,12 @@ class StepTrace:
             refs.num_command, refs.num_gait = len(steps), len(gsteps)
             for c, st in enumerate(steps):
                 refs.command_step[c] = C.addressof(st[1])
-            self._gait_swaps = []
-            P = nat.GfReplayPatch
-            reward_args = tail[1][1] if refs.reward else None
             for g, st in enumerate(gsteps):
-                refs.gait_step[g] = C.addressof(st[1])
-                mgr = st[2]
-                refs.gait_flags_next[g] = mgr._wave_flags_next.data_ptr()
-                # the launch reads the bytes the previous step left and writes its own into the manager's OTHER buffer, as the full
-                # fused launch does; the masked gait launch of the tail then finds the manager's CURRENT buffer (the rotor has
-                # advanced) and updates the reset blocks' bytes in place
-                sw = [P(nat.GF_PATCH_ROTATE, 0, nat.field_addr(st[1], "wave_flags"), C.addressof(refs) + nat.GfPostRefs.gait_flags_next.offset + 8 * g,
-                        C.addressof(mgr._flags_rotor))]
-                if reward_args is not None and reward_args.gait_wave_flags:
-                    sw.append(P(nat.GF_PATCH_COPY, 0, nat.field_addr(reward_args, "gait_wave_flags"), None, nat.field_addr(st[1], "wave_flags")))
-                self._gait_swaps.extend(sw)
-            return refs if self.backend.post_check(refs) else None
+                gait_swaps += self._gait_swaps(refs, g, st[2], st[1], None, reward_args)
+            return (refs, late, gait_swaps, rows_via_unroll) if self.backend.post_check(refs) else None
         if j >= len(fns) or fns[j] != "masked_reset":
             return None
         refs.reset = C.addressof(tail[j][1])
-        reward_args = tail[1][1] if refs.reward else None
         j += 1
         resets, gresets = [], []
         while j < len(fns) and fns[j] in ("command_step", "gait_step") and tail[j][1].mode == nat.GF_CMD_MASKED:
@@ -602,27 +622,29 @@ class StepTrace:
                 if j not in late_obs and len(obs) >= nat.GF_POST_MAX_OBS:
                     late_obs.add(j)           # more managers than the fused launch holds: the further ones observe behind it
                 if j in late_obs:
-                    self._late.add(i + j)     # (indices into `calls`) this manager's launch, and its gather, stay ops of their own
+                    late.add(i + j)           # (indices into `calls`) this manager's launch, and its gather, stay ops of their own
                 else:
                     obs.append(tail[j])
             elif any(tail[k][2] is tail[j][2] for k in late_obs):
-                self._late.add(i + j)
+                late.add(i + j)
             j += 1
         if late_obs and j < len(fns) and fns[j] == "rollout_write":
             return None   # (a rollout row out of an observation that is not part of the fused launch: keep the chains)
         if j < len(fns) and fns[j] == "rollout_write":   # learner.RolloutStorage: its rows are stored by the same launch
             refs.rollout = C.addressof(tail[j][1])
-            pol = next((m for m in self.env.managers["observation"] if m.name == tail[j][2].obs_name), None)
-            if pol is not None and pol._unrolled:
-                tail[j][1].obs_out = None   # … except the observation row of a ring-kept history: its gather writes it (learner.py)
+            if tail[j][2]._om._unrolled:
+                # … except the observation row of a ring-kept history: its gather writes it (learner.py).  Written in front of the
+                # decision because gf_post_physics_check reads the field; harmless when the launch is refused after all: the
+                # storage's per-step patch (RolloutStorage._next_rows) rewrites the field every step
+                tail[j][1].obs_out = None
             j += 1
             # the rows of the storage's other observation-group members (learner._GroupRows): a ring-kept history's gather stores its
             # row as second destination (no op); any other row is a rollout_write op of its own behind the fused launch
             while j < len(fns) and fns[j] == "rollout_write" and getattr(tail[j][2], "group_row", False):
                 if tail[j][2].unroll_ok():
-                    self._rows_via_unroll.add(C.addressof(tail[j][1]))
+                    rows_via_unroll.add(C.addressof(tail[j][1]))
                 else:
-                    self._late.add(i + j)
+                    late.add(i + j)
                 j += 1
         if j != len(fns) or len(steps) != len(resets) or len(steps) > nat.GF_POST_MAX_CMD or len(obs) > nat.GF_POST_MAX_OBS:
             return None
@@ -632,86 +654,61 @@ class StepTrace:
             if s[2] is not r[2]:
                 return None
         refs.num_gait = len(gsteps)
-        self._gait_swaps = []
         for g, (s, r) in enumerate(zip(gsteps, gresets)):
-            refs.gait_step[g] = C.addressof(s[1])
-            refs.gait_reset[g] = C.addressof(r[1])
-            mgr = s[2]
-            refs.gait_flags_next[g] = mgr._wave_flags_next.data_ptr()
-            # One launch reads the swing / stance bytes the previous step left and writes the bytes of the state it leaves into
-            # the manager's OTHER buffer (GfPostRefs): rotate the manager's two buffers, the other descriptors follow
-            P = nat.GfReplayPatch
-            sw = [P(nat.GF_PATCH_ROTATE, 0, nat.field_addr(s[1], "wave_flags"), C.addressof(refs) + nat.GfPostRefs.gait_flags_next.offset + 8 * g,
-                    C.addressof(mgr._flags_rotor)),
-                  P(nat.GF_PATCH_COPY, 0, nat.field_addr(r[1], "wave_flags"), None, nat.field_addr(s[1], "wave_flags"))]
-            if reward_args is not None and reward_args.gait_wave_flags:
-                sw.append(P(nat.GF_PATCH_COPY, 0, nat.field_addr(reward_args, "gait_wave_flags"), None, nat.field_addr(s[1], "wave_flags")))
-            self._gait_swaps.extend(sw)
+            gait_swaps += self._gait_swaps(refs, g, s[2], s[1], r[1], reward_args)
         refs.num_command, refs.num_observe = len(steps), len(obs)
         for c, (s, r) in enumerate(zip(steps, resets)):
             refs.command_step[c] = C.addressof(s[1])
             refs.command_reset[c] = C.addressof(r[1])
         for m, o in enumerate(obs):
             refs.observe[m] = C.addressof(o[1])
-        return refs if self.backend.post_check(refs) else None
+        return (refs, late, gait_swaps, rows_via_unroll) if self.backend.post_check(refs) else None
 
     # -- per-phase hooks ----------------------------------------------------------------------------
-    def _hooks(self, fn, args, owner):
+    def _hooks(self, t: _OpTables, fn, args, owner) -> None:
+        """Collects into ``t`` what one recorded call needs every step (for the op ``t.op``)."""
         env = self.env
         P = nat.GfReplayPatch
         if fn == "action_step":
-            self.action_owner = owner
-            self.native.append(P(nat.GF_PATCH_ACTIONS, 0, nat.field_addr(args, "actions_in"), None, None))
+            t.add([P(nat.GF_PATCH_ACTIONS, 0, nat.field_addr(args, "actions_in"), None, None)])
             # (owner None: the env's bookkeeping launch in front of a user-defined action manager class, whose own step() is a python phase)
             if owner is not None and not owner._quiet_action_errors:
-                self.afters.append((self._cur_op, owner._watch_flags))
+                t.afters.append((t.op, owner._watch_flags))
         elif fn == "synth_scene_step":
-            self.native.append(P(nat.GF_PATCH_COUNTER, 0, nat.field_addr(args, "tick"), None, C.addressof(owner._tick_c)))
+            t.add([P(nat.GF_PATCH_COUNTER, 0, nat.field_addr(args, "tick"), None, C.addressof(owner._tick_c))])
         elif fn == "termination_step":
-            self.afters.append((self._cur_op, owner.manager._publish))
-        elif fn == "reward_step":
-            pass
+            t.afters.append((t.op, owner.manager._publish))
         elif fn in ("command_step", "gait_step"):
-            self.patches.append(owner._trace_patch(args))
-            self.native.extend(owner._trace_native(args))
+            t.patches.append(owner._trace_patch(args))
+            t.add(owner._trace_native(args))
         elif fn == "masked_reset":
-            self.native.append(P(nat.GF_PATCH_STREAM, 0, nat.field_addr(args, "stream"), None, None))
+            t.add([P(nat.GF_PATCH_STREAM, 0, nat.field_addr(args, "stream"), None, None)])
             rm = env.managers["reward"]
             if rm is not None:
                 def patch(_actions, rm=rm):
                     if rm.enabled and rm.logging_enabled:
                         rm._register_log()
-                self.patches.append(patch)
-            self.afters.append((self._cur_op, partial(env._after_masked_reset_traced, *self.outputs[1:])))
+                t.patches.append(patch)
+            t.afters.append((t.op, partial(env._after_masked_reset_traced, *self.outputs[1:])))
         elif fn == "observe":
-            self.native.extend(owner._trace_native(args))
-            fresh = owner._trace_fresh_patch(args)
-            if fresh is not None:
-                self.patches.append(fresh)
+            t.add(owner._trace_native(args), owner._trace_fresh_patch(args))
             if not owner._unrolled:
-                self.afters.append((self._cur_op, owner._trace_after))
+                t.afters.append((t.op, owner._trace_after))
         elif fn == "history_unroll":
             patch, native = owner._trace_unroll(args)
-            if patch is not None:
-                self.patches.append(patch)
-            self.native.extend(native)
-            self.afters.append((self._cur_op, owner._trace_after))
+            t.add(native, patch)
+            t.afters.append((t.op, owner._trace_after))
         elif fn == "contact_step":
-            # (an adapter scene re-checks the contact arrays' shapes every replayed tick: _scene_pre)
-            if not hasattr(self, "_contact_args"):
-                self._contact_args = []
-            self._contact_args.append(args)
+            self._contact_args.append(args)   # (an adapter scene re-checks the contact arrays' shapes every replayed tick: _scene_pre)
         elif fn == "rollout_write" and getattr(owner, "group_row", False):
             patch, native = owner._trace(args, C.addressof(args) in self._rows_via_unroll)
-            if patch is not None:
-                self.patches.append(patch)
-            self.native.extend(native)
+            t.add(native, patch)
         elif fn == "rollout_write":
-            pol = next(m for m in env.managers["observation"] if m.name == owner.obs_name)
+            pol = owner._om
             fused = self.post_refs is not None and bool(self.post_refs.rollout)
-            self.patches.append(owner._trace_patch(args, pol if fused and pol._unrolled else None))
-            self.native.extend(owner._trace_native(args, pol, fused))
-        else:
+            t.patches.append(owner._trace_patch(args, pol if fused and pol._unrolled else None))
+            t.add(owner._trace_native(args, pol, fused))
+        elif fn != "reward_step":   # (the reward launch has no per-step field)
             raise RuntimeError(f"untraceable phase {fn}")
 
     # -- replay ---------------------------------------------------------------------------------------
@@ -794,10 +791,9 @@ class StepTrace:
             try:
                 env._reset_done(terminated, truncated)
                 obs_tail = env.get_observations()
-                ro = getattr(env, "_rollout", None)
+                ro = env._rollout
                 if ro is not None:
-                    pol = next((m for m in env.managers["observation"] if m.name == ro.obs_name), None)
-                    ro.write(pol._last_out if pol is not None else obs_tail, rew, terminated, truncated)
+                    ro.write(ro._om._last_out, rew, terminated, truncated)
             finally:
                 env.stats.ptr_override, env._in_step, env._tail_trace = None, False, None
                 if rec is not None:

@@ -215,7 +215,7 @@ class RolloutStorage:
         return self
 
     def detach(self) -> None:
-        if getattr(self.env, "_rollout", None) is self:
+        if self.env._rollout is self:
             self.env._rollout = None
             self.env.invalidate_trace()
 

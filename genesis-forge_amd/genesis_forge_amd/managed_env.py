@@ -91,6 +91,7 @@ class ManagedEnvironment(GenesisEnv):
         self.jit_programs: Optional[str] = None
         self._done_ids = None     # the index list of this step's done envs while a user reset() override holds it (reset() recognises it)
         self._done_masks = None   # … and the step's (terminated, truncated) it was made from: what the masked reset of those envs reads
+        self._rollout = None      # the attached learner.RolloutStorage: every step writes its rows
         self._tail_trace = None   # the recorded step whose Python tail is running (its reset / observation segments replay natively)
         #: record the step and replay it through gf_run_ops when possible (see _trace.py); GF_NO_TRACE=1 disables
         self.trace_enabled = os.environ.get("GF_NO_TRACE", "0") != "1"
@@ -234,7 +235,7 @@ class ManagedEnvironment(GenesisEnv):
             from . import _programs
             if tr.post_refs is not None:
                 _programs.on_recorded(self)
-            if getattr(tr, "_tail_refs", None) is not None and tr.tail_seg:
+            if tr._tail_refs is not None and tr.tail_seg:
                 _programs.on_recorded(self, tr._tail_refs)
         return tr
 
@@ -314,11 +315,10 @@ class ManagedEnvironment(GenesisEnv):
             obs = self._step_obs
         else:
             obs = self.get_observations()
-        ro = getattr(self, "_rollout", None)
+        ro = self._rollout
         if ro is not None and tm is not None:
             # the RL library's rollout rows (learner.RolloutStorage): written from the manager-owned buffers of this step
-            pol = next((m for m in self.managers["observation"] if m.name == ro.obs_name), None)
-            ro.write(pol._last_out if pol is not None else obs, rewards, terminated, truncated)
+            ro.write(ro._om._last_out, rewards, terminated, truncated)
         self._end_step()
         return obs, rewards, terminated, truncated, self.extras
 

@@ -16,6 +16,7 @@ int post_step(const GfPostRefs* r, const GfContactArgs* const* mgrs, int num_mgr
 int chain_a_try(const GfOp* ops, int i, int num_ops, hipStream_t s, int* rc, DeferredFlags* deferred);   // gf_chain.hip
 int chain_b_try(const GfOp* ops, int i, int num_ops, hipStream_t s, int* rc, DeferredFlags* deferred);
 int gait_launch(const GfGaitArgs* a, hipStream_t s, bool flags_all);                                      // gf_gait.hip
+int action_scene_try(const GfActionArgs* act, const GfSynthSceneArgs* a, hipStream_t s, int* rc);           // gf_scene.hip
 int unroll_pair(const GfHistoryUnrollArgs* a, const GfHistoryUnrollArgs* b, hipStream_t s, int* fused);   // gf_unroll.hip
 }
 
@@ -260,7 +261,15 @@ GF_EXPORT int gf_run_ops(const GfOp* ops, int num_ops, void* stream, int* failed
         int rc = GF_OK;
         const void* a = ops[i].args;
         switch (ops[i].phase) {
-            case GF_PHASE_ACTION: rc = gf_action_step((const GfActionArgs*)a, stream); break;
+            case GF_PHASE_ACTION: {
+                // the stand-in scene tick directly behind it streams the same rows with the same lanes: one launch for both, the
+                // targets stay in registers (gf_scene.hip; with an external simulator the two ops are never adjacent)
+                if (i + 1 < num_ops && ops[i + 1].phase == GF_PHASE_SCENE && ops[i + 1].args) {
+                    const int used = gf::action_scene_try((const GfActionArgs*)a, (const GfSynthSceneArgs*)ops[i + 1].args, s, &rc);
+                    if (used > 0) { i += used - 1; break; }
+                }
+                rc = gf_action_step((const GfActionArgs*)a, stream);
+            } break;
             case GF_PHASE_CONTACT: {
                 // consecutive ContactManagers over the same scene arrays share one launch (slot ids read once for all of them)
                 const GfContactArgs* run[4] = {(const GfContactArgs*)a};

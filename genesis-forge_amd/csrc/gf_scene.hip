@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "gf_action_row.h"
 #include "gf_launch.h"
 
 namespace gf {
@@ -156,10 +157,64 @@ constexpr int kSynthDofLanes = kSynthTileBlock - GF_WAVE;
 // no LDS access across this point
 __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_wave_barrier(); }
 
-template <int DV, int TE>
-__device__ __forceinline__ void synth_dof_tile(const GfSynthSceneArgs& a, const int64_t n0, const int rows, const int t) {
+// FOLD: the action phase of the step runs here too (gf_action_row.h).  The lanes that stream the tile's joint rows are the lanes
+// that own the same float4s of the flat action stream, so the targets never leave the registers between the two phases: every
+// load of the lane (raw actions, previous actions, joint positions) is issued before the first use, the row code runs, the
+// bookkeeping rows and the targets are stored as the action kernel stores them, and the joints take the targets from the registers.
+template <int DV, int TE, bool FOLD = false>
+__device__ __forceinline__ void synth_dof_tile(const GfSynthSceneArgs& a, const GfActionArgs& act, const int64_t n0, const int rows, const int t) {
     const float dt = a.dt, rate = a.joint_rate;
-    if (DV > 0) {
+    if constexpr (FOLD) {
+        static_assert(DV > 0, "the fold moves float4s");
+        constexpr int kIt = (TE * (DV > 0 ? DV : 1) + kSynthDofLanes - 1) / kSynthDofLanes;
+        const int cnt = rows * DV;
+        const int64_t f0 = n0 * DV;   // the tile's first float4 in the flat [N·D] streams
+        const float4* x4 = reinterpret_cast<const float4*>(act.actions_in) + f0;
+        const bool keep = act.env_actions != nullptr;
+        float4* e4 = reinterpret_cast<float4*>(keep ? act.env_actions : act.targets) + f0;
+        float4* l4 = reinterpret_cast<float4*>(keep ? act.env_last_actions : act.targets) + f0;
+        float4* t4 = reinterpret_cast<float4*>(act.targets) + f0;
+        float4* p4 = reinterpret_cast<float4*>(a.dof_pos) + f0;
+        float4* v4 = reinterpret_cast<float4*>(a.dof_vel) + f0;
+        const int mode = act.mode;
+        int flags = 0;
+        // a lane past the tile re-reads the tile's last float4, and without bookkeeping buffers the raw actions stand in for the
+        // previous ones: no branch around the loads, so all of them — with one float4 per lane the constants too, with more their
+        // registers are not worth the lost occupancy — are in flight before the first wait
+        constexpr bool kConstsFirst = kIt == 1;
+        const float4* q4 = keep ? e4 : x4;
+        float4 x[kIt], pv[kIt], dp[kIt];
+        ActionConsts4 c0;
+#pragma unroll
+        for (int k = 0; k < kIt; ++k) {
+            const int i = t + k * kSynthDofLanes < cnt ? t + k * kSynthDofLanes : cnt - 1;
+            x[k] = x4[i];
+            pv[k] = q4[i];
+            dp[k] = p4[i];
+            if constexpr (kConstsFirst) c0 = action_consts4(act, 4 * (i % DV), mode);   // (the tile starts at a row, so DOF = 4·(i mod DV))
+        }
+#pragma unroll
+        for (int k = 0; k < kIt; ++k) {
+            const int i = t + k * kSynthDofLanes;
+            if constexpr (!kConstsFirst) c0 = action_consts4(act, 4 * ((i < cnt ? i : cnt - 1) % DV), mode);
+            float4 last, actions, tg;
+            int fl = 0;
+            action_row4(act, c0, mode, x[k], pv[k], last, actions, tg, fl);
+            float4 v, p = dp[k];
+            synth_joint(tg.x, p.x, v.x, rate, dt);
+            synth_joint(tg.y, p.y, v.y, rate, dt);
+            synth_joint(tg.z, p.z, v.z, rate, dt);
+            synth_joint(tg.w, p.w, v.w, rate, dt);
+            if (i < cnt) {
+                flags |= fl;
+                if (keep) { l4[i] = last; e4[i] = actions; }
+                t4[i] = tg;
+                v4[i] = v;
+                p4[i] = p;
+            }
+        }
+        action_flags_commit(act, flags);   // whole waves get here
+    } else if (DV > 0) {
         constexpr int kIt = DV > 0 ? (TE * DV + kSynthDofLanes - 1) / kSynthDofLanes : 1;
         const int cnt = rows * DV;
         const float4* t4 = reinterpret_cast<const float4*>(a.targets) + n0 * DV;
@@ -197,8 +252,9 @@ __device__ __forceinline__ void synth_dof_tile(const GfSynthSceneArgs& a, const 
 }
 
 // wave 0: lane = env of the tile; s3 is this wave's LDS, 3 × [TE·3] floats.  Returns the lane's new base state (lane < rows).
-template <int TE>
-__device__ __forceinline__ void synth_base_tile(const GfSynthSceneArgs& a, const int64_t n0, const int rows, const int lane,
+// FOLD: episode_length[n] += 1 of the action phase (genesis_env.py:197) for the lane's env, its load issued with the others.
+template <int TE, bool FOLD = false>
+__device__ __forceinline__ void synth_base_tile(const GfSynthSceneArgs& a, const GfActionArgs& act, const int64_t n0, const int rows, const int lane,
                                                 float (&s3)[3][TE * 3], SynthBase& out) {
     constexpr int kJ = (TE * 3 + GF_WAVE - 1) / GF_WAVE;
     const int cnt = rows * 3;
@@ -214,6 +270,11 @@ __device__ __forceinline__ void synth_base_tile(const GfSynthSceneArgs& a, const
     }
     const bool mine = lane < rows;
     const float4 q4 = load_quat(a.quat, n0 + (mine ? lane : rows - 1));
+    int32_t ep = 0;
+    if constexpr (FOLD) {   // (without the counter the lane reads a word of its quaternion instead: no branch around the load)
+        const int32_t* e = act.episode_length ? act.episode_length : reinterpret_cast<const int32_t*>(a.quat);
+        ep = e[n0 + (mine ? lane : rows - 1)];
+    }
     const SynthDraws r = synth_draws(a, (uint32_t)(n0 + lane) + a.env_offset);
     // the Philox rounds run while the loads are in flight: the draws are pinned here, ahead of the first LDS write (which waits
     // for the loads); left alone, the compiler sinks the rounds to their first use behind that wait
@@ -243,6 +304,9 @@ __device__ __forceinline__ void synth_base_tile(const GfSynthSceneArgs& a, const
         if (i < cnt) { pos[i] = yp; lin[i] = yv; ang[i] = yw; }
     }
     if (mine) reinterpret_cast<float4*>(a.quat)[n0 + lane] = make_float4(out.q[0], out.q[1], out.q[2], out.q[3]);
+    if constexpr (FOLD) {
+        if (mine && act.episode_length) act.episode_length[n0 + lane] = ep + 1;
+    }
 }
 
 template <int DV>
@@ -254,11 +318,13 @@ __global__ __launch_bounds__(kEnvBlock) void synth_scene_kernel(const GfSynthSce
 }
 
 // The tick of tile [n0, n0 + rows) by a whole workgroup (see above): wave 0 returns the base state of env n0 + lane in `b`.
-template <int DV, int TE>
-__device__ __forceinline__ void synth_tick_tile(const GfSynthSceneArgs& a, const int64_t n0, const int rows, float (&s3)[3][TE * 3], SynthBase& b) {
+// (`act` is read only with FOLD)
+template <int DV, int TE, bool FOLD = false>
+__device__ __forceinline__ void synth_tick_tile(const GfSynthSceneArgs& a, const GfActionArgs& act, const int64_t n0, const int rows,
+                                                float (&s3)[3][TE * 3], SynthBase& b) {
     const int tid = threadIdx.x;
-    if (tid >= GF_WAVE) synth_dof_tile<DV, TE>(a, n0, rows, tid - GF_WAVE);
-    else synth_base_tile<TE>(a, n0, rows, tid, s3, b);
+    if (tid >= GF_WAVE) synth_dof_tile<DV, TE, FOLD>(a, act, n0, rows, tid - GF_WAVE);
+    else synth_base_tile<TE, FOLD>(a, act, n0, rows, tid, s3, b);
 }
 
 // A scene without per-link outputs or contacts (the benchmark's): workgroup b ticks envs [64b, 64b+64), the tile workgroup b of
@@ -269,7 +335,23 @@ __global__ __launch_bounds__(kSynthTileBlock) void synth_scene_tile_kernel(const
     const int64_t n0 = (int64_t)blockIdx.x * GF_WAVE;
     const int rows = (int)((int64_t)a.num_envs - n0 < GF_WAVE ? (int64_t)a.num_envs - n0 : GF_WAVE);
     SynthBase b;
-    synth_tick_tile<DV, GF_WAVE>(a, n0, rows, s3, b);
+    synth_tick_tile<DV, GF_WAVE>(a, GfActionArgs{}, n0, rows, s3, b);
+}
+
+// The action phase and the tick of a recorded step in ONE launch (gf_run_ops folds an action op directly in front of a scene op):
+// the `upkeep` leading workgroups keep the statistics ring as they do in action_kernel, tile b is workgroup b + upkeep (upkeep is
+// a multiple of 8: the tile stays on its XCD).  Same statements per element as the two launches, so the same bits.
+template <int DV>
+__global__ __launch_bounds__(kSynthTileBlock) void action_scene_tile_kernel(const GfActionArgs act, const GfSynthSceneArgs a, const int upkeep) {
+    if ((int)blockIdx.x < upkeep) {
+        action_upkeep(act, upkeep);
+        return;
+    }
+    __shared__ float s3[3][GF_WAVE * 3];
+    const int64_t n0 = (int64_t)(blockIdx.x - upkeep) * GF_WAVE;
+    const int rows = (int)((int64_t)a.num_envs - n0 < GF_WAVE ? (int64_t)a.num_envs - n0 : GF_WAVE);
+    SynthBase b;
+    synth_tick_tile<DV, GF_WAVE, true>(a, act, n0, rows, s3, b);
 }
 
 // Per-link outputs (orientation, velocity, position of scene link l of env n; flat index gid = n·NL + l) from the base state the
@@ -355,15 +437,14 @@ __device__ __forceinline__ void synth_contact_one(const GfSynthSceneArgs& a, con
 // element, so the outputs are bit-identical to the two-launch version and the oracle.
 // TE = envs per workgroup: 64 (the tile of the action / post-physics kernels, same XCD) when that still fills the chip, 16 below
 // ~32 k envs (4 096 envs are 64 tiles of 64 — a quarter of the CUs — but 256 tiles of 16).
-template <int DV, int TE, bool SPLIT>
-__global__ __launch_bounds__(kSynthTileBlock) void synth_tile_kernel(const GfSynthSceneArgs a, const int links, const int contacts) {
-    __shared__ float s_base[TE][13];   // p(3) q(4) v(3) w(3)
-    __shared__ float s3[3][SPLIT ? TE * 3 : 1];
-    const int64_t n0 = (int64_t)blockIdx.x * TE;
+template <int DV, int TE, bool SPLIT, bool FOLD = false>
+__device__ __forceinline__ void synth_tile_body(const GfSynthSceneArgs& a, const GfActionArgs& act, const int64_t n0, const int links, const int contacts,
+                                                float (&s_base)[TE][13], float (&s3)[3][SPLIT ? TE * 3 : 1]) {
+    static_assert(SPLIT || !FOLD, "only the split tick folds the action phase");
     const int rows = (int)((int64_t)a.num_envs - n0 < TE ? (int64_t)a.num_envs - n0 : TE);
     const int tid = threadIdx.x;
     SynthBase b;
-    if constexpr (SPLIT) synth_tick_tile<DV, TE>(a, n0, rows, s3, b);
+    if constexpr (SPLIT) synth_tick_tile<DV, TE, FOLD>(a, act, n0, rows, s3, b);
     else if (tid < rows) synth_state_body<DV>(a, n0 + tid, b);
     if (tid < rows) {
         float* r = s_base[tid];
@@ -389,6 +470,99 @@ __global__ __launch_bounds__(kSynthTileBlock) void synth_tile_kernel(const GfSyn
     }
 }
 
+template <int DV, int TE, bool SPLIT>
+__global__ __launch_bounds__(kSynthTileBlock) void synth_tile_kernel(const GfSynthSceneArgs a, const int links, const int contacts) {
+    __shared__ float s_base[TE][13];   // p(3) q(4) v(3) w(3)
+    __shared__ float s3[3][SPLIT ? TE * 3 : 1];
+    synth_tile_body<DV, TE, SPLIT>(a, GfActionArgs{}, (int64_t)blockIdx.x * TE, links, contacts, s_base, s3);
+}
+
+// … and with the action phase folded in, as action_scene_tile_kernel
+template <int DV, int TE>
+__global__ __launch_bounds__(kSynthTileBlock) __attribute__((amdgpu_num_sgpr(96))) void action_synth_tile_kernel(const GfActionArgs act, const GfSynthSceneArgs a, const int links, const int contacts,
+                                                                            const int upkeep) {
+    if ((int)blockIdx.x < upkeep) {
+        action_upkeep(act, upkeep);
+        return;
+    }
+    __shared__ float s_base[TE][13];
+    __shared__ float s3[3][TE * 3];
+    synth_tile_body<DV, TE, true, true>(a, act, (int64_t)(blockIdx.x - upkeep) * TE, links, contacts, s_base, s3);
+}
+
+// host side of the fold (gf_action.hip)
+int action_validate(const GfActionArgs* a);
+bool action_vec4(const GfActionArgs* a);
+bool action_const4(const GfActionArgs* a);
+
+static bool env_switch_on(const char* name) {   // set, not empty and not "0"; read per call so one process can run both ways
+    const char* v = getenv(name);
+    return v && v[0] && strcmp(v, "0") != 0;
+}
+
+struct SynthPlan {
+    bool links, contacts, small;
+    int dv;
+};
+static SynthPlan synth_plan(const GfSynthSceneArgs* a) {
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    const bool rows16 = (a->num_dofs % 4 == 0) && al16(a->targets) && al16(a->dof_pos) && al16(a->dof_vel);
+    SynthPlan p;
+    p.links = (a->links_quat_out || a->links_vel_out || a->links_pos_out) && a->num_scene_links > 0;
+    p.contacts = a->num_contacts > 0 && a->contact_force_out;
+    p.dv = !rows16 ? 0 : (a->num_dofs == 12 ? 3 : (a->num_dofs == 28 ? 7 : 0));
+    p.small = a->num_envs < 32768;
+    return p;
+}
+
+// What gf_synth_scene_step checks before it launches
+int scene_validate(const GfSynthSceneArgs* a) {
+    if (!a || !a->pos || !a->quat || !a->lin_vel || !a->ang_vel || !a->dof_pos || !a->dof_vel || !a->targets) return GF_E_NULL;
+    if (a->num_envs < 0 || a->num_dofs <= 0 || a->num_contacts < 0) return GF_E_RANGE;
+    if (a->num_contacts > 0 && a->contact_force_out && (!a->contact_pos_out || !a->link_a_out || !a->link_b_out || a->num_scene_links < 2)) return GF_E_NULL;
+    if (reinterpret_cast<uintptr_t>(a->quat) & 15u) return GF_E_UNSUPPORTED;
+    if (a->links_quat_out && (reinterpret_cast<uintptr_t>(a->links_quat_out) & 15u)) return GF_E_UNSUPPORTED;
+    return GF_OK;
+}
+
+// gf_run_ops, action op `act` directly in front of scene op `a`: run the pair as one launch when that is possible.
+// Returns 0: not folded, nothing enqueued — the caller runs the two ops through their entry points as ever;
+//         1: the action op fails its entry point's validation (*rc), nothing enqueued;
+//         2: the scene op fails its validation (*rc), nothing enqueued — or both ops are done, in one launch (*rc its status).
+// Both ops are validated BEFORE the fold conditions are looked at, so with the switches in their default position an invalid scene op
+// behind a valid action op leaves nothing enqueued even for a pair that would never fold (D = 5, say); when the peephole is off
+// (GF_FOLD_ACTION=0, GF_SCENE_LEGACY, a profiled action / scene phase: 0 is returned before any validation) the action launch is
+// enqueued and then the scene op fails, as it always did.  The return codes and the failed index are the same either way.
+// GF_FOLD_ACTION=0 keeps the two launches (A/B runs, tests/test_action_fold.py).
+int action_scene_try(const GfActionArgs* act, const GfSynthSceneArgs* a, hipStream_t s, int* rc) {
+    const char* sw = getenv("GF_FOLD_ACTION");
+    if (sw && strcmp(sw, "0") == 0) return 0;
+    if (env_switch_on("GF_SCENE_LEGACY")) return 0;
+    if (g_prof.phase == GF_PHASE_ACTION || g_prof.phase == GF_PHASE_SCENE) return 0;   // a profiled phase keeps its own launch
+    if ((*rc = action_validate(act)) != GF_OK) return 1;
+    if ((*rc = scene_validate(a)) != GF_OK) return 2;
+    if (act->num_envs <= 0 || act->num_envs != a->num_envs || act->num_dofs != a->num_dofs || a->targets != act->targets) return 0;
+    if (!action_vec4(act) || !action_const4(act)) return 0;
+    const SynthPlan p = synth_plan(a);
+    if (p.dv == 0) return 0;
+    const int upkeep = action_upkeep_blocks(act);
+    const dim3 tb(kSynthTileBlock);
+    if (p.links || p.contacts) {
+        const dim3 tg(env_grid(a->num_envs, p.small ? 16 : 64) + upkeep);
+#define GF_FOLD_TILE(DVV)                                                                                                        \
+        if (p.small) klaunch(action_synth_tile_kernel<DVV, 16>, tg, tb, 0, s, *act, *a, (int)p.links, (int)p.contacts, upkeep);   \
+        else klaunch(action_synth_tile_kernel<DVV, 64>, tg, tb, 0, s, *act, *a, (int)p.links, (int)p.contacts, upkeep)
+        if (p.dv == 3) { GF_FOLD_TILE(3); } else { GF_FOLD_TILE(7); }
+#undef GF_FOLD_TILE
+    } else {
+        const dim3 tg(env_grid(a->num_envs) + upkeep);
+        if (p.dv == 3) klaunch(action_scene_tile_kernel<3>, tg, tb, 0, s, *act, *a, upkeep);
+        else klaunch(action_scene_tile_kernel<7>, tg, tb, 0, s, *act, *a, upkeep);
+    }
+    *rc = launch_status();
+    return 2;
+}
+
 }  // namespace gf
 
 extern "C" __attribute__((visibility("default"))) int gf_entity_rotate(const GfRotateArgs* a, void* stream) {
@@ -406,27 +580,20 @@ extern "C" __attribute__((visibility("default"))) int gf_entity_rotate(const GfR
 }
 
 extern "C" __attribute__((visibility("default"))) int gf_synth_scene_step(const GfSynthSceneArgs* a, void* stream) {
-    if (!a || !a->pos || !a->quat || !a->lin_vel || !a->ang_vel || !a->dof_pos || !a->dof_vel || !a->targets) return GF_E_NULL;
-    if (a->num_envs < 0 || a->num_dofs <= 0 || a->num_contacts < 0) return GF_E_RANGE;
-    if (a->num_contacts > 0 && a->contact_force_out && (!a->contact_pos_out || !a->link_a_out || !a->link_b_out || a->num_scene_links < 2)) return GF_E_NULL;
-    if (reinterpret_cast<uintptr_t>(a->quat) & 15u) return GF_E_UNSUPPORTED;
-    if (a->links_quat_out && (reinterpret_cast<uintptr_t>(a->links_quat_out) & 15u)) return GF_E_UNSUPPORTED;
+    const int valid = gf::scene_validate(a);
+    if (valid != GF_OK) return valid;
     if (a->num_envs == 0) return GF_OK;
     hipStream_t s = (hipStream_t)stream;
     gf::PhaseScope scope(GF_PHASE_SCENE, s);
     scope.begin_bracket();
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    const bool rows16 = (a->num_dofs % 4 == 0) && al16(a->targets) && al16(a->dof_pos) && al16(a->dof_vel);
     const unsigned grid = gf::env_grid(a->num_envs);
-    const bool links = (a->links_quat_out || a->links_vel_out || a->links_pos_out) && a->num_scene_links > 0;
-    const bool contacts = a->num_contacts > 0 && a->contact_force_out;
-    const int dv = !rows16 ? 0 : (a->num_dofs == 12 ? 3 : (a->num_dofs == 28 ? 7 : 0));
+    const gf::SynthPlan plan = gf::synth_plan(a);
+    const bool links = plan.links, contacts = plan.contacts, small = plan.small;
+    const int dv = plan.dv;
     // GF_SCENE_LEGACY=1: the lane-per-env tick (A/B runs and tests/test_scene_tile.py); read per call so one process can run both
-    const char* legacy_env = getenv("GF_SCENE_LEGACY");
-    const bool legacy = legacy_env && legacy_env[0] && strcmp(legacy_env, "0") != 0;
+    const bool legacy = gf::env_switch_on("GF_SCENE_LEGACY");
     if (links || contacts) {   // tick + per-link rows + contact slots of a 64-env tile in one launch
         const dim3 tb(gf::kSynthTileBlock);
-        const bool small = a->num_envs < 32768;
         const dim3 tg(small ? gf::env_grid(a->num_envs, 16) : grid);
 #define GF_SYNTH_TILE(DVV, SPLIT)                                                                                      \
         if (small) gf::klaunch(gf::synth_tile_kernel<DVV, 16, SPLIT>, tg, tb, 0, s, *a, (int)links, (int)contacts);   \

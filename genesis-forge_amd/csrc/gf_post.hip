@@ -1,22 +1,19 @@
-// gf_post.hip — fused post-physics step: termination → reward → command.step → reset of done envs →
-// command.reset → observations (managed_env.py:303-326) as ONE launch.
-//
-// Every phase after scene.step() is per-env work over the same state, so one lane carries its env through
-// all of them with that state in registers:
-//   * pos / quat / lin / ang / the [N,D] rows / commands / episode_length are loaded ONCE, up front, all
-//     loads in flight together (straight-line load stream, zero-pad redirection, pinned kernarg pointers —
-//     see gf_reward.hip);
-//   * termination masks, the reward fold and the per-term episode sums (LDS-DMA prefetched) are evaluated by
-//     the shared term bodies of gf_terms.h — the same code the per-phase kernels run;
-//   * the reset of done envs is applied to the registers as well as to memory, so the observation that
-//     follows needs no reload: it reads post-reset dof_pos / dof_vel / velocities / commands from registers,
-//     and — reproducing the reference's stale EntityManager cache (entity_manager.py:163-167,189-195) — the
-//     PRE-reset quaternion;
-//   * the reward manager's reset (sum/seconds → log, sum ← 0) is folded into the sum update itself, which
-//     removes a whole read-modify-write pass over the [T,N] sums;
-//   * each wave assembles its [64, O] observation tile in LDS and streams it out with coalesced stores.
-// Semantics are, by construction, those of calling the phase entry points in sequence (the oracle twin does
-// exactly that); tests compare the two paths bit for bit.
+// gf_post.hip — host side of the fused post-physics step: termination → reward → command.step → reset of done envs →
+// command.reset → observations (managed_env.py:303-326) as ONE launch.  The kernel itself is post_ws_kernel<P> (gf_post_ws.h);
+// this file decides whether a step can run on it, describes the step to it and picks the program it runs.
+//   * pack() checks that the per-phase descriptors of a GfPostRefs describe one fusable step — the same env count, seed and
+//     masks in every phase, buffers that alias only where the kernel expects them to, sizes inside the kernel's tables — and
+//     packs them into one GfPostArgs (gf_post_args.h): shared views deduplicated, term / item slots remapped onto them, the
+//     `needs` bits that say which per-env inputs the launch loads.  Anything else is GF_E_UNSUPPORTED and the caller runs the
+//     phases one by one (GF_POST_WHY=1 names the rule).
+//   * fold_contacts() adds the scene's ContactManagers as a phase in front of the others (GfPostArgs.cfold), or refuses and
+//     leaves the contact kernel a launch of its own.
+//   * the program registry: the static programs of gf_post_programs.h, the programs compiled at run time and registered
+//     through gf_post_program_register, and select_program(), which matches a packed descriptor against their signatures.
+//   * post_launch() sizes the LDS for the selected program and launches it: a run-time compiled program, a built-in program,
+//     or the table interpreter Interp<DV, TAIL> for the step's DOF count.
+// Semantics are, by construction, those of calling the phase entry points in sequence (the oracle twin does exactly that);
+// tests compare the two paths bit for bit.
 // Algorithmic traffic, Go2 command config: R 13·4 + 5 rows·48 + cmd 12 + ep/max 8 + secs 4 + sums 24 = 340,
 // W masks 2 + reward 4 + sums 24 + secs 4 + obs 192 = 226  →  566 B/env.
 #include <dlfcn.h>
@@ -33,459 +30,8 @@
 
 namespace gf {
 
-template <int DV>
-__global__ __launch_bounds__(kEnvBlock) void post_kernel(const GfPostArgs karg) {
-    // The 2.7 KB descriptor is staged into LDS once, with vector loads (all 42 lines in flight together), and every
-    // later field read is a ds_read.  Reading it in place would cost one dependent, uncached scalar load per term /
-    // item / field group: the kernarg block is rewritten by the host for every launch and lives in memory the scalar
-    // cache does not keep, and in-kernel stamps showed ≈ 0.35 µs per table row — more than the arithmetic of the row.
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int kArgVec = (int)(sizeof(GfPostArgs) / 16);
-    {
-        const auto* src = (const __attribute__((address_space(4))) f32x4*)__builtin_amdgcn_kernarg_segment_ptr();
-        f32x4* dst = reinterpret_cast<f32x4*>(lds);
-        for (int i = threadIdx.x; i < kArgVec; i += kEnvBlock) dst[i] = src[i];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    const GfPostArgs& a = *reinterpret_cast<const GfPostArgs*>(lds);
-    GF_STAMP(1);
-    float* lds_sums = lds + kArgVec * 4;                     // [num_rew][64]
-    float* lds_aux = lds_sums + kPostMaxReward * kEnvBlock;  // [kPostAuxRows][64] per-lane scratch for rolled Philox loops (dof reset noise)
-    float* tile = lds_aux + kPostAuxRows * kEnvBlock;                  // [64][O+1]
-
-    const int lane = threadIdx.x;
-    const int64_t N = uni(a.num_envs);
-    const int64_t n0 = (int64_t)blockIdx.x * kEnvBlock;
-    const int64_t n_raw = n0 + lane;
-    const bool live = n_raw < N;
-    const int64_t n = live ? n_raw : N - 1;
-    const uint32_t e = (uint32_t)n;
-    const uint32_t genv = e + uni(a.env_offset);
-    const int D = uni(a.num_dofs);
-    const uint32_t needs = uni(a.needs);
-    const int n_term = uni(a.num_term), n_rew = uni(a.num_rew), n_cmd = uni(a.n_cmd), n_obs = uni(a.n_obs);
-    const uint64_t seed = uni(a.seed);
-    constexpr int R = DV;
-
-    // ---- 0. episode-sum columns: global -> LDS without VGPRs or waits ------------------------------------
-    const bool logging = uni(a.logging) != 0;
-    float* const k_sums = uni(a.episode_sums);
-    if (logging)
-        for (int k = 0; k < n_rew; ++k)
-            __builtin_amdgcn_global_load_lds(k_sums + (int64_t)uni(a.rterms[k].row) * N + n, lds_sums + k * kEnvBlock, 4, 0, 0);
-
-    // ---- 1. all per-env inputs, one straight-line burst ------------------------------------------------------
-    const float *k_pos = uni(a.pos), *k_quat = uni(a.quat), *k_lin = uni(a.lin_vel), *k_ang = uni(a.ang_vel), *k_dof = uni(a.dof_pos),
-                *k_dvel = uni(a.dof_vel);
-    const float *k_tgt = uni(a.targets), *k_act = uni(a.env_actions), *k_last = uni(a.env_last_actions), *k_def = uni(a.default_dof_pos),
-                *k_secs = uni(a.episode_seconds);
-    const int32_t *k_ep = uni(a.episode_length), *k_max = uni(a.max_episode_length);
-
-    const float4 q = ldg4(gsel((needs & PN_QUAT) != 0, k_quat, 4u * e));
-    const GF_GLOBAL float* pp = gsel((needs & PN_POS) != 0, k_pos, 3u * e);
-    const GF_GLOBAL float* lp = gsel((needs & PN_LIN) != 0, k_lin, 3u * e);
-    const GF_GLOBAL float* ap = gsel((needs & PN_ANG) != 0, k_ang, 3u * e);
-    V3 pos{pp[0], pp[1], pp[2]}, lin{lp[0], lp[1], lp[2]}, ang{ap[0], ap[1], ap[2]};
-    const int ep_len = *gsel((needs & PN_EPLEN) != 0, k_ep, e);
-    const int max_len = *gsel((needs & PN_MAXLEN) != 0, k_max, e);
-    const float secs_in = *gsel(n_rew >= 0 && k_secs != nullptr, k_secs, e);
-
-    const uint32_t ro = e * (uint32_t)D;
-    float4 r_pos[R], r_vel[R], r_tgt[R], r_act[R], r_last[R], r_def[R];
-    {
-        const GF_GLOBAL float* p0 = gsel((needs & PN_DOFPOS) != 0, k_dof, ro);
-        const GF_GLOBAL float* p1 = gsel((needs & PN_DOFVEL) != 0, k_dvel, ro);
-        const GF_GLOBAL float* p2 = gsel((needs & PN_TARGETS) != 0, k_tgt, ro);
-        const GF_GLOBAL float* p3 = gsel((needs & PN_ACTIONS) != 0, k_act, ro);
-        const GF_GLOBAL float* p4 = gsel((needs & PN_LAST) != 0, k_last, ro);
-        const GF_GLOBAL float* p5 = gsel(k_def != nullptr, k_def, 0u);
-#pragma unroll
-        for (int c = 0; c < DV; ++c) {
-            r_pos[c] = ldg4(p0 + 4 * c); r_vel[c] = ldg4(p1 + 4 * c); r_tgt[c] = ldg4(p2 + 4 * c);
-            r_act[c] = ldg4(p3 + 4 * c); r_last[c] = ldg4(p4 + 4 * c); r_def[c] = ldg4(p5 + 4 * c);
-        }
-    }
-    // command rows of the stepped managers (≤ 2 managers × ≤ 4 ranges)
-    float cmd[GF_POST_MAX_CMD][kPostMaxRanges];
-#pragma unroll
-    for (int c = 0; c < GF_POST_MAX_CMD; ++c) {
-        const bool on = c < n_cmd;
-        const uint32_t w = on ? (uint32_t)uni(a.cmds[c].width) : 0u;
-        const GF_GLOBAL float* cp = gsel(on, on ? uni(a.cmds[c].command) : nullptr, e * w);
-#pragma unroll
-        for (int j = 0; j < kPostMaxRanges; ++j) cmd[c][j] = cp[(uint32_t)j < w ? j : 0];
-    }
-
-    GF_STAMP(2);
-    // ---- 2. derived per-env quantities (pre-reset) ----------------------------------------------------------------
-    const V3 blin = rot_inv(q, lin), bang = rot_inv(q, ang), grav = rot_inv(q, V3{0.f, 0.f, -1.f});
-    float dof_dev = 0.f, act_rate = 0.f;
-#pragma unroll
-    for (int c = 0; c < DV; ++c) {
-        dof_dev += fabsf(r_pos[c].x - r_def[c].x);
-        dof_dev += fabsf(r_pos[c].y - r_def[c].y);
-        dof_dev += fabsf(r_pos[c].z - r_def[c].z);
-        dof_dev += fabsf(r_pos[c].w - r_def[c].w);
-    }
-#pragma unroll
-    for (int c = 0; c < DV; ++c) {
-        float d;
-        d = r_last[c].x - r_act[c].x; act_rate += d * d;
-        d = r_last[c].y - r_act[c].y; act_rate += d * d;
-        d = r_last[c].z - r_act[c].z; act_rate += d * d;
-        d = r_last[c].w - r_act[c].w; act_rate += d * d;
-    }
-    GfStepStats* const k_stats = uni(a.stats);
-    GfStepStats* shard = k_stats ? stats_shard(k_stats) : nullptr;
-
-    GF_STAMP(3);
-    // ---- 3. termination (termination_manager.py:151-190) ---------------------------------------------------------------
-    TermRegs tr;
-    const int has_maxlen = uni(a.has_maxlen);
-    tr.ep_len = ep_len; tr.max_len = max_len; tr.has_maxlen = has_maxlen != 0; tr.pos = pos; tr.m = n;
-    tr.tilt_sin = clamp_max(norm2(grav.x, grav.y), 0.99f);
-    int term = 0, trunc = 0;
-    for (int k = 0; k < n_term; ++k) {
-        const GfTerm t = a.tterms[k];
-        int v = eval_termination_term(t, a, tr, (uint32_t)has_maxlen);
-        v = live ? v : 0;
-        if (t.flags & GF_TERM_FLAG_TIME_OUT) trunc |= v; else term |= v;
-        if (shard) {
-            const unsigned long long hit = __ballot(v);
-            if (hit && lane == 0) atomicAdd(&shard->term_fired[k], popc64(hit));
-        }
-    }
-    if (live) {
-        G(uni(a.terminated))[n_raw] = (uint8_t)term;
-        G(uni(a.truncated))[n_raw] = (uint8_t)trunc;
-    }
-    const bool done = live && (term | trunc);
-    const unsigned long long done_mask = __ballot(done);
-    if (shard && done_mask && lane == 0) atomicAdd(&shard->reset_count, popc64(done_mask));
-
-    GF_STAMP(4);
-    // ---- 4. reward (reward_manager.py:166-195) with the manager's reset (:197-222) folded into the sum update -----------
-    float* const k_reward = uni(a.reward);
-    if (n_rew >= 0 && k_reward) {
-        RewardRegs rr;
-        rr.pos = pos; rr.blin = blin; rr.bang = bang; rr.grav = grav; rr.dof_dev = dof_dev; rr.act_rate = act_rate; rr.terminated = term;
-        rr.n = n; rr.live = live;
-        const int c0 = uni(a.cmd_of_view[0]);
-        if (c0 >= 0) {
-            rr.cmd0[0] = c0 == 0 ? cmd[0][0] : cmd[1][0];
-            rr.cmd0[1] = c0 == 0 ? cmd[0][1] : cmd[1][1];
-            rr.cmd0[2] = c0 == 0 ? cmd[0][2] : cmd[1][2];
-        } else {
-            const float* v0 = uni(a.command[0].command);
-            const bool nv = v0 != nullptr;
-            const uint32_t w = nv ? (uint32_t)uni(a.command[0].width) : 0u;
-            const uint32_t st = nv ? (uint32_t)(uni(a.command[0].stride) ? uni(a.command[0].stride) : uni(a.command[0].width)) : 0u;
-            const GF_GLOBAL float* cp = gsel(nv, v0, e * st);
-            rr.cmd0[0] = cp[0]; rr.cmd0[1] = cp[w > 1 ? 1 : 0]; rr.cmd0[2] = cp[w > 2 ? 2 : 0];
-        }
-        const float dt = uni(a.dt);
-        const uint32_t log_mask = uni(a.reward_log_mask);
-        const float secs_new = secs_in + dt;
-        if (logging) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        float buf = 0.f;
-        const bool log_reset = logging && done_mask != 0;
-        for (int k = 0; k < n_rew; ++k) {
-            const GfTerm t = a.rterms[k];
-            float v = eval_reward_term(t, a, rr);
-            v = v * t.w;
-            buf += v;
-            if (logging) {
-                float s = lds_sums[k * kEnvBlock + lane] + v;
-                if (log_reset) {
-                    // RewardManager.reset: value /= seconds; mean → log; value ← 0 (zero-weight rows are not logged)
-                    const float per_sec = done ? s / secs_new : 0.f;
-                    if (shard && (log_mask & (1u << t.row))) {
-                        if (popc64(done_mask) > 4) {
-                            const double w = wave_sum((double)per_sec);
-                            if (lane == 0) unsafeAtomicAdd(&shard->reward_episode_sum[t.row], w);
-                        } else if (done) {
-                            unsafeAtomicAdd(&shard->reward_episode_sum[t.row], (double)per_sec);
-                        }
-                    }
-                    if (done) s = 0.f;
-                }
-                if (live) G(k_sums)[(int64_t)t.row * N + n_raw] = s;
-            }
-        }
-        if (live) {
-            G(k_reward)[n_raw] = buf;
-            G(const_cast<float*>(k_secs))[n_raw] = done ? 1e-10f : secs_new;
-        }
-        if (done && logging)
-            for (int row = 0; row < a.reward_rows; ++row)
-                if (a.uncovered_rows & (1u << row)) G(k_sums)[(int64_t)row * N + n_raw] = 0.f;
-    }
-
-    GF_STAMP(5);
-    // ---- 5. command.step: resample where episode_length % resample_steps == 0 (command_manager.py:152-162) --------------
-    bool cmd_dirty[GF_POST_MAX_CMD] = {false, false};
-#pragma unroll
-    for (int c = 0; c < GF_POST_MAX_CMD; ++c) {
-        if (c < n_cmd) {
-            const PostCmd cm = a.cmds[c];
-            const bool go = live && (ep_len % uni(cm.resample_steps)) == 0;
-            if (shard) {
-                const unsigned long long m = __ballot(go);
-                if (m && lane == 0) atomicAdd(&shard->resample_count, popc64(m));
-            }
-            if (go) {
-                const float4 u4 = draw_unit4(seed, cm.stream_step, genv, 0u);
-                const float nv[kPostMaxRanges] = {uniform_range(u4.x, cm.lo[0], cm.hi[0]), uniform_range(u4.y, cm.lo[1], cm.hi[1]),
-                                                  uniform_range(u4.z, cm.lo[2], cm.hi[2]), uniform_range(u4.w, cm.lo[3], cm.hi[3])};
-#pragma unroll
-                for (int j = 0; j < kPostMaxRanges; ++j)
-                    if (j < cm.width) cmd[c][j] = nv[j];
-                cmd_dirty[c] = true;
-            }
-        }
-    }
-
-    GF_STAMP(6);
-    // ---- 6. reset of done envs (managed_env.py:336-366), applied to memory AND to the registers the observation reads ----
-    float4 o_act[R];  // raw actions as the observation sees them
-#pragma unroll
-    for (int c = 0; c < DV; ++c) o_act[c] = r_act[c];
-    if (done) {
-        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if ((a.reset_env & 1) && a.env_actions) {
-            GF_GLOBAL f32x4* ra = reinterpret_cast<GF_GLOBAL f32x4*>(G(const_cast<float*>(k_act)) + n * D);
-            GF_GLOBAL f32x4* rl = reinterpret_cast<GF_GLOBAL f32x4*>(G(const_cast<float*>(k_last)) + n * D);
-#pragma unroll
-            for (int c = 0; c < DV; ++c) { ra[c] = f32x4{0.f, 0.f, 0.f, 0.f}; rl[c] = f32x4{0.f, 0.f, 0.f, 0.f}; o_act[c] = z4; }
-        }
-        if (a.reset_env & 2) G(const_cast<int32_t*>(k_ep))[n] = 0;
-        if (a.max_episode_length && a.max_random_scaling > 0.0f) {
-            const float u = draw_unit4(seed, a.stream_reset, genv, 0u).x;
-            const float rnd = uniform_range(u, -1.0f, 1.0f) * a.max_random_scaling;
-            G(const_cast<int32_t*>(k_max))[n] = (int32_t)rintf((float)a.base_max_episode_length + rnd);
-        }
-        for (int m = 0; m < a.n_air; ++m) {
-            const int L = a.air_links[m];
-            for (int s = 0; s < 4; ++s) {
-                GF_GLOBAL float* p = G(a.air_state[m][s]);
-                if (p)
-                    for (int l = 0; l < L; ++l) p[n * L + l] = 0.0f;
-            }
-        }
-        if (a.reset_dofs) {
-            GF_GLOBAL f32x4* dp = reinterpret_cast<GF_GLOBAL f32x4*>(G(const_cast<float*>(k_dof)) + n * D);
-            GF_GLOBAL f32x4* dv = reinterpret_cast<GF_GLOBAL f32x4*>(G(const_cast<float*>(k_dvel)) + n * D);
-            const float dof_noise = a.dof_noise_scale;
-            if (dof_noise != 0.0f) {
-                // one Philox block yields the four draws of columns 4+4c .. 4+4c+3 (they share counter (4+4c)>>2)
-#pragma nounroll
-                for (int c = 0; c < DV; ++c) {
-                    const float4 r4 = draw_unit4(seed, a.stream_reset, genv, (uint32_t)(1 + c));
-                    float* sc = lds_aux + (4 * c) * kEnvBlock + lane;
-                    sc[0 * kEnvBlock] = uniform_range(r4.x, -1.0f, 1.0f) * dof_noise;
-                    sc[1 * kEnvBlock] = uniform_range(r4.y, -1.0f, 1.0f) * dof_noise;
-                    sc[2 * kEnvBlock] = uniform_range(r4.z, -1.0f, 1.0f) * dof_noise;
-                    sc[3 * kEnvBlock] = uniform_range(r4.w, -1.0f, 1.0f) * dof_noise;
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < DV; ++c) {
-                float4 p = r_def[c];
-                if (dof_noise != 0.0f) {
-                    const float* sc = lds_aux + (4 * c) * kEnvBlock + lane;
-                    p.x = p.x + sc[0 * kEnvBlock];
-                    p.y = p.y + sc[1 * kEnvBlock];
-                    p.z = p.z + sc[2 * kEnvBlock];
-                    p.w = p.w + sc[3 * kEnvBlock];
-                }
-                r_pos[c] = p;
-                dp[c] = f32x4{p.x, p.y, p.z, p.w};
-                if (k_dvel) { dv[c] = f32x4{0.f, 0.f, 0.f, 0.f}; r_vel[c] = z4; }
-            }
-        }
-        if (a.scene_reset) {
-            GF_GLOBAL float* wp = G(const_cast<float*>(k_pos)) + 3 * n;
-            float np[3] = {a.reset_pos[0], a.reset_pos[1], a.reset_pos[2]};
-            float4 nq = make_float4(a.reset_quat[0], a.reset_quat[1], a.reset_quat[2], a.reset_quat[3]);
-            bool set_quat = a.set_quat != 0;
-            if (a.spawn_mode) {  // mdp.reset.randomize_terrain_position
-                float u[5];
-                spawn_draws(nullptr, n, seed, a.stream_reset, genv, a.spawn_rot_mask, u);
-                spawn_pose(a, u, np, &nq);
-                set_quat = a.spawn_set_quat != 0;
-            }
-            wp[0] = np[0]; wp[1] = np[1]; wp[2] = np[2];
-            if (set_quat) {
-                if (a.quat_stash) reinterpret_cast<GF_GLOBAL f32x4*>(G(a.quat_stash))[n] = f32x4{q.x, q.y, q.z, q.w};
-                reinterpret_cast<GF_GLOBAL f32x4*>(G(const_cast<float*>(k_quat)))[n] = f32x4{nq.x, nq.y, nq.z, nq.w};
-            }
-            if (a.zero_velocity) {
-                GF_GLOBAL float* wl = G(const_cast<float*>(k_lin)) + 3 * n;
-                GF_GLOBAL float* wa = G(const_cast<float*>(k_ang)) + 3 * n;
-                wl[0] = 0.f; wl[1] = 0.f; wl[2] = 0.f;
-                wa[0] = 0.f; wa[1] = 0.f; wa[2] = 0.f;
-                lin = V3{0.f, 0.f, 0.f};
-                ang = V3{0.f, 0.f, 0.f};
-                if (k_dvel) {
-                    GF_GLOBAL f32x4* dv = reinterpret_cast<GF_GLOBAL f32x4*>(G(const_cast<float*>(k_dvel)) + n * D);
-#pragma unroll
-                    for (int c = 0; c < DV; ++c) { dv[c] = f32x4{0.f, 0.f, 0.f, 0.f}; r_vel[c] = z4; }
-                }
-            }
-        }
-    }
-
-    // ---- 7. command.reset for done envs (command_manager.py:164-170) + write back changed commands ------------------------
-#pragma unroll
-    for (int c = 0; c < GF_POST_MAX_CMD; ++c) {
-        if (c < n_cmd) {
-            const PostCmd cm = a.cmds[c];
-            if (done) {
-                const float4 u4 = draw_unit4(seed, cm.stream_reset, genv, 0u);
-                const float nv[kPostMaxRanges] = {uniform_range(u4.x, cm.lo[0], cm.hi[0]), uniform_range(u4.y, cm.lo[1], cm.hi[1]),
-                                                  uniform_range(u4.z, cm.lo[2], cm.hi[2]), uniform_range(u4.w, cm.lo[3], cm.hi[3])};
-#pragma unroll
-                for (int j = 0; j < kPostMaxRanges; ++j)
-                    if (j < cm.width) cmd[c][j] = nv[j];
-                cmd_dirty[c] = true;
-            }
-            if (cmd_dirty[c] && live) {
-                GF_GLOBAL float* crow = G(cm.command) + n * cm.width;
-#pragma unroll
-                for (int j = 0; j < kPostMaxRanges; ++j)
-                    if (j < cm.width) crow[j] = cmd[c][j];
-            }
-        }
-    }
-
-    GF_STAMP(7);
-    // ---- 8. observations (observation_manager.py:218-256): post-reset state, pre-reset quaternion ------------------------
-    // a done env's velocities were zeroed above and rot_inv(q, 0) is exactly +0: no second rotation needed
-    const bool zeroed = done && a.scene_reset && a.zero_velocity;
-    const V3 o_lin = zeroed ? V3{0.f, 0.f, 0.f} : blin, o_ang = zeroed ? V3{0.f, 0.f, 0.f} : bang;
-    for (int m = 0; m < n_obs; ++m) {
-        const PostObs& ob = a.obs[m];
-        const int O = uni(ob.width), S = O + 1, H = uni(ob.history), n_items = uni(ob.num_items);
-        float* const ob_out = uni(ob.obs);
-        const float* const ob_prev = uni(ob.prev);
-        const uint64_t ob_stream = uni(ob.stream);
-        float* row = tile + lane * S;
-        int col = 0;
-        for (int i = 0; i < n_items; ++i) {
-            const GfObsItem it = ob.items[i];  // by value: the tile stores below must not force reloads of the item
-            const float it_scale = uni(it.scale), it_noise = uni(it.noise);
-            const ObsFin f{it_scale, it_scale != 1.0f};
-            switch (uni(it.op)) {
-                case GF_O_COMMAND: {
-                    const int owner = a.cmd_of_view[it.i0];
-                    if (owner >= 0) {
-#pragma unroll
-                        for (int j = 0; j < kPostMaxRanges; ++j)
-                            if (j < it.width) row[col + j] = obs_finish(f, owner == 0 ? cmd[0][j] : cmd[1][j], col + j);
-                    } else {
-                        const GfCommandView cv = a.command[it.i0];
-                        for (int j = 0; j < it.width; ++j) row[col + j] = obs_finish(f, G(cv.command)[n * cmd_stride(cv) + j], col + j);
-                    }
-                } break;
-                case GF_O_ANG_VEL_BODY:
-                case GF_O_LIN_VEL_BODY:
-                case GF_O_PROJ_GRAVITY: {
-                    const V3 v = it.op == GF_O_ANG_VEL_BODY ? o_ang : (it.op == GF_O_LIN_VEL_BODY ? o_lin : grav);
-                    row[col + 0] = obs_finish(f, v.x, col + 0);
-                    row[col + 1] = obs_finish(f, v.y, col + 1);
-                    row[col + 2] = obs_finish(f, v.z, col + 2);
-                } break;
-                case GF_O_DOF_POS: put_row<DV>(f, r_pos, row, col, 4 * DV); break;
-                case GF_O_DOF_VEL: put_row<DV>(f, r_vel, row, col, 4 * DV); break;
-                case GF_O_ACTIONS: put_row<DV>(f, r_tgt, row, col, 4 * DV); break;
-                case GF_O_RAW_ACTIONS: put_row<DV>(f, o_act, row, col, 4 * DV); break;
-                case GF_O_DOF_FORCE: {
-                    const GF_GLOBAL float* r = G(a.dof_force) + n * D;
-                    for (int j = 0; j < it.width; ++j) row[col + j] = obs_finish(f, r[j], col + j);
-                } break;
-                case GF_O_CONTACT_FORCE_NORM: {
-                    const GfContactView cv = a.contact[it.i0];
-                    const GF_GLOBAL float* r = G(cv.contacts) + n * cv.num_links * 3;
-                    for (int l = 0; l < it.width; ++l) row[col + l] = obs_finish(f, norm3(r[3 * l], r[3 * l + 1], r[3 * l + 2]), col + l);
-                } break;
-                default: break;
-            }
-            const int it_w = uni(it.width);
-            if (it_noise != 0.0f) {
-                // += uniform_(-1,1)*noise on the scaled value (observation_manager.py:247-250); kept as a rolled loop so the
-                // kernel contains ONE inlined Philox here instead of one per observation element
-                // (column c draws word c & 3 of Philox block c >> 2: one block per four columns the item covers)
-                const int c_end = col + it_w;
-#pragma nounroll
-                for (int b = col >> 2; b <= ((c_end - 1) >> 2); ++b) {
-                    const float4 u4 = draw_unit4(seed, ob_stream, genv, (uint32_t)b);
-                    const float uu[4] = {u4.x, u4.y, u4.z, u4.w};
-#pragma unroll
-                    for (int w4 = 0; w4 < 4; ++w4) {
-                        const int c = 4 * b + w4;
-                        if (c >= col && c < c_end) row[c] = row[c] + uniform_range(uu[w4], -1.0f, 1.0f) * it_noise;
-                    }
-                }
-            }
-            col += it_w;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        GF_STAMP(8);
-
-        const int rows = (int)((N - n0) < kEnvBlock ? (N - n0) : kEnvBlock);
-        const int64_t OH = (int64_t)O * H;
-        GF_GLOBAL float* out = G(ob_out) + n0 * OH;
-        if ((O & 3) == 0) {
-            const int o4 = O >> 2;
-            const int qstep = GF_WAVE / o4, rstep = GF_WAVE - qstep * o4;  // wave-uniform: one division per tile, not per element
-            int rw = lane / o4, c4 = lane - rw * o4;
-            for (int i = lane; i < rows * o4; i += GF_WAVE) {
-                const float* r = tile + rw * S + c4 * 4;
-                reinterpret_cast<GF_GLOBAL f32x4*>(out + rw * OH)[c4] = f32x4{r[0], r[1], r[2], r[3]};
-                rw += qstep; c4 += rstep;
-                if (c4 >= o4) { c4 -= o4; ++rw; }
-            }
-            if (H > 1) {
-                const int h4 = (O * (H - 1)) >> 2;
-                const GF_GLOBAL float* prev = G(ob_prev) + n0 * OH;
-                for (int i = lane; i < rows * h4; i += GF_WAVE) {
-                    const int rw = i / h4, j = i - rw * h4;
-                    reinterpret_cast<GF_GLOBAL f32x4*>(out + rw * OH + O)[j] = reinterpret_cast<const GF_GLOBAL f32x4*>(prev + rw * OH)[j];
-                }
-            }
-        } else {
-            for (int i = lane; i < rows * O; i += GF_WAVE) {
-                const int rw = i / O, cc = i - rw * O;
-                out[rw * OH + cc] = tile[rw * S + cc];
-            }
-            if (H > 1) {
-                const int hw = O * (H - 1);
-                const GF_GLOBAL float* prev = G(ob_prev) + n0 * OH;
-                for (int i = lane; i < rows * hw; i += GF_WAVE) {
-                    const int rw = i / hw, j = i - rw * hw;
-                    out[rw * OH + O + j] = prev[rw * OH + j];
-                }
-            }
-        }
-        // the tile is reused by the next observation manager
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_wave_barrier();
-    }
-    GF_STAMP(9);
-}
-
 // ------------------------------------------------------------------------------------------------------------
-// Host side: validate that the per-phase descriptors describe one fusable step and pack them.
+// pack(): validate that the per-phase descriptors describe one fusable step and pack them.
 // ------------------------------------------------------------------------------------------------------------
 static int cmd_slot_of_reward_op(int op) {
     switch (op) {
@@ -952,7 +498,7 @@ static int pack(const GfPostRefs* r, Packer& pk) {
     UNSUP((needs & PN_ANG) && !a.ang_vel);
     UNSUP((needs & PN_EPLEN) && !a.episode_length);
     // DOF rows are ceil(D / 4) float4 chunks (a last chunk of fewer than four floats is handled element by element, gf_post_args.h):
-    // 12 and 28 DOF have static programs / both kernel variants, every other count up to 32 a four-wave interpreter variant
+    // 12 and 28 DOF have static programs, every count up to 32 an interpreter variant
     const bool dofs_ok = D >= 1 && D <= 32;
     UNSUP((needs & (PN_DOFPOS | PN_DOFVEL | PN_TARGETS | PN_ACTIONS | PN_LAST)) && !dofs_ok);
     UNSUP((a.reset_dofs || (a.reset_env & 1)) && !dofs_ok);
@@ -979,7 +525,7 @@ ContactMgrL contact_mgr_image(const GfContactArgs* a);
 // a statistics block other than the step's, an observation-only launch, GF_OPT_FOLD_CONTACT = 0).
 static int fold_contacts(Packer& pk, const GfContactArgs* const* mgrs, int num) {
     GfPostArgs& a = pk.a;
-    UNSUP(!g_options[GF_OPT_FOLD_CONTACT] || g_options[GF_OPT_POST_VARIANT] == 0);
+    UNSUP(!g_options[GF_OPT_FOLD_CONTACT]);
     UNSUP(num < 1 || num > kFoldMaxMgr || a.obs_only);
     PostContact& f = a.cfold;
     int total = 0;
@@ -1170,32 +716,24 @@ int gf::post_launch(const gf::GfPostArgs& packed, hipStream_t s) {
 #endif
     int omax = 0;
     for (int m = 0; m < a.n_obs; ++m) omax = a.obs[m].width > omax ? a.obs[m].width : omax;
-    const size_t lds = sizeof(gf::GfPostArgs) + ((size_t)(gf::kPostMaxReward + gf::kPostAuxRows) * gf::kEnvBlock + (size_t)(omax + 1) * gf::kEnvBlock) * sizeof(float);
     // a folded contact phase stages the tile's slot ids in the LDS the later phases use (behind the interpreter's descriptor copy)
     const size_t fold_lds = a.cfold.num_mgr > 0 ? gf::fold_lds_bytes(a.cfold.num_contacts) : 0;
     auto with_fold = [&](size_t bytes, bool interp) {
         const size_t need = fold_lds ? fold_lds + (interp ? sizeof(gf::GfPostArgs) : 0) : 0;
         return (bytes > need ? bytes : need) + (size_t)gf::kWsTilesLdsFloats * sizeof(float);
     };
-    const unsigned grid1 = gf::env_grid(a.num_envs);
+    const unsigned grid = gf::env_grid(a.num_envs);
     gf::PhaseScope scope(GF_PHASE_POST, s);
-    bool any_ring = false;
-    for (int m = 0; m < a.n_obs; ++m) any_ring = any_ring || a.obs[m].ring != 0;
-    const bool ws_only = a.n_gait || a.roll_obs || a.roll_reward || a.roll_done || any_ring || a.term_done || a.no_reset || (a.num_dofs != 12 && a.num_dofs != 28);   // the one-wave variant has neither a gait manager nor rollout stores
-    const unsigned grid = grid1;
-    if (gf::g_options[GF_OPT_POST_VARIANT] == 0 && !ws_only) {
-        if (a.num_dofs == 28) GF_LAUNCH(scope, gf::post_kernel<7>, grid1, gf::kEnvBlock, lds, s, a);
-        else GF_LAUNCH(scope, gf::post_kernel<3>, grid1, gf::kEnvBlock, lds, s, a);
-    } else if (const int prog = select_program(a); prog >= kDynBase) {
+    if (const int prog = select_program(a); prog >= kDynBase) {
         // a program compiled at run time: the plugin's kernel handle, launched like any other (launch sink, dispatch events)
         const DynProgram& d = g_dyn[prog - kDynBase];
         const size_t lds_dyn = with_fold(d.lds_bytes(omax, a.n_gait), false);
         void* kargs[1] = {const_cast<gf::GfPostArgs*>(&a)};
         if (scope.active()) {
             scope.use_dispatch_events();
-            (void)hipExtLaunchKernel(d.kernel, dim3(grid1), dim3(gf::kWsBlock), kargs, lds_dyn, s, scope.start(), scope.stop(), 0);
+            (void)hipExtLaunchKernel(d.kernel, dim3(grid), dim3(gf::kWsBlock), kargs, lds_dyn, s, scope.start(), scope.stop(), 0);
         } else {
-            gf::sink_launch(d.kernel, dim3(grid1), dim3(gf::kWsBlock), lds_dyn, s, kargs);
+            gf::sink_launch(d.kernel, dim3(grid), dim3(gf::kWsBlock), lds_dyn, s, kargs);
         }
     } else if (prog) {
 #define GF_RUN(id, P) \

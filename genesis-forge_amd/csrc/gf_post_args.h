@@ -1,34 +1,23 @@
 // gf_post_args.h — packed descriptor of the fused post-physics launch and the small device helpers its kernels share
-// (gf_post.hip: single-wave interpreter; gf_post_ws.h: wave-specialised interpreter and the static programs).
+// (gf_post_ws.h: the wave-specialised kernel, as table interpreter and as static programs; gf_post.hip: its host side).
 #pragma once
 
 #include "gf_launch.h"
 #include "gf_terms.h"
 #include "gf_contact_tile.h"
 
-// Diagnostic build only (tools/stamp_post.hip, -DGF_STAMPS): lane 0 of one workgroup records the 100 MHz wall
-// clock at the phase boundaries into a buffer of its own; no product build contains a stamp.
+// Diagnostic build only (tools/stamp_post.hip, -DGF_STAMPS): lane 0 of every wave of one workgroup records the 100 MHz
+// wall clock at the phase boundaries into a buffer of its own, stamps[16*wave + i]; no product build contains a stamp.
 #ifdef GF_STAMPS
 extern "C" unsigned long long* gf_debug_stamps;  // host variable set by the tool
-#define GF_STAMP(i)                                                                                          \
-    do {                                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-        if (a.stamps && blockIdx.x == a.stamp_block && threadIdx.x == 0) {                                   \
-            a.stamps[i] = __builtin_amdgcn_s_memrealtime();                                                  \
-            a.stamps[16 + i] = __builtin_amdgcn_s_memtime();                                                 \
-        }                                                                                                    \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-    } while (0)
-// per-wave stamps of the wave-specialised kernel: stamps[64 + 16*wave + i]
 #define GF_WSTAMP(i)                                                                                         \
     do {                                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
         if (a.stamps && blockIdx.x == a.stamp_block && (threadIdx.x & 63) == 0)                              \
-            a.stamps[64 + 16 * wave + i] = __builtin_amdgcn_s_memrealtime();                                 \
+            a.stamps[16 * wave + i] = __builtin_amdgcn_s_memrealtime();                                      \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
     } while (0)
 #else
-#define GF_STAMP(i)
 #define GF_WSTAMP(i)
 #endif
 

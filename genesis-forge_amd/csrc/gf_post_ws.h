@@ -1,8 +1,16 @@
 // gf_post_ws.h — wave-specialised fused post-physics kernel (included by gf_post.hip).
 //
-// In-kernel stamps showed the single-wave post_kernel to be ISSUE-bound: a CDNA SIMD hands a wave one instruction
-// every 4 cycles, so ≈ 5 500 instructions of one stream are ≈ 9 µs however little memory they move, and at N = 65 536
-// there are only 1 024 waves for 1 024 SIMDs.  Two answers live here, in ONE kernel source:
+// Every phase after scene.step() is per-env work over the same state, so one launch carries a 64-env tile through all of
+// them: the state is loaded ONCE, the reset of done envs is applied to the registers as well as to memory (the observation
+// that follows needs no reload; it reads — reproducing the reference's stale EntityManager cache, entity_manager.py:163-167,
+// 189-195 — the PRE-reset quaternion), and the reward manager's reset is folded into the episode-sum update.  The result
+// is, by definition, what the phase entry points called in sequence leave behind — gf_termination_step, gf_reward_step,
+// gf_command_step, gf_masked_reset, gf_command_step (masked), gf_observe: the oracle and the tests compare against that,
+// bit for bit.
+//
+// One wave per tile with one lane per env — the first version of this kernel — was ISSUE-bound: a CDNA SIMD hands a wave
+// one instruction every 4 cycles, so ≈ 5 500 instructions of one stream are ≈ 9 µs however little memory they move, and at
+// N = 65 536 there are only 1 024 waves for 1 024 SIMDs.  Two answers live here, in ONE kernel source:
 //
 //  1. Wave specialisation.  A workgroup of 4 waves shares a 64-env tile (lane = env in every wave), each wave runs a
 //     quarter of the step:
@@ -13,7 +21,8 @@
 //       wave 3  obs-misc: targets / raw-action rows; after the barrier: command, body-frame, action, contact items
 //     then all 256 lanes stream the observation tile out.  What the waves exchange (masks, body-frame vectors, new
 //     commands) goes through 5 KB of LDS and one s_barrier.  Every global load happens before the barrier and every store of
-//     state that another wave loads happens after it, so the phases see exactly the values they see in post_kernel.
+//     state that another wave loads happens after it, so every phase sees exactly the values it sees when the phase entry
+//     points run one after the other.
 //
 //  2. Static programs.  The kernel is templated on a policy P.  Interp<DV> walks the term / item tables at run time (they
 //     are staged in LDS and every row is decoded with scalar instructions — most of the instruction count).  A static

@@ -1,5 +1,5 @@
 // gf_terms.h — the term bodies of mdp/rewards.py and mdp/terminations.py as device functions, shared by the
-// per-phase kernels (gf_reward.hip, gf_termination.hip) and the fused post-physics kernel (gf_post.hip) so the
+// per-phase kernels (gf_reward.hip, gf_termination.hip) and the fused post-physics kernel (gf_post_ws.h) so the
 // three can never drift apart.  `Args` is any descriptor exposing the members the bodies read
 // (contact[], command[], ext[], state[], dt); per-env values arrive in registers.
 #pragma once

@@ -89,7 +89,7 @@ GF_OPT_PROFILE_STRIDE = 1  # gf_set_option: stamp every k-th launch of the profi
 GF_OPT_CHAIN = 3           # gf_set_option: 1 (default) = fold runs of per-env phases of a recorded step into phase-chain launches
 GF_OPT_GRAPH = 2           # gf_set_option: 1 = recorded steps replay as one hipGraphLaunch; 0 (default: measured faster) = plain launches
 GF_OPT_FOLD_CONTACT = 4    # gf_set_option: 1 (default) = the contact ops in front of a fused post-physics op run as that launch's first phase
-GF_OPT_POST_VARIANT = 0  # gf_set_option: 0 = interpreter, one wave per tile; 1 = interpreter, four waves; 2 = + static programs (default)
+GF_OPT_POST_VARIANT = 0  # gf_set_option: 1 = table interpreter; 2 = + static programs (default); 0 = accepted, means 1
 
 GF_ERRORS = {-1: "GF_E_NULL", -2: "GF_E_RANGE", -3: "GF_E_OPCODE", -4: "GF_E_SLOT", -5: "GF_E_UNSUPPORTED"}
 

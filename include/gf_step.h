@@ -984,9 +984,9 @@ typedef struct GfHistoryUnrollArgs {
  * ---------------------------------------------------------------------------------------- */
 int gf_abi_version(void);
 /* library-wide tuning switches (process global).  GF_OPT_POST_VARIANT selects the fused post-physics kernel:
- * 0 = table interpreter, one wave per 64-env tile; 1 = table interpreter, four specialised waves per tile;
- * 2 = (default) as 1, plus the static programs: a config whose structure matches a registered program runs
- * straight-line code compiled for it.  All variants produce bit-identical results. */
+ * 1 = table interpreter (four specialised waves per 64-env tile); 2 = (default) as 1, plus the static programs: a
+ * config whose structure matches a registered program runs straight-line code compiled for it.  0 selected a first
+ * version of the kernel that is gone: the value stays accepted and means 1.  All variants produce bit-identical results. */
 /* GF_OPT_PROFILE_STRIDE: gf_profile_begin stamps every k-th launch of the profiled phase (default 1 = every launch); a
  * stamped launch costs the host several microseconds more than a plain one, so a timed region samples instead. */
 /* GF_OPT_GRAPH (default 0): 1 = gf_run_ops_graph replays a recorded step as one hipGraphLaunch.  Off by default because it
@@ -1033,8 +1033,8 @@ int gf_adam_step(const GfAdamArgs* a, void* stream);             /* adaptive lr 
  * Fused post-physics step: everything ManagedEnvironment.step() does after scene.step() and the
  * contact managers — termination → reward → command.step → reset of done envs → command.reset →
  * observations (managed_env.py:303-326) — as ONE launch.  All of it is per-env work on the same
- * state (pos/quat/vel/ang, the [N,D] rows, commands), so one lane carries an env through every phase
- * with that state in registers: 566 B/env of traffic instead of 268 + 26 + 4 + 388 + the reset's
+ * state (pos/quat/vel/ang, the [N,D] rows, commands), so one workgroup carries a 64-env tile through every
+ * phase with that state in registers: 566 B/env of traffic instead of 268 + 26 + 4 + 388 + the reset's
  * re-reads, one launch instead of six.  The descriptors are the per-phase ones (so the semantics are by
  * definition those of calling the phases in sequence — which is what the oracle twin does); the call
  * packs them into one kernarg block.  Returns GF_E_UNSUPPORTED when the combination cannot be fused

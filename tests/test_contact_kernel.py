@@ -115,11 +115,13 @@ def test_folded_launch_equals_separate_launches(hip_backend):
 
 
 @pytest.mark.gpu
-def test_contact_step_as_first_phase_of_the_fused_launch_raw_abi(hip_backend):
+@pytest.mark.parametrize("post_variant", [2, 0])
+def test_contact_step_as_first_phase_of_the_fused_launch_raw_abi(hip_backend, post_variant):
     """gf_post_physics_step_contacts through the raw ABI on the reference-recorded contact arrays: link ids on both sides, empty slots,
     NaN / Inf forces, a with-filter on another entity and one on own links, air time — the three managers run as the first phase of a
     fused post-physics launch (of an unrelated Go2 env of the same size: any fusable step will do) and must leave exactly what three
-    gf_contact_step launches leave, which is what the reference left (fixture)."""
+    gf_contact_step launches leave, which is what the reference left (fixture).  GF_OPT_POST_VARIANT = 0 is the same as 1: the table
+    interpreter, and it folds the contact phase like every other variant."""
     import envs
     from genesis_forge_amd import _native as nat
 
@@ -134,7 +136,10 @@ def test_contact_step_as_first_phase_of_the_fused_launch_raw_abi(hip_backend):
     refs = host._trace.post_refs
     assert refs is not None
     hip_backend.set_option(nat.GF_OPT_FOLD_CONTACT, 2)
+    hip_backend.set_option(nat.GF_OPT_POST_VARIANT, post_variant)
     try:
+        if post_variant == 0:
+            assert hip_backend.post_describe(refs).split(":")[0] == "program 0 (interpreter)"
         for t in range(int(fix["steps"])):
             _load_step(env, fix, t, "cuda")
             air_before = [[x.clone() for x in (cm.last_air_time, cm.current_air_time, cm.last_contact_time, cm.current_contact_time)]
@@ -172,3 +177,4 @@ def test_contact_step_as_first_phase_of_the_fused_launch_raw_abi(hip_backend):
         assert hip_backend.post_step_contacts(refs, [bad]) == -5
     finally:
         hip_backend.set_option(nat.GF_OPT_FOLD_CONTACT, 1)
+        hip_backend.set_option(nat.GF_OPT_POST_VARIANT, 2)

@@ -756,8 +756,8 @@ def test_traced_step_equals_ordinary_hip(hip_backend):
 
 @pytest.fixture
 def post_variant(hip_backend, request):
-    """Selects the fused kernel's variant (0 = interpreter, one wave per tile; 1 = interpreter, four specialised waves;
-    2 = static programs where the config matches one) for one test."""
+    """Selects the fused kernel's variant (1 = table interpreter; 2 = static programs where the config matches one; 0 = accepted
+    and the same as 1 in every respect) for one test."""
     from genesis_forge_amd import _native as nat
 
     hip_backend.set_option(nat.GF_OPT_POST_VARIANT, request.param)

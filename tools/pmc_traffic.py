@@ -20,7 +20,7 @@ def medians(path, counter):
             if row.get("Counter_Name") != counter:
                 continue
             name = row["Kernel_Name"]
-            for key in ("post_ws_kernel", "post_kernel", "action_kernel", "synth_scene"):
+            for key in ("post_ws_kernel", "action_kernel", "synth_scene"):
                 if key in name:
                     per.setdefault(name if key.startswith("post") else key, []).append(float(row["Counter_Value"]))
     return {k: statistics.median(v) for k, v in per.items() if len(v) >= 10}

@@ -55,7 +55,7 @@ def run(config, steps):
     env.seed(1)
     env.reset()
     lib = _native.get_backend().lib
-    stamps = torch.zeros(128, dtype=torch.int64, device="cuda")
+    stamps = torch.zeros(64, dtype=torch.int64, device="cuda")
     D = env.action_space.shape[0]
     acts = [torch.randn(n, D, device="cuda") for _ in range(4)]
     for i in range(20):
@@ -67,10 +67,10 @@ def run(config, steps):
         env.step(acts[i % 4])
         torch.cuda.synchronize()
         h = stamps.cpu()
-        t0 = min(int(h[64 + 16 * w + 1]) for w in range(4))
+        t0 = min(int(h[16 * w + 1]) for w in range(4))
         for w in range(4):
             for k in range(1, 16):
-                acc[w, k] += (int(h[64 + 16 * w + k]) - t0) / 100.0
+                acc[w, k] += (int(h[16 * w + k]) - t0) / 100.0
     acc /= steps
     print(f"{config}: {n} envs, fused={env._trace.post_refs is not None}, mean of {steps} launches, us since the first wave had its args (middle workgroup)")
     print("          " + " ".join(f"{s:>17s}" for s in NAMES))

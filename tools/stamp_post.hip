@@ -177,22 +177,11 @@ int main(int argc, char** argv) {
     {
         const int rc = gf_post_physics_check(&pr);
         printf("gf_post_physics_check: %d (%s)\n", rc, gf_error_string(rc));
-        gf_set_option(GF_OPT_POST_VARIANT, 0);
         if (rc == 0) time_loop("gf_post_physics_step", iters, 566.0 * Nd, [&] { chk(gf_post_physics_step(&pr, 0), "post"); });
     }
     {
-        unsigned long long* st = dalloc<unsigned long long>(128);
+        unsigned long long* st = dalloc<unsigned long long>(64);
         gf_debug_stamps = st;
-        for (int rep = 0; rep < 3; ++rep) {
-            for (int i = 0; i < 50; ++i) chk(gf_post_physics_step(&pr, 0), "post");
-            CK(hipDeviceSynchronize());
-            unsigned long long h[32];
-            CK(hipMemcpy(h, st, sizeof(h), hipMemcpyDeviceToHost));
-            const char* names[] = {"prefetch kernarg", "issue loads", "derive", "termination", "reward", "command.step", "reset+command.reset", "obs tile build", "obs write-out", ""};
-            printf("stamps (us, middle workgroup):");
-            for (int i = 1; i < 10; ++i) printf("  %s %.2f", names[i - 1], (double)(h[i] - h[i - 1]) / 100.0);
-            printf("  | total %.2f us, %.0f shader cycles -> %.0f MHz\n", (double)(h[9] - h[0]) / 100.0, (double)(h[25] - h[16]), (double)(h[25] - h[16]) / ((double)(h[9] - h[0]) / 100.0));
-        }
       for (int variant = 1; variant <= 2; ++variant) {
         gf_set_option(GF_OPT_POST_VARIANT, variant);
         printf("---- variant %d\n", variant);
@@ -200,14 +189,14 @@ int main(int argc, char** argv) {
         for (int rep = 0; rep < 3; ++rep) {
             for (int i = 0; i < 50; ++i) chk(gf_post_physics_step(&pr, 0), "post");
             CK(hipDeviceSynchronize());
-            unsigned long long h[128];
+            unsigned long long h[64];
             CK(hipMemcpy(h, st, sizeof(h), hipMemcpyDeviceToHost));
             unsigned long long t0 = ~0ull;
-            for (int w = 0; w < 4; ++w) t0 = h[64 + 16 * w + 1] < t0 ? h[64 + 16 * w + 1] : t0;
+            for (int w = 0; w < 4; ++w) t0 = h[16 * w + 1] < t0 ? h[16 * w + 1] : t0;
             printf("ws stamps (us since first wave had its args; staged | pre-barrier done | past barrier A | role stores | state writer | tile built | past barrier B | end)\n");
             for (int w = 0; w < 4; ++w) {
                 printf("  wave %d:", w);
-                for (int i = 1; i <= 8; ++i) printf(" %6.2f", (double)(long long)(h[64 + 16 * w + i] - t0) / 100.0);
+                for (int i = 1; i <= 8; ++i) printf(" %6.2f", (double)(long long)(h[16 * w + i] - t0) / 100.0);
                 printf("\n");
             }
         }

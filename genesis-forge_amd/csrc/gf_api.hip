@@ -76,6 +76,7 @@ GF_EXPORT int gf_sizeof(int which) {
         case 26: return (int)sizeof(GfPpoLossArgs);
         case 27: return (int)sizeof(GfAdamArgs);
         case 28: return (int)sizeof(GfMlpActArgs);
+        case 29: return (int)sizeof(GfObsNormArgs);
         default: return -1;
     }
 }

@@ -10,6 +10,9 @@
 // pointers allow it, 8- or 4-byte chunks otherwise — and each lane issues kMbUnits chunk loads before their stores, so several
 // rows are in flight per wave.  Pure copy: bit-identical to src[indices].  Default-policy stores: the PPO forward pass reads
 // the output next.  Algorithmic traffic: R 4·Σw + 8, W 4·Σw bytes per minibatch row.
+// A field with a normaliser (mean != NULL: rsl_rl's EmpiricalNormalization.forward on the gathered observations) stores
+// (v - mean[c]) / (std[c] + eps) instead of v, in the same pass: the chunking follows the rows as before, mean and std — [src_width]
+// vectors that stay in cache, possibly a less aligned slice of a group's normaliser — are read by element.  NaN rows stay NaN.
 #include "gf_launch.h"
 
 namespace gf {
@@ -34,7 +37,20 @@ template <> struct MbVec<4> { typedef f32x4 T; };
 template <> struct MbVec<2> { typedef f32x2 T; };
 template <> struct MbVec<1> { typedef float T; };
 
+// the normalised chunk at source columns c0 … c0 + V - 1: one subtraction, one addition, one correctly rounded division per element
 template <int V>
+__device__ __forceinline__ typename MbVec<V>::T mb_normalise(typename MbVec<V>::T v, const GF_GLOBAL float* mean, const GF_GLOBAL float* sd,
+                                                             const float eps, const int64_t c0) {
+    if constexpr (V == 1) {
+        return (v - mean[c0]) / (sd[c0] + eps);
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] = (v[j] - mean[c0 + j]) / (sd[c0 + j] + eps);
+        return v;
+    }
+}
+
+template <int V, bool NORM>
 __device__ __forceinline__ void mb_copy_field(const GfMinibatchField& f, const int64_t* __restrict__ tile_idx, const int64_t row0,
                                               const int rows, const int chunks, const uint64_t magic) {
     typedef typename MbVec<V>::T VT;
@@ -54,8 +70,10 @@ __device__ __forceinline__ void mb_copy_field(const GfMinibatchField& f, const i
                 const int64_t c = it - r * chunks;
                 const int64_t s = tile_idx[r];
                 at[k] = r * dw + c * V;
-                if (s >= 0) v[k] = *reinterpret_cast<const GF_GLOBAL VT*>(src + s * sw + c * V);
-                else v[k] = (VT)__builtin_nanf("");   // (a scalar cast to an ext-vector splats)
+                if (s >= 0) {
+                    v[k] = *reinterpret_cast<const GF_GLOBAL VT*>(src + s * sw + c * V);
+                    if (NORM) v[k] = mb_normalise<V>(v[k], G(f.mean), G(f.std), f.eps, c * V);
+                } else v[k] = (VT)__builtin_nanf("");   // (a scalar cast to an ext-vector splats)
             }
         }
 #pragma unroll
@@ -64,6 +82,8 @@ __device__ __forceinline__ void mb_copy_field(const GfMinibatchField& f, const i
     }
 }
 
+// NORM: some field carries a normaliser.  A kernel of its own, so that the pure copy keeps the registers (and the occupancy) it had.
+template <bool NORM>
 __global__ __launch_bounds__(kMbBlock) void minibatch_gather_kernel(const GfMinibatchArgs a, const MbConsts mc) {
     __shared__ int64_t tile_idx[kMbMaxTile];
     const int64_t row0 = (int64_t)blockIdx.x * mc.tile;
@@ -76,9 +96,15 @@ __global__ __launch_bounds__(kMbBlock) void minibatch_gather_kernel(const GfMini
     __syncthreads();
     for (int f = 0; f < a.num_fields; ++f) {
         const int v = mc.vec[f];
-        if (v == 4) mb_copy_field<4>(a.fields[f], tile_idx, row0, rows, mc.chunks[f], mc.magic[f]);
-        else if (v == 2) mb_copy_field<2>(a.fields[f], tile_idx, row0, rows, mc.chunks[f], mc.magic[f]);
-        else mb_copy_field<1>(a.fields[f], tile_idx, row0, rows, mc.chunks[f], mc.magic[f]);
+        if (NORM && a.fields[f].mean) {
+            if (v == 4) mb_copy_field<4, true>(a.fields[f], tile_idx, row0, rows, mc.chunks[f], mc.magic[f]);
+            else if (v == 2) mb_copy_field<2, true>(a.fields[f], tile_idx, row0, rows, mc.chunks[f], mc.magic[f]);
+            else mb_copy_field<1, true>(a.fields[f], tile_idx, row0, rows, mc.chunks[f], mc.magic[f]);
+            continue;
+        }
+        if (v == 4) mb_copy_field<4, false>(a.fields[f], tile_idx, row0, rows, mc.chunks[f], mc.magic[f]);
+        else if (v == 2) mb_copy_field<2, false>(a.fields[f], tile_idx, row0, rows, mc.chunks[f], mc.magic[f]);
+        else mb_copy_field<1, false>(a.fields[f], tile_idx, row0, rows, mc.chunks[f], mc.magic[f]);
     }
 }
 
@@ -88,7 +114,7 @@ int minibatch_prep(const GfMinibatchArgs* a) {
     if (!a->indices) return GF_E_NULL;
     for (int f = 0; f < a->num_fields; ++f) {
         const GfMinibatchField& d = a->fields[f];
-        if (!d.src || !d.dst) return GF_E_NULL;
+        if (!d.src || !d.dst || (d.mean && !d.std)) return GF_E_NULL;
         if (d.src_width < 1 || d.dst_width < 1 || d.dst_col < 0 || (int64_t)d.dst_col + d.src_width > d.dst_width) return GF_E_RANGE;
     }
     return GF_OK;
@@ -125,6 +151,9 @@ extern "C" __attribute__((visibility("default"))) int gf_minibatch_gather(const 
     const int64_t blocks = (a->num_rows + tile - 1) / tile;
     if (blocks > 0x7fffffff) return GF_E_RANGE;
     hipStream_t s = (hipStream_t)stream;
-    gf::klaunch(gf::minibatch_gather_kernel, dim3((unsigned)blocks), dim3(gf::kMbBlock), 0, s, *a, mc);
+    bool norm = false;
+    for (int f = 0; f < a->num_fields; ++f) norm = norm || a->fields[f].mean != nullptr;
+    if (norm) gf::klaunch(gf::minibatch_gather_kernel<true>, dim3((unsigned)blocks), dim3(gf::kMbBlock), 0, s, *a, mc);
+    else gf::klaunch(gf::minibatch_gather_kernel<false>, dim3((unsigned)blocks), dim3(gf::kMbBlock), 0, s, *a, mc);
     return gf::launch_status();
 }

@@ -10,7 +10,8 @@
 //   * Activations stay in LDS (x: 32 rows x 513 floats; the odd stride keeps the 32 rows of a k column on 32 banks).  A layer reads
 //     x through its whole k loop into registers (the accumulators), the workgroup meets, and the ELU-ed outputs overwrite x: one
 //     buffer, never written to memory.  The first layer's input is copied from the segments into x, 512 columns at a time (the
-//     accumulators live through the passes).
+//     accumulators live through the passes) — through the net's input normaliser where it has one: (v - mean[k]) / (std[k] + eps)
+//     per real element, k the column of the whole input; the zero padding stays zero.
 //   * Weights never touch LDS: a lane reads its own row of W along k — torch's layout is contiguous there — 16 bytes at a time, a
 //     whole chunk of k (32 … 128 columns, 64 registers per wave) ahead of its multiplications; where a wave has one or two output
 //     blocks a second chunk is in flight meanwhile.  The two lane halves of a wave read the two halves of a chunk, so a register
@@ -134,7 +135,8 @@ __device__ __forceinline__ void mlp_k_loop(const MlpSmem& sm, const GF_GLOBAL fl
 
 // One Linear layer (+ ELU unless `last`) of the tile: x (LDS, K columns; the segments when `first`) -> x (O columns, zeros up to the
 // next multiple of 32).  NB = 32-column blocks per wave: every wave multiplies NB blocks (the ones past `out` are not stored).
-template <int NB>
+// NORM: the launch has a net with an input normaliser (a kernel of its own: the plain forward keeps the code it had).
+template <int NB, bool NORM>
 __device__ __forceinline__ void mlp_layer(MlpSmem& sm, const GfMlpNet& net, const GfMlpLayer& L, const int K, const bool first, const bool last,
                                           const int64_t row0, const int64_t N) {
     constexpr int KC = mlp_kc(NB);
@@ -142,6 +144,8 @@ __device__ __forceinline__ void mlp_layer(MlpSmem& sm, const GfMlpNet& net, cons
     const int CB = (O + 31) >> 5;
     const bool vec = (K & 3) == 0 && (reinterpret_cast<uintptr_t>(L.weight) & 15u) == 0;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+
+    const bool norm = NORM && first && net.in_mean != nullptr;   // (workgroup-uniform)
 
     f32x16 acc[NB];
     const GF_GLOBAL float* W = G(L.weight);
@@ -176,7 +180,11 @@ __device__ __forceinline__ void mlp_layer(MlpSmem& sm, const GfMlpNet& net, cons
                     off = hit ? n * w + k : off;
                     k -= w;
                 }
-                const float v = G(rows)[off];
+                float v = G(rows)[off];
+                if (NORM && norm) {   // rsl_rl EmpiricalNormalization.forward: one subtraction, one addition, one correctly rounded division
+                    const int c = in ? p0 + col : 0;
+                    v = (v - G(net.in_mean)[c]) / (G(net.in_std)[c] + net.in_eps);
+                }
                 sm.x[row * kMlpXS + col] = in ? v : 0.0f;
             }
             __syncthreads();
@@ -208,6 +216,7 @@ __device__ __forceinline__ void mlp_layer(MlpSmem& sm, const GfMlpNet& net, cons
     __syncthreads();
 }
 
+template <bool NORM>
 __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArgs a, const int first_net, const int vec_rows) {
     __shared__ MlpSmem sm;
     const bool is_critic = (int)blockIdx.y + first_net == 1;
@@ -222,10 +231,10 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArg
         const GfMlpLayer& L = net.layers[l];
         const int nb = (((L.out_width + 31) >> 5) + kMlpWaves - 1) / kMlpWaves;
         const bool first = l == 0, last = l == layers - 1;
-        if (nb == 1) mlp_layer<1>(sm, net, L, K, first, last, row0, N);
-        else if (nb == 2) mlp_layer<2>(sm, net, L, K, first, last, row0, N);
-        else if (nb == 3) mlp_layer<3>(sm, net, L, K, first, last, row0, N);
-        else mlp_layer<4>(sm, net, L, K, first, last, row0, N);
+        if (nb == 1) mlp_layer<1, NORM>(sm, net, L, K, first, last, row0, N);
+        else if (nb == 2) mlp_layer<2, NORM>(sm, net, L, K, first, last, row0, N);
+        else if (nb == 3) mlp_layer<3, NORM>(sm, net, L, K, first, last, row0, N);
+        else mlp_layer<4, NORM>(sm, net, L, K, first, last, row0, N);
         K = L.out_width;
     }
 
@@ -284,6 +293,7 @@ static int mlp_check_net(const GfMlpNet& net, bool critic, int* out_width) {
         in += net.inputs[s].width;
     }
     if (in > GF_MLP_MAX_INPUT_WIDTH) return GF_E_RANGE;
+    if (net.in_mean && !net.in_std) return GF_E_NULL;
     for (int l = 0; l < net.num_layers; ++l) {
         const GfMlpLayer& L = net.layers[l];
         if (!L.weight || !L.bias) return GF_E_NULL;
@@ -331,7 +341,9 @@ extern "C" __attribute__((visibility("default"))) int gf_mlp_act(const GfMlpActA
     const void* rows[] = {a->noise, a->actions, a->actions_out, a->mu_out, a->sigma_out, a->std};
     for (const void* p : rows) bits |= reinterpret_cast<uintptr_t>(p);
     const int vec_rows = (bits & 15u) == 0 && (A & 3) == 0;
-    gf::klaunch(gf::mlp_act_kernel, dim3((unsigned)tiles, actor && critic ? 2u : 1u), dim3(gf::kMlpBlock), 0, (hipStream_t)stream, *a,
-                actor ? 0 : 1, vec_rows);
+    const bool norm = (actor && a->actor.in_mean) || (critic && a->critic.in_mean);
+    const dim3 grid((unsigned)tiles, actor && critic ? 2u : 1u);
+    if (norm) gf::klaunch(gf::mlp_act_kernel<true>, grid, dim3(gf::kMlpBlock), 0, (hipStream_t)stream, *a, actor ? 0 : 1, vec_rows);
+    else gf::klaunch(gf::mlp_act_kernel<false>, grid, dim3(gf::kMlpBlock), 0, (hipStream_t)stream, *a, actor ? 0 : 1, vec_rows);
     return gf::launch_status();
 }

@@ -13,7 +13,7 @@ import ctypes as C
 import os
 from typing import Optional
 
-GF_ABI_VERSION = 7
+GF_ABI_VERSION = 8
 GF_MAX_TERMS = 24
 GF_MAX_TERM_TERMS = 16
 GF_MAX_OBS_ITEMS = 24
@@ -312,7 +312,8 @@ GF_SIZEOF_MINIBATCH = 23   # gf_sizeof index of GfMinibatchArgs (not in ABI_STRU
 
 
 class GfMinibatchField(C.Structure):
-    _fields_ = [("src", P), ("dst", P), ("src_width", C.c_int32), ("dst_width", C.c_int32), ("dst_col", C.c_int32), ("_pad", C.c_int32)]
+    _fields_ = [("src", P), ("dst", P), ("src_width", C.c_int32), ("dst_width", C.c_int32), ("dst_col", C.c_int32), ("_pad", C.c_int32),
+                ("mean", P), ("std", P), ("eps", C.c_float), ("_pad2", C.c_int32)]   # the field's normaliser (mean NULL: pure copy)
 
 
 class GfMinibatchArgs(C.Structure):
@@ -395,13 +396,34 @@ class GfMlpLayer(C.Structure):
 
 class GfMlpNet(C.Structure):
     _fields_ = [("num_layers", C.c_int32), ("num_inputs", C.c_int32), ("inputs", GfMlpSegment * GF_MLP_MAX_INPUTS),
-                ("layers", GfMlpLayer * GF_MLP_MAX_LAYERS)]
+                ("layers", GfMlpLayer * GF_MLP_MAX_LAYERS), ("in_mean", P), ("in_std", P), ("in_eps", C.c_float), ("_pad", C.c_int32)]
 
 
 class GfMlpActArgs(C.Structure):
     _fields_ = [("num_envs", C.c_int64), ("actor", GfMlpNet), ("critic", GfMlpNet), ("std", P), ("noise", P), ("seed", C.c_uint64),
                 ("stream", C.c_uint64), ("env_offset", C.c_uint32), ("std_per_env", C.c_int32), ("mean", P), ("values", P), ("actions", P),
                 ("actions_out", P), ("mu_out", P), ("sigma_out", P), ("values_out", P), ("log_prob_out", P)]
+
+
+# the running observation statistics (learner.EmpiricalNormalization.update): gf_obs_norm_update, not in ABI_STRUCTS either
+GF_SIZEOF_OBS_NORM = 29
+GF_OBS_NORM_MAX_SETS = 2
+GF_OBS_NORM_TILE_ROWS = 256
+GF_OBS_NORM_MAX_PARTIALS = 256
+
+
+def obs_norm_workspace_bytes(num_rows: int, width: int) -> int:
+    """GF_OBS_NORM_WORKSPACE_BYTES: {rows, mean[W], M2[W]} doubles per partial workgroup of one set."""
+    return min(-(-int(num_rows) // GF_OBS_NORM_TILE_ROWS), GF_OBS_NORM_MAX_PARTIALS) * (1 + 2 * int(width)) * 8
+
+
+class GfObsNormSet(C.Structure):
+    _fields_ = [("num_inputs", C.c_int32), ("_pad", C.c_int32), ("inputs", GfMlpSegment * GF_MLP_MAX_INPUTS), ("mean", P), ("var", P),
+                ("std", P), ("count", P), ("until", C.c_int64), ("workspace", P), ("workspace_bytes", C.c_int64)]
+
+
+class GfObsNormArgs(C.Structure):
+    _fields_ = [("num_rows", C.c_int64), ("num_sets", C.c_int32), ("_pad", C.c_int32), ("sets", GfObsNormSet * GF_OBS_NORM_MAX_SETS)]
 
 
 ABI_STRUCTS = [GfStepStats, GfActionArgs, GfContactArgs, GfTerminationArgs, GfRewardArgs, GfCommandArgs,
@@ -513,6 +535,12 @@ class Backend:
     def stats_clear(self, stats_ptr: int) -> None:  # pragma: no cover - interface
         raise NotImplementedError
 
+    def obs_norm_update(self, args) -> None:
+        """gf_obs_norm_update on the current stream (learner.EmpiricalNormalization.update, learner.ActorCriticMLP.update_normalization)."""
+        rc = self.lib.gf_obs_norm_update(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("obs_norm_update", rc)
+
     def run_ops(self, ops, n: int) -> None:  # pragma: no cover - interface
         raise NotImplementedError
 
@@ -622,7 +650,7 @@ class HipBackend(Backend):
         # the two pieces of the collection loop (RolloutStorage.act / process_env_step): the same kind of entry points
         for fn, idx, st in (("gf_policy_act", GF_SIZEOF_POLICY_ACT, GfPolicyActArgs), ("gf_episode_step", GF_SIZEOF_EPISODE, GfEpisodeArgs),
                             ("gf_ppo_loss", GF_SIZEOF_PPO_LOSS, GfPpoLossArgs), ("gf_adam_step", GF_SIZEOF_ADAM, GfAdamArgs),
-                            ("gf_mlp_act", GF_SIZEOF_MLP_ACT, GfMlpActArgs)):
+                            ("gf_mlp_act", GF_SIZEOF_MLP_ACT, GfMlpActArgs), ("gf_obs_norm_update", GF_SIZEOF_OBS_NORM, GfObsNormArgs)):
             n = self.lib.gf_sizeof(idx)
             if n != C.sizeof(st):
                 raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")

@@ -28,6 +28,10 @@ dependency and stays one; this module provides the two pieces of it that touch t
   it but the optimizer step.  This is the first place of the pipeline where xGMI bandwidth rather than latency matters.
 * :class:`ActorCriticMLP` — the policy of ``examples/*/train.py`` (ELU, hidden dims 512-256-128, learnable action std) as a
   plain torch module, so the two pieces above can be exercised without rsl_rl.
+* :class:`EmpiricalNormalization` — rsl_rl's running observation normaliser (the ``"empirical_normalization"`` switch of
+  ``examples/*/train.py``; rsl_rl 3.x's ``actor_obs_normalization`` / ``critic_obs_normalization``): the statistics of both
+  normalisers are ONE ``gf_obs_norm_update`` per collection step (two launches, no host read), and the normalisation itself has no
+  launch of its own — ``gf_mlp_act`` applies it as it stages the first layer's input, ``gf_minibatch_gather`` as it copies the rows.
 * :class:`PPO` — rsl_rl's ``PPO.update`` for the ``"algorithm"`` dict of ``examples/*/train.py``: per minibatch the MLP forward /
   backward stay in torch, the loss and its gradient w.r.t. the policy outputs are one ``gf_ppo_loss`` (two launches), the adaptive
   learning rate, ``clip_grad_norm_`` and Adam over the flat gradient bucket are one ``gf_adam_step`` (two launches) — no host
@@ -189,6 +193,7 @@ class RolloutStorage:
         self._moments = None
         self._returns_ready = False
         self._mb_args = nat.GfMinibatchArgs()
+        self._mb_normed = False   # the descriptor holds normaliser pointers (of the last gather)
         # the collection loop around env.step() (act / process_env_step).  `_serial` counts the transitions written; the policy rows
         # and the bootstrap are tracked as the serial of the transition they belong to.  The action noise has a Philox seed and
         # stream of its own (``seed()``): never the env's draws.
@@ -358,7 +363,8 @@ class RolloutStorage:
         policy.evaluate(obs))`` by ``store.act_policy(fwd, obs)`` draws the same noise.  ``obs`` / ``critic_obs``: a ``[N, W]`` tensor
         or a sequence of up to four (the members of an observation group side by side — no ``torch.cat``); ``critic_obs=None``: the
         critic reads ``obs``.  The mean and the value are k-ascending f32 fma chains (``gf_step.h``), not torch's GEMM bits: within
-        f32 rounding of ``policy.act_mean`` / ``evaluate``, and the same for a row whatever ``num_envs`` is.
+        f32 rounding of ``policy.act_mean`` / ``evaluate``, and the same for a row whatever ``num_envs`` is.  A policy with observation
+        normalisers (:class:`EmpiricalNormalization`) has them applied inside the same launch, to the raw ``obs`` / ``critic_obs``.
         Measured per collection step (profiles/r09_mlp_act.md): 3.5 x faster than ``act()`` on torch's forward at 4 096 envs, 1.4 x
         at 16 384, but 7 % SLOWER at 65 536 envs, where the large GEMMs win: there ``act()`` with the torch forward is the call to use.
         On a backend without ``gf_mlp_act`` (the test-only CPU oracle) this is exactly the ``act`` call above under ``no_grad``, and
@@ -478,13 +484,17 @@ class RolloutStorage:
         self._returns_ready = True
 
     # -- PPO minibatches ------------------------------------------------------------------------------------------------------------
-    def mini_batch_generator(self, num_mini_batches: int, num_epochs: int = 1, generator: Optional[torch.Generator] = None) -> Iterator[MiniBatch]:
+    def mini_batch_generator(self, num_mini_batches: int, num_epochs: int = 1, generator: Optional[torch.Generator] = None,
+                             obs_normalizer=None, critic_obs_normalizer=None) -> Iterator[MiniBatch]:
         """rsl_rl's ``RolloutStorage.mini_batch_generator``: ONE ``torch.randperm(num_mini_batches * mb)`` (``mb = T·N //
         num_mini_batches``; the remainder rows are never drawn) shared by all ``num_epochs`` epochs; minibatch ``i`` is rows
         ``indices[i·mb:(i+1)·mb]`` of every flattened ``[T·N, …]`` array, source row ``k`` being transition ``divmod(k, N)``.
         Each batch is gathered by one ``gf_minibatch_gather`` launch into fresh tensors (a consumer may keep a batch); the
         critic input is the concatenation of its group's members, written side by side by the same launch, and is ``obs`` itself
-        when the two groups are the same."""
+        when the two groups are the same (and so are the two normaliser objects).
+        ``obs_normalizer`` / ``critic_obs_normalizer``: an :class:`EmpiricalNormalization` of the group's width (``None`` /
+        ``nn.Identity``: none) — the batch's ``obs`` / ``critic_obs`` then come out as ``normalizer(rows)``, from the same single
+        launch.  The storage itself keeps the raw observations, as rsl_rl's does."""
         if not self._returns_ready:
             raise RuntimeError("mini_batch_generator() reads returns and advantages: call compute_returns() first")
         num_mini_batches, num_epochs = int(num_mini_batches), int(num_epochs)
@@ -494,13 +504,16 @@ class RolloutStorage:
         mb = (T * n) // num_mini_batches
         if mb < 1:
             raise ValueError(f"{T * n} transitions cannot fill {num_mini_batches} minibatches")
+        width = lambda group: sum(self.group_rows[m].shape[2] for m in self.obs_groups[group])
+        norms = (_as_normalizer(obs_normalizer, width("policy"), "obs_normalizer"),
+                 _as_normalizer(critic_obs_normalizer, width("critic"), "critic_obs_normalizer"))
         indices = torch.randperm(num_mini_batches * mb, device=gs.device, generator=generator)
-        return self._mini_batches(indices, num_mini_batches, num_epochs, mb)
+        return self._mini_batches(indices, num_mini_batches, num_epochs, mb, norms)
 
-    def _mini_batches(self, indices: torch.Tensor, num_mini_batches: int, num_epochs: int, mb: int) -> Iterator[MiniBatch]:
+    def _mini_batches(self, indices: torch.Tensor, num_mini_batches: int, num_epochs: int, mb: int, norms=(None, None)) -> Iterator[MiniBatch]:
         for _epoch in range(num_epochs):
             for i in range(num_mini_batches):
-                yield self._gather(indices[i * mb:(i + 1) * mb])
+                yield self._gather(indices[i * mb:(i + 1) * mb], *norms)
 
     def _flat(self) -> dict:
         """Every stored array as its ``[T·N, w]`` source rows (views)."""
@@ -511,42 +524,57 @@ class RolloutStorage:
         per = {k: getattr(self, k).flatten(0, 1) for k in _MB_FIELDS}   # ([T·N] or [T·N, A])
         return rows, per
 
-    def _gather(self, idx: torch.Tensor) -> MiniBatch:
+    def _gather(self, idx: torch.Tensor, obs_norm=None, critic_norm=None) -> MiniBatch:
         rows, per = self._flat()
         policy, critic = self.obs_groups["policy"], self.obs_groups["critic"]
-        same = list(critic) == list(policy)
+        same = list(critic) == list(policy) and critic_norm is obs_norm
         gather = getattr(self.env.backend, "minibatch_gather", None)
         if gather is None:   # (the test-only oracle backend) rsl_rl's expression itself
-            cat = lambda names: rows[names[0]][idx] if len(names) == 1 else torch.cat([rows[m][idx] for m in names], dim=-1)
-            obs = cat(policy)
-            return MiniBatch(obs, obs if same else cat(critic), *(per[k][idx] for k in _MB_FIELDS), idx)
+            def cat(names, norm):
+                x = rows[names[0]][idx] if len(names) == 1 else torch.cat([rows[m][idx] for m in names], dim=-1)
+                if norm is None:
+                    return x
+                with torch.no_grad():
+                    return norm(x)
+
+            obs = cat(policy, obs_norm)
+            return MiniBatch(obs, obs if same else cat(critic, critic_norm), *(per[k][idx] for k in _MB_FIELDS), idx)
         m = idx.shape[0]
         dev = self.observations.device
         empty = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
-        fields = []   # (source rows [T·N, w], destination, its width, first column)
+        fields = []   # (source rows [T·N, w], destination, its width, first column, the group's normaliser or None)
 
-        def group(names):
+        def group(names, norm):
             w = sum(rows[k].shape[1] for k in names)
             out, col = empty(m, w), 0
             for k in names:
-                fields.append((rows[k], out, w, col))
+                fields.append((rows[k], out, w, col, norm))
                 col += rows[k].shape[1]
             return out
 
-        obs = group(policy)
-        critic_obs = obs if same else group(critic)
+        obs = group(policy, obs_norm)
+        critic_obs = obs if same else group(critic, critic_norm)
         outs = []
         for k in _MB_FIELDS:
             src = per[k]
             outs.append(empty(m, *src.shape[1:]))
-            fields.append((src, outs[-1], src.shape[1] if src.dim() == 2 else 1, 0))
+            fields.append((src, outs[-1], src.shape[1] if src.dim() == 2 else 1, 0, None))
         a = self._mb_args
         a.num_rows, a.num_src_rows, a.indices = m, self.num_steps * self.env.num_envs, idx.data_ptr()
         for at in range(0, len(fields), nat.GF_MINIBATCH_MAX_FIELDS):   # (more members than one launch holds: a further launch)
             part = fields[at:at + nat.GF_MINIBATCH_MAX_FIELDS]
             a.num_fields = len(part)
-            for f, (src, dst, w, col) in zip(a.fields, part):
+            for f, (src, dst, w, col, norm) in zip(a.fields, part):
                 f.src, f.dst, f.src_width, f.dst_width, f.dst_col = src.data_ptr(), dst.data_ptr(), src.numel() // src.shape[0], w, col
+                if norm is not None:   # (the member's slice of the group's normaliser)
+                    f.mean, f.std, f.eps = norm._mean.data_ptr() + 4 * col, norm._std.data_ptr() + 4 * col, norm.eps
+                elif self._mb_normed:
+                    f.mean = f.std = None
+            normed = obs_norm is not None or critic_norm is not None
+            if self._mb_normed and not normed:   # (the slots past this part may still hold a pointer of an earlier call)
+                for f in a.fields:
+                    f.mean = f.std = None
+            self._mb_normed = normed
             gather(a)
         return MiniBatch(obs, critic_obs, *outs, idx)
 
@@ -684,11 +712,162 @@ class EpisodeStatistics:
         self._calls = 0
 
 
+def _obs_segments(x, width: int, name: str, device) -> tuple:
+    """``x`` as the tuple of ``[N, w]`` float32 contiguous segments, ``width`` wide together, a normaliser reads side by side (``act``'s
+    rules: nothing is cast)."""
+    parts = (x,) if isinstance(x, torch.Tensor) else tuple(x) if isinstance(x, (list, tuple)) else None
+    if not parts or len(parts) > nat.GF_MLP_MAX_INPUTS:
+        raise ValueError(f"{name} must be a tensor or a sequence of 1 to {nat.GF_MLP_MAX_INPUTS} tensors")
+    n = None
+    for i, t in enumerate(parts):
+        what = f"{name}[{i}]" if len(parts) > 1 else name
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] < 1:
+            raise ValueError(f"{what} must be a [N, W] tensor")
+        if not t.is_contiguous():
+            raise ValueError(f"EmpiricalNormalization reads contiguous observation rows: {what} is a strided view (an ObservationManager "
+                             "with output='window' hands one out) — use output='fresh' / 'static' for the managers it follows")
+        n = int(t.shape[0]) if n is None else n
+        _check_f32(t, what, {(n, int(t.shape[1]))}, device)
+    if sum(int(t.shape[1]) for t in parts) != width:
+        raise ValueError(f"{name} is {' + '.join(str(int(t.shape[1])) for t in parts)} wide; the normaliser keeps {width} columns")
+    return parts
+
+
+class _NormScratch:
+    """The native descriptor and the workspace of a module's ``gf_obs_norm_update`` calls: call-to-call scratch, so a copy or a
+    pickle of the module starts with a fresh one (a ctypes struct that holds pointers can be neither copied nor pickled)."""
+
+    def __init__(self):
+        self.args = nat.GfObsNormArgs()
+        self.workspace = None
+
+    def __deepcopy__(self, memo):
+        return _NormScratch()
+
+    def __reduce__(self):
+        return (_NormScratch, ())
+
+
+class EmpiricalNormalization(torch.nn.Module):
+    """rsl_rl's ``EmpiricalNormalization``: ``forward(x) = (x - mean) / (std + eps)`` with the running mean / variance of every batch
+    ``update`` has seen.  The buffers carry rsl_rl's names and shapes (``_mean`` / ``_var`` / ``_std`` ``[1, W]``, ``count`` an int64
+    scalar), so its checkpoints load.  ``until``: no update once ``count >= until``.
+
+    ``update(x)`` takes a ``[N, W]`` tensor or a sequence of up to four segments side by side (an observation group's members, no
+    ``torch.cat``); float32, contiguous, on the buffers' device — nothing is cast.  No-op in eval mode.  On the HIP backend it is one
+    ``gf_obs_norm_update`` (two launches) that writes the buffers in place and never reads the device from the host, the ``until``
+    test included; the batch moments and the update are evaluated in float64 and rounded to float32 once, so the buffers agree with
+    rsl_rl's float32 lines to rounding, not bit for bit.  For CPU tensors, or on a backend without the entry point (the test-only CPU
+    oracle), rsl_rl's lines run in torch.  ``ActorCriticMLP.update_normalization`` updates the actor's and the critic's in one call.
+    The statistics are rank-local, as rsl_rl's: nothing averages them across the ranks of a multi-GPU run."""
+
+    def __init__(self, shape, eps: float = 1e-2, until: Optional[int] = None):
+        super().__init__()
+        width = int(shape) if isinstance(shape, int) else (int(shape[0]) if len(shape) == 1 else None)
+        if width is None or width < 1:
+            raise ValueError(f"EmpiricalNormalization keeps one row of statistics: shape={shape!r} must be W or (W,), W >= 1")
+        self.width, self.eps, self.until = width, float(eps), until
+        self.register_buffer("_mean", torch.zeros(width).unsqueeze(0))
+        self.register_buffer("_var", torch.ones(width).unsqueeze(0))
+        self.register_buffer("_std", torch.ones(width).unsqueeze(0))
+        self.register_buffer("count", torch.tensor(0, dtype=torch.long))
+        self._scratch = _NormScratch()
+
+    @property
+    def mean(self) -> torch.Tensor:
+        return self._mean.squeeze(0).clone()
+
+    @property
+    def std(self) -> torch.Tensor:
+        return self._std.squeeze(0).clone()
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return (x - self._mean) / (self._std + self.eps)
+
+    def inverse(self, y: torch.Tensor) -> torch.Tensor:
+        return y * (self._std + self.eps) + self._mean
+
+    def update(self, x) -> None:
+        if not self.training:
+            return
+        _update_normalizers([(self, _obs_segments(x, self.width, "x", self._mean.device))], self._scratch.args)
+
+    def _update_torch(self, x: torch.Tensor) -> None:
+        """rsl_rl's lines."""
+        if self.until is not None and self.count >= self.until:
+            return
+        with torch.no_grad():
+            count_x = x.shape[0]
+            self.count += count_x
+            rate = count_x / self.count
+            var_x = torch.var(x, dim=0, unbiased=False, keepdim=True)
+            mean_x = torch.mean(x, dim=0, keepdim=True)
+            delta_mean = mean_x - self._mean
+            self._mean += rate * delta_mean
+            self._var += rate * (var_x - self._var + delta_mean * (mean_x - self._mean))
+            self._std = torch.sqrt(self._var)
+
+    def _fill(self, st, parts) -> None:
+        """Point set ``st`` of a GfObsNormArgs at the segments, the buffers and this normaliser's workspace."""
+        n, dev = int(parts[0].shape[0]), self._mean.device
+        need = max(1, nat.obs_norm_workspace_bytes(n, self.width) // 8)
+        ws = self._scratch.workspace
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = self._scratch.workspace = torch.empty(need, device=dev, dtype=torch.float64)
+        for b in (self._mean, self._var, self._std):
+            if b.dtype != torch.float32 or not b.is_contiguous():
+                raise ValueError("EmpiricalNormalization: the kernel updates float32 contiguous buffers in place")
+        st.num_inputs = len(parts)
+        for seg, t in zip(st.inputs, parts):
+            seg.rows, seg.width = t.data_ptr(), t.shape[1]
+        st.mean, st.var, st.std, st.count = self._mean.data_ptr(), self._var.data_ptr(), self._std.data_ptr(), self.count.data_ptr()
+        st.until = -1 if self.until is None else int(self.until)
+        st.workspace, st.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+
+
+def _update_normalizers(pairs, args) -> None:
+    """``[(normaliser, segments)]`` (at most GF_OBS_NORM_MAX_SETS, the same number of rows each) in one ``gf_obs_norm_update`` — or, for
+    CPU tensors and on a backend without it, rsl_rl's torch lines per normaliser."""
+    if not pairs:
+        return
+    n = int(pairs[0][1][0].shape[0])
+    if any(int(parts[0].shape[0]) != n for _, parts in pairs):
+        raise ValueError("the normalisers of one update read the same number of rows")
+    fn = getattr(nat.get_backend(), "obs_norm_update", None) if pairs[0][1][0].device.type == "cuda" else None
+    if fn is None:
+        for norm, parts in pairs:
+            norm._update_torch(parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1))
+        return
+    args.num_rows, args.num_sets = n, len(pairs)
+    for st, (norm, parts) in zip(args.sets, pairs):
+        norm._fill(st, parts)
+    fn(args)   # (the segments are the caller's tensors; the launches are on the current stream, in front of whatever frees them)
+
+
+def _as_normalizer(m, width: int, what: str) -> Optional["EmpiricalNormalization"]:
+    """``m`` as the EmpiricalNormalization of ``width`` columns it is, or None for ``None`` / ``nn.Identity``; anything else: ValueError."""
+    if m is None or isinstance(m, torch.nn.Identity):
+        return None
+    if not isinstance(m, EmpiricalNormalization):
+        raise ValueError(f"{what} is {type(m).__name__}; only EmpiricalNormalization or nn.Identity can be folded into the kernels")
+    if m.width != width:
+        raise ValueError(f"{what} keeps {m.width} columns; its input is {width} wide")
+    return m
+
+
+_POLICY_KEYS = ("class_name", "activation", "actor_hidden_dims", "critic_hidden_dims", "init_noise_std", "noise_std_type",
+                "actor_obs_normalization", "critic_obs_normalization")
+
+
 class ActorCriticMLP(torch.nn.Module):
-    """rsl_rl's ``ActorCritic`` as configured by the reference's training scripts (examples/simple/train.py:56-62)."""
+    """rsl_rl's ``ActorCritic`` as configured by the reference's training scripts (examples/simple/train.py:56-62).
+    ``actor_obs_normalization`` / ``critic_obs_normalization`` (rsl_rl 3.x): an :class:`EmpiricalNormalization` in front of the net
+    (``actor_obs_normalizer`` / ``critic_obs_normalizer``; ``nn.Identity()`` when off, as rsl_rl) — buffers only, so ``parameters()``
+    and their order are the same either way.  ``num_critic_obs``: the critic's input width where it differs from the actor's."""
 
     def __init__(self, num_obs: int, num_actions: int, actor_hidden_dims: Sequence[int] = (512, 256, 128),
-                 critic_hidden_dims: Sequence[int] = (512, 256, 128), init_noise_std: float = 1.0):
+                 critic_hidden_dims: Sequence[int] = (512, 256, 128), init_noise_std: float = 1.0, num_critic_obs: Optional[int] = None,
+                 actor_obs_normalization: bool = False, critic_obs_normalization: bool = False):
         super().__init__()
 
         def mlp(sizes):
@@ -699,15 +878,51 @@ class ActorCriticMLP(torch.nn.Module):
                     layers.append(torch.nn.ELU())
             return torch.nn.Sequential(*layers)
 
+        num_critic_obs = num_obs if num_critic_obs is None else int(num_critic_obs)
         self.actor = mlp([num_obs, *actor_hidden_dims, num_actions])
-        self.critic = mlp([num_obs, *critic_hidden_dims, 1])
+        self.critic = mlp([num_critic_obs, *critic_hidden_dims, 1])
         self.std = torch.nn.Parameter(init_noise_std * torch.ones(num_actions))
+        self.actor_obs_normalizer = EmpiricalNormalization(num_obs) if actor_obs_normalization else torch.nn.Identity()
+        self.critic_obs_normalizer = EmpiricalNormalization(num_critic_obs) if critic_obs_normalization else torch.nn.Identity()
+        self._scratch = _NormScratch()
+
+    @classmethod
+    def from_train_cfg(cls, train_cfg: dict, num_obs: int, num_actions: int, num_critic_obs: Optional[int] = None) -> "ActorCriticMLP":
+        """The policy of a ``training_cfg()`` dict of ``examples/*/train.py``: ``policy.actor_hidden_dims`` / ``critic_hidden_dims`` /
+        ``init_noise_std``, rsl_rl 3.x's ``policy.actor_obs_normalization`` / ``critic_obs_normalization``, and the top-level
+        ``empirical_normalization`` the scripts carry (truthy: both normalisers; ``None`` / ``False``: the policy keys decide).
+        Anything that cannot be honoured — another activation than ``"elu"``, another ``noise_std_type`` than ``"scalar"``, an
+        unknown policy key — raises ``ValueError`` naming the key."""
+        pol = dict(train_cfg.get("policy", {}))
+        bad = sorted(k for k in pol if k not in _POLICY_KEYS)
+        if bad:
+            raise ValueError(f"ActorCriticMLP: unsupported policy keys {bad}")
+        if pol.get("activation", "elu") != "elu":
+            raise ValueError(f"ActorCriticMLP: policy.activation={pol['activation']!r} is not supported (only 'elu')")
+        if pol.get("noise_std_type", "scalar") != "scalar":
+            raise ValueError(f"ActorCriticMLP: policy.noise_std_type={pol['noise_std_type']!r} is not supported (only 'scalar')")
+        if pol.get("class_name", "ActorCritic") != "ActorCritic":
+            raise ValueError(f"ActorCriticMLP: policy.class_name={pol['class_name']!r} is not supported (only 'ActorCritic')")
+        both = bool(train_cfg.get("empirical_normalization"))
+        return cls(num_obs, num_actions, tuple(pol.get("actor_hidden_dims", (512, 256, 128))), tuple(pol.get("critic_hidden_dims", (512, 256, 128))),
+                   float(pol.get("init_noise_std", 1.0)), num_critic_obs=num_critic_obs,
+                   actor_obs_normalization=both or bool(pol.get("actor_obs_normalization", False)),
+                   critic_obs_normalization=both or bool(pol.get("critic_obs_normalization", False)))
 
     def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
-        return self.actor(obs)
+        return self.actor(self.actor_obs_normalizer(obs))
 
     def evaluate(self, obs: torch.Tensor) -> torch.Tensor:
-        return self.critic(obs)
+        return self.critic(self.critic_obs_normalizer(obs))
+
+    def update_normalization(self, obs, critic_obs=None) -> None:
+        """rsl_rl's ``ActorCritic.update_normalization``: both normalisers see this step's observations (``critic_obs=None``: the critic
+        reads ``obs``) — ONE ``gf_obs_norm_update`` for the two.  ``obs`` / ``critic_obs``: a ``[N, W]`` tensor or up to four segments."""
+        pairs = []
+        for norm, x, name in ((self.actor_obs_normalizer, obs, "obs"), (self.critic_obs_normalizer, obs if critic_obs is None else critic_obs, "critic_obs")):
+            if isinstance(norm, EmpiricalNormalization) and norm.training:
+                pairs.append((norm, _obs_segments(x, norm.width, name, norm._mean.device)))
+        _update_normalizers(pairs, self._scratch.args)
 
 
 class PolicyForward:
@@ -719,6 +934,10 @@ class PolicyForward:
     structure is kept: the weight addresses are read from the parameters at every call, so a ``PolicyForward`` made before a
     :class:`PPO` (which re-seats every ``p.data`` into its flat buffer and updates it in place) sees the current weights.
 
+    ``policy.actor_obs_normalizer`` / ``policy.critic_obs_normalizer`` (missing, ``None``, ``nn.Identity`` or an
+    :class:`EmpiricalNormalization` of the first layer's width — anything else raises ``ValueError``) are looked up at every call like
+    the weights; the kernel normalises the input as it stages it, so a normalising policy's forward stays one launch.
+
     ``mean(obs)`` / ``value(critic_obs)``: play-time inference and the bootstrap value, one launch each, fresh tensors;
     ``RolloutStorage.act_policy(forward, obs)``: the collection step.  An observation is a ``[N, W]`` tensor or a sequence of up to
     four whose widths add up to the first layer's input (an observation group's members, no ``torch.cat``)."""
@@ -729,6 +948,7 @@ class PolicyForward:
         self.critic = self._walk(getattr(policy, "critic", None), "critic", 1)
         if self.actor is None and self.critic is None:
             raise ValueError("PolicyForward: the policy has neither an actor nor a critic")
+        self._normalizer("actor"), self._normalizer("critic")   # (refuses what the kernel cannot fold in)
         std = getattr(policy, "std", None)
         self.num_actions = None
         if self.actor is not None and isinstance(std, torch.Tensor):
@@ -777,6 +997,13 @@ class PolicyForward:
             raise ValueError(f"PolicyForward: policy.{name} has {out} outputs; at most {max_out}")
         return layers
 
+    def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
+        """The policy's current normaliser in front of ``name`` (None: the net reads its input as it is)."""
+        layers = self.actor if name == "actor" else self.critic
+        if layers is None:
+            return None
+        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), int(layers[0][0].shape[1]), f"PolicyForward: policy.{name}_obs_normalizer")
+
     @staticmethod
     def _segments(obs, layers, name: str, n: Optional[int], dev) -> tuple:
         """``obs`` as the tuple of ``[n, w]`` float32 contiguous segments the first layer of ``layers`` reads side by side."""
@@ -797,10 +1024,17 @@ class PolicyForward:
         return parts
 
     @staticmethod
-    def _fill_net(net, layers, parts) -> None:
+    def _fill_net(net, layers, parts, norm=None) -> None:
         if layers is None or parts is None:
             net.num_layers = 0
             return
+        if norm is None:
+            if net.in_mean is not None:
+                net.in_mean = net.in_std = None
+        else:
+            if norm._mean.device != parts[0].device:
+                raise ValueError(f"the observation lives on {parts[0].device}, the normaliser on {norm._mean.device}")
+            net.in_mean, net.in_std, net.in_eps = norm._mean.data_ptr(), norm._std.data_ptr(), norm.eps
         net.num_layers, net.num_inputs = len(layers), len(parts)
         for seg, x in zip(net.inputs, parts):
             seg.rows, seg.width = x.data_ptr(), x.shape[1]
@@ -811,8 +1045,8 @@ class PolicyForward:
         """The descriptor with both nets pointed at the current weights and the given inputs (None: that net is left out)."""
         a = self._args
         a.num_envs = n
-        self._fill_net(a.actor, self.actor, actor_parts)
-        self._fill_net(a.critic, self.critic, critic_parts)
+        self._fill_net(a.actor, self.actor, actor_parts, self._normalizer("actor"))
+        self._fill_net(a.critic, self.critic, critic_parts, self._normalizer("critic"))
         return a
 
     def _one(self, obs, layers, name: str, torch_fn) -> torch.Tensor:
@@ -821,8 +1055,10 @@ class PolicyForward:
         parts = self._segments(obs, layers, "obs", None, None)
         fn = getattr(nat.get_backend(), "mlp_act", None)
         if fn is None:   # (the test-only oracle backend)
+            norm = self._normalizer(name)
             with torch.no_grad():
-                return torch_fn(parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1))
+                x = parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+                return torch_fn(x if norm is None else norm(x))
         n = int(parts[0].shape[0])
         out = torch.empty((n, int(layers[-1][0].shape[0])), device=parts[0].device, dtype=torch.float32)
         a = self._fill(n, parts if name == "actor" else None, parts if name == "critic" else None)
@@ -927,7 +1163,18 @@ class PPO:
     Per minibatch ``update()`` zeroes the bucket, runs the actor / critic forward, ``gf_ppo_loss`` (the loss, its gradient w.r.t.
     mu / value / std), back-propagates the kernel's gradients, all-reduces ``kl_mean`` over the ranks when there are several,
     averages the bucket, and ``gf_adam_step`` (schedule, clipping, Adam) — no host synchronisation; the returned means are one read
-    at the end.  On a backend without these entry points (the test-only CPU oracle) the same arithmetic runs in torch."""
+    at the end.  On a backend without these entry points (the test-only CPU oracle) the same arithmetic runs in torch.
+
+    A policy with observation normalisers (:class:`EmpiricalNormalization` as ``policy.actor_obs_normalizer`` /
+    ``critic_obs_normalizer``) gets its minibatches normalised by the gather's own launch and ``policy.actor`` / ``policy.critic``
+    run on them directly — the statistics are frozen during an update, so this is rsl_rl's ``policy.act(obs_batch)``.  The
+    collection loop updates them where rsl_rl's ``process_env_step`` does::
+
+        actions = storage.act_policy(forward, obs)
+        obs, rew, term, trunc, extras = env.step(actions)
+        policy.update_normalization(obs)
+        storage.process_env_step(trunc, gamma=ppo.gamma, episodes=stats)
+    """
 
     def __init__(self, policy: "ActorCriticMLP", storage: RolloutStorage, grad_sync: Optional[GradientAllReduce] = None, **algorithm):
         algorithm = dict(algorithm)
@@ -1003,18 +1250,26 @@ class PPO:
         """``num_learning_epochs x num_mini_batches`` minibatches of ``storage.mini_batch_generator`` (``generator``: its randperm's);
         returns rsl_rl 3.x's ``{"value_function", "surrogate", "entropy"}`` means — the one host read of the update."""
         self._sums.zero_()
-        for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, generator=generator):
-            self._minibatch(batch)
+        norms = self._normalizers()
+        for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, generator=generator,
+                                                       obs_normalizer=norms[0], critic_obs_normalizer=norms[1]):
+            self._minibatch(batch, norms)
         vf, surr, ent = self._sums.tolist()
         k = self.num_learning_epochs * self.num_mini_batches
         return {"value_function": vf / k, "surrogate": surr / k, "entropy": ent / k}
 
     # -- one minibatch ------------------------------------------------------------------------------------------------------------
-    def _minibatch(self, b: MiniBatch) -> None:
+    def _normalizers(self):
+        """The policy's (actor, critic) observation normalisers that are EmpiricalNormalization; None for Identity / a missing one."""
+        pick = lambda m: m if isinstance(m, EmpiricalNormalization) else None
+        return pick(getattr(self.policy, "actor_obs_normalizer", None)), pick(getattr(self.policy, "critic_obs_normalizer", None))
+
+    def _minibatch(self, b: MiniBatch, norms=(None, None)) -> None:
+        """``norms``: the normalisers the batch's ``obs`` / ``critic_obs`` have already been through (the gather applied them)."""
         sync, policy = self.grad_sync, self.policy
         sync.zero_grad()
-        mu = policy.act_mean(b.obs)
-        value = policy.evaluate(b.critic_obs)
+        mu = policy.act_mean(b.obs) if norms[0] is None else policy.actor(b.obs)
+        value = policy.evaluate(b.critic_obs) if norms[1] is None else policy.critic(b.critic_obs)
         backend = self.storage.env.backend
         hip = getattr(backend, "ppo_loss", None) is not None   # (else the test-only oracle backend: rsl_rl's expression, autograd, torch Adam)
         if hip:

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 7
+#define GF_ABI_VERSION 8
 
 #define GF_MAX_TERMS 24          /* reward terms per manager          */
 #define GF_MAX_TERM_TERMS 16     /* termination terms per manager     */
@@ -686,7 +686,13 @@ typedef struct GfCompactArgs {
  *     fields[f].dst[i * dst_width + dst_col + c] = fields[f].src[indices[i] * src_width + c]   (i < num_rows, c < src_width)
  * `dst_col` lets the members of a concatenated observation group land side by side in one [num_rows, dst_width] output.
  * An index outside [0, num_src_rows) is never dereferenced: its row is written as quiet NaN in every field.  Pure copy:
- * bit-identical to `src[indices]`.  Not a phase of the step: it never enters a recorded step's op table.
+ * bit-identical to `src[indices]` — unless the field carries a normaliser (`mean != NULL`; rsl_rl EmpiricalNormalization.forward
+ * on the gathered observations): its elements are then stored as
+ *     (src[indices[i], c] - mean[c]) / (std[c] + eps)        (one subtraction, one addition, one correctly rounded division)
+ * by the same launch.  `mean` / `std` are `[src_width]`; a member of a concatenated group points at its slice of the group's
+ * normaliser (`norm.mean + dst_col`), so the two vectors may be less aligned than the rows: they are read by element.  Rows of
+ * out-of-range indices stay quiet NaN.  Refusals: GF_E_NULL — `mean` without `std`.
+ * Not a phase of the step: it never enters a recorded step's op table.
  * ---------------------------------------------------------------------------------------- */
 #define GF_MINIBATCH_MAX_FIELDS 12
 
@@ -697,6 +703,10 @@ typedef struct GfMinibatchField {
     int32_t dst_width;          /* >= dst_col + src_width */
     int32_t dst_col;            /* first destination column of this field */
     int32_t _pad;
+    const float* mean;          /* [src_width] normaliser mean, or NULL: pure copy */
+    const float* std;           /* [src_width] normaliser std (required with mean) */
+    float eps;                  /* added to std */
+    int32_t _pad2;
 } GfMinibatchField;
 
 typedef struct GfMinibatchArgs {
@@ -902,11 +912,16 @@ typedef struct GfAdamArgs {
  * One chain per output element, no split-K, no atomics: row n's results depend on row n's inputs only — not on num_envs, the tile it
  * falls in, env_offset or the run.  The f32 MFMA is bit for bit such a chain (one rounding per fma, f32 accumulator).
  *
+ * Input normalisation (rsl_rl EmpiricalNormalization.forward in front of a net; `in_mean == NULL`: none, the path above bit for bit):
+ *     x[n, k] = (obs[n, k] - in_mean[k]) / (in_std[k] + in_eps)     (one subtraction, one addition, one correctly rounded division)
+ * applied to every real element as the first layer's input is staged — k is the column of the whole input, across the segments; the
+ * zero padding of rows past num_envs and of columns past the input width stays zero.  No launch and no [N, W] tensor of its own.
+ *
  * Either net may be absent (num_layers == 0): actor only = play-time inference, critic only = the bootstrap value.  With an actor,
  * `actions == NULL` computes the mean only and draws nothing (then `mean` is required and actions_out / mu_out / sigma_out /
  * log_prob_out must be NULL).  `mean` / `values` are optional fresh outputs.
- * Refusals, before anything is launched: GF_E_NULL — args, a weight / bias / segment pointer, std with actions, an actor without
- * mean and actions, a critic without values and values_out, an actor's or critic's output pointer with that net absent;
+ * Refusals, before anything is launched: GF_E_NULL — args, a weight / bias / segment pointer, in_mean without in_std, std with
+ * actions, an actor without mean and actions, a critic without values and values_out, an actor's or critic's output pointer with that net absent;
  * GF_E_RANGE — num_envs < 0, more than GF_MLP_MAX_LAYERS layers, a segment count outside 1 … GF_MLP_MAX_INPUTS, a width < 1, a
  * hidden width > GF_MLP_MAX_HIDDEN, a total input width > GF_MLP_MAX_INPUT_WIDTH, an actor output > GF_MLP_MAX_ACTIONS,
  * std_per_env outside {0, 1}; GF_E_UNSUPPORTED — both nets absent, a critic output other than 1.  num_envs == 0 is a no-op.
@@ -937,6 +952,10 @@ typedef struct GfMlpNet {
     int32_t num_inputs;         /* 1 … GF_MLP_MAX_INPUTS */
     GfMlpSegment inputs[GF_MLP_MAX_INPUTS];
     GfMlpLayer layers[GF_MLP_MAX_LAYERS];
+    const float* in_mean;       /* [input width] normaliser mean spanning all segments, or NULL: the input is read as it is */
+    const float* in_std;        /* [input width] normaliser std (required with in_mean) */
+    float in_eps;               /* added to in_std */
+    int32_t _pad;
 } GfMlpNet;
 
 typedef struct GfMlpActArgs {
@@ -958,6 +977,61 @@ typedef struct GfMlpActArgs {
     float* values_out;
     float* log_prob_out;
 } GfMlpActArgs;
+
+/* ------------------------------------------------------------------------------------------
+ * Running observation statistics (rsl_rl EmpiricalNormalization.update; the "empirical_normalization" switch of the training
+ * scripts, rsl_rl 3.x's actor_obs_normalization / critic_obs_normalization).  rsl_rl updates a normaliser with torch.mean, torch.var
+ * and a handful of elementwise launches — about ten per normaliser and collection step.  gf_obs_norm_update updates up to
+ * GF_OBS_NORM_MAX_SETS normalisers (the actor's and the critic's) from num_rows rows each in TWO launches.  A set reads its input as
+ * up to GF_MLP_MAX_INPUTS segments `[N, width]` side by side (as gf_mlp_act: no torch.cat), total width W <= GF_MLP_MAX_INPUT_WIDTH.
+ * Per set and column c, with N = num_rows:
+ *     if until >= 0 and count >= until:  nothing of the set is written
+ *     mx = (Σ_n x[n,c]) / N          vx = (Σ_n (x[n,c] - mx)²) / N           (biased, as torch.var(unbiased=False))
+ *     count' = count + N             rate = N / count'
+ *     d = mx - mean                  mean' = mean + rate·d
+ *     var' = var + rate·(vx - var + d·(mx - mean'))
+ *     std' = sqrtf(var')             (from the f32-rounded var': torch.sqrt(_var) bit for bit)
+ * Everything down to var' is evaluated in float64 from the f32 inputs and the f32 state; mean' and var' are rounded to f32 once each
+ * when stored.
+ * Launch 1: workgroups own tiles of GF_OBS_NORM_TILE_ROWS rows (at most GF_OBS_NORM_MAX_PARTIALS workgroups per set, grid-stride
+ * above); a lane keeps a fixed column (a fixed four above 256 columns) as it walks rows and accumulates Σ(x - s), Σ(x - s)² in float64
+ * around s = the first element it reads; a workgroup leaves one record per column — its row count once, then (mean, M2 = Σ(x - mean)²)
+ * per column — in the caller's workspace.  Launch 2: ONE workgroup per set sums the records in a fixed order, applies the update and
+ * writes mean / var / std / count — the only workgroup that reads or writes `count`.  grid y = set in both launches.  No float atomics,
+ * no hand-off or wait between workgroups: bitwise reproducible from run to run, and a column's result does not depend on the other set.
+ * Refusals, before anything is launched: GF_E_NULL — args, a segment / mean / var / std / count / workspace pointer; GF_E_RANGE —
+ * num_rows < 0, num_sets outside 1 … GF_OBS_NORM_MAX_SETS, a segment count outside 1 … GF_MLP_MAX_INPUTS, a width < 1, a total width
+ * > GF_MLP_MAX_INPUT_WIDTH, a workspace smaller than GF_OBS_NORM_WORKSPACE_BYTES(num_rows, W) or not 8-byte aligned, a count pointer
+ * not 8-byte aligned.  num_rows == 0 is a no-op.  No allocation, no copy, no synchronisation inside.  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_OBS_NORM_MAX_SETS 2         /* normalisers per call (actor, critic) */
+#define GF_OBS_NORM_TILE_ROWS 256      /* rows per tile of launch 1 */
+#define GF_OBS_NORM_MAX_PARTIALS 256   /* workgroups (partial records) per set at most */
+#define GF_OBS_NORM_PARTIALS(N) \
+    ((((N) + GF_OBS_NORM_TILE_ROWS - 1) / GF_OBS_NORM_TILE_ROWS) < GF_OBS_NORM_MAX_PARTIALS ? \
+     (((N) + GF_OBS_NORM_TILE_ROWS - 1) / GF_OBS_NORM_TILE_ROWS) : GF_OBS_NORM_MAX_PARTIALS)
+/* workspace of one set: (1 + 2 W) doubles per partial workgroup — {rows, mean[W], M2[W]} — 8-byte aligned */
+#define GF_OBS_NORM_WORKSPACE_BYTES(N, W) ((int64_t)GF_OBS_NORM_PARTIALS((int64_t)(N)) * (1 + 2 * (int64_t)(W)) * 8)
+
+typedef struct GfObsNormSet {
+    int32_t num_inputs;         /* 1 … GF_MLP_MAX_INPUTS */
+    int32_t _pad;
+    GfMlpSegment inputs[GF_MLP_MAX_INPUTS];   /* [num_rows, width] each, side by side: W = the sum of the widths */
+    float* mean;                /* [W] running mean, updated in place */
+    float* var;                 /* [W] running (biased) variance */
+    float* std;                 /* [W] sqrt(var) */
+    int64_t* count;             /* one word: rows seen so far (rsl_rl's `count` buffer) */
+    int64_t until;              /* >= 0: no update once count >= until; negative: none */
+    void* workspace;            /* GF_OBS_NORM_WORKSPACE_BYTES(num_rows, W) bytes, 8-byte aligned; not shared with the other set */
+    int64_t workspace_bytes;
+} GfObsNormSet;
+
+typedef struct GfObsNormArgs {
+    int64_t num_rows;           /* N >= 0 rows of every set; 0: nothing is launched */
+    int32_t num_sets;           /* 1 … GF_OBS_NORM_MAX_SETS */
+    int32_t _pad;
+    GfObsNormSet sets[GF_OBS_NORM_MAX_SETS];
+} GfObsNormArgs;
 
 /* ------------------------------------------------------------------------------------------
  * History ring -> the reference's observation layout.  The reference keeps a list of H frames, pops the oldest, inserts the new
@@ -1000,7 +1074,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -1027,6 +1101,7 @@ int gf_policy_act(const GfPolicyActArgs* a, void* stream);       /* Normal sampl
 int gf_episode_step(const GfEpisodeArgs* a, void* stream);       /* time-out bootstrap + the runner's rewbuffer / lenbuffer upkeep (rsl_rl OnPolicyRunner.learn) */
 int gf_ppo_loss(const GfPpoLossArgs* a, void* stream);           /* minibatch loss + its gradient w.r.t. mu / value / sigma (rsl_rl PPO.update: the KL block, surrogate, value loss, loss, loss.backward() down to the policy outputs, the three .item()) */
 int gf_mlp_act(const GfMlpActArgs* a, void* stream);             /* actor + critic MLP forward on the f32 matrix cores, then gf_policy_act's sampling and rows, in one launch (rsl_rl ActorCritic.act / evaluate inside PPO.act) */
+int gf_obs_norm_update(const GfObsNormArgs* a, void* stream);    /* running mean / var / std / count of up to two observation normalisers in two launches (rsl_rl EmpiricalNormalization.update) */
 int gf_adam_step(const GfAdamArgs* a, void* stream);             /* adaptive lr + clip_grad_norm_ + Adam.step over the flat bucket (rsl_rl PPO.update: the lr schedule, nn.utils.clip_grad_norm_, optimizer.step()) */
 
 /* ------------------------------------------------------------------------------------------

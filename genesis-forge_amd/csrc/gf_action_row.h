@@ -29,9 +29,10 @@ constexpr int kActionUpkeepBlocks = 24;
 
 inline int action_upkeep_blocks(const GfActionArgs* a) { return (a->stats_zero || (a->stats_fold_src && a->stats_fold_dst)) ? kActionUpkeepBlocks : 0; }
 
-// the body of an upkeep workgroup (blockIdx.x < upkeep); any workgroup size that is a multiple of the wave
-__device__ __forceinline__ void action_upkeep(const GfActionArgs& a, const int upkeep) {
-    const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x), nt = (int)(upkeep * blockDim.x);
+// the body of an upkeep workgroup (blockIdx.x < upkeep); any workgroup size that is a multiple of the wave (`block`: a kernel that
+// knows its size at compile time says so, and needs no implicit kernel argument for it)
+__device__ __forceinline__ void action_upkeep(const GfActionArgs& a, const int upkeep, const unsigned block = blockDim.x) {
+    const int t = (int)(blockIdx.x * block + threadIdx.x), nt = (int)(upkeep * block);
     if (a.stats_zero) {   // nobody else touches the next slot during this step
         constexpr int kWords = (int)(sizeof(GfStepStats) * GF_STATS_SHARDS / 4);
         for (int w = t; w < kWords; w += nt) reinterpret_cast<uint32_t*>(a.stats_zero)[w] = 0u;

@@ -17,6 +17,7 @@ int chain_a_try(const GfOp* ops, int i, int num_ops, hipStream_t s, int* rc, Def
 int chain_b_try(const GfOp* ops, int i, int num_ops, hipStream_t s, int* rc, DeferredFlags* deferred);
 int gait_launch(const GfGaitArgs* a, hipStream_t s, bool flags_all);                                      // gf_gait.hip
 int action_scene_try(const GfActionArgs* act, const GfSynthSceneArgs* a, hipStream_t s, int* rc);           // gf_scene.hip
+int step_fold_try(const GfActionArgs* act, const GfSynthSceneArgs* sc, const GfPostRefs* refs, hipStream_t s, int* rc);   // gf_post.hip
 int unroll_pair(const GfHistoryUnrollArgs* a, const GfHistoryUnrollArgs* b, hipStream_t s, int* fused);   // gf_unroll.hip
 }
 
@@ -266,6 +267,12 @@ GF_EXPORT int gf_run_ops(const GfOp* ops, int num_ops, void* stream, int* failed
                 // the stand-in scene tick directly behind it streams the same rows with the same lanes: one launch for both, the
                 // targets stay in registers (gf_scene.hip; with an external simulator the two ops are never adjacent)
                 if (i + 1 < num_ops && ops[i + 1].phase == GF_PHASE_SCENE && ops[i + 1].args) {
+                    // … and with the fused post-physics op directly behind the pair — a recorded step on the stand-in scene — the tick
+                    // runs as that kernel's prologue: the step is one launch (gf_post.hip); otherwise nothing has happened here
+                    if (i + 2 < num_ops && ops[i + 2].phase == GF_OP_POST_PHYSICS && ops[i + 2].args) {
+                        const int done = gf::step_fold_try((const GfActionArgs*)a, (const GfSynthSceneArgs*)ops[i + 1].args, (const GfPostRefs*)ops[i + 2].args, s, &rc);
+                        if (done > 0) { i += done - 1; break; }
+                    }
                     const int used = gf::action_scene_try((const GfActionArgs*)a, (const GfSynthSceneArgs*)ops[i + 1].args, s, &rc);
                     if (used > 0) { i += used - 1; break; }
                 }

@@ -150,6 +150,13 @@ inline int launch_status() {
     return e == hipSuccess ? GF_OK : (int)e;
 }
 
+// how an action op directly in front of a stand-in scene op runs inside the tick's launch (gf_scene.hip: action_scene_check)
+struct ActionScenePlan {
+    int dv;                        // float4 chunks per DOF row: 3 or 7
+    bool links, contacts, small;   // per-link outputs, contact slots (the tile kernel with 16-env tiles when `small`)
+    int upkeep;                    // leading statistics-upkeep workgroups
+};
+
 // gait states whose swing / stance bytes chain A left for a later masked gait launch of the same gf_run_ops call (gf_chain.hip)
 struct DeferredFlags {
     const float* state[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -577,8 +577,20 @@ static int fold_contacts(Packer& pk, const GfContactArgs* const* mgrs, int num) 
     return GF_OK;
 }
 
-static int post_launch(const GfPostArgs& a, hipStream_t s);
+// the action and scene ops of a step that run as the launch's tick prologue (post_ws_kernel_tick)
+struct TickLaunch {
+    const GfActionArgs* act;
+    const GfSynthSceneArgs* scene;
+    int upkeep;
+};
+// launches the post-physics kernel of program `prog` (select_program; -1: selected here); with `tick`, that program's tick variant
+// (the caller has asked tick_variant)
+static int post_launch(const GfPostArgs& a, hipStream_t s, int prog = -1, const TickLaunch* tick = nullptr);
+int action_scene_check(const GfActionArgs* act, const GfSynthSceneArgs* a, int* rc, ActionScenePlan* plan);   // gf_scene.hip
+int action_scene_launch(const GfActionArgs* act, const GfSynthSceneArgs* a, const ActionScenePlan& p, hipStream_t s);
 bool post_program_folds(const GfPostArgs& a);   // the kernel this descriptor selects carries the contact phase
+
+int step_fold_try(const GfActionArgs* act, const GfSynthSceneArgs* sc, const GfPostRefs* refs, hipStream_t s, int* rc);
 
 int post_step(const GfPostRefs* r, const GfContactArgs* const* mgrs, int num_mgr, hipStream_t s) {
     Packer pk;
@@ -705,7 +717,12 @@ extern "C" __attribute__((visibility("default"))) int gf_post_physics_describe(c
     return GF_OK;
 }
 
-int gf::post_launch(const gf::GfPostArgs& packed, hipStream_t s) {
+#define GF_TICK_INTERP(DV_) gf::Interp<DV_, false>   // (a macro argument cannot hold the comma)
+// Which programs carry the tick prologue: static programs 1 and 2 and the 12- / 28-DOF table interpreter.  A program compiled at run
+// time and the other built-in ones (contact phases, per-link rows: scenes the tick variant does not cover) keep their own launch.
+static bool tick_variant(int prog, int num_dofs) { return prog == 1 || prog == 2 || (prog == 0 && (num_dofs == 12 || num_dofs == 28)); }
+
+int gf::post_launch(const gf::GfPostArgs& packed, hipStream_t s, int prog, const gf::TickLaunch* tick) {
 #ifdef GF_STAMPS
     gf::GfPostArgs stamped = packed;
     stamped.stamps = gf_debug_stamps;
@@ -723,8 +740,20 @@ int gf::post_launch(const gf::GfPostArgs& packed, hipStream_t s) {
         return (bytes > need ? bytes : need) + (size_t)gf::kWsTilesLdsFloats * sizeof(float);
     };
     const unsigned grid = gf::env_grid(a.num_envs);
+    if (prog < 0) prog = select_program(a);
+    if (tick) {
+        const dim3 tg(grid + (unsigned)tick->upkeep), tb(gf::kWsBlock);
+#define GF_RUN_TICK(P, interp) \
+        gf::klaunch(gf::post_ws_kernel_tick<P>, tg, tb, with_fold((interp ? sizeof(gf::GfPostArgs) : 0) + lds_ws_floats<P>(omax, a.n_gait) * sizeof(float), interp), s, a, *tick->act, *tick->scene, tick->upkeep)
+        if (prog == 1) GF_RUN_TICK(gf::ProgGo2CommandDirection, false);
+        else if (prog == 2) GF_RUN_TICK(gf::ProgGo2Simple, false);
+        else if (a.num_dofs == 12) GF_RUN_TICK(GF_TICK_INTERP(3), true);
+        else GF_RUN_TICK(GF_TICK_INTERP(7), true);
+#undef GF_RUN_TICK
+        return gf::launch_status();
+    }
     gf::PhaseScope scope(GF_PHASE_POST, s);
-    if (const int prog = select_program(a); prog >= kDynBase) {
+    if (prog >= kDynBase) {
         // a program compiled at run time: the plugin's kernel handle, launched like any other (launch sink, dispatch events)
         const DynProgram& d = g_dyn[prog - kDynBase];
         const size_t lds_dyn = with_fold(d.lds_bytes(omax, a.n_gait), false);
@@ -766,6 +795,55 @@ int gf::post_launch(const gf::GfPostArgs& packed, hipStream_t s) {
     }
     return gf::launch_status();
 }
+
+// gf_run_ops, the ops of a recorded step on the stand-in scene in a row — action, scene, post-physics: ONE launch, the post-physics kernel
+// with the tile's tick as its prologue.  Returns the number of ops that are done:
+//   0: nothing enqueued or reported — the caller goes on as if this peephole did not exist (an op is invalid, the pair does not fold, a
+//      switch is off: the action / scene pair and the post-physics op run, fold and fail as they always did);
+//   2: the pair is done in its own launch, as action_scene_try does it (*rc its status); the post-physics op is the caller's — a scene
+//      with per-link rows or contact slots, or a post-physics op that does not pack (it then fails, or runs unfused, with its own index);
+//   3: all three are done (*rc the status of the last launch): in one launch, or — the packed step is out of the fold's scope, the
+//      selected program has no tick variant — in the two launches of the unfolded step, without validating and packing twice.
+// What is on the stream after an error and the index it is reported with are the same in every case.
+// GF_FOLD_STEP=0 switches the peephole off (A/B runs, tests/test_step_fold.py); read per call.
+static std::atomic<long> g_step_folds{0};
+int gf::step_fold_try(const GfActionArgs* act, const GfSynthSceneArgs* sc, const GfPostRefs* refs, hipStream_t s, int* rc) {
+    const char* sw = getenv("GF_FOLD_STEP");
+    if (sw && strcmp(sw, "0") == 0) return 0;
+    if (gf::g_prof.phase == GF_PHASE_POST) return 0;   // a profiled phase keeps its own launch (… ACTION, SCENE: action_scene_check)
+    gf::ActionScenePlan plan;
+    int vrc = GF_OK;
+    if (gf::action_scene_check(act, sc, &vrc, &plan) != 3) return 0;
+    gf::Packer pk;
+    if (plan.links || plan.contacts || gf::pack(refs, pk) != GF_OK) {
+        *rc = gf::action_scene_launch(act, sc, plan, s);
+        return 2;
+    }
+    const gf::GfPostArgs& a = pk.a;
+    // what the post-physics phase reads of the arrays the tick writes, it reads of ITS tile: the same arrays, row for row
+    auto same = [](const void* p, const void* q) { return !p || p == q; };
+    const bool in_scope = a.num_envs == sc->num_envs && a.num_dofs == sc->num_dofs &&
+                          // block 0 of a launch that reads the gait manager's per-block bytes is its tile 0 (gf_terms.h), and a launch with
+                          // a gait manager writes one byte per block: not with upkeep workgroups in front
+                          a.n_gait == 0 && !a.gait_wave_flags &&
+                          same(a.pos, sc->pos) && same(a.quat, sc->quat) && same(a.lin_vel, sc->lin_vel) && same(a.ang_vel, sc->ang_vel) &&
+                          same(a.dof_pos, sc->dof_pos) && same(a.dof_vel, sc->dof_vel) && same(a.targets, sc->targets) &&
+                          same(a.env_actions, act->env_actions) && same(a.env_last_actions, act->env_last_actions) &&
+                          same(a.episode_length, act->episode_length);
+    const int prog = select_program(a);
+    if (in_scope && tick_variant(prog, a.num_dofs)) {
+        const gf::TickLaunch tick{act, sc, plan.upkeep};
+        *rc = gf::post_launch(a, s, prog, &tick);
+        g_step_folds.fetch_add(1, std::memory_order_relaxed);
+        return 3;
+    }
+    if ((*rc = gf::action_scene_launch(act, sc, plan, s)) != GF_OK) return 2;
+    *rc = gf::post_launch(a, s, prog);
+    return 3;
+}
+
+// steps gf_run_ops ran as one launch since the library was loaded (tests: the fold took place)
+extern "C" __attribute__((visibility("default"))) long gf_step_fold_count(void) { return g_step_folds.load(std::memory_order_relaxed); }
 
 extern "C" __attribute__((visibility("default"))) int gf_post_physics_step(const GfPostRefs* r, void* stream) {
     return gf::post_step(r, nullptr, 0, (hipStream_t)stream);

@@ -8,12 +8,13 @@
 
 // Diagnostic build only (tools/stamp_post.hip, -DGF_STAMPS): lane 0 of every wave of one workgroup records the 100 MHz
 // wall clock at the phase boundaries into a buffer of its own, stamps[16*wave + i]; no product build contains a stamp.
+// (ws_block: the workgroup's tile id in post_ws_body — blockIdx.x less the upkeep workgroups of a tick program.)
 #ifdef GF_STAMPS
 extern "C" unsigned long long* gf_debug_stamps;  // host variable set by the tool
 #define GF_WSTAMP(i)                                                                                         \
     do {                                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
-        if (a.stamps && blockIdx.x == a.stamp_block && (threadIdx.x & 63) == 0)                              \
+        if (a.stamps && ws_block == a.stamp_block && (threadIdx.x & 63) == 0)                              \
             a.stamps[16 * wave + i] = __builtin_amdgcn_s_memrealtime();                                      \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
     } while (0)

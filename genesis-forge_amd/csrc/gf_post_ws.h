@@ -37,6 +37,7 @@
 
 #include "gf_obs_hist.h"
 #include "gf_post_args.h"
+#include "gf_scene_tile.h"
 
 namespace gf {
 
@@ -65,6 +66,19 @@ struct Interp {
     // compile-time constant like in the static programs (a run-time test per row load cost the 12-DOF interpreter 8 % at 1 M envs)
     static constexpr bool kTail = TAIL_;
 };
+
+// WithTick<P>: program P with the stand-in scene's tick — the action phase folded into it — of the workgroup's tile as a prologue
+// (post_ws_kernel_tick: a recorded step on the stand-in scene as ONE launch).  Everything the post-physics phase reads that the tick
+// writes belongs to the tile, and producer and consumer are the same workgroup on one CU, so a workgroup barrier is all that stands
+// between the two phases.
+template <class P>
+struct WithTick : P {
+    static constexpr bool kTick = true;
+};
+template <class P, class = void>
+struct prog_tick : std::false_type {};
+template <class P>
+struct prog_tick<P, std::void_t<decltype(P::kTick)>> : std::bool_constant<P::kTick> {};
 
 template <class F, int... I>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
@@ -188,9 +202,22 @@ __host__ __device__ constexpr bool ws_prog_folds() {
 #endif
 constexpr int kWsTilesLdsFloats = GF_WS_AHEAD > 0 ? 4 * kEnvBlock : 0;   // (experiment: one scratch row per wave, the target of the look-ahead requests)
 
+// The kernel's body.  tick_act / tick_scene / tick_upkeep are read by a WithTick program only (the descriptors of the step's action and
+// scene ops and the number of leading statistics-upkeep workgroups, as in action_scene_tile_kernel); every other program passes nothing.
 template <class P>
-__global__ __launch_bounds__(kWsBlock) void post_ws_kernel(const GfPostArgs karg) {
+__device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfActionArgs* const tick_act, const GfSynthSceneArgs* const tick_scene,
+                                             const int tick_upkeep) {
     constexpr int DV = P::DV;
+    constexpr bool kTick = prog_tick<P>::value;
+    // tile b is workgroup b + upkeep behind the upkeep workgroups of a tick program (a multiple of 8: the tile keeps its XCD)
+    unsigned ws_block = blockIdx.x;
+    if constexpr (kTick) {
+        if ((int)blockIdx.x < tick_upkeep) {
+            action_upkeep(*tick_act, tick_upkeep, kWsBlock);
+            return;
+        }
+        ws_block = blockIdx.x - (unsigned)tick_upkeep;
+    }
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int kArgVec = P::kStatic ? 0 : (int)(sizeof(GfPostArgs) / 16);
     if constexpr (!P::kStatic) {
@@ -218,7 +245,7 @@ __global__ __launch_bounds__(kWsBlock) void post_ws_kernel(const GfPostArgs karg
     GF_WSTAMP(1);
     const int lane = threadIdx.x & (GF_WAVE - 1);
     const int64_t N = UNI(a.num_envs);
-    const int64_t tile_id = blockIdx.x;
+    const int64_t tile_id = ws_block;
     const int64_t n0 = tile_id * kEnvBlock;
     const int64_t n_raw = n0 + lane;
     const bool live = n_raw < N;
@@ -249,6 +276,24 @@ __global__ __launch_bounds__(kWsBlock) void post_ws_kernel(const GfPostArgs karg
     float* const k_reward = UNI(a.reward);
     const bool has_reward = n_rew >= 0 && k_reward != nullptr;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    // ---- tick prologue: the action phase and the stand-in scene's tick of this tile (gf_scene_tile.h), in front of everything that
+    // reads what they write — pos, quat, lin_vel, ang_vel, dof_pos, dof_vel, targets, env_actions, env_last_actions, episode_length.
+    // The tick's stores go to memory as ever; the workgroup barrier behind it (release + acquire at workgroup scope) makes them
+    // visible to the tile's waves, which are on the same CU and read them back through the same L1 — as the contact phase below
+    // does.  EVERY load of those arrays is issued behind this barrier.  The tick's LDS (three transposed [64·3] blocks of wave 0) is
+    // carved from the exchange rows, which are free until the roles publish.
+    if constexpr (kTick) {
+        static_assert(GF_WS_AHEAD == 0, "the look-ahead experiment would pull rows of a tile whose tick has not run into this CU's L1");
+        static_assert(kSynthTileBlock == kWsBlock && 3 * 3 * kEnvBlock <= X_FIELDS * kEnvBlock, "the tick's workgroup and LDS fit the kernel's");
+        const GfSynthSceneArgs& sc = *tick_scene;
+        const int rows = (int)((int64_t)sc.num_envs - n0 < kEnvBlock ? (int64_t)sc.num_envs - n0 : kEnvBlock);
+        float (&s3)[3][kEnvBlock * 3] = *reinterpret_cast<float (*)[3][kEnvBlock * 3]>(xch);
+        SynthBase ticked;
+        synth_tick_tile<DV, kEnvBlock, true>(sc, *tick_act, n0, rows, s3, ticked);
+        GF_WSTAMP(12);
+        __syncthreads();
+        GF_WSTAMP(13);
+    }
 #if GF_WS_AHEAD > 0
     {   // EXPERIMENT (tools/ab_build.sh -DGF_WS_AHEAD=K): the rows of the tile K workgroups ahead — same XCD when K % 8 == 0 —
         // are pulled towards the caches while this tile works: one LDS-DMA dword per lane and array (every line of that tile's block is
@@ -299,7 +344,7 @@ __global__ __launch_bounds__(kWsBlock) void post_ws_kernel(const GfPostArgs karg
     // one lane per (env, tracked link), the tile's slot ids staged in LDS — the region the later phases use is free until then.  The
     // managers' public buffers are written to memory as before (they are API); the workgroup barrier behind the phase makes them
     // visible to this workgroup's waves (one CU, one L1), which read them back as L2 hits instead of as a dependent launch's loads.
-    if constexpr (ws_prog_folds<P>()) {
+    if constexpr (ws_prog_folds<P>() && !kTick) {   // (a tick program never carries the contact phase: gf_post.hip folds no step that has one)
         int fold_mgr = 0;
         if constexpr (P::kStatic) fold_mgr = karg.cfold.num_mgr;
         else fold_mgr = UNI(a.cfold.num_mgr);
@@ -1240,6 +1285,22 @@ __global__ __launch_bounds__(kWsBlock) void post_ws_kernel(const GfPostArgs karg
         }
     }
     GF_WSTAMP(8);
+}
+
+template <class P>
+__global__ __launch_bounds__(kWsBlock) void post_ws_kernel(const GfPostArgs karg) {
+    post_ws_body<P>(karg, nullptr, nullptr, 0);
+}
+
+// A recorded step on the stand-in scene in ONE launch (gf_run_ops: action op, scene op, post-physics op in a row): program
+// WithTick<P>.  A kernel of its own because a kernel's parameter list cannot depend on the program without changing the signature of
+// every instantiation (the plugins' included); the descriptor stays the FIRST parameter, where the interpreter's copy to LDS and the
+// contact tables expect it.  The tick's descriptors travel as parameters too: the whole explicit argument block stays within the 4 KiB
+// a launch may carry.
+static_assert(sizeof(GfPostArgs) + sizeof(GfActionArgs) + sizeof(GfSynthSceneArgs) + 8 <= 4096, "kernel arguments of post_ws_kernel_tick");
+template <class P>
+__global__ __launch_bounds__(kWsBlock) void post_ws_kernel_tick(const GfPostArgs karg, const GfActionArgs act, const GfSynthSceneArgs scene, const int upkeep) {
+    post_ws_body<WithTick<P>>(karg, &act, &scene, upkeep);
 }
 
 }  // namespace gf

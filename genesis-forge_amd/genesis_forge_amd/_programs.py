@@ -42,7 +42,7 @@ PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(PKG_DIR, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 _HEADERS = ("gf_post_args.h", "gf_post_ws.h", "gf_post_programs.h", "gf_terms.h", "gf_device.h", "gf_obs_hist.h", "gf_prefetch.h",
-            "gf_launch.h", "gf_contact_tile.h")
+            "gf_launch.h", "gf_contact_tile.h", "gf_scene_tile.h", "gf_action_row.h")
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-fvisibility=hidden", "-Wno-unused-value"]
 
 

@@ -1230,7 +1230,15 @@ typedef struct GfStatsCopyArgs {
     void* event;              /* from gf_event_create(); recorded after the copy; may be NULL */
 } GfStatsCopyArgs;
 
+/* Runs the ops in order; stops at the first op that fails and reports its index.  Neighbouring ops share launches where that gives
+ * the same results: an action op directly in front of a stand-in scene op runs inside the tick's launch (GF_FOLD_ACTION=0: not), and
+ * with a GF_OP_POST_PHYSICS op directly behind that pair — a recorded step on the stand-in scene without per-link rows or contact
+ * slots — the three ops are ONE launch, the tick as the post-physics kernel's prologue (GF_FOLD_STEP=0: not; both switches are
+ * read per call); contact ops in front of a post-physics op are its first phase (GF_OPT_FOLD_CONTACT); runs of per-env phases chain
+ * (GF_OPT_CHAIN).  A profiled phase keeps its own launch.  Return codes and failed_index do not depend on any of this. */
 int gf_run_ops(const GfOp* ops, int num_ops, void* stream, int* failed_index);
+/* steps gf_run_ops ran as one launch since the library was loaded */
+long gf_step_fold_count(void);
 
 /* Recorded step, patched natively: the few descriptor fields that change from one step to the next are described ONCE as a
  * patch table (which host address receives what), and a step is a single call — apply the table, then gf_run_ops — instead of

@@ -80,6 +80,7 @@ def run(config, steps):
     for w in (0, 1, 2):
         print(f"  wave {w}: " + " ".join(f"{float(acc[w, k]):17.2f}" for k in range(9, 12 if w < 2 else 10)))
     print("  folded contact phase (0 when the launch has none): slot ids + masks in LDS | prefix done | contributions in LDS | links done")
+    print("  (a step folded into one launch, post_ws_kernel_tick, has no contact phase: tick of the tile done | past the tick's barrier | 0 | 0)")
     for w in range(4):
         print(f"  wave {w}: " + " ".join(f"{float(acc[w, k]):17.2f}" for k in range(12, 16)))
 

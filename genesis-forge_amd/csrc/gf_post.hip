@@ -611,6 +611,20 @@ extern "C" __attribute__((visibility("default"))) int gf_post_physics_check(cons
     return gf::pack(r, pk);
 }
 
+static_assert(gf::PN_POS == GF_POST_NEEDS_POS && gf::PN_QUAT == GF_POST_NEEDS_QUAT && gf::PN_LIN == GF_POST_NEEDS_LIN && gf::PN_ANG == GF_POST_NEEDS_ANG &&
+              gf::PN_DOFPOS == GF_POST_NEEDS_DOFPOS && gf::PN_DOFVEL == GF_POST_NEEDS_DOFVEL && gf::PN_TARGETS == GF_POST_NEEDS_TARGETS &&
+              gf::PN_ACTIONS == GF_POST_NEEDS_ACTIONS && gf::PN_LAST == GF_POST_NEEDS_LAST && gf::PN_EPLEN == GF_POST_NEEDS_EPLEN &&
+              gf::PN_MAXLEN == GF_POST_NEEDS_MAXLEN && gf::PN_DOFDEV == GF_POST_NEEDS_DOFDEV && gf::PN_ACTRATE == GF_POST_NEEDS_ACTRATE &&
+              gf::PN_DOFFORCE == GF_POST_NEEDS_DOFFORCE, "gf_step.h names the kernel's bits");
+extern "C" __attribute__((visibility("default"))) int gf_post_physics_needs(const GfPostRefs* r, uint32_t* needs_out) {
+    if (!needs_out) return GF_E_NULL;
+    gf::Packer pk;
+    const int rc = gf::pack(r, pk);
+    if (rc) return rc;
+    *needs_out = pk.a.needs;
+    return GF_OK;
+}
+
 using gf::lds_ws_floats;
 
 // ---- programs compiled at run time (include/gf_step.h: gf_post_program_register) ---------------------------------------------
@@ -744,7 +758,7 @@ int gf::post_launch(const gf::GfPostArgs& packed, hipStream_t s, int prog, const
     if (tick) {
         const dim3 tg(grid + (unsigned)tick->upkeep), tb(gf::kWsBlock);
 #define GF_RUN_TICK(P, interp) \
-        gf::klaunch(gf::post_ws_kernel_tick<P>, tg, tb, with_fold((interp ? sizeof(gf::GfPostArgs) : 0) + lds_ws_floats<P>(omax, a.n_gait) * sizeof(float), interp), s, a, *tick->act, *tick->scene, tick->upkeep)
+        gf::klaunch(gf::post_ws_kernel_tick<P>, tg, tb, with_fold((interp ? sizeof(gf::GfPostArgs) : 0) + lds_ws_floats<gf::WithTick<P>>(omax, a.n_gait) * sizeof(float), interp), s, a, *tick->act, *tick->scene, tick->upkeep)
         if (prog == 1) GF_RUN_TICK(gf::ProgGo2CommandDirection, false);
         else if (prog == 2) GF_RUN_TICK(gf::ProgGo2Simple, false);
         else if (a.num_dofs == 12) GF_RUN_TICK(GF_TICK_INTERP(3), true);

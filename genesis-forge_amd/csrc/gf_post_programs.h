@@ -253,10 +253,14 @@ struct ProgHumanoid28Stress {
     static constexpr int n_gait = 0;
 };
 
-// dynamic LDS of post_ws_kernel<P>, in floats (a static program keeps no copy of the descriptor in LDS; the interpreter adds one)
+// dynamic LDS of post_ws_kernel<P>, in floats (a static program keeps no copy of the descriptor in LDS; the interpreter adds one).
+// P = WithTick<…> of a program that hands its tick's tile over: the handed rows start at the scratch rows and need not fit the tile.
 template <class P>
 inline size_t lds_ws_floats(int omax, int n_gait) {
-    return (size_t)(x_fields(n_gait) + ws_sum_rows<P>() + ws_aux_rows<P>() + ws_pre_rows<P>() + ws_obs_norm_rows<P>()) * kEnvBlock + (size_t)(omax + 1) * kEnvBlock;
+    const size_t front = (size_t)(x_fields(n_gait) + ws_sum_rows<P>()) * kEnvBlock;
+    const size_t back = (size_t)(ws_aux_rows<P>() + ws_pre_rows<P>() + ws_obs_norm_rows<P>()) * kEnvBlock + (size_t)(omax + 1) * kEnvBlock;
+    if constexpr (ws_hands_over<P>()) return front + (back > (size_t)ws_hand_floats<P>() ? back : (size_t)ws_hand_floats<P>());
+    else return front + back;
 }
 
 template <class P>

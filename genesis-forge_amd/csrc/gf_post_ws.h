@@ -80,6 +80,28 @@ struct prog_tick : std::false_type {};
 template <class P>
 struct prog_tick<P, std::void_t<decltype(P::kTick)>> : std::bool_constant<P::kTick> {};
 
+// The tile a tick program's tick leaves, handed to the post-physics phase of the same workgroup through LDS (ws_hands_over<P>(), below):
+// the five joint streams as the DOF lanes store them — float4 i of stream s at rows[s·TE·DV + i], that is [stream][env][D] rows —
+// and wave 0's base rows, written besides the stores to memory.  (The sink of synth_tick_tile, gf_scene_tile.h.)
+enum : int { H_DOFPOS = 0, H_DOFVEL = 1, H_TARGETS = 2, H_ACTIONS = 3, H_LAST = 4, H_STREAMS = 5 };
+enum : int { HB_POS = 0, HB_QUAT = 3, HB_LIN = 7, HB_ANG = 10, HB_EPLEN = 13, HB_FIELDS = 14 };   // the base rows [field][env] behind the streams
+template <int DV, int TE>
+struct TickHand {
+    float4* rows;   // [H_STREAMS][TE · DV]
+    float* base_rows;   // [HB_FIELDS][TE]: the env's new position, quaternion, velocities and (as bits) episode_length
+    __device__ __forceinline__ void dof(const int i, const float4& last, const float4& actions, const float4& tg, const float4& v, const float4& p) const {
+        rows[H_DOFPOS * TE * DV + i] = p; rows[H_DOFVEL * TE * DV + i] = v; rows[H_TARGETS * TE * DV + i] = tg;
+        rows[H_ACTIONS * TE * DV + i] = actions; rows[H_LAST * TE * DV + i] = last;
+    }
+    __device__ __forceinline__ void base(const int e, const SynthBase& b) const {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { base_rows[(HB_POS + j) * TE + e] = b.p[j]; base_rows[(HB_LIN + j) * TE + e] = b.v[j]; base_rows[(HB_ANG + j) * TE + e] = b.w[j]; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) base_rows[(HB_QUAT + j) * TE + e] = b.q[j];
+    }
+    __device__ __forceinline__ void episode(const int e, const int32_t len) const { base_rows[HB_EPLEN * TE + e] = __builtin_bit_cast(float, len); }
+};
+
 template <class F, int... I>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
     (f(std::integral_constant<int, I>{}), ...);
@@ -197,6 +219,20 @@ __host__ __device__ constexpr bool ws_prog_folds() {
     }
 }
 
+// Does program P take what its tick wrote from the tick itself, through LDS — the joint rows, the base state, the step counter —
+// instead of reading it back from memory behind the tick's barrier?  The static tick programs and the 12-DOF table interpreter do.
+// The handed rows live in the LDS no role writes before the role barrier: the DOF-reset scratch rows and the observation tile behind
+// them (one run when the program parks no reward / norm rows between the two), grown to the rows' size.  The 28-DOF interpreter keeps
+// the read-back: its rows alone are 35 KB.
+template <class P>
+__host__ __device__ constexpr bool ws_hands_over() {
+    if constexpr (!prog_tick<P>::value) return false;
+    else if constexpr (P::kStatic) return ws_pre_rows<P>() == 0 && ws_obs_norm_rows<P>() == 0;
+    else return P::DV == 3 && !P::kTail;
+}
+template <class P>
+__host__ __device__ constexpr int ws_hand_floats() { return H_STREAMS * kEnvBlock * 4 * P::DV + HB_FIELDS * kEnvBlock + 4 * P::DV; }   // streams, base rows, zero row
+
 #ifndef GF_WS_AHEAD
 #define GF_WS_AHEAD 0
 #endif
@@ -280,16 +316,36 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
     // reads what they write — pos, quat, lin_vel, ang_vel, dof_pos, dof_vel, targets, env_actions, env_last_actions, episode_length.
     // The tick's stores go to memory as ever; the workgroup barrier behind it (release + acquire at workgroup scope) makes them
     // visible to the tile's waves, which are on the same CU and read them back through the same L1 — as the contact phase below
-    // does.  EVERY load of those arrays is issued behind this barrier.  The tick's LDS (three transposed [64·3] blocks of wave 0) is
+    // does.  A program that reads them back issues EVERY load of those arrays behind this barrier.  The tick's LDS (three transposed [64·3] blocks of wave 0) is
     // carved from the exchange rows, which are free until the roles publish.
+    //
+    // A program that hands over (ws_hands_over) reads NONE of them back: the DOF lanes leave their five float4 streams in LDS besides
+    // storing them, and wave 0 leaves the new base state and step counter of its lane's env as LDS rows [field][env], for the control
+    // wave (itself) and the reward wave.  The handed region starts at the DOF-reset scratch rows and runs into the observation tile:
+    // nothing writes there before the role barrier, when every role has its rows in registers — unlike the exchange rows, the
+    // episode-sum rows and the parked rows, which roles fill while others may still be reading.  The roles take a handed value only
+    // where they would load the array today (`needs`), and a lane past the tile takes the tile's last env's, as its clamped load
+    // does: every role sees the bits it sees after a read-back.
+    constexpr bool kHand = ws_hands_over<P>();
+    float4* const hand_rows = reinterpret_cast<float4*>(lds_aux);          // [H_STREAMS][64 · DV]
+    float* const hand_base = lds_aux + H_STREAMS * kEnvBlock * 4 * DV;     // [HB_FIELDS][64]
+    float4* const hand_zero = reinterpret_cast<float4*>(hand_base + HB_FIELDS * kEnvBlock);   // [DV]: the row of an array the launch does not need
+    int hand_env = lane;   // the env of the tile whose handed rows this lane reads
     if constexpr (kTick) {
         static_assert(GF_WS_AHEAD == 0, "the look-ahead experiment would pull rows of a tile whose tick has not run into this CU's L1");
         static_assert(kSynthTileBlock == kWsBlock && 3 * 3 * kEnvBlock <= X_FIELDS * kEnvBlock, "the tick's workgroup and LDS fit the kernel's");
         const GfSynthSceneArgs& sc = *tick_scene;
         const int rows = (int)((int64_t)sc.num_envs - n0 < kEnvBlock ? (int64_t)sc.num_envs - n0 : kEnvBlock);
         float (&s3)[3][kEnvBlock * 3] = *reinterpret_cast<float (*)[3][kEnvBlock * 3]>(xch);
-        SynthBase ticked;
-        synth_tick_tile<DV, kEnvBlock, true>(sc, *tick_act, n0, rows, s3, ticked);
+        SynthBase ticked;   // (the body's out-parameter, unused here: what the roles need of it goes through the sink, inside wave 0's branch)
+        if constexpr (kHand) {
+            static_assert(kPreRows == 0 && kNormRows == 0, "the handed rows run from the scratch rows into the observation tile");
+            synth_tick_tile<DV, kEnvBlock, true>(sc, *tick_act, n0, rows, s3, ticked, TickHand<DV, kEnvBlock>{hand_rows, hand_base});
+            hand_env = lane < rows ? lane : rows - 1;
+            if (threadIdx.x < DV) hand_zero[threadIdx.x] = z4;
+        } else {
+            synth_tick_tile<DV, kEnvBlock, true>(sc, *tick_act, n0, rows, s3, ticked);
+        }
         GF_WSTAMP(12);
         __syncthreads();
         GF_WSTAMP(13);
@@ -495,15 +551,40 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
     // values (scalar registers) — the fold behind the barrier then starts with them in hand instead of a scalar load per term
     float fold_w[kSumRows > 0 ? kSumRows : 1];
     int32_t fold_row[kSumRows > 0 ? kSumRows : 1];
+    // a handed row / base vector of this lane's env (kHand).  A row the launch does not need is read from the zero row, as its load went
+    // to the zero pad: the select is on the address, like gsel's (a branch around the reads or a select on the values costs the
+    // static programs 3 … 16 VGPRs and with them the sixth wave per SIMD)
+    auto hand_row = [&](float4 (&r)[R], const bool on, const int stream) GF_INLINE_LAMBDA {
+        const float4* const src = on ? hand_rows + stream * kEnvBlock * DV + hand_env * DV : hand_zero;
+#pragma unroll
+        for (int c = 0; c < DV; ++c) r[c] = src[c];
+    };
+    auto hand_v3 = [&](const bool on, const int field) GF_INLINE_LAMBDA {
+        const float* const h = hand_base + field * kEnvBlock + hand_env;
+        return on ? V3{h[0], h[kEnvBlock], h[2 * kEnvBlock]} : V3{0.f, 0.f, 0.f};
+    };
+    auto hand_quat = [&](const bool on) GF_INLINE_LAMBDA {
+        const float* const h = hand_base + HB_QUAT * kEnvBlock + hand_env;
+        return on ? make_float4(h[0], h[kEnvBlock], h[2 * kEnvBlock], h[3 * kEnvBlock]) : z4;
+    };
     if (wave == 0) {
         // ---- control: loads -------------------------------------------------------------------------------------------
-        q = ldg4(gsel((needs & PN_QUAT) != 0, UNI(a.quat), 4u * e));
-        const GF_GLOBAL float* pp = gsel((needs & PN_POS) != 0, UNI(a.pos), 3u * e);
-        const GF_GLOBAL float* lp = gsel((needs & PN_LIN) != 0, UNI(a.lin_vel), 3u * e);
-        const GF_GLOBAL float* ap = gsel((needs & PN_ANG) != 0, UNI(a.ang_vel), 3u * e);
-        const V3 pos{pp[0], pp[1], pp[2]};
-        const V3 lin{lp[0], lp[1], lp[2]}, ang{ap[0], ap[1], ap[2]};
-        ep_len = *gsel((needs & PN_EPLEN) != 0, UNI(a.episode_length), e);
+        V3 pos, lin, ang;
+        if constexpr (kHand) {   // the tick's results for this lane's env; an array the launch does not need reads as the zero pad does
+            q = hand_quat((needs & PN_QUAT) != 0);
+            pos = hand_v3((needs & PN_POS) != 0, HB_POS);
+            lin = hand_v3((needs & PN_LIN) != 0, HB_LIN);
+            ang = hand_v3((needs & PN_ANG) != 0, HB_ANG);
+            ep_len = (needs & PN_EPLEN) != 0 ? __builtin_bit_cast(int, hand_base[HB_EPLEN * kEnvBlock + hand_env]) : 0;
+        } else {
+            q = ldg4(gsel((needs & PN_QUAT) != 0, UNI(a.quat), 4u * e));
+            const GF_GLOBAL float* pp = gsel((needs & PN_POS) != 0, UNI(a.pos), 3u * e);
+            const GF_GLOBAL float* lp = gsel((needs & PN_LIN) != 0, UNI(a.lin_vel), 3u * e);
+            const GF_GLOBAL float* ap = gsel((needs & PN_ANG) != 0, UNI(a.ang_vel), 3u * e);
+            pos = V3{pp[0], pp[1], pp[2]};
+            lin = V3{lp[0], lp[1], lp[2]}; ang = V3{ap[0], ap[1], ap[2]};
+            ep_len = *gsel((needs & PN_EPLEN) != 0, UNI(a.episode_length), e);
+        }
         const int max_len = *gsel((needs & PN_MAXLEN) != 0, UNI(a.max_episode_length), e);
 #pragma unroll
         for (int c = 0; c < GF_POST_MAX_CMD; ++c) {
@@ -676,19 +757,30 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
                     __builtin_amdgcn_global_load_lds(k_sums + (int64_t)uni(a.rterms[k].row) * N + n, lds_sums + k * kEnvBlock, 4, 0, 0);
             }
         }
-        const GF_GLOBAL float* p0 = gsel((needs & PN_DOFDEV) != 0, UNI(a.dof_pos), ro);
-        const GF_GLOBAL float* p1 = gsel((needs & PN_ACTRATE) != 0, UNI(a.env_actions), ro);
-        const GF_GLOBAL float* p2 = gsel((needs & PN_ACTRATE) != 0, UNI(a.env_last_actions), ro);
         const GF_GLOBAL float* p3 = gsel((needs & PN_DOFDEV) != 0, UNI(a.default_dof_pos), 0u);
         float4 r_def[R];
-        row_load<DV>(r_a, p0, D); row_load<DV>(r_b, p1, D); row_load<DV>(r_c, p2, D); row_load<DV>(r_def, p3, D);
-        const GF_GLOBAL float* pp = gsel((needs & PN_POS) != 0, UNI(a.pos), 3u * e);
-        const V3 pos{pp[0], pp[1], pp[2]};
+        V3 pos;
+        if constexpr (kHand) {
+            row_load<DV>(r_def, p3, D);
+            hand_row(r_a, (needs & PN_DOFDEV) != 0, H_DOFPOS); hand_row(r_b, (needs & PN_ACTRATE) != 0, H_ACTIONS); hand_row(r_c, (needs & PN_ACTRATE) != 0, H_LAST);
+            pos = hand_v3((needs & PN_POS) != 0, HB_POS);
+        } else {
+            const GF_GLOBAL float* p0 = gsel((needs & PN_DOFDEV) != 0, UNI(a.dof_pos), ro);
+            const GF_GLOBAL float* p1 = gsel((needs & PN_ACTRATE) != 0, UNI(a.env_actions), ro);
+            const GF_GLOBAL float* p2 = gsel((needs & PN_ACTRATE) != 0, UNI(a.env_last_actions), ro);
+            row_load<DV>(r_a, p0, D); row_load<DV>(r_b, p1, D); row_load<DV>(r_c, p2, D); row_load<DV>(r_def, p3, D);
+            const GF_GLOBAL float* pp = gsel((needs & PN_POS) != 0, UNI(a.pos), 3u * e);
+            pos = V3{pp[0], pp[1], pp[2]};
+        }
         // a static program whose terms read body-frame vectors: this wave derives them itself (see below) — the rows it needs for that
         // are requested here, with the tile's other loads
         float4 qb = make_float4(1.f, 0.f, 0.f, 0.f);
         V3 wlin{0.f, 0.f, 0.f}, wang{0.f, 0.f, 0.f};
-        if constexpr (ws_rew_body_frame<P>()) {
+        if constexpr (ws_rew_body_frame<P>() && kHand) {
+            qb = hand_quat((needs & PN_QUAT) != 0);
+            wlin = hand_v3((needs & PN_LIN) != 0, HB_LIN);
+            wang = hand_v3((needs & PN_ANG) != 0, HB_ANG);
+        } else if constexpr (ws_rew_body_frame<P>()) {
             qb = ldg4(gsel((needs & PN_QUAT) != 0, UNI(a.quat), 4u * e));
             const GF_GLOBAL float* lp = gsel((needs & PN_LIN) != 0, UNI(a.lin_vel), 3u * e);
             const GF_GLOBAL float* ap = gsel((needs & PN_ANG) != 0, UNI(a.ang_vel), 3u * e);
@@ -772,11 +864,16 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
             });
         }
     } else if (wave == 2) {
-        const GF_GLOBAL float* p0 = gsel((needs & PN_DOFPOS) != 0, UNI(a.dof_pos), ro);
-        const GF_GLOBAL float* p1 = gsel((needs & PN_DOFVEL) != 0, UNI(a.dof_vel), ro);
         const float* k_def = UNI(a.default_dof_pos);
         const GF_GLOBAL float* p2 = gsel(k_def != nullptr, k_def, 0u);
-        row_load<DV>(r_a, p0, D); row_load<DV>(r_b, p1, D); row_load<DV>(r_c, p2, D);
+        if constexpr (kHand) {
+            hand_row(r_a, (needs & PN_DOFPOS) != 0, H_DOFPOS); hand_row(r_b, (needs & PN_DOFVEL) != 0, H_DOFVEL);
+        } else {
+            const GF_GLOBAL float* p0 = gsel((needs & PN_DOFPOS) != 0, UNI(a.dof_pos), ro);
+            const GF_GLOBAL float* p1 = gsel((needs & PN_DOFVEL) != 0, UNI(a.dof_vel), ro);
+            row_load<DV>(r_a, p0, D); row_load<DV>(r_b, p1, D);
+        }
+        row_load<DV>(r_c, p2, D);
         GF_WSTAMP(9);
         if constexpr (kPreRows > 0) {   // the memory-only reward terms (see reward_op_memory_only), parked for the fold
             RewardRegs rp;   // (parked rows exist only in a program with reward terms, which matches only a launch that has the reward manager)
@@ -794,9 +891,13 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
             });
         }
     } else {
-        const GF_GLOBAL float* p0 = gsel((needs & PN_TARGETS) != 0, UNI(a.targets), ro);
-        const GF_GLOBAL float* p1 = gsel((needs & PN_ACTIONS) != 0, UNI(a.env_actions), ro);
-        row_load<DV>(r_a, p0, D); row_load<DV>(r_b, p1, D);
+        if constexpr (kHand) {
+            hand_row(r_a, (needs & PN_TARGETS) != 0, H_TARGETS); hand_row(r_b, (needs & PN_ACTIONS) != 0, H_ACTIONS);
+        } else {
+            const GF_GLOBAL float* p0 = gsel((needs & PN_TARGETS) != 0, UNI(a.targets), ro);
+            const GF_GLOBAL float* p1 = gsel((needs & PN_ACTIONS) != 0, UNI(a.env_actions), ro);
+            row_load<DV>(r_a, p0, D); row_load<DV>(r_b, p1, D);
+        }
         if constexpr (P::kStatic && ws_obs_has<P>(GF_O_DOF_FORCE)) {   // the dof_force row: this wave's third row set is free
             row_load<DV>(r_c, gsel(UNI(a.dof_force) != nullptr, UNI(a.dof_force), ro), D);
         }

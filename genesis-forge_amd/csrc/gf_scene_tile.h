@@ -77,12 +77,24 @@ constexpr int kSynthDofLanes = kSynthTileBlock - GF_WAVE;
 // no LDS access across this point
 __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_wave_barrier(); }
 
+// What a tick hands to code that follows it in the same kernel, BESIDES its stores: `dof` is called by the lane that stores float4 i of
+// the tile's five joint streams (FOLD only), `base` by lane e of wave 0 with the new base state of env e of the tile, `episode` by the
+// same lane with that env's new step counter (FOLD only).  The default takes nothing and compiles to nothing; gf_post_ws.h hands
+// the tile to its post-physics phase through LDS.  (The sink is called where the values are stored, inside the wave's branch: a
+// result handed back to the caller instead would stay live in wave 0's registers while the other branch of the workgroup runs.)
+struct SynthNoSink {
+    __device__ __forceinline__ void dof(int, const float4&, const float4&, const float4&, const float4&, const float4&) const {}
+    __device__ __forceinline__ void base(int, const SynthBase&) const {}
+    __device__ __forceinline__ void episode(int, int32_t) const {}
+};
+
 // FOLD: the action phase of the step runs here too (gf_action_row.h).  The lanes that stream the tile's joint rows are the lanes
 // that own the same float4s of the flat action stream, so the targets never leave the registers between the two phases: every
 // load of the lane (raw actions, previous actions, joint positions) is issued before the first use, the row code runs, the
 // bookkeeping rows and the targets are stored as the action kernel stores them, and the joints take the targets from the registers.
-template <int DV, int TE, bool FOLD = false>
-__device__ __forceinline__ void synth_dof_tile(const GfSynthSceneArgs& a, const GfActionArgs& act, const int64_t n0, const int rows, const int t) {
+template <int DV, int TE, bool FOLD = false, class Sink = SynthNoSink>
+__device__ __forceinline__ void synth_dof_tile(const GfSynthSceneArgs& a, const GfActionArgs& act, const int64_t n0, const int rows, const int t,
+                                               const Sink& sink = Sink{}) {
     const float dt = a.dt, rate = a.joint_rate;
     if constexpr (FOLD) {
         static_assert(DV > 0, "the fold moves float4s");
@@ -131,6 +143,7 @@ __device__ __forceinline__ void synth_dof_tile(const GfSynthSceneArgs& a, const 
                 t4[i] = tg;
                 v4[i] = v;
                 p4[i] = p;
+                sink.dof(i, last, actions, tg, v, p);
             }
         }
         action_flags_commit(act, flags);   // whole waves get here
@@ -173,9 +186,9 @@ __device__ __forceinline__ void synth_dof_tile(const GfSynthSceneArgs& a, const 
 
 // wave 0: lane = env of the tile; s3 is this wave's LDS, 3 × [TE·3] floats.  Returns the lane's new base state (lane < rows).
 // FOLD: episode_length[n] += 1 of the action phase (genesis_env.py:197) for the lane's env, its load issued with the others.
-template <int TE, bool FOLD = false>
+template <int TE, bool FOLD = false, class Sink = SynthNoSink>
 __device__ __forceinline__ void synth_base_tile(const GfSynthSceneArgs& a, const GfActionArgs& act, const int64_t n0, const int rows, const int lane,
-                                                float (&s3)[3][TE * 3], SynthBase& out) {
+                                                float (&s3)[3][TE * 3], SynthBase& out, const Sink& sink = Sink{}) {
     constexpr int kJ = (TE * 3 + GF_WAVE - 1) / GF_WAVE;
     const int cnt = rows * 3;
     float* const pos = a.pos + n0 * 3;
@@ -223,20 +236,24 @@ __device__ __forceinline__ void synth_base_tile(const GfSynthSceneArgs& a, const
         const float yp = s3[0][i < TE * 3 ? i : 0], yv = s3[1][i < TE * 3 ? i : 0], yw = s3[2][i < TE * 3 ? i : 0];
         if (i < cnt) { pos[i] = yp; lin[i] = yv; ang[i] = yw; }
     }
-    if (mine) reinterpret_cast<float4*>(a.quat)[n0 + lane] = make_float4(out.q[0], out.q[1], out.q[2], out.q[3]);
+    if (mine) {
+        reinterpret_cast<float4*>(a.quat)[n0 + lane] = make_float4(out.q[0], out.q[1], out.q[2], out.q[3]);
+        sink.base(lane, out);
+    }
     if constexpr (FOLD) {
         if (mine && act.episode_length) act.episode_length[n0 + lane] = ep + 1;
+        if (mine) sink.episode(lane, ep + 1);
     }
 }
 
 // The tick of tile [n0, n0 + rows) by a whole workgroup (see above): wave 0 returns the base state of env n0 + lane in `b`.
-// (`act` is read only with FOLD)
-template <int DV, int TE, bool FOLD = false>
+// (`act` is read only with FOLD; `sink`: see SynthNoSink)
+template <int DV, int TE, bool FOLD = false, class Sink = SynthNoSink>
 __device__ __forceinline__ void synth_tick_tile(const GfSynthSceneArgs& a, const GfActionArgs& act, const int64_t n0, const int rows,
-                                                float (&s3)[3][TE * 3], SynthBase& b) {
+                                                float (&s3)[3][TE * 3], SynthBase& b, const Sink& sink = Sink{}) {
     const int tid = threadIdx.x;
-    if (tid >= GF_WAVE) synth_dof_tile<DV, TE, FOLD>(a, act, n0, rows, tid - GF_WAVE);
-    else synth_base_tile<TE, FOLD>(a, act, n0, rows, tid, s3, b);
+    if (tid >= GF_WAVE) synth_dof_tile<DV, TE, FOLD>(a, act, n0, rows, tid - GF_WAVE, sink);
+    else synth_base_tile<TE, FOLD>(a, act, n0, rows, tid, s3, b, sink);
 }
 
 }  // namespace gf

@@ -627,6 +627,8 @@ class HipBackend(Backend):
         self.lib.gf_post_physics_step_contacts.argtypes = [C.POINTER(GfPostRefs), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
         self.lib.gf_post_physics_describe.restype = C.c_int
         self.lib.gf_post_physics_describe.argtypes = [C.POINTER(GfPostRefs), C.c_char_p, C.c_int]
+        self.lib.gf_post_physics_needs.restype = C.c_int
+        self.lib.gf_post_physics_needs.argtypes = [C.POINTER(GfPostRefs), C.POINTER(C.c_uint32)]
         self.lib.gf_post_program_register.restype = C.c_int
         self.lib.gf_post_program_register.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
         self.lib.gf_event_create.restype = C.c_void_p
@@ -755,6 +757,14 @@ class HipBackend(Backend):
         if rc != 0:
             self._raise("post_physics_describe", rc)
         return buf.value.decode()
+
+    def post_needs(self, refs) -> int:
+        """The GF_POST_NEEDS_* word of this combination's fused launch: which state arrays it reads.  Host-only."""
+        word = C.c_uint32(0)
+        rc = self.lib.gf_post_physics_needs(C.byref(refs), C.byref(word))
+        if rc != 0:
+            self._raise("post_physics_needs", rc)
+        return int(word.value)
 
     def register_program(self, plugin_path: str) -> int:
         """Register a static program compiled at run time (genesis_forge_amd/_programs.py); returns its program id."""

@@ -1180,6 +1180,13 @@ int gf_post_physics_step_contacts(const GfPostRefs* r, const GfContactArgs* cons
  * gf_post_physics_step would launch (id 0 = table interpreter, >0 = a static program compiled for exactly this
  * structure) and the signature in the notation of csrc/gf_post_programs.h.  Host-only, no GPU needed. */
 int gf_post_physics_describe(const GfPostRefs* r, char* buf, int cap);
+/* Which state arrays the fused launch of this combination reads, as packed: a word of GF_POST_NEEDS_* bits.  An array whose bit is
+ * off is never read — a role that would take its rows sees zeros.  Host-only, no GPU needed. */
+enum { GF_POST_NEEDS_POS = 1, GF_POST_NEEDS_QUAT = 2, GF_POST_NEEDS_LIN = 4, GF_POST_NEEDS_ANG = 8, GF_POST_NEEDS_DOFPOS = 16,
+       GF_POST_NEEDS_DOFVEL = 32, GF_POST_NEEDS_TARGETS = 64, GF_POST_NEEDS_ACTIONS = 128, GF_POST_NEEDS_LAST = 256,
+       GF_POST_NEEDS_EPLEN = 512, GF_POST_NEEDS_MAXLEN = 1024, GF_POST_NEEDS_DOFDEV = 2048 /* the reward wave's dof_pos rows */,
+       GF_POST_NEEDS_ACTRATE = 4096 /* the reward wave's action / last-action rows */, GF_POST_NEEDS_DOFFORCE = 8192 };
+int gf_post_physics_needs(const GfPostRefs* r, uint32_t* needs_out);
 /* Static programs for configs the library was not built with.  The reference's configs are live Python dicts
  * (managers/config/config_item.py:31-44; reward_manager.py:166-195 walks whatever the dict holds), so a user's task is not
  * one of the compiled-in structures; it would run the table interpreter (about 1.3 x the kernel time).  Instead the host

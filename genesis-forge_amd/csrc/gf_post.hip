@@ -8,10 +8,11 @@
 //     phases one by one (GF_POST_WHY=1 names the rule).
 //   * fold_contacts() adds the scene's ContactManagers as a phase in front of the others (GfPostArgs.cfold), or refuses and
 //     leaves the contact kernel a launch of its own.
-//   * the program registry: the static programs of gf_post_programs.h, the programs compiled at run time and registered
-//     through gf_post_program_register, and select_program(), which matches a packed descriptor against their signatures.
-//   * post_launch() sizes the LDS for the selected program and launches it: a run-time compiled program, a built-in program,
-//     or the table interpreter Interp<DV, TAIL> for the step's DOF count.
+//   * the program table: one PostProgram record per program — name, matcher, kernel handle, LDS size, whether it carries the contact
+//     phase, its tick variant — for the static programs of gf_post_programs.h (kBuiltin), the table interpreter Interp<DV, TAIL> by DOF
+//     count (kInterp) and the programs compiled at run time and registered through gf_post_program_register (g_dyn); select_program()
+//     matches a packed descriptor against them once per step.
+//   * post_launch() sizes the LDS for the selected record and launches its kernel by handle.
 // Semantics are, by construction, those of calling the phase entry points in sequence (the oracle twin does exactly that);
 // tests compare the two paths bit for bit.
 // Algorithmic traffic, Go2 command config: R 13·4 + 5 rows·48 + cmd 12 + ep/max 8 + secs 4 + sums 24 = 340,
@@ -577,33 +578,6 @@ static int fold_contacts(Packer& pk, const GfContactArgs* const* mgrs, int num) 
     return GF_OK;
 }
 
-// the action and scene ops of a step that run as the launch's tick prologue (post_ws_kernel_tick)
-struct TickLaunch {
-    const GfActionArgs* act;
-    const GfSynthSceneArgs* scene;
-    int upkeep;
-};
-// launches the post-physics kernel of program `prog` (select_program; -1: selected here); with `tick`, that program's tick variant
-// (the caller has asked tick_variant)
-static int post_launch(const GfPostArgs& a, hipStream_t s, int prog = -1, const TickLaunch* tick = nullptr);
-int action_scene_check(const GfActionArgs* act, const GfSynthSceneArgs* a, int* rc, ActionScenePlan* plan);   // gf_scene.hip
-int action_scene_launch(const GfActionArgs* act, const GfSynthSceneArgs* a, const ActionScenePlan& p, hipStream_t s);
-bool post_program_folds(const GfPostArgs& a);   // the kernel this descriptor selects carries the contact phase
-
-int step_fold_try(const GfActionArgs* act, const GfSynthSceneArgs* sc, const GfPostRefs* refs, hipStream_t s, int* rc);
-
-int post_step(const GfPostRefs* r, const GfContactArgs* const* mgrs, int num_mgr, hipStream_t s) {
-    Packer pk;
-    int rc = pack(r, pk);
-    if (rc) return rc;
-    if (num_mgr > 0) {
-        UNSUP(!post_program_folds(pk.a));
-        rc = fold_contacts(pk, mgrs, num_mgr);
-        if (rc) return rc;
-    }
-    return post_launch(pk.a, s);
-}
-
 }  // namespace gf
 
 extern "C" __attribute__((visibility("default"))) int gf_post_physics_check(const GfPostRefs* r) {
@@ -625,189 +599,158 @@ extern "C" __attribute__((visibility("default"))) int gf_post_physics_needs(cons
     return GF_OK;
 }
 
-using gf::lds_ws_floats;
+// ------------------------------------------------------------------------------------------------------------
+// The program table: everything the host knows about a program of the fused launch is one PostProgram record.
+// ------------------------------------------------------------------------------------------------------------
+namespace gf {
+
+struct PostProgram {
+    int id;                                  // 0: table interpreter, 1…: built-in, kDynBase…: compiled at run time
+    const char* name;
+    int (*matches)(const GfPostArgs*);       // built-in / run-time programs; an interpreter row is picked by DOF count (interp_program)
+    const void* kernel;                      // post_ws_kernel<P>
+    size_t (*lds_bytes)(int omax, int n_gait);   // everything the program itself needs, the interpreter's descriptor copy included
+    bool keeps_args_in_lds;                  // interpreter: a folded contact phase stages its slots behind the descriptor copy
+    bool folds;                              // ws_prog_folds<P>(): the kernel carries the contact phase
+    const void* tick_kernel;                 // post_ws_kernel_tick<P>; nullptr: the program has no tick variant
+    size_t (*tick_lds_bytes)(int omax, int n_gait);
+};
+
+template <class P>
+static size_t program_lds_bytes(int omax, int n_gait) {
+    return (P::kStatic ? 0 : sizeof(GfPostArgs)) + lds_ws_floats<P>(omax, n_gait) * sizeof(float);
+}
+// kWithTick instantiates post_ws_kernel_tick<P> (a kernel of its own, as large as post_ws_kernel<P>): named per program, on purpose.
+// The tick prologue covers static programs 1 and 2 and the 12- / 28-DOF table interpreter; the other built-in programs (contact
+// phases, per-link rows: scenes the tick variant does not cover) and every program compiled at run time keep their own launch.
+template <class P, bool kWithTick = false>
+static PostProgram make_program(int id) {
+    PostProgram p{};
+    p.id = id;
+    if constexpr (P::kStatic) {
+        p.name = P::name;
+        p.matches = [](const GfPostArgs* a) -> int { return program_matches<P>(*a); };
+    } else {
+        p.name = "interpreter";
+    }
+    p.kernel = reinterpret_cast<const void*>(&post_ws_kernel<P>);
+    p.lds_bytes = program_lds_bytes<P>;
+    p.keeps_args_in_lds = !P::kStatic;
+    p.folds = ws_prog_folds<P>();
+    if constexpr (kWithTick) {
+        p.tick_kernel = reinterpret_cast<const void*>(&post_ws_kernel_tick<P>);
+        p.tick_lds_bytes = program_lds_bytes<WithTick<P>>;
+    }
+    return p;
+}
+
+// Built-in programs in registration order: the first that matches runs.  tools/register_program.py --write appends to this list.
+static const PostProgram kBuiltin[] = {
+    make_program<ProgGo2CommandDirection, true>(1),
+    make_program<ProgGo2Simple, true>(2),
+    make_program<ProgGo2Contacts>(3),
+    make_program<ProgGo2RoughTerrain>(4),
+    make_program<ProgBerkeleyHumanoid>(5),
+    make_program<ProgGo2GaitTrainer>(6),
+    make_program<ProgHumanoid28Stress>(7),
+    make_program<ProgGo2GaitTrainerFront>(8),
+    make_program<ProgGo2GaitTrainerObs>(9),
+};
+
+// The table interpreter, one kernel per (float4 chunks of a DOF row, short last chunk): row [chunks - 1][tail].  Chunks 1 … 8 are the
+// DOF counts 1 … 32 that pack() admits for a step that reads a DOF row; chunk 3 serves 9 … 11 (tail) and 12.
+static const PostProgram kInterp[8][2] = {
+    {make_program<Interp<1, false>>(0), make_program<Interp<1, true>>(0)},
+    {make_program<Interp<2, false>>(0), make_program<Interp<2, true>>(0)},
+    {make_program<Interp<3, false>, true>(0), make_program<Interp<3, true>>(0)},
+    {make_program<Interp<4, false>>(0), make_program<Interp<4, true>>(0)},
+    {make_program<Interp<5, false>>(0), make_program<Interp<5, true>>(0)},
+    {make_program<Interp<6, false>>(0), make_program<Interp<6, true>>(0)},
+    {make_program<Interp<7, false>, true>(0), make_program<Interp<7, true>>(0)},
+    {make_program<Interp<8, false>>(0), make_program<Interp<8, true>>(0)},
+};
+static const PostProgram& interp_program(int num_dofs) {
+    // pack() turns "no phase reads a DOF row" into 4; a count above 32 gets past it only in such a step and runs the 12-DOF row
+    if (num_dofs < 1 || num_dofs > 32) num_dofs = 12;
+    return kInterp[(num_dofs + 3) / 4 - 1][num_dofs % 4 != 0];
+}
 
 // ---- programs compiled at run time (include/gf_step.h: gf_post_program_register) ---------------------------------------------
 // A plugin is a small shared object built from csrc/gf_post_ws.h + ONE generated program struct (genesis_forge_amd/_programs.py):
 // it carries post_ws_kernel<P> in its own code object and exports the matcher, the kernel's host handle and its LDS size.  The
-// library only keeps the table; ids start at kDynBase.  Registration is rare and append-only (fixed-size table, the count is
+// library only keeps their records; ids start at kDynBase.  Registration is rare and append-only (fixed-size table, the count is
 // published last), selection walks it on every launch of a config no built-in program matches.
-namespace {
 constexpr int kDynBase = 100, kDynMax = 256;   // (programs registered per process)
-struct DynProgram {
-    void* dl;
-    char name[64];
-    int (*matches)(const gf::GfPostArgs*);
-    const void* kernel;
-    size_t (*lds_bytes)(int, int);
-    bool folds;   // gfp_folds(): the plugin's kernel carries the contact phase (ws_prog_folds<P>)
-};
-DynProgram g_dyn[kDynMax];
-std::atomic<int> g_dyn_count{0};
-std::mutex g_dyn_mutex;
-}  // namespace
+static PostProgram g_dyn[kDynMax];
+static char g_dyn_name[kDynMax][64];
+static std::atomic<int> g_dyn_count{0};
+static std::mutex g_dyn_mutex;
 
-extern "C" __attribute__((visibility("default"))) int gf_post_program_register(const char* path, int* id_out) {
-    if (!path) return GF_E_NULL;
-    void* dl = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!dl) return GF_E_UNSUPPORTED;
-    auto abi = (int (*)(void))dlsym(dl, "gfp_abi_version");
-    auto asz = (int (*)(void))dlsym(dl, "gfp_args_size");
-    auto nm = (const char* (*)(void))dlsym(dl, "gfp_name");
-    auto mt = (int (*)(const gf::GfPostArgs*))dlsym(dl, "gfp_matches");
-    auto kn = (const void* (*)(void))dlsym(dl, "gfp_kernel");
-    auto ld = (size_t (*)(int, int))dlsym(dl, "gfp_lds_bytes");
-    // the packed descriptor is the interface between library and plugin: both must come from the same headers
-    if (!abi || !asz || !nm || !mt || !kn || !ld || abi() != GF_ABI_VERSION || asz() != (int)sizeof(gf::GfPostArgs)) {
-        dlclose(dl);
-        return GF_E_UNSUPPORTED;
+static const PostProgram& select_program(const GfPostArgs& a) {
+    if (g_options[GF_OPT_POST_VARIANT] >= 2) {
+        for (const PostProgram& p : kBuiltin)
+            if (p.matches(&a)) return p;
+        const int n = g_dyn_count.load();
+        for (int i = 0; i < n; ++i)
+            if (g_dyn[i].matches(&a)) return g_dyn[i];
     }
-    std::lock_guard<std::mutex> lock(g_dyn_mutex);
-    const int n = g_dyn_count.load();
-    for (int i = 0; i < n; ++i)
-        if (!strncmp(g_dyn[i].name, nm(), sizeof(g_dyn[i].name) - 1)) {   // already there (same signature hash in the name)
-            dlclose(dl);
-            if (id_out) *id_out = kDynBase + i;
-            return GF_OK;
-        }
-    if (n >= kDynMax) { dlclose(dl); return GF_E_RANGE; }
-    DynProgram& d = g_dyn[n];
-    d.dl = dl;
-    snprintf(d.name, sizeof(d.name), "%s", nm());
-    d.matches = mt;
-    d.kernel = kn();
-    d.lds_bytes = ld;
-    auto fo = (int (*)(void))dlsym(dl, "gfp_folds");
-    d.folds = fo && fo() != 0;
-    g_dyn_count.store(n + 1);
-    if (id_out) *id_out = kDynBase + n;
-    return GF_OK;
+    return interp_program(a.num_dofs);
 }
 
-extern "C" __attribute__((visibility("default"))) int gf_post_program_count(void) { return g_dyn_count.load(); }
-
-// Static programs in registration order; program id = 1 + index (0 = table interpreter).
-#define GF_POST_PROGRAMS(X)                                                                                                \
-    X(1, gf::ProgGo2CommandDirection) X(2, gf::ProgGo2Simple) X(3, gf::ProgGo2Contacts) X(4, gf::ProgGo2RoughTerrain) \
-    X(5, gf::ProgBerkeleyHumanoid) X(6, gf::ProgGo2GaitTrainer) \
-    X(7, gf::ProgHumanoid28Stress) X(8, gf::ProgGo2GaitTrainerFront) X(9, gf::ProgGo2GaitTrainerObs)
-
-static int select_program(const gf::GfPostArgs& a) {
-    if (gf::g_options[GF_OPT_POST_VARIANT] < 2) return 0;
-#define GF_MATCH(id, P) \
-    if (gf::program_matches<P>(a)) return id;
-    GF_POST_PROGRAMS(GF_MATCH)
-#undef GF_MATCH
-    const int n = g_dyn_count.load();
-    for (int i = 0; i < n; ++i)
-        if (g_dyn[i].matches(&a)) return kDynBase + i;
-    return 0;
-}
-
-bool gf::post_program_folds(const gf::GfPostArgs& a) {
-    const int id = select_program(a);
-    if (id >= kDynBase) return g_dyn[id - kDynBase].folds;
-#define GF_FOLDS(pid, P) \
-    if (id == pid) return gf::ws_prog_folds<P>();
-    GF_POST_PROGRAMS(GF_FOLDS)
-#undef GF_FOLDS
-    return true;   // the table interpreter
-}
-
-extern "C" __attribute__((visibility("default"))) int gf_post_physics_describe(const GfPostRefs* r, char* buf, int cap) {
-    gf::Packer pk;
-    const int rc = gf::pack(r, pk);
-    if (rc) return rc;
-    if (!buf || cap <= 0) return GF_E_NULL;
-    const int id = select_program(pk.a);
-    const char* name = "interpreter";
-#define GF_NAME(pid, P) \
-    if (id == pid) name = P::name;
-    GF_POST_PROGRAMS(GF_NAME)
-#undef GF_NAME
-    if (id >= kDynBase) name = g_dyn[id - kDynBase].name;
-    int n = snprintf(buf, (size_t)cap, "program %d (%s): ", id, name);
-    if (n < cap) gf::describe_program(pk.a, buf + n, cap - n);
-    return GF_OK;
-}
-
-#define GF_TICK_INTERP(DV_) gf::Interp<DV_, false>   // (a macro argument cannot hold the comma)
-// Which programs carry the tick prologue: static programs 1 and 2 and the 12- / 28-DOF table interpreter.  A program compiled at run
-// time and the other built-in ones (contact phases, per-link rows: scenes the tick variant does not cover) keep their own launch.
-static bool tick_variant(int prog, int num_dofs) { return prog == 1 || prog == 2 || (prog == 0 && (num_dofs == 12 || num_dofs == 28)); }
-
-int gf::post_launch(const gf::GfPostArgs& packed, hipStream_t s, int prog, const gf::TickLaunch* tick) {
+// the action and scene ops of a step that run as the launch's tick prologue (post_ws_kernel_tick)
+struct TickLaunch {
+    const GfActionArgs* act;
+    const GfSynthSceneArgs* scene;
+    int upkeep;
+};
+// launches the post-physics kernel of program `p`; with `tick`, its tick variant (p.tick_kernel, the caller has looked)
+static int post_launch(const GfPostArgs& packed, hipStream_t s, const PostProgram& p, const TickLaunch* tick = nullptr) {
 #ifdef GF_STAMPS
-    gf::GfPostArgs stamped = packed;
+    GfPostArgs stamped = packed;
     stamped.stamps = gf_debug_stamps;
     stamped.stamp_block = (uint32_t)(packed.num_envs / 64 / 2);
-    const gf::GfPostArgs& a = stamped;
+    const GfPostArgs& a = stamped;
 #else
-    const gf::GfPostArgs& a = packed;
+    const GfPostArgs& a = packed;
 #endif
     int omax = 0;
     for (int m = 0; m < a.n_obs; ++m) omax = a.obs[m].width > omax ? a.obs[m].width : omax;
     // a folded contact phase stages the tile's slot ids in the LDS the later phases use (behind the interpreter's descriptor copy)
-    const size_t fold_lds = a.cfold.num_mgr > 0 ? gf::fold_lds_bytes(a.cfold.num_contacts) : 0;
-    auto with_fold = [&](size_t bytes, bool interp) {
-        const size_t need = fold_lds ? fold_lds + (interp ? sizeof(gf::GfPostArgs) : 0) : 0;
-        return (bytes > need ? bytes : need) + (size_t)gf::kWsTilesLdsFloats * sizeof(float);
-    };
-    const unsigned grid = gf::env_grid(a.num_envs);
-    if (prog < 0) prog = select_program(a);
+    const size_t fold_lds = a.cfold.num_mgr > 0 ? fold_lds_bytes(a.cfold.num_contacts) + (p.keeps_args_in_lds ? sizeof(GfPostArgs) : 0) : 0;
+    const size_t own_lds = (tick ? p.tick_lds_bytes : p.lds_bytes)(omax, a.n_gait);
+    const size_t lds = own_lds > fold_lds ? own_lds : fold_lds;
+    const dim3 grid(env_grid(a.num_envs) + (unsigned)(tick ? tick->upkeep : 0)), block(kWsBlock);
+    const void* const kernel = tick ? p.tick_kernel : p.kernel;
+    void* kargs[4] = {const_cast<GfPostArgs*>(&a), nullptr, nullptr, nullptr};   // (post_ws_kernel reads the first only)
     if (tick) {
-        const dim3 tg(grid + (unsigned)tick->upkeep), tb(gf::kWsBlock);
-#define GF_RUN_TICK(P, interp) \
-        gf::klaunch(gf::post_ws_kernel_tick<P>, tg, tb, with_fold((interp ? sizeof(gf::GfPostArgs) : 0) + lds_ws_floats<gf::WithTick<P>>(omax, a.n_gait) * sizeof(float), interp), s, a, *tick->act, *tick->scene, tick->upkeep)
-        if (prog == 1) GF_RUN_TICK(gf::ProgGo2CommandDirection, false);
-        else if (prog == 2) GF_RUN_TICK(gf::ProgGo2Simple, false);
-        else if (a.num_dofs == 12) GF_RUN_TICK(GF_TICK_INTERP(3), true);
-        else GF_RUN_TICK(GF_TICK_INTERP(7), true);
-#undef GF_RUN_TICK
-        return gf::launch_status();
+        kargs[1] = const_cast<GfActionArgs*>(tick->act);
+        kargs[2] = const_cast<GfSynthSceneArgs*>(tick->scene);
+        kargs[3] = const_cast<int*>(&tick->upkeep);
     }
-    gf::PhaseScope scope(GF_PHASE_POST, s);
-    if (prog >= kDynBase) {
-        // a program compiled at run time: the plugin's kernel handle, launched like any other (launch sink, dispatch events)
-        const DynProgram& d = g_dyn[prog - kDynBase];
-        const size_t lds_dyn = with_fold(d.lds_bytes(omax, a.n_gait), false);
-        void* kargs[1] = {const_cast<gf::GfPostArgs*>(&a)};
-        if (scope.active()) {
-            scope.use_dispatch_events();
-            (void)hipExtLaunchKernel(d.kernel, dim3(grid), dim3(gf::kWsBlock), kargs, lds_dyn, s, scope.start(), scope.stop(), 0);
-        } else {
-            gf::sink_launch(d.kernel, dim3(grid), dim3(gf::kWsBlock), lds_dyn, s, kargs);
-        }
-    } else if (prog) {
-#define GF_RUN(id, P) \
-        if (prog == id) GF_LAUNCH(scope, gf::post_ws_kernel<P>, grid, gf::kWsBlock, with_fold(lds_ws_floats<P>(omax, a.n_gait) * sizeof(float), false), s, a);
-        GF_POST_PROGRAMS(GF_RUN)
-#undef GF_RUN
+    PhaseScope scope(GF_PHASE_POST, s);   // (never active with a tick: step_fold_try leaves a profiled phase its own launch)
+    if (scope.active()) {
+        scope.use_dispatch_events();
+        (void)hipExtLaunchKernel(kernel, grid, block, kargs, lds, s, scope.start(), scope.stop(), 0);
     } else {
-#define GF_RUN_INTERP_T(DV_, T_)                                                                                              \
-        do {                                                                                                                  \
-            using Var = gf::Interp<DV_, T_>;                                                                                  \
-            const size_t lds_var = with_fold(sizeof(gf::GfPostArgs) + lds_ws_floats<Var>(omax, a.n_gait) * sizeof(float), true); \
-            GF_LAUNCH(scope, gf::post_ws_kernel<Var>, grid, gf::kWsBlock, lds_var, s, a);                                     \
-        } while (0)
-#define GF_RUN_INTERP(DV_) \
-        do { if (a.num_dofs == 4 * DV_) GF_RUN_INTERP_T(DV_, false); else GF_RUN_INTERP_T(DV_, true); } while (0)
-        switch ((a.num_dofs + 3) / 4) {   // chunks per row
-            case 1: GF_RUN_INTERP(1); break;
-            case 2: GF_RUN_INTERP(2); break;
-            case 4: GF_RUN_INTERP(4); break;
-            case 5: GF_RUN_INTERP(5); break;
-            case 6: GF_RUN_INTERP(6); break;
-            case 7: GF_RUN_INTERP(7); break;
-            case 8: GF_RUN_INTERP(8); break;
-            default:   // 9 … 12 DOF; configs without DOF rows (num_dofs of the action manager all the same; pack() let nothing above 32 through)
-                if (a.num_dofs >= 9 && a.num_dofs < 12) GF_RUN_INTERP_T(3, true); else GF_RUN_INTERP_T(3, false);
-                break;
-        }
-#undef GF_RUN_INTERP_T
-#undef GF_RUN_INTERP
+        sink_launch(kernel, grid, block, lds, s, kargs);
     }
-    return gf::launch_status();
+    return launch_status();
+}
+
+int action_scene_check(const GfActionArgs* act, const GfSynthSceneArgs* a, int* rc, ActionScenePlan* plan);   // gf_scene.hip
+int action_scene_launch(const GfActionArgs* act, const GfSynthSceneArgs* a, const ActionScenePlan& p, hipStream_t s);
+
+int post_step(const GfPostRefs* r, const GfContactArgs* const* mgrs, int num_mgr, hipStream_t s) {
+    Packer pk;
+    int rc = pack(r, pk);
+    if (rc) return rc;
+    const PostProgram& p = select_program(pk.a);
+    if (num_mgr > 0) {
+        UNSUP(!p.folds);   // the kernel this descriptor selects does not carry the contact phase
+        rc = fold_contacts(pk, mgrs, num_mgr);
+        if (rc) return rc;
+    }
+    return post_launch(pk.a, s, p);
 }
 
 // gf_run_ops, the ops of a recorded step on the stand-in scene in a row — action, scene, post-physics: ONE launch, the post-physics kernel
@@ -821,19 +764,19 @@ int gf::post_launch(const gf::GfPostArgs& packed, hipStream_t s, int prog, const
 // What is on the stream after an error and the index it is reported with are the same in every case.
 // GF_FOLD_STEP=0 switches the peephole off (A/B runs, tests/test_step_fold.py); read per call.
 static std::atomic<long> g_step_folds{0};
-int gf::step_fold_try(const GfActionArgs* act, const GfSynthSceneArgs* sc, const GfPostRefs* refs, hipStream_t s, int* rc) {
+int step_fold_try(const GfActionArgs* act, const GfSynthSceneArgs* sc, const GfPostRefs* refs, hipStream_t s, int* rc) {
     const char* sw = getenv("GF_FOLD_STEP");
     if (sw && strcmp(sw, "0") == 0) return 0;
-    if (gf::g_prof.phase == GF_PHASE_POST) return 0;   // a profiled phase keeps its own launch (… ACTION, SCENE: action_scene_check)
-    gf::ActionScenePlan plan;
+    if (g_prof.phase == GF_PHASE_POST) return 0;   // a profiled phase keeps its own launch (… ACTION, SCENE: action_scene_check)
+    ActionScenePlan plan;
     int vrc = GF_OK;
-    if (gf::action_scene_check(act, sc, &vrc, &plan) != 3) return 0;
-    gf::Packer pk;
-    if (plan.links || plan.contacts || gf::pack(refs, pk) != GF_OK) {
-        *rc = gf::action_scene_launch(act, sc, plan, s);
+    if (action_scene_check(act, sc, &vrc, &plan) != 3) return 0;
+    Packer pk;
+    if (plan.links || plan.contacts || pack(refs, pk) != GF_OK) {
+        *rc = action_scene_launch(act, sc, plan, s);
         return 2;
     }
-    const gf::GfPostArgs& a = pk.a;
+    const GfPostArgs& a = pk.a;
     // what the post-physics phase reads of the arrays the tick writes, it reads of ITS tile: the same arrays, row for row
     auto same = [](const void* p, const void* q) { return !p || p == q; };
     const bool in_scope = a.num_envs == sc->num_envs && a.num_dofs == sc->num_dofs &&
@@ -844,20 +787,68 @@ int gf::step_fold_try(const GfActionArgs* act, const GfSynthSceneArgs* sc, const
                           same(a.dof_pos, sc->dof_pos) && same(a.dof_vel, sc->dof_vel) && same(a.targets, sc->targets) &&
                           same(a.env_actions, act->env_actions) && same(a.env_last_actions, act->env_last_actions) &&
                           same(a.episode_length, act->episode_length);
-    const int prog = select_program(a);
-    if (in_scope && tick_variant(prog, a.num_dofs)) {
-        const gf::TickLaunch tick{act, sc, plan.upkeep};
-        *rc = gf::post_launch(a, s, prog, &tick);
+    const PostProgram& p = select_program(a);
+    if (in_scope && p.tick_kernel) {
+        const TickLaunch tick{act, sc, plan.upkeep};
+        *rc = post_launch(a, s, p, &tick);
         g_step_folds.fetch_add(1, std::memory_order_relaxed);
         return 3;
     }
-    if ((*rc = gf::action_scene_launch(act, sc, plan, s)) != GF_OK) return 2;
-    *rc = gf::post_launch(a, s, prog);
+    if ((*rc = action_scene_launch(act, sc, plan, s)) != GF_OK) return 2;
+    *rc = post_launch(a, s, p);
     return 3;
 }
 
+}  // namespace gf
+
+extern "C" __attribute__((visibility("default"))) int gf_post_program_register(const char* path, int* id_out) {
+    using namespace gf;
+    if (!path) return GF_E_NULL;
+    void* dl = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!dl) return GF_E_UNSUPPORTED;
+    auto abi = (int (*)(void))dlsym(dl, "gfp_abi_version");
+    auto asz = (int (*)(void))dlsym(dl, "gfp_args_size");
+    auto nm = (const char* (*)(void))dlsym(dl, "gfp_name");
+    auto mt = (int (*)(const GfPostArgs*))dlsym(dl, "gfp_matches");
+    auto kn = (const void* (*)(void))dlsym(dl, "gfp_kernel");
+    auto ld = (size_t (*)(int, int))dlsym(dl, "gfp_lds_bytes");
+    // the packed descriptor is the interface between library and plugin: both must come from the same headers
+    if (!abi || !asz || !nm || !mt || !kn || !ld || abi() != GF_ABI_VERSION || asz() != (int)sizeof(GfPostArgs)) {
+        dlclose(dl);
+        return GF_E_UNSUPPORTED;
+    }
+    std::lock_guard<std::mutex> lock(g_dyn_mutex);
+    const int n = g_dyn_count.load();
+    for (int i = 0; i < n; ++i)
+        if (!strncmp(g_dyn_name[i], nm(), sizeof(g_dyn_name[i]) - 1)) {   // already there (same signature hash in the name)
+            dlclose(dl);
+            if (id_out) *id_out = kDynBase + i;
+            return GF_OK;
+        }
+    if (n >= kDynMax) { dlclose(dl); return GF_E_RANGE; }
+    snprintf(g_dyn_name[n], sizeof(g_dyn_name[n]), "%s", nm());
+    auto fo = (int (*)(void))dlsym(dl, "gfp_folds");   // the plugin's kernel carries the contact phase (ws_prog_folds<P>)
+    g_dyn[n] = PostProgram{kDynBase + n, g_dyn_name[n], mt, kn(), ld, false, fo && fo() != 0, nullptr, nullptr};   // (the plugin stays loaded)
+    g_dyn_count.store(n + 1);
+    if (id_out) *id_out = kDynBase + n;
+    return GF_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) int gf_post_program_count(void) { return gf::g_dyn_count.load(); }
+
+extern "C" __attribute__((visibility("default"))) int gf_post_physics_describe(const GfPostRefs* r, char* buf, int cap) {
+    gf::Packer pk;
+    const int rc = gf::pack(r, pk);
+    if (rc) return rc;
+    if (!buf || cap <= 0) return GF_E_NULL;
+    const gf::PostProgram& p = gf::select_program(pk.a);
+    int n = snprintf(buf, (size_t)cap, "program %d (%s): ", p.id, p.name);
+    if (n < cap) gf::describe_program(pk.a, buf + n, cap - n);
+    return GF_OK;
+}
+
 // steps gf_run_ops ran as one launch since the library was loaded (tests: the fold took place)
-extern "C" __attribute__((visibility("default"))) long gf_step_fold_count(void) { return g_step_folds.load(std::memory_order_relaxed); }
+extern "C" __attribute__((visibility("default"))) long gf_step_fold_count(void) { return gf::g_step_folds.load(std::memory_order_relaxed); }
 
 extern "C" __attribute__((visibility("default"))) int gf_post_physics_step(const GfPostRefs* r, void* stream) {
     return gf::post_step(r, nullptr, 0, (hipStream_t)stream);

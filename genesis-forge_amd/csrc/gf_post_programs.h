@@ -5,7 +5,8 @@
 // ranges, scales, rows, pointers, sizes, seeds) stay run-time kernel arguments.  program_matches<P>() compares a packed
 // descriptor against the signature field by field; only an exact match launches post_ws_kernel<P>, anything else runs the
 // table interpreter.  gf_post_physics_describe() prints a packed descriptor in exactly this notation, so registering a new
-// task is: run it once, paste the printed struct here, add it to GF_POST_PROGRAMS.
+// task is: run it once, paste the printed struct above the "matching" heading, add a make_program<…>(next id) line to kBuiltin in
+// gf_post.hip (tools/register_program.py --write does both).
 #pragma once
 
 #include "gf_post_ws.h"
@@ -230,7 +231,6 @@ struct ProgGo2GaitTrainerObs {
     static constexpr bool term_done = true;   // the termination masks are inputs (Python-level terms ran behind a termination launch of its own)
 };
 
-// ---- matching -------------------------------------------------------------------------------------------------------------------
 // a recorded signature (registered with tools/register_program.py)
 struct ProgHumanoid28Stress {
     static constexpr bool kStatic = true;
@@ -252,6 +252,9 @@ struct ProgHumanoid28Stress {
     static constexpr int n_air = 2;
     static constexpr int n_gait = 0;
 };
+
+// ---- matching -------------------------------------------------------------------------------------------------------------------
+// (new program structs go above this heading: tools/register_program.py --write inserts them there)
 
 // dynamic LDS of post_ws_kernel<P>, in floats (a static program keeps no copy of the descriptor in LDS; the interpreter adds one).
 // P = WithTick<…> of a program that hands its tick's tile over: the handed rows start at the scratch rows and need not fit the tile.

@@ -233,11 +233,6 @@ __host__ __device__ constexpr bool ws_hands_over() {
 template <class P>
 __host__ __device__ constexpr int ws_hand_floats() { return H_STREAMS * kEnvBlock * 4 * P::DV + HB_FIELDS * kEnvBlock + 4 * P::DV; }   // streams, base rows, zero row
 
-#ifndef GF_WS_AHEAD
-#define GF_WS_AHEAD 0
-#endif
-constexpr int kWsTilesLdsFloats = GF_WS_AHEAD > 0 ? 4 * kEnvBlock : 0;   // (experiment: one scratch row per wave, the target of the look-ahead requests)
-
 // The kernel's body.  tick_act / tick_scene / tick_upkeep are read by a WithTick program only (the descriptors of the step's action and
 // scene ops and the number of leading statistics-upkeep workgroups, as in action_scene_tile_kernel); every other program passes nothing.
 template <class P>
@@ -266,7 +261,7 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
     bool has_gait = false;
     if constexpr (P::kStatic) has_gait = P::n_gait > 0;
     else has_gait = UNI(a.n_gait) > 0;
-    float* xch = lds + kArgVec * 4 + kWsTilesLdsFloats;      // [x_fields][64]
+    float* xch = lds + kArgVec * 4;      // [x_fields][64]
     // a static program knows how many reward rows it has and every variant knows its DOF chunks: the LDS a workgroup asks for decides
     // how many of them a CU holds (Go2 programs: 30 KB → 22.5 KB, five → seven workgroups per CU, what their 72 VGPRs allow)
     constexpr int kSumRows = ws_sum_rows<P>(), kAuxRows = ws_aux_rows<P>();
@@ -332,7 +327,6 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
     float4* const hand_zero = reinterpret_cast<float4*>(hand_base + HB_FIELDS * kEnvBlock);   // [DV]: the row of an array the launch does not need
     int hand_env = lane;   // the env of the tile whose handed rows this lane reads
     if constexpr (kTick) {
-        static_assert(GF_WS_AHEAD == 0, "the look-ahead experiment would pull rows of a tile whose tick has not run into this CU's L1");
         static_assert(kSynthTileBlock == kWsBlock && 3 * 3 * kEnvBlock <= X_FIELDS * kEnvBlock, "the tick's workgroup and LDS fit the kernel's");
         const GfSynthSceneArgs& sc = *tick_scene;
         const int rows = (int)((int64_t)sc.num_envs - n0 < kEnvBlock ? (int64_t)sc.num_envs - n0 : kEnvBlock);
@@ -350,43 +344,6 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
         __syncthreads();
         GF_WSTAMP(13);
     }
-#if GF_WS_AHEAD > 0
-    {   // EXPERIMENT (tools/ab_build.sh -DGF_WS_AHEAD=K): the rows of the tile K workgroups ahead — same XCD when K % 8 == 0 —
-        // are pulled towards the caches while this tile works: one LDS-DMA dword per lane and array (every line of that tile's block is
-        // touched), no register, no wait.  (A loop over two tiles per workgroup, the other form of the pipeline, makes the compiler hoist the
-        // descriptor's scalar loads out of the loop: SGPRs spill into VGPR lanes, 77 -> 137 VGPRs — not measurable as a pipeline.)
-        const int64_t next_id = tile_id + GF_WS_AHEAD;
-        if (next_id < (N + kEnvBlock - 1) / kEnvBlock) {
-            const int64_t n2 = next_id * kEnvBlock + lane;
-            const uint32_t e2 = (uint32_t)(n2 < N ? n2 : N - 1), ro2 = e2 * (uint32_t)D;
-            float* const pf = lds + kArgVec * 4 + wave * kEnvBlock;
-            auto warm = [&](const bool on, const float* base, const uint32_t off) GF_INLINE_LAMBDA {
-                __builtin_amdgcn_global_load_lds(gsel(on, base, off), pf, 4, 0, 0);
-            };
-            if (wave == 0) {
-                warm((needs & PN_QUAT) != 0, UNI(a.quat), 4u * e2);
-                warm((needs & PN_POS) != 0, UNI(a.pos), 3u * e2);
-                warm((needs & PN_LIN) != 0, UNI(a.lin_vel), 3u * e2);
-                warm((needs & PN_ANG) != 0, UNI(a.ang_vel), 3u * e2);
-                warm((needs & PN_EPLEN) != 0, reinterpret_cast<const float*>(UNI(a.episode_length)), e2);
-                warm((needs & PN_MAXLEN) != 0, reinterpret_cast<const float*>(UNI(a.max_episode_length)), e2);
-                if (has_gait) warm(true, UNI(a.gait.state), (uint32_t)GF_GAIT_ROW * e2);
-            } else if (wave == 1) {
-                warm((needs & PN_DOFDEV) != 0, UNI(a.dof_pos), ro2);
-                warm((needs & PN_ACTRATE) != 0, UNI(a.env_actions), ro2);
-                warm((needs & PN_ACTRATE) != 0, UNI(a.env_last_actions), ro2);
-                warm(has_reward && UNI(a.episode_seconds) != nullptr, UNI(a.episode_seconds), e2);
-            } else if (wave == 2) {
-                warm((needs & PN_DOFPOS) != 0, UNI(a.dof_pos), ro2);
-                warm((needs & PN_DOFVEL) != 0, UNI(a.dof_vel), ro2);
-            } else {
-                warm((needs & PN_TARGETS) != 0, UNI(a.targets), ro2);
-                warm((needs & PN_ACTIONS) != 0, UNI(a.env_actions), ro2);
-                warm(UNI(a.dof_force) != nullptr, UNI(a.dof_force), ro2);
-            }
-        }
-    }
-#endif
 
     // the command managers' table rows; a static program knows the widths
     auto cmd_row = [&](int c) GF_INLINE_LAMBDA {

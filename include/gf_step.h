@@ -1196,7 +1196,7 @@ int gf_post_physics_needs(const GfPostRefs* r, uint32_t* needs_out);
  * that matches it — ids from 100 upwards in gf_post_physics_describe.  Structure only: weights, parameters, ranges, scales
  * stay run-time kernel arguments, a config whose STRUCTURE changes simply stops matching (interpreter until its own program is
  * there).  The plugin exports gfp_abi_version / gfp_args_size (checked against this library: GF_E_UNSUPPORTED on a mismatch or
- * an unloadable file) / gfp_name / gfp_matches / gfp_kernel / gfp_lds_bytes.  Append-only, at most 64, thread-safe. */
+ * an unloadable file) / gfp_name / gfp_matches / gfp_kernel / gfp_lds_bytes.  Append-only, at most 256, thread-safe. */
 int gf_post_program_register(const char* plugin_path, int* program_id_out);
 int gf_post_program_count(void);
 

@@ -118,3 +118,22 @@ def test_no_kernel_spills_to_scratch_and_the_fused_kernels_keep_their_occupancy(
     assert vgprs("post_ws_kernelINS_6InterpILi7ELb0EEE") <= 168      # 28-DOF interpreter: three
     assert vgprs("post_ws_kernelINS_23ProgGo2CommandDirectionE") <= 84   # the benchmark's program: six
     assert vgprs("post_ws_kernelINS_18ProgGo2GaitTrainerE") <= 100   # five
+
+
+def test_the_fused_kernel_is_instantiated_for_exactly_the_programs_of_the_table():
+    """post_ws_kernel<P> exists for the nine built-in programs and the 8 x 2 rows of the table interpreter, post_ws_kernel_tick<P> for
+    the four programs that carry the tick prologue: a kernel more is ~1 150 source lines of build time and library size nobody launches
+    (a helper that instantiates a tick variant per program adds twenty of them), a kernel less is a program the table cannot launch."""
+    import pytest
+
+    if not os.path.exists(READELF):
+        pytest.skip("no llvm-readelf")
+    builtin = ["23ProgGo2CommandDirection", "13ProgGo2Simple", "15ProgGo2Contacts", "19ProgGo2RoughTerrain", "20ProgBerkeleyHumanoid",
+               "18ProgGo2GaitTrainer", "20ProgHumanoid28Stress", "23ProgGo2GaitTrainerFront", "21ProgGo2GaitTrainerObs"]
+    interp = ["6InterpILi%dELb%dEE" % (dv, tail) for dv in range(1, 9) for tail in (0, 1)]
+    tick = ["23ProgGo2CommandDirection", "13ProgGo2Simple", "6InterpILi3ELb0EE", "6InterpILi7ELb0EE"]
+    want = {"_ZN2gf14post_ws_kernelINS_%sEEEvNS_10GfPostArgsE" % p for p in builtin + interp}
+    want |= {"_ZN2gf19post_ws_kernel_tickINS_%sEEEvNS_10GfPostArgsE12GfActionArgs16GfSynthSceneArgsi" % p for p in tick}
+    assert len(want) == 9 + 16 + 4
+    have = {k for k in _kernel_resources(nat.lib_path()) if "post_ws_kernel" in k}
+    assert have == want, (sorted(have - want), sorted(want - have))

@@ -1030,20 +1030,26 @@ def test_recorded_step_follows_live_manager_attributes(oracle_backend):
     assert not any(k.startswith("Rewards /") for k in a[-1][5]) and int(a[-1][4].min()) < 30
 
 
-@pytest.mark.parametrize("dofs", [7, 16])
+# one DOF count per row of the fused launch's interpreter table (chunks of a DOF row 1 … 8, with and without a short last chunk) that
+# the counts above them in the lists leave out, at one full 64-env tile and a partial one
+_INTERP_ROW_DOFS = [(3, 70), (4, 70), (13, 70), (17, 70), (21, 70), (26, 70), (30, 70), (32, 70)]
+
+
+@pytest.mark.parametrize("dofs", [7, 16] + [d for d, _ in _INTERP_ROW_DOFS])
 def test_other_dof_counts_use_phase_chains_cpu(oracle_backend, dofs):
-    """Other DOF counts: the step is still recorded; on the GPU every count up to 28 runs the fused launch."""
-    a, _ = _run_humanoid("cpu", "ordinary", 50, dofs)
-    b, env = _run_humanoid("cpu", "fused", 50, dofs)
+    """Other DOF counts: the step is still recorded; on the GPU every count up to 32 runs the fused launch."""
+    n = dict(_INTERP_ROW_DOFS).get(dofs, 50)
+    a, _ = _run_humanoid("cpu", "ordinary", n, dofs)
+    b, env = _run_humanoid("cpu", "fused", n, dofs)
     assert env._trace is not None
     _same_h(a, b)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dofs,n", [(7, 300), (10, 65), (16, 1000), (20, 129), (8, 257), (24, 1000)])
+@pytest.mark.parametrize("dofs,n", [(7, 300), (10, 65), (16, 1000), (20, 129), (8, 257), (24, 1000)] + _INTERP_ROW_DOFS)
 def test_other_dof_counts_hip(hip_backend, oracle_lib_path, dofs, n):
     """Scalar-row (D % 4 != 0) variants of the reward / action / scene kernels (ordinary steps) and the fused launch's interpreter for
-    7 / 8 / 10 / 16 / 20 / 24 DOF (recorded steps): recorded == ordinary on HIP, and HIP == oracle."""
+    7 / 8 / 10 / 16 / 20 / 24 DOF and the rest of its table's rows (recorded steps): recorded == ordinary on HIP, and HIP == oracle."""
     from genesis_forge_amd import _native as nat
     from genesis_forge_amd import gs
     from oracle_backend import OracleBackend
@@ -1051,7 +1057,7 @@ def test_other_dof_counts_hip(hip_backend, oracle_lib_path, dofs, n):
     a, _ = _run_humanoid("cuda", "ordinary", n, dofs)
     b, env = _run_humanoid("cuda", "fused", n, dofs)
     assert env._trace is not None
-    assert env._trace.post_refs is not None, "every DOF count up to 28 runs the fused launch (ceil(D / 4) row chunks, the last one element by element)"
+    assert env._trace.post_refs is not None, "every DOF count up to 32 runs the fused launch (ceil(D / 4) row chunks, the last one element by element)"
     _same_h(a, b)
     torch.cuda.synchronize()
     gs.set_device("cpu")

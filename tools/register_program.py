@@ -69,21 +69,19 @@ def main():
     text = struct_text(parse(sig), args.name, cls, f"{origin} (registered with tools/register_program.py)")
     if not args.write:
         print(text)
-        print(f"// and in gf_post.hip, GF_POST_PROGRAMS: X(<next id>, gf::{cls})")
+        print(f"// above the \"matching\" heading of gf_post_programs.h; and in gf_post.hip, kBuiltin: make_program<{cls}>(<next id>),")
         return
     hp = os.path.join(CSRC, "gf_post_programs.h")
     src = open(hp).read()
-    anchor = "template <class P>\nbool program_matches"
-    assert anchor in src and cls not in src
+    anchor = "// ---- matching ----"
+    assert src.count(anchor) == 1 and cls not in src
     open(hp, "w").write(src.replace(anchor, text.lstrip("\n") + "\n" + anchor, 1))
     pp = os.path.join(CSRC, "gf_post.hip")
     src = open(pp).read()
-    m = re.search(r"(#define GF_POST_PROGRAMS\(X\).*?\n)((?:\s+X\(.*\\?\n)+)", src)
-    ids = [int(x) for x in re.findall(r"X\((\d+),", m.group(2))]
-    last = m.group(2).rstrip("\n")
-    new = last + f" \\\n    X({max(ids) + 1}, gf::{cls})\n"
-    open(pp, "w").write(src.replace(m.group(2), new, 1))
-    print(f"registered {cls} as program {max(ids) + 1}; rebuild: make -C genesis-forge_amd/csrc", file=sys.stderr)
+    m = re.search(r"static const PostProgram kBuiltin\[\] = \{\n((?:    make_program<.*\n)+)(?=\};)", src)
+    next_id = max(int(x) for x in re.findall(r">\((\d+)\),", m.group(1))) + 1
+    open(pp, "w").write(src[:m.end(1)] + f"    make_program<{cls}>({next_id}),\n" + src[m.end(1):])
+    print(f"registered {cls} as program {next_id}; rebuild: make -C genesis-forge_amd/csrc", file=sys.stderr)
 
 
 if __name__ == "__main__":

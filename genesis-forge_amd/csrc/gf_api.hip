@@ -78,6 +78,7 @@ GF_EXPORT int gf_sizeof(int which) {
         case 27: return (int)sizeof(GfAdamArgs);
         case 28: return (int)sizeof(GfMlpActArgs);
         case 29: return (int)sizeof(GfObsNormArgs);
+        case 30: return (int)sizeof(GfRolloutFrameArgs);
         default: return -1;
     }
 }

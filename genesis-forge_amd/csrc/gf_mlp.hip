@@ -177,7 +177,8 @@ __device__ __forceinline__ void mlp_layer(MlpSmem& sm, const GfMlpNet& net, cons
                     const int w = s < net.num_inputs ? net.inputs[s].width : 0;
                     const bool hit = in && k >= 0 && k < w;
                     rows = hit ? net.inputs[s].rows : rows;
-                    off = hit ? n * w + k : off;
+                    const int stride = net.inputs[s].row_stride ? net.inputs[s].row_stride : w;
+                    off = hit ? n * stride + k : off;
                     k -= w;
                 }
                 float v = G(rows)[off];
@@ -289,7 +290,7 @@ static int mlp_check_net(const GfMlpNet& net, bool critic, int* out_width) {
     int64_t in = 0;
     for (int s = 0; s < net.num_inputs; ++s) {
         if (!net.inputs[s].rows) return GF_E_NULL;
-        if (net.inputs[s].width < 1) return GF_E_RANGE;
+        if (net.inputs[s].width < 1 || (net.inputs[s].row_stride && net.inputs[s].row_stride < net.inputs[s].width)) return GF_E_RANGE;
         in += net.inputs[s].width;
     }
     if (in > GF_MLP_MAX_INPUT_WIDTH) return GF_E_RANGE;

@@ -30,17 +30,17 @@ struct OnColumn {
 
 __device__ __forceinline__ OnColumn on_column(const GfObsNormSet& set, int c) {
     const float* rows = set.inputs[0].rows;
-    int width = set.inputs[0].width, at = 0, k = c;
+    int stride = set.inputs[0].row_stride ? set.inputs[0].row_stride : set.inputs[0].width, at = 0, k = c;
 #pragma unroll
     for (int s = 0; s < GF_MLP_MAX_INPUTS; ++s) {
         const int w = s < set.num_inputs ? set.inputs[s].width : 0;
         const bool hit = k >= 0 && k < w;
         rows = hit ? set.inputs[s].rows : rows;
-        width = hit ? w : width;
+        stride = hit ? (set.inputs[s].row_stride ? set.inputs[s].row_stride : w) : stride;
         at = hit ? k : at;
         k -= w;
     }
-    return OnColumn{G(rows) + at, (int64_t)width};
+    return OnColumn{G(rows) + at, (int64_t)stride};
 }
 
 // Q = columns per lane: 1 (W <= 256: floor(256 / W) lanes per column) or 4 (W > 256: one lane per column group)
@@ -217,7 +217,7 @@ extern "C" __attribute__((visibility("default"))) int gf_obs_norm_update(const G
         int64_t W = 0;
         for (int s = 0; s < set.num_inputs; ++s) {
             if (!set.inputs[s].rows) return GF_E_NULL;
-            if (set.inputs[s].width < 1) return GF_E_RANGE;
+            if (set.inputs[s].width < 1 || (set.inputs[s].row_stride && set.inputs[s].row_stride < set.inputs[s].width)) return GF_E_RANGE;
             W += set.inputs[s].width;
         }
         if (W > GF_MLP_MAX_INPUT_WIDTH) return GF_E_RANGE;

@@ -142,7 +142,104 @@ __global__ __launch_bounds__(kRollBlock) void gae_normalize_kernel(float* adv, c
     }
 }
 
+// ---- the newest frame of up to GF_ROLLOUT_FRAME_MAX history observations into a frame-major storage ------------------------------
+// grid y = segment.  Lanes cover (env, chunk) pairs of the segment's [N, width] destination; the source row of env n starts
+// n * src_stride floats into `src` (the tensor the step returned: a contiguous [N, H·O] row block or an output="window" view), of
+// which only the first `width` columns — the newest frame — are read.  kFrameUnits chunk loads are issued before their stores.
+// Pure copy; R 4·O, W 4·O bytes per env and segment.
+constexpr int kFrameUnits = 4;
+
+struct FrameConsts {
+    uint64_t magic[GF_ROLLOUT_FRAME_MAX];   // ceil(2^64 / chunks) (chunks >= 2): e / chunks = umulhi64(e, magic) for e·chunks < 2^64
+    int32_t chunks[GF_ROLLOUT_FRAME_MAX];   // chunks per env
+    int32_t vec[GF_ROLLOUT_FRAME_MAX];      // floats per chunk: 4, 2 or 1
+};
+
+typedef float frame_f32x2 __attribute__((ext_vector_type(2)));
+template <int V> struct FrameVec;
+template <> struct FrameVec<4> { typedef f32x4 T; };
+template <> struct FrameVec<2> { typedef frame_f32x2 T; };
+template <> struct FrameVec<1> { typedef float T; };
+
+template <int V>
+__device__ __forceinline__ void frame_copy(const GfRolloutFrameSeg& g, const int64_t N, const int chunks, const uint64_t magic) {
+    typedef typename FrameVec<V>::T VT;
+    const int64_t items = N * chunks;
+    const int64_t step = (int64_t)gridDim.x * kRollBlock;
+    const GF_GLOBAL float* src = G(g.src);
+    GF_GLOBAL float* dst = G(g.dst);
+    for (int64_t base = (int64_t)blockIdx.x * kRollBlock + threadIdx.x; base < items; base += step * kFrameUnits) {
+        VT v[kFrameUnits];
+        int64_t at[kFrameUnits];
+#pragma unroll
+        for (int k = 0; k < kFrameUnits; ++k) {
+            const int64_t it = base + (int64_t)k * step;
+            at[k] = -1;
+            if (it < items) {
+                const int64_t n = chunks == 1 ? it : (int64_t)__umul64hi((uint64_t)it, magic);
+                const int64_t c = it - n * chunks;
+                at[k] = it * V;   // (n * width + c * V: the destination rows are contiguous)
+                v[k] = *reinterpret_cast<const GF_GLOBAL VT*>(src + n * g.src_stride + c * V);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kFrameUnits; ++k)
+            if (at[k] >= 0) *reinterpret_cast<GF_GLOBAL VT*>(dst + at[k]) = v[k];
+    }
+}
+
+__global__ __launch_bounds__(kRollBlock) void rollout_frame_kernel(const GfRolloutFrameArgs a, const FrameConsts fc) {
+    const int s = blockIdx.y;
+    const int v = fc.vec[s];
+    if (v == 4) frame_copy<4>(a.segs[s], a.num_envs, fc.chunks[s], fc.magic[s]);
+    else if (v == 2) frame_copy<2>(a.segs[s], a.num_envs, fc.chunks[s], fc.magic[s]);
+    else frame_copy<1>(a.segs[s], a.num_envs, fc.chunks[s], fc.magic[s]);
+}
+
+int rollout_frame_prep(const GfRolloutFrameArgs* a) {
+    if (!a) return GF_E_NULL;
+    if (a->num_envs < 0 || a->num_segs < 1 || a->num_segs > GF_ROLLOUT_FRAME_MAX) return GF_E_RANGE;
+    for (int s = 0; s < a->num_segs; ++s) {
+        const GfRolloutFrameSeg& g = a->segs[s];
+        if (!g.src || !g.dst) return GF_E_NULL;
+        if (g.width < 1 || g.src_stride < g.width) return GF_E_RANGE;
+    }
+    return GF_OK;
+}
+
+// widest chunk (floats) every row of the segment can be moved in
+static int frame_vec(const GfRolloutFrameSeg& g) {
+    const uintptr_t p = reinterpret_cast<uintptr_t>(g.src) | reinterpret_cast<uintptr_t>(g.dst);
+    const int32_t w = g.width | g.src_stride;
+    if ((p & 15u) == 0 && (w & 3) == 0) return 4;
+    if ((p & 7u) == 0 && (w & 1) == 0) return 2;
+    return 1;
+}
+
 }  // namespace gf
+
+extern "C" __attribute__((visibility("default"))) int gf_rollout_frame_write(const GfRolloutFrameArgs* a, void* stream) {
+    const int rc = gf::rollout_frame_prep(a);
+    if (rc) return rc;
+    if (a->num_envs == 0) return GF_OK;
+    gf::FrameConsts fc{};
+    int64_t most = 0;
+    for (int s = 0; s < a->num_segs; ++s) {
+        const int v = gf::frame_vec(a->segs[s]);
+        const int chunks = a->segs[s].width / v;
+        fc.vec[s] = v;
+        fc.chunks[s] = chunks;
+        fc.magic[s] = chunks > 1 ? ~(uint64_t)0 / (uint64_t)chunks + 1 : 0;
+        const int64_t items = a->num_envs * chunks;
+        most = items > most ? items : most;
+    }
+    // one workgroup per kRollBlock * kFrameUnits chunks of the largest segment (a smaller segment's surplus workgroups find no item)
+    const int64_t per = (int64_t)gf::kRollBlock * gf::kFrameUnits;
+    const int64_t blocks = (most + per - 1) / per;
+    if (blocks > 0x7fffffff) return GF_E_RANGE;
+    gf::klaunch(gf::rollout_frame_kernel, dim3((unsigned)blocks, (unsigned)a->num_segs), dim3(gf::kRollBlock), 0, (hipStream_t)stream, *a, fc);
+    return gf::launch_status();
+}
 
 extern "C" __attribute__((visibility("default"))) int gf_rollout_policy_write(const GfRolloutPolicyArgs* a, void* stream) {
     if (!a) return GF_E_NULL;

@@ -13,7 +13,7 @@ import ctypes as C
 import os
 from typing import Optional
 
-GF_ABI_VERSION = 8
+GF_ABI_VERSION = 9
 GF_MAX_TERMS = 24
 GF_MAX_TERM_TERMS = 16
 GF_MAX_OBS_ITEMS = 24
@@ -312,8 +312,10 @@ GF_SIZEOF_MINIBATCH = 23   # gf_sizeof index of GfMinibatchArgs (not in ABI_STRU
 
 
 class GfMinibatchField(C.Structure):
-    _fields_ = [("src", P), ("dst", P), ("src_width", C.c_int32), ("dst_width", C.c_int32), ("dst_col", C.c_int32), ("_pad", C.c_int32),
-                ("mean", P), ("std", P), ("eps", C.c_float), ("_pad2", C.c_int32)]   # the field's normaliser (mean NULL: pure copy)
+    _fields_ = [("src", P), ("dst", P), ("src_width", C.c_int32), ("dst_width", C.c_int32), ("dst_col", C.c_int32),
+                ("history_len", C.c_int32),          # H > 1: `src` holds frames [(T + H)·N, src_width], the field is H·src_width columns wide
+                ("mean", P), ("std", P), ("eps", C.c_float),   # the field's normaliser (mean NULL: pure copy)
+                ("frame_stride_rows", C.c_int32)]    # N: source rows from a frame to the next newer one
 
 
 class GfMinibatchArgs(C.Structure):
@@ -387,7 +389,7 @@ GF_MLP_TILE_ROWS = 32
 
 
 class GfMlpSegment(C.Structure):
-    _fields_ = [("rows", P), ("width", C.c_int32), ("_pad", C.c_int32)]
+    _fields_ = [("rows", P), ("width", C.c_int32), ("row_stride", C.c_int32)]   # row_stride in floats; 0: width (contiguous rows)
 
 
 class GfMlpLayer(C.Structure):
@@ -424,6 +426,20 @@ class GfObsNormSet(C.Structure):
 
 class GfObsNormArgs(C.Structure):
     _fields_ = [("num_rows", C.c_int64), ("num_sets", C.c_int32), ("_pad", C.c_int32), ("sets", GfObsNormSet * GF_OBS_NORM_MAX_SETS)]
+
+
+# the newest frame of a history observation into a frame-major rollout storage (learner.RolloutStorage(history="frames")):
+# gf_rollout_frame_write, issued by the storage behind the step's rollout_write — not a phase, not in ABI_STRUCTS either
+GF_SIZEOF_ROLLOUT_FRAME = 30
+GF_ROLLOUT_FRAME_MAX = 4
+
+
+class GfRolloutFrameSeg(C.Structure):
+    _fields_ = [("src", P), ("dst", P), ("width", C.c_int32), ("src_stride", C.c_int32)]
+
+
+class GfRolloutFrameArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("num_segs", C.c_int32), ("_pad", C.c_int32), ("segs", GfRolloutFrameSeg * GF_ROLLOUT_FRAME_MAX)]
 
 
 ABI_STRUCTS = [GfStepStats, GfActionArgs, GfContactArgs, GfTerminationArgs, GfRewardArgs, GfCommandArgs,
@@ -652,7 +668,8 @@ class HipBackend(Backend):
         # the two pieces of the collection loop (RolloutStorage.act / process_env_step): the same kind of entry points
         for fn, idx, st in (("gf_policy_act", GF_SIZEOF_POLICY_ACT, GfPolicyActArgs), ("gf_episode_step", GF_SIZEOF_EPISODE, GfEpisodeArgs),
                             ("gf_ppo_loss", GF_SIZEOF_PPO_LOSS, GfPpoLossArgs), ("gf_adam_step", GF_SIZEOF_ADAM, GfAdamArgs),
-                            ("gf_mlp_act", GF_SIZEOF_MLP_ACT, GfMlpActArgs), ("gf_obs_norm_update", GF_SIZEOF_OBS_NORM, GfObsNormArgs)):
+                            ("gf_mlp_act", GF_SIZEOF_MLP_ACT, GfMlpActArgs), ("gf_obs_norm_update", GF_SIZEOF_OBS_NORM, GfObsNormArgs),
+                            ("gf_rollout_frame_write", GF_SIZEOF_ROLLOUT_FRAME, GfRolloutFrameArgs)):
             n = self.lib.gf_sizeof(idx)
             if n != C.sizeof(st):
                 raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")
@@ -690,6 +707,12 @@ class HipBackend(Backend):
         rc = self.lib.gf_minibatch_gather(C.byref(args), self._stream())
         if rc != 0:
             self._raise("minibatch_gather", rc)
+
+    def rollout_frame_write(self, args) -> None:
+        """gf_rollout_frame_write on the current stream (learner.RolloutStorage(history="frames"): behind the step's rollout_write)."""
+        rc = self.lib.gf_rollout_frame_write(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("rollout_frame_write", rc)
 
     def policy_act(self, args) -> None:
         """gf_policy_act on the current stream (learner.RolloutStorage.act)."""

@@ -708,6 +708,8 @@ class StepTrace:
             fused = self.post_refs is not None and bool(self.post_refs.rollout)
             t.patches.append(owner._trace_patch(args, pol if fused and pol._unrolled else None))
             t.add(owner._trace_native(args, pol, fused))
+            if owner._frame_parts:   # history="frames": the newest frames go into the storage by a launch of the storage's own, behind the step's
+                t.afters.append((t.op, owner._write_frames))
         elif fn != "reward_step":   # (the reward launch has no per-step field)
             raise RuntimeError(f"untraceable phase {fn}")
 

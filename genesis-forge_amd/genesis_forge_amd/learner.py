@@ -12,6 +12,9 @@ dependency and stays one; this module provides the two pieces of it that touch t
   (``add_policy``), and the end-of-rollout return computation (rsl_rl ``compute_returns``: a backwards loop of eight
   elementwise launches per step, then the advantage normalisation) is ``gf_gae`` (``compute_returns``): one lane per env
   walks its T steps, rows are coalesced, the recurrence is the torch loop's arithmetic operation for operation.
+  ``history="frames"`` keeps a history observation (``history_len`` = H > 1) once per FRAME — ``frames[name] [T+H, N, O]`` instead of
+  rows ``[T+1, N, H·O]``: a step stores O floats per env (``gf_rollout_frame_write``, one launch for all such managers, behind the
+  step's own), the minibatch gather rebuilds the ``[mb, H·O]`` rows — and so follows an ``output="window"`` manager too.
   ``obs_groups`` (rsl_rl's dict form) adds the rows of further ObservationManagers — the gait trainer's asymmetric critic —
   stored by the step's own launches too, and ``mini_batch_generator`` reads the rollout back as PPO minibatches: rsl_rl's nine
   per-field index launches per minibatch are one ``gf_minibatch_gather`` launch.
@@ -68,8 +71,16 @@ _MB_FIELDS = ("actions", "values", "advantages", "returns", "actions_log_prob", 
 _LOG_SQRT_2PI = math.log(math.sqrt(2 * math.pi))   # the constant of torch's Normal.log_prob
 
 
-def _check_f32(x, name: str, shapes, device) -> None:
-    """``act``'s inputs are taken as they are: float32, contiguous, on the storage's device, one of ``shapes`` — nothing is cast."""
+def _rows_ok(x: torch.Tensor) -> bool:
+    """Contiguous rows — or the history window an ``ObservationManager(output="window")`` handed out (it marks its views): unit
+    column stride, rows at least a width apart.  ``gf_mlp_act`` and ``gf_obs_norm_update`` read such a view in place (``row_stride``);
+    any other strided tensor stays refused: nothing says how long its rows stay what they are."""
+    return x.is_contiguous() or (getattr(x, "_gf_window", False) and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1])
+
+
+def _check_f32(x, name: str, shapes, device, window: bool = False) -> None:
+    """``act``'s inputs are taken as they are: float32, contiguous, on the storage's device, one of ``shapes`` — nothing is cast.
+    ``window``: an observation — the strided view of a window-mode ObservationManager is taken as it is too (``_rows_ok``)."""
     if not isinstance(x, torch.Tensor):
         raise ValueError(f"{name} must be a tensor")
     if x.dtype != torch.float32:
@@ -78,7 +89,7 @@ def _check_f32(x, name: str, shapes, device) -> None:
         raise ValueError(f"{name} lives on {x.device}, the storage on {device}")
     if tuple(x.shape) not in shapes:
         raise ValueError(f"{name} has shape {tuple(x.shape)}; expected one of {sorted(shapes)}")
-    if not x.is_contiguous():
+    if not (_rows_ok(x) if window else x.is_contiguous()):
         raise ValueError(f"{name} must be contiguous")
 
 
@@ -144,19 +155,39 @@ class RolloutStorage:
     concatenation of the named ObservationManagers' rows in list order.  Rows are kept once per distinct manager, not per group:
     ``observations`` for ``obs_name``, ``group_rows[name]`` for every member (the ``obs_name`` entry is ``observations``
     itself).  ``None``: both groups are ``[obs_name]`` — nothing beyond ``observations`` is stored.
-    ``mini_batch_generator`` reads the rollout back as PPO minibatches."""
+    ``mini_batch_generator`` reads the rollout back as PPO minibatches.
 
-    def __init__(self, env, num_steps: int, obs_name: str = "policy", obs_groups: Optional[Dict[str, Sequence[str]]] = None):
-        self.env, self.num_steps, self.obs_name = env, int(num_steps), obs_name
+    ``history="frames"``: every followed manager with ``history_len`` = H > 1 is kept once per frame — ``frames[name]`` is
+    ``[T + H, N, O]``, observation row ``r`` (0 … T) of that manager is frames ``r … r+H-1``, frame ``r+H-1`` the newest (the
+    reference's history is a pure sliding window — never cleared per env, untouched by a reset — so row ``t`` is frames
+    ``t, t-1, … t-H+1``).  Such a manager has no entry in ``group_rows``, and ``observations`` is ``None`` when ``obs_name`` is one;
+    ``observation_rows()`` materialises the rows.  A step stores the newest frame only (columns ``0 … O-1`` of the tensor the step
+    returned, whatever its row stride: ``output="fresh"``, ``"static"`` and ``"window"`` are all newest first; ``"ring"`` is ordered
+    by slot and refused), one ``gf_rollout_frame_write`` launch for all of them behind the step's own; the minibatch gather rebuilds
+    the ``[mb, H·O]`` rows (a pure copy: the same bits).  Managers without a history keep their rows; the default ``"rows"`` is the
+    layout above for every manager."""
+
+    def __init__(self, env, num_steps: int, obs_name: str = "policy", obs_groups: Optional[Dict[str, Sequence[str]]] = None,
+                 history: str = "rows"):
+        if history not in ("rows", "frames"):
+            raise ValueError(f"history must be 'rows' or 'frames', not {history!r}")
+        self.env, self.num_steps, self.obs_name, self.history = env, int(num_steps), obs_name, history
         n = env.num_envs
         managers = {m.name: m for m in env.managers["observation"]}
         om = managers.get(obs_name)
         if om is None:
             raise ValueError(f"no ObservationManager named '{obs_name}'")
         self._om = om
-        self._refuse_window(om)
+        self.frames: Dict[str, torch.Tensor] = {}
+        self._frame_oms: list = []   # the frame-stored managers, in the order of their segments
         self.obs_width = int(om.observation_space.shape[0])
-        self.observations = torch.zeros((self.num_steps + 1, n, self.obs_width), device=gs.device, dtype=torch.float32)
+        self._widths = {obs_name: self.obs_width}
+        if self._framed(om):
+            self.observations = None
+            self._add_frames(om)
+        else:
+            self._refuse_window(om)
+            self.observations = torch.zeros((self.num_steps + 1, n, self.obs_width), device=gs.device, dtype=torch.float32)
         groups = {"policy": [obs_name], "critic": [obs_name]} if obs_groups is None else {k: list(v) for k, v in obs_groups.items()}
         if "policy" not in groups:
             raise ValueError("obs_groups needs a 'policy' group")
@@ -168,11 +199,15 @@ class RolloutStorage:
             if not members:
                 raise ValueError("an observation group needs at least one ObservationManager")
             for name in members:
-                if name in self.group_rows:
+                if name in self.group_rows or name in self.frames:
                     continue
                 m = managers.get(name)
                 if m is None:
                     raise ValueError(f"obs_groups names '{name}', but the env has no ObservationManager of that name")
+                self._widths[name] = int(m.observation_space.shape[0])
+                if self._framed(m):
+                    self._add_frames(m)
+                    continue
                 self._refuse_window(m)
                 if name == obs_name:
                     self.group_rows[name] = self.observations
@@ -181,10 +216,22 @@ class RolloutStorage:
                 self.group_rows[name] = rows
                 self._group_writers.append(_GroupRows(m, rows))
         self.rewards = torch.zeros((self.num_steps, n), device=gs.device, dtype=torch.float32)
+        self._device = self.rewards.device
         self.dones = torch.zeros((self.num_steps, n), device=gs.device, dtype=torch.bool)
         self.step = 0            # transitions written in the current rollout
         self._args = nat.GfRolloutArgs()
         self._args.num_envs, self._args.obs_width = n, self.obs_width
+        # one descriptor per GF_ROLLOUT_FRAME_MAX frame-stored managers: each is one gf_rollout_frame_write launch per step
+        k = nat.GF_ROLLOUT_FRAME_MAX
+        self._frame_parts = [(nat.GfRolloutFrameArgs(), self._frame_oms[at:at + k]) for at in range(0, len(self._frame_oms), k)]
+        for fa, oms in self._frame_parts:
+            fa.num_envs, fa.num_segs = n, len(oms)
+            for seg, m in zip(fa.segs, oms):
+                seg.width = self.frames[m.name].shape[2]
+        # per frame-stored manager: (manager, frames, address of frame H, bytes per frame); the output mode its tensor was last checked in
+        self._frame_dst = {m.name: (self.frames[m.name].data_ptr() + m._history_len * self.frames[m.name].stride(0) * 4, self.frames[m.name].stride(0) * 4)
+                           for m in self._frame_oms}
+        self._frame_checked: Dict[str, str] = {}
         # the policy's rows and the return computation (allocated on first use: a storage that only takes the env's rows stays small)
         self.num_actions = None
         self.actions = self.values = self.actions_log_prob = self.mu = self.sigma = self.returns = self.advantages = None
@@ -210,6 +257,22 @@ class RolloutStorage:
             raise ValueError(f"RolloutStorage copies contiguous observation rows: ObservationManager '{om.name}' has output='window' and "
                              "hands out a strided view — use output='fresh' / 'static' for the managers the storage follows")
 
+    def _framed(self, om) -> bool:
+        return self.history == "frames" and om._history_len > 1
+
+    def _add_frames(self, om) -> None:
+        if getattr(om, "output", None) == "ring":
+            raise ValueError(f"RolloutStorage(history='frames') stores the newest frame of a newest-first observation: ObservationManager "
+                             f"'{om.name}' has output='ring', which is ordered by slot — use output='fresh', 'static' or 'window'")
+        H = om._history_len
+        O = int(om.observation_space.shape[0]) // H
+        self.frames[om.name] = torch.zeros((self.num_steps + H, self.env.num_envs, O), device=gs.device, dtype=torch.float32)
+        self._frame_oms.append(om)
+
+    @property
+    def device(self) -> torch.device:
+        return self._device
+
     @property
     def full(self) -> bool:
         return self.step >= self.num_steps
@@ -227,24 +290,36 @@ class RolloutStorage:
     def begin(self, obs: torch.Tensor, extras: Optional[dict] = None) -> None:
         """Start a rollout from ``obs`` and ``extras`` (what ``env.reset()`` returned; the group members' starting rows are read from
         ``extras["observations"]``, so ``extras`` is required when ``obs_groups`` names a manager other than ``obs_name``)."""
-        if self._group_writers:
+        if self._group_writers or any(m is not self._om for m in self._frame_oms):
             if extras is None or "observations" not in extras:
                 raise ValueError("begin(obs, extras): the observation groups need every member's starting rows — pass what env.reset() returned")
             for w in self._group_writers:
                 w.rows[0].copy_(extras["observations"][w.om.name])
-        self.observations[0].copy_(obs)
+        for m in self._frame_oms:   # row 0 as its H frames: column block j (newest first) is frame H-1-j
+            row = obs if m is self._om else extras["observations"][m.name]
+            F = self.frames[m.name]
+            H, O = m._history_len, F.shape[2]
+            for j in range(H):
+                F[H - 1 - j].copy_(row[:, j * O:(j + 1) * O])
+        if self.observations is not None:
+            self.observations[0].copy_(obs)
         self.step = 0
         self._pol_serial = self._boot_serial = -1
 
     def _next_rows(self, a: nat.GfRolloutArgs) -> None:
         """Point the descriptor at transition ``step``'s rows and advance (wrapping into the next rollout)."""
-        if self.step >= self.num_steps:
-            self.observations[0].copy_(self.observations[self.num_steps])
+        T = self.num_steps
+        if self.step >= T:
+            if self.observations is not None:
+                self.observations[0].copy_(self.observations[T])
             for w in self._group_writers:
-                w.rows[0].copy_(w.rows[self.num_steps])
+                w.rows[0].copy_(w.rows[T])
+            for F in self.frames.values():   # row T's frames become row 0's: one contiguous block, which overlaps itself when H > T
+                H = F.shape[0] - T
+                F[:H].copy_(F[T:].clone() if H > T else F[T:])
             self.step = 0
         t = self.step
-        a.obs_out = self.observations.data_ptr() + (t + 1) * self.observations.stride(0) * 4
+        a.obs_out = None if self.observations is None else self.observations.data_ptr() + (t + 1) * self.observations.stride(0) * 4
         a.reward_out = self.rewards.data_ptr() + t * self.rewards.stride(0) * 4
         a.done_out = self.dones.data_ptr() + t * self.dones.stride(0)
         for w in self._group_writers:
@@ -254,16 +329,75 @@ class RolloutStorage:
 
     def write(self, obs: torch.Tensor, reward: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor) -> None:
         """One transition through ``gf_rollout_write`` (the phase-by-phase path; a recorded step fuses it, _trace.py)."""
-        if not obs.is_contiguous():   # (an ObservationManager switched to output="window" after this storage was made)
-            raise ValueError("RolloutStorage copies contiguous observation rows: the observation it follows is a strided view (output='window')")
         a = self._args
-        a.obs, a.reward = obs.data_ptr(), reward.data_ptr()
+        if self.observations is None:   # (the observation is frame-stored: this launch writes the reward and done rows only)
+            a.obs = None
+        elif not obs.is_contiguous():   # (an ObservationManager switched to output="window" after this storage was made)
+            raise ValueError("RolloutStorage copies contiguous observation rows: the observation it follows is a strided view (output='window')")
+        else:
+            a.obs = obs.data_ptr()
+        a.reward = reward.data_ptr()
         a.terminated, a.truncated = terminated.data_ptr(), truncated.data_ptr()
         self._next_rows(a)
         self._keep = (obs, reward, terminated, truncated)
         self.env.backend.call("rollout_write", a, owner=self)
         for w in self._group_writers:   # (behind the storage's own launch: a recorded step advances the rows in that order)
             w.write(self.env.backend)
+        if self._frame_parts:
+            self._write_frames()
+
+    def _write_frames(self) -> None:
+        """The newest frame of every frame-stored manager into ``frames[step - 1 + H]``: one ``gf_rollout_frame_write`` per four of
+        them, right behind the step's ``rollout_write`` (a recorded step calls this after its launches are enqueued, _trace.py) — or the
+        same copy in torch on a backend without the entry point (the test-only oracle backend)."""
+        t = self.step - 1
+        fn = getattr(self.env.backend, "rollout_frame_write", None)
+        keep = []
+        for fa, oms in self._frame_parts:
+            for seg, m in zip(fa.segs, oms):
+                out = m._last_out
+                if self._frame_checked.get(m.name) != m._output:   # (once, and again after the manager's output mode was switched)
+                    self._check_frame_source(m, out)
+                if fn is None:
+                    F = self.frames[m.name]
+                    F[t + m._history_len].copy_(out[:, :F.shape[2]])
+                    continue
+                base, step = self._frame_dst[m.name]
+                seg.src, seg.src_stride, seg.dst = out.data_ptr(), out.stride(0), base + t * step
+                keep.append(out)
+            if fn is not None:
+                fn(fa)
+        self._keep_frames = keep
+
+    def _check_frame_source(self, m, out: torch.Tensor) -> None:
+        """What a manager's tensors are in one output mode: checked when the mode is first seen, not on every step."""
+        F = self.frames[m.name]
+        n, H, O = self.env.num_envs, m._history_len, F.shape[2]
+        if m._output == "ring":   # (switched after this storage was made)
+            raise ValueError(f"RolloutStorage(history='frames'): ObservationManager '{m.name}' has output='ring', which is ordered by slot")
+        if (out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (n, H * O) or out.device != F.device
+                or (out.stride(1) != 1 and H * O > 1) or out.stride(0) < O):
+            raise ValueError(f"RolloutStorage(history='frames'): the observation of '{m.name}' is not a float32 [{n}, {H * O}] tensor with unit column stride")
+        self._frame_checked[m.name] = m._output
+
+    def observation_rows(self, name: Optional[str] = None, t: Optional[int] = None) -> torch.Tensor:
+        """The observation rows of manager ``name`` (``None``: ``obs_name``) as rsl_rl keeps them: a new ``[T+1, N, W]`` tensor, or the
+        ``[N, W]`` of row ``t`` — for a frame-stored manager built from its frames with torch indexing (newest frame first).  For
+        inspecting a rollout and for tests: it allocates; the minibatch gather reads the frames themselves."""
+        name = self.obs_name if name is None else name
+        T = self.num_steps
+        if t is not None and not 0 <= int(t) <= T:
+            raise ValueError(f"row {t} is outside 0 … {T}")
+        F = self.frames.get(name)
+        if F is None:
+            rows = self.observations if name == self.obs_name else self.group_rows.get(name)
+            if rows is None:
+                raise ValueError(f"the storage follows no ObservationManager named '{name}'")
+            return rows.clone() if t is None else rows[int(t)].clone()
+        H = F.shape[0] - T
+        if t is None:
+            return torch.cat([F[H - 1 - j:H + T - j] for j in range(H)], dim=-1)
+        return torch.cat([F[int(t) + H - 1 - j] for j in range(H)], dim=-1)
 
     # -- the policy's half of a transition, returns ---------------------------------------------------------------------------
     def _ensure_policy_rows(self, num_actions: int) -> None:
@@ -321,7 +455,7 @@ class RolloutStorage:
         global env id, column) — the stream advances once per call, the env's own stream is never touched.
         ``noise``: ``[N, A]`` standard normals used instead of the draws (parity tests; the only mode of the CPU oracle backend).
         Inputs must be float32, contiguous and on the storage's device: nothing is cast (``ValueError``)."""
-        n, dev = self.env.num_envs, self.observations.device
+        n, dev = self.env.num_envs, self.device
         if not isinstance(mean, torch.Tensor) or mean.dim() != 2 or mean.shape[0] != n or mean.shape[1] < 1:
             raise ValueError(f"mean must be a [{n}, A] tensor")
         A = int(mean.shape[1])
@@ -362,7 +496,8 @@ class RolloutStorage:
         noise stream and seed, and the input rules are ``act``'s: a loop that replaces ``store.act(policy.act_mean(obs), policy.std,
         policy.evaluate(obs))`` by ``store.act_policy(fwd, obs)`` draws the same noise.  ``obs`` / ``critic_obs``: a ``[N, W]`` tensor
         or a sequence of up to four (the members of an observation group side by side — no ``torch.cat``); ``critic_obs=None``: the
-        critic reads ``obs``.  The mean and the value are k-ascending f32 fma chains (``gf_step.h``), not torch's GEMM bits: within
+        critic reads ``obs``.  The strided view of an ``output="window"`` ObservationManager is read in place (``row_stride``); any other
+        non-contiguous tensor is refused.  The mean and the value are k-ascending f32 fma chains (``gf_step.h``), not torch's GEMM bits: within
         f32 rounding of ``policy.act_mean`` / ``evaluate``, and the same for a row whatever ``num_envs`` is.  A policy with observation
         normalisers (:class:`EmpiricalNormalization`) has them applied inside the same launch, to the raw ``obs`` / ``critic_obs``.
         Measured per collection step (profiles/r09_mlp_act.md): 3.5 x faster than ``act()`` on torch's forward at 4 096 envs, 1.4 x
@@ -371,10 +506,10 @@ class RolloutStorage:
         ``noise`` is required."""
         if not isinstance(forward, PolicyForward):
             raise ValueError("act_policy(forward, ...) takes a PolicyForward")
-        n, dev = self.env.num_envs, self.observations.device
+        n, dev = self.env.num_envs, self.device
         if forward.actor is None or forward.critic is None or forward.num_actions is None:
             raise ValueError("act_policy needs a policy with an actor, a critic and a [A] std")
-        segs = forward._segments(obs, forward.actor, "obs", n, dev)
+        segs = forward._segments(obs, forward.actor, "obs", n, dev)   # (a window-mode manager's strided view is read in place)
         csegs = forward._segments(obs if critic_obs is None else critic_obs, forward.critic, "obs (the critic's input)" if critic_obs is None else "critic_obs", n, dev)
         A = forward.num_actions
         std = forward.policy.std
@@ -431,7 +566,7 @@ class RolloutStorage:
         t = self.step - 1
         if self._pol_serial != self._serial:
             raise RuntimeError(f"process_env_step() needs the policy rows of transition {t}: call act() before env.step() or add_policy() after it")
-        n, dev = self.env.num_envs, self.observations.device
+        n, dev = self.env.num_envs, self.device
         if time_outs is not None:
             if self._boot_serial == self._serial:
                 raise RuntimeError(f"the rewards of transition {t} are already bootstrapped (add_policy(time_outs=...) or process_env_step)")
@@ -504,7 +639,7 @@ class RolloutStorage:
         mb = (T * n) // num_mini_batches
         if mb < 1:
             raise ValueError(f"{T * n} transitions cannot fill {num_mini_batches} minibatches")
-        width = lambda group: sum(self.group_rows[m].shape[2] for m in self.obs_groups[group])
+        width = lambda group: sum(self._widths[m] for m in self.obs_groups[group])
         norms = (_as_normalizer(obs_normalizer, width("policy"), "obs_normalizer"),
                  _as_normalizer(critic_obs_normalizer, width("critic"), "critic_obs_normalizer"))
         indices = torch.randperm(num_mini_batches * mb, device=gs.device, generator=generator)
@@ -516,11 +651,14 @@ class RolloutStorage:
                 yield self._gather(indices[i * mb:(i + 1) * mb], *norms)
 
     def _flat(self) -> dict:
-        """Every stored array as its ``[T·N, w]`` source rows (views)."""
+        """Every stored array as its ``[T·N, w]`` source rows (views); a frame-stored manager as its ``[(T+H)·N, O]`` frames, of which
+        row ``t·N + n`` is the OLDEST frame of observation row ``t`` (its newer frames lie multiples of N rows further on)."""
         T, n = self.num_steps, self.env.num_envs
         rows = {name: r[:T].view(T * n, r.shape[2]) for name, r in self.group_rows.items()}
-        if self.obs_name not in rows:
+        if self.obs_name not in rows and self.observations is not None:
             rows[self.obs_name] = self.observations[:T].view(T * n, self.obs_width)
+        for name, F in self.frames.items():
+            rows[name] = F.view(F.shape[0] * n, F.shape[2])
         per = {k: getattr(self, k).flatten(0, 1) for k in _MB_FIELDS}   # ([T·N] or [T·N, A])
         return rows, per
 
@@ -529,7 +667,11 @@ class RolloutStorage:
         policy, critic = self.obs_groups["policy"], self.obs_groups["critic"]
         same = list(critic) == list(policy) and critic_norm is obs_norm
         gather = getattr(self.env.backend, "minibatch_gather", None)
-        if gather is None:   # (the test-only oracle backend) rsl_rl's expression itself
+        if gather is None:   # (the test-only oracle backend) rsl_rl's expression itself, on the materialised rows of a frame-stored manager
+            T, n = self.num_steps, self.env.num_envs
+            for k in self.frames:
+                rows[k] = self.observation_rows(k)[:T].reshape(T * n, self._widths[k])
+
             def cat(names, norm):
                 x = rows[names[0]][idx] if len(names) == 1 else torch.cat([rows[m][idx] for m in names], dim=-1)
                 if norm is None:
@@ -540,16 +682,17 @@ class RolloutStorage:
             obs = cat(policy, obs_norm)
             return MiniBatch(obs, obs if same else cat(critic, critic_norm), *(per[k][idx] for k in _MB_FIELDS), idx)
         m = idx.shape[0]
-        dev = self.observations.device
+        dev = self.device
         empty = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
-        fields = []   # (source rows [T·N, w], destination, its width, first column, the group's normaliser or None)
+        fields = []   # (source rows [T·N, w] or frames, destination, its width, first column, the group's normaliser or None, H or 0)
+        frames, widths = self.frames, self._widths
 
         def group(names, norm):
-            w = sum(rows[k].shape[1] for k in names)
+            w = sum(widths[k] for k in names)
             out, col = empty(m, w), 0
             for k in names:
-                fields.append((rows[k], out, w, col, norm))
-                col += rows[k].shape[1]
+                fields.append((rows[k], out, w, col, norm, frames[k].shape[0] - self.num_steps if k in frames else 0))
+                col += widths[k]
             return out
 
         obs = group(policy, obs_norm)
@@ -558,14 +701,16 @@ class RolloutStorage:
         for k in _MB_FIELDS:
             src = per[k]
             outs.append(empty(m, *src.shape[1:]))
-            fields.append((src, outs[-1], src.shape[1] if src.dim() == 2 else 1, 0, None))
+            fields.append((src, outs[-1], src.shape[1] if src.dim() == 2 else 1, 0, None, 0))
         a = self._mb_args
         a.num_rows, a.num_src_rows, a.indices = m, self.num_steps * self.env.num_envs, idx.data_ptr()
         for at in range(0, len(fields), nat.GF_MINIBATCH_MAX_FIELDS):   # (more members than one launch holds: a further launch)
             part = fields[at:at + nat.GF_MINIBATCH_MAX_FIELDS]
             a.num_fields = len(part)
-            for f, (src, dst, w, col, norm) in zip(a.fields, part):
+            for f, (src, dst, w, col, norm, H) in zip(a.fields, part):
                 f.src, f.dst, f.src_width, f.dst_width, f.dst_col = src.data_ptr(), dst.data_ptr(), src.numel() // src.shape[0], w, col
+                if frames:   # (a history field is rebuilt from its H frames; a row storage leaves the two words zero: plain fields)
+                    f.history_len, f.frame_stride_rows = H, self.env.num_envs if H else 0
                 if norm is not None:   # (the member's slice of the group's normaliser)
                     f.mean, f.std, f.eps = norm._mean.data_ptr() + 4 * col, norm._std.data_ptr() + 4 * col, norm.eps
                 elif self._mb_normed:
@@ -582,6 +727,9 @@ class RolloutStorage:
         """Recorded step: advance the rows.  ``via_unroll`` = the policy ObservationManager when it keeps its history as a ring and
         the step is fused: the fused launch only holds the new frame, so the observation row is written by the manager's gather
         (second destination of gf_history_unroll) and the fused launch gets no observation row."""
+        if self.observations is None:   # (frame-stored: no observation row, from the launch or from the gather)
+            via_unroll = None
+
         def patch(_actions, a=args, self=self, om=via_unroll):
             self._next_rows(a)
             if om is not None:
@@ -593,6 +741,9 @@ class RolloutStorage:
         """`obs` follows the tensor the observation launch (or the gather of a ring-kept history) writes this step — that
         manager's rotation comes earlier in the table."""
         P = nat.GfReplayPatch
+        if self.observations is None:   # frame-stored: the launch stores no observation row (obs_out stays NULL), `obs` is not read
+            args.obs = None
+            return []
         if getattr(pol, "_window", False):
             from ._trace import Untraceable
             raise Untraceable("the rollout rows of a window-mode observation (a strided view) cannot be copied by the step's launch")
@@ -713,8 +864,8 @@ class EpisodeStatistics:
 
 
 def _obs_segments(x, width: int, name: str, device) -> tuple:
-    """``x`` as the tuple of ``[N, w]`` float32 contiguous segments, ``width`` wide together, a normaliser reads side by side (``act``'s
-    rules: nothing is cast)."""
+    """``x`` as the tuple of ``[N, w]`` float32 segments, ``width`` wide together, a normaliser reads side by side (``act``'s rules:
+    nothing is cast) — contiguous, or the strided view a window-mode ObservationManager handed out (``_rows_ok``)."""
     parts = (x,) if isinstance(x, torch.Tensor) else tuple(x) if isinstance(x, (list, tuple)) else None
     if not parts or len(parts) > nat.GF_MLP_MAX_INPUTS:
         raise ValueError(f"{name} must be a tensor or a sequence of 1 to {nat.GF_MLP_MAX_INPUTS} tensors")
@@ -723,11 +874,11 @@ def _obs_segments(x, width: int, name: str, device) -> tuple:
         what = f"{name}[{i}]" if len(parts) > 1 else name
         if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] < 1:
             raise ValueError(f"{what} must be a [N, W] tensor")
-        if not t.is_contiguous():
-            raise ValueError(f"EmpiricalNormalization reads contiguous observation rows: {what} is a strided view (an ObservationManager "
-                             "with output='window' hands one out) — use output='fresh' / 'static' for the managers it follows")
+        if not _rows_ok(t):
+            raise ValueError(f"EmpiricalNormalization reads contiguous observation rows: {what} is a strided view (only the window an "
+                             "ObservationManager with output='window' hands out is read in place)")
         n = int(t.shape[0]) if n is None else n
-        _check_f32(t, what, {(n, int(t.shape[1]))}, device)
+        _check_f32(t, what, {(n, int(t.shape[1]))}, device, window=True)
     if sum(int(t.shape[1]) for t in parts) != width:
         raise ValueError(f"{name} is {' + '.join(str(int(t.shape[1])) for t in parts)} wide; the normaliser keeps {width} columns")
     return parts
@@ -754,7 +905,8 @@ class EmpiricalNormalization(torch.nn.Module):
     scalar), so its checkpoints load.  ``until``: no update once ``count >= until``.
 
     ``update(x)`` takes a ``[N, W]`` tensor or a sequence of up to four segments side by side (an observation group's members, no
-    ``torch.cat``); float32, contiguous, on the buffers' device — nothing is cast.  No-op in eval mode.  On the HIP backend it is one
+    ``torch.cat``); float32, contiguous (or the strided view a window-mode ObservationManager handed out, read in place), on the buffers'
+    device — nothing is cast.  No-op in eval mode.  On the HIP backend it is one
     ``gf_obs_norm_update`` (two launches) that writes the buffers in place and never reads the device from the host, the ``until``
     test included; the batch moments and the update are evaluated in float64 and rounded to float32 once, so the buffers agree with
     rsl_rl's float32 lines to rounding, not bit for bit.  For CPU tensors, or on a backend without the entry point (the test-only CPU
@@ -819,7 +971,7 @@ class EmpiricalNormalization(torch.nn.Module):
                 raise ValueError("EmpiricalNormalization: the kernel updates float32 contiguous buffers in place")
         st.num_inputs = len(parts)
         for seg, t in zip(st.inputs, parts):
-            seg.rows, seg.width = t.data_ptr(), t.shape[1]
+            seg.rows, seg.width, seg.row_stride = t.data_ptr(), t.shape[1], 0 if t.is_contiguous() else t.stride(0)
         st.mean, st.var, st.std, st.count = self._mean.data_ptr(), self._var.data_ptr(), self._std.data_ptr(), self.count.data_ptr()
         st.until = -1 if self.until is None else int(self.until)
         st.workspace, st.workspace_bytes = ws.data_ptr(), ws.numel() * 8
@@ -1006,7 +1158,8 @@ class PolicyForward:
 
     @staticmethod
     def _segments(obs, layers, name: str, n: Optional[int], dev) -> tuple:
-        """``obs`` as the tuple of ``[n, w]`` float32 contiguous segments the first layer of ``layers`` reads side by side."""
+        """``obs`` as the tuple of ``[n, w]`` float32 segments the first layer of ``layers`` reads side by side — contiguous, or the
+        strided view a window-mode ObservationManager handed out (``_rows_ok``)."""
         parts = (obs,) if isinstance(obs, torch.Tensor) else tuple(obs) if isinstance(obs, (list, tuple)) else None
         if not parts or len(parts) > nat.GF_MLP_MAX_INPUTS:
             raise ValueError(f"{name} must be a tensor or a sequence of 1 to {nat.GF_MLP_MAX_INPUTS} tensors")
@@ -1015,7 +1168,7 @@ class PolicyForward:
                 raise ValueError(f"{name}[{i}] must be a [N, W] tensor" if len(parts) > 1 else f"{name} must be a [N, W] tensor")
             if n is None:
                 n, dev = int(x.shape[0]), x.device
-            _check_f32(x, f"{name}[{i}]" if len(parts) > 1 else name, {(n, int(x.shape[1]))}, dev)
+            _check_f32(x, f"{name}[{i}]" if len(parts) > 1 else name, {(n, int(x.shape[1]))}, dev, window=True)
         want = int(layers[0][0].shape[1])
         if sum(int(x.shape[1]) for x in parts) != want:
             raise ValueError(f"{name} is {' + '.join(str(int(x.shape[1])) for x in parts)} wide; the first layer reads {want}")
@@ -1037,7 +1190,7 @@ class PolicyForward:
             net.in_mean, net.in_std, net.in_eps = norm._mean.data_ptr(), norm._std.data_ptr(), norm.eps
         net.num_layers, net.num_inputs = len(layers), len(parts)
         for seg, x in zip(net.inputs, parts):
-            seg.rows, seg.width = x.data_ptr(), x.shape[1]
+            seg.rows, seg.width, seg.row_stride = x.data_ptr(), x.shape[1], 0 if x.is_contiguous() else x.stride(0)
         for lay, (w, b) in zip(net.layers, layers):
             lay.weight, lay.bias, lay.out_width = w.data_ptr(), b.data_ptr(), w.shape[0]
 

@@ -37,9 +37,12 @@ persistent ``[N, S + H - 1, O]`` buffer (``S = H + window_slack`` slots are cycl
 the first ``H - 1`` so that a window never wraps), a call writes only the new frame and returns ``H`` consecutive slots of it as an
 ``[N, H*O]`` strided VIEW — newest frame first, exactly the reference's concatenation, no gather and no copy (``O`` floats per env and
 call, plus ``2(H-1)·O / S`` for the mirror copy once per cycle; rows are contiguous, the row stride is ``(S + H - 1)·O``, which
-``torch.nn.functional.linear`` and ``copy_`` take as they are).  The contract: a returned tensor stays intact for ``window_slack + 1``
-further observations of this manager (default ``H + 1``: enough for an RL loop that stores ``obs_t`` after ``step t + 1``, as rsl_rl's
-does), then its oldest frames are overwritten; it is read-only for the caller.
+``torch.nn.functional.linear`` and ``copy_`` take as they are).  The contract: a returned tensor stays intact for ``window_slack``
+further observations of this manager (default ``H``: enough for an RL loop that stores ``obs_t`` after ``step t + 1``, as rsl_rl's
+does) — the one after those may overwrite its oldest frame; it is read-only for the caller.  ``learner.RolloutStorage(history="frames")``
+and the learner's kernels read the view within the step that returned it.  The learner (``act_policy``, ``PolicyForward``,
+``EmpiricalNormalization.update`` / ``update_normalization``) reads in place only the very tensor object handed out — the manager marks
+it — not a slice, ``detach()`` or other new view of it: those are strided tensors like any other and are refused.
 """
 from __future__ import annotations
 
@@ -83,7 +86,7 @@ class ObservationManager(BaseManager):
     #: how a history of H > 1 frames becomes the [N, H*O] tensor in the "fresh" / "static" modes: "shift", "unroll" or "auto"
     default_history = os.environ.get("GF_OBS_HISTORY", "auto")
     static_slots = _OBS_RING
-    #: output="window": further observations a returned tensor survives, minus one (None: history_len)
+    #: output="window": further observations a returned tensor survives (None: history_len)
     window_slack: Optional[int] = None
 
     """Generates an observation tensor from a dict of items (ctor as observation_manager.py:134-156)."""
@@ -386,7 +389,9 @@ class ObservationManager(BaseManager):
     def _window_at(self, slot: int) -> torch.Tensor:
         """H consecutive frame slots from ``slot`` on, as the reference's [N, H*O] newest-first tensor (a strided view)."""
         O = self._frame
-        return torch.as_strided(self._win, (self._win.shape[0], self._history_len * O), (self._win_slots * O, 1), slot * O)
+        view = torch.as_strided(self._win, (self._win.shape[0], self._history_len * O), (self._win_slots * O, 1), slot * O)
+        view._gf_window = True   # (the learner's kernels read this view in place — and no other strided tensor: learner._rows_ok)
+        return view
 
     def _mirror_tail(self) -> None:
         """The slot walk wraps from 0 to S - 1: the newest H - 1 frames (slots 0 … H-2) are copied behind slot S - 1, so that the

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 8
+#define GF_ABI_VERSION 9
 
 #define GF_MAX_TERMS 24          /* reward terms per manager          */
 #define GF_MAX_TERM_TERMS 16     /* termination terms per manager     */
@@ -605,6 +605,37 @@ typedef struct GfRolloutArgs {
 } GfRolloutArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * The newest frame of a history observation into a frame-major rollout storage (learner.RolloutStorage(history="frames")).
+ * The reference's observation history is a pure sliding window (observation_manager.py:218-226: pop, insert(0, obs), cat — never
+ * cleared per env, untouched by a reset), so the [N, H·O] row a step returns is frames t, t-1 … t-H+1 and a storage that keeps
+ * every FRAME once — frames [T + H, N, O] — holds every row: observation row r is frames r … r+H-1, frame r+H-1 the newest.
+ * A step then stores O floats per env instead of H·O.  gf_rollout_frame_write copies, for up to GF_ROLLOUT_FRAME_MAX managers in
+ * ONE launch,
+ *     segs[s].dst[n * width + c] = segs[s].src[n * src_stride + c]        (n < num_envs, c < width)
+ * `src` is the tensor the step returned (newest frame first: columns 0 … O-1), `src_stride` its row stride in floats — H·O for a
+ * contiguous row, the slot stride of an output="window" view.  Chunks of 16, 8 or 4 bytes, chosen per segment from the alignment of
+ * src, dst, width and src_stride.  Pure copy.  Algorithmic traffic: R 4·O, W 4·O bytes per env and segment.
+ * Refusals, before anything is launched: GF_E_NULL — args, a src / dst pointer; GF_E_RANGE — num_envs < 0, num_segs outside
+ * 1 … GF_ROLLOUT_FRAME_MAX, width < 1, src_stride < width.  num_envs == 0 is a no-op.  Not a phase of the step: it never enters a
+ * recorded step's op table (the storage issues it right behind the step's gf_rollout_write).
+ * ---------------------------------------------------------------------------------------- */
+#define GF_ROLLOUT_FRAME_MAX 4
+
+typedef struct GfRolloutFrameSeg {
+    const float* src;           /* [N, >= width] rows src_stride floats apart: the newest frame is columns 0 … width-1 */
+    float* dst;                 /* [N, width] contiguous: &frames[t + H][0][0] */
+    int32_t width;              /* O >= 1 */
+    int32_t src_stride;         /* >= width, in floats */
+} GfRolloutFrameSeg;
+
+typedef struct GfRolloutFrameArgs {
+    int64_t num_envs;           /* N >= 0; 0: nothing is launched */
+    int32_t num_segs;           /* 1 … GF_ROLLOUT_FRAME_MAX */
+    int32_t _pad;
+    GfRolloutFrameSeg segs[GF_ROLLOUT_FRAME_MAX];
+} GfRolloutFrameArgs;
+
+/* ------------------------------------------------------------------------------------------
  * The policy's half of a transition and the return computation (remainder).  rsl_rl's OnPolicyRunner
  * (third-party; configured and called by the reference at examples/simple/train.py:37-79,125-129: PPO, gamma 0.99, lam 0.95,
  * num_steps_per_env 24) stores, besides the env's outputs, what the policy produced for the step — actions, value estimate,
@@ -692,6 +723,15 @@ typedef struct GfCompactArgs {
  * by the same launch.  `mean` / `std` are `[src_width]`; a member of a concatenated group points at its slice of the group's
  * normaliser (`norm.mean + dst_col`), so the two vectors may be less aligned than the rows: they are read by element.  Rows of
  * out-of-range indices stay quiet NaN.  Refusals: GF_E_NULL — `mean` without `std`.
+ * History field (`history_len` = H > 1; 0 or 1: the plain field above): `src` is a frame-major storage [(T + H)·N, O] (O = src_width,
+ * N = frame_stride_rows) whose row t·N + n is the OLDEST frame of observation row t of env n; the newer frames lie whole multiples
+ * of N rows further on, so no division by N is needed.  The field fills H·O destination columns, newest frame first:
+ *     dst[i * dst_width + dst_col + j * O + c] = src[(indices[i] + (H-1-j) * N) * O + c]          (j < H, c < O)
+ * The caller guarantees that `src` holds num_src_rows + (H-1)·N rows.  An out-of-range index gives quiet NaN in all H·O columns.
+ * With a normaliser, `mean` / `std` span the field's H·O columns (index j·O + c); the arithmetic per element is unchanged.  The
+ * chunk width must hold for every frame's address too: frame_stride_rows·src_width enters the alignment test (it is a multiple
+ * of the chunk whenever src_width is: O = 78 moves in 8-byte chunks for every N, O = 16 in 16-byte chunks).  Refusals: GF_E_RANGE — history_len < 0, frame_stride_rows < 1 with history_len > 1,
+ * dst_col + H·O > dst_width.
  * Not a phase of the step: it never enters a recorded step's op table.
  * ---------------------------------------------------------------------------------------- */
 #define GF_MINIBATCH_MAX_FIELDS 12
@@ -700,13 +740,13 @@ typedef struct GfMinibatchField {
     const float* src;           /* [num_src_rows, src_width] f32, row-major */
     float* dst;                 /* [num_rows, dst_width] f32, row-major */
     int32_t src_width;          /* >= 1 */
-    int32_t dst_width;          /* >= dst_col + src_width */
+    int32_t dst_width;          /* >= dst_col + max(H, 1) * src_width */
     int32_t dst_col;            /* first destination column of this field */
-    int32_t _pad;
-    const float* mean;          /* [src_width] normaliser mean, or NULL: pure copy */
-    const float* std;           /* [src_width] normaliser std (required with mean) */
+    int32_t history_len;        /* H; 0 or 1: a plain field.  > 1: `src` holds frames, the field is H * src_width columns wide */
+    const float* mean;          /* [max(H, 1) * src_width] normaliser mean, or NULL: pure copy */
+    const float* std;           /* [max(H, 1) * src_width] normaliser std (required with mean) */
     float eps;                  /* added to std */
-    int32_t _pad2;
+    int32_t frame_stride_rows;  /* N: source rows from a frame to the next newer one (read when history_len > 1; then >= 1) */
 } GfMinibatchField;
 
 typedef struct GfMinibatchArgs {
@@ -904,7 +944,8 @@ typedef struct GfAdamArgs {
  * the f32 matrix cores (v_mfma_f32_32x32x2_f32) and keeps the tile's activations in LDS; only mean, values, actions and the storage
  * rows are written to memory.  Weights are read in place, `[out, in]` row-major f32 exactly as torch.nn.Linear stores them; the first
  * layer reads its input as up to GF_MLP_MAX_INPUTS segments `[N, width]` side by side (an observation group of several managers
- * needs no torch.cat).  Layers are Linear with ELU(alpha = 1) between them and none after the last.
+ * needs no torch.cat); a segment's rows are `row_stride` floats apart (0: `width`, contiguous rows) — the strided view an
+ * ObservationManager with output="window" hands out is read in place.  Layers are Linear with ELU(alpha = 1) between them and none after the last.
  *
  * Arithmetic (the one exception to "a left fold of separately rounded operations"):
  *     y[n, j] = chain over k = 0 … K-1, ascending, of fma(x[n, k], W[j, k], acc),  acc starting from bias[j];
@@ -923,7 +964,7 @@ typedef struct GfAdamArgs {
  * Refusals, before anything is launched: GF_E_NULL — args, a weight / bias / segment pointer, in_mean without in_std, std with
  * actions, an actor without mean and actions, a critic without values and values_out, an actor's or critic's output pointer with that net absent;
  * GF_E_RANGE — num_envs < 0, more than GF_MLP_MAX_LAYERS layers, a segment count outside 1 … GF_MLP_MAX_INPUTS, a width < 1, a
- * hidden width > GF_MLP_MAX_HIDDEN, a total input width > GF_MLP_MAX_INPUT_WIDTH, an actor output > GF_MLP_MAX_ACTIONS,
+ * non-zero row_stride < width, a hidden width > GF_MLP_MAX_HIDDEN, a total input width > GF_MLP_MAX_INPUT_WIDTH, an actor output > GF_MLP_MAX_ACTIONS,
  * std_per_env outside {0, 1}; GF_E_UNSUPPORTED — both nets absent, a critic output other than 1.  num_envs == 0 is a no-op.
  * No allocation, no copy, no synchronisation inside.  Not a phase of the step.
  * ---------------------------------------------------------------------------------------- */
@@ -935,9 +976,9 @@ typedef struct GfAdamArgs {
 #define GF_MLP_TILE_ROWS 32            /* rows per workgroup */
 
 typedef struct GfMlpSegment {
-    const float* rows;          /* [N, width] contiguous */
+    const float* rows;          /* [N, width], row n at rows + n * row_stride */
     int32_t width;              /* >= 1 */
-    int32_t _pad;
+    int32_t row_stride;         /* floats from a row to the next; 0: `width` (contiguous rows); otherwise >= width */
 } GfMlpSegment;
 
 typedef struct GfMlpLayer {
@@ -983,7 +1024,7 @@ typedef struct GfMlpActArgs {
  * scripts, rsl_rl 3.x's actor_obs_normalization / critic_obs_normalization).  rsl_rl updates a normaliser with torch.mean, torch.var
  * and a handful of elementwise launches — about ten per normaliser and collection step.  gf_obs_norm_update updates up to
  * GF_OBS_NORM_MAX_SETS normalisers (the actor's and the critic's) from num_rows rows each in TWO launches.  A set reads its input as
- * up to GF_MLP_MAX_INPUTS segments `[N, width]` side by side (as gf_mlp_act: no torch.cat), total width W <= GF_MLP_MAX_INPUT_WIDTH.
+ * up to GF_MLP_MAX_INPUTS segments `[N, width]` side by side (as gf_mlp_act: no torch.cat, `row_stride` floats from row to row), total width W <= GF_MLP_MAX_INPUT_WIDTH.
  * Per set and column c, with N = num_rows:
  *     if until >= 0 and count >= until:  nothing of the set is written
  *     mx = (Σ_n x[n,c]) / N          vx = (Σ_n (x[n,c] - mx)²) / N           (biased, as torch.var(unbiased=False))
@@ -1000,8 +1041,8 @@ typedef struct GfMlpActArgs {
  * writes mean / var / std / count — the only workgroup that reads or writes `count`.  grid y = set in both launches.  No float atomics,
  * no hand-off or wait between workgroups: bitwise reproducible from run to run, and a column's result does not depend on the other set.
  * Refusals, before anything is launched: GF_E_NULL — args, a segment / mean / var / std / count / workspace pointer; GF_E_RANGE —
- * num_rows < 0, num_sets outside 1 … GF_OBS_NORM_MAX_SETS, a segment count outside 1 … GF_MLP_MAX_INPUTS, a width < 1, a total width
- * > GF_MLP_MAX_INPUT_WIDTH, a workspace smaller than GF_OBS_NORM_WORKSPACE_BYTES(num_rows, W) or not 8-byte aligned, a count pointer
+ * num_rows < 0, num_sets outside 1 … GF_OBS_NORM_MAX_SETS, a segment count outside 1 … GF_MLP_MAX_INPUTS, a width < 1, a non-zero
+ * row_stride < width, a total width > GF_MLP_MAX_INPUT_WIDTH, a workspace smaller than GF_OBS_NORM_WORKSPACE_BYTES(num_rows, W) or not 8-byte aligned, a count pointer
  * not 8-byte aligned.  num_rows == 0 is a no-op.  No allocation, no copy, no synchronisation inside.  Not a phase of the step.
  * ---------------------------------------------------------------------------------------- */
 #define GF_OBS_NORM_MAX_SETS 2         /* normalisers per call (actor, critic) */
@@ -1074,7 +1115,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -1092,6 +1133,7 @@ int gf_entity_rotate(const GfRotateArgs* a, void* stream);        /* replaces en
 int gf_terrain_height(const GfTerrainHeightArgs* a, void* stream);/* replaces terrain_manager.py:100-166 */
 int gf_synth_scene_step(const GfSynthSceneArgs* a, void* stream); /* stands in for scene.step() (managed_env.py:292) */
 int gf_rollout_write(const GfRolloutArgs* a, void* stream);       /* replaces the RolloutStorage copy_ launches of the RL library (examples/simple/train.py:125-129) */
+int gf_rollout_frame_write(const GfRolloutFrameArgs* a, void* stream);   /* the newest frame of up to four history observations into a frame-major rollout storage, one launch */
 int gf_history_unroll(const GfHistoryUnrollArgs* a, void* stream);/* replaces the torch.cat of observation_manager.py:226 */
 int gf_rollout_policy_write(const GfRolloutPolicyArgs* a, void* stream);   /* the policy's rows of a transition + time-out bootstrap (rsl_rl add_transitions; call site examples/simple/train.py:125-129) */
 int gf_done_compact(const GfCompactArgs* a, void* stream);       /* replaces the nonzero() of managed_env.py:308-310 where an index list is still needed */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One PPO collection step (Go2 ``go2_cmd``) with the actor and critic forward passes, in three forms:
+"""One PPO collection step (Go2 ``go2_cmd``, or ``--config gait``) with the actor and critic forward passes, in three forms:
 
 * ``rsl_rl``: rsl_rl's PPO.act (torch ``Normal``: sample, log_prob(...).sum(-1), mean, stddev), env.step, ``add_policy(...,
   time_outs=…)``, then OnPolicyRunner.learn's episode bookkeeping verbatim — ``nonzero()`` and two ``.cpu()`` copies per step;
@@ -16,7 +16,12 @@ and divide the kernel count by the steps run (warm-up + timed).
 env.step(), where rsl_rl's process_env_step does: the ``rsl_rl`` form runs rsl_rl's normaliser lines in torch (tests/rsl_rl_norm.py
 is the same class) around its forward, ``fused`` normalises through ``policy.act_mean`` / ``evaluate`` and updates both normalisers
 with one gf_obs_norm_update, ``fused_mlp`` normalises inside the gf_mlp_act launch as well.
-    python tools/bench_collect.py [--sizes 4096,16384,65536] [--forms rsl_rl,fused,fused_mlp] [--steps 240] [--warmup 48] [--reps 5] [--normalize]"""
+``--config gait``: the gait trainer (history_len 5, policy and critic managers, the asymmetric critic's ``obs_groups``).
+``--history frames``: ``RolloutStorage(history="frames")`` — a history observation is stored once per frame (one gf_rollout_frame_write
+launch behind the step's own); ``--output window``: the ObservationManagers hand out strided history windows (``frames`` only).
+``collector()`` builds one such loop and times batches of it, for scripts that alternate several forms in one process.
+    python tools/bench_collect.py [--sizes 4096,16384,65536] [--forms rsl_rl,fused,fused_mlp] [--steps 240] [--warmup 48] [--reps 5] [--normalize]
+                                  [--config go2_cmd|gait] [--history rows|frames] [--output fresh|window]"""
 import argparse
 import json
 import os
@@ -30,6 +35,7 @@ sys.path.insert(0, os.path.join(ROOT, "genesis-forge_amd"))
 import torch
 from genesis_forge_amd import gs, tasks
 from genesis_forge_amd.learner import ActorCriticMLP, EpisodeStatistics, PolicyForward, RolloutStorage
+from genesis_forge_amd.managers import ObservationManager
 
 T = 24   # num_steps_per_env of examples/simple/train.py
 torch.distributions.Normal.set_default_validate_args(False)   # as rsl_rl's ActorCritic.__init__ does (no per-step support checks)
@@ -61,55 +67,93 @@ class RslRlNormalizer(torch.nn.Module):
         self._std = torch.sqrt(self._var)
 
 
-def run(n: int, form: str, steps: int, warmup: int, reps: int, normalize: bool = False) -> dict:
-    env = tasks.bench_env(n)
-    env.build()
-    env.seed(1234)
-    obs, extras = env.reset()
-    A = env.action_space.shape[0]
-    store = RolloutStorage(env, T).attach()
-    store.begin(obs, extras)
+GAIT_GROUPS = {"policy": ["policy"], "critic": ["policy", "critic"]}   # obs_groups of examples/gait_trainer/train.py
+
+
+class collector:
+    """One collection loop: ``batch(steps)`` runs ``steps`` of it and returns µs per step (ending in a device synchronise)."""
+
+    def __init__(self, n: int, form: str, normalize: bool = False, config: str = "go2_cmd", history: str = "rows", output: str = "fresh"):
+        old, ObservationManager.default_output = ObservationManager.default_output, output
+        try:   # (the managers are created by env.config(), i.e. inside build())
+            env = tasks.BASELINE_CONFIGS[config][1](n)
+            env.build()
+        finally:
+            ObservationManager.default_output = old
+        env.seed(1234)
+        self.env, self.form, self.state = env, form, env.reset()
+        self.store = RolloutStorage(env, T, obs_groups=GAIT_GROUPS if config == "gait" else None, history=history).attach()
+        self.store.begin(*self.state)
+        self.step, self.stats, self.rewbuffer = _make_step(env, self.store, form, normalize)
+
+    def batch(self, steps: int) -> float:
+        obs, extras = self.state
+        with torch.no_grad():
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                obs, extras = self.step(obs, extras)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+        self.state = (obs, extras)
+        return dt / steps * 1e6
+
+    def mean_reward(self):
+        if self.stats is not None:
+            return self.stats.mean_reward()
+        return statistics.mean(self.rewbuffer) if self.rewbuffer else None
+
+
+def _make_step(env, store, form: str, normalize: bool):
+    n, A = env.num_envs, env.action_space.shape[0]
+    width = {m.name: int(m.observation_space.shape[0]) for m in env.managers["observation"]}
+    critic = store.obs_groups["critic"]
+    same = critic == store.obs_groups["policy"]
+    critic_w = sum(width[m] for m in critic)
+    parts = (lambda obs, extras: obs) if same else (lambda obs, extras: tuple(extras["observations"][m] for m in critic))
+    cat = (lambda obs, extras: obs) if same else (lambda obs, extras: torch.cat([extras["observations"][m] for m in critic], dim=-1))
     torch.manual_seed(0)
     fused_norm = normalize and form != "rsl_rl"
-    policy = ActorCriticMLP(store.obs_width, A, actor_obs_normalization=fused_norm, critic_obs_normalization=fused_norm).to(gs.device)
+    policy = ActorCriticMLP(store.obs_width, A, num_critic_obs=critic_w, actor_obs_normalization=fused_norm,
+                            critic_obs_normalization=fused_norm).to(gs.device)
     gamma = 0.99
+    stats, rewbuffer = None, None
     if form == "fused":
         stats = EpisodeStatistics(n)
 
-        def step(obs):
-            actions = store.act(policy.act_mean(obs), policy.std, policy.evaluate(obs))
-            obs, _rew, _term, trunc, _ = env.step(actions)
+        def step(obs, extras):
+            actions = store.act(policy.act_mean(obs), policy.std, policy.evaluate(cat(obs, extras)))
+            obs, _rew, _term, trunc, extras = env.step(actions)
             if normalize:
-                policy.update_normalization(obs)
+                policy.update_normalization(obs, parts(obs, extras))
             store.process_env_step(trunc, gamma=gamma, episodes=stats)
-            return obs
+            return obs, extras
     elif form == "fused_mlp":
         stats = EpisodeStatistics(n)
         fwd = PolicyForward(policy)
 
-        def step(obs):
-            actions = store.act_policy(fwd, obs)
-            obs, _rew, _term, trunc, _ = env.step(actions)
+        def step(obs, extras):
+            actions = store.act_policy(fwd, obs, critic_obs=parts(obs, extras))
+            obs, _rew, _term, trunc, extras = env.step(actions)
             if normalize:
-                policy.update_normalization(obs)
+                policy.update_normalization(obs, parts(obs, extras))
             store.process_env_step(trunc, gamma=gamma, episodes=stats)
-            return obs
+            return obs, extras
     else:
         cur_reward_sum = torch.zeros(n, device=gs.device)
         cur_episode_length = torch.zeros(n, device=gs.device)
         rewbuffer, lenbuffer = deque(maxlen=100), deque(maxlen=100)
         actor_norm = RslRlNormalizer(store.obs_width).to(gs.device) if normalize else (lambda x: x)
-        critic_norm = RslRlNormalizer(store.obs_width).to(gs.device) if normalize else (lambda x: x)
+        critic_norm = RslRlNormalizer(critic_w).to(gs.device) if normalize else (lambda x: x)
 
-        def step(obs):
-            mean, values = policy.act_mean(actor_norm(obs)), policy.evaluate(critic_norm(obs))
+        def step(obs, extras):
+            mean, values = policy.act_mean(actor_norm(obs)), policy.evaluate(critic_norm(cat(obs, extras)))
             dist = torch.distributions.Normal(mean, policy.std.expand_as(mean))   # rsl_rl ActorCritic.update_distribution
             actions = dist.sample()
             log_prob = dist.log_prob(actions).sum(dim=-1)
-            obs, rew, term, trunc, _ = env.step(actions)
+            obs, rew, term, trunc, extras = env.step(actions)
             if normalize:   # rsl_rl PPO.process_env_step: policy.update_normalization(obs)
                 actor_norm.update(obs)
-                critic_norm.update(obs)
+                critic_norm.update(cat(obs, extras))
             store.add_policy(actions, values, log_prob, dist.mean, dist.stddev, time_outs=trunc, gamma=gamma)
             dones = term | trunc
             cur_reward_sum.add_(rew)   # OnPolicyRunner.learn
@@ -119,27 +163,22 @@ def run(n: int, form: str, steps: int, warmup: int, reps: int, normalize: bool =
             lenbuffer.extend(cur_episode_length[new_ids][:, 0].cpu().numpy().tolist())
             cur_reward_sum[new_ids] = 0
             cur_episode_length[new_ids] = 0
-            return obs
+            return obs, extras
 
-    times = []
-    with torch.no_grad():
-        for _ in range(warmup):
-            obs = step(obs)
-        torch.cuda.synchronize()
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                obs = step(obs)
-            torch.cuda.synchronize()
-            times.append((time.perf_counter() - t0) / steps * 1e6)
-    out = {"tool": "bench_collect", "config": "go2_cmd", "num_envs": n, "form": form, "normalize": normalize, "steps": steps, "warmup": warmup, "reps": reps,
+    return step, stats, rewbuffer
+
+
+def run(n: int, form: str, steps: int, warmup: int, reps: int, normalize: bool = False, config: str = "go2_cmd", history: str = "rows",
+        output: str = "fresh") -> dict:
+    c = collector(n, form, normalize, config, history, output)
+    if warmup:
+        c.batch(warmup)
+    times = [c.batch(steps) for _ in range(reps)]
+    out = {"tool": "bench_collect", "config": config, "history": history, "output": output, "num_envs": n, "form": form, "normalize": normalize,
+           "steps": steps, "warmup": warmup, "reps": reps,
            "us_per_step_best": round(min(times), 2), "us_per_step_median": round(statistics.median(times), 2),
-           "recorded_step": env._trace is not None}
-    if form in ("fused", "fused_mlp"):
-        out["mean_reward"] = stats.mean_reward()
-    else:
-        out["mean_reward"] = statistics.mean(rewbuffer) if rewbuffer else None
-    store.detach()
+           "recorded_step": c.env._trace is not None, "mean_reward": c.mean_reward()}
+    c.store.detach()
     return out
 
 
@@ -151,7 +190,12 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=48)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--normalize", action="store_true", help="empirical observation normalisation on the actor and the critic")
+    ap.add_argument("--config", default="go2_cmd", choices=["go2_cmd", "gait"], help="the task: bench.py's Go2 config or the gait trainer")
+    ap.add_argument("--history", default="rows", choices=["rows", "frames"], help="RolloutStorage(history=): rows, or one entry per frame")
+    ap.add_argument("--output", default="fresh", choices=["fresh", "window"], help="what the ObservationManagers hand out")
     a = ap.parse_args()
+    if a.output == "window" and a.history != "frames":
+        raise SystemExit("--output window needs --history frames: a row storage copies contiguous observation rows")
     if not torch.cuda.is_available():
         raise SystemExit("bench_collect.py times the collection loop on a ROCm GPU: no device visible")
     gs.set_device("cuda:0")
@@ -159,7 +203,7 @@ def main() -> None:
         for form in a.forms.split(","):
             if form not in ("rsl_rl", "fused", "fused_mlp"):
                 raise SystemExit(f"unknown form {form!r}")
-            print(json.dumps(run(n, form, a.steps, a.warmup, a.reps, a.normalize)), flush=True)
+            print(json.dumps(run(n, form, a.steps, a.warmup, a.reps, a.normalize, a.config, a.history, a.output)), flush=True)
 
 
 if __name__ == "__main__":

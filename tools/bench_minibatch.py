@@ -1,10 +1,13 @@
 """PPO minibatches of a filled RolloutStorage: one gf_minibatch_gather launch per minibatch against rsl_rl's per-field torch indexing.
 
 usage: python tools/bench_minibatch.py --num-envs 65536 --steps 24 --mini-batches 4 [--obs-width 48] [--critic-width 0]
-                                       [--num-actions 12] [--epochs 5] [--repeats 20]
+                                       [--num-actions 12] [--epochs 5] [--repeats 20] [--history-len 1] [--history rows|frames]
 
 The storage is filled with random rows; no env is stepped (only the buffers matter).  ``--critic-width W`` adds a second
 observation-group member of W floats and the gait trainer's groups ({"policy": ["policy"], "critic": ["policy", "critic"]}).
+``--history-len H --history frames``: the observations are histories of H frames (the widths are the rows': H·O, the gait trainer's
+are 390 and 80 with H = 5) kept once per frame — ``RolloutStorage(history="frames")`` — and the gather rebuilds the rows from
+synthetic frames; ``--history rows`` gathers the same minibatches from stored rows.  The torch path indexes materialised rows either way.
 Both paths are timed with HIP events over ``--repeats`` generator calls of ``--epochs`` epochs (after one warm-up call) and
 checked equal bit for bit.  Prints one JSON line: µs per minibatch of each path, the bytes one minibatch moves (the gathered
 rows read + written, plus the indices) and that over each path's time as a fraction of 8 TB/s."""
@@ -26,18 +29,19 @@ class _Obs(SimpleNamespace):
     """What RolloutStorage reads of an ObservationManager when no step runs."""
 
 
-def storage(n, T, obs_w, critic_w, A):
+def storage(n, T, obs_w, critic_w, A, history_len=1, history="rows"):
     from genesis_forge_amd import _native as nat
     from genesis_forge_amd.learner import RolloutStorage
 
-    mk = lambda name, w: _Obs(name=name, observation_space=SimpleNamespace(shape=(w,)), output="fresh", _history_len=1, _unrolled=False)
+    mk = lambda name, w: _Obs(name=name, observation_space=SimpleNamespace(shape=(w,)), output="fresh", _history_len=history_len, _unrolled=False)
     mgrs = [mk("policy", obs_w)] + ([mk("critic", critic_w)] if critic_w else [])
     env = SimpleNamespace(num_envs=n, managers={"observation": mgrs}, backend=nat.get_backend())
     groups = {"policy": ["policy"], "critic": ["policy", "critic"]} if critic_w else None
-    st = RolloutStorage(env, T, obs_groups=groups)
+    st = RolloutStorage(env, T, obs_groups=groups, history=history)
     st._ensure_policy_rows(A)
     g = torch.Generator(device="cuda").manual_seed(0)
-    for t in [st.observations, *st.group_rows.values(), st.actions, st.values, st.advantages, st.returns, st.actions_log_prob, st.mu, st.sigma]:
+    obs = [] if st.observations is None else [st.observations]
+    for t in [*obs, *st.group_rows.values(), *st.frames.values(), st.actions, st.values, st.advantages, st.returns, st.actions_log_prob, st.mu, st.sigma]:
         t.copy_(torch.randn(t.shape, device="cuda", generator=g))
     st._returns_ready = True
     return st
@@ -47,7 +51,8 @@ def torch_sources(st):
     """rsl_rl's flattened [T·N, …] arrays.  Its storage keeps the critic input as one buffer (privileged_observations), already
     concatenated when it was stored: built once here, outside the timed region, so the torch path pays one index per field."""
     T = st.num_steps
-    flat = {k: r[:T].flatten(0, 1) for k, r in st.group_rows.items()}
+    names = {m for members in st.obs_groups.values() for m in members}
+    flat = {k: st.observation_rows(k)[:T].flatten(0, 1) for k in names}   # (a frame-stored manager: its rows, materialised once)
     obs = flat["policy"]
     critic = torch.cat([flat[k] for k in st.obs_groups["critic"]], dim=-1) if st.obs_groups["critic"] != st.obs_groups["policy"] else None
     rest = [x.flatten(0, 1) for x in (st.actions, st.values, st.advantages, st.returns, st.actions_log_prob, st.mu, st.sigma)]
@@ -86,13 +91,17 @@ def main():
     ap.add_argument("--critic-width", type=int, default=0)
     ap.add_argument("--num-actions", type=int, default=12)
     ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--history-len", type=int, default=1, help="H: the observation widths are H frames side by side")
+    ap.add_argument("--history", default="rows", choices=["rows", "frames"], help="RolloutStorage(history=)")
     a = ap.parse_args()
+    if a.history_len < 1 or a.obs_width % a.history_len or a.critic_width % a.history_len:
+        raise SystemExit("--history-len must divide --obs-width and --critic-width")
     if not torch.cuda.is_available():
         raise SystemExit("bench_minibatch: no ROCm device (this tool measures the GPU only)")
     from genesis_forge_amd import gs
 
     gs.set_device("cuda:0")
-    st = storage(a.num_envs, a.steps, a.obs_width, a.critic_width, a.num_actions)
+    st = storage(a.num_envs, a.steps, a.obs_width, a.critic_width, a.num_actions, a.history_len, a.history)
     nmb, ep = a.mini_batches, a.epochs
     mb = a.num_envs * a.steps // nmb
     gen = torch.Generator(device="cuda").manual_seed(1)
@@ -118,6 +127,7 @@ def main():
     nbytes = mb * (row_floats * 4 * 2 + 8)
     print(json.dumps({"num_envs": a.num_envs, "steps": a.steps, "mini_batches": nmb, "epochs": ep, "rows_per_minibatch": mb,
                       "obs_width": a.obs_width, "critic_width": critic, "num_actions": a.num_actions,
+                      "history_len": a.history_len, "history": a.history if st.frames else "rows",
                       "bytes_per_minibatch": nbytes, "hip_us_per_minibatch": round(hip_us, 2), "torch_us_per_minibatch": round(torch_us, 2),
                       "hip_frac_of_8TBps": round(nbytes / (hip_us * 1e-6) / PEAK, 3),
                       "torch_frac_of_8TBps": round(nbytes / (torch_us * 1e-6) / PEAK, 3),

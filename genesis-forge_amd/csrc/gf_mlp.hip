@@ -136,6 +136,7 @@ __device__ __forceinline__ void mlp_k_loop(const MlpSmem& sm, const GF_GLOBAL fl
 // One Linear layer (+ ELU unless `last`) of the tile: x (LDS, K columns; the segments when `first`) -> x (O columns, zeros up to the
 // next multiple of 32).  NB = 32-column blocks per wave: every wave multiplies NB blocks (the ones past `out` are not stored).
 // NORM: the launch has a net with an input normaliser (a kernel of its own: the plain forward keeps the code it had).
+// (LOG, the kernel's other flag — std holds log_std — is the same kind: only the sampling lanes at the end differ.)
 template <int NB, bool NORM>
 __device__ __forceinline__ void mlp_layer(MlpSmem& sm, const GfMlpNet& net, const GfMlpLayer& L, const int K, const bool first, const bool last,
                                           const int64_t row0, const int64_t N) {
@@ -217,7 +218,7 @@ __device__ __forceinline__ void mlp_layer(MlpSmem& sm, const GfMlpNet& net, cons
     __syncthreads();
 }
 
-template <bool NORM>
+template <bool NORM, bool LOG>
 __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArgs a, const int first_net, const int vec_rows) {
     __shared__ MlpSmem sm;
     const bool is_critic = (int)blockIdx.y + first_net == 1;
@@ -267,7 +268,7 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArg
     p.seed = a.seed;
     p.stream = a.stream;
     p.env_offset = a.env_offset;
-    p._pad = 0;
+    p.std_is_log = LOG;
     p.actions = a.actions;
     p.actions_out = a.actions_out;
     p.mu_out = a.mu_out;
@@ -278,8 +279,8 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArg
 #pragma unroll
         for (int k = 0; k < 4; ++k) m[k] = out[c0 + k];   // (columns past A: zeros, or x's finite leftovers — never folded or stored)
     };
-    if (vec_rows) policy_act_row<true>(p, n, load_mean);
-    else policy_act_row<false>(p, n, load_mean);
+    if (vec_rows) policy_act_row<true, LOG>(p, n, load_mean);
+    else policy_act_row<false, LOG>(p, n, load_mean);
 }
 
 // GF_OK and the net's widths, or the refusal
@@ -315,7 +316,7 @@ static int mlp_check_net(const GfMlpNet& net, bool critic, int* out_width) {
 
 extern "C" __attribute__((visibility("default"))) int gf_mlp_act(const GfMlpActArgs* a, void* stream) {
     if (!a) return GF_E_NULL;
-    if (a->num_envs < 0 || (a->std_per_env != 0 && a->std_per_env != 1)) return GF_E_RANGE;
+    if (a->num_envs < 0 || (a->std_per_env != 0 && a->std_per_env != 1) || (a->std_is_log != 0 && a->std_is_log != 1)) return GF_E_RANGE;
     int A = 0, one = 0;
     int rc = gf::mlp_check_net(a->actor, false, &A);
     if (rc != GF_OK) return rc;
@@ -344,7 +345,15 @@ extern "C" __attribute__((visibility("default"))) int gf_mlp_act(const GfMlpActA
     const int vec_rows = (bits & 15u) == 0 && (A & 3) == 0;
     const bool norm = (actor && a->actor.in_mean) || (critic && a->critic.in_mean);
     const dim3 grid((unsigned)tiles, actor && critic ? 2u : 1u);
-    if (norm) gf::klaunch(gf::mlp_act_kernel<true>, grid, dim3(gf::kMlpBlock), 0, (hipStream_t)stream, *a, actor ? 0 : 1, vec_rows);
-    else gf::klaunch(gf::mlp_act_kernel<false>, grid, dim3(gf::kMlpBlock), 0, (hipStream_t)stream, *a, actor ? 0 : 1, vec_rows);
+    const dim3 block(gf::kMlpBlock);
+    hipStream_t s = (hipStream_t)stream;
+    const int first_net = actor ? 0 : 1;
+    if (a->std_is_log && a->actions) {   // (without actions nothing is sampled: the plain instances)
+        if (norm) gf::klaunch(gf::mlp_act_kernel<true, true>, grid, block, 0, s, *a, first_net, vec_rows);
+        else gf::klaunch(gf::mlp_act_kernel<false, true>, grid, block, 0, s, *a, first_net, vec_rows);
+    } else {
+        if (norm) gf::klaunch(gf::mlp_act_kernel<true, false>, grid, block, 0, s, *a, first_net, vec_rows);
+        else gf::klaunch(gf::mlp_act_kernel<false, false>, grid, block, 0, s, *a, first_net, vec_rows);
+    }
     return gf::launch_status();
 }

@@ -4,7 +4,8 @@
 //
 // gf_policy_act: one lane per env walks its A columns in groups of four — one Philox block per group gives the group's four
 // normals — and folds log_prob left to right in a register.  16-byte loads and stores where A % 4 == 0 and every [N, A] row is
-// 16-byte aligned, scalar ones otherwise; the arithmetic is the same.  Algorithmic traffic per env: R 4A (mean) + 4A (std, [N, A]
+// 16-byte aligned, scalar ones otherwise; the arithmetic is the same.  With std_is_log every loaded std element goes through expf
+// first (policy_sigma; a kernel instance of its own).  Algorithmic traffic per env: R 4A (mean) + 4A (std, [N, A]
 // only) + 4A (noise, parity mode only) + 4, W 16A + 8 bytes.
 //
 // gf_episode_step: 256 lanes x 4 consecutive envs per workgroup.  A lane's done envs get their ranks from a wave scan and the
@@ -21,13 +22,13 @@ namespace gf {
 // (the row's body is gf_policy_row.h: gf_mlp_act samples with it too)
 constexpr int kActBlock = 256;
 
-template <bool V>
+template <bool V, bool LOG>
 __global__ __launch_bounds__(kActBlock) void policy_act_kernel(const GfPolicyActArgs a) {
     const int64_t n = (int64_t)blockIdx.x * kActBlock + threadIdx.x;
     if (n >= a.num_envs) return;
     const int A = a.num_actions;
     const GF_GLOBAL float* mean = G(a.mean) + n * A;
-    policy_act_row<V>(a, n, [&](int c0, float (&m)[4]) { act_load4<V>(mean, c0, A, m); });
+    policy_act_row<V, LOG>(a, n, [&](int c0, float (&m)[4]) { act_load4<V>(mean, c0, A, m); });
 }
 
 // ---- gf_episode_step ------------------------------------------------------------------------------------------------------------
@@ -215,7 +216,8 @@ __global__ __launch_bounds__(kEpBlock) void episode_kernel(const GfEpisodeArgs a
 extern "C" __attribute__((visibility("default"))) int gf_policy_act(const GfPolicyActArgs* a, void* stream) {
     if (!a || !a->mean || !a->std || !a->actions) return GF_E_NULL;
     if (a->values_out && !a->values) return GF_E_NULL;
-    if (a->num_envs < 0 || a->num_actions < 1 || (a->std_per_env != 0 && a->std_per_env != 1)) return GF_E_RANGE;
+    if (a->num_envs < 0 || a->num_actions < 1 || (a->std_per_env != 0 && a->std_per_env != 1) || a->std_is_log > 1u)
+        return GF_E_RANGE;
     if (a->num_envs == 0) return GF_OK;
     const int64_t blocks = (a->num_envs + gf::kActBlock - 1) / gf::kActBlock;
     if (blocks > 0x7fffffff) return GF_E_RANGE;
@@ -224,8 +226,14 @@ extern "C" __attribute__((visibility("default"))) int gf_policy_act(const GfPoli
     for (const void* p : rows) bits |= reinterpret_cast<uintptr_t>(p);
     const bool vec = (bits & 15u) == 0 && (a->num_actions & 3) == 0;
     hipStream_t s = (hipStream_t)stream;
-    if (vec) gf::klaunch(gf::policy_act_kernel<true>, dim3((unsigned)blocks), dim3(gf::kActBlock), 0, s, *a);
-    else gf::klaunch(gf::policy_act_kernel<false>, dim3((unsigned)blocks), dim3(gf::kActBlock), 0, s, *a);
+    const dim3 grid((unsigned)blocks), block(gf::kActBlock);
+    if (a->std_is_log) {   // (a kernel instance of its own: the plain one keeps the code it had)
+        if (vec) gf::klaunch(gf::policy_act_kernel<true, true>, grid, block, 0, s, *a);
+        else gf::klaunch(gf::policy_act_kernel<false, true>, grid, block, 0, s, *a);
+    } else {
+        if (vec) gf::klaunch(gf::policy_act_kernel<true, false>, grid, block, 0, s, *a);
+        else gf::klaunch(gf::policy_act_kernel<false, false>, grid, block, 0, s, *a);
+    }
     return gf::launch_status();
 }
 

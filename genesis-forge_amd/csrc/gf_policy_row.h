@@ -20,6 +20,11 @@ __device__ __forceinline__ void box_muller(uint32_t w1, uint32_t w2, float& z0, 
     z1 = r * s;
 }
 
+// The action std of a column from the policy's parameter: the parameter itself (rsl_rl's noise_std_type "scalar") or expf of it
+// ("log").  gf_policy_act, gf_mlp_act and gf_ppo_loss all come through here, so one log_std gives the same sigma bits in all three.
+// The two sampling kernels pass a compile-time flag (LOG, a kernel instance of its own): their flag-0 code is what it was.
+__device__ __forceinline__ float policy_sigma(float raw, int is_log) { return is_log ? expf(raw) : raw; }
+
 template <bool V>
 __device__ __forceinline__ void act_load4(const GF_GLOBAL float* p, int c0, int A, float (&v)[4]) {
     if (V) {
@@ -45,7 +50,8 @@ __device__ __forceinline__ void act_store4(float* p, int64_t off, int c0, int A,
 }
 
 // Row n of gf_policy_act.  `load_mean(c0, m)` fills m[0 … 3] with the mean of columns c0 … c0 + 3 (any finite filler past A).
-template <bool V, class MeanLoad>
+// LOG: a.std holds log_std (a.std_is_log, decided at the launch).
+template <bool V, bool LOG, class MeanLoad>
 __device__ __forceinline__ void policy_act_row(const GfPolicyActArgs& a, const int64_t n, MeanLoad load_mean) {
     const int A = a.num_actions;
     const int64_t row = n * A;
@@ -58,6 +64,8 @@ __device__ __forceinline__ void policy_act_row(const GfPolicyActArgs& a, const i
         float m[4], s[4], e[4], act[4];
         load_mean(c0, m);
         act_load4<V>(sd, c0, A, s);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] = policy_sigma(s[k], LOG);
         if (noise) {
             act_load4<V>(noise, c0, A, e);
         } else {

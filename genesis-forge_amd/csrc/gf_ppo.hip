@@ -6,13 +6,16 @@
 // gf_policy_act), then, once the row's ratio is known, d loss / d mu and the row's share of d loss / d sigma.  16-byte loads and
 // stores where A % 4 == 0 and every [mb, A] row is 16-byte aligned, scalar ones otherwise.  Each workgroup sums its rows' three
 // loss terms and A sigma-gradient columns in double (wave butterfly, then the four waves in order through LDS) into its record
-// of the workspace; a one-workgroup launch sums the records in a fixed order, one wave per column.  Algorithmic traffic per row: R 16A + 20 (+ 8A
+// of the workspace; a one-workgroup launch sums the records in a fixed order, one wave per column.  With sigma_is_log `sigma` is
+// log_std: every loaded element goes through policy_sigma (gf_policy_row.h, gf_policy_act's expf) and the finalize launch writes
+// d loss / d log_std = grad_sigma · sigma, one more f32 product.  Algorithmic traffic per row: R 16A + 20 (+ 8A
 // re-read of mu / actions), W 4A + 4 bytes.
 //
 // gf_adam_step: launch 1 — each workgroup sums g^2 of its 1 024-element chunks (double) into one partial; launch 2 — every
 // workgroup sums all partials in the same order (so all agree on the norm without a hand-off), applies the schedule to
 // state[parity], and updates its 1 024 elements.  Algorithmic traffic per element: R 4 (norm) + 16, W 16 bytes.
 #include "gf_launch.h"
+#include "gf_policy_row.h"
 
 namespace gf {
 
@@ -71,6 +74,8 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_loss_rows_kernel(const GfPpoLos
         ppo_load4<V>(mu, c0, A, m);
         ppo_load4<V>(x, c0, A, xa);
         ppo_load4<V>(sd, c0, A, s);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] = policy_sigma(s[k], a.sigma_is_log);
         ppo_load4<V>(omu, c0, A, om);
         ppo_load4<V>(osd, c0, A, os);
 #pragma unroll
@@ -139,6 +144,7 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_loss_rows_kernel(const GfPpoLos
         ppo_load4<V>(sd, c0, A, s);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
+            s[k] = policy_sigma(s[k], a.sigma_is_log);
             const float d = xa[k] - m[k];
             const float var = s[k] * s[k];
             gm[k] = (dlp / (2.0f * var)) * (2.0f * d);                  // d/d mu of -(d^2) / (2 var)
@@ -181,8 +187,9 @@ __global__ __launch_bounds__(kPpoFinBlock) void ppo_loss_finalize_kernel(const G
             if (q < 3) {
                 s_tot[q] = t;
             } else {   // + the entropy term: sum over the rows of (-entropy_coef / mb) / sigma = -entropy_coef / sigma
-                const float s = G(a.sigma)[q - 3];
-                G(a.grad_sigma)[q - 3] = (float)(t - (double)a.entropy_coef / (double)s);
+                const float s = policy_sigma(G(a.sigma)[q - 3], a.sigma_is_log);
+                const float g = (float)(t - (double)a.entropy_coef / (double)s);
+                G(a.grad_sigma)[q - 3] = a.sigma_is_log ? g * s : g;   // exp's backward: d loss / d log_std = (d loss / d sigma) · sigma
             }
         }
     }
@@ -190,7 +197,7 @@ __global__ __launch_bounds__(kPpoFinBlock) void ppo_loss_finalize_kernel(const G
     if (threadIdx.x != 0) return;
     float ent = 0.0f;   // every row's entropy is the same sum: its mean over the rows is that sum
     for (int c = 0; c < A; ++c) {
-        const float e = kPpoEntropyC + logf(G(a.sigma)[c]);
+        const float e = kPpoEntropyC + logf(policy_sigma(G(a.sigma)[c], a.sigma_is_log));
         ent = c == 0 ? e : ent + e;
     }
     const float surrogate = (float)(s_tot[0] / mb), value_loss = (float)(s_tot[1] / mb), kl_mean = (float)(s_tot[2] / mb);
@@ -337,7 +344,9 @@ extern "C" __attribute__((visibility("default"))) int gf_ppo_loss(const GfPpoLos
     if (a->use_clipped_value_loss && !a->target_values) return GF_E_NULL;
     const int grads = (a->grad_mu != nullptr) + (a->grad_value != nullptr) + (a->grad_sigma != nullptr);
     if (grads != 0 && grads != 3) return GF_E_NULL;   // half a gradient set
-    if (a->num_rows < 0 || a->num_actions < 1 || (a->use_clipped_value_loss != 0 && a->use_clipped_value_loss != 1)) return GF_E_RANGE;
+    if (a->num_rows < 0 || a->num_actions < 1 || (a->use_clipped_value_loss != 0 && a->use_clipped_value_loss != 1) ||
+        (a->sigma_is_log != 0 && a->sigma_is_log != 1))
+        return GF_E_RANGE;
     if (a->num_rows == 0) return GF_OK;
     const int64_t nb = (a->num_rows + gf::kPpoBlock - 1) / gf::kPpoBlock;
     if (nb > 0x7fffffff) return GF_E_RANGE;

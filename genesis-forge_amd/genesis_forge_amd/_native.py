@@ -13,7 +13,7 @@ import ctypes as C
 import os
 from typing import Optional
 
-GF_ABI_VERSION = 9
+GF_ABI_VERSION = 10
 GF_MAX_TERMS = 24
 GF_MAX_TERM_TERMS = 16
 GF_MAX_OBS_ITEMS = 24
@@ -334,7 +334,7 @@ GF_EPISODE_SINGLE_MAX = 65536
 
 class GfPolicyActArgs(C.Structure):
     _fields_ = [("num_envs", C.c_int64), ("num_actions", C.c_int32), ("std_per_env", C.c_int32), ("mean", P), ("std", P), ("values", P),
-                ("noise", P), ("seed", C.c_uint64), ("stream", C.c_uint64), ("env_offset", C.c_uint32), ("_pad", C.c_uint32),
+                ("noise", P), ("seed", C.c_uint64), ("stream", C.c_uint64), ("env_offset", C.c_uint32), ("std_is_log", C.c_uint32),
                 ("actions", P), ("actions_out", P), ("mu_out", P), ("sigma_out", P), ("values_out", P), ("log_prob_out", P)]
 
 
@@ -368,7 +368,7 @@ def adam_workspace_bytes(numel: int) -> int:
 class GfPpoLossArgs(C.Structure):
     _fields_ = [("num_rows", C.c_int64), ("num_actions", C.c_int32), ("use_clipped_value_loss", C.c_int32), ("mu", P), ("sigma", P),
                 ("value", P), ("actions", P), ("old_log_prob", P), ("advantages", P), ("target_values", P), ("returns", P), ("old_mu", P),
-                ("old_sigma", P), ("clip_param", C.c_float), ("value_loss_coef", C.c_float), ("entropy_coef", C.c_float), ("_pad", C.c_float),
+                ("old_sigma", P), ("clip_param", C.c_float), ("value_loss_coef", C.c_float), ("entropy_coef", C.c_float), ("sigma_is_log", C.c_int32),
                 ("grad_mu", P), ("grad_value", P), ("grad_sigma", P), ("out", P), ("sums", P), ("workspace", P), ("workspace_bytes", C.c_int64)]
 
 
@@ -404,7 +404,7 @@ class GfMlpNet(C.Structure):
 class GfMlpActArgs(C.Structure):
     _fields_ = [("num_envs", C.c_int64), ("actor", GfMlpNet), ("critic", GfMlpNet), ("std", P), ("noise", P), ("seed", C.c_uint64),
                 ("stream", C.c_uint64), ("env_offset", C.c_uint32), ("std_per_env", C.c_int32), ("mean", P), ("values", P), ("actions", P),
-                ("actions_out", P), ("mu_out", P), ("sigma_out", P), ("values_out", P), ("log_prob_out", P)]
+                ("actions_out", P), ("mu_out", P), ("sigma_out", P), ("values_out", P), ("log_prob_out", P), ("std_is_log", C.c_int32), ("_pad", C.c_int32)]
 
 
 # the running observation statistics (learner.EmpiricalNormalization.update): gf_obs_norm_update, not in ABI_STRUCTS either

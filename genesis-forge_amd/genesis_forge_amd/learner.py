@@ -446,12 +446,15 @@ class RolloutStorage:
         self._act_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self._act_stream = 0
 
-    def act(self, mean: torch.Tensor, std: torch.Tensor, values: torch.Tensor, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def act(self, mean: torch.Tensor, std: torch.Tensor, values: torch.Tensor, noise: Optional[torch.Tensor] = None,
+            std_is_log: bool = False) -> torch.Tensor:
         """rsl_rl's ``PPO.act`` from the actor's ``mean`` ``[N, A]``, the action ``std`` (``[A]``, rsl_rl's ``noise_std_type=
-        "scalar"``; pass ``log_std.exp()`` for ``"log"``; or ``[N, A]``) and the critic's ``values`` (``[N]`` or ``[N, 1]``):
+        "scalar"``; or ``[N, A]``) and the critic's ``values`` (``[N]`` or ``[N, 1]``):
         returns ``Normal(mean, std).sample()`` as a fresh ``[N, A]`` tensor and writes the policy's rows of the transition the next
         ``env.step()`` writes (row ``step``, 0 once the storage is ``full``): actions, mu, sigma (``std`` expanded), values and
-        ``log_prob(actions).sum(-1)``.  One ``gf_policy_act`` launch; the draws are Philox + Box–Muller keyed by (seed, stream,
+        ``log_prob(actions).sum(-1)``.  ``std_is_log=True`` (``noise_std_type="log"``): ``std`` is the policy's ``log_std`` and the
+        kernel exponentiates it — the sample, the log-probability and the sigma row all see ``exp(log_std)``, the same bits
+        ``gf_ppo_loss`` later derives from that ``log_std``.  One ``gf_policy_act`` launch; the draws are Philox + Box–Muller keyed by (seed, stream,
         global env id, column) — the stream advances once per call, the env's own stream is never touched.
         ``noise``: ``[N, A]`` standard normals used instead of the draws (parity tests; the only mode of the CPU oracle backend).
         Inputs must be float32, contiguous and on the storage's device: nothing is cast (``ValueError``)."""
@@ -473,10 +476,11 @@ class RolloutStorage:
         if fn is None:   # (the test-only oracle backend) the same expression in torch, from the given draws
             if noise is None:
                 raise RuntimeError("act() draws its noise in the HIP kernel: on a backend without gf_policy_act pass noise=")
-            self._act_torch(mean, std, values, noise, actions, t)
+            self._act_torch(mean, std, values, noise, actions, t, std_is_log)
         else:
             a = self._act_args
             a.num_envs, a.num_actions, a.std_per_env = n, A, 1 if std.dim() == 2 else 0
+            a.std_is_log = 1 if std_is_log else 0
             a.mean, a.std, a.values = mean.data_ptr(), std.data_ptr(), values.data_ptr()
             a.noise = None if noise is None else noise.data_ptr()
             a.seed = self.env._rng_seed if self._act_seed is None else self._act_seed
@@ -490,7 +494,8 @@ class RolloutStorage:
         return actions
 
     def act_policy(self, forward: "PolicyForward", obs, critic_obs=None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``act(policy.act_mean(obs), policy.std, policy.evaluate(critic_obs), noise)`` with the two forward passes inside the launch:
+        """``act(policy.act_mean(obs), policy.std, policy.evaluate(critic_obs), noise)`` (``policy.log_std`` and ``std_is_log=True`` for
+        a ``noise_std_type="log"`` policy) with the two forward passes inside the launch:
         ONE ``gf_mlp_act`` runs the actor and the critic MLP of ``forward`` (a :class:`PolicyForward`) on the f32 matrix cores, samples
         and writes the policy's rows — instead of torch's GEMM and ELU launch per layer and ``gf_policy_act`` behind them.  The row, the
         noise stream and seed, and the input rules are ``act``'s: a loop that replaces ``store.act(policy.act_mean(obs), policy.std,
@@ -508,17 +513,17 @@ class RolloutStorage:
             raise ValueError("act_policy(forward, ...) takes a PolicyForward")
         n, dev = self.env.num_envs, self.device
         if forward.actor is None or forward.critic is None or forward.num_actions is None:
-            raise ValueError("act_policy needs a policy with an actor, a critic and a [A] std")
+            raise ValueError("act_policy needs a policy with an actor, a critic and a [A] std (or log_std)")
         segs = forward._segments(obs, forward.actor, "obs", n, dev)   # (a window-mode manager's strided view is read in place)
         csegs = forward._segments(obs if critic_obs is None else critic_obs, forward.critic, "obs (the critic's input)" if critic_obs is None else "critic_obs", n, dev)
         A = forward.num_actions
-        std = forward.policy.std
+        std, is_log = getattr(forward.policy, forward._std_name), forward.std_is_log
         fn = getattr(self.env.backend, "mlp_act", None)
         if fn is None:   # (the test-only oracle backend) today's path, bit for bit
             cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
             with torch.no_grad():
-                return self.act(forward.policy.act_mean(cat(segs)), std.detach(), forward.policy.evaluate(cat(csegs)), noise)
-        _check_f32(std, "policy.std", {(A,)}, dev)
+                return self.act(forward.policy.act_mean(cat(segs)), std.detach(), forward.policy.evaluate(cat(csegs)), noise, std_is_log=is_log)
+        _check_f32(std, "policy.log_std" if is_log else "policy.std", {(A,)}, dev)
         if noise is not None:
             _check_f32(noise, "noise", {(n, A)}, dev)
         t = 0 if self.full else self.step
@@ -527,7 +532,7 @@ class RolloutStorage:
         stream = self._act_stream
         self._act_stream += 1
         a = forward._fill(n, segs, csegs)
-        a.std, a.std_per_env = std.data_ptr(), 0
+        a.std, a.std_per_env, a.std_is_log = std.data_ptr(), 0, 1 if is_log else 0
         a.noise = None if noise is None else noise.data_ptr()
         a.seed = self.env._rng_seed if self._act_seed is None else self._act_seed
         a.stream, a.env_offset = stream, int(getattr(self.env, "env_offset", 0))
@@ -540,9 +545,9 @@ class RolloutStorage:
         self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
         return actions
 
-    def _act_torch(self, mean, std, values, noise, actions, t) -> None:
+    def _act_torch(self, mean, std, values, noise, actions, t, std_is_log: bool = False) -> None:
         with torch.no_grad():
-            sd = std.expand_as(mean)
+            sd = (std.exp() if std_is_log else std).expand_as(mean)
             actions.copy_(mean + sd * noise)
             d = actions - mean
             term = -(d * d) / (2 * (sd * sd)) - sd.log() - _LOG_SQRT_2PI
@@ -1015,12 +1020,18 @@ class ActorCriticMLP(torch.nn.Module):
     """rsl_rl's ``ActorCritic`` as configured by the reference's training scripts (examples/simple/train.py:56-62).
     ``actor_obs_normalization`` / ``critic_obs_normalization`` (rsl_rl 3.x): an :class:`EmpiricalNormalization` in front of the net
     (``actor_obs_normalizer`` / ``critic_obs_normalizer``; ``nn.Identity()`` when off, as rsl_rl) — buffers only, so ``parameters()``
-    and their order are the same either way.  ``num_critic_obs``: the critic's input width where it differs from the actor's."""
+    and their order are the same either way.  ``num_critic_obs``: the critic's input width where it differs from the actor's.
+    ``noise_std_type``: ``"scalar"`` — a ``std`` parameter ``[A]`` starting at ``init_noise_std``; ``"log"`` — a ``log_std``
+    parameter starting at ``log(init_noise_std)`` in its place (no ``std`` parameter; rsl_rl's names, so checkpoints interchange),
+    which keeps the std positive whatever step Adam takes.  ``action_std`` is the current std of either."""
 
     def __init__(self, num_obs: int, num_actions: int, actor_hidden_dims: Sequence[int] = (512, 256, 128),
                  critic_hidden_dims: Sequence[int] = (512, 256, 128), init_noise_std: float = 1.0, num_critic_obs: Optional[int] = None,
-                 actor_obs_normalization: bool = False, critic_obs_normalization: bool = False):
+                 actor_obs_normalization: bool = False, critic_obs_normalization: bool = False, noise_std_type: str = "scalar"):
         super().__init__()
+        if noise_std_type not in ("scalar", "log"):
+            raise ValueError(f"ActorCriticMLP: noise_std_type={noise_std_type!r} is not supported ('scalar' or 'log')")
+        self.noise_std_type = noise_std_type
 
         def mlp(sizes):
             layers = []
@@ -1033,7 +1044,10 @@ class ActorCriticMLP(torch.nn.Module):
         num_critic_obs = num_obs if num_critic_obs is None else int(num_critic_obs)
         self.actor = mlp([num_obs, *actor_hidden_dims, num_actions])
         self.critic = mlp([num_critic_obs, *critic_hidden_dims, 1])
-        self.std = torch.nn.Parameter(init_noise_std * torch.ones(num_actions))
+        if noise_std_type == "scalar":
+            self.std = torch.nn.Parameter(init_noise_std * torch.ones(num_actions))
+        else:
+            self.log_std = torch.nn.Parameter(torch.log(init_noise_std * torch.ones(num_actions)))
         self.actor_obs_normalizer = EmpiricalNormalization(num_obs) if actor_obs_normalization else torch.nn.Identity()
         self.critic_obs_normalizer = EmpiricalNormalization(num_critic_obs) if critic_obs_normalization else torch.nn.Identity()
         self._scratch = _NormScratch()
@@ -1043,7 +1057,8 @@ class ActorCriticMLP(torch.nn.Module):
         """The policy of a ``training_cfg()`` dict of ``examples/*/train.py``: ``policy.actor_hidden_dims`` / ``critic_hidden_dims`` /
         ``init_noise_std``, rsl_rl 3.x's ``policy.actor_obs_normalization`` / ``critic_obs_normalization``, and the top-level
         ``empirical_normalization`` the scripts carry (truthy: both normalisers; ``None`` / ``False``: the policy keys decide).
-        Anything that cannot be honoured — another activation than ``"elu"``, another ``noise_std_type`` than ``"scalar"``, an
+        ``policy.noise_std_type`` (``"scalar"`` or ``"log"``).
+        Anything that cannot be honoured — another activation than ``"elu"``, another ``noise_std_type`` than those two, an
         unknown policy key — raises ``ValueError`` naming the key."""
         pol = dict(train_cfg.get("policy", {}))
         bad = sorted(k for k in pol if k not in _POLICY_KEYS)
@@ -1051,15 +1066,21 @@ class ActorCriticMLP(torch.nn.Module):
             raise ValueError(f"ActorCriticMLP: unsupported policy keys {bad}")
         if pol.get("activation", "elu") != "elu":
             raise ValueError(f"ActorCriticMLP: policy.activation={pol['activation']!r} is not supported (only 'elu')")
-        if pol.get("noise_std_type", "scalar") != "scalar":
-            raise ValueError(f"ActorCriticMLP: policy.noise_std_type={pol['noise_std_type']!r} is not supported (only 'scalar')")
+        if pol.get("noise_std_type", "scalar") not in ("scalar", "log"):
+            raise ValueError(f"ActorCriticMLP: policy.noise_std_type={pol['noise_std_type']!r} is not supported ('scalar' or 'log')")
         if pol.get("class_name", "ActorCritic") != "ActorCritic":
             raise ValueError(f"ActorCriticMLP: policy.class_name={pol['class_name']!r} is not supported (only 'ActorCritic')")
         both = bool(train_cfg.get("empirical_normalization"))
         return cls(num_obs, num_actions, tuple(pol.get("actor_hidden_dims", (512, 256, 128))), tuple(pol.get("critic_hidden_dims", (512, 256, 128))),
                    float(pol.get("init_noise_std", 1.0)), num_critic_obs=num_critic_obs,
                    actor_obs_normalization=both or bool(pol.get("actor_obs_normalization", False)),
-                   critic_obs_normalization=both or bool(pol.get("critic_obs_normalization", False)))
+                   critic_obs_normalization=both or bool(pol.get("critic_obs_normalization", False)),
+                   noise_std_type=pol.get("noise_std_type", "scalar"))
+
+    @property
+    def action_std(self) -> torch.Tensor:
+        """The current action std ``[A]`` (detached): ``std``, or ``exp(log_std)``."""
+        return self.log_std.detach().exp() if self.noise_std_type == "log" else self.std.detach().clone()
 
     def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
         return self.actor(self.actor_obs_normalizer(obs))
@@ -1075,6 +1096,14 @@ class ActorCriticMLP(torch.nn.Module):
             if isinstance(norm, EmpiricalNormalization) and norm.training:
                 pairs.append((norm, _obs_segments(x, norm.width, name, norm._mean.device)))
         _update_normalizers(pairs, self._scratch.args)
+
+
+def _policy_std(policy):
+    """``(parameter, is_log)``: ``policy.log_std`` where ``policy.noise_std_type == "log"`` (rsl_rl's attribute names: a foreign policy
+    works too), ``policy.std`` otherwise; the parameter is None where the policy has none."""
+    is_log = getattr(policy, "noise_std_type", "scalar") == "log"
+    p = getattr(policy, "log_std" if is_log else "std", None)
+    return (p if isinstance(p, torch.Tensor) else None), is_log
 
 
 class PolicyForward:
@@ -1101,14 +1130,21 @@ class PolicyForward:
         if self.actor is None and self.critic is None:
             raise ValueError("PolicyForward: the policy has neither an actor nor a critic")
         self._normalizer("actor"), self._normalizer("critic")   # (refuses what the kernel cannot fold in)
-        std = getattr(policy, "std", None)
+        std, is_log = _policy_std(policy)
+        self.std_is_log, self._std_name = is_log, "log_std" if is_log else "std"   # (the type is fixed; the parameter is looked up per call)
         self.num_actions = None
-        if self.actor is not None and isinstance(std, torch.Tensor):
+        if self.actor is not None and std is not None:
             A = self.actor[-1][0].shape[0]
             if std.dtype != torch.float32 or tuple(std.shape) != (A,):
-                raise ValueError(f"PolicyForward: policy.std must be a float32 [{A}] tensor, not {std.dtype} {tuple(std.shape)}")
+                name = "log_std" if is_log else "std"
+                raise ValueError(f"PolicyForward: policy.{name} must be a float32 [{A}] tensor, not {std.dtype} {tuple(std.shape)}")
             self.num_actions = int(A)
         self._args = nat.GfMlpActArgs()
+
+    def std_param(self):
+        """``(policy.std, False)`` or, for a ``noise_std_type="log"`` policy, ``(policy.log_std, True)`` — the parameter is looked up at
+        every call, the type was read at construction."""
+        return getattr(self.policy, self._std_name, None), self.std_is_log
 
     @staticmethod
     def _walk(net, name: str, max_out: int):
@@ -1215,6 +1251,7 @@ class PolicyForward:
         n = int(parts[0].shape[0])
         out = torch.empty((n, int(layers[-1][0].shape[0])), device=parts[0].device, dtype=torch.float32)
         a = self._fill(n, parts if name == "actor" else None, parts if name == "critic" else None)
+        a.std_is_log = 0
         a.std = a.noise = a.actions = a.actions_out = a.mu_out = a.sigma_out = a.values_out = a.log_prob_out = None
         a.mean, a.values = (out.data_ptr(), None) if name == "actor" else (None, out.data_ptr())
         self._keep = (parts, out)
@@ -1314,7 +1351,8 @@ class PPO:
     double, the step) are allocated once.
 
     Per minibatch ``update()`` zeroes the bucket, runs the actor / critic forward, ``gf_ppo_loss`` (the loss, its gradient w.r.t.
-    mu / value / std), back-propagates the kernel's gradients, all-reduces ``kl_mean`` over the ranks when there are several,
+    mu / value / std — or log_std, for a ``noise_std_type="log"`` policy: the kernel exponentiates it and returns
+    ``d loss / d log_std``), back-propagates the kernel's gradients, all-reduces ``kl_mean`` over the ranks when there are several,
     averages the bucket, and ``gf_adam_step`` (schedule, clipping, Adam) — no host synchronisation; the returned means are one read
     at the end.  On a backend without these entry points (the test-only CPU oracle) the same arithmetic runs in torch.
 
@@ -1355,9 +1393,9 @@ class PPO:
         self.schedule = cfg["schedule"]
         self.desired_kl = None if cfg["desired_kl"] is None else float(cfg["desired_kl"])
         self.adaptive = self.schedule == "adaptive" and self.desired_kl is not None   # (rsl_rl: `if desired_kl is not None and schedule == "adaptive"`)
-        std = getattr(policy, "std", None)
-        if not isinstance(std, torch.Tensor) or std.dim() != 1:
-            raise ValueError("PPO needs a policy with act_mean(), evaluate() and a [A] std parameter (ActorCriticMLP)")
+        std, _is_log = _policy_std(policy)
+        if std is None or std.dim() != 1:
+            raise ValueError("PPO needs a policy with act_mean(), evaluate() and a [A] std (or, with noise_std_type='log', log_std) parameter (ActorCriticMLP)")
         self.num_actions = int(std.numel())
         self.grad_sync = grad_sync if grad_sync is not None else GradientAllReduce(policy.parameters())
         sync = self.grad_sync
@@ -1461,7 +1499,7 @@ class PPO:
 
     def _loss_hip(self, backend, mu, value, b: MiniBatch):
         mb, A = int(b.actions.shape[0]), self.num_actions
-        std = self.policy.std
+        std, is_log = _policy_std(self.policy)   # (std, or log_std: the kernel exponentiates and applies exp's backward)
         for name, t, shape in (("mu", mu, (mb, A)), ("value", value, (mb, 1))):
             if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError(f"PPO: the policy's {name} must be a contiguous float32 {shape} tensor, not {tuple(t.shape)} {t.dtype}")
@@ -1472,7 +1510,8 @@ class PPO:
         a.actions, a.old_log_prob, a.advantages = b.actions.data_ptr(), b.old_log_prob.data_ptr(), b.advantages.data_ptr()
         a.target_values, a.returns, a.old_mu, a.old_sigma = b.values.data_ptr(), b.returns.data_ptr(), b.old_mu.data_ptr(), b.old_sigma.data_ptr()
         a.clip_param, a.value_loss_coef, a.entropy_coef = self.clip_param, self.value_loss_coef, self.entropy_coef
-        # d loss / d std goes straight into its slot of the (just zeroed) bucket: nothing in the graph of mu / value reaches std
+        a.sigma_is_log = 1 if is_log else 0
+        # d loss / d std (d loss / d log_std) goes straight into its slot of the (just zeroed) bucket: nothing in the graph of mu / value reaches std
         a.grad_mu, a.grad_value, a.grad_sigma = gmu.data_ptr(), gval.data_ptr(), std.grad.data_ptr()
         a.out, a.sums = self._out.data_ptr(), self._sums.data_ptr()
         a.workspace, a.workspace_bytes = self._loss_ws.data_ptr(), self._loss_ws.numel() * 8
@@ -1498,8 +1537,8 @@ class PPO:
     # -- the same arithmetic in torch (backends without gf_ppo_loss / gf_adam_step) -------------------------------------------------
     def _loss_torch(self, mu, value, b: MiniBatch) -> None:
         """rsl_rl PPO.update's loss lines, ``loss.backward()``, and the values gf_ppo_loss leaves in ``out`` / ``sums``."""
-        std = self.policy.std
-        sigma = std.expand_as(mu)
+        std, is_log = _policy_std(self.policy)
+        sigma = (torch.exp(std) if is_log else std).expand_as(mu)
         dist = torch.distributions.Normal(mu, sigma, validate_args=False)   # (rsl_rl's ActorCritic turns validation off: no host read)
         logp = dist.log_prob(b.actions).sum(dim=-1)
         entropy = dist.entropy().sum(dim=-1)

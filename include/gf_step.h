@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 9
+#define GF_ABI_VERSION 10
 
 #define GF_MAX_TERMS 24          /* reward terms per manager          */
 #define GF_MAX_TERM_TERMS 16     /* termination terms per manager     */
@@ -768,6 +768,11 @@ typedef struct GfMinibatchArgs {
  *                                                                       (the operation order of torch's Normal.log_prob)
  * and stores actions into the fresh `actions` tensor and, where given, the storage rows of transition t (actions, mu = mean,
  * sigma = std expanded to [N, A], values, actions_log_prob).
+ * std_is_log = 1 (rsl_rl's noise_std_type = "log"): `std` holds log_std and every loaded element e stands for expf(e) — in the
+ * sample, in the log_prob fold (logf of the exponentiated value, as torch's scale.log()) and in the sigma row, which holds std,
+ * never log_std.  gf_mlp_act and gf_ppo_loss exponentiate by the same code: one log_std gives the same sigma bits in all three.
+ * With the flag 0 nothing is exponentiated.  Refusals, before anything is launched: GF_E_NULL — args, mean, std, actions,
+ * values_out without values; GF_E_RANGE — num_envs < 0, num_actions < 1, std_per_env or std_is_log outside {0, 1}.
  * Draws: Philox block (env_offset + n, a / 4, stream_lo, stream_hi) keyed by seed ^ GF_POLICY_SEED_TAG (never the env's own key,
  * so no env draw is ever repeated) gives the normals of columns 4k … 4k+3: words (x, y) -> columns 4k, 4k+1 and (z, w) -> 4k+2, 4k+3,
  *     u1 = ((word1 >> 8) + 1) · 2^-24 ∈ (0, 1],  u2 = (word2 >> 8) · 2^-24,  r = sqrt(-2 · log(u1)),
@@ -781,13 +786,13 @@ typedef struct GfPolicyActArgs {
     int32_t num_actions;        /* A >= 1 */
     int32_t std_per_env;        /* 0: std is [A] (shared by every env), 1: std is [N, A] */
     const float* mean;          /* [N, A] actor output */
-    const float* std;           /* [A] or [N, A] */
+    const float* std;           /* [A] or [N, A]: the std, or log_std with std_is_log */
     const float* values;        /* [N] critic output, or NULL (then values_out must be NULL) */
     const float* noise;         /* [N, A] standard normals (parity mode), or NULL: Philox + Box–Muller */
     uint64_t seed;              /* Philox key = seed ^ GF_POLICY_SEED_TAG */
     uint64_t stream;            /* Philox counter words 2-3 */
     uint32_t env_offset;        /* global index of local env 0 (env sharding) */
-    uint32_t _pad;
+    uint32_t std_is_log;        /* 0: `std` is the std, 1: it is log_std (sigma = expf) */
     float* actions;             /* [N, A] out (required) */
     float* actions_out;         /* [N, A] storage row, or NULL */
     float* mu_out;              /* [N, A] storage row, or NULL */
@@ -856,6 +861,9 @@ typedef struct GfEpisodeArgs {
  * row is 16-byte aligned).  Every workgroup leaves 3 + A double partials (surrogate, value loss and KL sums, then the
  * column sums of grad_sigma) in the caller's workspace; a second, one-workgroup launch sums them in a fixed order and writes
  * grad_sigma, out[] and the running sums.  No float atomics, no hand-off between workgroups: bitwise reproducible.
+ * sigma_is_log = 1 (rsl_rl's noise_std_type = "log"): `sigma` points at log_std [A] and sigma_a = expf(log_std_a) — the same code
+ * as gf_policy_act's, so the same bits — stands wherever sigma does above.  grad_sigma[a] then receives d loss / d log_std_a =
+ * g · sigma_a (exp's backward), g the float32 value the flag-0 call writes for that sigma: one more correctly rounded f32 product.
  *
  * gf_adam_step — torch.nn.utils.clip_grad_norm_ then torch.optim.Adam (defaults: no weight decay, no amsgrad; foreach order)
  * over one flat float32 parameter buffer and its flat gradient (the GradientAllReduce bucket):
@@ -868,8 +876,8 @@ typedef struct GfEpisodeArgs {
  * same order (no hand-off), apply the schedule to state[parity] and update its elements; workgroup 0 writes state[1 - parity]
  * (double-buffered by call parity, as GfEpisodeArgs.ring_state).
  *
- * Neither is a phase of the step.  Refusals (GF_E_NULL / GF_E_RANGE) launch nothing; mb == 0 / numel == 0 is a no-op.  No
- * allocation, no copy, no synchronisation inside either entry point.
+ * Neither is a phase of the step.  Refusals (GF_E_NULL / GF_E_RANGE; sigma_is_log outside {0, 1} is GF_E_RANGE) launch nothing;
+ * mb == 0 / numel == 0 is a no-op.  No allocation, no copy, no synchronisation inside either entry point.
  * ---------------------------------------------------------------------------------------- */
 #define GF_PPO_BLOCK_ROWS 256          /* rows per workgroup of gf_ppo_loss: one partial record per workgroup */
 #define GF_PPO_OUT_COUNT 5             /* out[]: surrogate, value_loss, entropy, kl_mean, loss */
@@ -889,7 +897,7 @@ typedef struct GfPpoLossArgs {
     int32_t num_actions;        /* A >= 1 */
     int32_t use_clipped_value_loss;   /* 0 or 1 */
     const float* mu;            /* [mb, A] actor mean of this update */
-    const float* sigma;         /* [A] action std (shared by every row) */
+    const float* sigma;         /* [A] action std (shared by every row), or log_std with sigma_is_log */
     const float* value;         /* [mb] critic output of this update */
     const float* actions;       /* [mb, A] minibatch actions */
     const float* old_log_prob;  /* [mb] */
@@ -901,10 +909,10 @@ typedef struct GfPpoLossArgs {
     float clip_param;
     float value_loss_coef;
     float entropy_coef;
-    float _pad;
+    int32_t sigma_is_log;       /* 0: `sigma` is the std, 1: it is log_std and grad_sigma receives d loss / d log_std */
     float* grad_mu;             /* [mb, A] d loss / d mu, or NULL: no gradients (then all three are NULL) */
     float* grad_value;          /* [mb] */
-    float* grad_sigma;          /* [A] */
+    float* grad_sigma;          /* [A] d loss / d sigma (d loss / d log_std with sigma_is_log) */
     float* out;                 /* [GF_PPO_OUT_COUNT] (required) */
     double* sums;               /* [3] += value_loss, surrogate, entropy (rsl_rl's loss-dict order), or NULL */
     void* workspace;            /* GF_PPO_LOSS_WORKSPACE_BYTES(mb, A) bytes, 8-byte aligned */
@@ -960,12 +968,13 @@ typedef struct GfAdamArgs {
  *
  * Either net may be absent (num_layers == 0): actor only = play-time inference, critic only = the bootstrap value.  With an actor,
  * `actions == NULL` computes the mean only and draws nothing (then `mean` is required and actions_out / mu_out / sigma_out /
- * log_prob_out must be NULL).  `mean` / `values` are optional fresh outputs.
+ * log_prob_out must be NULL).  `mean` / `values` are optional fresh outputs.  std_is_log = 1: `std` holds log_std, as
+ * GfPolicyActArgs.std_is_log (the flag is forwarded to the same row code; without `actions` it is only range-checked).
  * Refusals, before anything is launched: GF_E_NULL — args, a weight / bias / segment pointer, in_mean without in_std, std with
  * actions, an actor without mean and actions, a critic without values and values_out, an actor's or critic's output pointer with that net absent;
  * GF_E_RANGE — num_envs < 0, more than GF_MLP_MAX_LAYERS layers, a segment count outside 1 … GF_MLP_MAX_INPUTS, a width < 1, a
  * non-zero row_stride < width, a hidden width > GF_MLP_MAX_HIDDEN, a total input width > GF_MLP_MAX_INPUT_WIDTH, an actor output > GF_MLP_MAX_ACTIONS,
- * std_per_env outside {0, 1}; GF_E_UNSUPPORTED — both nets absent, a critic output other than 1.  num_envs == 0 is a no-op.
+ * std_per_env or std_is_log outside {0, 1}; GF_E_UNSUPPORTED — both nets absent, a critic output other than 1.  num_envs == 0 is a no-op.
  * No allocation, no copy, no synchronisation inside.  Not a phase of the step.
  * ---------------------------------------------------------------------------------------- */
 #define GF_MLP_MAX_LAYERS 6            /* Linear layers per net */
@@ -1003,7 +1012,7 @@ typedef struct GfMlpActArgs {
     int64_t num_envs;           /* N >= 0; 0: nothing is launched */
     GfMlpNet actor;             /* output width A <= GF_MLP_MAX_ACTIONS */
     GfMlpNet critic;            /* output width 1 */
-    const float* std;           /* [A] or [N, A] (required with actions) */
+    const float* std;           /* [A] or [N, A] (required with actions): the std, or log_std with std_is_log */
     const float* noise;         /* [N, A] standard normals (parity mode), or NULL: Philox + Box–Muller */
     uint64_t seed;              /* as GfPolicyActArgs */
     uint64_t stream;
@@ -1017,6 +1026,8 @@ typedef struct GfMlpActArgs {
     float* sigma_out;
     float* values_out;
     float* log_prob_out;
+    int32_t std_is_log;         /* 0: `std` is the std, 1: it is log_std (sigma = expf), as GfPolicyActArgs */
+    int32_t _pad;
 } GfMlpActArgs;
 
 /* ------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ with one gf_obs_norm_update, ``fused_mlp`` normalises inside the gf_mlp_act laun
 ``--history frames``: ``RolloutStorage(history="frames")`` — a history observation is stored once per frame (one gf_rollout_frame_write
 launch behind the step's own); ``--output window``: the ObservationManagers hand out strided history windows (``frames`` only).
 ``collector()`` builds one such loop and times batches of it, for scripts that alternate several forms in one process.
-    python tools/bench_collect.py [--sizes 4096,16384,65536] [--forms rsl_rl,fused,fused_mlp] [--steps 240] [--warmup 48] [--reps 5] [--normalize]
+    python tools/bench_collect.py [--sizes 4096,16384,65536] [--forms rsl_rl,fused,fused_mlp] [--steps 240] [--warmup 48] [--reps 5] [--normalize] [--noise-std-type scalar|log]
                                   [--config go2_cmd|gait] [--history rows|frames] [--output fresh|window]"""
 import argparse
 import json
@@ -73,7 +73,8 @@ GAIT_GROUPS = {"policy": ["policy"], "critic": ["policy", "critic"]}   # obs_gro
 class collector:
     """One collection loop: ``batch(steps)`` runs ``steps`` of it and returns µs per step (ending in a device synchronise)."""
 
-    def __init__(self, n: int, form: str, normalize: bool = False, config: str = "go2_cmd", history: str = "rows", output: str = "fresh"):
+    def __init__(self, n: int, form: str, normalize: bool = False, config: str = "go2_cmd", history: str = "rows", output: str = "fresh",
+                 noise_std_type: str = "scalar"):
         old, ObservationManager.default_output = ObservationManager.default_output, output
         try:   # (the managers are created by env.config(), i.e. inside build())
             env = tasks.BASELINE_CONFIGS[config][1](n)
@@ -84,7 +85,7 @@ class collector:
         self.env, self.form, self.state = env, form, env.reset()
         self.store = RolloutStorage(env, T, obs_groups=GAIT_GROUPS if config == "gait" else None, history=history).attach()
         self.store.begin(*self.state)
-        self.step, self.stats, self.rewbuffer = _make_step(env, self.store, form, normalize)
+        self.step, self.stats, self.rewbuffer = _make_step(env, self.store, form, normalize, noise_std_type)
 
     def batch(self, steps: int) -> float:
         obs, extras = self.state
@@ -103,7 +104,7 @@ class collector:
         return statistics.mean(self.rewbuffer) if self.rewbuffer else None
 
 
-def _make_step(env, store, form: str, normalize: bool):
+def _make_step(env, store, form: str, normalize: bool, noise_std_type: str = "scalar"):
     n, A = env.num_envs, env.action_space.shape[0]
     width = {m.name: int(m.observation_space.shape[0]) for m in env.managers["observation"]}
     critic = store.obs_groups["critic"]
@@ -114,14 +115,16 @@ def _make_step(env, store, form: str, normalize: bool):
     torch.manual_seed(0)
     fused_norm = normalize and form != "rsl_rl"
     policy = ActorCriticMLP(store.obs_width, A, num_critic_obs=critic_w, actor_obs_normalization=fused_norm,
-                            critic_obs_normalization=fused_norm).to(gs.device)
+                            critic_obs_normalization=fused_norm, noise_std_type=noise_std_type).to(gs.device)
+    is_log = noise_std_type == "log"
+    std_param = policy.log_std if is_log else policy.std
     gamma = 0.99
     stats, rewbuffer = None, None
     if form == "fused":
         stats = EpisodeStatistics(n)
 
         def step(obs, extras):
-            actions = store.act(policy.act_mean(obs), policy.std, policy.evaluate(cat(obs, extras)))
+            actions = store.act(policy.act_mean(obs), std_param, policy.evaluate(cat(obs, extras)), std_is_log=is_log)
             obs, _rew, _term, trunc, extras = env.step(actions)
             if normalize:
                 policy.update_normalization(obs, parts(obs, extras))
@@ -147,7 +150,8 @@ def _make_step(env, store, form: str, normalize: bool):
 
         def step(obs, extras):
             mean, values = policy.act_mean(actor_norm(obs)), policy.evaluate(critic_norm(cat(obs, extras)))
-            dist = torch.distributions.Normal(mean, policy.std.expand_as(mean))   # rsl_rl ActorCritic.update_distribution
+            std = torch.exp(std_param) if is_log else std_param
+            dist = torch.distributions.Normal(mean, std.expand_as(mean))   # rsl_rl ActorCritic.update_distribution
             actions = dist.sample()
             log_prob = dist.log_prob(actions).sum(dim=-1)
             obs, rew, term, trunc, extras = env.step(actions)
@@ -169,12 +173,13 @@ def _make_step(env, store, form: str, normalize: bool):
 
 
 def run(n: int, form: str, steps: int, warmup: int, reps: int, normalize: bool = False, config: str = "go2_cmd", history: str = "rows",
-        output: str = "fresh") -> dict:
-    c = collector(n, form, normalize, config, history, output)
+        output: str = "fresh", noise_std_type: str = "scalar") -> dict:
+    c = collector(n, form, normalize, config, history, output, noise_std_type)
     if warmup:
         c.batch(warmup)
     times = [c.batch(steps) for _ in range(reps)]
     out = {"tool": "bench_collect", "config": config, "history": history, "output": output, "num_envs": n, "form": form, "normalize": normalize,
+           "noise_std_type": noise_std_type,
            "steps": steps, "warmup": warmup, "reps": reps,
            "us_per_step_best": round(min(times), 2), "us_per_step_median": round(statistics.median(times), 2),
            "recorded_step": c.env._trace is not None, "mean_reward": c.mean_reward()}
@@ -193,6 +198,7 @@ def main() -> None:
     ap.add_argument("--config", default="go2_cmd", choices=["go2_cmd", "gait"], help="the task: bench.py's Go2 config or the gait trainer")
     ap.add_argument("--history", default="rows", choices=["rows", "frames"], help="RolloutStorage(history=): rows, or one entry per frame")
     ap.add_argument("--output", default="fresh", choices=["fresh", "window"], help="what the ObservationManagers hand out")
+    ap.add_argument("--noise-std-type", default="scalar", choices=["scalar", "log"], help="the policy's std parameter: std, or log_std")
     a = ap.parse_args()
     if a.output == "window" and a.history != "frames":
         raise SystemExit("--output window needs --history frames: a row storage copies contiguous observation rows")
@@ -203,7 +209,7 @@ def main() -> None:
         for form in a.forms.split(","):
             if form not in ("rsl_rl", "fused", "fused_mlp"):
                 raise SystemExit(f"unknown form {form!r}")
-            print(json.dumps(run(n, form, a.steps, a.warmup, a.reps, a.normalize, a.config, a.history, a.output)), flush=True)
+            print(json.dumps(run(n, form, a.steps, a.warmup, a.reps, a.normalize, a.config, a.history, a.output, a.noise_std_type)), flush=True)
 
 
 if __name__ == "__main__":

@@ -1429,6 +1429,83 @@ class PPO:
         """The current learning rate (one host read)."""
         return float(self._state_lr[2 * (self._calls & 1)])
 
+    # -- the optimizer state, in torch.optim.Adam's format ---------------------------------------------------------------------------
+    def optimizer_state_dict(self) -> dict:
+        """What ``torch.optim.Adam(policy.parameters(), lr).state_dict()`` would hold now (rsl_rl's ``"optimizer_state_dict"``):
+        ``"state"`` — ``{i: {"step", "exp_avg", "exp_avg_sq"}}`` for parameter ``i`` of the bucket's order (``policy.parameters()``'s),
+        the moments as clones shaped like the parameter, ``step`` the 0-dim tensor the installed torch writes; ``{}`` before the first
+        step, as torch's — and one ``"param_groups"`` entry with the installed torch's own keys, the current ``lr`` (one host read),
+        the module's betas and eps, and ``params = [0 … P-1]``."""
+        # the group's keys and the step's dtype and device come from the installed torch: a throw-away Adam that takes one step
+        dummy = torch.nn.Parameter(torch.zeros(1))
+        dummy.grad = torch.zeros(1)
+        probe = torch.optim.Adam([dummy], lr=1.0)
+        probe.step()
+        probe = probe.state_dict()
+        step_like = probe["state"][0]["step"]
+        params = self.grad_sync.params
+        group = dict(probe["param_groups"][0], lr=self.learning_rate, betas=_ADAM_BETAS, eps=_ADAM_EPS, params=list(range(len(params))))
+        state, off = {}, 0
+        if self._calls > 0:
+            for i, p in enumerate(params):
+                k = p.numel()
+                state[i] = {"step": torch.full_like(step_like, self._calls),
+                            "exp_avg": self.exp_avg[off:off + k].view_as(p).clone(), "exp_avg_sq": self.exp_avg_sq[off:off + k].view_as(p).clone()}
+                off += k
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, sd: dict) -> None:
+        """The inverse: the moments are copied into the flat ``exp_avg`` / ``exp_avg_sq`` in place, ``lr`` and ``step`` go into the slot
+        of the control block the next ``gf_adam_step`` reads.  An empty ``"state"`` zeroes the moments and the step.  ``ValueError`` for
+        what this Adam cannot continue from: another parameter count or shape, ``step`` values that differ between the parameters,
+        ``amsgrad`` / ``weight_decay`` / ``maximize`` off their defaults, betas or eps other than this module's."""
+        groups = sd.get("param_groups") if isinstance(sd, dict) else None
+        if not isinstance(groups, (list, tuple)) or len(groups) != 1 or not isinstance(sd.get("state"), dict):
+            raise ValueError("PPO.load_optimizer_state_dict: expected torch.optim.Adam's {'state', 'param_groups'} with one parameter group")
+        group, state, params = groups[0], sd["state"], self.grad_sync.params
+        if len(group.get("params", ())) != len(params):
+            raise ValueError(f"PPO.load_optimizer_state_dict: the state holds {len(group.get('params', ()))} parameters, the policy {len(params)}")
+        for key, default in (("amsgrad", False), ("weight_decay", 0), ("maximize", False)):
+            if group.get(key, default) != default:
+                raise ValueError(f"PPO.load_optimizer_state_dict: {key}={group[key]!r} is not supported (only Adam's default {default!r})")
+        if tuple(float(b) for b in group.get("betas", _ADAM_BETAS)) != _ADAM_BETAS:
+            raise ValueError(f"PPO.load_optimizer_state_dict: betas={tuple(group['betas'])!r}; this Adam steps with {_ADAM_BETAS}")
+        if float(group.get("eps", _ADAM_EPS)) != _ADAM_EPS:
+            raise ValueError(f"PPO.load_optimizer_state_dict: eps={group['eps']!r}; this Adam steps with {_ADAM_EPS}")
+        if "lr" not in group:
+            raise ValueError("PPO.load_optimizer_state_dict: the parameter group has no lr")
+        lr, step = float(group["lr"]), 0
+        if state:
+            ids = list(group["params"])
+            if sorted(state) != sorted(ids):
+                raise ValueError(f"PPO.load_optimizer_state_dict: the state covers parameters {sorted(state)}, the group lists {sorted(ids)}: a different parameter count")
+            for i, p in zip(ids, params):
+                for name in ("step", "exp_avg", "exp_avg_sq"):
+                    if name not in state[i]:
+                        raise ValueError(f"PPO.load_optimizer_state_dict: parameter {i} has no {name}")
+                for name in ("exp_avg", "exp_avg_sq"):
+                    if tuple(state[i][name].shape) != tuple(p.shape):
+                        raise ValueError(f"PPO.load_optimizer_state_dict: {name} of parameter {i} has shape {tuple(state[i][name].shape)}, the parameter {tuple(p.shape)}")
+            steps = {float(state[i]["step"]) for i in ids}
+            step = int(steps.pop())
+            if steps or step < 0:
+                raise ValueError("PPO.load_optimizer_state_dict: the parameters' step values are not all equal (one flat bucket takes one step count)")
+        with torch.no_grad():
+            if state:
+                off = 0
+                for i, p in zip(ids, params):
+                    k = p.numel()
+                    self.exp_avg[off:off + k].view_as(p).copy_(state[i]["exp_avg"])
+                    self.exp_avg_sq[off:off + k].view_as(p).copy_(state[i]["exp_avg_sq"])
+                    off += k
+            else:
+                self.exp_avg.zero_()
+                self.exp_avg_sq.zero_()
+            par = step & 1   # (the slot the next step reads: every step reads `_calls & 1` and writes the other)
+            self._state_lr[2 * par] = lr
+            self._state[2 * par + 1] = step
+        self._calls = step
+
     def compute_returns(self, last_critic_obs: torch.Tensor) -> None:
         """rsl_rl ``PPO.compute_returns``: the critic's value of the bootstrap observation, then GAE over the storage.  The value is
         torch's forward (so results stay what they were); a loop that wants the one-launch forward passes

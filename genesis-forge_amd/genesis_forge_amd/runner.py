@@ -1,0 +1,270 @@
+"""
+rsl_rl's ``OnPolicyRunner`` over this package's learner (the call site of every ``examples/*/train.py``, ``eval.py`` and
+``gamepad.py``)::
+
+    runner = OnPolicyRunner(env, cfg, log_path, device=gs.device)
+    runner.learn(num_learning_iterations=..., init_at_random_ep_len=False)   # writes model_{it}.pt
+    runner.load(model); policy = runner.get_inference_policy(device=gs.device)
+
+The runner adds no launch of its own.  It composes :class:`~.learner.RolloutStorage`, :class:`~.learner.PolicyForward`,
+:class:`~.learner.EpisodeStatistics`, :class:`~.learner.ActorCriticMLP` and :class:`~.learner.PPO` in the order the ``PPO`` docstring
+gives, writes rsl_rl's checkpoint files (``model_state_dict`` / ``optimizer_state_dict`` / ``iter`` / ``infos``, the optimizer state
+in ``torch.optim.Adam``'s own format) and keeps one log record per iteration.
+"""
+from __future__ import annotations
+
+import json
+import os
+import time
+from typing import Callable, Optional
+
+import torch
+
+from . import gs
+from .learner import ActorCriticMLP, EpisodeStatistics, PolicyForward, PPO, RolloutStorage, _policy_std
+from .wrappers import RslRlWrapper
+
+CHECKPOINT_VERSION = 1   # of the "genesis_forge_amd" block of a checkpoint file
+
+
+class OnPolicyRunner:
+    """``OnPolicyRunner(env, train_cfg, log_dir=None, device=None, *, forward="hip", action_noise=None)``.
+
+    ``env``: a built ``ManagedEnvironment``, possibly inside ``VideoWrapper``, possibly inside ``RslRlWrapper`` (the reference's call
+    site).  An outer ``RslRlWrapper`` only reformats and is stripped; the runner steps whatever is inside it, so a ``VideoWrapper``
+    still sees every step.  The storage is built on ``env.unwrapped`` and attached to it.
+
+    ``train_cfg``: the ``training_cfg()`` dict of ``examples/*/train.py`` as written.  Honoured: ``"policy"`` and
+    ``"empirical_normalization"`` (``ActorCriticMLP.from_train_cfg``), ``"algorithm"`` (``PPO(**…)``), ``"num_steps_per_env"``,
+    ``"save_interval"``, ``"obs_groups"`` (``RolloutStorage``; group members reach the kernels as segments, no ``torch.cat`` on the HIP
+    path) and ``"seed"`` (``store.seed(seed)`` and the runner's own ``torch.Generator`` for the minibatch permutations; without it the
+    storage keeps the env's seed and the generator takes ``torch.initial_seed()``).  Every other top-level key is ignored, as rsl_rl
+    ignores it.  A missing ``"num_steps_per_env"`` or ``"algorithm"`` raises ``ValueError``; what ``from_train_cfg`` or ``PPO`` refuses
+    stays refused, with their messages.
+
+    ``forward``: ``"hip"`` (default) collects with ``store.act_policy(fwd, …)`` — the actor, the critic, the sampling and the rows in
+    one ``gf_mlp_act`` launch — and takes the bootstrap value from ``fwd.value(…)``; ``"torch"`` collects with
+    ``store.act(policy.act_mean(…), std or log_std, policy.evaluate(…), std_is_log=…)`` and ``ppo.compute_returns``.  Nothing switches
+    between them by env count: the only measurements are the three sizes of profiles/r09_mlp_act.md — per collection step the HIP
+    forward is 3.5 x faster than the torch forward at 4 096 envs, 1.4 x faster at 16 384 and 7 % slower at 65 536 — so the choice is
+    the caller's.
+
+    ``action_noise``: a CPU ``torch.Generator``; when given, each step's ``[N, A]`` standard normals are drawn from it and passed as
+    ``noise=``.  Required on a backend that cannot draw (the test-only CPU oracle: ``act`` raises ``RuntimeError`` otherwise), optional on
+    HIP, where the kernel's own Philox draws are the default.
+
+    Attributes: ``alg`` (the ``PPO``; ``alg.policy``), ``current_learning_iteration``, ``log_dir``, ``git_status_repos`` (a plain list
+    the reference assigns to; nothing reads it), ``last_log``.
+
+    Not here: multi-rank training, TensorBoard / W&B writers, recurrent policies, video handling, and the env's own state — as with
+    rsl_rl, a resumed run goes on from the env as it is."""
+
+    def __init__(self, env, train_cfg: dict, log_dir: Optional[str] = None, device=None, *, forward: str = "hip",
+                 action_noise: Optional[torch.Generator] = None):
+        if forward not in ("hip", "torch"):
+            raise ValueError(f"OnPolicyRunner: forward={forward!r} is not supported ('hip' or 'torch')")
+        for key in ("num_steps_per_env", "algorithm"):
+            if key not in train_cfg:
+                raise ValueError(f"OnPolicyRunner: train_cfg has no '{key}'")
+        self.env = env.env if isinstance(env, RslRlWrapper) else env   # (what is stepped)
+        base = self.env.unwrapped
+        self.device = torch.device(gs.device if device is None else device)
+        self.forward, self.action_noise = forward, action_noise
+        self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
+        self.save_interval = int(train_cfg.get("save_interval", 50))
+        self.log_dir = log_dir
+        self.git_status_repos: list = []
+        self.current_learning_iteration = 0
+        self.last_log: Optional[dict] = None
+
+        groups = train_cfg.get("obs_groups")
+        obs_name = "policy" if groups is None or "policy" not in groups or not groups["policy"] else groups["policy"][0]
+        self.storage = store = RolloutStorage(base, self.num_steps_per_env, obs_name=obs_name, obs_groups=groups).attach()
+        width = lambda group: sum(store._widths[m] for m in store.obs_groups[group])
+        policy = ActorCriticMLP.from_train_cfg(train_cfg, width("policy"), base.action_space.shape[0], num_critic_obs=width("critic"))
+        policy = policy.to(self.device)
+        self.alg = PPO(policy, store, **train_cfg["algorithm"])
+        self._fwd = PolicyForward(policy) if forward == "hip" else None
+        self._generator = torch.Generator(device=self.device)
+        seed = train_cfg.get("seed")
+        if seed is None:
+            self._generator.manual_seed(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)
+        else:
+            store.seed(int(seed))
+            self._generator.manual_seed(int(seed))
+        self._shared_critic = list(store.obs_groups["critic"]) == list(store.obs_groups["policy"])
+
+    # -- observations ---------------------------------------------------------------------------------------------------------------
+    def _inputs(self, obs: torch.Tensor, extras: dict):
+        """(actor input, critic input or None where the critic reads the actor's) of this step: a tensor, or the group's members as a
+        tuple of segments."""
+        store = self.storage
+        rows = extras.get("observations", {}) if extras is not None else {}
+
+        def group(names):
+            parts = tuple(obs if m == store.obs_name else rows[m] for m in names)
+            return parts[0] if len(parts) == 1 else parts
+
+        return group(store.obs_groups["policy"]), None if self._shared_critic else group(store.obs_groups["critic"])
+
+    @staticmethod
+    def _cat(x) -> torch.Tensor:
+        return x if isinstance(x, torch.Tensor) else torch.cat(x, dim=-1)
+
+    def _noise(self, n: int, A: int) -> Optional[torch.Tensor]:
+        if self.action_noise is None:
+            return None
+        return torch.randn(n, A, generator=self.action_noise).to(self.device)
+
+    # -- one iteration ----------------------------------------------------------------------------------------------------------------
+    def _collect(self, obs: torch.Tensor, extras: dict, stats: EpisodeStatistics):
+        """``num_steps_per_env`` steps: act -> step -> update_normalization -> process_env_step; returns the last (obs, extras)."""
+        store, ppo, policy, env = self.storage, self.alg, self.alg.policy, self.env
+        n, A = store.env.num_envs, ppo.num_actions
+        for _ in range(self.num_steps_per_env):
+            x, cx = self._inputs(obs, extras)
+            if self._fwd is not None:
+                actions = store.act_policy(self._fwd, x, cx, noise=self._noise(n, A))
+            else:
+                std, is_log = _policy_std(policy)   # (std, or log_std with std_is_log)
+                with torch.no_grad():
+                    mean = policy.act_mean(self._cat(x))
+                    values = policy.evaluate(self._cat(x if cx is None else cx))
+                actions = store.act(mean, std.detach(), values, noise=self._noise(n, A), std_is_log=is_log)
+            obs, _rew, _terminated, truncated, extras = env.step(actions)
+            x, cx = self._inputs(obs, extras)
+            policy.update_normalization(x, cx)
+            store.process_env_step(truncated, gamma=ppo.gamma, episodes=stats)
+        return obs, extras
+
+    def _returns(self, obs: torch.Tensor, extras: dict) -> None:
+        x, cx = self._inputs(obs, extras)
+        last = x if cx is None else cx
+        if self._fwd is not None:
+            self.storage.compute_returns(self._fwd.value(last), gamma=self.alg.gamma, lam=self.alg.lam)
+        else:
+            self.alg.compute_returns(self._cat(last))
+
+    def learn(self, num_learning_iterations: int, init_at_random_ep_len: bool = False) -> None:
+        """rsl_rl's ``OnPolicyRunner.learn``: iterations ``current_learning_iteration … + num_learning_iterations``, each
+        ``num_steps_per_env`` collection steps, the returns and ``PPO.update``.  With ``log_dir`` set, ``model_{it}.pt`` is written when
+        ``it % save_interval == 0`` and once more after the loop (``model_{current_learning_iteration}.pt``, the last iteration run —
+        rsl_rl's rule, so a resumed run starts at that index), and each iteration's log record is appended to ``progress.jsonl``.
+        The episode statistics are fresh per call, as rsl_rl's buffers are locals of ``learn``.
+        ``init_at_random_ep_len``: every env's ``episode_length`` starts at a random value below its ``max_episode_length``."""
+        env, base, store = self.env, self.env.unwrapped, self.storage
+        if init_at_random_ep_len:
+            self._randomize_episode_length(base)
+        obs = env.get_observations()
+        extras = base.extras
+        store.begin(obs if store.obs_name == "policy" else extras["observations"][store.obs_name], extras)
+        self.train_mode()
+        stats = EpisodeStatistics(base.num_envs)
+        if self.log_dir is not None:
+            os.makedirs(self.log_dir, exist_ok=True)
+        start = self.current_learning_iteration
+        for it in range(start, start + int(num_learning_iterations)):
+            t0 = time.perf_counter()
+            obs, extras = self._collect(obs, extras, stats)
+            self._returns(obs, extras)
+            t1 = time.perf_counter()
+            losses = self.alg.update(generator=self._generator)
+            t2 = time.perf_counter()
+            self.current_learning_iteration = it
+            self._log(it, losses, stats, t1 - t0, t2 - t1)
+            if self.log_dir is not None and it % self.save_interval == 0:
+                self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
+        if self.log_dir is not None:
+            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+
+    @staticmethod
+    def _randomize_episode_length(base) -> None:
+        limit = getattr(base, "max_episode_length", None)
+        if limit is None:
+            limit = getattr(base, "max_episode_length_steps", None)
+            if limit is None:
+                raise ValueError("init_at_random_ep_len=True needs an env with a max_episode_length")
+        length = base.episode_length
+        with torch.no_grad():   # randint(0, max) per env: floor(U[0, 1) * max)
+            top = (limit if isinstance(limit, torch.Tensor) else torch.full_like(length, int(limit))).to(length.dtype)
+            drawn = (torch.rand(length.shape, device=length.device) * top.to(torch.float32)).to(length.dtype)
+            length.copy_(torch.minimum(drawn, top - 1).clamp_(min=0))   # (the f32 product may round up to max itself)
+
+    def _log(self, it: int, losses: dict, stats: EpisodeStatistics, collection_s: float, learn_s: float) -> None:
+        """One record per iteration (the runner's own host reads are all here).  ``collection_time`` is the host's time to enqueue the
+        rollout and ``learn_time`` ends at the update's one host read, which waits for the device: their sum is the iteration's."""
+        steps = self.num_steps_per_env * self.storage.env.num_envs
+        record = {"iteration": it, "value_function": losses["value_function"], "surrogate": losses["surrogate"], "entropy": losses["entropy"],
+                  "learning_rate": self.alg.learning_rate, "mean_action_std": float(self.alg.policy.action_std.mean()),
+                  "mean_reward": stats.mean_reward(), "mean_episode_length": stats.mean_episode_length(),
+                  "steps_per_second": steps / max(collection_s + learn_s, 1e-9), "collection_time": collection_s, "learn_time": learn_s}
+        self.last_log = record
+        if self.log_dir is not None:
+            with open(os.path.join(self.log_dir, "progress.jsonl"), "a") as f:
+                f.write(json.dumps(record) + "\n")
+
+    # -- checkpoints --------------------------------------------------------------------------------------------------------------------
+    def save(self, path: str, infos=None) -> None:
+        """rsl_rl's checkpoint: ``{"model_state_dict", "optimizer_state_dict", "iter", "infos"}`` — the state dict's tensors cloned (the
+        parameters are views of ``PPO``'s flat buffer; the file does not carry that storage), the optimizer state in
+        ``torch.optim.Adam``'s format — plus this package's own ``"genesis_forge_amd"`` block, which rsl_rl never looks at: the format
+        version, the storage's action-noise seed and stream, the permutation generator's state and, where the runner draws its noise
+        from ``action_noise``, that generator's state."""
+        store = self.storage
+        torch.save({
+            "model_state_dict": {k: v.detach().clone() for k, v in self.alg.policy.state_dict().items()},
+            "optimizer_state_dict": self.alg.optimizer_state_dict(),
+            "iter": self.current_learning_iteration,
+            "infos": infos,
+            "genesis_forge_amd": {"version": CHECKPOINT_VERSION, "act_seed": store._act_seed, "act_stream": store._act_stream,
+                                  "generator_state": self._generator.get_state(),
+                                  "action_noise_state": None if self.action_noise is None else self.action_noise.get_state()},
+        }, path)
+
+    def load(self, path: str, load_optimizer: bool = True):
+        """rsl_rl's ``load``: the policy (copied in place, so the parameters stay views of ``PPO``'s flat buffer — checked), the optimizer
+        state unless ``load_optimizer=False``, ``current_learning_iteration``, and this package's block if the file has one (a file with
+        rsl_rl's four keys alone loads too).  Returns ``infos``.  A ``model_state_dict`` that does not fit raises torch's own error."""
+        loaded = torch.load(path, map_location=self.device, weights_only=False)
+        ppo = self.alg
+        ppo.policy.load_state_dict(loaded["model_state_dict"])
+        lo, hi = ppo.params.data_ptr(), ppo.params.data_ptr() + ppo.params.numel() * ppo.params.element_size()
+        for name, p in ppo.policy.named_parameters():
+            if p.requires_grad and not lo <= p.data_ptr() < hi:
+                raise RuntimeError(f"OnPolicyRunner.load: parameter '{name}' no longer lives in PPO's flat buffer")
+        if load_optimizer:
+            ppo.load_optimizer_state_dict(loaded["optimizer_state_dict"])
+        self.current_learning_iteration = int(loaded["iter"])
+        ours = loaded.get("genesis_forge_amd")
+        if ours is not None:
+            if ours.get("version") != CHECKPOINT_VERSION:
+                raise ValueError(f"OnPolicyRunner.load: 'genesis_forge_amd' block of version {ours.get('version')!r}; this build reads {CHECKPOINT_VERSION}")
+            self.storage._act_seed, self.storage._act_stream = ours["act_seed"], int(ours["act_stream"])
+            self._generator.set_state(ours["generator_state"].cpu())
+            if self.action_noise is not None and ours.get("action_noise_state") is not None:
+                self.action_noise.set_state(ours["action_noise_state"].cpu())
+        return loaded.get("infos")
+
+    # -- inference ----------------------------------------------------------------------------------------------------------------------
+    def get_inference_policy(self, device=None) -> Callable:
+        """``policy(obs) -> [N, A]`` in eval mode (the normalisers no longer update).  ``forward="hip"``: ``PolicyForward.mean`` — one
+        launch, the normaliser applied inside; otherwise ``policy.act_mean`` under ``no_grad``.  ``obs``: a tensor or a sequence of
+        segments, under ``PolicyForward``'s rules."""
+        self.eval_mode()
+        if device is not None and torch.device(device).type != self.device.type:   # (moving the module would take its parameters out of PPO's flat buffer)
+            raise ValueError(f"get_inference_policy: the policy lives on {self.device}; device={device!r} is not supported")
+        if self._fwd is not None:
+            return self._fwd.mean
+        policy = self.alg.policy
+
+        def act_mean(obs):
+            with torch.no_grad():
+                return policy.act_mean(self._cat(tuple(obs) if isinstance(obs, (list, tuple)) else obs))
+
+        return act_mean
+
+    def train_mode(self) -> None:
+        self.alg.policy.train()
+
+    def eval_mode(self) -> None:
+        self.alg.policy.eval()

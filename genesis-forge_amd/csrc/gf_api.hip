@@ -79,6 +79,8 @@ GF_EXPORT int gf_sizeof(int which) {
         case 28: return (int)sizeof(GfMlpActArgs);
         case 29: return (int)sizeof(GfObsNormArgs);
         case 30: return (int)sizeof(GfRolloutFrameArgs);
+        case 31: return (int)sizeof(GfMirrorRowsArgs);
+        case 32: return (int)sizeof(GfMirrorLossArgs);
         default: return -1;
     }
 }

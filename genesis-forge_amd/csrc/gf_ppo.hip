@@ -9,7 +9,8 @@
 // of the workspace; a one-workgroup launch sums the records in a fixed order, one wave per column.  With sigma_is_log `sigma` is
 // log_std: every loaded element goes through policy_sigma (gf_policy_row.h, gf_policy_act's expf) and the finalize launch writes
 // d loss / d log_std = grad_sigma · sigma, one more f32 product.  Algorithmic traffic per row: R 16A + 20 (+ 8A
-// re-read of mu / actions), W 4A + 4 bytes.
+// re-read of mu / actions), W 4A + 4 bytes.  kl_rows > 0: rows past it add nothing to the KL sum and read row 0 of old_mu /
+// old_sigma (which end at kl_rows); the finalize launch divides the KL sum by kl_rows.
 //
 // gf_adam_step: launch 1 — each workgroup sums g^2 of its 1 024-element chunks (double) into one partial; launch 2 — every
 // workgroup sums all partials in the same order (so all agree on the norm without a hand-off), applies the schedule to
@@ -64,8 +65,9 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_loss_rows_kernel(const GfPpoLos
     GF_GLOBAL double* rec = G(reinterpret_cast<double*>(a.workspace)) + blockIdx.x;   // record q of this workgroup: rec[q * nb]
     const GF_GLOBAL float* mu = G(a.mu) + row;
     const GF_GLOBAL float* x = G(a.actions) + row;
-    const GF_GLOBAL float* omu = G(a.old_mu) + row;
-    const GF_GLOBAL float* osd = G(a.old_sigma) + row;
+    const bool in_kl = a.kl_rows == 0 || i < a.kl_rows;   // the KL covers the first kl_rows rows (0: all); old_mu / old_sigma end there
+    const GF_GLOBAL float* omu = G(a.old_mu) + (in_kl ? row : 0);
+    const GF_GLOBAL float* osd = G(a.old_sigma) + (in_kl ? row : 0);
     const GF_GLOBAL float* sd = G(a.sigma);
     // pass 1: log_prob and KL of the row
     float lp = 0.0f, kl = 0.0f;
@@ -127,7 +129,7 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_loss_rows_kernel(const GfPpoLos
         dv = -(gv * (2.0f * e));
     }
     if (in && a.grad_value) G(a.grad_value)[i] = dv;
-    const double sums3[3] = {in ? (double)surr : 0.0, in ? (double)vl : 0.0, in ? (double)kl : 0.0};
+    const double sums3[3] = {in ? (double)surr : 0.0, in ? (double)vl : 0.0, in && in_kl ? (double)kl : 0.0};
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
         const double t = block_sum_d(sums3[q], s_w);
@@ -200,7 +202,8 @@ __global__ __launch_bounds__(kPpoFinBlock) void ppo_loss_finalize_kernel(const G
         const float e = kPpoEntropyC + logf(policy_sigma(G(a.sigma)[c], a.sigma_is_log));
         ent = c == 0 ? e : ent + e;
     }
-    const float surrogate = (float)(s_tot[0] / mb), value_loss = (float)(s_tot[1] / mb), kl_mean = (float)(s_tot[2] / mb);
+    const double kl_n = a.kl_rows ? (double)a.kl_rows : mb;
+    const float surrogate = (float)(s_tot[0] / mb), value_loss = (float)(s_tot[1] / mb), kl_mean = (float)(s_tot[2] / kl_n);
     const float loss = (surrogate + a.value_loss_coef * value_loss) - a.entropy_coef * ent;
     GF_GLOBAL float* out = G(a.out);
     out[0] = surrogate;
@@ -345,7 +348,7 @@ extern "C" __attribute__((visibility("default"))) int gf_ppo_loss(const GfPpoLos
     const int grads = (a->grad_mu != nullptr) + (a->grad_value != nullptr) + (a->grad_sigma != nullptr);
     if (grads != 0 && grads != 3) return GF_E_NULL;   // half a gradient set
     if (a->num_rows < 0 || a->num_actions < 1 || (a->use_clipped_value_loss != 0 && a->use_clipped_value_loss != 1) ||
-        (a->sigma_is_log != 0 && a->sigma_is_log != 1))
+        (a->sigma_is_log != 0 && a->sigma_is_log != 1) || a->kl_rows < 0 || a->kl_rows > a->num_rows)
         return GF_E_RANGE;
     if (a->num_rows == 0) return GF_OK;
     const int64_t nb = (a->num_rows + gf::kPpoBlock - 1) / gf::kPpoBlock;

@@ -10,8 +10,9 @@ reference's operator interface.  ``install_as_genesis_forge()`` registers it und
 from .genesis_env import GenesisEnv, EnvMode
 from .managed_env import ManagedEnvironment
 from .runner import OnPolicyRunner
+from .symmetry import MirrorSymmetry
 
-__all__ = ["GenesisEnv", "ManagedEnvironment", "EnvMode", "OnPolicyRunner", "install_as_genesis_forge"]
+__all__ = ["GenesisEnv", "ManagedEnvironment", "EnvMode", "OnPolicyRunner", "MirrorSymmetry", "install_as_genesis_forge"]
 __version__ = "0.1.0"
 
 

@@ -13,7 +13,7 @@ import ctypes as C
 import os
 from typing import Optional
 
-GF_ABI_VERSION = 10
+GF_ABI_VERSION = 11
 GF_MAX_TERMS = 24
 GF_MAX_TERM_TERMS = 16
 GF_MAX_OBS_ITEMS = 24
@@ -369,13 +369,48 @@ class GfPpoLossArgs(C.Structure):
     _fields_ = [("num_rows", C.c_int64), ("num_actions", C.c_int32), ("use_clipped_value_loss", C.c_int32), ("mu", P), ("sigma", P),
                 ("value", P), ("actions", P), ("old_log_prob", P), ("advantages", P), ("target_values", P), ("returns", P), ("old_mu", P),
                 ("old_sigma", P), ("clip_param", C.c_float), ("value_loss_coef", C.c_float), ("entropy_coef", C.c_float), ("sigma_is_log", C.c_int32),
-                ("grad_mu", P), ("grad_value", P), ("grad_sigma", P), ("out", P), ("sums", P), ("workspace", P), ("workspace_bytes", C.c_int64)]
+                ("grad_mu", P), ("grad_value", P), ("grad_sigma", P), ("out", P), ("sums", P), ("workspace", P), ("workspace_bytes", C.c_int64),
+                ("kl_rows", C.c_int64)]   # 0: the KL covers every row; 1 … num_rows: the first kl_rows rows (the originals of an augmented minibatch)
 
 
 class GfAdamArgs(C.Structure):
     _fields_ = [("numel", C.c_int64), ("params", P), ("grads", P), ("exp_avg", P), ("exp_avg_sq", P), ("state", P), ("kl_mean", P),
                 ("workspace", P), ("workspace_bytes", C.c_int64), ("desired_kl", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
                 ("eps", C.c_double), ("max_grad_norm", C.c_float), ("schedule", C.c_int32), ("parity", C.c_int32), ("_pad", C.c_int32)]
+
+
+# mirror symmetry of the PPO update (symmetry.MirrorSymmetry, learner.PPO(symmetry_cfg=...)): gf_mirror_rows / gf_mirror_loss, not in
+# ABI_STRUCTS either
+GF_SIZEOF_MIRROR_ROWS = 31
+GF_SIZEOF_MIRROR_LOSS = 32
+GF_MIRROR_MAX_FIELDS = 4
+GF_MIRROR_MAX_SCALARS = 4
+GF_MIRROR_MAX_WIDTH = 8192
+GF_MIRROR_LOSS_BLOCK_ROWS = 256
+
+
+def mirror_loss_workspace_bytes(mb: int) -> int:
+    """GF_MIRROR_LOSS_WORKSPACE_BYTES: one double per workgroup of GF_MIRROR_LOSS_BLOCK_ROWS rows."""
+    return -(-int(mb) // GF_MIRROR_LOSS_BLOCK_ROWS) * 8
+
+
+class GfMirrorField(C.Structure):
+    _fields_ = [("src", P), ("dst_copy", P), ("dst_mirror", P), ("perm", P), ("sign", P), ("in_mean", P), ("in_std", P),
+                ("in_eps", C.c_float), ("width", C.c_int32), ("row_stride", C.c_int32), ("_pad", C.c_int32)]
+
+
+class GfMirrorScalar(C.Structure):
+    _fields_ = [("src", P), ("dst", P)]
+
+
+class GfMirrorRowsArgs(C.Structure):
+    _fields_ = [("num_rows", C.c_int64), ("num_fields", C.c_int32), ("num_scalars", C.c_int32),
+                ("fields", GfMirrorField * GF_MIRROR_MAX_FIELDS), ("scalars", GfMirrorScalar * GF_MIRROR_MAX_SCALARS)]
+
+
+class GfMirrorLossArgs(C.Structure):
+    _fields_ = [("num_rows", C.c_int64), ("num_actions", C.c_int32), ("coeff", C.c_float), ("mu_mirror", P), ("mu_orig", P), ("perm", P),
+                ("sign", P), ("grad", P), ("out", P), ("sums", P), ("workspace", P), ("workspace_bytes", C.c_int64)]
 
 
 # the actor-critic forward of a collection step (learner.PolicyForward / RolloutStorage.act_policy): gf_mlp_act, not in ABI_STRUCTS either
@@ -669,7 +704,8 @@ class HipBackend(Backend):
         for fn, idx, st in (("gf_policy_act", GF_SIZEOF_POLICY_ACT, GfPolicyActArgs), ("gf_episode_step", GF_SIZEOF_EPISODE, GfEpisodeArgs),
                             ("gf_ppo_loss", GF_SIZEOF_PPO_LOSS, GfPpoLossArgs), ("gf_adam_step", GF_SIZEOF_ADAM, GfAdamArgs),
                             ("gf_mlp_act", GF_SIZEOF_MLP_ACT, GfMlpActArgs), ("gf_obs_norm_update", GF_SIZEOF_OBS_NORM, GfObsNormArgs),
-                            ("gf_rollout_frame_write", GF_SIZEOF_ROLLOUT_FRAME, GfRolloutFrameArgs)):
+                            ("gf_rollout_frame_write", GF_SIZEOF_ROLLOUT_FRAME, GfRolloutFrameArgs),
+                            ("gf_mirror_rows", GF_SIZEOF_MIRROR_ROWS, GfMirrorRowsArgs), ("gf_mirror_loss", GF_SIZEOF_MIRROR_LOSS, GfMirrorLossArgs)):
             n = self.lib.gf_sizeof(idx)
             if n != C.sizeof(st):
                 raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")
@@ -737,6 +773,18 @@ class HipBackend(Backend):
         rc = self.lib.gf_adam_step(C.byref(args), self._stream())
         if rc != 0:
             self._raise("adam_step", rc)
+
+    def mirror_rows(self, args) -> None:
+        """gf_mirror_rows on the current stream (learner.PPO.update with a symmetry_cfg)."""
+        rc = self.lib.gf_mirror_rows(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("mirror_rows", rc)
+
+    def mirror_loss(self, args) -> None:
+        """gf_mirror_loss on the current stream (learner.PPO.update with a symmetry_cfg)."""
+        rc = self.lib.gf_mirror_loss(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("mirror_loss", rc)
 
     def mlp_act(self, args) -> None:
         """gf_mlp_act on the current stream (learner.PolicyForward, learner.RolloutStorage.act_policy)."""

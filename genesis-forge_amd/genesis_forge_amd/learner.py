@@ -38,10 +38,13 @@ dependency and stays one; this module provides the two pieces of it that touch t
 * :class:`PPO` — rsl_rl's ``PPO.update`` for the ``"algorithm"`` dict of ``examples/*/train.py``: per minibatch the MLP forward /
   backward stay in torch, the loss and its gradient w.r.t. the policy outputs are one ``gf_ppo_loss`` (two launches), the adaptive
   learning rate, ``clip_grad_norm_`` and Adam over the flat gradient bucket are one ``gf_adam_step`` (two launches) — no host
-  synchronisation per minibatch; the three logged means are read once per update.
+  synchronisation per minibatch; the three logged means are read once per update.  With rsl_rl's ``symmetry_cfg`` (a
+  :class:`~genesis_forge_amd.symmetry.MirrorSymmetry` as its function) the augmented minibatch is one ``gf_mirror_rows`` and the mirror
+  loss with its gradient one ``gf_mirror_loss``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import statistics
@@ -1337,12 +1340,13 @@ _PPO_KEYS = ("clip_param", "desired_kl", "entropy_coef", "gamma", "lam", "learni
 _PPO_DEFAULTS = dict(clip_param=0.2, desired_kl=0.01, entropy_coef=0.01, gamma=0.99, lam=0.95, learning_rate=0.001, max_grad_norm=1.0,
                      num_learning_epochs=5, num_mini_batches=4, schedule="adaptive", use_clipped_value_loss=True, value_loss_coef=1.0)
 # rsl_rl keys whose default is all this class does: accepted with that value only
-_PPO_ONLY_DEFAULT = {"normalize_advantage_per_mini_batch": False, "rnd_cfg": None, "symmetry_cfg": None}
+_PPO_ONLY_DEFAULT = {"normalize_advantage_per_mini_batch": False, "rnd_cfg": None}
+_SYMMETRY_KEYS = ("use_data_augmentation", "use_mirror_loss", "mirror_loss_coeff", "data_augmentation_func")   # rsl_rl's symmetry_cfg
 _ADAM_BETAS, _ADAM_EPS = (0.9, 0.999), 1e-8   # torch.optim.Adam's defaults, as rsl_rl constructs it
 
 
 class PPO:
-    """rsl_rl's ``PPO`` (non-recurrent, no RND, no symmetry) over a :class:`RolloutStorage` and an :class:`ActorCriticMLP`.
+    """rsl_rl's ``PPO`` (non-recurrent, no RND) over a :class:`RolloutStorage` and an :class:`ActorCriticMLP`.
 
     ``PPO(policy, storage, **train_cfg["algorithm"])`` takes the dict of ``examples/*/train.py`` as written (``class_name`` is
     ignored); unknown keys and unsupported values raise ``ValueError``.  ``grad_sync``: the :class:`GradientAllReduce` of a multi-rank
@@ -1365,11 +1369,22 @@ class PPO:
         obs, rew, term, trunc, extras = env.step(actions)
         policy.update_normalization(obs)
         storage.process_env_step(trunc, gamma=ppo.gamma, episodes=stats)
+
+    ``symmetry_cfg`` (rsl_rl's dict: ``use_data_augmentation``, ``use_mirror_loss``, ``mirror_loss_coeff``, ``data_augmentation_func``)
+    is honoured when its function is a :class:`~genesis_forge_amd.symmetry.MirrorSymmetry` whose tables fit the policy input, the
+    critic input and the actions; anything else — no function, a string, a plain callable (the HIP path runs tables, not Python),
+    other widths, other keys — raises ``ValueError``.  Augmentation: the minibatch is gathered raw, ONE ``gf_mirror_rows`` writes the
+    originals and their mirrors (observations through the normalisers, actions, the four replicated per-row scalars), the actor and
+    the critic run on ``2·mb`` rows and ``gf_ppo_loss`` takes the KL of the schedule from the first ``mb`` (``kl_rows``).  The symmetry
+    loss ``MSE(actor(mirror(obs)), mirror(actor(obs)).detach())`` is one ``gf_mirror_loss``: on the ``mu`` of that forward when
+    augmenting, on one extra actor forward of the mirrored rows otherwise; its gradient joins the update only with
+    ``use_mirror_loss`` (``mirror_loss_coeff`` times), and ``update()`` returns its mean as ``"symmetry"`` either way.
     """
 
     def __init__(self, policy: "ActorCriticMLP", storage: RolloutStorage, grad_sync: Optional[GradientAllReduce] = None, **algorithm):
         algorithm = dict(algorithm)
         algorithm.pop("class_name", None)
+        symmetry_cfg = algorithm.pop("symmetry_cfg", None)
         bad = [k for k in algorithm if k not in _PPO_KEYS and k not in _PPO_ONLY_DEFAULT]
         if bad:
             raise ValueError(f"PPO: unsupported algorithm keys {sorted(bad)}")
@@ -1397,6 +1412,7 @@ class PPO:
         if std is None or std.dim() != 1:
             raise ValueError("PPO needs a policy with act_mean(), evaluate() and a [A] std (or, with noise_std_type='log', log_std) parameter (ActorCriticMLP)")
         self.num_actions = int(std.numel())
+        self.symmetry = self._parse_symmetry(symmetry_cfg)   # None, or {"func", "augment", "mirror", "coeff"}
         self.grad_sync = grad_sync if grad_sync is not None else GradientAllReduce(policy.parameters())
         sync = self.grad_sync
         ids = {id(p) for p in sync.params}
@@ -1420,9 +1436,43 @@ class PPO:
         self._calls = 0
         self._adam_ws = torch.zeros(max(1, nat.adam_workspace_bytes(self.params.numel()) // 8), device=dev, dtype=torch.float64)
         self._out = torch.zeros(nat.GF_PPO_OUT_COUNT, device=dev, dtype=torch.float32)   # surrogate, value_loss, entropy, kl_mean, loss
-        self._sums = torch.zeros(3, device=dev, dtype=torch.float64)                      # value_function, surrogate, entropy
+        self._sums = torch.zeros(4, device=dev, dtype=torch.float64)                      # value_function, surrogate, entropy, symmetry
         self._mb_key = None
         self._loss_args, self._adam_args = nat.GfPpoLossArgs(), nat.GfAdamArgs()
+        if self.symmetry is not None:   # the tables go up here, once: no copy from the host inside an update
+            for kind in ("policy", "critic", "actions"):
+                self.symmetry["func"].tables(kind, dev)
+        self._sym_key = None
+        self._mir_args, self._mir_loss_args = nat.GfMirrorRowsArgs(), nat.GfMirrorLossArgs()
+
+    def _parse_symmetry(self, cfg) -> Optional[dict]:
+        """rsl_rl's ``symmetry_cfg`` as this class runs it, or ``ValueError`` (always naming ``symmetry_cfg``)."""
+        from .symmetry import MirrorSymmetry
+
+        if cfg is None:
+            return None
+        if not isinstance(cfg, dict):
+            raise ValueError(f"PPO: symmetry_cfg={cfg!r} must be a dict (or None)")
+        bad = sorted(k for k in cfg if k not in _SYMMETRY_KEYS)
+        if bad:
+            raise ValueError(f"PPO: symmetry_cfg has unsupported keys {bad} (honoured: {list(_SYMMETRY_KEYS)})")
+        fn = cfg.get("data_augmentation_func")
+        if fn is None:
+            raise ValueError("PPO: symmetry_cfg needs a data_augmentation_func (a MirrorSymmetry): without one there is nothing to mirror with")
+        if isinstance(fn, str):
+            raise ValueError(f"PPO: symmetry_cfg data_augmentation_func={fn!r} is a string; pass the MirrorSymmetry object itself "
+                             "(nothing is resolved by name)")
+        if not isinstance(fn, MirrorSymmetry):
+            raise ValueError(f"PPO: symmetry_cfg data_augmentation_func is {type(fn).__name__}: the HIP path cannot run a Python callable — "
+                             "it mirrors with the validated tables of a genesis_forge_amd.MirrorSymmetry")
+        st = self.storage
+        width = lambda group: sum(st._widths[m] for m in st.obs_groups[group])
+        for what, have, want in (("policy observation", fn.obs_width, width("policy")), ("critic observation", fn.critic_obs_width, width("critic")),
+                                 ("action", fn.num_actions, self.num_actions)):
+            if have != want:
+                raise ValueError(f"PPO: symmetry_cfg: the {what} table of the MirrorSymmetry is {have} wide, the {what} {want}")
+        return {"func": fn, "augment": bool(cfg.get("use_data_augmentation", False)), "mirror": bool(cfg.get("use_mirror_loss", False)),
+                "coeff": float(cfg.get("mirror_loss_coeff", 0.0))}
 
     @property
     def learning_rate(self) -> float:
@@ -1516,15 +1566,30 @@ class PPO:
 
     def update(self, generator: Optional[torch.Generator] = None) -> Dict[str, float]:
         """``num_learning_epochs x num_mini_batches`` minibatches of ``storage.mini_batch_generator`` (``generator``: its randperm's);
-        returns rsl_rl 3.x's ``{"value_function", "surrogate", "entropy"}`` means — the one host read of the update."""
+        returns rsl_rl 3.x's ``{"value_function", "surrogate", "entropy"}`` means — and ``"symmetry"`` with a ``symmetry_cfg`` — the one
+        host read of the update."""
         self._sums.zero_()
         norms = self._normalizers()
-        for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, generator=generator,
-                                                       obs_normalizer=norms[0], critic_obs_normalizer=norms[1]):
-            self._minibatch(batch, norms)
-        vf, surr, ent = self._sums.tolist()
+        if self.symmetry is None:
+            for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, generator=generator,
+                                                           obs_normalizer=norms[0], critic_obs_normalizer=norms[1]):
+                self._minibatch(batch, norms)
+        else:
+            for batch in self._symmetry_batches(generator, norms):
+                self._minibatch_symmetry(batch, norms)
+        vf, surr, ent, symm = self._sums.tolist()
         k = self.num_learning_epochs * self.num_mini_batches
-        return {"value_function": vf / k, "surrogate": surr / k, "entropy": ent / k}
+        out = {"value_function": vf / k, "surrogate": surr / k, "entropy": ent / k}
+        if self.symmetry is not None:
+            out["symmetry"] = symm / k
+        return out
+
+    def _symmetry_batches(self, generator, norms) -> Iterator[MiniBatch]:
+        """The minibatches ``_minibatch_symmetry`` takes: the observations RAW (the mirror is taken of the raw value; ``gf_mirror_rows``
+        normalises), the critic's rows too when augmenting — otherwise they are not mirrored and the gather normalises them as ever."""
+        critic_norm = None if self.symmetry["augment"] else norms[1]
+        return self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, generator=generator,
+                                                 obs_normalizer=None, critic_obs_normalizer=critic_norm)
 
     # -- one minibatch ------------------------------------------------------------------------------------------------------------
     def _normalizers(self):
@@ -1553,6 +1618,146 @@ class PPO:
         else:
             self._adam_torch()
 
+    # -- one minibatch with a symmetry_cfg ---------------------------------------------------------------------------------------------
+    def _minibatch_symmetry(self, b: MiniBatch, norms=(None, None)) -> None:
+        """One minibatch of ``_symmetry_batches`` (rsl_rl PPO.update with ``symmetry``).  ``norms``: the policy's normalisers —
+        applied here, by ``gf_mirror_rows`` (or by the policy's own modules on a backend without it)."""
+        sync, backend = self.grad_sync, self.storage.env.backend
+        sync.zero_grad()
+        if getattr(backend, "mirror_rows", None) is None:   # (the test-only oracle backend) the same arithmetic in torch
+            self._symmetry_torch(b)
+        else:
+            self._symmetry_hip(backend, b, norms)
+        self._reduce_kl()
+        sync.average()
+        sync.wait()
+        if getattr(backend, "ppo_loss", None) is not None:
+            self._adam_hip(backend)
+        else:
+            self._adam_torch()
+
+    def _symmetry_torch(self, b: MiniBatch) -> None:
+        """rsl_rl's lines through the MirrorSymmetry's ``__call__`` (plain torch): ``b`` carries raw observations, the policy's own
+        normaliser modules apply (``act_mean`` / ``evaluate``) — except the critic's rows of a batch that is not augmented, which the
+        gather normalised."""
+        sym, policy = self.symmetry, self.policy
+        fn, mb = sym["func"], int(b.actions.shape[0])
+        if sym["augment"]:
+            obs, actions = fn(obs=b.obs, actions=b.actions, env=self.storage.env, obs_type="policy")
+            critic_obs, _ = fn(obs=b.critic_obs, actions=None, env=self.storage.env, obs_type="critic")
+            rep = lambda t: t.repeat(fn.num_aug)
+            b2 = b._replace(obs=obs, critic_obs=critic_obs, actions=actions, values=rep(b.values), advantages=rep(b.advantages),
+                            returns=rep(b.returns), old_log_prob=rep(b.old_log_prob))
+            mu, value = policy.act_mean(obs), policy.evaluate(critic_obs)
+            mu_all = mu
+        else:
+            b2 = b
+            mu = policy.act_mean(b.obs)
+            normed = isinstance(getattr(policy, "critic_obs_normalizer", None), EmpiricalNormalization)
+            value = policy.critic(b.critic_obs) if normed else policy.evaluate(b.critic_obs)
+            obs2, _ = fn(obs=b.obs, actions=None, env=self.storage.env, obs_type="policy")
+            with contextlib.nullcontext() if sym["mirror"] else torch.no_grad():
+                mu_all = torch.cat([mu, policy.act_mean(obs2[mb:])], dim=0)
+        _, target = fn(obs=None, actions=mu_all[:mb].detach(), env=self.storage.env)
+        symmetry_loss = torch.nn.functional.mse_loss(mu_all[mb:], target[mb:])
+        self._loss_torch(mu, value, b2, kl_rows=mb if sym["augment"] else 0, extra=sym["coeff"] * symmetry_loss if sym["mirror"] else None)
+        with torch.no_grad():
+            self._sums[3].add_(symmetry_loss.detach().to(torch.float64))
+
+    def _symmetry_buffers(self, mb: int, critic_too: bool):
+        """The destinations of ``gf_mirror_rows`` for ``mb`` original rows, kept from minibatch to minibatch (the graph of a minibatch
+        is gone before the next one writes them)."""
+        fn = self.symmetry["func"]
+        key = (mb, critic_too)
+        if self._sym_key != key:
+            dev = self.params.device
+            e = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+            self._sym_obs = e(2 * mb, fn.obs_width)
+            self._sym_critic = e(2 * mb, fn.critic_obs_width) if critic_too else None
+            self._sym_actions = e(2 * mb, self.num_actions)
+            self._sym_scalars = e(4, 2 * mb)   # old_log_prob, advantages, values, returns
+            self._sym_grad = e(mb, self.num_actions)
+            self._sym_out = torch.zeros(1, device=dev, dtype=torch.float32)
+            self._sym_ws = torch.empty(max(1, nat.mirror_loss_workspace_bytes(mb) // 8), device=dev, dtype=torch.float64)
+            self._sym_key = key
+        return self._sym_obs, self._sym_critic, self._sym_actions, self._sym_scalars
+
+    @staticmethod
+    def _mirror_field(f, src, dst, mb: int, tables, norm, copy: bool = True) -> None:
+        """Field ``f`` of a GfMirrorRowsArgs: ``src`` ``[mb, W]`` into the two halves of ``dst`` ``[2·mb, W]`` (``copy=False``: the
+        mirrored half only, into ``dst`` ``[mb, W]``)."""
+        w = int(src.shape[1])
+        f.src, f.width, f.row_stride = src.data_ptr(), w, 0 if src.is_contiguous() else src.stride(0)
+        f.dst_copy = dst.data_ptr() if copy else None
+        f.dst_mirror = dst.data_ptr() + (mb * w * 4 if copy else 0)
+        f.perm, f.sign = tables[0].data_ptr(), tables[1].data_ptr()
+        if norm is None:
+            f.in_mean = f.in_std = None
+            f.in_eps = 0.0
+        else:
+            f.in_mean, f.in_std, f.in_eps = norm._mean.data_ptr(), norm._std.data_ptr(), norm.eps
+
+    def _mirror_loss_hip(self, backend, mu_mirror, mu_orig, grad) -> None:
+        a, fn = self._mir_loss_args, self.symmetry["func"]
+        perm, sign = fn.tables("actions", mu_mirror.device)
+        a.num_rows, a.num_actions, a.coeff = int(mu_mirror.shape[0]), self.num_actions, self.symmetry["coeff"]
+        a.mu_mirror, a.mu_orig, a.perm, a.sign = mu_mirror.data_ptr(), mu_orig.data_ptr(), perm.data_ptr(), sign.data_ptr()
+        a.grad = None if grad is None else grad.data_ptr()
+        a.out, a.sums = self._sym_out.data_ptr(), self._sums.data_ptr() + 3 * 8
+        a.workspace, a.workspace_bytes = self._sym_ws.data_ptr(), self._sym_ws.numel() * 8
+        backend.mirror_loss(a)
+
+    def _symmetry_hip(self, backend, b: MiniBatch, norms) -> None:
+        sym, policy = self.symmetry, self.policy
+        fn, mb, A, dev = sym["func"], int(b.actions.shape[0]), self.num_actions, self.params.device
+        actor = policy.act_mean if norms[0] is None else policy.actor        # (a normaliser is applied by gf_mirror_rows)
+        a = self._mir_args
+        a.num_rows = mb
+        if sym["augment"]:
+            critic = policy.evaluate if norms[1] is None else policy.critic
+            # the critic reads the actor's rows when the two inputs, their tables and their normalisers are the same
+            shared = b.critic_obs is b.obs and norms[1] is norms[0] and fn._host["critic"] is fn._host["policy"]
+            obs2, cobs2, act2, scal2 = self._symmetry_buffers(mb, not shared)
+            self._mirror_field(a.fields[0], b.obs, obs2, mb, fn.tables("policy", dev), norms[0])
+            self._mirror_field(a.fields[1], b.actions, act2, mb, fn.tables("actions", dev), None)
+            a.num_fields = 2
+            if not shared:
+                self._mirror_field(a.fields[2], b.critic_obs, cobs2, mb, fn.tables("critic", dev), norms[1])
+                a.num_fields = 3
+            for sc, src, dst in zip(a.scalars, (b.old_log_prob, b.advantages, b.values, b.returns), scal2):
+                sc.src, sc.dst = src.data_ptr(), dst.data_ptr()
+            a.num_scalars = 4
+            backend.mirror_rows(a)
+            mu, value = actor(obs2), critic(obs2 if shared else cobs2)
+            b2 = b._replace(obs=obs2, critic_obs=obs2 if shared else cobs2, actions=act2, old_log_prob=scal2[0], advantages=scal2[1],
+                            values=scal2[2], returns=scal2[3])
+            gmu, gval = self._loss_hip(backend, mu, value, b2, kl_rows=mb)
+            # the mirrored half of that forward against the mirror of the original half; its gradient joins the mirrored half's
+            self._mirror_loss_hip(backend, mu[mb:], mu[:mb], gmu[mb:] if sym["mirror"] else None)
+            torch.autograd.backward((mu, value), (gmu, gval.view_as(value)))
+            return
+        critic = policy.evaluate if norms[1] is None else policy.critic   # (the critic's rows came normalised from the gather)
+        obs2 = self._symmetry_buffers(mb, False)[0]
+        # the originals go through the normaliser here too (the gather left them raw); without one the batch's own rows are the input
+        self._mirror_field(a.fields[0], b.obs, obs2, mb, fn.tables("policy", dev), norms[0])
+        if norms[0] is None:
+            a.fields[0].dst_copy = None
+        a.num_fields, a.num_scalars = 1, 0
+        backend.mirror_rows(a)
+        mu = actor(b.obs if norms[0] is None else obs2[:mb])
+        value = critic(b.critic_obs)
+        gmu, gval = self._loss_hip(backend, mu, value, b)
+        if sym["mirror"]:   # one extra actor forward on the mirrored rows; its output's gradient starts from zero
+            mu_m = actor(obs2[mb:])
+            gm = self._sym_grad.zero_()
+            self._mirror_loss_hip(backend, mu_m, mu, gm)
+            torch.autograd.backward((mu, value, mu_m), (gmu, gval.view_as(value), gm))
+        else:               # logging only
+            with torch.no_grad():
+                mu_m = actor(obs2[mb:])
+            self._mirror_loss_hip(backend, mu_m, mu, None)
+            torch.autograd.backward((mu, value), (gmu, gval.view_as(value)))
+
     def _reduce_kl(self) -> None:
         """rsl_rl: with several ranks, ``all_reduce(kl_mean, SUM)`` then ``kl_mean /= world_size`` (every rank then takes the same lr)."""
         sync = self.grad_sync
@@ -1574,7 +1779,8 @@ class PPO:
             self._mb_key = key
         return self._grad_mu, self._grad_value
 
-    def _loss_hip(self, backend, mu, value, b: MiniBatch):
+    def _loss_hip(self, backend, mu, value, b: MiniBatch, kl_rows: int = 0):
+        """``kl_rows``: the KL covers the first ``kl_rows`` rows (``b.old_mu`` / ``b.old_sigma`` hold that many); 0: all of them."""
         mb, A = int(b.actions.shape[0]), self.num_actions
         std, is_log = _policy_std(self.policy)   # (std, or log_std: the kernel exponentiates and applies exp's backward)
         for name, t, shape in (("mu", mu, (mb, A)), ("value", value, (mb, 1))):
@@ -1592,6 +1798,7 @@ class PPO:
         a.grad_mu, a.grad_value, a.grad_sigma = gmu.data_ptr(), gval.data_ptr(), std.grad.data_ptr()
         a.out, a.sums = self._out.data_ptr(), self._sums.data_ptr()
         a.workspace, a.workspace_bytes = self._loss_ws.data_ptr(), self._loss_ws.numel() * 8
+        a.kl_rows = int(kl_rows)
         self._keep = (mu, value, b)
         backend.ppo_loss(a)
         return gmu, gval
@@ -1612,16 +1819,18 @@ class PPO:
         self._calls += 1
 
     # -- the same arithmetic in torch (backends without gf_ppo_loss / gf_adam_step) -------------------------------------------------
-    def _loss_torch(self, mu, value, b: MiniBatch) -> None:
-        """rsl_rl PPO.update's loss lines, ``loss.backward()``, and the values gf_ppo_loss leaves in ``out`` / ``sums``."""
+    def _loss_torch(self, mu, value, b: MiniBatch, kl_rows: int = 0, extra=None) -> None:
+        """rsl_rl PPO.update's loss lines, ``loss.backward()``, and the values gf_ppo_loss leaves in ``out`` / ``sums``.  ``kl_rows``:
+        the KL is taken from the first ``kl_rows`` rows (0: all); ``extra``: a term added to the loss before ``backward()``."""
         std, is_log = _policy_std(self.policy)
         sigma = (torch.exp(std) if is_log else std).expand_as(mu)
         dist = torch.distributions.Normal(mu, sigma, validate_args=False)   # (rsl_rl's ActorCritic turns validation off: no host read)
         logp = dist.log_prob(b.actions).sum(dim=-1)
         entropy = dist.entropy().sum(dim=-1)
         with torch.no_grad():
-            kl = torch.sum(torch.log(sigma / b.old_sigma + 1.0e-5) + (torch.square(b.old_sigma) + torch.square(b.old_mu - mu))
-                           / (2.0 * torch.square(sigma)) - 0.5, dim=-1)
+            mu_kl, sigma_kl = (mu[:kl_rows], sigma[:kl_rows]) if kl_rows else (mu, sigma)
+            kl = torch.sum(torch.log(sigma_kl / b.old_sigma + 1.0e-5) + (torch.square(b.old_sigma) + torch.square(b.old_mu - mu_kl))
+                           / (2.0 * torch.square(sigma_kl)) - 0.5, dim=-1)
             kl_mean = torch.mean(kl)
         ratio = torch.exp(logp - torch.squeeze(b.old_log_prob))
         surrogate = -torch.squeeze(b.advantages) * ratio
@@ -1635,10 +1844,12 @@ class PPO:
             value_loss = (ret - v).pow(2).mean()
         ent_mean = entropy.mean()
         loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * ent_mean
+        if extra is not None:
+            loss = loss + extra
         loss.backward()
         with torch.no_grad():
             self._out.copy_(torch.stack([surrogate_loss, value_loss, ent_mean, kl_mean, loss]).to(torch.float32))
-            self._sums.add_(torch.stack([value_loss, surrogate_loss, ent_mean]).to(torch.float64))
+            self._sums[:3].add_(torch.stack([value_loss, surrogate_loss, ent_mean]).to(torch.float64))
 
     def _adam_torch(self) -> None:
         """The schedule, ``clip_grad_norm_`` and torch.optim.Adam's foreach arithmetic as tensor operations (no host read)."""

@@ -198,6 +198,8 @@ class OnPolicyRunner:
                   "learning_rate": self.alg.learning_rate, "mean_action_std": float(self.alg.policy.action_std.mean()),
                   "mean_reward": stats.mean_reward(), "mean_episode_length": stats.mean_episode_length(),
                   "steps_per_second": steps / max(collection_s + learn_s, 1e-9), "collection_time": collection_s, "learn_time": learn_s}
+        if "symmetry" in losses:   # (only with algorithm.symmetry_cfg: records without one keep their keys)
+            record["symmetry"] = losses["symmetry"]
         self.last_log = record
         if self.log_dir is not None:
             with open(os.path.join(self.log_dir, "progress.jsonl"), "a") as f:

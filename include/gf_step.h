@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 10
+#define GF_ABI_VERSION 11
 
 #define GF_MAX_TERMS 24          /* reward terms per manager          */
 #define GF_MAX_TERM_TERMS 16     /* termination terms per manager     */
@@ -842,7 +842,7 @@ typedef struct GfEpisodeArgs {
 } GfEpisodeArgs;
 
 /* ------------------------------------------------------------------------------------------
- * The PPO update (rsl_rl PPO.update, non-recurrent path without RND / symmetry).  Per minibatch rsl_rl evaluates the policy,
+ * The PPO update (rsl_rl PPO.update, non-recurrent path without RND; the symmetry options have their own block below).  Per minibatch rsl_rl evaluates the policy,
  * builds the loss from a few dozen elementwise and reduction launches (and as many for their backward), clips the gradient
  * norm, takes an Adam step and reads four scalars back to the host (the KL test of the adaptive schedule, three .item()).
  * The MLP forward / backward stay in torch; the rest is two entry points that never synchronise:
@@ -864,6 +864,10 @@ typedef struct GfEpisodeArgs {
  * sigma_is_log = 1 (rsl_rl's noise_std_type = "log"): `sigma` points at log_std [A] and sigma_a = expf(log_std_a) — the same code
  * as gf_policy_act's, so the same bits — stands wherever sigma does above.  grad_sigma[a] then receives d loss / d log_std_a =
  * g · sigma_a (exp's backward), g the float32 value the flag-0 call writes for that sigma: one more correctly rounded f32 product.
+ * kl_rows (rsl_rl with symmetry augmentation: the minibatch is [originals; mirrored copies] and the KL of the schedule is taken from
+ * the original rows): 0 — the KL sum and its divisor cover all mb rows, the bits of a call without the field; 1 … mb — they cover the
+ * first kl_rows rows, and old_mu / old_sigma hold kl_rows rows (rows past them are never read); every other output is unchanged.
+ * Anything else is GF_E_RANGE.
  *
  * gf_adam_step — torch.nn.utils.clip_grad_norm_ then torch.optim.Adam (defaults: no weight decay, no amsgrad; foreach order)
  * over one flat float32 parameter buffer and its flat gradient (the GradientAllReduce bucket):
@@ -917,6 +921,7 @@ typedef struct GfPpoLossArgs {
     double* sums;               /* [3] += value_loss, surrogate, entropy (rsl_rl's loss-dict order), or NULL */
     void* workspace;            /* GF_PPO_LOSS_WORKSPACE_BYTES(mb, A) bytes, 8-byte aligned */
     int64_t workspace_bytes;
+    int64_t kl_rows;            /* 0: the KL covers all mb rows; 1 … mb: the first kl_rows rows only (old_mu / old_sigma are then [kl_rows, A]) */
 } GfPpoLossArgs;
 
 typedef struct GfAdamState {    /* device control block; GfAdamArgs.state points at two of them */
@@ -941,6 +946,91 @@ typedef struct GfAdamArgs {
     int32_t parity;             /* 0 or 1 */
     int32_t _pad;
 } GfAdamArgs;
+
+/* ------------------------------------------------------------------------------------------
+ * Mirror symmetry of the PPO update (rsl_rl's symmetry_cfg: data augmentation and mirror loss for a left/right symmetric robot).
+ * A mirror is a signed permutation per tensor kind:  mirror(x)[n, j] = sign[j] · x[n, perm[j]].  rsl_rl runs a Python callback, a
+ * torch.cat per field, a repeat per scalar and an MSELoss with its backward per minibatch; here:
+ *
+ * gf_mirror_rows — ONE launch for up to GF_MIRROR_MAX_FIELDS row fields (observations, critic observations, actions, one spare) and
+ * up to GF_MIRROR_MAX_SCALARS per-row scalars (old log-prob, advantages, target values, returns).  Per field
+ *     dst_copy  [n, j] = f_j(src[n, j])                       (dst_copy == NULL: not written)
+ *     dst_mirror[n, j] = f_j(sign[j] · src[n, perm[j]])
+ * with f_j the identity, or with a normaliser (in_mean != NULL)  f_j(v) = (v - in_mean[j]) / (in_std[j] + in_eps)  — one
+ * subtraction, one addition, one correctly rounded division, the operations of gf_minibatch_gather and gf_mlp_act.  The mirror is
+ * taken of the RAW value and normalised at the DESTINATION column: rsl_rl augments first and normalises inside the policy.  Source
+ * row n is at src + n · row_stride (0: width, as GfMlpSegment); the two destinations have contiguous rows and usually are the two
+ * halves of one [2·rows, width] tensor.  Per scalar  dst[i] = dst[rows + i] = src[i].
+ * A workgroup stages a tile of source rows in LDS — every source row is read from memory once — and writes both destinations from it;
+ * 16-byte loads and stores where the width, the row stride and every pointer of the field allow it, by element otherwise.  No atomics,
+ * no workspace, no allocation, no synchronisation.  Bit-exact: a signed permutation rounds nothing.
+ * `perm` / `sign` are TRUSTED: the entry point cannot look at device memory, an entry outside 0 … width-1 reads outside the tile.
+ * They come from genesis_forge_amd.MirrorSymmetry, which validates on the host (a permutation, signs ±1, an involution) before it
+ * uploads them; no caller may hand over anything else.
+ * Refusals, before anything is launched: GF_E_NULL — args, a field's src / dst_mirror / perm / sign, in_mean without in_std, a
+ * scalar's src / dst; GF_E_RANGE — num_rows < 0, num_fields outside 0 … GF_MIRROR_MAX_FIELDS, num_scalars outside 0 …
+ * GF_MIRROR_MAX_SCALARS, both zero, a width outside 1 … GF_MIRROR_MAX_WIDTH, a non-zero row_stride < width.  num_rows == 0 is a no-op.
+ *
+ * gf_mirror_loss — rsl_rl's symmetry loss  MSE(actor(mirror(obs)), mirror(actor(obs)).detach())  and its gradient:
+ *     d[n, j] = mu_mirror[n, j] - sign[j] · mu_orig[n, perm[j]]            (one rounding)
+ *     loss    = mean over the mb·A elements of d²   -> out[0] (float32), and sums[0] += (double)out[0] when sums != NULL
+ *     grad[n, j] += coeff · 2 · d[n, j] / (mb·A)                           (grad != NULL; mu_orig is a constant: no gradient)
+ * as ((coeff · inv) · (2 · d)) with inv = 1 / (float)(mb·A): three more roundings, then the addition into what `grad` holds — the
+ * mirrored half of gf_ppo_loss's grad_mu when augmenting, a zeroed buffer otherwise.  grad == NULL is the logging-only mode: nothing
+ * but out / sums is written.  The shape of gf_ppo_loss: one lane per row, one double partial per workgroup in the caller's
+ * workspace, a second one-workgroup launch sums them in a fixed order.  No atomics: bitwise reproducible.  `perm` / `sign` are the
+ * action tables, trusted as above.
+ * Refusals: GF_E_NULL — args, mu_mirror, mu_orig, perm, sign, out, workspace; GF_E_RANGE — num_rows < 0, num_actions < 1, a
+ * workspace smaller than GF_MIRROR_LOSS_WORKSPACE_BYTES(mb) or not 8-byte aligned.  num_rows == 0 is a no-op.
+ * Neither is a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_MIRROR_MAX_FIELDS 4
+#define GF_MIRROR_MAX_SCALARS 4
+#define GF_MIRROR_MAX_WIDTH 8192       /* floats of the LDS tile: one row must fit */
+#define GF_MIRROR_LOSS_BLOCK_ROWS 256  /* rows per workgroup of gf_mirror_loss: one double partial per workgroup */
+#define GF_MIRROR_LOSS_WORKSPACE_BYTES(mb) ((int64_t)(((mb) + GF_MIRROR_LOSS_BLOCK_ROWS - 1) / GF_MIRROR_LOSS_BLOCK_ROWS) * 8)
+
+typedef struct GfMirrorField {
+    const float* src;           /* [rows, width], row n at src + n * row_stride */
+    float* dst_copy;            /* [rows, width] contiguous, or NULL */
+    float* dst_mirror;          /* [rows, width] contiguous */
+    const int32_t* perm;        /* [width] source column of destination column j (trusted: 0 … width-1) */
+    const float* sign;          /* [width] ±1 */
+    const float* in_mean;       /* [width] normaliser mean, or NULL: f_j is the identity */
+    const float* in_std;        /* [width] normaliser std (required with in_mean) */
+    float in_eps;               /* added to in_std */
+    int32_t width;              /* 1 … GF_MIRROR_MAX_WIDTH */
+    int32_t row_stride;         /* floats from a source row to the next; 0: `width`; otherwise >= width */
+    int32_t _pad;
+} GfMirrorField;
+
+typedef struct GfMirrorScalar {
+    const float* src;           /* [rows] */
+    float* dst;                 /* [2 * rows]: both halves receive src */
+} GfMirrorScalar;
+
+typedef struct GfMirrorRowsArgs {
+    int64_t num_rows;           /* rows >= 0; 0: nothing is launched */
+    int32_t num_fields;         /* 0 … GF_MIRROR_MAX_FIELDS */
+    int32_t num_scalars;        /* 0 … GF_MIRROR_MAX_SCALARS (not both 0) */
+    GfMirrorField fields[GF_MIRROR_MAX_FIELDS];
+    GfMirrorScalar scalars[GF_MIRROR_MAX_SCALARS];
+} GfMirrorRowsArgs;
+
+typedef struct GfMirrorLossArgs {
+    int64_t num_rows;           /* mb >= 0; 0: nothing is launched */
+    int32_t num_actions;        /* A >= 1 */
+    float coeff;                /* mirror_loss_coeff: scales the gradient only (the loss is logged unscaled) */
+    const float* mu_mirror;     /* [mb, A] the actor on the mirrored observations */
+    const float* mu_orig;       /* [mb, A] the actor on the originals (a constant) */
+    const int32_t* perm;        /* [A] action tables (trusted) */
+    const float* sign;          /* [A] */
+    float* grad;                /* [mb, A] += coeff · d loss / d mu_mirror, or NULL: loss only */
+    float* out;                 /* [1] the loss (required) */
+    double* sums;               /* [1] += the loss, or NULL */
+    void* workspace;            /* GF_MIRROR_LOSS_WORKSPACE_BYTES(mb) bytes, 8-byte aligned */
+    int64_t workspace_bytes;
+} GfMirrorLossArgs;
 
 /* ------------------------------------------------------------------------------------------
  * The actor-critic forward of a collection step (rsl_rl ActorCritic.act / evaluate inside PPO.act): torch runs each MLP as one GEMM
@@ -1126,7 +1216,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs, 31 GfMirrorRowsArgs, 32 GfMirrorLossArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -1153,6 +1243,8 @@ int gf_minibatch_gather(const GfMinibatchArgs* a, void* stream);  /* every field
 int gf_policy_act(const GfPolicyActArgs* a, void* stream);       /* Normal sample + log_prob + the policy's storage rows in one launch (rsl_rl PPO.act) */
 int gf_episode_step(const GfEpisodeArgs* a, void* stream);       /* time-out bootstrap + the runner's rewbuffer / lenbuffer upkeep (rsl_rl OnPolicyRunner.learn) */
 int gf_ppo_loss(const GfPpoLossArgs* a, void* stream);           /* minibatch loss + its gradient w.r.t. mu / value / sigma (rsl_rl PPO.update: the KL block, surrogate, value loss, loss, loss.backward() down to the policy outputs, the three .item()) */
+int gf_mirror_rows(const GfMirrorRowsArgs* a, void* stream);     /* originals + mirrored copies of up to four row fields, and the replicated per-row scalars, in one launch (rsl_rl PPO.update: data_augmentation_func, torch.cat, repeat) */
+int gf_mirror_loss(const GfMirrorLossArgs* a, void* stream);     /* symmetry loss and its gradient w.r.t. the mirrored rows' mu (rsl_rl PPO.update: MSELoss(mean_actions[mb:], mirrored mean_actions[:mb].detach()) and its backward) */
 int gf_mlp_act(const GfMlpActArgs* a, void* stream);             /* actor + critic MLP forward on the f32 matrix cores, then gf_policy_act's sampling and rows, in one launch (rsl_rl ActorCritic.act / evaluate inside PPO.act) */
 int gf_obs_norm_update(const GfObsNormArgs* a, void* stream);    /* running mean / var / std / count of up to two observation normalisers in two launches (rsl_rl EmpiricalNormalization.update) */
 int gf_adam_step(const GfAdamArgs* a, void* stream);             /* adaptive lr + clip_grad_norm_ + Adam.step over the flat bucket (rsl_rl PPO.update: the lr schedule, nn.utils.clip_grad_norm_, optimizer.step()) */

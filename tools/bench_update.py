@@ -4,6 +4,7 @@ PPO.update restated in torch (tests/rsl_rl_ppo.py: torch.optim.Adam, clip_grad_n
 
 usage: python tools/bench_update.py [--sizes go2_cmd:4096,go2_cmd:16384,go2_cmd:65536,gait:4096] [--steps 24] [--reps 7]
                                     [--forms rsl_rl,fused] [--out FILE] [--noise-std-type scalar|log]
+                                    [--symmetry none|augment|mirror|both]
 
 Per size: one rollout of T steps is collected with act / process_env_step by the reference policy (ELU MLPs 512-256-128, as
 examples/*/train.py) and its returns computed; then every rep runs each form once, alternating, from the same initial weights,
@@ -13,7 +14,9 @@ critic (obs_groups {"policy": ["policy"], "critic": ["policy", "critic"]}).  Pri
 median ms per update over the reps (after one warm-up update per form), and the losses of the last rep.
 ``--synthetic``: random storage rows instead of a rollout — two such runs of one form under ``rocprofv3 --kernel-trace --stats``
 that differ only in ``--reps`` differ by exactly that many updates, which gives the dispatches per minibatch.
-``--noise-std-type log``: the policy holds ``log_std`` (the torch restatement reads ``std = exp(log_std)`` through a property)."""
+``--noise-std-type log``: the policy holds ``log_std`` (the torch restatement reads ``std = exp(log_std)`` through a property).
+``--symmetry``: both forms get rsl_rl's ``symmetry_cfg`` with the Go2 left/right mirror (``go2_mirror``) — ``augment``: data
+augmentation, ``mirror``: the mirror loss, ``both``; the torch form is then tests/rsl_rl_symmetry.py."""
 import argparse
 import copy
 import json
@@ -105,6 +108,35 @@ def synthetic(config: str, n: int, T: int, noise_std_type: str = "scalar"):
     return env, st, policy
 
 
+# Go2's left/right mirror.  Joints are ordered FL, FR, RL, RR x (hip, thigh, calf): legs swap sides, the hip (abduction) changes sign.
+# Under the reflection y -> -y a velocity / the gravity direction flips y, an angular velocity (a pseudo-vector) flips x and z, and
+# the command (vx, vy, yaw rate) flips vy and the yaw rate.
+GO2_JOINT_MIRROR = ([3, 4, 5, 0, 1, 2, 9, 10, 11, 6, 7, 8], [-1, 1, 1] * 4)
+GO2_ITEM_MIRROR = {"velocity_cmd": ([0, 1, 2], [1, -1, -1]), "angle_velocity": ([0, 1, 2], [-1, 1, -1]), "linear_velocity": ([0, 1, 2], [1, -1, 1]),
+                   "projected_gravity": ([0, 1, 2], [1, -1, 1]), "dof_position": GO2_JOINT_MIRROR, "dof_velocity": GO2_JOINT_MIRROR,
+                   "actions": GO2_JOINT_MIRROR}
+
+
+def go2_mirror(st):
+    """The MirrorSymmetry of a storage's observation groups: the Go2 tables for the items a manager has (any other item maps onto
+    itself); a storage without real managers (``--synthetic``) gets a column reversal of every width."""
+    from genesis_forge_amd import MirrorSymmetry
+
+    managers = {m.name: m for m in st.env.managers["observation"]}
+
+    def tables(group):
+        members = [managers[name] for name in st.obs_groups[group]]
+        if not all(getattr(m, "_plan", None) for m in members):
+            w = sum(st._widths[name] for name in st.obs_groups[group])
+            return list(range(w - 1, -1, -1)), [1.0] * w
+        have = {name for m in members for name, *_ in m._plan}
+        items = {k: v for k, v in GO2_ITEM_MIRROR.items() if k in have and all(w == len(v[0]) for m in members for n, _c, _s, w in m._plan if n == k)}
+        return MirrorSymmetry.item_tables(members, items)
+
+    (op, os_), (cp, cs) = tables("policy"), tables("critic")
+    return MirrorSymmetry(op, os_, *GO2_JOINT_MIRROR, critic_obs_perm=cp, critic_obs_sign=cs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="go2_cmd:4096,go2_cmd:16384,go2_cmd:65536,gait:4096")
@@ -114,11 +146,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--synthetic", action="store_true", help="random storage rows, no env (dispatch counts under rocprofv3)")
     ap.add_argument("--noise-std-type", default="scalar", choices=["scalar", "log"], help="the policy's std parameter: std, or log_std")
+    ap.add_argument("--symmetry", default="none", choices=["none", "augment", "mirror", "both"], help="rsl_rl's symmetry_cfg with the Go2 mirror")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_update.py measures on a ROCm GPU: none is visible")
     from genesis_forge_amd.learner import PPO
     from rsl_rl_ppo import RslRlPPO
+    from rsl_rl_symmetry import RslRlSymmetryPPO
 
     forms = args.forms.split(",")
     lines = []
@@ -126,13 +160,17 @@ def main():
         config, n = spec.split(":")
         env, st, policy0 = (synthetic if args.synthetic else rollout)(config, int(n), args.steps, args.noise_std_type)
         init = copy.deepcopy(policy0.state_dict())
+        algo_cfg = dict(ALGO)
+        if args.symmetry != "none":
+            algo_cfg["symmetry_cfg"] = dict(use_data_augmentation=args.symmetry in ("augment", "both"), use_mirror_loss=args.symmetry in ("mirror", "both"),
+                                            mirror_loss_coeff=0.5, data_augmentation_func=go2_mirror(st))
         times = {f: [] for f in forms}
         last = {}
         for rep in range(args.reps + 1):   # rep 0: warm-up
             for form in forms:
                 policy = copy.deepcopy(policy0)
                 policy.load_state_dict(init)
-                algo = PPO(policy, st, **ALGO) if form == "fused" else RslRlPPO(policy, st, **ALGO)
+                algo = PPO(policy, st, **algo_cfg) if form == "fused" else (RslRlSymmetryPPO if args.symmetry != "none" else RslRlPPO)(policy, st, **algo_cfg)
                 gen = torch.Generator(device="cuda").manual_seed(rep)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -145,7 +183,7 @@ def main():
         mb = st.num_steps * st.env.num_envs // ALGO["num_mini_batches"]
         for form in forms:
             row = dict(config=config, num_envs=int(n), steps=args.steps, minibatch=mb, form=form, reps=args.reps,
-                       noise_std_type=args.noise_std_type,
+                       noise_std_type=args.noise_std_type, symmetry=args.symmetry,
                        best_ms=round(min(times[form]), 3) if times[form] else None,
                        median_ms=round(statistics.median(times[form]), 3) if times[form] else None,
                        losses=last[form][0], lr=last[form][1], device=torch.cuda.get_device_name(0))

@@ -81,6 +81,8 @@ GF_EXPORT int gf_sizeof(int which) {
         case 30: return (int)sizeof(GfRolloutFrameArgs);
         case 31: return (int)sizeof(GfMirrorRowsArgs);
         case 32: return (int)sizeof(GfMirrorLossArgs);
+        case 33: return (int)sizeof(GfMlpDistillArgs);
+        case 34: return (int)sizeof(GfBcLossArgs);
         default: return -1;
     }
 }

@@ -1,4 +1,4 @@
-// gf_mlp.hip — gf_mlp_act: the actor and critic MLPs of a collection step and gf_policy_act's sampling in one launch
+// gf_mlp.hip — gf_mlp_act (and gf_mlp_distill_act): the actor and critic MLPs of a collection step and gf_policy_act's sampling in one launch
 // (include/gf_step.h has the contract).  The first kernel of the library on the matrix cores: every other one is bandwidth- or
 // latency-bound, this one is 0.76 MFLOP per env.
 //
@@ -23,6 +23,8 @@
 //   * The last layer's outputs land in x like any other; lane r < 32 of the workgroup then finishes row r: the actor workgroup stores
 //     `mean` and runs gf_policy_act's row (gf_policy_row.h) with the mean read from LDS, the critic workgroup stores the value.
 // LDS: 65 664 B, registers <= 256: two workgroups per CU, so one's barriers, ELU and load latency hide behind the other's MFMAs.
+// gf_mlp_distill_act is the same tile walk with grid y = student / teacher (a distillation collection step): the student workgroup is
+// the actor path above, the teacher workgroup stores its outputs to two destinations and samples nothing.
 #include "gf_launch.h"
 #include "gf_policy_row.h"
 
@@ -218,14 +220,9 @@ __device__ __forceinline__ void mlp_layer(MlpSmem& sm, const GfMlpNet& net, cons
     __syncthreads();
 }
 
-template <bool NORM, bool LOG>
-__global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArgs a, const int first_net, const int vec_rows) {
-    __shared__ MlpSmem sm;
-    const bool is_critic = (int)blockIdx.y + first_net == 1;
-    const GfMlpNet& net = is_critic ? a.critic : a.actor;
-    const int64_t N = a.num_envs;
-    const int64_t row0 = (int64_t)blockIdx.x * kMlpRows;
-
+// every layer of `net` on the tile's rows: the last layer's outputs are left in x; returns their width
+template <bool NORM>
+__device__ __forceinline__ int mlp_forward(MlpSmem& sm, const GfMlpNet& net, const int64_t row0, const int64_t N) {
     int K = 0;
     for (int s = 0; s < net.num_inputs; ++s) K += net.inputs[s].width;
     const int layers = net.num_layers;
@@ -239,6 +236,18 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArg
         else mlp_layer<4, NORM>(sm, net, L, K, first, last, row0, N);
         K = L.out_width;
     }
+    return K;
+}
+
+template <bool NORM, bool LOG>
+__global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArgs a, const int first_net, const int vec_rows) {
+    __shared__ MlpSmem sm;
+    const bool is_critic = (int)blockIdx.y + first_net == 1;
+    const GfMlpNet& net = is_critic ? a.critic : a.actor;
+    const int64_t N = a.num_envs;
+    const int64_t row0 = (int64_t)blockIdx.x * kMlpRows;
+
+    const int K = mlp_forward<NORM>(sm, net, row0, N);
 
     // one lane per row finishes it from the outputs in x
     const int r = (int)threadIdx.x;
@@ -281,6 +290,69 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArg
     };
     if (vec_rows) policy_act_row<true, LOG>(p, n, load_mean);
     else policy_act_row<false, LOG>(p, n, load_mean);
+}
+
+// gf_mlp_distill_act: grid y = 0 the student (gf_mlp_act's actor path: mean, sample, the storage row), y = 1 the teacher (its output
+// to two destinations).  LOG is a run-time, workgroup-uniform choice here — only the sampling lanes at the end differ, and two
+// instances (NORM) are what the launch needs.
+template <bool NORM>
+__global__ __launch_bounds__(kMlpBlock, 2) void mlp_distill_kernel(const GfMlpDistillArgs a, const int vec_rows) {
+    __shared__ MlpSmem sm;
+    const bool is_teacher = blockIdx.y == 1;
+    const GfMlpNet& net = is_teacher ? a.teacher : a.student;
+    const int64_t N = a.num_envs;
+    const int64_t row0 = (int64_t)blockIdx.x * kMlpRows;
+
+    const int A = mlp_forward<NORM>(sm, net, row0, N);
+
+    // one lane per row finishes it from the outputs in x
+    const int r = (int)threadIdx.x;
+    const int64_t n = row0 + r;
+    if (r >= kMlpRows || n >= N) return;
+    const float* out = sm.x + r * kMlpXS;
+    if (is_teacher) {
+        GF_GLOBAL float* t0 = G(a.teacher_actions) + n * A;
+        GF_GLOBAL float* t1 = a.teacher_actions_out ? G(a.teacher_actions_out) + n * A : nullptr;
+        for (int c = 0; c < A; ++c) {
+            const float v = out[c];
+            t0[c] = v;
+            if (t1) t1[c] = v;
+        }
+        return;
+    }
+    if (a.mean) {
+        GF_GLOBAL float* m = G(a.mean) + n * A;
+        for (int c = 0; c < A; ++c) m[c] = out[c];
+    }
+    GfPolicyActArgs p;
+    p.num_envs = N;
+    p.num_actions = A;
+    p.std_per_env = 0;
+    p.mean = nullptr;
+    p.std = a.std;
+    p.values = nullptr;
+    p.noise = a.noise;
+    p.seed = a.seed;
+    p.stream = a.stream;
+    p.env_offset = a.env_offset;
+    p.std_is_log = (uint32_t)a.std_is_log;
+    p.actions = a.actions;
+    p.actions_out = a.actions_out;
+    p.mu_out = nullptr;
+    p.sigma_out = nullptr;
+    p.values_out = nullptr;
+    p.log_prob_out = nullptr;
+    const auto load_mean = [&](int c0, float (&m)[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m[k] = out[c0 + k];   // (columns past A: zeros, or x's finite leftovers — never folded or stored)
+    };
+    if (a.std_is_log) {
+        if (vec_rows) policy_act_row<true, true>(p, n, load_mean);
+        else policy_act_row<false, true>(p, n, load_mean);
+    } else {
+        if (vec_rows) policy_act_row<true, false>(p, n, load_mean);
+        else policy_act_row<false, false>(p, n, load_mean);
+    }
 }
 
 // GF_OK and the net's widths, or the refusal
@@ -355,5 +427,31 @@ extern "C" __attribute__((visibility("default"))) int gf_mlp_act(const GfMlpActA
         if (norm) gf::klaunch(gf::mlp_act_kernel<true, false>, grid, block, 0, s, *a, first_net, vec_rows);
         else gf::klaunch(gf::mlp_act_kernel<false, false>, grid, block, 0, s, *a, first_net, vec_rows);
     }
+    return gf::launch_status();
+}
+
+extern "C" __attribute__((visibility("default"))) int gf_mlp_distill_act(const GfMlpDistillArgs* a, void* stream) {
+    if (!a) return GF_E_NULL;
+    if (a->num_envs < 0 || (a->std_is_log != 0 && a->std_is_log != 1)) return GF_E_RANGE;
+    int A = 0, At = 0;
+    int rc = gf::mlp_check_net(a->student, false, &A);
+    if (rc != GF_OK) return rc;
+    rc = gf::mlp_check_net(a->teacher, false, &At);
+    if (rc != GF_OK) return rc;
+    if (a->student.num_layers == 0 || a->teacher.num_layers == 0) return GF_E_UNSUPPORTED;
+    if (A != At) return GF_E_RANGE;
+    if (!a->std || !a->actions || !a->teacher_actions) return GF_E_NULL;
+    if (a->num_envs == 0) return GF_OK;
+    const int64_t tiles = (a->num_envs + gf::kMlpRows - 1) / gf::kMlpRows;
+    if (tiles > 0x7fffffff) return GF_E_RANGE;
+    uintptr_t bits = 0;
+    const void* rows[] = {a->noise, a->actions, a->actions_out, a->std};
+    for (const void* p : rows) bits |= reinterpret_cast<uintptr_t>(p);
+    const int vec_rows = (bits & 15u) == 0 && (A & 3) == 0;
+    const dim3 grid((unsigned)tiles, 2u);
+    const dim3 block(gf::kMlpBlock);
+    hipStream_t s = (hipStream_t)stream;
+    if (a->student.in_mean || a->teacher.in_mean) gf::klaunch(gf::mlp_distill_kernel<true>, grid, block, 0, s, *a, vec_rows);
+    else gf::klaunch(gf::mlp_distill_kernel<false>, grid, block, 0, s, *a, vec_rows);
     return gf::launch_status();
 }

@@ -442,6 +442,31 @@ class GfMlpActArgs(C.Structure):
                 ("actions_out", P), ("mu_out", P), ("sigma_out", P), ("values_out", P), ("log_prob_out", P), ("std_is_log", C.c_int32), ("_pad", C.c_int32)]
 
 
+# teacher–student distillation (learner.DistillForward / RolloutStorage.act_distill, learner.Distillation): gf_mlp_distill_act /
+# gf_bc_loss, not in ABI_STRUCTS either
+GF_SIZEOF_MLP_DISTILL = 33
+GF_SIZEOF_BC_LOSS = 34
+GF_BC_LOSS_MSE = 0
+GF_BC_LOSS_HUBER = 1
+GF_BC_LOSS_BLOCK_ROWS = 256
+
+
+def bc_loss_workspace_bytes(num_rows: int) -> int:
+    """GF_BC_LOSS_WORKSPACE_BYTES: one double per workgroup of GF_BC_LOSS_BLOCK_ROWS rows."""
+    return -(-int(num_rows) // GF_BC_LOSS_BLOCK_ROWS) * 8
+
+
+class GfMlpDistillArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("student", GfMlpNet), ("teacher", GfMlpNet), ("std", P), ("noise", P), ("seed", C.c_uint64),
+                ("stream", C.c_uint64), ("env_offset", C.c_uint32), ("std_is_log", C.c_int32), ("mean", P), ("actions", P),
+                ("actions_out", P), ("teacher_actions", P), ("teacher_actions_out", P)]
+
+
+class GfBcLossArgs(C.Structure):
+    _fields_ = [("num_rows", C.c_int64), ("num_actions", C.c_int32), ("loss_type", C.c_int32), ("mu", P), ("target", P), ("grad", P),
+                ("out", P), ("sums", P), ("workspace", P), ("workspace_bytes", C.c_int64)]
+
+
 # the running observation statistics (learner.EmpiricalNormalization.update): gf_obs_norm_update, not in ABI_STRUCTS either
 GF_SIZEOF_OBS_NORM = 29
 GF_OBS_NORM_MAX_SETS = 2
@@ -705,7 +730,8 @@ class HipBackend(Backend):
                             ("gf_ppo_loss", GF_SIZEOF_PPO_LOSS, GfPpoLossArgs), ("gf_adam_step", GF_SIZEOF_ADAM, GfAdamArgs),
                             ("gf_mlp_act", GF_SIZEOF_MLP_ACT, GfMlpActArgs), ("gf_obs_norm_update", GF_SIZEOF_OBS_NORM, GfObsNormArgs),
                             ("gf_rollout_frame_write", GF_SIZEOF_ROLLOUT_FRAME, GfRolloutFrameArgs),
-                            ("gf_mirror_rows", GF_SIZEOF_MIRROR_ROWS, GfMirrorRowsArgs), ("gf_mirror_loss", GF_SIZEOF_MIRROR_LOSS, GfMirrorLossArgs)):
+                            ("gf_mirror_rows", GF_SIZEOF_MIRROR_ROWS, GfMirrorRowsArgs), ("gf_mirror_loss", GF_SIZEOF_MIRROR_LOSS, GfMirrorLossArgs),
+                            ("gf_mlp_distill_act", GF_SIZEOF_MLP_DISTILL, GfMlpDistillArgs), ("gf_bc_loss", GF_SIZEOF_BC_LOSS, GfBcLossArgs)):
             n = self.lib.gf_sizeof(idx)
             if n != C.sizeof(st):
                 raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")
@@ -791,6 +817,18 @@ class HipBackend(Backend):
         rc = self.lib.gf_mlp_act(C.byref(args), self._stream())
         if rc != 0:
             self._raise("mlp_act", rc)
+
+    def mlp_distill_act(self, args) -> None:
+        """gf_mlp_distill_act on the current stream (learner.DistillForward.act, learner.RolloutStorage.act_distill)."""
+        rc = self.lib.gf_mlp_distill_act(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("mlp_distill_act", rc)
+
+    def bc_loss(self, args) -> None:
+        """gf_bc_loss on the current stream (learner.Distillation.update)."""
+        rc = self.lib.gf_bc_loss(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("bc_loss", rc)
 
     def run_ops(self, ops, n: int) -> None:
         failed = C.c_int(-1)

@@ -41,6 +41,11 @@ dependency and stays one; this module provides the two pieces of it that touch t
   synchronisation per minibatch; the three logged means are read once per update.  With rsl_rl's ``symmetry_cfg`` (a
   :class:`~genesis_forge_amd.symmetry.MirrorSymmetry` as its function) the augmented minibatch is one ``gf_mirror_rows`` and the mirror
   loss with its gradient one ``gf_mirror_loss``.
+* :class:`StudentTeacherMLP`, :class:`DistillForward`, :class:`Distillation` — rsl_rl's ``Distillation`` algorithm with a
+  ``StudentTeacher`` policy, the step after PPO: a student that reads only deployable observations is regressed onto the frozen PPO
+  actor.  ``RolloutStorage.act_distill`` runs both MLPs of a collection step, the sampling and the two storage rows in ONE
+  ``gf_mlp_distill_act`` launch; an update walks ``RolloutStorage.step_batches()`` with one ``gf_bc_loss`` per time step and one
+  ``gf_adam_step`` every ``gradient_length`` steps, and reads the device once.
 """
 from __future__ import annotations
 
@@ -238,6 +243,7 @@ class RolloutStorage:
         # the policy's rows and the return computation (allocated on first use: a storage that only takes the env's rows stays small)
         self.num_actions = None
         self.actions = self.values = self.actions_log_prob = self.mu = self.sigma = self.returns = self.advantages = None
+        self.privileged_actions = None   # [T, N, A] the teacher's actions of a distillation rollout (act_distill)
         self._pol_args = nat.GfRolloutPolicyArgs()
         self._gae_args = nat.GfGaeArgs()
         self._moments = None
@@ -404,7 +410,7 @@ class RolloutStorage:
 
     # -- the policy's half of a transition, returns ---------------------------------------------------------------------------
     def _ensure_policy_rows(self, num_actions: int) -> None:
-        if self.actions is not None and self.num_actions == num_actions:
+        if self.values is not None and self.num_actions == num_actions:   # (act_distill allocates `actions` alone)
             return
         T, n = self.num_steps, self.env.num_envs
         z = lambda *shape: torch.zeros(shape, device=gs.device, dtype=torch.float32)
@@ -548,6 +554,94 @@ class RolloutStorage:
         self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
         return actions
 
+    # -- teacher–student distillation: the collection step and the update's batches ------------------------------------------------
+    def _ensure_distill_rows(self, num_actions: int) -> None:
+        T, n = self.num_steps, self.env.num_envs
+        if self.actions is None or self.num_actions != num_actions:
+            self.num_actions = int(num_actions)
+            self.actions = torch.zeros((T, n, num_actions), device=gs.device, dtype=torch.float32)
+            self.values = None   # (PPO's rows, if any, were of another width)
+        if self.privileged_actions is None or self.privileged_actions.shape[2] != num_actions:
+            self.privileged_actions = torch.zeros((T, n, num_actions), device=gs.device, dtype=torch.float32)
+
+    def act_distill(self, forward: "DistillForward", obs, teacher_obs=None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """rsl_rl's ``Distillation.act``: returns ``Normal(student(obs), std).sample()`` as a fresh ``[N, A]`` tensor and writes
+        ``actions[t]`` and ``privileged_actions[t] = teacher(teacher_obs)`` (``[T, N, A]``, allocated on first use) for the transition
+        the next ``env.step()`` writes — ONE ``gf_mlp_distill_act`` launch for both MLPs of ``forward`` (a :class:`DistillForward`), the
+        sampling and the two rows.  The row, the noise seed and stream and the input rules are ``act_policy``'s (segments and the
+        strided view of a window-mode manager are read in place; ``teacher_obs=None``: the teacher reads ``obs``).  No value,
+        log-probability, mu or sigma row is written: ``process_env_step(None, episodes=stats)`` is what follows the step.  On a backend
+        without the entry point (the test-only CPU oracle) the same values are computed in torch and ``noise`` is required."""
+        if not isinstance(forward, DistillForward):
+            raise ValueError("act_distill(forward, ...) takes a DistillForward")
+        n, dev, A = self.env.num_envs, self.device, forward.num_actions
+        PolicyForward._segments(obs, forward.student, "obs", n, dev)   # (the storage's env count and device; act() checks the rest)
+        t = 0 if self.full else self.step   # (env.step() does the wrap's row copies; only the row index is needed here)
+        self._ensure_distill_rows(A)
+        stream = self._act_stream
+        self._act_stream += 1
+        actions, _teacher = forward.act(obs, teacher_obs, noise, seed=self.env._rng_seed if self._act_seed is None else self._act_seed,
+                                        stream=stream, env_offset=int(getattr(self.env, "env_offset", 0)), actions_out=self.actions[t],
+                                        teacher_actions_out=self.privileged_actions[t], backend=self.env.backend)
+        self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
+        return actions
+
+    def _act_distill_rows(self, mean: torch.Tensor, std: torch.Tensor, teacher_actions: torch.Tensor, noise: Optional[torch.Tensor] = None,
+                          std_is_log: bool = False) -> torch.Tensor:
+        """``act_distill`` from the two networks' outputs (the torch forwards of ``DistillationRunner(forward="torch")``): ``act``'s
+        sampling — ``gf_policy_act`` with only the action row — and a copy of ``teacher_actions`` into ``privileged_actions[t]``."""
+        n, dev = self.env.num_envs, self.device
+        A = int(mean.shape[1])
+        for x, name, shapes in ((mean, "mean", {(n, A)}), (std, "std", {(A,)}), (teacher_actions, "teacher_actions", {(n, A)})):
+            _check_f32(x, name, shapes, dev)
+        if noise is not None:
+            _check_f32(noise, "noise", {(n, A)}, dev)
+        t = 0 if self.full else self.step
+        self._ensure_distill_rows(A)
+        actions = torch.empty((n, A), device=dev, dtype=torch.float32)
+        stream = self._act_stream
+        self._act_stream += 1
+        fn = getattr(self.env.backend, "policy_act", None)
+        if fn is None:   # (the test-only oracle backend)
+            if noise is None:
+                raise RuntimeError("act() draws its noise in the HIP kernel: on a backend without gf_policy_act pass noise=")
+            with torch.no_grad():
+                actions.copy_(mean + (std.exp() if std_is_log else std).expand_as(mean) * noise)
+                self.actions[t].copy_(actions)
+        else:
+            a = self._act_args
+            a.num_envs, a.num_actions, a.std_per_env, a.std_is_log = n, A, 0, 1 if std_is_log else 0
+            a.mean, a.std, a.values = mean.data_ptr(), std.data_ptr(), None
+            a.noise = None if noise is None else noise.data_ptr()
+            a.seed = self.env._rng_seed if self._act_seed is None else self._act_seed
+            a.stream, a.env_offset = stream, int(getattr(self.env, "env_offset", 0))
+            a.actions, a.actions_out = actions.data_ptr(), self.actions[t].data_ptr()
+            a.mu_out = a.sigma_out = a.values_out = a.log_prob_out = None
+            self._keep_act = (mean, std, noise)
+            fn(a)
+        with torch.no_grad():
+            self.privileged_actions[t].copy_(teacher_actions)
+        self._pol_serial = self._serial + 1
+        return actions
+
+    def step_batches(self) -> Iterator[tuple]:
+        """rsl_rl's distillation ``generator()``: for ``t = 0 … T-1`` in time order ``(obs_t, privileged_actions[t])`` — the policy
+        group's observation of transition ``t`` and the teacher's actions ``act_distill`` stored for it.  Views of the stored rows, no
+        gather launch; a group of several managers is concatenated per step, a frame-stored manager goes through
+        ``observation_rows(name, t)``."""
+        if self.privileged_actions is None:
+            raise RuntimeError("step_batches() reads the teacher's actions: collect the rollout with act_distill() first")
+        names = self.obs_groups["policy"]
+
+        def rows(name, t):
+            if name in self.frames:
+                return self.observation_rows(name, t)
+            return (self.observations if name == self.obs_name else self.group_rows[name])[t]
+
+        for t in range(self.num_steps):
+            obs = rows(names[0], t) if len(names) == 1 else torch.cat([rows(m, t) for m in names], dim=-1)
+            yield obs, self.privileged_actions[t]
+
     def _act_torch(self, mean, std, values, noise, actions, t, std_is_log: bool = False) -> None:
         with torch.no_grad():
             sd = (std.exp() if std_is_log else std).expand_as(mean)
@@ -583,7 +677,10 @@ class RolloutStorage:
             raise ValueError(f"episodes keeps {episodes.num_envs} envs, the storage {n}")
         if time_outs is None and episodes is None:
             return
-        rewards, dones, values = self.rewards[t], self.dones[t], self.values[t]
+        if time_outs is not None and self.values is None:
+            raise RuntimeError("process_env_step(time_outs) bootstraps with the value rows: a rollout collected with act_distill() has none")
+        rewards, dones = self.rewards[t], self.dones[t]
+        values = None if self.values is None else self.values[t]   # (None: a distillation rollout — the statistics only)
         fn = getattr(self.env.backend, "episode_step", None)
         if fn is None:   # (the test-only oracle backend) the runner's and PPO's torch expressions
             if episodes is not None:
@@ -1101,12 +1198,169 @@ class ActorCriticMLP(torch.nn.Module):
         _update_normalizers(pairs, self._scratch.args)
 
 
+_STUDENT_TEACHER_KEYS = ("class_name", "activation", "student_hidden_dims", "teacher_hidden_dims", "init_noise_std", "noise_std_type",
+                         "student_obs_normalization", "teacher_obs_normalization")
+
+
+class StudentTeacherMLP(torch.nn.Module):
+    """rsl_rl's ``StudentTeacher`` (feed-forward): a ``student`` that reads the deployable observations and is trained, and a frozen
+    ``teacher`` that reads the privileged ones and labels every step.  Both are ``nn.Sequential`` of ``Linear`` with ``ELU`` between;
+    ``std`` (or ``log_std`` with ``noise_std_type="log"``) is the exploration noise of the student's actions during collection;
+    ``student_obs_normalizer`` / ``teacher_obs_normalizer`` are an :class:`EmpiricalNormalization` or ``nn.Identity`` — rsl_rl's
+    names throughout, so model state dicts interchange.  The teacher's parameters have ``requires_grad=False`` and the teacher and its
+    normaliser stay in eval mode whatever ``train()`` is given.
+
+    ``load_state_dict`` follows rsl_rl's rule: a PPO checkpoint (``actor.*`` keys) fills the teacher — and the teacher's normaliser
+    from ``actor_obs_normalizer.*`` when both exist — leaves the student alone and returns ``False`` ("not a resume"); a distillation
+    checkpoint (``student.*`` keys) is loaded whole and returns ``True``; both set ``loaded_teacher``; anything else raises
+    ``ValueError``."""
+
+    def __init__(self, num_student_obs: int, num_teacher_obs: int, num_actions: int, student_hidden_dims: Sequence[int] = (256, 256, 256),
+                 teacher_hidden_dims: Sequence[int] = (256, 256, 256), init_noise_std: float = 0.1, student_obs_normalization: bool = False,
+                 teacher_obs_normalization: bool = False, noise_std_type: str = "scalar"):
+        super().__init__()
+        if noise_std_type not in ("scalar", "log"):
+            raise ValueError(f"StudentTeacherMLP: noise_std_type={noise_std_type!r} is not supported ('scalar' or 'log')")
+        self.noise_std_type = noise_std_type
+        self.loaded_teacher = False
+
+        def mlp(sizes):
+            layers = []
+            for i in range(len(sizes) - 1):
+                layers.append(torch.nn.Linear(sizes[i], sizes[i + 1]))
+                if i < len(sizes) - 2:
+                    layers.append(torch.nn.ELU())
+            return torch.nn.Sequential(*layers)
+
+        self.student = mlp([int(num_student_obs), *student_hidden_dims, int(num_actions)])
+        self.teacher = mlp([int(num_teacher_obs), *teacher_hidden_dims, int(num_actions)])
+        for p in self.teacher.parameters():
+            p.requires_grad_(False)
+        if noise_std_type == "scalar":
+            self.std = torch.nn.Parameter(init_noise_std * torch.ones(num_actions))
+        else:
+            self.log_std = torch.nn.Parameter(torch.log(init_noise_std * torch.ones(num_actions)))
+        self.student_obs_normalizer = EmpiricalNormalization(int(num_student_obs)) if student_obs_normalization else torch.nn.Identity()
+        self.teacher_obs_normalizer = EmpiricalNormalization(int(num_teacher_obs)) if teacher_obs_normalization else torch.nn.Identity()
+        self._scratch = _NormScratch()
+        self.teacher.eval()
+        self.teacher_obs_normalizer.eval()
+
+    @classmethod
+    def from_train_cfg(cls, train_cfg: dict, num_student_obs: int, num_teacher_obs: int, num_actions: int) -> "StudentTeacherMLP":
+        """The policy of a distillation ``train_cfg``: ``policy.student_hidden_dims`` / ``teacher_hidden_dims`` / ``init_noise_std`` /
+        ``noise_std_type`` / ``student_obs_normalization`` / ``teacher_obs_normalization``.  Anything that cannot be honoured — an
+        unknown policy key, another activation than ``"elu"``, another class name than ``"StudentTeacher"`` — raises ``ValueError``
+        naming the key."""
+        pol = dict(train_cfg.get("policy", {}))
+        bad = sorted(k for k in pol if k not in _STUDENT_TEACHER_KEYS)
+        if bad:
+            raise ValueError(f"StudentTeacherMLP: unsupported policy keys {bad}")
+        if pol.get("activation", "elu") != "elu":
+            raise ValueError(f"StudentTeacherMLP: policy.activation={pol['activation']!r} is not supported (only 'elu')")
+        if pol.get("noise_std_type", "scalar") not in ("scalar", "log"):
+            raise ValueError(f"StudentTeacherMLP: policy.noise_std_type={pol['noise_std_type']!r} is not supported ('scalar' or 'log')")
+        if pol.get("class_name", "StudentTeacher") != "StudentTeacher":
+            raise ValueError(f"StudentTeacherMLP: policy.class_name={pol['class_name']!r} is not supported (only 'StudentTeacher')")
+        return cls(num_student_obs, num_teacher_obs, num_actions, tuple(pol.get("student_hidden_dims", (256, 256, 256))),
+                   tuple(pol.get("teacher_hidden_dims", (256, 256, 256))), float(pol.get("init_noise_std", 0.1)),
+                   student_obs_normalization=bool(pol.get("student_obs_normalization", False)),
+                   teacher_obs_normalization=bool(pol.get("teacher_obs_normalization", False)),
+                   noise_std_type=pol.get("noise_std_type", "scalar"))
+
+    @property
+    def action_std(self) -> torch.Tensor:
+        """The current action std ``[A]`` (detached): ``std``, or ``exp(log_std)``."""
+        return self.log_std.detach().exp() if self.noise_std_type == "log" else self.std.detach().clone()
+
+    def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
+        """The student on its normalised input (rsl_rl's ``act_inference``)."""
+        return self.student(self.student_obs_normalizer(obs))
+
+    def evaluate(self, teacher_obs: torch.Tensor) -> torch.Tensor:
+        """The teacher's actions, under ``no_grad``."""
+        with torch.no_grad():
+            return self.teacher(self.teacher_obs_normalizer(teacher_obs))
+
+    def update_normalization(self, obs) -> None:
+        """The student's normaliser sees this step's observations (a ``[N, W]`` tensor or up to four segments); the teacher's is
+        frozen with the teacher."""
+        norm = self.student_obs_normalizer
+        if isinstance(norm, EmpiricalNormalization) and norm.training:
+            _update_normalizers([(norm, _obs_segments(obs, norm.width, "obs", norm._mean.device))], self._scratch.args)
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        self.teacher.eval()
+        self.teacher_obs_normalizer.eval()
+        return self
+
+    def load_state_dict(self, state_dict, strict: bool = True) -> bool:
+        if any(k.startswith("actor.") for k in state_dict):   # a PPO checkpoint: its actor becomes the teacher
+            self.teacher.load_state_dict({k[len("actor."):]: v for k, v in state_dict.items() if k.startswith("actor.")}, strict=strict)
+            norm = {k[len("actor_obs_normalizer."):]: v for k, v in state_dict.items() if k.startswith("actor_obs_normalizer.")}
+            if norm and isinstance(self.teacher_obs_normalizer, EmpiricalNormalization):
+                self.teacher_obs_normalizer.load_state_dict(norm, strict=strict)
+            resumed = False
+        elif any(k.startswith("student.") for k in state_dict):
+            super().load_state_dict(state_dict, strict=strict)
+            resumed = True
+        else:
+            raise ValueError("StudentTeacherMLP.load_state_dict: the state dict has neither 'actor.*' keys (a PPO checkpoint) nor "
+                             "'student.*' keys (a distillation checkpoint)")
+        self.loaded_teacher = True
+        self.teacher.eval()
+        self.teacher_obs_normalizer.eval()
+        return resumed
+
+
 def _policy_std(policy):
     """``(parameter, is_log)``: ``policy.log_std`` where ``policy.noise_std_type == "log"`` (rsl_rl's attribute names: a foreign policy
     works too), ``policy.std`` otherwise; the parameter is None where the policy has none."""
     is_log = getattr(policy, "noise_std_type", "scalar") == "log"
     p = getattr(policy, "log_std" if is_log else "std", None)
     return (p if isinstance(p, torch.Tensor) else None), is_log
+
+
+def _walk_mlp(net, name: str, max_out: int, who: str = "PolicyForward"):
+    """[(weight, bias)] of the Linear layers of ``policy.<name>`` as ``gf_mlp_act`` / ``gf_mlp_distill_act`` read them (the Parameter
+    objects: their storage may be re-seated later), or None for a missing net; ``ValueError`` (``who: policy.<name> …``) for anything
+    the kernel cannot run."""
+    if net is None:
+        return None
+    if not isinstance(net, torch.nn.Sequential) or len(net) == 0:
+        raise ValueError(f"{who}: policy.{name} must be a non-empty nn.Sequential of Linear and ELU")
+    layers = []
+    for i, m in enumerate(net):
+        if i % 2 == 0:
+            if not isinstance(m, torch.nn.Linear):
+                raise ValueError(f"{who}: policy.{name}[{i}] is {type(m).__name__}; expected Linear")
+            if m.bias is None:
+                raise ValueError(f"{who}: policy.{name}[{i}] has no bias")
+            for p, what in ((m.weight, "weight"), (m.bias, "bias")):
+                if p.dtype != torch.float32:
+                    raise ValueError(f"{who}: policy.{name}[{i}].{what} is {p.dtype}; the kernel reads float32")
+                if not p.is_contiguous():
+                    raise ValueError(f"{who}: policy.{name}[{i}].{what} is not contiguous")
+            layers.append((m.weight, m.bias))
+        elif not isinstance(m, torch.nn.ELU) or float(m.alpha) != 1.0:
+            what = f"ELU(alpha={m.alpha})" if isinstance(m, torch.nn.ELU) else type(m).__name__
+            raise ValueError(f"{who}: policy.{name}[{i}] is {what}; only ELU(alpha=1) between Linear layers is supported")
+    if len(net) % 2 == 0:
+        raise ValueError(f"{who}: policy.{name} ends in an activation; the last module must be a Linear")
+    if len(layers) > nat.GF_MLP_MAX_LAYERS:
+        raise ValueError(f"{who}: policy.{name} has {len(layers)} Linear layers; at most {nat.GF_MLP_MAX_LAYERS}")
+    if layers[0][0].shape[1] > nat.GF_MLP_MAX_INPUT_WIDTH:
+        raise ValueError(f"{who}: policy.{name} reads {layers[0][0].shape[1]} inputs; at most {nat.GF_MLP_MAX_INPUT_WIDTH}")
+    for i, (w, _b) in enumerate(layers[:-1]):
+        if w.shape[0] > nat.GF_MLP_MAX_HIDDEN:
+            raise ValueError(f"{who}: policy.{name} has a hidden layer of width {w.shape[0]}; at most {nat.GF_MLP_MAX_HIDDEN}")
+    out = layers[-1][0].shape[0]
+    if name == "critic" and out != 1:
+        raise ValueError(f"{who}: policy.critic has {out} outputs; the value is one")
+    if out > max_out:
+        raise ValueError(f"{who}: policy.{name} has {out} outputs; at most {max_out}")
+    return layers
 
 
 class PolicyForward:
@@ -1152,41 +1406,7 @@ class PolicyForward:
     @staticmethod
     def _walk(net, name: str, max_out: int):
         """[(weight, bias)] of the net's Linear layers (the Parameter objects: their storage may be re-seated later), or None."""
-        if net is None:
-            return None
-        if not isinstance(net, torch.nn.Sequential) or len(net) == 0:
-            raise ValueError(f"PolicyForward: policy.{name} must be a non-empty nn.Sequential of Linear and ELU")
-        layers = []
-        for i, m in enumerate(net):
-            if i % 2 == 0:
-                if not isinstance(m, torch.nn.Linear):
-                    raise ValueError(f"PolicyForward: policy.{name}[{i}] is {type(m).__name__}; expected Linear")
-                if m.bias is None:
-                    raise ValueError(f"PolicyForward: policy.{name}[{i}] has no bias")
-                for p, what in ((m.weight, "weight"), (m.bias, "bias")):
-                    if p.dtype != torch.float32:
-                        raise ValueError(f"PolicyForward: policy.{name}[{i}].{what} is {p.dtype}; the kernel reads float32")
-                    if not p.is_contiguous():
-                        raise ValueError(f"PolicyForward: policy.{name}[{i}].{what} is not contiguous")
-                layers.append((m.weight, m.bias))
-            elif not isinstance(m, torch.nn.ELU) or float(m.alpha) != 1.0:
-                what = f"ELU(alpha={m.alpha})" if isinstance(m, torch.nn.ELU) else type(m).__name__
-                raise ValueError(f"PolicyForward: policy.{name}[{i}] is {what}; only ELU(alpha=1) between Linear layers is supported")
-        if len(net) % 2 == 0:
-            raise ValueError(f"PolicyForward: policy.{name} ends in an activation; the last module must be a Linear")
-        if len(layers) > nat.GF_MLP_MAX_LAYERS:
-            raise ValueError(f"PolicyForward: policy.{name} has {len(layers)} Linear layers; at most {nat.GF_MLP_MAX_LAYERS}")
-        if layers[0][0].shape[1] > nat.GF_MLP_MAX_INPUT_WIDTH:
-            raise ValueError(f"PolicyForward: policy.{name} reads {layers[0][0].shape[1]} inputs; at most {nat.GF_MLP_MAX_INPUT_WIDTH}")
-        for i, (w, _b) in enumerate(layers[:-1]):
-            if w.shape[0] > nat.GF_MLP_MAX_HIDDEN:
-                raise ValueError(f"PolicyForward: policy.{name} has a hidden layer of width {w.shape[0]}; at most {nat.GF_MLP_MAX_HIDDEN}")
-        out = layers[-1][0].shape[0]
-        if name == "critic" and out != 1:
-            raise ValueError(f"PolicyForward: policy.critic has {out} outputs; the value is one")
-        if out > max_out:
-            raise ValueError(f"PolicyForward: policy.{name} has {out} outputs; at most {max_out}")
-        return layers
+        return _walk_mlp(net, name, max_out)
 
     def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
         """The policy's current normaliser in front of ``name`` (None: the net reads its input as it is)."""
@@ -1270,6 +1490,106 @@ class PolicyForward:
         return self._one(critic_obs, self.critic, "critic", self.policy.critic)
 
 
+class DistillForward:
+    """The student and the teacher of a policy (``policy.student`` / ``policy.teacher``, a :class:`StudentTeacherMLP` or anything of
+    that shape) as ``gf_mlp_distill_act`` reads them — the counterpart of :class:`PolicyForward`, under its rules: the structure is
+    checked once, the weight addresses and the normalisers (``policy.student_obs_normalizer`` / ``teacher_obs_normalizer``) are looked
+    up at every call.  Both nets are required and must have the same output width; ``policy.std`` (``log_std``) must be ``[A]``.
+
+    ``mean(obs)``: the student's mean — play-time inference, one ``gf_mlp_act`` launch.  ``act(obs, teacher_obs)``: the collection
+    step, ONE ``gf_mlp_distill_act`` launch; ``RolloutStorage.act_distill`` calls it with its rows as the second destinations."""
+
+    def __init__(self, policy):
+        self.policy = policy
+        self.student = _walk_mlp(getattr(policy, "student", None), "student", nat.GF_MLP_MAX_ACTIONS, "DistillForward")
+        self.teacher = _walk_mlp(getattr(policy, "teacher", None), "teacher", nat.GF_MLP_MAX_ACTIONS, "DistillForward")
+        if self.student is None or self.teacher is None:
+            raise ValueError("DistillForward: the policy needs a student and a teacher")
+        A = int(self.student[-1][0].shape[0])
+        if int(self.teacher[-1][0].shape[0]) != A:
+            raise ValueError(f"DistillForward: policy.student has {A} outputs, policy.teacher {int(self.teacher[-1][0].shape[0])}")
+        self._normalizer("student"), self._normalizer("teacher")   # (refuses what the kernel cannot fold in)
+        std, is_log = _policy_std(policy)
+        self.std_is_log, self._std_name = is_log, "log_std" if is_log else "std"
+        if std is None or std.dtype != torch.float32 or tuple(std.shape) != (A,):
+            raise ValueError(f"DistillForward: policy.{self._std_name} must be a float32 [{A}] tensor")
+        self.num_actions = A
+        self._args, self._mean_args = nat.GfMlpDistillArgs(), nat.GfMlpActArgs()
+
+    def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
+        layers = self.student if name == "student" else self.teacher
+        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), int(layers[0][0].shape[1]), f"DistillForward: policy.{name}_obs_normalizer")
+
+    def mean(self, obs) -> torch.Tensor:
+        """The student's output ``[N, A]`` (``policy.act_mean(obs)``): one launch, a fresh tensor."""
+        parts = PolicyForward._segments(obs, self.student, "obs", None, None)
+        norm = self._normalizer("student")
+        fn = getattr(nat.get_backend(), "mlp_act", None)
+        if fn is None:   # (the test-only oracle backend)
+            with torch.no_grad():
+                x = parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+                return self.policy.student(x if norm is None else norm(x))
+        n = int(parts[0].shape[0])
+        out = torch.empty((n, self.num_actions), device=parts[0].device, dtype=torch.float32)
+        a = self._mean_args
+        a.num_envs = n
+        PolicyForward._fill_net(a.actor, self.student, parts, norm)
+        a.critic.num_layers = 0
+        a.mean = out.data_ptr()
+        self._keep_mean = (parts, out)
+        fn(a)
+        return out
+
+    def act(self, obs, teacher_obs=None, noise: Optional[torch.Tensor] = None, seed: int = 0, stream: int = 0, env_offset: int = 0,
+            actions_out: Optional[torch.Tensor] = None, teacher_actions_out: Optional[torch.Tensor] = None, backend=None):
+        """``(actions, teacher_actions)``, fresh ``[N, A]`` tensors: ``Normal(student(obs), std).sample()`` and ``teacher(teacher_obs)``
+        (``teacher_obs=None``: the teacher reads ``obs``) in ONE ``gf_mlp_distill_act`` launch; ``actions_out`` / ``teacher_actions_out``:
+        contiguous ``[N, A]`` rows that receive the same values from the same launch.  ``noise`` / ``seed`` / ``stream`` /
+        ``env_offset``: as ``gf_policy_act``'s.  On a backend without the entry point (the test-only CPU oracle) the same expression
+        runs in torch and ``noise`` is required."""
+        segs = PolicyForward._segments(obs, self.student, "obs", None, None)
+        n, dev = int(segs[0].shape[0]), segs[0].device
+        tsegs = PolicyForward._segments(obs if teacher_obs is None else teacher_obs, self.teacher,
+                                        "obs (the teacher's input)" if teacher_obs is None else "teacher_obs", n, dev)
+        A = self.num_actions
+        std = getattr(self.policy, self._std_name)
+        _check_f32(std, f"policy.{self._std_name}", {(A,)}, dev)
+        for t, name in ((noise, "noise"), (actions_out, "actions_out"), (teacher_actions_out, "teacher_actions_out")):
+            if t is not None:
+                _check_f32(t, name, {(n, A)}, dev)
+        backend = nat.get_backend() if backend is None else backend
+        fn = getattr(backend, "mlp_distill_act", None)
+        if fn is None:   # (the test-only oracle backend) the same expression in torch, from the given draws
+            if noise is None:
+                raise RuntimeError("act() draws its noise in the HIP kernel: on a backend without gf_mlp_distill_act pass noise=")
+            cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+            with torch.no_grad():
+                mean, teacher = self.policy.act_mean(cat(segs)), self.policy.evaluate(cat(tsegs)).clone()
+                sd = (std.exp() if self.std_is_log else std).expand_as(mean)
+                actions = mean + sd * noise
+                if actions_out is not None:
+                    actions_out.copy_(actions)
+                if teacher_actions_out is not None:
+                    teacher_actions_out.copy_(teacher)
+            return actions, teacher
+        actions = torch.empty((n, A), device=dev, dtype=torch.float32)
+        teacher = torch.empty((n, A), device=dev, dtype=torch.float32)
+        a = self._args
+        a.num_envs = n
+        PolicyForward._fill_net(a.student, self.student, segs, self._normalizer("student"))
+        PolicyForward._fill_net(a.teacher, self.teacher, tsegs, self._normalizer("teacher"))
+        a.std, a.std_is_log = std.data_ptr(), 1 if self.std_is_log else 0
+        a.noise = None if noise is None else noise.data_ptr()
+        a.seed, a.stream, a.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(env_offset)
+        a.mean = None
+        a.actions, a.teacher_actions = actions.data_ptr(), teacher.data_ptr()
+        a.actions_out = None if actions_out is None else actions_out.data_ptr()
+        a.teacher_actions_out = None if teacher_actions_out is None else teacher_actions_out.data_ptr()
+        self._keep = (segs, tsegs, noise, actions_out, teacher_actions_out)
+        fn(a)
+        return actions, teacher
+
+
 class GradientAllReduce:
     """Average the gradients of ``params`` over the ranks of ``group`` with one collective.
 
@@ -1345,7 +1665,157 @@ _SYMMETRY_KEYS = ("use_data_augmentation", "use_mirror_loss", "mirror_loss_coeff
 _ADAM_BETAS, _ADAM_EPS = (0.9, 0.999), 1e-8   # torch.optim.Adam's defaults, as rsl_rl constructs it
 
 
-class PPO:
+class _FlatAdam:
+    """What :class:`PPO` and :class:`Distillation` share: the trainable parameters of ``grad_sync`` (a :class:`GradientAllReduce`) as
+    views of ONE flat buffer in the bucket's order, flat Adam moments, the device control block (lr as a double, the step), the
+    ``gf_adam_step`` call with its torch twin, and the optimizer state in ``torch.optim.Adam``'s format.  The host class provides
+    ``grad_sync``, ``max_grad_norm``, ``adaptive``, ``desired_kl`` and — for the adaptive schedule — ``_out`` with ``kl_mean`` at [3]."""
+
+    def _init_flat(self, learning_rate: float) -> None:
+        sync = self.grad_sync
+        # the parameters as views of one flat buffer, in the bucket's order
+        self.params = torch.empty_like(sync.bucket)
+        off = 0
+        with torch.no_grad():
+            for p in sync.params:
+                k = p.numel()
+                self.params[off:off + k].copy_(p.data.reshape(-1))
+                p.data = self.params[off:off + k].view_as(p)
+                off += k
+        dev = self.params.device
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        # device control block: GfAdamState[2] = {lr (double), step (int64)} x 2, read at parity, written at 1 - parity
+        self._state = torch.zeros(4, device=dev, dtype=torch.int64)
+        self._state_lr = self._state.view(torch.float64)
+        self._state_lr[0] = float(learning_rate)
+        self._calls = 0
+        self._adam_ws = torch.zeros(max(1, nat.adam_workspace_bytes(self.params.numel()) // 8), device=dev, dtype=torch.float64)
+        self._adam_args = nat.GfAdamArgs()
+
+    @property
+    def learning_rate(self) -> float:
+        """The current learning rate (one host read)."""
+        return float(self._state_lr[2 * (self._calls & 1)])
+
+    # -- the optimizer state, in torch.optim.Adam's format ---------------------------------------------------------------------------
+    def optimizer_state_dict(self) -> dict:
+        """What ``torch.optim.Adam(policy.parameters(), lr).state_dict()`` would hold now (rsl_rl's ``"optimizer_state_dict"``):
+        ``"state"`` — ``{i: {"step", "exp_avg", "exp_avg_sq"}}`` for parameter ``i`` of the bucket's order (``policy.parameters()``'s),
+        the moments as clones shaped like the parameter, ``step`` the 0-dim tensor the installed torch writes; ``{}`` before the first
+        step, as torch's — and one ``"param_groups"`` entry with the installed torch's own keys, the current ``lr`` (one host read),
+        the module's betas and eps, and ``params = [0 … P-1]``."""
+        # the group's keys and the step's dtype and device come from the installed torch: a throw-away Adam that takes one step
+        dummy = torch.nn.Parameter(torch.zeros(1))
+        dummy.grad = torch.zeros(1)
+        probe = torch.optim.Adam([dummy], lr=1.0)
+        probe.step()
+        probe = probe.state_dict()
+        step_like = probe["state"][0]["step"]
+        params = self.grad_sync.params
+        group = dict(probe["param_groups"][0], lr=self.learning_rate, betas=_ADAM_BETAS, eps=_ADAM_EPS, params=list(range(len(params))))
+        state, off = {}, 0
+        if self._calls > 0:
+            for i, p in enumerate(params):
+                k = p.numel()
+                state[i] = {"step": torch.full_like(step_like, self._calls),
+                            "exp_avg": self.exp_avg[off:off + k].view_as(p).clone(), "exp_avg_sq": self.exp_avg_sq[off:off + k].view_as(p).clone()}
+                off += k
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, sd: dict) -> None:
+        """The inverse: the moments are copied into the flat ``exp_avg`` / ``exp_avg_sq`` in place, ``lr`` and ``step`` go into the slot
+        of the control block the next ``gf_adam_step`` reads.  An empty ``"state"`` zeroes the moments and the step.  ``ValueError`` for
+        what this Adam cannot continue from: another parameter count or shape, ``step`` values that differ between the parameters,
+        ``amsgrad`` / ``weight_decay`` / ``maximize`` off their defaults, betas or eps other than this module's."""
+        who = f"{type(self).__name__}.load_optimizer_state_dict"
+        groups = sd.get("param_groups") if isinstance(sd, dict) else None
+        if not isinstance(groups, (list, tuple)) or len(groups) != 1 or not isinstance(sd.get("state"), dict):
+            raise ValueError(f"{who}: expected torch.optim.Adam's {{'state', 'param_groups'}} with one parameter group")
+        group, state, params = groups[0], sd["state"], self.grad_sync.params
+        if len(group.get("params", ())) != len(params):
+            raise ValueError(f"{who}: the state holds {len(group.get('params', ()))} parameters, the policy {len(params)}")
+        for key, default in (("amsgrad", False), ("weight_decay", 0), ("maximize", False)):
+            if group.get(key, default) != default:
+                raise ValueError(f"{who}: {key}={group[key]!r} is not supported (only Adam's default {default!r})")
+        if tuple(float(b) for b in group.get("betas", _ADAM_BETAS)) != _ADAM_BETAS:
+            raise ValueError(f"{who}: betas={tuple(group['betas'])!r}; this Adam steps with {_ADAM_BETAS}")
+        if float(group.get("eps", _ADAM_EPS)) != _ADAM_EPS:
+            raise ValueError(f"{who}: eps={group['eps']!r}; this Adam steps with {_ADAM_EPS}")
+        if "lr" not in group:
+            raise ValueError(f"{who}: the parameter group has no lr")
+        lr, step = float(group["lr"]), 0
+        if state:
+            ids = list(group["params"])
+            if sorted(state) != sorted(ids):
+                raise ValueError(f"{who}: the state covers parameters {sorted(state)}, the group lists {sorted(ids)}: a different parameter count")
+            for i, p in zip(ids, params):
+                for name in ("step", "exp_avg", "exp_avg_sq"):
+                    if name not in state[i]:
+                        raise ValueError(f"{who}: parameter {i} has no {name}")
+                for name in ("exp_avg", "exp_avg_sq"):
+                    if tuple(state[i][name].shape) != tuple(p.shape):
+                        raise ValueError(f"{who}: {name} of parameter {i} has shape {tuple(state[i][name].shape)}, the parameter {tuple(p.shape)}")
+            steps = {float(state[i]["step"]) for i in ids}
+            step = int(steps.pop())
+            if steps or step < 0:
+                raise ValueError(f"{who}: the parameters' step values are not all equal (one flat bucket takes one step count)")
+        with torch.no_grad():
+            if state:
+                off = 0
+                for i, p in zip(ids, params):
+                    k = p.numel()
+                    self.exp_avg[off:off + k].view_as(p).copy_(state[i]["exp_avg"])
+                    self.exp_avg_sq[off:off + k].view_as(p).copy_(state[i]["exp_avg_sq"])
+                    off += k
+            else:
+                self.exp_avg.zero_()
+                self.exp_avg_sq.zero_()
+            par = step & 1   # (the slot the next step reads: every step reads `_calls & 1` and writes the other)
+            self._state_lr[2 * par] = lr
+            self._state[2 * par + 1] = step
+        self._calls = step
+
+    def _adam_hip(self, backend) -> None:
+        a, par = self._adam_args, self._calls & 1
+        a.numel = self.params.numel()
+        a.params, a.grads, a.exp_avg, a.exp_avg_sq = (t.data_ptr() for t in (self.params, self.grad_sync.bucket, self.exp_avg, self.exp_avg_sq))
+        a.state = self._state.data_ptr()
+        a.kl_mean = self._out.data_ptr() + 3 * 4 if self.adaptive else None
+        a.workspace, a.workspace_bytes = self._adam_ws.data_ptr(), self._adam_ws.numel() * 8
+        a.desired_kl = self.desired_kl if self.adaptive else 0.0
+        a.beta1, a.beta2, a.eps = _ADAM_BETAS[0], _ADAM_BETAS[1], _ADAM_EPS
+        a.max_grad_norm = self.max_grad_norm
+        a.schedule = nat.GF_ADAM_SCHEDULE_ADAPTIVE if self.adaptive else nat.GF_ADAM_SCHEDULE_FIXED
+        a.parity = par
+        backend.adam_step(a)
+        self._calls += 1
+
+    def _adam_torch(self) -> None:
+        """The schedule, ``clip_grad_norm_`` and torch.optim.Adam's foreach arithmetic as tensor operations (no host read)."""
+        par = self._calls & 1
+        with torch.no_grad():
+            lr = self._state_lr[2 * par].clone()
+            if self.adaptive:
+                kl = self._out[3]   # (float32 against a Python float: compared in float32, as rsl_rl's `kl_mean > desired_kl * 2.0`)
+                down = torch.clamp(lr / 1.5, min=1e-5)
+                up = torch.clamp(lr * 1.5, max=1e-2)
+                lr = torch.where(kl > self.desired_kl * 2.0, down, torch.where((kl < self.desired_kl / 2.0) & (kl > 0.0), up, lr))
+            step = self._calls + 1
+            g = self.grad_sync.bucket
+            torch.nn.utils.clip_grad_norm_(self.grad_sync.params, self.max_grad_norm)
+            b1, b2 = _ADAM_BETAS
+            bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+            step_size = ((lr / bc1) * -1).to(torch.float32)
+            self.exp_avg.lerp_(g, 1 - b1)
+            self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
+            denom = (self.exp_avg_sq.sqrt() / (bc2 ** 0.5)).add_(_ADAM_EPS)
+            self.params.add_(step_size * (self.exp_avg / denom))
+            self._state_lr[2 * (1 - par)] = lr
+            self._state[2 * (1 - par) + 1] = step
+        self._calls += 1
+
+
+class PPO(_FlatAdam):
     """rsl_rl's ``PPO`` (non-recurrent, no RND) over a :class:`RolloutStorage` and an :class:`ActorCriticMLP`.
 
     ``PPO(policy, storage, **train_cfg["algorithm"])`` takes the dict of ``examples/*/train.py`` as written (``class_name`` is
@@ -1418,27 +1888,12 @@ class PPO:
         ids = {id(p) for p in sync.params}
         if any(p.requires_grad and id(p) not in ids for p in policy.parameters()) or id(std) not in ids:
             raise ValueError("grad_sync must hold every trainable parameter of the policy")
-        # the parameters as views of one flat buffer, in the bucket's order
-        self.params = torch.empty_like(sync.bucket)
-        off = 0
-        with torch.no_grad():
-            for p in sync.params:
-                k = p.numel()
-                self.params[off:off + k].copy_(p.data.reshape(-1))
-                p.data = self.params[off:off + k].view_as(p)
-                off += k
+        self._init_flat(float(cfg["learning_rate"]))
         dev = self.params.device
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        # device control block: GfAdamState[2] = {lr (double), step (int64)} x 2, read at parity, written at 1 - parity
-        self._state = torch.zeros(4, device=dev, dtype=torch.int64)
-        self._state_lr = self._state.view(torch.float64)
-        self._state_lr[0] = float(cfg["learning_rate"])
-        self._calls = 0
-        self._adam_ws = torch.zeros(max(1, nat.adam_workspace_bytes(self.params.numel()) // 8), device=dev, dtype=torch.float64)
         self._out = torch.zeros(nat.GF_PPO_OUT_COUNT, device=dev, dtype=torch.float32)   # surrogate, value_loss, entropy, kl_mean, loss
         self._sums = torch.zeros(4, device=dev, dtype=torch.float64)                      # value_function, surrogate, entropy, symmetry
         self._mb_key = None
-        self._loss_args, self._adam_args = nat.GfPpoLossArgs(), nat.GfAdamArgs()
+        self._loss_args = nat.GfPpoLossArgs()
         if self.symmetry is not None:   # the tables go up here, once: no copy from the host inside an update
             for kind in ("policy", "critic", "actions"):
                 self.symmetry["func"].tables(kind, dev)
@@ -1473,88 +1928,6 @@ class PPO:
                 raise ValueError(f"PPO: symmetry_cfg: the {what} table of the MirrorSymmetry is {have} wide, the {what} {want}")
         return {"func": fn, "augment": bool(cfg.get("use_data_augmentation", False)), "mirror": bool(cfg.get("use_mirror_loss", False)),
                 "coeff": float(cfg.get("mirror_loss_coeff", 0.0))}
-
-    @property
-    def learning_rate(self) -> float:
-        """The current learning rate (one host read)."""
-        return float(self._state_lr[2 * (self._calls & 1)])
-
-    # -- the optimizer state, in torch.optim.Adam's format ---------------------------------------------------------------------------
-    def optimizer_state_dict(self) -> dict:
-        """What ``torch.optim.Adam(policy.parameters(), lr).state_dict()`` would hold now (rsl_rl's ``"optimizer_state_dict"``):
-        ``"state"`` — ``{i: {"step", "exp_avg", "exp_avg_sq"}}`` for parameter ``i`` of the bucket's order (``policy.parameters()``'s),
-        the moments as clones shaped like the parameter, ``step`` the 0-dim tensor the installed torch writes; ``{}`` before the first
-        step, as torch's — and one ``"param_groups"`` entry with the installed torch's own keys, the current ``lr`` (one host read),
-        the module's betas and eps, and ``params = [0 … P-1]``."""
-        # the group's keys and the step's dtype and device come from the installed torch: a throw-away Adam that takes one step
-        dummy = torch.nn.Parameter(torch.zeros(1))
-        dummy.grad = torch.zeros(1)
-        probe = torch.optim.Adam([dummy], lr=1.0)
-        probe.step()
-        probe = probe.state_dict()
-        step_like = probe["state"][0]["step"]
-        params = self.grad_sync.params
-        group = dict(probe["param_groups"][0], lr=self.learning_rate, betas=_ADAM_BETAS, eps=_ADAM_EPS, params=list(range(len(params))))
-        state, off = {}, 0
-        if self._calls > 0:
-            for i, p in enumerate(params):
-                k = p.numel()
-                state[i] = {"step": torch.full_like(step_like, self._calls),
-                            "exp_avg": self.exp_avg[off:off + k].view_as(p).clone(), "exp_avg_sq": self.exp_avg_sq[off:off + k].view_as(p).clone()}
-                off += k
-        return {"state": state, "param_groups": [group]}
-
-    def load_optimizer_state_dict(self, sd: dict) -> None:
-        """The inverse: the moments are copied into the flat ``exp_avg`` / ``exp_avg_sq`` in place, ``lr`` and ``step`` go into the slot
-        of the control block the next ``gf_adam_step`` reads.  An empty ``"state"`` zeroes the moments and the step.  ``ValueError`` for
-        what this Adam cannot continue from: another parameter count or shape, ``step`` values that differ between the parameters,
-        ``amsgrad`` / ``weight_decay`` / ``maximize`` off their defaults, betas or eps other than this module's."""
-        groups = sd.get("param_groups") if isinstance(sd, dict) else None
-        if not isinstance(groups, (list, tuple)) or len(groups) != 1 or not isinstance(sd.get("state"), dict):
-            raise ValueError("PPO.load_optimizer_state_dict: expected torch.optim.Adam's {'state', 'param_groups'} with one parameter group")
-        group, state, params = groups[0], sd["state"], self.grad_sync.params
-        if len(group.get("params", ())) != len(params):
-            raise ValueError(f"PPO.load_optimizer_state_dict: the state holds {len(group.get('params', ()))} parameters, the policy {len(params)}")
-        for key, default in (("amsgrad", False), ("weight_decay", 0), ("maximize", False)):
-            if group.get(key, default) != default:
-                raise ValueError(f"PPO.load_optimizer_state_dict: {key}={group[key]!r} is not supported (only Adam's default {default!r})")
-        if tuple(float(b) for b in group.get("betas", _ADAM_BETAS)) != _ADAM_BETAS:
-            raise ValueError(f"PPO.load_optimizer_state_dict: betas={tuple(group['betas'])!r}; this Adam steps with {_ADAM_BETAS}")
-        if float(group.get("eps", _ADAM_EPS)) != _ADAM_EPS:
-            raise ValueError(f"PPO.load_optimizer_state_dict: eps={group['eps']!r}; this Adam steps with {_ADAM_EPS}")
-        if "lr" not in group:
-            raise ValueError("PPO.load_optimizer_state_dict: the parameter group has no lr")
-        lr, step = float(group["lr"]), 0
-        if state:
-            ids = list(group["params"])
-            if sorted(state) != sorted(ids):
-                raise ValueError(f"PPO.load_optimizer_state_dict: the state covers parameters {sorted(state)}, the group lists {sorted(ids)}: a different parameter count")
-            for i, p in zip(ids, params):
-                for name in ("step", "exp_avg", "exp_avg_sq"):
-                    if name not in state[i]:
-                        raise ValueError(f"PPO.load_optimizer_state_dict: parameter {i} has no {name}")
-                for name in ("exp_avg", "exp_avg_sq"):
-                    if tuple(state[i][name].shape) != tuple(p.shape):
-                        raise ValueError(f"PPO.load_optimizer_state_dict: {name} of parameter {i} has shape {tuple(state[i][name].shape)}, the parameter {tuple(p.shape)}")
-            steps = {float(state[i]["step"]) for i in ids}
-            step = int(steps.pop())
-            if steps or step < 0:
-                raise ValueError("PPO.load_optimizer_state_dict: the parameters' step values are not all equal (one flat bucket takes one step count)")
-        with torch.no_grad():
-            if state:
-                off = 0
-                for i, p in zip(ids, params):
-                    k = p.numel()
-                    self.exp_avg[off:off + k].view_as(p).copy_(state[i]["exp_avg"])
-                    self.exp_avg_sq[off:off + k].view_as(p).copy_(state[i]["exp_avg_sq"])
-                    off += k
-            else:
-                self.exp_avg.zero_()
-                self.exp_avg_sq.zero_()
-            par = step & 1   # (the slot the next step reads: every step reads `_calls & 1` and writes the other)
-            self._state_lr[2 * par] = lr
-            self._state[2 * par + 1] = step
-        self._calls = step
 
     def compute_returns(self, last_critic_obs: torch.Tensor) -> None:
         """rsl_rl ``PPO.compute_returns``: the critic's value of the bootstrap observation, then GAE over the storage.  The value is
@@ -1803,21 +2176,6 @@ class PPO:
         backend.ppo_loss(a)
         return gmu, gval
 
-    def _adam_hip(self, backend) -> None:
-        a, par = self._adam_args, self._calls & 1
-        a.numel = self.params.numel()
-        a.params, a.grads, a.exp_avg, a.exp_avg_sq = (t.data_ptr() for t in (self.params, self.grad_sync.bucket, self.exp_avg, self.exp_avg_sq))
-        a.state = self._state.data_ptr()
-        a.kl_mean = self._out.data_ptr() + 3 * 4 if self.adaptive else None
-        a.workspace, a.workspace_bytes = self._adam_ws.data_ptr(), self._adam_ws.numel() * 8
-        a.desired_kl = self.desired_kl if self.adaptive else 0.0
-        a.beta1, a.beta2, a.eps = _ADAM_BETAS[0], _ADAM_BETAS[1], _ADAM_EPS
-        a.max_grad_norm = self.max_grad_norm
-        a.schedule = nat.GF_ADAM_SCHEDULE_ADAPTIVE if self.adaptive else nat.GF_ADAM_SCHEDULE_FIXED
-        a.parity = par
-        backend.adam_step(a)
-        self._calls += 1
-
     # -- the same arithmetic in torch (backends without gf_ppo_loss / gf_adam_step) -------------------------------------------------
     def _loss_torch(self, mu, value, b: MiniBatch, kl_rows: int = 0, extra=None) -> None:
         """rsl_rl PPO.update's loss lines, ``loss.backward()``, and the values gf_ppo_loss leaves in ``out`` / ``sums``.  ``kl_rows``:
@@ -1851,26 +2209,122 @@ class PPO:
             self._out.copy_(torch.stack([surrogate_loss, value_loss, ent_mean, kl_mean, loss]).to(torch.float32))
             self._sums[:3].add_(torch.stack([value_loss, surrogate_loss, ent_mean]).to(torch.float64))
 
-    def _adam_torch(self) -> None:
-        """The schedule, ``clip_grad_norm_`` and torch.optim.Adam's foreach arithmetic as tensor operations (no host read)."""
-        par = self._calls & 1
+
+# ---- teacher–student distillation: rsl_rl Distillation.update -----------------------------------------------------------------------
+_DISTILL_KEYS = ("num_learning_epochs", "gradient_length", "learning_rate", "max_grad_norm", "loss_type")
+_DISTILL_DEFAULTS = dict(num_learning_epochs=1, gradient_length=15, learning_rate=1e-3, max_grad_norm=None, loss_type="mse")
+_BC_LOSS_TYPES = {"mse": nat.GF_BC_LOSS_MSE, "huber": nat.GF_BC_LOSS_HUBER}
+
+
+class Distillation(_FlatAdam):
+    """rsl_rl's ``Distillation`` (feed-forward student, one rank) over a :class:`RolloutStorage` collected with ``act_distill`` and a
+    :class:`StudentTeacherMLP`: the student is regressed onto the teacher's stored actions.
+
+    ``Distillation(policy, storage, **train_cfg["algorithm"])``: ``num_learning_epochs``, ``gradient_length``, ``learning_rate``,
+    ``max_grad_norm`` (``None``: no clipping) and ``loss_type`` (``"mse"`` or ``"huber"``); ``class_name`` is ignored, unknown keys
+    and bad values raise ``ValueError``.  At construction the STUDENT's parameters move into one flat buffer with flat Adam moments
+    and the device control block, as :class:`PPO` does it; ``std`` and the teacher stay where they are and are never stepped.
+
+    ``update()`` walks ``storage.step_batches()`` in time order, ``num_learning_epochs`` times: per step the student's forward and
+    backward stay in torch, the loss and its gradient w.r.t. the student's mean are one ``gf_bc_loss`` (two launches) whose gradient
+    is back-propagated into the bucket; every ``gradient_length`` steps — the counter runs on across the epochs of one update — one
+    ``gf_adam_step`` (fixed schedule; ``max_grad_norm=None`` is passed as the largest finite float, a clip coefficient of exactly 1)
+    applies the accumulated gradient and the bucket is zeroed.  Gradients still pending when the update ends are dropped — rsl_rl's
+    behaviour: the loss accumulated since the last optimizer step is discarded — so the steps behind the update's last optimizer step
+    run their forward without a graph and ``gf_bc_loss`` in its loss-only mode: they are logged, nothing is back-propagated.  No host synchronisation per step (rsl_rl reads
+    ``behavior_loss.item()`` each time); the returned mean is the one read of the update.  On a backend without the entry points
+    (the test-only CPU oracle) the same arithmetic runs in torch.
+
+    ``optimizer_state_dict()`` is ``torch.optim.Adam``'s format over the student's parameters.  It is NOT interchangeable with
+    rsl_rl's distillation checkpoints, whose Adam was built over every parameter of the policy (the teacher's and ``std`` take index
+    slots there); only the model state interchanges."""
+
+    def __init__(self, policy: "StudentTeacherMLP", storage: RolloutStorage, **algorithm):
+        algorithm = dict(algorithm)
+        algorithm.pop("class_name", None)
+        bad = sorted(k for k in algorithm if k not in _DISTILL_KEYS)
+        if bad:
+            raise ValueError(f"Distillation: unsupported algorithm keys {bad}")
+        cfg = dict(_DISTILL_DEFAULTS, **algorithm)
+        if cfg["loss_type"] not in _BC_LOSS_TYPES:
+            raise ValueError(f"Distillation: loss_type={cfg['loss_type']!r} is not supported ('mse' or 'huber')")
+        if int(cfg["gradient_length"]) < 1 or int(cfg["num_learning_epochs"]) < 1:
+            raise ValueError("Distillation: gradient_length and num_learning_epochs must be >= 1")
+        if cfg["max_grad_norm"] is not None and not float(cfg["max_grad_norm"]) > 0.0:
+            raise ValueError(f"Distillation: max_grad_norm={cfg['max_grad_norm']!r} must be > 0 (or None)")
+        if not isinstance(getattr(policy, "student", None), torch.nn.Module) or not isinstance(getattr(policy, "teacher", None), torch.nn.Module):
+            raise ValueError("Distillation needs a policy with a student, a teacher, act_mean() and evaluate() (StudentTeacherMLP)")
+        self.policy, self.storage = policy, storage
+        self.num_learning_epochs, self.gradient_length = int(cfg["num_learning_epochs"]), int(cfg["gradient_length"])
+        self.loss_type = cfg["loss_type"]
+        # None: the largest finite float — the norm of a finite gradient never exceeds it, so the clip coefficient is exactly 1
+        self.max_grad_norm = torch.finfo(torch.float32).max if cfg["max_grad_norm"] is None else float(cfg["max_grad_norm"])
+        self.schedule, self.adaptive, self.desired_kl = "fixed", False, None
+        self.num_actions = int(policy.student[-1].weight.shape[0])
+        self.grad_sync = GradientAllReduce(policy.student.parameters())   # (one rank: a bucket, never a collective)
+        self._init_flat(float(cfg["learning_rate"]))
+        dev = self.params.device
+        self._out = torch.zeros(1, device=dev, dtype=torch.float32)
+        self._sums = torch.zeros(1, device=dev, dtype=torch.float64)
+        self._loss_args = nat.GfBcLossArgs()
+        self._grad = self._loss_ws = None
+
+    def _bc_hip(self, backend, mu: torch.Tensor, target: torch.Tensor, want_grad: bool = True) -> torch.Tensor:
+        n, A = int(target.shape[0]), self.num_actions
+        if tuple(mu.shape) != (n, A) or mu.dtype != torch.float32 or not mu.is_contiguous():
+            raise ValueError(f"Distillation: the student's mean must be a contiguous float32 {(n, A)} tensor, not {tuple(mu.shape)} {mu.dtype}")
+        if self._grad is None or tuple(self._grad.shape) != (n, A):
+            self._grad = torch.empty((n, A), device=mu.device, dtype=torch.float32)
+            self._loss_ws = torch.empty(max(1, nat.bc_loss_workspace_bytes(n) // 8), device=mu.device, dtype=torch.float64)
+        a = self._loss_args
+        a.num_rows, a.num_actions, a.loss_type = n, A, _BC_LOSS_TYPES[self.loss_type]
+        a.mu, a.target, a.grad = mu.data_ptr(), target.data_ptr(), self._grad.data_ptr() if want_grad else None
+        a.out, a.sums = self._out.data_ptr(), self._sums.data_ptr()
+        a.workspace, a.workspace_bytes = self._loss_ws.data_ptr(), self._loss_ws.numel() * 8
+        self._keep = (mu, target)
+        backend.bc_loss(a)
+        return self._grad
+
+    def _bc_torch(self, mu: torch.Tensor, target: torch.Tensor, backward: bool = True) -> None:
+        """rsl_rl's ``loss_fn(actions, privileged_actions)`` and its ``backward()``, which accumulates into the bucket."""
+        fn = torch.nn.functional.mse_loss if self.loss_type == "mse" else torch.nn.functional.huber_loss
+        loss = fn(mu, target)
+        if backward:
+            loss.backward()
         with torch.no_grad():
-            lr = self._state_lr[2 * par].clone()
-            if self.adaptive:
-                kl = self._out[3]   # (float32 against a Python float: compared in float32, as rsl_rl's `kl_mean > desired_kl * 2.0`)
-                down = torch.clamp(lr / 1.5, min=1e-5)
-                up = torch.clamp(lr * 1.5, max=1e-2)
-                lr = torch.where(kl > self.desired_kl * 2.0, down, torch.where((kl < self.desired_kl / 2.0) & (kl > 0.0), up, lr))
-            step = self._calls + 1
-            g = self.grad_sync.bucket
-            torch.nn.utils.clip_grad_norm_(self.grad_sync.params, self.max_grad_norm)
-            b1, b2 = _ADAM_BETAS
-            bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
-            step_size = ((lr / bc1) * -1).to(torch.float32)
-            self.exp_avg.lerp_(g, 1 - b1)
-            self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
-            denom = (self.exp_avg_sq.sqrt() / (bc2 ** 0.5)).add_(_ADAM_EPS)
-            self.params.add_(step_size * (self.exp_avg / denom))
-            self._state_lr[2 * (1 - par)] = lr
-            self._state[2 * (1 - par) + 1] = step
-        self._calls += 1
+            self._out[0] = loss.detach()
+            self._sums[0] += loss.detach().to(torch.float64)
+
+    def update(self) -> Dict[str, float]:
+        """One distillation update over the stored rollout; returns ``{"behavior": mean loss per step}`` — its one host read."""
+        sync, policy, backend = self.grad_sync, self.policy, self.storage.env.backend
+        hip = getattr(backend, "bc_loss", None) is not None   # (else the test-only oracle backend: torch's loss, autograd, torch Adam)
+        self._sums.zero_()
+        sync.zero_grad()
+        total = self.num_learning_epochs * self.storage.num_steps
+        stepped = total - total % self.gradient_length   # the steps past it never reach an optimizer step: their loss is logged only
+        cnt = 0
+        for _epoch in range(self.num_learning_epochs):
+            for obs, target in self.storage.step_batches():
+                if cnt >= stepped:   # no graph, no gradient, no backward
+                    with torch.no_grad():
+                        mu = policy.act_mean(obs)
+                        if hip:
+                            self._bc_hip(backend, mu, target, want_grad=False)
+                        else:
+                            self._bc_torch(mu, target, backward=False)
+                    cnt += 1
+                    continue
+                mu = policy.act_mean(obs)
+                if hip:
+                    torch.autograd.backward(mu, self._bc_hip(backend, mu, target))
+                else:
+                    self._bc_torch(mu, target)
+                cnt += 1
+                if cnt % self.gradient_length == 0:
+                    if hip:
+                        self._adam_hip(backend)
+                    else:
+                        self._adam_torch()
+                    sync.zero_grad()
+        return {"behavior": self._sums.tolist()[0] / cnt}

@@ -10,6 +10,10 @@ The runner adds no launch of its own.  It composes :class:`~.learner.RolloutStor
 :class:`~.learner.EpisodeStatistics`, :class:`~.learner.ActorCriticMLP` and :class:`~.learner.PPO` in the order the ``PPO`` docstring
 gives, writes rsl_rl's checkpoint files (``model_state_dict`` / ``optimizer_state_dict`` / ``iter`` / ``infos``, the optimizer state
 in ``torch.optim.Adam``'s own format) and keeps one log record per iteration.
+
+:class:`DistillationRunner` is rsl_rl's ``DistillationRunner`` in the same way: the same loop, files and arguments over
+:class:`~.learner.StudentTeacherMLP`, :class:`~.learner.DistillForward` and :class:`~.learner.Distillation`, with a PPO checkpoint
+as the source of its teacher.
 """
 from __future__ import annotations
 
@@ -21,7 +25,8 @@ from typing import Callable, Optional
 import torch
 
 from . import gs
-from .learner import ActorCriticMLP, EpisodeStatistics, PolicyForward, PPO, RolloutStorage, _policy_std
+from .learner import (ActorCriticMLP, DistillForward, Distillation, EpisodeStatistics, PolicyForward, PPO, RolloutStorage, StudentTeacherMLP,
+                      _policy_std)
 from .wrappers import RslRlWrapper
 
 CHECKPOINT_VERSION = 1   # of the "genesis_forge_amd" block of a checkpoint file
@@ -80,11 +85,7 @@ class OnPolicyRunner:
         groups = train_cfg.get("obs_groups")
         obs_name = "policy" if groups is None or "policy" not in groups or not groups["policy"] else groups["policy"][0]
         self.storage = store = RolloutStorage(base, self.num_steps_per_env, obs_name=obs_name, obs_groups=groups).attach()
-        width = lambda group: sum(store._widths[m] for m in store.obs_groups[group])
-        policy = ActorCriticMLP.from_train_cfg(train_cfg, width("policy"), base.action_space.shape[0], num_critic_obs=width("critic"))
-        policy = policy.to(self.device)
-        self.alg = PPO(policy, store, **train_cfg["algorithm"])
-        self._fwd = PolicyForward(policy) if forward == "hip" else None
+        self._build_algorithm(train_cfg, base, store)
         self._generator = torch.Generator(device=self.device)
         seed = train_cfg.get("seed")
         if seed is None:
@@ -94,18 +95,29 @@ class OnPolicyRunner:
             self._generator.manual_seed(int(seed))
         self._shared_critic = list(store.obs_groups["critic"]) == list(store.obs_groups["policy"])
 
+    _NAME = "OnPolicyRunner"
+
+    def _build_algorithm(self, train_cfg: dict, base, store: RolloutStorage) -> None:
+        """``self.alg`` (the policy inside it) and ``self._fwd``, the one-launch forward of ``forward="hip"``."""
+        width = lambda group: sum(store._widths[m] for m in store.obs_groups[group])
+        policy = ActorCriticMLP.from_train_cfg(train_cfg, width("policy"), base.action_space.shape[0], num_critic_obs=width("critic"))
+        policy = policy.to(self.device)
+        self.alg = PPO(policy, store, **train_cfg["algorithm"])
+        self._fwd = PolicyForward(policy) if self.forward == "hip" else None
+
     # -- observations ---------------------------------------------------------------------------------------------------------------
+    def _group(self, names, obs: torch.Tensor, extras: dict):
+        """The members of an observation group of this step: a tensor, or a tuple of segments."""
+        rows = extras.get("observations", {}) if extras is not None else {}
+        parts = tuple(obs if m == self.storage.obs_name else rows[m] for m in names)
+        return parts[0] if len(parts) == 1 else parts
+
     def _inputs(self, obs: torch.Tensor, extras: dict):
         """(actor input, critic input or None where the critic reads the actor's) of this step: a tensor, or the group's members as a
         tuple of segments."""
         store = self.storage
-        rows = extras.get("observations", {}) if extras is not None else {}
-
-        def group(names):
-            parts = tuple(obs if m == store.obs_name else rows[m] for m in names)
-            return parts[0] if len(parts) == 1 else parts
-
-        return group(store.obs_groups["policy"]), None if self._shared_critic else group(store.obs_groups["critic"])
+        return (self._group(store.obs_groups["policy"], obs, extras),
+                None if self._shared_critic else self._group(store.obs_groups["critic"], obs, extras))
 
     @staticmethod
     def _cat(x) -> torch.Tensor:
@@ -145,6 +157,9 @@ class OnPolicyRunner:
         else:
             self.alg.compute_returns(self._cat(last))
 
+    def _update(self) -> dict:
+        return self.alg.update(generator=self._generator)
+
     def learn(self, num_learning_iterations: int, init_at_random_ep_len: bool = False) -> None:
         """rsl_rl's ``OnPolicyRunner.learn``: iterations ``current_learning_iteration … + num_learning_iterations``, each
         ``num_steps_per_env`` collection steps, the returns and ``PPO.update``.  With ``log_dir`` set, ``model_{it}.pt`` is written when
@@ -168,7 +183,7 @@ class OnPolicyRunner:
             obs, extras = self._collect(obs, extras, stats)
             self._returns(obs, extras)
             t1 = time.perf_counter()
-            losses = self.alg.update(generator=self._generator)
+            losses = self._update()
             t2 = time.perf_counter()
             self.current_learning_iteration = it
             self._log(it, losses, stats, t1 - t0, t2 - t1)
@@ -190,11 +205,15 @@ class OnPolicyRunner:
             drawn = (torch.rand(length.shape, device=length.device) * top.to(torch.float32)).to(length.dtype)
             length.copy_(torch.minimum(drawn, top - 1).clamp_(min=0))   # (the f32 product may round up to max itself)
 
+    @staticmethod
+    def _loss_record(losses: dict) -> dict:
+        return {"value_function": losses["value_function"], "surrogate": losses["surrogate"], "entropy": losses["entropy"]}
+
     def _log(self, it: int, losses: dict, stats: EpisodeStatistics, collection_s: float, learn_s: float) -> None:
         """One record per iteration (the runner's own host reads are all here).  ``collection_time`` is the host's time to enqueue the
         rollout and ``learn_time`` ends at the update's one host read, which waits for the device: their sum is the iteration's."""
         steps = self.num_steps_per_env * self.storage.env.num_envs
-        record = {"iteration": it, "value_function": losses["value_function"], "surrogate": losses["surrogate"], "entropy": losses["entropy"],
+        record = {"iteration": it, **self._loss_record(losses),
                   "learning_rate": self.alg.learning_rate, "mean_action_std": float(self.alg.policy.action_std.mean()),
                   "mean_reward": stats.mean_reward(), "mean_episode_length": stats.mean_episode_length(),
                   "steps_per_second": steps / max(collection_s + learn_s, 1e-9), "collection_time": collection_s, "learn_time": learn_s}
@@ -230,17 +249,28 @@ class OnPolicyRunner:
         loaded = torch.load(path, map_location=self.device, weights_only=False)
         ppo = self.alg
         ppo.policy.load_state_dict(loaded["model_state_dict"])
-        lo, hi = ppo.params.data_ptr(), ppo.params.data_ptr() + ppo.params.numel() * ppo.params.element_size()
-        for name, p in ppo.policy.named_parameters():
-            if p.requires_grad and not lo <= p.data_ptr() < hi:
-                raise RuntimeError(f"OnPolicyRunner.load: parameter '{name}' no longer lives in PPO's flat buffer")
+        self._check_flat()
+        return self._load_rest(loaded, load_optimizer)
+
+    def _check_flat(self) -> None:
+        """``load_state_dict`` copied in place: the stepped parameters are still views of the algorithm's flat buffer."""
+        alg = self.alg
+        lo, hi = alg.params.data_ptr(), alg.params.data_ptr() + alg.params.numel() * alg.params.element_size()
+        stepped = {id(p) for p in alg.grad_sync.params}
+        for name, p in alg.policy.named_parameters():
+            if id(p) in stepped and not lo <= p.data_ptr() < hi:
+                raise RuntimeError(f"{self._NAME}.load: parameter '{name}' no longer lives in {type(alg).__name__}'s flat buffer")
+
+    def _load_rest(self, loaded: dict, load_optimizer: bool):
+        """Everything of a checkpoint but the model: the optimizer state, the iteration and this package's block.  Returns ``infos``."""
+        ppo = self.alg
         if load_optimizer:
             ppo.load_optimizer_state_dict(loaded["optimizer_state_dict"])
         self.current_learning_iteration = int(loaded["iter"])
         ours = loaded.get("genesis_forge_amd")
         if ours is not None:
             if ours.get("version") != CHECKPOINT_VERSION:
-                raise ValueError(f"OnPolicyRunner.load: 'genesis_forge_amd' block of version {ours.get('version')!r}; this build reads {CHECKPOINT_VERSION}")
+                raise ValueError(f"{self._NAME}.load: 'genesis_forge_amd' block of version {ours.get('version')!r}; this build reads {CHECKPOINT_VERSION}")
             self.storage._act_seed, self.storage._act_stream = ours["act_seed"], int(ours["act_stream"])
             self._generator.set_state(ours["generator_state"].cpu())
             if self.action_noise is not None and ours.get("action_noise_state") is not None:
@@ -270,3 +300,75 @@ class OnPolicyRunner:
 
     def eval_mode(self) -> None:
         self.alg.policy.eval()
+
+
+class DistillationRunner(OnPolicyRunner):
+    """``DistillationRunner(env, train_cfg, log_dir=None, device=None, *, forward="hip", action_noise=None)`` — rsl_rl's
+    ``DistillationRunner``: :class:`OnPolicyRunner`'s loop, files and arguments over a :class:`~.learner.StudentTeacherMLP` and
+    :class:`~.learner.Distillation`.
+
+    ``train_cfg["obs_groups"]`` must have ``"policy"`` (the student's input — the deployable observations) and ``"teacher"`` (the
+    privileged ones); ``"policy"`` is read by ``StudentTeacherMLP.from_train_cfg``, ``"algorithm"`` by ``Distillation(**…)``.
+
+    ``learn`` needs a teacher: ``load(path)`` of a PPO checkpoint (an ``OnPolicyRunner``'s ``model_*.pt``) takes its actor — and the
+    actor's normaliser — as the teacher and nothing else: not the optimizer, not the iteration counter, not the noise state.  A
+    distillation checkpoint is a full resume.  Per iteration: ``num_steps_per_env`` steps of ``store.act_distill`` (ONE
+    ``gf_mlp_distill_act`` launch for the student, the teacher, the sampling and the two rows; ``forward="torch"``: the two torch
+    forwards and ``gf_policy_act``) → ``env.step`` → ``policy.update_normalization`` → ``store.process_env_step(None, episodes=…)``,
+    then ``Distillation.update()``.  The log record carries ``"behavior"`` in place of the three PPO losses.
+    ``get_inference_policy()`` is the student's mean."""
+
+    _NAME = "DistillationRunner"
+
+    def _build_algorithm(self, train_cfg: dict, base, store: RolloutStorage) -> None:
+        if "teacher" not in store.obs_groups or not store.obs_groups["teacher"]:
+            raise ValueError("DistillationRunner: train_cfg['obs_groups'] needs a 'teacher' group (the teacher's privileged observations)")
+        width = lambda group: sum(store._widths[m] for m in store.obs_groups[group])
+        policy = StudentTeacherMLP.from_train_cfg(train_cfg, width("policy"), width("teacher"), base.action_space.shape[0]).to(self.device)
+        self.alg = Distillation(policy, store, **train_cfg["algorithm"])
+        self._fwd = DistillForward(policy) if self.forward == "hip" else None
+
+    def _collect(self, obs: torch.Tensor, extras: dict, stats: EpisodeStatistics):
+        store, policy, env = self.storage, self.alg.policy, self.env
+        n, A = store.env.num_envs, self.alg.num_actions
+        groups = store.obs_groups
+        for _ in range(self.num_steps_per_env):
+            x, tx = self._group(groups["policy"], obs, extras), self._group(groups["teacher"], obs, extras)
+            if self._fwd is not None:
+                actions = store.act_distill(self._fwd, x, tx, noise=self._noise(n, A))
+            else:
+                std, is_log = _policy_std(policy)
+                with torch.no_grad():
+                    mean, teacher = policy.act_mean(self._cat(x)), policy.evaluate(self._cat(tx))
+                actions = store._act_distill_rows(mean, std.detach(), teacher, noise=self._noise(n, A), std_is_log=is_log)
+            obs, _rew, _terminated, _truncated, extras = env.step(actions)
+            policy.update_normalization(self._group(groups["policy"], obs, extras))
+            store.process_env_step(None, episodes=stats)
+        return obs, extras
+
+    def _returns(self, obs: torch.Tensor, extras: dict) -> None:
+        pass   # (no critic, no returns)
+
+    def _update(self) -> dict:
+        return self.alg.update()
+
+    @staticmethod
+    def _loss_record(losses: dict) -> dict:
+        return {"behavior": losses["behavior"]}
+
+    def learn(self, num_learning_iterations: int, init_at_random_ep_len: bool = False) -> None:
+        if not self.alg.policy.loaded_teacher:
+            raise ValueError("DistillationRunner.learn: no teacher is loaded — load() a PPO checkpoint (its actor becomes the teacher) "
+                             "or a distillation checkpoint first")
+        super().learn(num_learning_iterations, init_at_random_ep_len)
+
+    def load(self, path: str, load_optimizer: bool = True):
+        """A PPO checkpoint: the teacher (and its normaliser) only — ``StudentTeacherMLP.load_state_dict`` returned ``False``; the
+        optimizer state, the iteration counter and this package's block are not taken.  A distillation checkpoint: everything, as
+        ``OnPolicyRunner.load``.  Returns ``infos``."""
+        loaded = torch.load(path, map_location=self.device, weights_only=False)
+        resumed = self.alg.policy.load_state_dict(loaded["model_state_dict"])
+        self._check_flat()
+        if not resumed:
+            return loaded.get("infos")
+        return self._load_rest(loaded, load_optimizer)

@@ -1121,6 +1121,79 @@ typedef struct GfMlpActArgs {
 } GfMlpActArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * The collection step of teacher–student distillation (rsl_rl Distillation.act: StudentTeacher.act on the deployable observations,
+ * StudentTeacher.evaluate on the privileged ones).  The two MLPs have no data dependency, and at a few thousand envs one net leaves
+ * half the device idle (N / GF_MLP_TILE_ROWS workgroups per net): gf_mlp_distill_act runs both in ONE launch, grid y = net, with
+ * gf_mlp_act's tile, LDS and weight-streaming scheme and its layer code unchanged:
+ *     observations            -> student MLP -> mean -> sample (gf_policy_act's row code) -> actions, actions_out
+ *     privileged observations -> teacher MLP -> teacher_actions, teacher_actions_out
+ * Each net is a GfMlpNet of its own — segments, row_stride, layers, optional in_mean / in_std / in_eps — so depth, input width and
+ * normaliser may differ; both outputs are A <= GF_MLP_MAX_ACTIONS wide.  Nothing of the teacher is sampled; no value, log-probability,
+ * mu or sigma row is written.
+ *
+ * Arithmetic: a row's results are the k-ascending fma chains of gf_mlp_act (see above), so
+ *     actions, mean, actions_out  ==  those of a gf_mlp_act launch with `student` as its actor and the same std / std_is_log, noise,
+ *                                     seed, stream and env_offset, bit for bit;
+ *     teacher_actions (and teacher_actions_out)  ==  the `mean` of a gf_mlp_act launch with `teacher` as its actor, bit for bit.
+ * `std` is [A] (std_is_log = 1: log_std, as GfPolicyActArgs.std_is_log).
+ * Refusals, before anything is launched: GF_E_NULL — args, a weight / bias / segment pointer, in_mean without in_std, std, actions,
+ * teacher_actions; GF_E_RANGE — num_envs < 0, std_is_log outside {0, 1}, what gf_mlp_act ranges per net (layer and segment counts,
+ * widths, row_stride, hidden and input widths, an output > GF_MLP_MAX_ACTIONS), student and teacher output widths that differ;
+ * GF_E_UNSUPPORTED — either net absent (num_layers == 0).  num_envs == 0 is a no-op.
+ * No allocation, no copy, no synchronisation inside.  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct GfMlpDistillArgs {
+    int64_t num_envs;           /* N >= 0; 0: nothing is launched */
+    GfMlpNet student;           /* output width A <= GF_MLP_MAX_ACTIONS */
+    GfMlpNet teacher;           /* output width A */
+    const float* std;           /* [A] (required): the student's std, or log_std with std_is_log */
+    const float* noise;         /* [N, A] standard normals (parity mode), or NULL: Philox + Box–Muller */
+    uint64_t seed;              /* as GfPolicyActArgs */
+    uint64_t stream;
+    uint32_t env_offset;
+    int32_t std_is_log;         /* 0: `std` is the std, 1: it is log_std (sigma = expf) */
+    float* mean;                /* [N, A] out: the student's output, or NULL */
+    float* actions;             /* [N, A] out: the sample (required) */
+    float* actions_out;         /* [N, A] the storage row of the sample, or NULL */
+    float* teacher_actions;     /* [N, A] out: the teacher's output (required) */
+    float* teacher_actions_out; /* [N, A] a second destination of it (the storage row), or NULL */
+} GfMlpDistillArgs;
+
+/* ------------------------------------------------------------------------------------------
+ * The behaviour-cloning loss of one time step of a distillation update and its gradient (rsl_rl Distillation.update:
+ * loss_fn(student mean, stored teacher actions) with loss_type "mse" or "huber", and its backward down to the student's output):
+ *     d[n, j] = mu[n, j] - target[n, j]                                      (one rounding)
+ *     GF_BC_LOSS_MSE:    e = d²                         grad[n, j] = inv · (2 · d)
+ *     GF_BC_LOSS_HUBER:  e = |d| < 1 ? 0.5·d² : |d| - 0.5   grad[n, j] = inv · clamp(d, -1, 1)      (torch's huber_loss, delta 1)
+ *     loss = mean over the N·A elements of e   -> out[0] (float32), and sums[0] += (double)out[0] when sums != NULL
+ * with inv = 1 / (float)(N·A).  `grad` is WRITTEN, not added to; grad == NULL is the loss-only mode: nothing but out / sums is
+ * written.  e is evaluated and summed in double from the f32 d.  The mse form is gf_mirror_loss's operation order with coeff = 1, the
+ * identity permutation, sign +1 and a zeroed grad: the two agree bit for bit.
+ * The shape of gf_mirror_loss: one lane per row, one double partial per workgroup in the caller's workspace, a second one-workgroup
+ * launch sums them in a fixed order.  No atomics: bitwise reproducible.
+ * Refusals, before anything is launched: GF_E_NULL — args, mu, target, out, workspace; GF_E_RANGE — num_rows < 0, num_actions < 1,
+ * loss_type outside {0, 1}, a workspace smaller than GF_BC_LOSS_WORKSPACE_BYTES(N) or not 8-byte aligned.  num_rows == 0 is a no-op.
+ * No allocation, no copy, no synchronisation inside.  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_BC_LOSS_MSE 0
+#define GF_BC_LOSS_HUBER 1
+#define GF_BC_LOSS_BLOCK_ROWS 256      /* rows per workgroup of gf_bc_loss: one double partial per workgroup */
+#define GF_BC_LOSS_WORKSPACE_BYTES(n) ((int64_t)(((n) + GF_BC_LOSS_BLOCK_ROWS - 1) / GF_BC_LOSS_BLOCK_ROWS) * 8)
+
+typedef struct GfBcLossArgs {
+    int64_t num_rows;           /* N >= 0; 0: nothing is launched */
+    int32_t num_actions;        /* A >= 1 */
+    int32_t loss_type;          /* GF_BC_LOSS_MSE / GF_BC_LOSS_HUBER */
+    const float* mu;            /* [N, A] the student's mean of this update */
+    const float* target;        /* [N, A] the stored teacher actions (a constant) */
+    float* grad;                /* [N, A] = d loss / d mu, or NULL: loss only */
+    float* out;                 /* [1] the loss (required) */
+    double* sums;               /* [1] += the loss, or NULL */
+    void* workspace;            /* GF_BC_LOSS_WORKSPACE_BYTES(N) bytes, 8-byte aligned */
+    int64_t workspace_bytes;
+} GfBcLossArgs;
+
+/* ------------------------------------------------------------------------------------------
  * Running observation statistics (rsl_rl EmpiricalNormalization.update; the "empirical_normalization" switch of the training
  * scripts, rsl_rl 3.x's actor_obs_normalization / critic_obs_normalization).  rsl_rl updates a normaliser with torch.mean, torch.var
  * and a handful of elementwise launches — about ten per normaliser and collection step.  gf_obs_norm_update updates up to
@@ -1216,7 +1289,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs, 31 GfMirrorRowsArgs, 32 GfMirrorLossArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs, 31 GfMirrorRowsArgs, 32 GfMirrorLossArgs, 33 GfMlpDistillArgs, 34 GfBcLossArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -1246,6 +1319,8 @@ int gf_ppo_loss(const GfPpoLossArgs* a, void* stream);           /* minibatch lo
 int gf_mirror_rows(const GfMirrorRowsArgs* a, void* stream);     /* originals + mirrored copies of up to four row fields, and the replicated per-row scalars, in one launch (rsl_rl PPO.update: data_augmentation_func, torch.cat, repeat) */
 int gf_mirror_loss(const GfMirrorLossArgs* a, void* stream);     /* symmetry loss and its gradient w.r.t. the mirrored rows' mu (rsl_rl PPO.update: MSELoss(mean_actions[mb:], mirrored mean_actions[:mb].detach()) and its backward) */
 int gf_mlp_act(const GfMlpActArgs* a, void* stream);             /* actor + critic MLP forward on the f32 matrix cores, then gf_policy_act's sampling and rows, in one launch (rsl_rl ActorCritic.act / evaluate inside PPO.act) */
+int gf_mlp_distill_act(const GfMlpDistillArgs* a, void* stream); /* student + teacher MLP forward in one launch, the student sampled by gf_policy_act's row code (rsl_rl Distillation.act: StudentTeacher.act / evaluate) */
+int gf_bc_loss(const GfBcLossArgs* a, void* stream);             /* behaviour-cloning loss of one time step (mse / huber) and its gradient w.r.t. the student's mean (rsl_rl Distillation.update: loss_fn(actions, privileged_actions) and its backward) */
 int gf_obs_norm_update(const GfObsNormArgs* a, void* stream);    /* running mean / var / std / count of up to two observation normalisers in two launches (rsl_rl EmpiricalNormalization.update) */
 int gf_adam_step(const GfAdamArgs* a, void* stream);             /* adaptive lr + clip_grad_norm_ + Adam.step over the flat bucket (rsl_rl PPO.update: the lr schedule, nn.utils.clip_grad_norm_, optimizer.step()) */
 

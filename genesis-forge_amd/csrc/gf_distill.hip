@@ -6,18 +6,14 @@
 // butterfly, then the four waves in order) is one record of the workspace, a one-workgroup launch sums the records in a fixed order.
 // The gradient needs no sum: it is written by the lane that computed d.  R 8A, W 4A bytes per row.
 #include "gf_launch.h"
+#include "gf_reduce.h"
 
 namespace gf {
 
 constexpr int kBcBlock = GF_BC_LOSS_BLOCK_ROWS;
 constexpr int kBcFinBlock = 256;
 
-// wave butterfly of a double, as gf_mirror.hip's: the same order whatever the data
-__device__ __forceinline__ double bc_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, GF_WAVE);
-    return v;
-}
+static_assert(kBcBlock == kSumBlock, "block_wave_sums folds four waves");
 
 template <int TYPE>
 __global__ __launch_bounds__(kBcBlock) void bc_loss_rows_kernel(const GfBcLossArgs a) {
@@ -43,25 +39,12 @@ __global__ __launch_bounds__(kBcBlock) void bc_loss_rows_kernel(const GfBcLossAr
             }
         }
     }
-    acc = bc_wave_sum(acc);
-    if ((threadIdx.x & (GF_WAVE - 1)) == 0) s_w[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) G(reinterpret_cast<double*>(a.workspace))[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+    block_wave_sums(acc, s_w);
+    if (threadIdx.x == 0) G(reinterpret_cast<double*>(a.workspace))[blockIdx.x] = fold_wave_sums(s_w);
 }
 
 __global__ __launch_bounds__(kBcFinBlock) void bc_loss_finalize_kernel(const GfBcLossArgs a, const int64_t nb) {
-    __shared__ double s_w[kBcFinBlock / GF_WAVE];
-    const GF_GLOBAL double* ws = G(reinterpret_cast<const double*>(a.workspace));
-    double acc = 0.0;
-    for (int64_t b = threadIdx.x; b < nb; b += kBcFinBlock) acc += ws[b];
-    acc = bc_wave_sum(acc);
-    if ((threadIdx.x & (GF_WAVE - 1)) == 0) s_w[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const double total = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-    const float loss = (float)(total / ((double)a.num_rows * (double)a.num_actions));
-    G(a.out)[0] = loss;
-    if (a.sums) G(a.sums)[0] = G(a.sums)[0] + (double)loss;   // rsl_rl: mean_behavior_loss += behavior_loss.item()
+    finalize_mean_loss<kBcFinBlock>(a.workspace, nb, a.num_rows, a.num_actions, a.out, a.sums);   // sums: mean_behavior_loss
 }
 
 }  // namespace gf

@@ -13,6 +13,7 @@
 // order) is one record of the workspace, a one-workgroup launch sums the records in a fixed order.  The gradient needs no sum: it is
 // added into `grad` by the lane that computed d.  R 8A (+ 4A of grad), W 4A bytes per row.
 #include "gf_launch.h"
+#include "gf_reduce.h"
 
 namespace gf {
 
@@ -145,12 +146,7 @@ __global__ __launch_bounds__(kMirBlock) void mirror_rows_kernel(const GfMirrorRo
     }
 }
 
-// wave butterfly / workgroup sum of a double, as gf_ppo.hip's: the same order whatever the data
-__device__ __forceinline__ double mir_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, GF_WAVE);
-    return v;
-}
+static_assert(kMirLossBlock == kSumBlock, "block_wave_sums folds four waves");
 
 __global__ __launch_bounds__(kMirLossBlock) void mirror_loss_rows_kernel(const GfMirrorLossArgs a) {
     __shared__ double s_w[kMirLossBlock / GF_WAVE];
@@ -172,25 +168,12 @@ __global__ __launch_bounds__(kMirLossBlock) void mirror_loss_rows_kernel(const G
             if (g) g[j] = g[j] + scale * (2.0f * d);   // pow(2)'s backward: 2·d
         }
     }
-    acc = mir_wave_sum(acc);
-    if ((threadIdx.x & (GF_WAVE - 1)) == 0) s_w[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) G(reinterpret_cast<double*>(a.workspace))[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+    block_wave_sums(acc, s_w);
+    if (threadIdx.x == 0) G(reinterpret_cast<double*>(a.workspace))[blockIdx.x] = fold_wave_sums(s_w);
 }
 
 __global__ __launch_bounds__(kMirFinBlock) void mirror_loss_finalize_kernel(const GfMirrorLossArgs a, const int64_t nb) {
-    __shared__ double s_w[kMirFinBlock / GF_WAVE];
-    const GF_GLOBAL double* ws = G(reinterpret_cast<const double*>(a.workspace));
-    double acc = 0.0;
-    for (int64_t b = threadIdx.x; b < nb; b += kMirFinBlock) acc += ws[b];
-    acc = mir_wave_sum(acc);
-    if ((threadIdx.x & (GF_WAVE - 1)) == 0) s_w[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const double total = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-    const float loss = (float)(total / ((double)a.num_rows * (double)a.num_actions));
-    G(a.out)[0] = loss;
-    if (a.sums) G(a.sums)[0] = G(a.sums)[0] + (double)loss;   // rsl_rl: mean_symmetry_loss += symmetry_loss.item()
+    finalize_mean_loss<kMirFinBlock>(a.workspace, nb, a.num_rows, a.num_actions, a.out, a.sums);   // sums: mean_symmetry_loss
 }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

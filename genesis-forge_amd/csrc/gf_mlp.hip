@@ -25,6 +25,8 @@
 // LDS: 65 664 B, registers <= 256: two workgroups per CU, so one's barriers, ELU and load latency hide behind the other's MFMAs.
 // gf_mlp_distill_act is the same tile walk with grid y = student / teacher (a distillation collection step): the student workgroup is
 // the actor path above, the teacher workgroup stores its outputs to two destinations and samples nothing.
+#include <initializer_list>
+
 #include "gf_launch.h"
 #include "gf_policy_row.h"
 
@@ -239,6 +241,18 @@ __device__ __forceinline__ int mlp_forward(MlpSmem& sm, const GfMlpNet& net, con
     return K;
 }
 
+// gf_policy_act's row n (gf_policy_row.h) with the mean read from the row's outputs in x: the sampling tail of both kernels, each of
+// which fills `p` its own way
+template <bool LOG>
+__device__ __forceinline__ void mlp_sample_row(const GfPolicyActArgs& p, const float* out, const int64_t n, const int vec_rows) {
+    const auto load_mean = [&](int c0, float (&m)[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m[k] = out[c0 + k];   // (columns past A: zeros, or x's finite leftovers — never folded or stored)
+    };
+    if (vec_rows) policy_act_row<true, LOG>(p, n, load_mean);
+    else policy_act_row<false, LOG>(p, n, load_mean);
+}
+
 template <bool NORM, bool LOG>
 __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArgs a, const int first_net, const int vec_rows) {
     __shared__ MlpSmem sm;
@@ -284,12 +298,7 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArg
     p.sigma_out = a.sigma_out;
     p.values_out = nullptr;   // (the critic workgroup's)
     p.log_prob_out = a.log_prob_out;
-    const auto load_mean = [&](int c0, float (&m)[4]) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) m[k] = out[c0 + k];   // (columns past A: zeros, or x's finite leftovers — never folded or stored)
-    };
-    if (vec_rows) policy_act_row<true, LOG>(p, n, load_mean);
-    else policy_act_row<false, LOG>(p, n, load_mean);
+    mlp_sample_row<LOG>(p, out, n, vec_rows);
 }
 
 // gf_mlp_distill_act: grid y = 0 the student (gf_mlp_act's actor path: mean, sample, the storage row), y = 1 the teacher (its output
@@ -342,17 +351,8 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_distill_kernel(const GfMlpDi
     p.sigma_out = nullptr;
     p.values_out = nullptr;
     p.log_prob_out = nullptr;
-    const auto load_mean = [&](int c0, float (&m)[4]) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) m[k] = out[c0 + k];   // (columns past A: zeros, or x's finite leftovers — never folded or stored)
-    };
-    if (a.std_is_log) {
-        if (vec_rows) policy_act_row<true, true>(p, n, load_mean);
-        else policy_act_row<false, true>(p, n, load_mean);
-    } else {
-        if (vec_rows) policy_act_row<true, false>(p, n, load_mean);
-        else policy_act_row<false, false>(p, n, load_mean);
-    }
+    if (a.std_is_log) mlp_sample_row<true>(p, out, n, vec_rows);
+    else mlp_sample_row<false>(p, out, n, vec_rows);
 }
 
 // GF_OK and the net's widths, or the refusal
@@ -384,6 +384,19 @@ static int mlp_check_net(const GfMlpNet& net, bool critic, int* out_width) {
     return GF_OK;
 }
 
+// the launch's row tiles, or -1 where they pass a grid's x range
+static int64_t mlp_tiles(int64_t num_envs) {
+    const int64_t tiles = (num_envs + kMlpRows - 1) / kMlpRows;
+    return tiles > 0x7fffffff ? -1 : tiles;
+}
+
+// whether the sampling lanes may use 16-byte accesses: every given [N, A] row pointer (and std) 16-byte aligned, A a multiple of 4
+static int mlp_vec_rows(std::initializer_list<const void*> rows, int A) {
+    uintptr_t bits = 0;
+    for (const void* p : rows) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & 15u) == 0 && (A & 3) == 0;
+}
+
 }  // namespace gf
 
 extern "C" __attribute__((visibility("default"))) int gf_mlp_act(const GfMlpActArgs* a, void* stream) {
@@ -409,12 +422,9 @@ extern "C" __attribute__((visibility("default"))) int gf_mlp_act(const GfMlpActA
         return GF_E_NULL;
     }
     if (a->num_envs == 0) return GF_OK;
-    const int64_t tiles = (a->num_envs + gf::kMlpRows - 1) / gf::kMlpRows;
-    if (tiles > 0x7fffffff) return GF_E_RANGE;
-    uintptr_t bits = 0;
-    const void* rows[] = {a->noise, a->actions, a->actions_out, a->mu_out, a->sigma_out, a->std};
-    for (const void* p : rows) bits |= reinterpret_cast<uintptr_t>(p);
-    const int vec_rows = (bits & 15u) == 0 && (A & 3) == 0;
+    const int64_t tiles = gf::mlp_tiles(a->num_envs);
+    if (tiles < 0) return GF_E_RANGE;
+    const int vec_rows = gf::mlp_vec_rows({a->noise, a->actions, a->actions_out, a->mu_out, a->sigma_out, a->std}, A);
     const bool norm = (actor && a->actor.in_mean) || (critic && a->critic.in_mean);
     const dim3 grid((unsigned)tiles, actor && critic ? 2u : 1u);
     const dim3 block(gf::kMlpBlock);
@@ -442,12 +452,9 @@ extern "C" __attribute__((visibility("default"))) int gf_mlp_distill_act(const G
     if (A != At) return GF_E_RANGE;
     if (!a->std || !a->actions || !a->teacher_actions) return GF_E_NULL;
     if (a->num_envs == 0) return GF_OK;
-    const int64_t tiles = (a->num_envs + gf::kMlpRows - 1) / gf::kMlpRows;
-    if (tiles > 0x7fffffff) return GF_E_RANGE;
-    uintptr_t bits = 0;
-    const void* rows[] = {a->noise, a->actions, a->actions_out, a->std};
-    for (const void* p : rows) bits |= reinterpret_cast<uintptr_t>(p);
-    const int vec_rows = (bits & 15u) == 0 && (A & 3) == 0;
+    const int64_t tiles = gf::mlp_tiles(a->num_envs);
+    if (tiles < 0) return GF_E_RANGE;
+    const int vec_rows = gf::mlp_vec_rows({a->noise, a->actions, a->actions_out, a->std}, A);
     const dim3 grid((unsigned)tiles, 2u);
     const dim3 block(gf::kMlpBlock);
     hipStream_t s = (hipStream_t)stream;

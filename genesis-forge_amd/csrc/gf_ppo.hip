@@ -17,6 +17,7 @@
 // state[parity], and updates its 1 024 elements.  Algorithmic traffic per element: R 4 (norm) + 16, W 16 bytes.
 #include "gf_launch.h"
 #include "gf_policy_row.h"
+#include "gf_reduce.h"
 
 namespace gf {
 
@@ -24,22 +25,6 @@ constexpr int kPpoBlock = GF_PPO_BLOCK_ROWS;
 constexpr int kPpoFinBlock = 1024;
 constexpr float kPpoLogSqrt2Pi = 0.918938533204672742f;   // (float)math.log(math.sqrt(2 * math.pi)), Normal.log_prob's constant
 constexpr float kPpoEntropyC = 1.41893853320467274f;      // (float)(0.5 + 0.5 * math.log(2 * math.pi)), Normal.entropy's constant
-
-// wave butterfly: every lane ends with the same sum, in the same order whatever the data
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, GF_WAVE);
-    return v;
-}
-
-// workgroup sum of a double (blockDim 256): the four wave sums added in wave order; every lane gets the result
-__device__ __forceinline__ double block_sum_d(double v, double* s_w) {
-    v = wave_sum_d(v);
-    __syncthreads();   // (s_w may still be read by an earlier use)
-    if ((threadIdx.x & (GF_WAVE - 1)) == 0) s_w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
 
 template <bool V>
 __device__ __forceinline__ void ppo_load4(const GF_GLOBAL float* p, int c0, int A, float (&v)[4]) {
@@ -132,7 +117,7 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_loss_rows_kernel(const GfPpoLos
     const double sums3[3] = {in ? (double)surr : 0.0, in ? (double)vl : 0.0, in && in_kl ? (double)kl : 0.0};
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-        const double t = block_sum_d(sums3[q], s_w);
+        const double t = block_sum_all(sums3[q], s_w);
         if (threadIdx.x == 0) rec[q * nb] = t;
     }
     if (!a.grad_mu) return;   // (block-uniform)
@@ -164,7 +149,7 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_loss_rows_kernel(const GfPpoLos
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (c0 + k >= A) break;   // (uniform: A is a launch constant)
-            const double t = block_sum_d(in ? gs[k] : 0.0, s_w);
+            const double t = block_sum_all(in ? gs[k] : 0.0, s_w);
             if (threadIdx.x == 0) rec[(3 + c0 + k) * nb] = t;
         }
     }
@@ -184,7 +169,7 @@ __global__ __launch_bounds__(kPpoFinBlock) void ppo_loss_finalize_kernel(const G
         double acc = 0.0;
 #pragma unroll 4
         for (int64_t b = lane; b < nb; b += GF_WAVE) acc += ws[q * nb + b];
-        const double t = wave_sum_d(acc);
+        const double t = wave_xor_sum(acc);
         if (lane == 0) {
             if (q < 3) {
                 s_tot[q] = t;
@@ -222,6 +207,7 @@ __global__ __launch_bounds__(kPpoFinBlock) void ppo_loss_finalize_kernel(const G
 // ---- gf_adam_step ---------------------------------------------------------------------------------------------------------------
 constexpr int kAdamBlock = 256;
 static_assert(kAdamBlock * 4 == GF_ADAM_BLOCK_ELEMS, "elements per workgroup and pass");
+static_assert(kPpoBlock == kSumBlock && kAdamBlock == kSumBlock, "block_sum_all folds four waves");
 
 template <bool V>
 __device__ __forceinline__ void adam_load4(const GF_GLOBAL float* p, int64_t e, int64_t n, float (&v)[4]) {
@@ -262,7 +248,7 @@ __global__ __launch_bounds__(kAdamBlock) void adam_norm_kernel(const GfAdamArgs 
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc += (double)g[k] * (double)g[k];
     }
-    const double t = block_sum_d(acc, s_w);
+    const double t = block_sum_all(acc, s_w);
     if (threadIdx.x == 0) G(reinterpret_cast<double*>(a.workspace))[blockIdx.x] = t;
 }
 
@@ -272,7 +258,7 @@ __global__ __launch_bounds__(kAdamBlock) void adam_update_kernel(const GfAdamArg
     // the norm: every workgroup sums the same partials in the same order
     double acc = 0.0;
     for (int b = threadIdx.x; b < num_partials; b += kAdamBlock) acc += G(reinterpret_cast<const double*>(a.workspace))[b];
-    const double sq = block_sum_d(acc, s_w);
+    const double sq = block_sum_all(acc, s_w);
     const float total_norm = (float)sqrt(sq);
     float coef = a.max_grad_norm / (total_norm + 1.0e-6f);   // clip_grad_norm_: max_norm / (total_norm + 1e-6), clamp(max=1)
     coef = coef > 1.0f ? 1.0f : coef;

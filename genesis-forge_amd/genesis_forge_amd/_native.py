@@ -764,72 +764,6 @@ class HipBackend(Backend):
         if rc != 0:
             self._raise(fn, rc)
 
-    def minibatch_gather(self, args) -> None:
-        """gf_minibatch_gather on the current stream (learner.RolloutStorage.mini_batch_generator)."""
-        rc = self.lib.gf_minibatch_gather(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("minibatch_gather", rc)
-
-    def rollout_frame_write(self, args) -> None:
-        """gf_rollout_frame_write on the current stream (learner.RolloutStorage(history="frames"): behind the step's rollout_write)."""
-        rc = self.lib.gf_rollout_frame_write(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("rollout_frame_write", rc)
-
-    def policy_act(self, args) -> None:
-        """gf_policy_act on the current stream (learner.RolloutStorage.act)."""
-        rc = self.lib.gf_policy_act(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("policy_act", rc)
-
-    def episode_step(self, args) -> None:
-        """gf_episode_step on the current stream (learner.RolloutStorage.process_env_step, learner.EpisodeStatistics.update)."""
-        rc = self.lib.gf_episode_step(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("episode_step", rc)
-
-    def ppo_loss(self, args) -> None:
-        """gf_ppo_loss on the current stream (learner.PPO.update)."""
-        rc = self.lib.gf_ppo_loss(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("ppo_loss", rc)
-
-    def adam_step(self, args) -> None:
-        """gf_adam_step on the current stream (learner.PPO.update)."""
-        rc = self.lib.gf_adam_step(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("adam_step", rc)
-
-    def mirror_rows(self, args) -> None:
-        """gf_mirror_rows on the current stream (learner.PPO.update with a symmetry_cfg)."""
-        rc = self.lib.gf_mirror_rows(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("mirror_rows", rc)
-
-    def mirror_loss(self, args) -> None:
-        """gf_mirror_loss on the current stream (learner.PPO.update with a symmetry_cfg)."""
-        rc = self.lib.gf_mirror_loss(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("mirror_loss", rc)
-
-    def mlp_act(self, args) -> None:
-        """gf_mlp_act on the current stream (learner.PolicyForward, learner.RolloutStorage.act_policy)."""
-        rc = self.lib.gf_mlp_act(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("mlp_act", rc)
-
-    def mlp_distill_act(self, args) -> None:
-        """gf_mlp_distill_act on the current stream (learner.DistillForward.act, learner.RolloutStorage.act_distill)."""
-        rc = self.lib.gf_mlp_distill_act(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("mlp_distill_act", rc)
-
-    def bc_loss(self, args) -> None:
-        """gf_bc_loss on the current stream (learner.Distillation.update)."""
-        rc = self.lib.gf_bc_loss(C.byref(args), self._stream())
-        if rc != 0:
-            self._raise("bc_loss", rc)
-
     def run_ops(self, ops, n: int) -> None:
         failed = C.c_int(-1)
         rc = self.lib.gf_run_ops(ops, n, self._stream(), C.byref(failed))
@@ -932,6 +866,40 @@ class HipBackend(Backend):
 
     def build_info(self) -> str:
         return self.lib.gf_build_info().decode()
+
+
+# The learner's entry points, none a phase of the step: HipBackend.<name>(args) is gf_<name> on the current stream.  Only the HIP
+# backend has them — `getattr(backend, name, None) is None` is how the learner detects the test-only oracle backend.
+_LEARNER_ENTRIES = {
+    "minibatch_gather": "learner.RolloutStorage.mini_batch_generator",
+    "rollout_frame_write": 'learner.RolloutStorage(history="frames"): behind the step\'s rollout_write',
+    "policy_act": "learner.RolloutStorage.act",
+    "episode_step": "learner.RolloutStorage.process_env_step, learner.EpisodeStatistics.update",
+    "ppo_loss": "learner.PPO.update",
+    "adam_step": "learner.PPO.update",
+    "mirror_rows": "learner.PPO.update with a symmetry_cfg",
+    "mirror_loss": "learner.PPO.update with a symmetry_cfg",
+    "mlp_act": "learner.PolicyForward, learner.RolloutStorage.act_policy",
+    "mlp_distill_act": "learner.DistillForward.act, learner.RolloutStorage.act_distill",
+    "bc_loss": "learner.Distillation.update",
+}
+
+
+def _learner_entry(name: str, used_by: str):
+    symbol = "gf_" + name
+
+    def entry(self, args) -> None:
+        rc = getattr(self.lib, symbol)(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise(name, rc)
+
+    entry.__name__, entry.__qualname__ = name, f"HipBackend.{name}"
+    entry.__doc__ = f"{symbol} on the current stream ({used_by})."
+    return entry
+
+
+for _name, _used_by in _LEARNER_ENTRIES.items():
+    setattr(HipBackend, _name, _learner_entry(_name, _used_by))
 
 
 _backend: Optional[Backend] = None

@@ -433,8 +433,7 @@ class RolloutStorage:
         t, a = self.step - 1, self._pol_args
         a.num_envs, a.num_actions = self.env.num_envs, self.num_actions
         a.actions, a.values, a.log_prob, a.mu, a.sigma = (x.data_ptr() for x in (actions, values, log_prob, mu, sigma))
-        a.actions_out, a.mu_out, a.sigma_out = (x.data_ptr() + t * x.stride(0) * 4 for x in (self.actions, self.mu, self.sigma))
-        a.values_out, a.log_prob_out = (x.data_ptr() + t * x.stride(0) * 4 for x in (self.values, self.actions_log_prob))
+        self._policy_row_ptrs(a, t)
         if time_outs is not None:
             if time_outs.dtype != torch.bool and time_outs.dtype != torch.uint8:
                 time_outs = time_outs != 0
@@ -476,11 +475,34 @@ class RolloutStorage:
         _check_f32(values, "values", {(n,), (n, 1)}, dev)
         if noise is not None:
             _check_f32(noise, "noise", {(n, A)}, dev)
-        t = 0 if self.full else self.step   # (env.step() does the wrap's row copies; only the row index is needed here)
         self._ensure_policy_rows(A)
-        actions = torch.empty((n, A), device=dev, dtype=torch.float32)
+        return self._policy_act(mean, std, values, noise, std_is_log)
+
+    def _open_act(self) -> tuple:
+        """What every act call starts from: ``(t, stream, seed, env_offset)`` — the row of the transition the next ``env.step()``
+        writes (``step``, 0 once the storage is ``full``: env.step() does the wrap's row copies, only the index is needed here), the
+        noise stream (advanced by this call), the Philox seed and the global id of env 0."""
         stream = self._act_stream
         self._act_stream += 1
+        seed = self.env._rng_seed if self._act_seed is None else self._act_seed
+        return self._act_row(), stream, seed, int(getattr(self.env, "env_offset", 0))
+
+    def _act_row(self) -> int:
+        return 0 if self.full else self.step
+
+    def _policy_row_ptrs(self, a, t: int, actions_only: bool = False) -> None:
+        """Point the five ``*_out`` fields of a descriptor at row ``t`` of the policy's rows (``actions_only``: the other four are None)."""
+        row = lambda x: x.data_ptr() + t * x.stride(0) * 4
+        a.actions_out = row(self.actions)
+        a.mu_out, a.sigma_out, a.values_out, a.log_prob_out = (
+            (None,) * 4 if actions_only else (row(x) for x in (self.mu, self.sigma, self.values, self.actions_log_prob)))
+
+    def _policy_act(self, mean, std, values, noise, std_is_log: bool) -> torch.Tensor:
+        """``act`` behind its checks: one ``gf_policy_act`` launch.  ``values=None`` (a distillation step): only the action row is
+        written."""
+        n, A = mean.shape
+        actions = torch.empty((n, A), device=self.device, dtype=torch.float32)
+        t, stream, seed, env_offset = self._open_act()
         fn = getattr(self.env.backend, "policy_act", None)
         if fn is None:   # (the test-only oracle backend) the same expression in torch, from the given draws
             if noise is None:
@@ -490,13 +512,11 @@ class RolloutStorage:
             a = self._act_args
             a.num_envs, a.num_actions, a.std_per_env = n, A, 1 if std.dim() == 2 else 0
             a.std_is_log = 1 if std_is_log else 0
-            a.mean, a.std, a.values = mean.data_ptr(), std.data_ptr(), values.data_ptr()
+            a.mean, a.std, a.values = mean.data_ptr(), std.data_ptr(), None if values is None else values.data_ptr()
             a.noise = None if noise is None else noise.data_ptr()
-            a.seed = self.env._rng_seed if self._act_seed is None else self._act_seed
-            a.stream, a.env_offset = stream, int(getattr(self.env, "env_offset", 0))
+            a.seed, a.stream, a.env_offset = seed, stream, env_offset
             a.actions = actions.data_ptr()
-            a.actions_out, a.mu_out, a.sigma_out = (x.data_ptr() + t * x.stride(0) * 4 for x in (self.actions, self.mu, self.sigma))
-            a.values_out, a.log_prob_out = (x.data_ptr() + t * x.stride(0) * 4 for x in (self.values, self.actions_log_prob))
+            self._policy_row_ptrs(a, t, actions_only=values is None)
             self._keep_act = (mean, std, values, noise)
             fn(a)
         self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
@@ -523,32 +543,27 @@ class RolloutStorage:
         n, dev = self.env.num_envs, self.device
         if forward.actor is None or forward.critic is None or forward.num_actions is None:
             raise ValueError("act_policy needs a policy with an actor, a critic and a [A] std (or log_std)")
-        segs = forward._segments(obs, forward.actor, "obs", n, dev)   # (a window-mode manager's strided view is read in place)
-        csegs = forward._segments(obs if critic_obs is None else critic_obs, forward.critic, "obs (the critic's input)" if critic_obs is None else "critic_obs", n, dev)
+        segs = _segments(obs, "obs", n, dev, forward.actor)   # (a window-mode manager's strided view is read in place)
+        csegs = _segments(obs if critic_obs is None else critic_obs, "obs (the critic's input)" if critic_obs is None else "critic_obs", n, dev, forward.critic)
         A = forward.num_actions
         std, is_log = getattr(forward.policy, forward._std_name), forward.std_is_log
         fn = getattr(self.env.backend, "mlp_act", None)
         if fn is None:   # (the test-only oracle backend) today's path, bit for bit
-            cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
             with torch.no_grad():
-                return self.act(forward.policy.act_mean(cat(segs)), std.detach(), forward.policy.evaluate(cat(csegs)), noise, std_is_log=is_log)
+                return self.act(forward.policy.act_mean(_cat(segs)), std.detach(), forward.policy.evaluate(_cat(csegs)), noise, std_is_log=is_log)
         _check_f32(std, "policy.log_std" if is_log else "policy.std", {(A,)}, dev)
         if noise is not None:
             _check_f32(noise, "noise", {(n, A)}, dev)
-        t = 0 if self.full else self.step
         self._ensure_policy_rows(A)
         actions = torch.empty((n, A), device=dev, dtype=torch.float32)
-        stream = self._act_stream
-        self._act_stream += 1
+        t, stream, seed, env_offset = self._open_act()
         a = forward._fill(n, segs, csegs)
         a.std, a.std_per_env, a.std_is_log = std.data_ptr(), 0, 1 if is_log else 0
         a.noise = None if noise is None else noise.data_ptr()
-        a.seed = self.env._rng_seed if self._act_seed is None else self._act_seed
-        a.stream, a.env_offset = stream, int(getattr(self.env, "env_offset", 0))
+        a.seed, a.stream, a.env_offset = seed, stream, env_offset
         a.mean = a.values = None
         a.actions = actions.data_ptr()
-        a.actions_out, a.mu_out, a.sigma_out = (x.data_ptr() + t * x.stride(0) * 4 for x in (self.actions, self.mu, self.sigma))
-        a.values_out, a.log_prob_out = (x.data_ptr() + t * x.stride(0) * 4 for x in (self.values, self.actions_log_prob))
+        self._policy_row_ptrs(a, t)
         self._keep_act = (segs, csegs, noise)
         fn(a)
         self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
@@ -575,13 +590,10 @@ class RolloutStorage:
         if not isinstance(forward, DistillForward):
             raise ValueError("act_distill(forward, ...) takes a DistillForward")
         n, dev, A = self.env.num_envs, self.device, forward.num_actions
-        PolicyForward._segments(obs, forward.student, "obs", n, dev)   # (the storage's env count and device; act() checks the rest)
-        t = 0 if self.full else self.step   # (env.step() does the wrap's row copies; only the row index is needed here)
+        _segments(obs, "obs", n, dev, forward.student)   # (the storage's env count and device; act() checks the rest)
         self._ensure_distill_rows(A)
-        stream = self._act_stream
-        self._act_stream += 1
-        actions, _teacher = forward.act(obs, teacher_obs, noise, seed=self.env._rng_seed if self._act_seed is None else self._act_seed,
-                                        stream=stream, env_offset=int(getattr(self.env, "env_offset", 0)), actions_out=self.actions[t],
+        t, stream, seed, env_offset = self._open_act()
+        actions, _teacher = forward.act(obs, teacher_obs, noise, seed=seed, stream=stream, env_offset=env_offset, actions_out=self.actions[t],
                                         teacher_actions_out=self.privileged_actions[t], backend=self.env.backend)
         self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
         return actions
@@ -596,32 +608,11 @@ class RolloutStorage:
             _check_f32(x, name, shapes, dev)
         if noise is not None:
             _check_f32(noise, "noise", {(n, A)}, dev)
-        t = 0 if self.full else self.step
         self._ensure_distill_rows(A)
-        actions = torch.empty((n, A), device=dev, dtype=torch.float32)
-        stream = self._act_stream
-        self._act_stream += 1
-        fn = getattr(self.env.backend, "policy_act", None)
-        if fn is None:   # (the test-only oracle backend)
-            if noise is None:
-                raise RuntimeError("act() draws its noise in the HIP kernel: on a backend without gf_policy_act pass noise=")
-            with torch.no_grad():
-                actions.copy_(mean + (std.exp() if std_is_log else std).expand_as(mean) * noise)
-                self.actions[t].copy_(actions)
-        else:
-            a = self._act_args
-            a.num_envs, a.num_actions, a.std_per_env, a.std_is_log = n, A, 0, 1 if std_is_log else 0
-            a.mean, a.std, a.values = mean.data_ptr(), std.data_ptr(), None
-            a.noise = None if noise is None else noise.data_ptr()
-            a.seed = self.env._rng_seed if self._act_seed is None else self._act_seed
-            a.stream, a.env_offset = stream, int(getattr(self.env, "env_offset", 0))
-            a.actions, a.actions_out = actions.data_ptr(), self.actions[t].data_ptr()
-            a.mu_out = a.sigma_out = a.values_out = a.log_prob_out = None
-            self._keep_act = (mean, std, noise)
-            fn(a)
+        t = self._act_row()
+        actions = self._policy_act(mean, std, None, noise, std_is_log)
         with torch.no_grad():
             self.privileged_actions[t].copy_(teacher_actions)
-        self._pol_serial = self._serial + 1
         return actions
 
     def step_batches(self) -> Iterator[tuple]:
@@ -643,15 +634,18 @@ class RolloutStorage:
             yield obs, self.privileged_actions[t]
 
     def _act_torch(self, mean, std, values, noise, actions, t, std_is_log: bool = False) -> None:
+        """``gf_policy_act``'s row in torch (the test-only oracle backend); ``values=None``: only the action row."""
         with torch.no_grad():
-            sd = (std.exp() if std_is_log else std).expand_as(mean)
-            actions.copy_(mean + sd * noise)
+            sampled, sd = _sample_torch(mean, std, noise, std_is_log)
+            actions.copy_(sampled)
+            self.actions[t].copy_(actions)
+            if values is None:
+                return
             d = actions - mean
             term = -(d * d) / (2 * (sd * sd)) - sd.log() - _LOG_SQRT_2PI
             lp = term[:, 0].clone()
             for c in range(1, term.shape[1]):   # (a left fold, as the kernel)
                 lp = lp + term[:, c]
-            self.actions[t].copy_(actions)
             self.mu[t].copy_(mean)
             self.sigma[t].copy_(sd)
             self.values[t].copy_(values.reshape(-1))
@@ -968,24 +962,43 @@ class EpisodeStatistics:
         self._calls = 0
 
 
-def _obs_segments(x, width: int, name: str, device) -> tuple:
-    """``x`` as the tuple of ``[N, w]`` float32 segments, ``width`` wide together, a normaliser reads side by side (``act``'s rules:
-    nothing is cast) — contiguous, or the strided view a window-mode ObservationManager handed out (``_rows_ok``)."""
-    parts = (x,) if isinstance(x, torch.Tensor) else tuple(x) if isinstance(x, (list, tuple)) else None
+def _cat(x) -> torch.Tensor:
+    """An observation as one tensor: itself, or its segments side by side (the only one as it is)."""
+    if isinstance(x, torch.Tensor):
+        return x
+    return x[0] if len(x) == 1 else torch.cat(x, dim=-1)
+
+
+def _sample_torch(mean, std, noise, std_is_log: bool) -> tuple:
+    """``(mean + sigma · noise, sigma)``, ``sigma`` = ``std`` (``exp(std)`` where it is a log_std) expanded to ``mean``: the kernels'
+    sampling expression in torch, for the test-only oracle backend."""
+    sd = (std.exp() if std_is_log else std).expand_as(mean)
+    return mean + sd * noise, sd
+
+
+def _segments(obs, name: str, n: Optional[int], dev, layers=None, norm_width: Optional[int] = None) -> tuple:
+    """``obs`` as the tuple of ``[n, w]`` float32 segments that are read side by side (``act``'s rules: nothing is cast) — contiguous,
+    or the strided view a window-mode ObservationManager handed out (``_rows_ok``).  The reader is the first layer of ``layers``
+    (``[(weight, bias)]``), or a normaliser of ``norm_width`` columns; ``n`` / ``dev`` ``None``: the first segment's."""
+    parts = (obs,) if isinstance(obs, torch.Tensor) else tuple(obs) if isinstance(obs, (list, tuple)) else None
     if not parts or len(parts) > nat.GF_MLP_MAX_INPUTS:
         raise ValueError(f"{name} must be a tensor or a sequence of 1 to {nat.GF_MLP_MAX_INPUTS} tensors")
-    n = None
-    for i, t in enumerate(parts):
+    for i, x in enumerate(parts):
         what = f"{name}[{i}]" if len(parts) > 1 else name
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] < 1:
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] < 1:
             raise ValueError(f"{what} must be a [N, W] tensor")
-        if not _rows_ok(t):
+        if layers is None and not _rows_ok(x):
             raise ValueError(f"EmpiricalNormalization reads contiguous observation rows: {what} is a strided view (only the window an "
                              "ObservationManager with output='window' hands out is read in place)")
-        n = int(t.shape[0]) if n is None else n
-        _check_f32(t, what, {(n, int(t.shape[1]))}, device, window=True)
-    if sum(int(t.shape[1]) for t in parts) != width:
-        raise ValueError(f"{name} is {' + '.join(str(int(t.shape[1])) for t in parts)} wide; the normaliser keeps {width} columns")
+        n = int(x.shape[0]) if n is None else n
+        dev = x.device if dev is None else dev
+        _check_f32(x, what, {(n, int(x.shape[1]))}, dev, window=True)
+    want = norm_width if layers is None else int(layers[0][0].shape[1])
+    if sum(int(x.shape[1]) for x in parts) != want:
+        reader = f"the normaliser keeps {want} columns" if layers is None else f"the first layer reads {want}"
+        raise ValueError(f"{name} is {' + '.join(str(int(x.shape[1])) for x in parts)} wide; {reader}")
+    if layers is not None and layers[0][0].device != parts[0].device:
+        raise ValueError(f"{name} lives on {parts[0].device}, the policy on {layers[0][0].device}")
     return parts
 
 
@@ -1047,7 +1060,7 @@ class EmpiricalNormalization(torch.nn.Module):
     def update(self, x) -> None:
         if not self.training:
             return
-        _update_normalizers([(self, _obs_segments(x, self.width, "x", self._mean.device))], self._scratch.args)
+        _update_normalizers([(self, _segments(x, "x", None, self._mean.device, norm_width=self.width))], self._scratch.args)
 
     def _update_torch(self, x: torch.Tensor) -> None:
         """rsl_rl's lines."""
@@ -1093,7 +1106,7 @@ def _update_normalizers(pairs, args) -> None:
     fn = getattr(nat.get_backend(), "obs_norm_update", None) if pairs[0][1][0].device.type == "cuda" else None
     if fn is None:
         for norm, parts in pairs:
-            norm._update_torch(parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1))
+            norm._update_torch(_cat(parts))
         return
     args.num_rows, args.num_sets = n, len(pairs)
     for st, (norm, parts) in zip(args.sets, pairs):
@@ -1112,11 +1125,58 @@ def _as_normalizer(m, width: int, what: str) -> Optional["EmpiricalNormalization
     return m
 
 
+def _mlp(sizes) -> torch.nn.Sequential:
+    """``Linear(sizes[i], sizes[i + 1])`` layers with ``ELU`` between them and nothing after the last."""
+    layers = []
+    for i in range(len(sizes) - 1):
+        layers.append(torch.nn.Linear(sizes[i], sizes[i + 1]))
+        if i < len(sizes) - 2:
+            layers.append(torch.nn.ELU())
+    return torch.nn.Sequential(*layers)
+
+
+class _ActionStd:
+    """The learnable action std of :class:`ActorCriticMLP` and :class:`StudentTeacherMLP`: a ``std`` parameter ``[A]``
+    (``noise_std_type="scalar"``) or a ``log_std`` one in its place (``"log"``) — rsl_rl's names."""
+
+    def _set_noise_std_type(self, who: str, noise_std_type: str) -> None:
+        if noise_std_type not in ("scalar", "log"):
+            raise ValueError(f"{who}: noise_std_type={noise_std_type!r} is not supported ('scalar' or 'log')")
+        self.noise_std_type = noise_std_type
+
+    def _make_std(self, init_noise_std: float, num_actions: int) -> None:
+        if self.noise_std_type == "scalar":
+            self.std = torch.nn.Parameter(init_noise_std * torch.ones(num_actions))
+        else:
+            self.log_std = torch.nn.Parameter(torch.log(init_noise_std * torch.ones(num_actions)))
+
+    @property
+    def action_std(self) -> torch.Tensor:
+        """The current action std ``[A]`` (detached): ``std``, or ``exp(log_std)``."""
+        return self.log_std.detach().exp() if self.noise_std_type == "log" else self.std.detach().clone()
+
+
+def _policy_cfg(train_cfg: dict, who: str, keys: tuple, class_name: str) -> dict:
+    """``train_cfg["policy"]`` for ``who.from_train_cfg``; ``ValueError`` naming the key for an unknown one, another activation than
+    ``"elu"``, another ``noise_std_type`` than ``"scalar"`` / ``"log"`` or another ``class_name`` than the one given."""
+    pol = dict(train_cfg.get("policy", {}))
+    bad = sorted(k for k in pol if k not in keys)
+    if bad:
+        raise ValueError(f"{who}: unsupported policy keys {bad}")
+    if pol.get("activation", "elu") != "elu":
+        raise ValueError(f"{who}: policy.activation={pol['activation']!r} is not supported (only 'elu')")
+    if pol.get("noise_std_type", "scalar") not in ("scalar", "log"):
+        raise ValueError(f"{who}: policy.noise_std_type={pol['noise_std_type']!r} is not supported ('scalar' or 'log')")
+    if pol.get("class_name", class_name) != class_name:
+        raise ValueError(f"{who}: policy.class_name={pol['class_name']!r} is not supported (only '{class_name}')")
+    return pol
+
+
 _POLICY_KEYS = ("class_name", "activation", "actor_hidden_dims", "critic_hidden_dims", "init_noise_std", "noise_std_type",
                 "actor_obs_normalization", "critic_obs_normalization")
 
 
-class ActorCriticMLP(torch.nn.Module):
+class ActorCriticMLP(_ActionStd, torch.nn.Module):
     """rsl_rl's ``ActorCritic`` as configured by the reference's training scripts (examples/simple/train.py:56-62).
     ``actor_obs_normalization`` / ``critic_obs_normalization`` (rsl_rl 3.x): an :class:`EmpiricalNormalization` in front of the net
     (``actor_obs_normalizer`` / ``critic_obs_normalizer``; ``nn.Identity()`` when off, as rsl_rl) — buffers only, so ``parameters()``
@@ -1129,25 +1189,12 @@ class ActorCriticMLP(torch.nn.Module):
                  critic_hidden_dims: Sequence[int] = (512, 256, 128), init_noise_std: float = 1.0, num_critic_obs: Optional[int] = None,
                  actor_obs_normalization: bool = False, critic_obs_normalization: bool = False, noise_std_type: str = "scalar"):
         super().__init__()
-        if noise_std_type not in ("scalar", "log"):
-            raise ValueError(f"ActorCriticMLP: noise_std_type={noise_std_type!r} is not supported ('scalar' or 'log')")
-        self.noise_std_type = noise_std_type
-
-        def mlp(sizes):
-            layers = []
-            for i in range(len(sizes) - 1):
-                layers.append(torch.nn.Linear(sizes[i], sizes[i + 1]))
-                if i < len(sizes) - 2:
-                    layers.append(torch.nn.ELU())
-            return torch.nn.Sequential(*layers)
+        self._set_noise_std_type("ActorCriticMLP", noise_std_type)
 
         num_critic_obs = num_obs if num_critic_obs is None else int(num_critic_obs)
-        self.actor = mlp([num_obs, *actor_hidden_dims, num_actions])
-        self.critic = mlp([num_critic_obs, *critic_hidden_dims, 1])
-        if noise_std_type == "scalar":
-            self.std = torch.nn.Parameter(init_noise_std * torch.ones(num_actions))
-        else:
-            self.log_std = torch.nn.Parameter(torch.log(init_noise_std * torch.ones(num_actions)))
+        self.actor = _mlp([num_obs, *actor_hidden_dims, num_actions])
+        self.critic = _mlp([num_critic_obs, *critic_hidden_dims, 1])
+        self._make_std(init_noise_std, num_actions)
         self.actor_obs_normalizer = EmpiricalNormalization(num_obs) if actor_obs_normalization else torch.nn.Identity()
         self.critic_obs_normalizer = EmpiricalNormalization(num_critic_obs) if critic_obs_normalization else torch.nn.Identity()
         self._scratch = _NormScratch()
@@ -1160,27 +1207,13 @@ class ActorCriticMLP(torch.nn.Module):
         ``policy.noise_std_type`` (``"scalar"`` or ``"log"``).
         Anything that cannot be honoured — another activation than ``"elu"``, another ``noise_std_type`` than those two, an
         unknown policy key — raises ``ValueError`` naming the key."""
-        pol = dict(train_cfg.get("policy", {}))
-        bad = sorted(k for k in pol if k not in _POLICY_KEYS)
-        if bad:
-            raise ValueError(f"ActorCriticMLP: unsupported policy keys {bad}")
-        if pol.get("activation", "elu") != "elu":
-            raise ValueError(f"ActorCriticMLP: policy.activation={pol['activation']!r} is not supported (only 'elu')")
-        if pol.get("noise_std_type", "scalar") not in ("scalar", "log"):
-            raise ValueError(f"ActorCriticMLP: policy.noise_std_type={pol['noise_std_type']!r} is not supported ('scalar' or 'log')")
-        if pol.get("class_name", "ActorCritic") != "ActorCritic":
-            raise ValueError(f"ActorCriticMLP: policy.class_name={pol['class_name']!r} is not supported (only 'ActorCritic')")
+        pol = _policy_cfg(train_cfg, "ActorCriticMLP", _POLICY_KEYS, "ActorCritic")
         both = bool(train_cfg.get("empirical_normalization"))
         return cls(num_obs, num_actions, tuple(pol.get("actor_hidden_dims", (512, 256, 128))), tuple(pol.get("critic_hidden_dims", (512, 256, 128))),
                    float(pol.get("init_noise_std", 1.0)), num_critic_obs=num_critic_obs,
                    actor_obs_normalization=both or bool(pol.get("actor_obs_normalization", False)),
                    critic_obs_normalization=both or bool(pol.get("critic_obs_normalization", False)),
                    noise_std_type=pol.get("noise_std_type", "scalar"))
-
-    @property
-    def action_std(self) -> torch.Tensor:
-        """The current action std ``[A]`` (detached): ``std``, or ``exp(log_std)``."""
-        return self.log_std.detach().exp() if self.noise_std_type == "log" else self.std.detach().clone()
 
     def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
         return self.actor(self.actor_obs_normalizer(obs))
@@ -1194,7 +1227,7 @@ class ActorCriticMLP(torch.nn.Module):
         pairs = []
         for norm, x, name in ((self.actor_obs_normalizer, obs, "obs"), (self.critic_obs_normalizer, obs if critic_obs is None else critic_obs, "critic_obs")):
             if isinstance(norm, EmpiricalNormalization) and norm.training:
-                pairs.append((norm, _obs_segments(x, norm.width, name, norm._mean.device)))
+                pairs.append((norm, _segments(x, name, None, norm._mean.device, norm_width=norm.width)))
         _update_normalizers(pairs, self._scratch.args)
 
 
@@ -1202,7 +1235,7 @@ _STUDENT_TEACHER_KEYS = ("class_name", "activation", "student_hidden_dims", "tea
                          "student_obs_normalization", "teacher_obs_normalization")
 
 
-class StudentTeacherMLP(torch.nn.Module):
+class StudentTeacherMLP(_ActionStd, torch.nn.Module):
     """rsl_rl's ``StudentTeacher`` (feed-forward): a ``student`` that reads the deployable observations and is trained, and a frozen
     ``teacher`` that reads the privileged ones and labels every step.  Both are ``nn.Sequential`` of ``Linear`` with ``ELU`` between;
     ``std`` (or ``log_std`` with ``noise_std_type="log"``) is the exploration noise of the student's actions during collection;
@@ -1219,27 +1252,14 @@ class StudentTeacherMLP(torch.nn.Module):
                  teacher_hidden_dims: Sequence[int] = (256, 256, 256), init_noise_std: float = 0.1, student_obs_normalization: bool = False,
                  teacher_obs_normalization: bool = False, noise_std_type: str = "scalar"):
         super().__init__()
-        if noise_std_type not in ("scalar", "log"):
-            raise ValueError(f"StudentTeacherMLP: noise_std_type={noise_std_type!r} is not supported ('scalar' or 'log')")
-        self.noise_std_type = noise_std_type
+        self._set_noise_std_type("StudentTeacherMLP", noise_std_type)
         self.loaded_teacher = False
 
-        def mlp(sizes):
-            layers = []
-            for i in range(len(sizes) - 1):
-                layers.append(torch.nn.Linear(sizes[i], sizes[i + 1]))
-                if i < len(sizes) - 2:
-                    layers.append(torch.nn.ELU())
-            return torch.nn.Sequential(*layers)
-
-        self.student = mlp([int(num_student_obs), *student_hidden_dims, int(num_actions)])
-        self.teacher = mlp([int(num_teacher_obs), *teacher_hidden_dims, int(num_actions)])
+        self.student = _mlp([int(num_student_obs), *student_hidden_dims, int(num_actions)])
+        self.teacher = _mlp([int(num_teacher_obs), *teacher_hidden_dims, int(num_actions)])
         for p in self.teacher.parameters():
             p.requires_grad_(False)
-        if noise_std_type == "scalar":
-            self.std = torch.nn.Parameter(init_noise_std * torch.ones(num_actions))
-        else:
-            self.log_std = torch.nn.Parameter(torch.log(init_noise_std * torch.ones(num_actions)))
+        self._make_std(init_noise_std, num_actions)
         self.student_obs_normalizer = EmpiricalNormalization(int(num_student_obs)) if student_obs_normalization else torch.nn.Identity()
         self.teacher_obs_normalizer = EmpiricalNormalization(int(num_teacher_obs)) if teacher_obs_normalization else torch.nn.Identity()
         self._scratch = _NormScratch()
@@ -1252,26 +1272,12 @@ class StudentTeacherMLP(torch.nn.Module):
         ``noise_std_type`` / ``student_obs_normalization`` / ``teacher_obs_normalization``.  Anything that cannot be honoured — an
         unknown policy key, another activation than ``"elu"``, another class name than ``"StudentTeacher"`` — raises ``ValueError``
         naming the key."""
-        pol = dict(train_cfg.get("policy", {}))
-        bad = sorted(k for k in pol if k not in _STUDENT_TEACHER_KEYS)
-        if bad:
-            raise ValueError(f"StudentTeacherMLP: unsupported policy keys {bad}")
-        if pol.get("activation", "elu") != "elu":
-            raise ValueError(f"StudentTeacherMLP: policy.activation={pol['activation']!r} is not supported (only 'elu')")
-        if pol.get("noise_std_type", "scalar") not in ("scalar", "log"):
-            raise ValueError(f"StudentTeacherMLP: policy.noise_std_type={pol['noise_std_type']!r} is not supported ('scalar' or 'log')")
-        if pol.get("class_name", "StudentTeacher") != "StudentTeacher":
-            raise ValueError(f"StudentTeacherMLP: policy.class_name={pol['class_name']!r} is not supported (only 'StudentTeacher')")
+        pol = _policy_cfg(train_cfg, "StudentTeacherMLP", _STUDENT_TEACHER_KEYS, "StudentTeacher")
         return cls(num_student_obs, num_teacher_obs, num_actions, tuple(pol.get("student_hidden_dims", (256, 256, 256))),
                    tuple(pol.get("teacher_hidden_dims", (256, 256, 256))), float(pol.get("init_noise_std", 0.1)),
                    student_obs_normalization=bool(pol.get("student_obs_normalization", False)),
                    teacher_obs_normalization=bool(pol.get("teacher_obs_normalization", False)),
                    noise_std_type=pol.get("noise_std_type", "scalar"))
-
-    @property
-    def action_std(self) -> torch.Tensor:
-        """The current action std ``[A]`` (detached): ``std``, or ``exp(log_std)``."""
-        return self.log_std.detach().exp() if self.noise_std_type == "log" else self.std.detach().clone()
 
     def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
         """The student on its normalised input (rsl_rl's ``act_inference``)."""
@@ -1287,7 +1293,7 @@ class StudentTeacherMLP(torch.nn.Module):
         frozen with the teacher."""
         norm = self.student_obs_normalizer
         if isinstance(norm, EmpiricalNormalization) and norm.training:
-            _update_normalizers([(norm, _obs_segments(obs, norm.width, "obs", norm._mean.device))], self._scratch.args)
+            _update_normalizers([(norm, _segments(obs, "obs", None, norm._mean.device, norm_width=norm.width))], self._scratch.args)
 
     def train(self, mode: bool = True):
         super().train(mode)
@@ -1363,7 +1369,73 @@ def _walk_mlp(net, name: str, max_out: int, who: str = "PolicyForward"):
     return layers
 
 
-class PolicyForward:
+def _fill_net(net, layers, parts, norm=None) -> None:
+    """Point a GfMlpNet at the current weights of ``layers``, the input segments ``parts`` and the normaliser in front (``layers`` or
+    ``parts`` None: the net is left out of the launch)."""
+    if layers is None or parts is None:
+        net.num_layers = 0
+        return
+    if norm is None:
+        if net.in_mean is not None:
+            net.in_mean = net.in_std = None
+    else:
+        if norm._mean.device != parts[0].device:
+            raise ValueError(f"the observation lives on {parts[0].device}, the normaliser on {norm._mean.device}")
+        net.in_mean, net.in_std, net.in_eps = norm._mean.data_ptr(), norm._std.data_ptr(), norm.eps
+    net.num_layers, net.num_inputs = len(layers), len(parts)
+    for seg, x in zip(net.inputs, parts):
+        seg.rows, seg.width, seg.row_stride = x.data_ptr(), x.shape[1], 0 if x.is_contiguous() else x.stride(0)
+    for lay, (w, b) in zip(net.layers, layers):
+        lay.weight, lay.bias, lay.out_width = w.data_ptr(), b.data_ptr(), w.shape[0]
+
+
+class _MlpForward:
+    """What :class:`PolicyForward` and :class:`DistillForward` share.  The host class keeps ``policy`` and, per net name, the
+    ``[(weight, bias)]`` list ``_walk_mlp`` returned (or None) as the attribute of that name."""
+
+    def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
+        """The policy's current normaliser in front of net ``name`` (None: the net reads its input as it is)."""
+        layers = getattr(self, name)
+        if layers is None:
+            return None
+        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), int(layers[0][0].shape[1]),
+                              f"{type(self).__name__}: policy.{name}_obs_normalizer")
+
+    def _read_std(self):
+        """Fix the std's type (the parameter itself is looked up per call) and return the parameter, None where the policy has none."""
+        std, is_log = _policy_std(self.policy)
+        self.std_is_log, self._std_name = is_log, "log_std" if is_log else "std"
+        return std
+
+    @staticmethod
+    def _std_ok(std, A: int) -> bool:
+        return std.dtype == torch.float32 and tuple(std.shape) == (A,)
+
+    def _one(self, obs, name: str, torch_fn, fill) -> torch.Tensor:
+        """The output of net ``name`` alone for ``obs``: one ``gf_mlp_act`` launch on the descriptor ``fill(n, segments)`` returns, a
+        fresh tensor."""
+        layers = getattr(self, name)
+        if layers is None:
+            raise ValueError(f"{type(self).__name__}: the policy has no {name}")
+        parts = _segments(obs, "obs", None, None, layers)
+        fn = getattr(nat.get_backend(), "mlp_act", None)
+        if fn is None:   # (the test-only oracle backend)
+            norm = self._normalizer(name)
+            with torch.no_grad():
+                x = _cat(parts)
+                return torch_fn(x if norm is None else norm(x))
+        n = int(parts[0].shape[0])
+        out = torch.empty((n, int(layers[-1][0].shape[0])), device=parts[0].device, dtype=torch.float32)
+        a = fill(n, parts)
+        a.std_is_log = 0
+        a.std = a.noise = a.actions = a.actions_out = a.mu_out = a.sigma_out = a.values_out = a.log_prob_out = None
+        a.mean, a.values = (None, out.data_ptr()) if name == "critic" else (out.data_ptr(), None)
+        self._keep_one = (parts, out)
+        fn(a)
+        return out
+
+
+class PolicyForward(_MlpForward):
     """The actor and critic of a policy as ``gf_mlp_act`` reads them: one launch per forward pass, weights read in place.
 
     ``policy.actor`` / ``policy.critic`` (either may be missing or ``None``) must be ``nn.Sequential`` of ``Linear`` layers with
@@ -1387,14 +1459,12 @@ class PolicyForward:
         if self.actor is None and self.critic is None:
             raise ValueError("PolicyForward: the policy has neither an actor nor a critic")
         self._normalizer("actor"), self._normalizer("critic")   # (refuses what the kernel cannot fold in)
-        std, is_log = _policy_std(policy)
-        self.std_is_log, self._std_name = is_log, "log_std" if is_log else "std"   # (the type is fixed; the parameter is looked up per call)
+        std = self._read_std()
         self.num_actions = None
         if self.actor is not None and std is not None:
             A = self.actor[-1][0].shape[0]
-            if std.dtype != torch.float32 or tuple(std.shape) != (A,):
-                name = "log_std" if is_log else "std"
-                raise ValueError(f"PolicyForward: policy.{name} must be a float32 [{A}] tensor, not {std.dtype} {tuple(std.shape)}")
+            if not self._std_ok(std, A):
+                raise ValueError(f"PolicyForward: policy.{self._std_name} must be a float32 [{A}] tensor, not {std.dtype} {tuple(std.shape)}")
             self.num_actions = int(A)
         self._args = nat.GfMlpActArgs()
 
@@ -1408,89 +1478,24 @@ class PolicyForward:
         """[(weight, bias)] of the net's Linear layers (the Parameter objects: their storage may be re-seated later), or None."""
         return _walk_mlp(net, name, max_out)
 
-    def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
-        """The policy's current normaliser in front of ``name`` (None: the net reads its input as it is)."""
-        layers = self.actor if name == "actor" else self.critic
-        if layers is None:
-            return None
-        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), int(layers[0][0].shape[1]), f"PolicyForward: policy.{name}_obs_normalizer")
-
-    @staticmethod
-    def _segments(obs, layers, name: str, n: Optional[int], dev) -> tuple:
-        """``obs`` as the tuple of ``[n, w]`` float32 segments the first layer of ``layers`` reads side by side — contiguous, or the
-        strided view a window-mode ObservationManager handed out (``_rows_ok``)."""
-        parts = (obs,) if isinstance(obs, torch.Tensor) else tuple(obs) if isinstance(obs, (list, tuple)) else None
-        if not parts or len(parts) > nat.GF_MLP_MAX_INPUTS:
-            raise ValueError(f"{name} must be a tensor or a sequence of 1 to {nat.GF_MLP_MAX_INPUTS} tensors")
-        for i, x in enumerate(parts):
-            if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] < 1:
-                raise ValueError(f"{name}[{i}] must be a [N, W] tensor" if len(parts) > 1 else f"{name} must be a [N, W] tensor")
-            if n is None:
-                n, dev = int(x.shape[0]), x.device
-            _check_f32(x, f"{name}[{i}]" if len(parts) > 1 else name, {(n, int(x.shape[1]))}, dev, window=True)
-        want = int(layers[0][0].shape[1])
-        if sum(int(x.shape[1]) for x in parts) != want:
-            raise ValueError(f"{name} is {' + '.join(str(int(x.shape[1])) for x in parts)} wide; the first layer reads {want}")
-        if layers[0][0].device != parts[0].device:
-            raise ValueError(f"{name} lives on {parts[0].device}, the policy on {layers[0][0].device}")
-        return parts
-
-    @staticmethod
-    def _fill_net(net, layers, parts, norm=None) -> None:
-        if layers is None or parts is None:
-            net.num_layers = 0
-            return
-        if norm is None:
-            if net.in_mean is not None:
-                net.in_mean = net.in_std = None
-        else:
-            if norm._mean.device != parts[0].device:
-                raise ValueError(f"the observation lives on {parts[0].device}, the normaliser on {norm._mean.device}")
-            net.in_mean, net.in_std, net.in_eps = norm._mean.data_ptr(), norm._std.data_ptr(), norm.eps
-        net.num_layers, net.num_inputs = len(layers), len(parts)
-        for seg, x in zip(net.inputs, parts):
-            seg.rows, seg.width, seg.row_stride = x.data_ptr(), x.shape[1], 0 if x.is_contiguous() else x.stride(0)
-        for lay, (w, b) in zip(net.layers, layers):
-            lay.weight, lay.bias, lay.out_width = w.data_ptr(), b.data_ptr(), w.shape[0]
-
     def _fill(self, n: int, actor_parts, critic_parts):
         """The descriptor with both nets pointed at the current weights and the given inputs (None: that net is left out)."""
         a = self._args
         a.num_envs = n
-        self._fill_net(a.actor, self.actor, actor_parts, self._normalizer("actor"))
-        self._fill_net(a.critic, self.critic, critic_parts, self._normalizer("critic"))
+        _fill_net(a.actor, self.actor, actor_parts, self._normalizer("actor"))
+        _fill_net(a.critic, self.critic, critic_parts, self._normalizer("critic"))
         return a
-
-    def _one(self, obs, layers, name: str, torch_fn) -> torch.Tensor:
-        if layers is None:
-            raise ValueError(f"PolicyForward: the policy has no {name}")
-        parts = self._segments(obs, layers, "obs", None, None)
-        fn = getattr(nat.get_backend(), "mlp_act", None)
-        if fn is None:   # (the test-only oracle backend)
-            norm = self._normalizer(name)
-            with torch.no_grad():
-                x = parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
-                return torch_fn(x if norm is None else norm(x))
-        n = int(parts[0].shape[0])
-        out = torch.empty((n, int(layers[-1][0].shape[0])), device=parts[0].device, dtype=torch.float32)
-        a = self._fill(n, parts if name == "actor" else None, parts if name == "critic" else None)
-        a.std_is_log = 0
-        a.std = a.noise = a.actions = a.actions_out = a.mu_out = a.sigma_out = a.values_out = a.log_prob_out = None
-        a.mean, a.values = (out.data_ptr(), None) if name == "actor" else (None, out.data_ptr())
-        self._keep = (parts, out)
-        fn(a)
-        return out
 
     def mean(self, obs) -> torch.Tensor:
         """The actor's output ``[N, A]`` (``policy.act_mean(obs)``): one launch, a fresh tensor."""
-        return self._one(obs, self.actor, "actor", self.policy.actor)
+        return self._one(obs, "actor", self.policy.actor, lambda n, parts: self._fill(n, parts, None))
 
     def value(self, critic_obs) -> torch.Tensor:
         """The critic's output ``[N, 1]`` (``policy.evaluate(critic_obs)``): one launch, a fresh tensor."""
-        return self._one(critic_obs, self.critic, "critic", self.policy.critic)
+        return self._one(critic_obs, "critic", self.policy.critic, lambda n, parts: self._fill(n, None, parts))
 
 
-class DistillForward:
+class DistillForward(_MlpForward):
     """The student and the teacher of a policy (``policy.student`` / ``policy.teacher``, a :class:`StudentTeacherMLP` or anything of
     that shape) as ``gf_mlp_distill_act`` reads them — the counterpart of :class:`PolicyForward`, under its rules: the structure is
     checked once, the weight addresses and the normalisers (``policy.student_obs_normalizer`` / ``teacher_obs_normalizer``) are looked
@@ -1509,36 +1514,22 @@ class DistillForward:
         if int(self.teacher[-1][0].shape[0]) != A:
             raise ValueError(f"DistillForward: policy.student has {A} outputs, policy.teacher {int(self.teacher[-1][0].shape[0])}")
         self._normalizer("student"), self._normalizer("teacher")   # (refuses what the kernel cannot fold in)
-        std, is_log = _policy_std(policy)
-        self.std_is_log, self._std_name = is_log, "log_std" if is_log else "std"
-        if std is None or std.dtype != torch.float32 or tuple(std.shape) != (A,):
+        std = self._read_std()
+        if std is None or not self._std_ok(std, A):
             raise ValueError(f"DistillForward: policy.{self._std_name} must be a float32 [{A}] tensor")
         self.num_actions = A
         self._args, self._mean_args = nat.GfMlpDistillArgs(), nat.GfMlpActArgs()
 
-    def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
-        layers = self.student if name == "student" else self.teacher
-        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), int(layers[0][0].shape[1]), f"DistillForward: policy.{name}_obs_normalizer")
-
     def mean(self, obs) -> torch.Tensor:
         """The student's output ``[N, A]`` (``policy.act_mean(obs)``): one launch, a fresh tensor."""
-        parts = PolicyForward._segments(obs, self.student, "obs", None, None)
-        norm = self._normalizer("student")
-        fn = getattr(nat.get_backend(), "mlp_act", None)
-        if fn is None:   # (the test-only oracle backend)
-            with torch.no_grad():
-                x = parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
-                return self.policy.student(x if norm is None else norm(x))
-        n = int(parts[0].shape[0])
-        out = torch.empty((n, self.num_actions), device=parts[0].device, dtype=torch.float32)
+        return self._one(obs, "student", self.policy.student, self._fill_mean)
+
+    def _fill_mean(self, n: int, parts):
         a = self._mean_args
         a.num_envs = n
-        PolicyForward._fill_net(a.actor, self.student, parts, norm)
+        _fill_net(a.actor, self.student, parts, self._normalizer("student"))
         a.critic.num_layers = 0
-        a.mean = out.data_ptr()
-        self._keep_mean = (parts, out)
-        fn(a)
-        return out
+        return a
 
     def act(self, obs, teacher_obs=None, noise: Optional[torch.Tensor] = None, seed: int = 0, stream: int = 0, env_offset: int = 0,
             actions_out: Optional[torch.Tensor] = None, teacher_actions_out: Optional[torch.Tensor] = None, backend=None):
@@ -1547,10 +1538,10 @@ class DistillForward:
         contiguous ``[N, A]`` rows that receive the same values from the same launch.  ``noise`` / ``seed`` / ``stream`` /
         ``env_offset``: as ``gf_policy_act``'s.  On a backend without the entry point (the test-only CPU oracle) the same expression
         runs in torch and ``noise`` is required."""
-        segs = PolicyForward._segments(obs, self.student, "obs", None, None)
+        segs = _segments(obs, "obs", None, None, self.student)
         n, dev = int(segs[0].shape[0]), segs[0].device
-        tsegs = PolicyForward._segments(obs if teacher_obs is None else teacher_obs, self.teacher,
-                                        "obs (the teacher's input)" if teacher_obs is None else "teacher_obs", n, dev)
+        tsegs = _segments(obs if teacher_obs is None else teacher_obs, "obs (the teacher's input)" if teacher_obs is None else "teacher_obs", n, dev,
+                          self.teacher)
         A = self.num_actions
         std = getattr(self.policy, self._std_name)
         _check_f32(std, f"policy.{self._std_name}", {(A,)}, dev)
@@ -1562,11 +1553,9 @@ class DistillForward:
         if fn is None:   # (the test-only oracle backend) the same expression in torch, from the given draws
             if noise is None:
                 raise RuntimeError("act() draws its noise in the HIP kernel: on a backend without gf_mlp_distill_act pass noise=")
-            cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
             with torch.no_grad():
-                mean, teacher = self.policy.act_mean(cat(segs)), self.policy.evaluate(cat(tsegs)).clone()
-                sd = (std.exp() if self.std_is_log else std).expand_as(mean)
-                actions = mean + sd * noise
+                mean, teacher = self.policy.act_mean(_cat(segs)), self.policy.evaluate(_cat(tsegs)).clone()
+                actions, _sd = _sample_torch(mean, std, noise, self.std_is_log)
                 if actions_out is not None:
                     actions_out.copy_(actions)
                 if teacher_actions_out is not None:
@@ -1576,8 +1565,8 @@ class DistillForward:
         teacher = torch.empty((n, A), device=dev, dtype=torch.float32)
         a = self._args
         a.num_envs = n
-        PolicyForward._fill_net(a.student, self.student, segs, self._normalizer("student"))
-        PolicyForward._fill_net(a.teacher, self.teacher, tsegs, self._normalizer("teacher"))
+        _fill_net(a.student, self.student, segs, self._normalizer("student"))
+        _fill_net(a.teacher, self.teacher, tsegs, self._normalizer("teacher"))
         a.std, a.std_is_log = std.data_ptr(), 1 if self.std_is_log else 0
         a.noise = None if noise is None else noise.data_ptr()
         a.seed, a.stream, a.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(env_offset)
@@ -1774,6 +1763,14 @@ class _FlatAdam:
             self._state_lr[2 * par] = lr
             self._state[2 * par + 1] = step
         self._calls = step
+
+    def _adam_step(self, backend) -> None:
+        """One optimizer step over the flat bucket: ``gf_adam_step``, or its torch twin on a backend without it (the test-only
+        oracle backend, whose losses went through autograd)."""
+        if getattr(backend, "adam_step", None) is not None:
+            self._adam_hip(backend)
+        else:
+            self._adam_torch()
 
     def _adam_hip(self, backend) -> None:
         a, par = self._adam_args, self._calls & 1
@@ -1986,10 +1983,7 @@ class PPO(_FlatAdam):
         self._reduce_kl()
         sync.average()
         sync.wait()
-        if hip:
-            self._adam_hip(backend)
-        else:
-            self._adam_torch()
+        self._adam_step(backend)
 
     # -- one minibatch with a symmetry_cfg ---------------------------------------------------------------------------------------------
     def _minibatch_symmetry(self, b: MiniBatch, norms=(None, None)) -> None:
@@ -2004,10 +1998,7 @@ class PPO(_FlatAdam):
         self._reduce_kl()
         sync.average()
         sync.wait()
-        if getattr(backend, "ppo_loss", None) is not None:
-            self._adam_hip(backend)
-        else:
-            self._adam_torch()
+        self._adam_step(backend)
 
     def _symmetry_torch(self, b: MiniBatch) -> None:
         """rsl_rl's lines through the MirrorSymmetry's ``__call__`` (plain torch): ``b`` carries raw observations, the policy's own
@@ -2322,9 +2313,6 @@ class Distillation(_FlatAdam):
                     self._bc_torch(mu, target)
                 cnt += 1
                 if cnt % self.gradient_length == 0:
-                    if hip:
-                        self._adam_hip(backend)
-                    else:
-                        self._adam_torch()
+                    self._adam_step(backend)
                     sync.zero_grad()
         return {"behavior": self._sums.tolist()[0] / cnt}

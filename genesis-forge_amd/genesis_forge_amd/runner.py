@@ -26,7 +26,7 @@ import torch
 
 from . import gs
 from .learner import (ActorCriticMLP, DistillForward, Distillation, EpisodeStatistics, PolicyForward, PPO, RolloutStorage, StudentTeacherMLP,
-                      _policy_std)
+                      _cat, _policy_std)
 from .wrappers import RslRlWrapper
 
 CHECKPOINT_VERSION = 1   # of the "genesis_forge_amd" block of a checkpoint file
@@ -119,10 +119,6 @@ class OnPolicyRunner:
         return (self._group(store.obs_groups["policy"], obs, extras),
                 None if self._shared_critic else self._group(store.obs_groups["critic"], obs, extras))
 
-    @staticmethod
-    def _cat(x) -> torch.Tensor:
-        return x if isinstance(x, torch.Tensor) else torch.cat(x, dim=-1)
-
     def _noise(self, n: int, A: int) -> Optional[torch.Tensor]:
         if self.action_noise is None:
             return None
@@ -140,8 +136,8 @@ class OnPolicyRunner:
             else:
                 std, is_log = _policy_std(policy)   # (std, or log_std with std_is_log)
                 with torch.no_grad():
-                    mean = policy.act_mean(self._cat(x))
-                    values = policy.evaluate(self._cat(x if cx is None else cx))
+                    mean = policy.act_mean(_cat(x))
+                    values = policy.evaluate(_cat(x if cx is None else cx))
                 actions = store.act(mean, std.detach(), values, noise=self._noise(n, A), std_is_log=is_log)
             obs, _rew, _terminated, truncated, extras = env.step(actions)
             x, cx = self._inputs(obs, extras)
@@ -155,7 +151,7 @@ class OnPolicyRunner:
         if self._fwd is not None:
             self.storage.compute_returns(self._fwd.value(last), gamma=self.alg.gamma, lam=self.alg.lam)
         else:
-            self.alg.compute_returns(self._cat(last))
+            self.alg.compute_returns(_cat(last))
 
     def _update(self) -> dict:
         return self.alg.update(generator=self._generator)
@@ -291,7 +287,7 @@ class OnPolicyRunner:
 
         def act_mean(obs):
             with torch.no_grad():
-                return policy.act_mean(self._cat(tuple(obs) if isinstance(obs, (list, tuple)) else obs))
+                return policy.act_mean(_cat(tuple(obs) if isinstance(obs, (list, tuple)) else obs))
 
         return act_mean
 
@@ -339,7 +335,7 @@ class DistillationRunner(OnPolicyRunner):
             else:
                 std, is_log = _policy_std(policy)
                 with torch.no_grad():
-                    mean, teacher = policy.act_mean(self._cat(x)), policy.evaluate(self._cat(tx))
+                    mean, teacher = policy.act_mean(_cat(x)), policy.evaluate(_cat(tx))
                 actions = store._act_distill_rows(mean, std.detach(), teacher, noise=self._noise(n, A), std_is_log=is_log)
             obs, _rew, _terminated, _truncated, extras = env.step(actions)
             policy.update_normalization(self._group(groups["policy"], obs, extras))

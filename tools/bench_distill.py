@@ -55,7 +55,7 @@ def run_forms(forms: dict, reps: int, calls: int) -> dict:
 
 def collect_forms(n: int):
     from genesis_forge_amd import _native as nat
-    from genesis_forge_amd.learner import DistillForward, PolicyForward, StudentTeacherMLP
+    from genesis_forge_amd.learner import DistillForward, StudentTeacherMLP, _fill_net
 
     backend = nat.get_backend()
     torch.manual_seed(0)
@@ -74,7 +74,7 @@ def collect_forms(n: int):
     actions = torch.empty(n, A, device="cuda")
     for a, layers, x in ((sa, fwd.student, obs), (ta, fwd.teacher, tobs)):
         a.num_envs = n
-        PolicyForward._fill_net(a.actor, layers, (x,), None)
+        _fill_net(a.actor, layers, (x,), None)
     sa.std, sa.seed, sa.actions, sa.actions_out = policy.std.data_ptr(), 3, actions.data_ptr(), row_a.data_ptr()
     ta.mean = row_t.data_ptr()
 

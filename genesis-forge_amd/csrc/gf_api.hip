@@ -83,6 +83,7 @@ GF_EXPORT int gf_sizeof(int which) {
         case 32: return (int)sizeof(GfMirrorLossArgs);
         case 33: return (int)sizeof(GfMlpDistillArgs);
         case 34: return (int)sizeof(GfBcLossArgs);
+        case 35: return (int)sizeof(GfRndRewardArgs);
         default: return -1;
     }
 }

@@ -1,4 +1,4 @@
-// gf_mlp.hip — gf_mlp_act (and gf_mlp_distill_act): the actor and critic MLPs of a collection step and gf_policy_act's sampling in one launch
+// gf_mlp.hip — gf_mlp_act (and gf_mlp_distill_act, gf_rnd_reward): the actor and critic MLPs of a collection step and gf_policy_act's sampling in one launch
 // (include/gf_step.h has the contract).  The first kernel of the library on the matrix cores: every other one is bandwidth- or
 // latency-bound, this one is 0.76 MFLOP per env.
 //
@@ -29,6 +29,7 @@
 
 #include "gf_launch.h"
 #include "gf_policy_row.h"
+#include "gf_reduce.h"
 
 namespace gf {
 
@@ -355,6 +356,144 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_distill_kernel(const GfMlpDi
     else mlp_sample_row<false>(p, out, n, vec_rows);
 }
 
+// gf_rnd_reward (rsl_rl RandomNetworkDistillation.get_intrinsic_reward): ONE workgroup walks the frozen target, stashes the tile's
+// E <= GF_MLP_MAX_ACTIONS outputs in a second LDS array, walks the predictor from the re-staged input, and lane r < 32 finishes row
+// r: ‖target − predictor‖₂, the weight, the storage row's add.  Chosen over grid y = net (gf_mlp_distill_act's shape) because the
+// distance needs both embeddings of a row in one place: this way they never leave LDS and no second launch has to wait for them.
+// LDS: 65 664 + 8 320 = 73 984 B, still two workgroups per CU.  With the reward normaliser updating, this launch leaves the raw
+// distances in `intrinsic`, the new `avg` and one {rows, mean, M2} record of the tile's avg in the workspace, and a snapshot of the
+// old statistics (workgroup 0); rnd_scale_kernel then folds the records — every workgroup the same fold, in index order — applies the
+// update, scales its rows and adds.  The workgroup that stores the new statistics is the only one that touches them in that launch.
+constexpr int kRndES = GF_MLP_MAX_ACTIONS + 1;   // row stride of the stashed embeddings (odd: 32 rows on 32 banks)
+constexpr int kRndHead = 4;                      // doubles in front of the records: old mean, var, std, count (as int64)
+static_assert(kSumBlock == kMlpBlock, "the scale launch folds with gf_reduce.h's four-wave sums");
+
+// the row's end: i = v · weight -> intrinsic, rewards += i, the two per-env accumulators
+__device__ __forceinline__ void rnd_finish_row(const GfRndRewardArgs& a, const int64_t n, const float v) {
+    const float i = v * a.weight;
+    G(a.intrinsic)[n] = i;
+    if (a.rewards) {
+        const float rw = G(a.rewards)[n];
+        if (a.acc_extrinsic) G(a.acc_extrinsic)[n] = G(a.acc_extrinsic)[n] + (double)rw;
+        G(a.rewards)[n] = rw + i;
+    }
+    if (a.acc_intrinsic) G(a.acc_intrinsic)[n] = G(a.acc_intrinsic)[n] + (double)i;
+}
+
+// (one instance, mlp_forward<true>: whether a net has a normaliser is its workgroup-uniform run-time test there; an instance
+// without it came out at 256 VGPRs with 64 B of scratch once the two walks and the row's end shared a kernel, this one at 249)
+__global__ __launch_bounds__(kMlpBlock, 2) void rnd_tile_kernel(const GfRndRewardArgs a, const int two_pass) {
+    constexpr bool NORM = true;
+    __shared__ MlpSmem sm;
+    __shared__ float s_emb[kMlpRows * kRndES];
+    const int64_t N = a.num_envs;
+    const int64_t row0 = (int64_t)blockIdx.x * kMlpRows;
+
+    const int E = mlp_forward<NORM>(sm, a.target, row0, N);
+    for (int e = (int)threadIdx.x; e < kMlpRows * E; e += kMlpBlock) {
+        const int row = e / E, c = e - row * E;
+        s_emb[row * kRndES + c] = sm.x[row * kMlpXS + c];
+    }
+    __syncthreads();   // (the predictor's first layer stages its input over x)
+    mlp_forward<NORM>(sm, a.predictor, row0, N);
+
+    if (threadIdx.x >= GF_WAVE) return;   // wave 0 finishes the tile: lane r < 32 owns row r
+    const int lane = (int)threadIdx.x;
+    const int64_t n = row0 + lane;
+    const bool live = lane < kMlpRows && n < N;
+    float r = 0.0f;
+    if (live) {
+        const float* t = s_emb + lane * kRndES;
+        const float* p = sm.x + lane * kMlpXS;
+        double s = 0.0;
+        for (int j = 0; j < E; ++j) {
+            const float d = t[j] - p[j];
+            s += (double)d * (double)d;
+        }
+        r = (float)sqrt(s);
+    }
+    if (!two_pass) {
+        if (!live) return;
+        float v = r;
+        if (a.normalize) {   // (no update in this call: nobody writes the statistics)
+            const float sd = G(a.std)[0];
+            v = sd > 0.0f ? r / sd : r;
+        }
+        rnd_finish_row(a, n, v);
+        return;
+    }
+    float av = 0.0f;
+    if (live) {
+        av = a.first ? r : __fadd_rn(__fmul_rn(G(a.avg)[n], a.gamma), r);   // rsl_rl: avg * gamma + rew, two roundings
+        G(a.avg)[n] = av;
+        G(a.intrinsic)[n] = r;   // (raw: the scale launch reads it back)
+    }
+    const int64_t left = N - row0;
+    const double cnt = (double)(left < kMlpRows ? left : kMlpRows);
+    const double mean = wave_xor_sum(live ? (double)av : 0.0) / cnt;
+    const double dv = live ? (double)av - mean : 0.0;
+    const double m2 = wave_xor_sum(dv * dv);
+    if (lane != 0) return;
+    GF_GLOBAL double* ws = G(reinterpret_cast<double*>(a.workspace));
+    GF_GLOBAL double* rec = ws + kRndHead + 3 * (int64_t)blockIdx.x;
+    rec[0] = cnt;
+    rec[1] = mean;
+    rec[2] = m2;
+    if (blockIdx.x == 0) {   // the statistics as they were: the scale launch reads these, never the live ones
+        ws[0] = (double)G(a.mean)[0];
+        ws[1] = (double)G(a.var)[0];
+        ws[2] = (double)G(a.std)[0];
+        reinterpret_cast<GF_GLOBAL int64_t*>(ws)[3] = *G(a.count);
+    }
+}
+
+// the reward normaliser's update and the rows' end: every workgroup folds the P records the same way (records strided over the lanes,
+// the wave butterfly, the four waves in order), so all of them hold the same new std; workgroup 0 stores the statistics
+__global__ __launch_bounds__(kSumBlock) void rnd_scale_kernel(const GfRndRewardArgs a, const int64_t P) {
+    __shared__ double s_w[kSumBlock / GF_WAVE];
+    const GF_GLOBAL double* ws = G(reinterpret_cast<const double*>(a.workspace));
+    const GF_GLOBAL double* rec = ws + kRndHead;
+    const int64_t count = reinterpret_cast<const GF_GLOBAL int64_t*>(ws)[3];
+    float sd = (float)ws[2];
+    if (!(a.until >= 0 && count >= a.until)) {   // (workgroup-uniform)
+        const double m0 = rec[1];
+        double a1 = 0.0, a2 = 0.0, am = 0.0;
+        for (int64_t b = threadIdx.x; b < P; b += kSumBlock) {
+            const double nb = rec[3 * b], dm = rec[3 * b + 1] - m0;
+            a1 += nb * dm;
+            a2 += nb * (dm * dm);
+            am += rec[3 * b + 2];
+        }
+        a1 = block_sum_all(a1, s_w);
+        a2 = block_sum_all(a2, s_w);
+        am = block_sum_all(am, s_w);
+        // rsl_rl's update lines on the batch of N avg values, in float64 from the f32 state (as gf_obs_norm_update)
+        const double n = (double)a.num_envs;
+        const double t = a1 / n;
+        const double between = a2 - a1 * t;
+        const double mx = m0 + t;
+        const double vx = (am + (between > 0.0 ? between : 0.0)) / n;
+        const double mean = ws[0], var = ws[1];
+        const int64_t count1 = count + a.num_envs;
+        const double rate = n / (double)count1;
+        const double d = mx - mean;
+        const double mean1 = mean + rate * d;
+        const double var1 = var + rate * (vx - var + d * (mx - mean1));
+        const float var_f = (float)var1;
+        sd = sqrtf(var_f);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            G(a.mean)[0] = (float)mean1;
+            G(a.var)[0] = var_f;
+            G(a.std)[0] = sd;
+            *G(a.count) = count1;
+        }
+    }
+    const int64_t n = (int64_t)blockIdx.x * kSumBlock + threadIdx.x;
+    if (n >= a.num_envs) return;
+    const float r = G(a.intrinsic)[n];
+    rnd_finish_row(a, n, sd > 0.0f ? r / sd : r);   // rsl_rl: no eps in this division
+}
+
 // GF_OK and the net's widths, or the refusal
 static int mlp_check_net(const GfMlpNet& net, bool critic, int* out_width) {
     if (net.num_layers < 0 || net.num_layers > GF_MLP_MAX_LAYERS) return GF_E_RANGE;
@@ -460,5 +599,39 @@ extern "C" __attribute__((visibility("default"))) int gf_mlp_distill_act(const G
     hipStream_t s = (hipStream_t)stream;
     if (a->student.in_mean || a->teacher.in_mean) gf::klaunch(gf::mlp_distill_kernel<true>, grid, block, 0, s, *a, vec_rows);
     else gf::klaunch(gf::mlp_distill_kernel<false>, grid, block, 0, s, *a, vec_rows);
+    return gf::launch_status();
+}
+
+extern "C" __attribute__((visibility("default"))) int gf_rnd_reward(const GfRndRewardArgs* a, void* stream) {
+    if (!a) return GF_E_NULL;
+    if (a->num_envs < 0 || (a->normalize != 0 && a->normalize != 1) || (a->update != 0 && a->update != 1) || (a->first != 0 && a->first != 1))
+        return GF_E_RANGE;
+    int Et = 0, Ep = 0;
+    int rc = gf::mlp_check_net(a->target, false, &Et);
+    if (rc != GF_OK) return rc;
+    rc = gf::mlp_check_net(a->predictor, false, &Ep);
+    if (rc != GF_OK) return rc;
+    if (a->target.num_layers == 0 || a->predictor.num_layers == 0) return GF_E_UNSUPPORTED;
+    if (Et != Ep || a->target.num_inputs != a->predictor.num_inputs) return GF_E_RANGE;
+    for (int s = 0; s < a->target.num_inputs; ++s) {
+        const GfMlpSegment &x = a->target.inputs[s], &y = a->predictor.inputs[s];
+        if (x.rows != y.rows || x.width != y.width || x.row_stride != y.row_stride) return GF_E_RANGE;
+    }
+    if (!a->intrinsic || !a->workspace) return GF_E_NULL;
+    if (a->normalize && (!a->avg || !a->mean || !a->var || !a->std || !a->count)) return GF_E_NULL;
+    if (a->workspace_bytes < GF_RND_WORKSPACE_BYTES(a->num_envs) || (reinterpret_cast<uintptr_t>(a->workspace) & 7u) ||
+        (a->normalize && (reinterpret_cast<uintptr_t>(a->count) & 7u)))
+        return GF_E_RANGE;
+    if (a->num_envs == 0) return GF_OK;
+    const int64_t tiles = gf::mlp_tiles(a->num_envs);
+    if (tiles < 0) return GF_E_RANGE;
+    const int two_pass = a->normalize && a->update;
+    const dim3 grid((unsigned)tiles), block(gf::kMlpBlock);
+    hipStream_t s = (hipStream_t)stream;
+    gf::klaunch(gf::rnd_tile_kernel, grid, block, 0, s, *a, two_pass);
+    if (two_pass) {
+        const int64_t nb = (a->num_envs + gf::kSumBlock - 1) / gf::kSumBlock;
+        gf::klaunch(gf::rnd_scale_kernel, dim3((unsigned)nb), dim3(gf::kSumBlock), 0, s, *a, tiles);
+    }
     return gf::launch_status();
 }

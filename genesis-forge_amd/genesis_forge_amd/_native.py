@@ -467,6 +467,22 @@ class GfBcLossArgs(C.Structure):
                 ("out", P), ("sums", P), ("workspace", P), ("workspace_bytes", C.c_int64)]
 
 
+# random network distillation (learner.RndForward / RolloutStorage.intrinsic_reward): gf_rnd_reward, not in ABI_STRUCTS either
+GF_SIZEOF_RND_REWARD = 35
+
+
+def rnd_workspace_bytes(num_envs: int) -> int:
+    """GF_RND_WORKSPACE_BYTES: a header of four doubles, then {rows, mean, M2} per tile of GF_MLP_TILE_ROWS rows."""
+    return (4 + 3 * (-(-int(num_envs) // GF_MLP_TILE_ROWS))) * 8
+
+
+class GfRndRewardArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("target", GfMlpNet), ("predictor", GfMlpNet), ("weight", C.c_float), ("gamma", C.c_float),
+                ("normalize", C.c_int32), ("update", C.c_int32), ("first", C.c_int32), ("_pad", C.c_int32), ("avg", P), ("mean", P), ("var", P),
+                ("std", P), ("count", P), ("until", C.c_int64), ("rewards", P), ("intrinsic", P), ("acc_extrinsic", P), ("acc_intrinsic", P),
+                ("workspace", P), ("workspace_bytes", C.c_int64)]
+
+
 # the running observation statistics (learner.EmpiricalNormalization.update): gf_obs_norm_update, not in ABI_STRUCTS either
 GF_SIZEOF_OBS_NORM = 29
 GF_OBS_NORM_MAX_SETS = 2
@@ -731,7 +747,8 @@ class HipBackend(Backend):
                             ("gf_mlp_act", GF_SIZEOF_MLP_ACT, GfMlpActArgs), ("gf_obs_norm_update", GF_SIZEOF_OBS_NORM, GfObsNormArgs),
                             ("gf_rollout_frame_write", GF_SIZEOF_ROLLOUT_FRAME, GfRolloutFrameArgs),
                             ("gf_mirror_rows", GF_SIZEOF_MIRROR_ROWS, GfMirrorRowsArgs), ("gf_mirror_loss", GF_SIZEOF_MIRROR_LOSS, GfMirrorLossArgs),
-                            ("gf_mlp_distill_act", GF_SIZEOF_MLP_DISTILL, GfMlpDistillArgs), ("gf_bc_loss", GF_SIZEOF_BC_LOSS, GfBcLossArgs)):
+                            ("gf_mlp_distill_act", GF_SIZEOF_MLP_DISTILL, GfMlpDistillArgs), ("gf_bc_loss", GF_SIZEOF_BC_LOSS, GfBcLossArgs),
+                            ("gf_rnd_reward", GF_SIZEOF_RND_REWARD, GfRndRewardArgs)):
             n = self.lib.gf_sizeof(idx)
             if n != C.sizeof(st):
                 raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")
@@ -882,6 +899,7 @@ _LEARNER_ENTRIES = {
     "mlp_act": "learner.PolicyForward, learner.RolloutStorage.act_policy",
     "mlp_distill_act": "learner.DistillForward.act, learner.RolloutStorage.act_distill",
     "bc_loss": "learner.Distillation.update",
+    "rnd_reward": "learner.RndForward.reward, learner.RolloutStorage.intrinsic_reward",
 }
 
 

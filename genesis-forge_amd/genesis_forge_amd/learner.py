@@ -46,6 +46,12 @@ dependency and stays one; this module provides the two pieces of it that touch t
   actor.  ``RolloutStorage.act_distill`` runs both MLPs of a collection step, the sampling and the two storage rows in ONE
   ``gf_mlp_distill_act`` launch; an update walks ``RolloutStorage.step_batches()`` with one ``gf_bc_loss`` per time step and one
   ``gf_adam_step`` every ``gradient_length`` steps, and reads the device once.
+* :class:`RandomNetworkDistillation`, :class:`EmpiricalDiscountedVariationNormalization`, :class:`RndForward` — rsl_rl's curiosity
+  bonus (``algorithm.rnd_cfg``): a frozen random target and a trained predictor read an ``"rnd_state"`` observation group, the distance
+  of their outputs is an intrinsic reward.  ``RolloutStorage.intrinsic_reward`` adds it to the storage row of a collection step with
+  ONE ``gf_rnd_reward`` launch — both MLPs, the distance, the reward normaliser, the weight and the add; two launches with the
+  reward normaliser updating, no host read — and :class:`PPO` trains the predictor per minibatch (``group_rows_batch``,
+  ``gf_bc_loss``, an Adam of its own).
 """
 from __future__ import annotations
 
@@ -254,11 +260,13 @@ class RolloutStorage:
         # and the bootstrap are tracked as the serial of the transition they belong to.  The action noise has a Philox seed and
         # stream of its own (``seed()``): never the env's draws.
         self._serial = 0
-        self._pol_serial = self._boot_serial = -1
+        self._pol_serial = self._boot_serial = self._rnd_serial = self._proc_serial = -1
         self._act_seed: Optional[int] = None   # None: the env's seed (the kernel XORs GF_POLICY_SEED_TAG into it either way)
         self._act_stream = 0
         self._act_args = nat.GfPolicyActArgs()
         self._ep_args = nat.GfEpisodeArgs()
+        self._grp_args = nat.GfMinibatchArgs()   # group_rows_batch's own descriptor (the minibatch gather's keeps its normaliser state)
+        self.rnd_sums: Optional[torch.Tensor] = None   # [2, N] float64: per-env sums of the extrinsic / intrinsic rewards (intrinsic_reward)
 
     @staticmethod
     def _refuse_window(om) -> None:
@@ -313,7 +321,7 @@ class RolloutStorage:
         if self.observations is not None:
             self.observations[0].copy_(obs)
         self.step = 0
-        self._pol_serial = self._boot_serial = -1
+        self._pol_serial = self._boot_serial = self._rnd_serial = self._proc_serial = -1
 
     def _next_rows(self, a: nat.GfRolloutArgs) -> None:
         """Point the descriptor at transition ``step``'s rows and advance (wrapping into the next rollout)."""
@@ -669,6 +677,7 @@ class RolloutStorage:
             time_outs = _check_mask(time_outs, "time_outs", n, dev)
         if episodes is not None and episodes.num_envs != n:
             raise ValueError(f"episodes keeps {episodes.num_envs} envs, the storage {n}")
+        self._proc_serial = self._serial
         if time_outs is None and episodes is None:
             return
         if time_outs is not None and self.values is None:
@@ -698,6 +707,88 @@ class RolloutStorage:
                 episodes._calls += 1
         if time_outs is not None:
             self._boot_serial = self._serial
+
+    def intrinsic_reward(self, rnd, rnd_state) -> torch.Tensor:
+        """rsl_rl's RND lines of ``PPO.process_env_step`` for the transition the last ``env.step()`` wrote (row ``step - 1``):
+        ``rewards[t] += rnd.get_intrinsic_reward(rnd_state)``; returns the intrinsic reward ``[N]``.  ``rnd``: a :class:`RndForward` —
+        ONE ``gf_rnd_reward`` launch (two with the reward normaliser updating) for both MLPs, the distance, the normaliser, the weight
+        and the row's add, no host read — or the :class:`RandomNetworkDistillation` itself: its torch lines.  ``rnd_state``: the
+        post-step observation of the ``"rnd_state"`` group, a ``[N, W]`` tensor or its members as segments.  It comes after
+        ``env.step()`` and before ``process_env_step`` (the episode statistics then see extrinsic + intrinsic, as rsl_rl's
+        ``rewbuffer`` does, and the bootstrap is added to the sum); a second call for one transition raises ``RuntimeError``.
+        ``rnd_sums`` ``[2, N]`` (float64, allocated here) accumulates the extrinsic and the intrinsic reward per env — the runner's
+        per-iteration means; zero it to start a new window."""
+        if not isinstance(rnd, (RndForward, RandomNetworkDistillation)):
+            raise ValueError("intrinsic_reward(rnd, ...) takes a RndForward or a RandomNetworkDistillation")
+        if self.step < 1 or self._serial == 0:
+            raise RuntimeError("intrinsic_reward() follows the env.step() whose transition it completes")
+        t = self.step - 1
+        if self._rnd_serial == self._serial:
+            raise RuntimeError(f"the rewards of transition {t} already hold their intrinsic reward")
+        if self._proc_serial == self._serial or self._boot_serial == self._serial:
+            raise RuntimeError(f"intrinsic_reward() comes before process_env_step(): transition {t} is already processed")
+        n = self.env.num_envs
+        if self.rnd_sums is None:
+            self.rnd_sums = torch.zeros((2, n), device=self.device, dtype=torch.float64)
+        rewards = self.rewards[t]
+        if isinstance(rnd, RndForward):
+            _segments(rnd_state, "rnd_state", n, self.device, rnd.target)
+            out = rnd.reward(rnd_state, rewards, self.rnd_sums[0], self.rnd_sums[1], backend=self.env.backend)
+        else:
+            x = _cat(tuple(rnd_state) if isinstance(rnd_state, (list, tuple)) else rnd_state)
+            _check_f32(x, "rnd_state", {(n, rnd.num_states)}, self.device, window=True)
+            out = _rnd_reward_torch(rnd, x, rewards, self.rnd_sums[0], self.rnd_sums[1])
+        self._rnd_serial = self._serial
+        return out
+
+    def group_rows_batch(self, group: str, indices: torch.Tensor, normalizer=None) -> torch.Tensor:
+        """Rows ``indices`` (transition ``divmod(index, N)``, observation row ``t``) of observation group ``group`` as a fresh
+        ``[mb, W]`` tensor, its members side by side — through ``normalizer`` (an :class:`EmpiricalNormalization` of the group's
+        width; ``None`` / ``nn.Identity``: raw).  ONE ``gf_minibatch_gather`` launch over the members (frame-stored ones rebuilt from
+        their frames, as the minibatch gather does); plain indexing on a backend without it (the test-only CPU oracle).  What
+        :class:`PPO` reads the ``"rnd_state"`` rows of a minibatch with: ``MiniBatch`` keeps its ten fields."""
+        names = self.obs_groups.get(group)
+        if not names:
+            raise ValueError(f"the storage follows no observation group '{group}'")
+        w = sum(self._widths[k] for k in names)
+        norm = _as_normalizer(normalizer, w, "normalizer")
+        rows = self._flat_rows()
+        T, n = self.num_steps, self.env.num_envs
+        gather = getattr(self.env.backend, "minibatch_gather", None)
+        if gather is None:
+            for k in names:
+                if k in self.frames:
+                    rows[k] = self.observation_rows(k)[:T].reshape(T * n, self._widths[k])
+            x = rows[names[0]][indices] if len(names) == 1 else torch.cat([rows[k][indices] for k in names], dim=-1)
+            if norm is None:
+                return x
+            with torch.no_grad():
+                return norm(x)
+        if indices.dtype != torch.int64 or indices.dim() != 1 or not indices.is_contiguous() or indices.device != self.device:
+            raise ValueError(f"indices must be a contiguous int64 [mb] tensor on {self.device}")
+        m = int(indices.shape[0])
+        out = torch.empty((m, w), device=self.device, dtype=torch.float32)
+        a = self._grp_args
+        a.num_rows, a.num_src_rows, a.indices = m, T * n, indices.data_ptr()
+        col, at = 0, 0
+        members = list(names)
+        while at < len(members):   # (more members than one launch holds: a further launch)
+            part = members[at:at + nat.GF_MINIBATCH_MAX_FIELDS]
+            a.num_fields = len(part)
+            for f, k in zip(a.fields, part):
+                src = rows[k]
+                H = self.frames[k].shape[0] - T if k in self.frames else 0
+                f.src, f.dst, f.src_width, f.dst_width, f.dst_col = src.data_ptr(), out.data_ptr(), src.shape[1], w, col
+                f.history_len, f.frame_stride_rows = H, n if H else 0
+                if norm is None:
+                    f.mean = f.std = None
+                else:
+                    f.mean, f.std, f.eps = norm._mean.data_ptr() + 4 * col, norm._std.data_ptr() + 4 * col, norm.eps
+                col += self._widths[k]
+            gather(a)
+            at += len(part)
+        self._keep_grp = indices
+        return out
 
     def compute_returns(self, last_values: torch.Tensor, gamma: float = 0.99, lam: float = 0.95, normalize: bool = True) -> None:
         """``returns`` / ``advantages`` of the finished rollout (rsl_rl ``RolloutStorage.compute_returns``; gamma / lam as
@@ -752,14 +843,18 @@ class RolloutStorage:
     def _flat(self) -> dict:
         """Every stored array as its ``[T·N, w]`` source rows (views); a frame-stored manager as its ``[(T+H)·N, O]`` frames, of which
         row ``t·N + n`` is the OLDEST frame of observation row ``t`` (its newer frames lie multiples of N rows further on)."""
+        per = {k: getattr(self, k).flatten(0, 1) for k in _MB_FIELDS}   # ([T·N] or [T·N, A])
+        return self._flat_rows(), per
+
+    def _flat_rows(self) -> dict:
+        """The observation half of ``_flat``: a storage without policy rows has it too."""
         T, n = self.num_steps, self.env.num_envs
         rows = {name: r[:T].view(T * n, r.shape[2]) for name, r in self.group_rows.items()}
         if self.obs_name not in rows and self.observations is not None:
             rows[self.obs_name] = self.observations[:T].view(T * n, self.obs_width)
         for name, F in self.frames.items():
             rows[name] = F.view(F.shape[0] * n, F.shape[2])
-        per = {k: getattr(self, k).flatten(0, 1) for k in _MB_FIELDS}   # ([T·N] or [T·N, A])
-        return rows, per
+        return rows
 
     def _gather(self, idx: torch.Tensor, obs_norm=None, critic_norm=None) -> MiniBatch:
         rows, per = self._flat()
@@ -1133,6 +1228,127 @@ def _mlp(sizes) -> torch.nn.Sequential:
         if i < len(sizes) - 2:
             layers.append(torch.nn.ELU())
     return torch.nn.Sequential(*layers)
+
+
+class EmpiricalDiscountedVariationNormalization(torch.nn.Module):
+    """rsl_rl's ``EmpiricalDiscountedVariationNormalization``: a reward is divided by the running std of a per-env discounted sum of
+    the rewards seen so far.  ``emp_norm`` is an :class:`EmpiricalNormalization` of width 1 (its buffers are the state dict);
+    ``avg`` ``[N]`` is the discounted sum — not part of the state dict: ``None`` until the first call, and again after a load.
+    Training mode: ``avg = rew`` on the first call, ``avg * gamma + rew`` after it, then ``emp_norm`` is updated with the ``N`` values
+    of ``avg`` as one batch (``until`` included).  Either mode: ``rew / emp_norm._std`` if that std is positive, else ``rew`` — no eps
+    in the division.  ``gamma`` is the normaliser's own, not PPO's.  This ``forward`` is the torch path (one host read, the ``if``);
+    the HIP path is ``gf_rnd_reward`` (:class:`RndForward`), which reads ``avg`` and the buffers in place."""
+
+    def __init__(self, shape=(), eps: float = 1e-2, gamma: float = 0.99, until: Optional[int] = None):
+        super().__init__()
+        self.emp_norm = EmpiricalNormalization(1, eps=eps, until=until)
+        self.gamma = float(gamma)
+        self.avg: Optional[torch.Tensor] = None
+
+    def forward(self, rew: torch.Tensor) -> torch.Tensor:
+        if self.training:
+            with torch.no_grad():
+                self.avg = rew.clone() if self.avg is None else self.avg * self.gamma + rew
+                self.emp_norm._update_torch(self.avg.reshape(-1, 1))
+        std = self.emp_norm._std.reshape(())
+        return rew / std if std > 0 else rew
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self.avg = None   # (the discounted sums are not in the state dict: they start again, as a fresh module's)
+        return super()._load_from_state_dict(*args, **kwargs)
+
+
+_RND_SCHEDULE_KEYS = {"constant": (), "step": ("final_step", "final_value"), "linear": ("initial_step", "final_step", "final_value")}
+
+
+class RandomNetworkDistillation(torch.nn.Module):
+    """rsl_rl's ``RandomNetworkDistillation``: a frozen random ``target`` MLP and a trained ``predictor`` MLP read the ``rnd_state``
+    observation; ``‖target(x) − predictor(x)‖₂`` per env is the intrinsic reward (``get_intrinsic_reward``), scaled by ``weight``.
+
+    ``predictor`` / ``target``: ``Linear`` + ``ELU``, nothing after the last layer (only ``activation="elu"``; a hidden width of ``-1``
+    means ``num_states``); the target is in eval mode with ``requires_grad=False`` whatever ``train()`` is given.
+    ``state_normalization``: an :class:`EmpiricalNormalization` ``(num_states, until=10**8)`` in front of both nets, updated by
+    ``update_normalization(rnd_state)``; ``reward_normalization``: an :class:`EmpiricalDiscountedVariationNormalization`
+    ``(eps=1e-2, gamma=0.99, until=10**8)`` behind the distance; ``nn.Identity`` otherwise, as rsl_rl.
+    ``weight_schedule``: ``None`` / ``{"mode": "constant"}``; ``{"mode": "step", "final_step", "final_value"}`` — the initial weight
+    while ``update_counter < final_step``, then ``final_value``; ``{"mode": "linear", "initial_step", "final_step", "final_value"}``.
+    The weight is a Python float computed on the host from ``update_counter`` (one more per ``get_intrinsic_reward``).
+
+    The methods here are the torch path (CPU tensors, the oracle backend, ``forward="torch"``); :class:`RndForward` is the HIP one."""
+
+    def __init__(self, num_states: int, num_outputs: int, predictor_hidden_dims: Sequence[int], target_hidden_dims: Sequence[int],
+                 activation: str = "elu", weight: float = 0.0, state_normalization: bool = False, reward_normalization: bool = False,
+                 weight_schedule: Optional[dict] = None):
+        super().__init__()
+        if activation != "elu":
+            raise ValueError(f"RandomNetworkDistillation: activation={activation!r} is not supported (only 'elu')")
+        self.num_states, self.num_outputs = int(num_states), int(num_outputs)
+        if self.num_states < 1 or self.num_outputs < 1:
+            raise ValueError("RandomNetworkDistillation: num_states and num_outputs must be >= 1")
+        dims = lambda hidden: [self.num_states if int(h) == -1 else int(h) for h in hidden]
+        self.predictor = _mlp([self.num_states, *dims(predictor_hidden_dims), self.num_outputs])
+        self.target = _mlp([self.num_states, *dims(target_hidden_dims), self.num_outputs])
+        for p in self.target.parameters():
+            p.requires_grad_(False)
+        self.initial_weight = self.weight = float(weight)
+        self.weight_schedule = self._check_schedule(weight_schedule)
+        self.state_normalization, self.reward_normalization = bool(state_normalization), bool(reward_normalization)
+        self.state_normalizer = EmpiricalNormalization(self.num_states, until=10 ** 8) if state_normalization else torch.nn.Identity()
+        self.reward_normalizer = (EmpiricalDiscountedVariationNormalization((), until=10 ** 8) if reward_normalization
+                                  else torch.nn.Identity())
+        self.update_counter = 0
+        self.target.eval()
+
+    @staticmethod
+    def _check_schedule(sched) -> Optional[dict]:
+        if sched is None:
+            return None
+        if not isinstance(sched, dict) or sched.get("mode") not in _RND_SCHEDULE_KEYS:
+            raise ValueError(f"RandomNetworkDistillation: weight_schedule={sched!r} needs a 'mode' of {sorted(_RND_SCHEDULE_KEYS)}")
+        want = _RND_SCHEDULE_KEYS[sched["mode"]]
+        missing = [k for k in want if k not in sched]
+        bad = sorted(k for k in sched if k != "mode" and k not in want)
+        if missing or bad:
+            raise ValueError(f"RandomNetworkDistillation: weight_schedule mode {sched['mode']!r} takes {list(want)}"
+                             f"{'; missing ' + str(missing) if missing else ''}{'; unknown ' + str(bad) if bad else ''}")
+        if sched["mode"] == "linear" and not int(sched["final_step"]) > int(sched["initial_step"]):
+            raise ValueError("RandomNetworkDistillation: weight_schedule 'linear' needs final_step > initial_step")
+        return dict(sched)
+
+    def _scheduled_weight(self) -> float:
+        s, step, w0 = self.weight_schedule, self.update_counter, self.initial_weight
+        if s is None or s["mode"] == "constant":
+            return w0
+        if s["mode"] == "step":
+            return w0 if step < s["final_step"] else float(s["final_value"])
+        if step < s["initial_step"]:
+            return w0
+        if step > s["final_step"]:
+            return float(s["final_value"])
+        return w0 + (float(s["final_value"]) - w0) * (step - s["initial_step"]) / (s["final_step"] - s["initial_step"])
+
+    def _advance(self) -> float:
+        """The host half of ``get_intrinsic_reward``: ``update_counter += 1`` and the schedule's weight for this call."""
+        self.update_counter += 1
+        self.weight = self._scheduled_weight()
+        return self.weight
+
+    def update_normalization(self, rnd_state) -> None:
+        if isinstance(self.state_normalizer, EmpiricalNormalization):
+            self.state_normalizer.update(rnd_state)
+
+    def get_intrinsic_reward(self, rnd_state: torch.Tensor) -> torch.Tensor:
+        weight = self._advance()
+        with torch.no_grad():
+            x = self.state_normalizer(rnd_state)
+            r = torch.linalg.norm(self.target(x) - self.predictor(x), dim=1)
+            r = self.reward_normalizer(r)
+        return r * weight
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        self.target.eval()
+        return self
 
 
 class _ActionStd:
@@ -1579,6 +1795,102 @@ class DistillForward(_MlpForward):
         return actions, teacher
 
 
+def _rnd_reward_torch(rnd: "RandomNetworkDistillation", rnd_state: torch.Tensor, rewards=None, acc_extrinsic=None, acc_intrinsic=None) -> torch.Tensor:
+    """rsl_rl's lines: ``get_intrinsic_reward`` and ``rewards += intrinsic``, with ``gf_rnd_reward``'s two per-env accumulators."""
+    intrinsic = rnd.get_intrinsic_reward(rnd_state)
+    with torch.no_grad():
+        if rewards is not None:
+            if acc_extrinsic is not None:
+                acc_extrinsic += rewards.to(torch.float64)
+            rewards.copy_(rewards + intrinsic)
+        if acc_intrinsic is not None:
+            acc_intrinsic += intrinsic.to(torch.float64)
+    return intrinsic
+
+
+class RndForward:
+    """The target and the predictor of a :class:`RandomNetworkDistillation` as ``gf_rnd_reward`` reads them — the counterpart of
+    :class:`PolicyForward`, under its rules: the structure is checked once, the weight addresses, the state normaliser and the reward
+    normaliser's buffers are looked up at every call (:class:`PPO` re-seats the predictor's parameters into a flat buffer of its own).
+
+    ``reward(rnd_state, rewards=None)``: ``rnd.get_intrinsic_reward(rnd_state)`` as a fresh ``[N]`` tensor — both MLPs, the distance,
+    the reward normaliser (its update included, in training mode) and the weight in ONE launch, two with the reward normaliser
+    updating, and no host read; ``rewards`` (``[N]``, contiguous) is added to in place by the same launch, ``acc_extrinsic`` /
+    ``acc_intrinsic`` (``[N]`` float64) accumulate the two terms per env.  ``rnd_state``: a ``[N, W]`` tensor or up to four segments.
+    The embeddings are ``gf_mlp_act``'s fma chains, the normaliser's update is evaluated in float64: within rounding of the module's
+    torch lines, not bit for bit.  ``update_counter`` and the schedule's weight advance on the host, as in the module.  For CPU
+    tensors and on a backend without the entry point (the test-only CPU oracle) the module's own lines run."""
+
+    def __init__(self, rnd: "RandomNetworkDistillation"):
+        if not isinstance(rnd, RandomNetworkDistillation):
+            raise ValueError("RndForward(rnd) takes a RandomNetworkDistillation")
+        self.rnd = rnd
+        self.target = _walk_mlp(rnd.target, "target", nat.GF_MLP_MAX_ACTIONS, "RndForward")
+        self.predictor = _walk_mlp(rnd.predictor, "predictor", nat.GF_MLP_MAX_ACTIONS, "RndForward")
+        self._state_norm()
+        self._args = nat.GfRndRewardArgs()
+        self._ws = self._avg_scratch = None
+
+    def _state_norm(self) -> Optional[EmpiricalNormalization]:
+        return _as_normalizer(self.rnd.state_normalizer, self.rnd.num_states, "RndForward: rnd.state_normalizer")
+
+    def reward(self, rnd_state, rewards: Optional[torch.Tensor] = None, acc_extrinsic: Optional[torch.Tensor] = None,
+               acc_intrinsic: Optional[torch.Tensor] = None, backend=None) -> torch.Tensor:
+        rnd = self.rnd
+        segs = _segments(rnd_state, "rnd_state", None, None, self.target)
+        n, dev = int(segs[0].shape[0]), segs[0].device
+        if rewards is not None:
+            _check_f32(rewards, "rewards", {(n,)}, dev)
+        for acc, name in ((acc_extrinsic, "acc_extrinsic"), (acc_intrinsic, "acc_intrinsic")):
+            if acc is not None and (acc.dtype != torch.float64 or tuple(acc.shape) != (n,) or acc.device != dev or not acc.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float64 [{n}] tensor on {dev}")
+        backend = nat.get_backend() if backend is None else backend
+        fn = getattr(backend, "rnd_reward", None) if dev.type == "cuda" else None
+        if fn is None:
+            return _rnd_reward_torch(rnd, _cat(segs), rewards, acc_extrinsic, acc_intrinsic)
+        weight = rnd._advance()
+        out = torch.empty(n, device=dev, dtype=torch.float32)
+        a = self._args
+        a.num_envs = n
+        norm = self._state_norm()
+        _fill_net(a.target, self.target, segs, norm)
+        _fill_net(a.predictor, self.predictor, segs, norm)
+        a.weight = weight
+        need = nat.rnd_workspace_bytes(n) // 8
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, device=dev, dtype=torch.float64)
+        rn = rnd.reward_normalizer
+        if isinstance(rn, EmpiricalDiscountedVariationNormalization):
+            emp = rn.emp_norm
+            a.normalize, a.update, a.gamma = 1, 1 if rn.training else 0, rn.gamma
+            if rn.training:
+                if rn.avg is not None and (tuple(rn.avg.shape) != (n,) or rn.avg.device != dev or not rn.avg.is_contiguous()):
+                    raise ValueError(f"RndForward: the reward normaliser keeps {tuple(rn.avg.shape)} discounted sums on {rn.avg.device}; "
+                                     f"this call has {n} envs on {dev}")
+                a.first = 1 if rn.avg is None else 0
+                if rn.avg is None:   # (the first call writes every element)
+                    rn.avg = torch.empty(n, device=dev, dtype=torch.float32)
+                avg = rn.avg
+            else:   # (eval mode: avg is neither read nor written; the descriptor still wants an address)
+                a.first = 0
+                if self._avg_scratch is None or self._avg_scratch.numel() != n or self._avg_scratch.device != dev:
+                    self._avg_scratch = torch.zeros(n, device=dev, dtype=torch.float32)
+                avg = self._avg_scratch
+            a.avg, a.mean, a.var, a.std, a.count = (t.data_ptr() for t in (avg, emp._mean, emp._var, emp._std, emp.count))
+            a.until = -1 if emp.until is None else int(emp.until)
+        else:
+            a.normalize = a.update = a.first = 0
+            a.avg = a.mean = a.var = a.std = a.count = None
+        a.rewards = None if rewards is None else rewards.data_ptr()
+        a.intrinsic = out.data_ptr()
+        a.acc_extrinsic = None if acc_extrinsic is None else acc_extrinsic.data_ptr()
+        a.acc_intrinsic = None if acc_intrinsic is None else acc_intrinsic.data_ptr()
+        a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel() * 8
+        self._keep = (segs, rewards, out)
+        fn(a)
+        return out
+
+
 class GradientAllReduce:
     """Average the gradients of ``params`` over the ranks of ``group`` with one collective.
 
@@ -1649,7 +1961,11 @@ _PPO_KEYS = ("clip_param", "desired_kl", "entropy_coef", "gamma", "lam", "learni
 _PPO_DEFAULTS = dict(clip_param=0.2, desired_kl=0.01, entropy_coef=0.01, gamma=0.99, lam=0.95, learning_rate=0.001, max_grad_norm=1.0,
                      num_learning_epochs=5, num_mini_batches=4, schedule="adaptive", use_clipped_value_loss=True, value_loss_coef=1.0)
 # rsl_rl keys whose default is all this class does: accepted with that value only
-_PPO_ONLY_DEFAULT = {"normalize_advantage_per_mini_batch": False, "rnd_cfg": None}
+_PPO_ONLY_DEFAULT = {"normalize_advantage_per_mini_batch": False}
+# rsl_rl's rnd_cfg: RandomNetworkDistillation's keyword arguments (num_states comes from the storage) and the predictor's learning rate
+_RND_KEYS = ("num_outputs", "predictor_hidden_dims", "target_hidden_dims", "activation", "weight", "state_normalization",
+             "reward_normalization", "weight_schedule", "learning_rate")
+_RND_REQUIRED = ("num_outputs", "predictor_hidden_dims", "target_hidden_dims")
 _SYMMETRY_KEYS = ("use_data_augmentation", "use_mirror_loss", "mirror_loss_coeff", "data_augmentation_func")   # rsl_rl's symmetry_cfg
 _ADAM_BETAS, _ADAM_EPS = (0.9, 0.999), 1e-8   # torch.optim.Adam's defaults, as rsl_rl constructs it
 
@@ -1812,8 +2128,19 @@ class _FlatAdam:
         self._calls += 1
 
 
+class _RndOptimizer(_FlatAdam):
+    """The predictor's Adam of a :class:`PPO` with an ``rnd_cfg``: its parameters in a flat buffer and a bucket of their own, a fixed
+    schedule and no clipping (the largest finite float as ``max_grad_norm``: a clip coefficient of exactly 1, Distillation's form)."""
+
+    def __init__(self, rnd: "RandomNetworkDistillation", learning_rate: float):
+        self.grad_sync = GradientAllReduce(rnd.predictor.parameters())   # (one rank: a bucket, never a collective)
+        self.max_grad_norm = torch.finfo(torch.float32).max
+        self.schedule, self.adaptive, self.desired_kl = "fixed", False, None
+        self._init_flat(float(learning_rate))
+
+
 class PPO(_FlatAdam):
-    """rsl_rl's ``PPO`` (non-recurrent, no RND) over a :class:`RolloutStorage` and an :class:`ActorCriticMLP`.
+    """rsl_rl's ``PPO`` (non-recurrent) over a :class:`RolloutStorage` and an :class:`ActorCriticMLP`.
 
     ``PPO(policy, storage, **train_cfg["algorithm"])`` takes the dict of ``examples/*/train.py`` as written (``class_name`` is
     ignored); unknown keys and unsupported values raise ``ValueError``.  ``grad_sync``: the :class:`GradientAllReduce` of a multi-rank
@@ -1846,12 +2173,27 @@ class PPO(_FlatAdam):
     loss ``MSE(actor(mirror(obs)), mirror(actor(obs)).detach())`` is one ``gf_mirror_loss``: on the ``mu`` of that forward when
     augmenting, on one extra actor forward of the mirrored rows otherwise; its gradient joins the update only with
     ``use_mirror_loss`` (``mirror_loss_coeff`` times), and ``update()`` returns its mean as ``"symmetry"`` either way.
+
+    ``rnd_cfg`` (rsl_rl's dict: :class:`RandomNetworkDistillation`'s keyword arguments and ``learning_rate``, default ``1e-3``) adds
+    random network distillation: ``self.rnd`` is the module, ``num_states`` the width of the storage's ``"rnd_state"`` observation
+    group.  The collection loop adds the intrinsic reward between ``update_normalization`` and ``process_env_step``::
+
+        ppo.rnd.update_normalization(rnd_state)
+        storage.intrinsic_reward(RndForward(ppo.rnd), rnd_state)      # rewards[t] += intrinsic: gf_rnd_reward
+
+    and every minibatch also trains the predictor: ``storage.group_rows_batch("rnd_state", indices, state normaliser)`` (one gather
+    launch; with augmentation the original rows only), the two nets' forward in torch, ``gf_bc_loss`` (mse) for
+    ``MSE(predictor(s), target(s))`` and its gradient, and a ``gf_adam_step`` of the predictor's own flat Adam — fixed schedule, no
+    clipping, one rank.  ``update()`` returns the mean loss as ``"rnd"``.  A storage without that group, a missing
+    ``num_outputs`` / ``predictor_hidden_dims`` / ``target_hidden_dims``, an unknown key, a bad ``weight_schedule``, another
+    activation than ``"elu"`` or a multi-rank ``grad_sync`` raises ``ValueError`` naming ``rnd_cfg``.
     """
 
     def __init__(self, policy: "ActorCriticMLP", storage: RolloutStorage, grad_sync: Optional[GradientAllReduce] = None, **algorithm):
         algorithm = dict(algorithm)
         algorithm.pop("class_name", None)
         symmetry_cfg = algorithm.pop("symmetry_cfg", None)
+        rnd_cfg = algorithm.pop("rnd_cfg", None)
         bad = [k for k in algorithm if k not in _PPO_KEYS and k not in _PPO_ONLY_DEFAULT]
         if bad:
             raise ValueError(f"PPO: unsupported algorithm keys {sorted(bad)}")
@@ -1880,6 +2222,7 @@ class PPO(_FlatAdam):
             raise ValueError("PPO needs a policy with act_mean(), evaluate() and a [A] std (or, with noise_std_type='log', log_std) parameter (ActorCriticMLP)")
         self.num_actions = int(std.numel())
         self.symmetry = self._parse_symmetry(symmetry_cfg)   # None, or {"func", "augment", "mirror", "coeff"}
+        self.rnd, rnd_lr = self._parse_rnd(rnd_cfg, grad_sync, std.device)   # None, or the RandomNetworkDistillation
         self.grad_sync = grad_sync if grad_sync is not None else GradientAllReduce(policy.parameters())
         sync = self.grad_sync
         ids = {id(p) for p in sync.params}
@@ -1888,7 +2231,10 @@ class PPO(_FlatAdam):
         self._init_flat(float(cfg["learning_rate"]))
         dev = self.params.device
         self._out = torch.zeros(nat.GF_PPO_OUT_COUNT, device=dev, dtype=torch.float32)   # surrogate, value_loss, entropy, kl_mean, loss
-        self._sums = torch.zeros(4, device=dev, dtype=torch.float64)                      # value_function, surrogate, entropy, symmetry
+        self._sums = torch.zeros(5, device=dev, dtype=torch.float64)                      # value_function, surrogate, entropy, symmetry, rnd
+        self._rnd_opt = None if self.rnd is None else _RndOptimizer(self.rnd, rnd_lr)
+        self._rnd_loss_args, self._rnd_key = nat.GfBcLossArgs(), None
+        self._rnd_out = torch.zeros(1, device=dev, dtype=torch.float32)
         self._mb_key = None
         self._loss_args = nat.GfPpoLossArgs()
         if self.symmetry is not None:   # the tables go up here, once: no copy from the host inside an update
@@ -1926,6 +2272,72 @@ class PPO(_FlatAdam):
         return {"func": fn, "augment": bool(cfg.get("use_data_augmentation", False)), "mirror": bool(cfg.get("use_mirror_loss", False)),
                 "coeff": float(cfg.get("mirror_loss_coeff", 0.0))}
 
+    def _parse_rnd(self, cfg, grad_sync, device):
+        """rsl_rl's ``rnd_cfg`` as ``(RandomNetworkDistillation on device, the predictor's lr)``, ``(None, None)`` without one, or
+        ``ValueError`` (always naming ``rnd_cfg``)."""
+        if cfg is None:
+            return None, None
+        if not isinstance(cfg, dict):
+            raise ValueError(f"PPO: rnd_cfg={cfg!r} must be a dict (or None)")
+        bad = sorted(k for k in cfg if k not in _RND_KEYS)
+        if bad:
+            raise ValueError(f"PPO: rnd_cfg has unsupported keys {bad} (honoured: {list(_RND_KEYS)})")
+        missing = [k for k in _RND_REQUIRED if k not in cfg]
+        if missing:
+            raise ValueError(f"PPO: rnd_cfg needs {missing}")
+        st = self.storage
+        if not st.obs_groups.get("rnd_state"):
+            raise ValueError("PPO: rnd_cfg needs a storage with an 'rnd_state' observation group (obs_groups={..., 'rnd_state': [...]})")
+        if grad_sync is not None and grad_sync.world > 1:
+            raise ValueError("PPO: rnd_cfg runs on one rank: the predictor's gradients are not averaged over a multi-rank grad_sync")
+        kwargs = {k: v for k, v in cfg.items() if k != "learning_rate"}
+        lr = float(cfg.get("learning_rate", 1e-3))
+        if not lr > 0.0:
+            raise ValueError(f"PPO: rnd_cfg learning_rate={cfg['learning_rate']!r} must be > 0")
+        try:
+            rnd = RandomNetworkDistillation(sum(st._widths[m] for m in st.obs_groups["rnd_state"]), **kwargs)
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"PPO: rnd_cfg: {e}") from e
+        return rnd.to(device), lr
+
+    def rnd_optimizer_state_dict(self) -> dict:
+        """rsl_rl's ``"rnd_optimizer_state_dict"``: ``torch.optim.Adam``'s format over ``rnd.predictor.parameters()``."""
+        return self._rnd_opt.optimizer_state_dict()
+
+    def load_rnd_optimizer_state_dict(self, sd: dict) -> None:
+        self._rnd_opt.load_optimizer_state_dict(sd)
+
+    def _rnd_step(self, backend, indices: torch.Tensor) -> None:
+        """rsl_rl PPO.update's RND lines for one minibatch: the predictor is regressed onto the target on the batch's rnd_state rows
+        (row ``t`` of the transitions, through the state normaliser) and its own Adam steps."""
+        rnd, opt = self.rnd, self._rnd_opt
+        opt.grad_sync.zero_grad()
+        norm = rnd.state_normalizer if isinstance(rnd.state_normalizer, EmpiricalNormalization) else None
+        s = self.storage.group_rows_batch("rnd_state", indices, norm)
+        pred = rnd.predictor(s)
+        with torch.no_grad():
+            tgt = rnd.target(s)
+        if getattr(backend, "bc_loss", None) is not None:
+            mb, E = int(pred.shape[0]), int(pred.shape[1])
+            if self._rnd_key != (mb, E):
+                self._rnd_grad = torch.empty((mb, E), device=pred.device, dtype=torch.float32)
+                self._rnd_ws = torch.empty(max(1, nat.bc_loss_workspace_bytes(mb) // 8), device=pred.device, dtype=torch.float64)
+                self._rnd_key = (mb, E)
+            a = self._rnd_loss_args
+            a.num_rows, a.num_actions, a.loss_type = mb, E, nat.GF_BC_LOSS_MSE
+            a.mu, a.target, a.grad = pred.data_ptr(), tgt.data_ptr(), self._rnd_grad.data_ptr()
+            a.out, a.sums = self._rnd_out.data_ptr(), self._sums.data_ptr() + 4 * 8
+            a.workspace, a.workspace_bytes = self._rnd_ws.data_ptr(), self._rnd_ws.numel() * 8
+            self._keep_rnd = (pred, tgt, s)
+            backend.bc_loss(a)
+            torch.autograd.backward(pred, self._rnd_grad)
+        else:   # (the test-only oracle backend) rsl_rl's lines with autograd
+            loss = torch.nn.functional.mse_loss(pred, tgt)
+            loss.backward()
+            with torch.no_grad():
+                self._sums[4].add_(loss.detach().to(torch.float64))
+        opt._adam_step(backend)
+
     def compute_returns(self, last_critic_obs: torch.Tensor) -> None:
         """rsl_rl ``PPO.compute_returns``: the critic's value of the bootstrap observation, then GAE over the storage.  The value is
         torch's forward (so results stay what they were); a loop that wants the one-launch forward passes
@@ -1936,7 +2348,7 @@ class PPO(_FlatAdam):
 
     def update(self, generator: Optional[torch.Generator] = None) -> Dict[str, float]:
         """``num_learning_epochs x num_mini_batches`` minibatches of ``storage.mini_batch_generator`` (``generator``: its randperm's);
-        returns rsl_rl 3.x's ``{"value_function", "surrogate", "entropy"}`` means — and ``"symmetry"`` with a ``symmetry_cfg`` — the one
+        returns rsl_rl 3.x's ``{"value_function", "surrogate", "entropy"}`` means — and ``"symmetry"`` with a ``symmetry_cfg``, ``"rnd"`` with an ``rnd_cfg`` — the one
         host read of the update."""
         self._sums.zero_()
         norms = self._normalizers()
@@ -1947,11 +2359,13 @@ class PPO(_FlatAdam):
         else:
             for batch in self._symmetry_batches(generator, norms):
                 self._minibatch_symmetry(batch, norms)
-        vf, surr, ent, symm = self._sums.tolist()
+        vf, surr, ent, symm, rnd = self._sums.tolist()
         k = self.num_learning_epochs * self.num_mini_batches
         out = {"value_function": vf / k, "surrogate": surr / k, "entropy": ent / k}
         if self.symmetry is not None:
             out["symmetry"] = symm / k
+        if self.rnd is not None:
+            out["rnd"] = rnd / k
         return out
 
     def _symmetry_batches(self, generator, norms) -> Iterator[MiniBatch]:
@@ -1984,6 +2398,8 @@ class PPO(_FlatAdam):
         sync.average()
         sync.wait()
         self._adam_step(backend)
+        if self.rnd is not None:
+            self._rnd_step(backend, b.indices)
 
     # -- one minibatch with a symmetry_cfg ---------------------------------------------------------------------------------------------
     def _minibatch_symmetry(self, b: MiniBatch, norms=(None, None)) -> None:
@@ -1999,6 +2415,8 @@ class PPO(_FlatAdam):
         sync.average()
         sync.wait()
         self._adam_step(backend)
+        if self.rnd is not None:
+            self._rnd_step(backend, b.indices)
 
     def _symmetry_torch(self, b: MiniBatch) -> None:
         """rsl_rl's lines through the MirrorSymmetry's ``__call__`` (plain torch): ``b`` carries raw observations, the policy's own

@@ -25,8 +25,8 @@ from typing import Callable, Optional
 import torch
 
 from . import gs
-from .learner import (ActorCriticMLP, DistillForward, Distillation, EpisodeStatistics, PolicyForward, PPO, RolloutStorage, StudentTeacherMLP,
-                      _cat, _policy_std)
+from .learner import (ActorCriticMLP, DistillForward, Distillation, EpisodeStatistics, PolicyForward, PPO, RndForward, RolloutStorage,
+                      StudentTeacherMLP, _cat, _policy_std)
 from .wrappers import RslRlWrapper
 
 CHECKPOINT_VERSION = 1   # of the "genesis_forge_amd" block of a checkpoint file
@@ -53,6 +53,15 @@ class OnPolicyRunner:
     between them by env count: the only measurements are the three sizes of profiles/r09_mlp_act.md — per collection step the HIP
     forward is 3.5 x faster than the torch forward at 4 096 envs, 1.4 x faster at 16 384 and 7 % slower at 65 536 — so the choice is
     the caller's.
+
+    ``algorithm.rnd_cfg`` (random network distillation, ``PPO``'s docstring): ``obs_groups`` needs an ``"rnd_state"`` group; every
+    collection step then runs ``alg.rnd.update_normalization(rnd_state)`` and ``store.intrinsic_reward(…, rnd_state)`` between
+    ``policy.update_normalization`` and ``process_env_step`` — ``forward="hip"``: ``gf_rnd_reward`` (one launch, two with the reward
+    normaliser, no host read); ``"torch"``: the module's lines (one host read per step with the reward normaliser).  The log record
+    gains ``"rnd"`` (the predictor's loss), ``"mean_intrinsic_reward"`` / ``"mean_extrinsic_reward"`` (per env-step of the iteration,
+    the weight included) and ``"rnd_weight"``; a checkpoint gains rsl_rl's ``"rnd_state_dict"`` / ``"rnd_optimizer_state_dict"`` and the
+    module's ``update_counter`` in this package's block.  The reward normaliser's per-env discounted sums are not saved: they start
+    again after a load, as rsl_rl's do.
 
     ``action_noise``: a CPU ``torch.Generator``; when given, each step's ``[N, A]`` standard normals are drawn from it and passed as
     ``noise=``.  Required on a backend that cannot draw (the test-only CPU oracle: ``act`` raises ``RuntimeError`` otherwise), optional on
@@ -104,6 +113,7 @@ class OnPolicyRunner:
         policy = policy.to(self.device)
         self.alg = PPO(policy, store, **train_cfg["algorithm"])
         self._fwd = PolicyForward(policy) if self.forward == "hip" else None
+        self._rnd_fwd = RndForward(self.alg.rnd) if self.forward == "hip" and self.alg.rnd is not None else None
 
     # -- observations ---------------------------------------------------------------------------------------------------------------
     def _group(self, names, obs: torch.Tensor, extras: dict):
@@ -129,6 +139,7 @@ class OnPolicyRunner:
         """``num_steps_per_env`` steps: act -> step -> update_normalization -> process_env_step; returns the last (obs, extras)."""
         store, ppo, policy, env = self.storage, self.alg, self.alg.policy, self.env
         n, A = store.env.num_envs, ppo.num_actions
+        rnd = ppo.rnd
         for _ in range(self.num_steps_per_env):
             x, cx = self._inputs(obs, extras)
             if self._fwd is not None:
@@ -142,6 +153,10 @@ class OnPolicyRunner:
             obs, _rew, _terminated, truncated, extras = env.step(actions)
             x, cx = self._inputs(obs, extras)
             policy.update_normalization(x, cx)
+            if rnd is not None:   # rsl_rl PPO.process_env_step: the intrinsic reward of the post-step state joins the row first
+                rs = self._group(store.obs_groups["rnd_state"], obs, extras)
+                rnd.update_normalization(rs)
+                store.intrinsic_reward(rnd if self._rnd_fwd is None else self._rnd_fwd, rs)
             store.process_env_step(truncated, gamma=ppo.gamma, episodes=stats)
         return obs, extras
 
@@ -176,6 +191,8 @@ class OnPolicyRunner:
         start = self.current_learning_iteration
         for it in range(start, start + int(num_learning_iterations)):
             t0 = time.perf_counter()
+            if store.rnd_sums is not None:
+                store.rnd_sums.zero_()
             obs, extras = self._collect(obs, extras, stats)
             self._returns(obs, extras)
             t1 = time.perf_counter()
@@ -215,6 +232,10 @@ class OnPolicyRunner:
                   "steps_per_second": steps / max(collection_s + learn_s, 1e-9), "collection_time": collection_s, "learn_time": learn_s}
         if "symmetry" in losses:   # (only with algorithm.symmetry_cfg: records without one keep their keys)
             record["symmetry"] = losses["symmetry"]
+        if "rnd" in losses:        # (only with algorithm.rnd_cfg)
+            extrinsic, intrinsic = self.storage.rnd_sums.sum(dim=1).tolist()
+            record.update({"rnd": losses["rnd"], "mean_intrinsic_reward": intrinsic / steps, "mean_extrinsic_reward": extrinsic / steps,
+                           "rnd_weight": self.alg.rnd.weight})
         self.last_log = record
         if self.log_dir is not None:
             with open(os.path.join(self.log_dir, "progress.jsonl"), "a") as f:
@@ -228,7 +249,7 @@ class OnPolicyRunner:
         version, the storage's action-noise seed and stream, the permutation generator's state and, where the runner draws its noise
         from ``action_noise``, that generator's state."""
         store = self.storage
-        torch.save({
+        saved = {
             "model_state_dict": {k: v.detach().clone() for k, v in self.alg.policy.state_dict().items()},
             "optimizer_state_dict": self.alg.optimizer_state_dict(),
             "iter": self.current_learning_iteration,
@@ -236,7 +257,13 @@ class OnPolicyRunner:
             "genesis_forge_amd": {"version": CHECKPOINT_VERSION, "act_seed": store._act_seed, "act_stream": store._act_stream,
                                   "generator_state": self._generator.get_state(),
                                   "action_noise_state": None if self.action_noise is None else self.action_noise.get_state()},
-        }, path)
+        }
+        rnd = getattr(self.alg, "rnd", None)
+        if rnd is not None:   # rsl_rl's two keys, and the schedule's counter in this package's block
+            saved["rnd_state_dict"] = {k: v.detach().clone() for k, v in rnd.state_dict().items()}
+            saved["rnd_optimizer_state_dict"] = self.alg.rnd_optimizer_state_dict()
+            saved["genesis_forge_amd"]["rnd_update_counter"] = rnd.update_counter
+        torch.save(saved, path)
 
     def load(self, path: str, load_optimizer: bool = True):
         """rsl_rl's ``load``: the policy (copied in place, so the parameters stay views of ``PPO``'s flat buffer — checked), the optimizer
@@ -246,6 +273,16 @@ class OnPolicyRunner:
         ppo = self.alg
         ppo.policy.load_state_dict(loaded["model_state_dict"])
         self._check_flat()
+        if ppo.rnd is not None:
+            if "rnd_state_dict" not in loaded:
+                raise ValueError(f"{self._NAME}.load: the runner has an rnd_cfg, the checkpoint no 'rnd_state_dict'")
+            ppo.rnd.load_state_dict(loaded["rnd_state_dict"])
+            if load_optimizer:
+                ppo.load_rnd_optimizer_state_dict(loaded["rnd_optimizer_state_dict"])
+            ours = loaded.get("genesis_forge_amd") or {}
+            if "rnd_update_counter" in ours:
+                ppo.rnd.update_counter = int(ours["rnd_update_counter"])
+                ppo.rnd.weight = ppo.rnd._scheduled_weight()
         return self._load_rest(loaded, load_optimizer)
 
     def _check_flat(self) -> None:
@@ -293,9 +330,13 @@ class OnPolicyRunner:
 
     def train_mode(self) -> None:
         self.alg.policy.train()
+        if getattr(self.alg, "rnd", None) is not None:
+            self.alg.rnd.train()
 
     def eval_mode(self) -> None:
         self.alg.policy.eval()
+        if getattr(self.alg, "rnd", None) is not None:
+            self.alg.rnd.eval()
 
 
 class DistillationRunner(OnPolicyRunner):

@@ -1160,6 +1160,64 @@ typedef struct GfMlpDistillArgs {
 } GfMlpDistillArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * The curiosity bonus of a collection step (rsl_rl RandomNetworkDistillation.get_intrinsic_reward and the `rewards += intrinsic` of
+ * PPO.process_env_step): a frozen random `target` MLP and a trained `predictor` MLP read the same rnd_state rows, the distance of
+ * their outputs is the intrinsic reward.  rsl_rl spends about twenty small launches and one host read (`if std > 0`) on it;
+ * gf_rnd_reward is ONE launch without the reward normaliser (or with it in eval mode) and TWO with it updating, no host read.
+ *     x       = (rnd_state - in_mean) / (in_std + in_eps)             (the state normaliser: each net's in_mean / in_std / in_eps)
+ *     t, p    = target(x), predictor(x)                               (gf_mlp_act's k-ascending fma chains: a row's embedding is the
+ *                                                                      `mean` of a gf_mlp_act launch with that net as actor, bit for bit)
+ *     r[n]    = (float)sqrt(Σ_j (double)(t[n,j] - p[n,j])²)           (d_j one f32 subtraction; j ascending; the sum in double)
+ * normalize == 0:  i = r · weight.
+ * normalize == 1 (rsl_rl EmpiricalDiscountedVariationNormalization), update == 1 (training mode):
+ *     avg[n]  = first ? r[n] : avg[n]·gamma + r[n]                    (one f32 multiply, one f32 add, not contracted)
+ *     unless until >= 0 and count >= until: mean / var / std / count take EmpiricalNormalization.update's lines on the N values of
+ *     avg as one batch (gf_obs_norm_update's arithmetic: batch moments and the update in float64, rounded to f32 once; std = sqrtf(var))
+ *   then, and with update == 0 at once (avg and the statistics are not touched):
+ *     i = (std > 0 ? r / std : r) · weight                            (the std after the update; no eps in this division)
+ * Either way:  intrinsic[n] = i;  with rewards != NULL:  acc_extrinsic[n] += rewards[n] (where given), rewards[n] = rewards[n] + i;
+ * acc_intrinsic[n] += i (where given).  The accumulators are per env: the caller's means need no reduction in the kernel.
+ *
+ * Launch 1 is gf_mlp_act's tile (GF_MLP_TILE_ROWS rows per workgroup, weights streamed, activations in LDS): the workgroup walks the
+ * target, keeps the tile's E outputs in a second LDS array, walks the predictor from the re-staged input; lane r finishes row r.
+ * With the normaliser updating it stores r in `intrinsic`, the new avg, one {rows, mean, M2} record of the tile's avg per workgroup
+ * and — workgroup 0 — the old mean / var / std / count in the workspace header.  Launch 2 (256 rows per workgroup): every workgroup
+ * folds the records in the same fixed order (gf_reduce.h) and applies the update from the header's snapshot, so all hold the same
+ * new std; workgroup 0 alone stores the statistics, nobody reads the live ones.  No atomics: bitwise reproducible.
+ * Refusals, before anything is launched: GF_E_NULL — args, a weight / bias / segment pointer, in_mean without in_std, intrinsic,
+ * workspace, avg / mean / var / std / count with normalize; GF_E_RANGE — num_envs < 0, normalize / update / first outside {0, 1},
+ * what gf_mlp_act ranges per net, output widths that differ, segment sets that differ (count, rows, width, row_stride), a workspace
+ * smaller than GF_RND_WORKSPACE_BYTES(N) or not 8-byte aligned, a count pointer not 8-byte aligned; GF_E_UNSUPPORTED — either net
+ * absent.  num_envs == 0 is a no-op.  No allocation, no copy, no synchronisation inside.  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+/* header of four doubles (the old mean, var, std, count) + {rows, mean, M2} per tile of GF_MLP_TILE_ROWS rows */
+#define GF_RND_WORKSPACE_BYTES(n) ((int64_t)(4 + 3 * (((int64_t)(n) + GF_MLP_TILE_ROWS - 1) / GF_MLP_TILE_ROWS)) * 8)
+
+typedef struct GfRndRewardArgs {
+    int64_t num_envs;           /* N >= 0; 0: nothing is launched */
+    GfMlpNet target;            /* the frozen net; output width E <= GF_MLP_MAX_ACTIONS */
+    GfMlpNet predictor;         /* the trained net: the same segments, output width E */
+    float weight;               /* the schedule's current weight (computed on the host, passed by value) */
+    float gamma;                /* the reward normaliser's own discount */
+    int32_t normalize;          /* 1: the reward normaliser divides by its std */
+    int32_t update;             /* 1 (with normalize): avg and the statistics are updated first (training mode) */
+    int32_t first;              /* 1 (with update): the first call — avg = r */
+    int32_t _pad;
+    float* avg;                 /* [N] per-env discounted sum, in and out (required with normalize) */
+    float* mean;                /* [1] running statistics of avg (required with normalize) */
+    float* var;                 /* [1] */
+    float* std;                 /* [1] */
+    int64_t* count;             /* one word (required with normalize) */
+    int64_t until;              /* >= 0: no update of the statistics once count >= until; negative: none */
+    float* rewards;             /* [N] the storage row, added to in place, or NULL */
+    float* intrinsic;           /* [N] out: the weighted intrinsic reward (required) */
+    double* acc_extrinsic;      /* [N] += rewards[n] before the add, or NULL */
+    double* acc_intrinsic;      /* [N] += intrinsic[n], or NULL */
+    void* workspace;            /* GF_RND_WORKSPACE_BYTES(N) bytes, 8-byte aligned (required) */
+    int64_t workspace_bytes;
+} GfRndRewardArgs;
+
+/* ------------------------------------------------------------------------------------------
  * The behaviour-cloning loss of one time step of a distillation update and its gradient (rsl_rl Distillation.update:
  * loss_fn(student mean, stored teacher actions) with loss_type "mse" or "huber", and its backward down to the student's output):
  *     d[n, j] = mu[n, j] - target[n, j]                                      (one rounding)
@@ -1289,7 +1347,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs, 31 GfMirrorRowsArgs, 32 GfMirrorLossArgs, 33 GfMlpDistillArgs, 34 GfBcLossArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs, 31 GfMirrorRowsArgs, 32 GfMirrorLossArgs, 33 GfMlpDistillArgs, 34 GfBcLossArgs, 35 GfRndRewardArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -1321,6 +1379,7 @@ int gf_mirror_loss(const GfMirrorLossArgs* a, void* stream);     /* symmetry los
 int gf_mlp_act(const GfMlpActArgs* a, void* stream);             /* actor + critic MLP forward on the f32 matrix cores, then gf_policy_act's sampling and rows, in one launch (rsl_rl ActorCritic.act / evaluate inside PPO.act) */
 int gf_mlp_distill_act(const GfMlpDistillArgs* a, void* stream); /* student + teacher MLP forward in one launch, the student sampled by gf_policy_act's row code (rsl_rl Distillation.act: StudentTeacher.act / evaluate) */
 int gf_bc_loss(const GfBcLossArgs* a, void* stream);             /* behaviour-cloning loss of one time step (mse / huber) and its gradient w.r.t. the student's mean (rsl_rl Distillation.update: loss_fn(actions, privileged_actions) and its backward) */
+int gf_rnd_reward(const GfRndRewardArgs* a, void* stream);       /* target + predictor MLP forward, their distance, the reward normaliser and the storage row's add in one launch (two with the normaliser updating) (rsl_rl RandomNetworkDistillation.get_intrinsic_reward inside PPO.process_env_step) */
 int gf_obs_norm_update(const GfObsNormArgs* a, void* stream);    /* running mean / var / std / count of up to two observation normalisers in two launches (rsl_rl EmpiricalNormalization.update) */
 int gf_adam_step(const GfAdamArgs* a, void* stream);             /* adaptive lr + clip_grad_norm_ + Adam.step over the flat bucket (rsl_rl PPO.update: the lr schedule, nn.utils.clip_grad_norm_, optimizer.step()) */
 

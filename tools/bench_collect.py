@@ -19,9 +19,14 @@ with one gf_obs_norm_update, ``fused_mlp`` normalises inside the gf_mlp_act laun
 ``--config gait``: the gait trainer (history_len 5, policy and critic managers, the asymmetric critic's ``obs_groups``).
 ``--history frames``: ``RolloutStorage(history="frames")`` — a history observation is stored once per frame (one gf_rollout_frame_write
 launch behind the step's own); ``--output window``: the ObservationManagers hand out strided history windows (``frames`` only).
+``--rnd``: random network distillation on top (``rnd_state`` = the policy observation, a 256-128 predictor and target with 16 outputs,
+both normalisers on): after env.step() every form updates the state normaliser and adds the intrinsic reward to the storage row —
+``rsl_rl`` with the module's torch lines (``RandomNetworkDistillation.get_intrinsic_reward``: one host read per step), ``fused`` /
+``fused_mlp`` with ``RolloutStorage.intrinsic_reward(RndForward(rnd), …)`` (gf_rnd_reward) — and one more line per size times the RND
+step ALONE in both forms, alternated in one process (``"form": "rnd_hip"`` / ``"rnd_torch"``).
 ``collector()`` builds one such loop and times batches of it, for scripts that alternate several forms in one process.
     python tools/bench_collect.py [--sizes 4096,16384,65536] [--forms rsl_rl,fused,fused_mlp] [--steps 240] [--warmup 48] [--reps 5] [--normalize] [--noise-std-type scalar|log]
-                                  [--config go2_cmd|gait] [--history rows|frames] [--output fresh|window]"""
+                                  [--config go2_cmd|gait] [--history rows|frames] [--output fresh|window] [--rnd]"""
 import argparse
 import json
 import os
@@ -34,7 +39,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "genesis-forge_amd"))
 import torch
 from genesis_forge_amd import gs, tasks
-from genesis_forge_amd.learner import ActorCriticMLP, EpisodeStatistics, PolicyForward, RolloutStorage
+from genesis_forge_amd.learner import (ActorCriticMLP, EpisodeStatistics, PolicyForward, RandomNetworkDistillation, RndForward, RolloutStorage,
+                                       _rnd_reward_torch)
 from genesis_forge_amd.managers import ObservationManager
 
 T = 24   # num_steps_per_env of examples/simple/train.py
@@ -68,13 +74,20 @@ class RslRlNormalizer(torch.nn.Module):
 
 
 GAIT_GROUPS = {"policy": ["policy"], "critic": ["policy", "critic"]}   # obs_groups of examples/gait_trainer/train.py
+RND_KWARGS = dict(num_outputs=16, predictor_hidden_dims=[256, 128], target_hidden_dims=[256, 128], weight=0.1, state_normalization=True,
+                  reward_normalization=True)
+
+
+def make_rnd(width: int) -> RandomNetworkDistillation:
+    torch.manual_seed(1)
+    return RandomNetworkDistillation(width, **RND_KWARGS).to(gs.device)
 
 
 class collector:
     """One collection loop: ``batch(steps)`` runs ``steps`` of it and returns µs per step (ending in a device synchronise)."""
 
     def __init__(self, n: int, form: str, normalize: bool = False, config: str = "go2_cmd", history: str = "rows", output: str = "fresh",
-                 noise_std_type: str = "scalar"):
+                 noise_std_type: str = "scalar", rnd: bool = False):
         old, ObservationManager.default_output = ObservationManager.default_output, output
         try:   # (the managers are created by env.config(), i.e. inside build())
             env = tasks.BASELINE_CONFIGS[config][1](n)
@@ -83,9 +96,12 @@ class collector:
             ObservationManager.default_output = old
         env.seed(1234)
         self.env, self.form, self.state = env, form, env.reset()
-        self.store = RolloutStorage(env, T, obs_groups=GAIT_GROUPS if config == "gait" else None, history=history).attach()
+        groups = dict(GAIT_GROUPS) if config == "gait" else ({"policy": ["policy"], "critic": ["policy"]} if rnd else None)
+        if rnd:
+            groups["rnd_state"] = ["policy"]
+        self.store = RolloutStorage(env, T, obs_groups=groups, history=history).attach()
         self.store.begin(*self.state)
-        self.step, self.stats, self.rewbuffer = _make_step(env, self.store, form, normalize, noise_std_type)
+        self.step, self.stats, self.rewbuffer = _make_step(env, self.store, form, normalize, noise_std_type, rnd)
 
     def batch(self, steps: int) -> float:
         obs, extras = self.state
@@ -104,8 +120,17 @@ class collector:
         return statistics.mean(self.rewbuffer) if self.rewbuffer else None
 
 
-def _make_step(env, store, form: str, normalize: bool, noise_std_type: str = "scalar"):
+def _make_step(env, store, form: str, normalize: bool, noise_std_type: str = "scalar", rnd: bool = False):
     n, A = env.num_envs, env.action_space.shape[0]
+    if rnd:   # rsl_rl PPO.process_env_step's RND lines, between the step and the bootstrap
+        module = make_rnd(store.obs_width)
+        reward_with = module if form == "rsl_rl" else RndForward(module)
+
+        def rnd_lines(obs):
+            module.update_normalization(obs)
+            store.intrinsic_reward(reward_with, obs)
+    else:
+        rnd_lines = lambda obs: None
     width = {m.name: int(m.observation_space.shape[0]) for m in env.managers["observation"]}
     critic = store.obs_groups["critic"]
     same = critic == store.obs_groups["policy"]
@@ -128,6 +153,7 @@ def _make_step(env, store, form: str, normalize: bool, noise_std_type: str = "sc
             obs, _rew, _term, trunc, extras = env.step(actions)
             if normalize:
                 policy.update_normalization(obs, parts(obs, extras))
+            rnd_lines(obs)
             store.process_env_step(trunc, gamma=gamma, episodes=stats)
             return obs, extras
     elif form == "fused_mlp":
@@ -139,6 +165,7 @@ def _make_step(env, store, form: str, normalize: bool, noise_std_type: str = "sc
             obs, _rew, _term, trunc, extras = env.step(actions)
             if normalize:
                 policy.update_normalization(obs, parts(obs, extras))
+            rnd_lines(obs)
             store.process_env_step(trunc, gamma=gamma, episodes=stats)
             return obs, extras
     else:
@@ -158,6 +185,7 @@ def _make_step(env, store, form: str, normalize: bool, noise_std_type: str = "sc
             if normalize:   # rsl_rl PPO.process_env_step: policy.update_normalization(obs)
                 actor_norm.update(obs)
                 critic_norm.update(cat(obs, extras))
+            rnd_lines(obs)
             store.add_policy(actions, values, log_prob, dist.mean, dist.stddev, time_outs=trunc, gamma=gamma)
             dones = term | trunc
             cur_reward_sum.add_(rew)   # OnPolicyRunner.learn
@@ -173,18 +201,54 @@ def _make_step(env, store, form: str, normalize: bool, noise_std_type: str = "sc
 
 
 def run(n: int, form: str, steps: int, warmup: int, reps: int, normalize: bool = False, config: str = "go2_cmd", history: str = "rows",
-        output: str = "fresh", noise_std_type: str = "scalar") -> dict:
-    c = collector(n, form, normalize, config, history, output, noise_std_type)
+        output: str = "fresh", noise_std_type: str = "scalar", rnd: bool = False) -> dict:
+    c = collector(n, form, normalize, config, history, output, noise_std_type, rnd)
     if warmup:
         c.batch(warmup)
     times = [c.batch(steps) for _ in range(reps)]
     out = {"tool": "bench_collect", "config": config, "history": history, "output": output, "num_envs": n, "form": form, "normalize": normalize,
-           "noise_std_type": noise_std_type,
+           "noise_std_type": noise_std_type, "rnd": rnd,
            "steps": steps, "warmup": warmup, "reps": reps,
            "us_per_step_best": round(min(times), 2), "us_per_step_median": round(statistics.median(times), 2),
            "recorded_step": c.env._trace is not None, "mean_reward": c.mean_reward()}
     c.store.detach()
     return out
+
+
+def run_rnd_alone(n: int, steps: int, warmup: int, reps: int, width: int = 48) -> list:
+    """The RND step alone — the state normaliser's update, the intrinsic reward, the row's add and the two accumulators — on fixed
+    random rnd_state rows: ``rnd_hip`` (gf_obs_norm_update + gf_rnd_reward) and ``rnd_torch`` (the module's lines) on copies of one
+    module, batches alternated."""
+    import copy
+
+    base = make_rnd(width)
+    modules = {"rnd_hip": base, "rnd_torch": copy.deepcopy(base)}
+    fwd = RndForward(base)
+    x = torch.randn(n, width, device=gs.device)
+    rows = {k: torch.zeros(n, device=gs.device) for k in modules}
+    acc = {k: torch.zeros(2, n, device=gs.device, dtype=torch.float64) for k in modules}
+
+    def batch(form: str, k: int) -> float:
+        m, r, a = modules[form], rows[form], acc[form]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(k):
+            m.update_normalization(x)
+            if form == "rnd_hip":
+                fwd.reward(x, r, a[0], a[1])
+            else:
+                _rnd_reward_torch(m, x, r, a[0], a[1])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / k * 1e6
+
+    times = {k: [] for k in modules}
+    for form in modules:
+        batch(form, warmup)
+    for _ in range(reps):
+        for form in modules:
+            times[form].append(batch(form, steps))
+    return [{"tool": "bench_collect", "num_envs": n, "form": form, "rnd_state_width": width, "steps": steps, "warmup": warmup, "reps": reps,
+             "us_per_step_best": round(min(t), 2), "us_per_step_median": round(statistics.median(t), 2)} for form, t in times.items()]
 
 
 def main() -> None:
@@ -199,6 +263,7 @@ def main() -> None:
     ap.add_argument("--history", default="rows", choices=["rows", "frames"], help="RolloutStorage(history=): rows, or one entry per frame")
     ap.add_argument("--output", default="fresh", choices=["fresh", "window"], help="what the ObservationManagers hand out")
     ap.add_argument("--noise-std-type", default="scalar", choices=["scalar", "log"], help="the policy's std parameter: std, or log_std")
+    ap.add_argument("--rnd", action="store_true", help="random network distillation: the intrinsic reward joins every step; the RND step alone is timed too")
     a = ap.parse_args()
     if a.output == "window" and a.history != "frames":
         raise SystemExit("--output window needs --history frames: a row storage copies contiguous observation rows")
@@ -209,7 +274,10 @@ def main() -> None:
         for form in a.forms.split(","):
             if form not in ("rsl_rl", "fused", "fused_mlp"):
                 raise SystemExit(f"unknown form {form!r}")
-            print(json.dumps(run(n, form, a.steps, a.warmup, a.reps, a.normalize, a.config, a.history, a.output, a.noise_std_type)), flush=True)
+            print(json.dumps(run(n, form, a.steps, a.warmup, a.reps, a.normalize, a.config, a.history, a.output, a.noise_std_type, a.rnd)), flush=True)
+        if a.rnd:
+            for line in run_rnd_alone(n, a.steps, a.warmup, a.reps):
+                print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@ PPO.update restated in torch (tests/rsl_rl_ppo.py: torch.optim.Adam, clip_grad_n
 
 usage: python tools/bench_update.py [--sizes go2_cmd:4096,go2_cmd:16384,go2_cmd:65536,gait:4096] [--steps 24] [--reps 7]
                                     [--forms rsl_rl,fused] [--out FILE] [--noise-std-type scalar|log]
-                                    [--symmetry none|augment|mirror|both]
+                                    [--symmetry none|augment|mirror|both] [--rnd]
 
 Per size: one rollout of T steps is collected with act / process_env_step by the reference policy (ELU MLPs 512-256-128, as
 examples/*/train.py) and its returns computed; then every rep runs each form once, alternating, from the same initial weights,
@@ -16,7 +16,9 @@ median ms per update over the reps (after one warm-up update per form), and the 
 that differ only in ``--reps`` differ by exactly that many updates, which gives the dispatches per minibatch.
 ``--noise-std-type log``: the policy holds ``log_std`` (the torch restatement reads ``std = exp(log_std)`` through a property).
 ``--symmetry``: both forms get rsl_rl's ``symmetry_cfg`` with the Go2 left/right mirror (``go2_mirror``) — ``augment``: data
-augmentation, ``mirror``: the mirror loss, ``both``; the torch form is then tests/rsl_rl_symmetry.py."""
+augmentation, ``mirror``: the mirror loss, ``both``; the torch form is then tests/rsl_rl_symmetry.py.
+``--rnd``: both forms get rsl_rl's ``rnd_cfg`` (``rnd_state`` = the policy observation, a 256-128 predictor and target with 16
+outputs, both normalisers on): every minibatch also trains the predictor; the torch form is then tests/rsl_rl_rnd.py."""
 import argparse
 import copy
 import json
@@ -34,6 +36,16 @@ import torch  # noqa: E402
 ALGO = dict(class_name="PPO", clip_param=0.2, desired_kl=0.01, entropy_coef=0.01, gamma=0.99, lam=0.95, learning_rate=0.001, max_grad_norm=1.0,
             num_learning_epochs=5, num_mini_batches=4, schedule="adaptive", use_clipped_value_loss=True, value_loss_coef=1.0)
 GAIT_GROUPS = {"policy": ["policy"], "critic": ["policy", "critic"]}
+RND_CFG = dict(num_outputs=16, predictor_hidden_dims=[256, 128], target_hidden_dims=[256, 128], weight=0.1, state_normalization=True,
+               reward_normalization=True, learning_rate=1e-3)
+
+
+def obs_groups(config: str, rnd: bool):
+    """The storage's observation groups: the gait trainer's asymmetric critic, and the policy observation as ``rnd_state`` with --rnd."""
+    groups = dict(GAIT_GROUPS) if config == "gait" else ({"policy": ["policy"], "critic": ["policy"]} if rnd else None)
+    if rnd:
+        groups["rnd_state"] = ["policy"]
+    return groups
 
 
 def make_policy(num_obs: int, A: int, noise_std_type: str):
@@ -50,7 +62,7 @@ def make_policy(num_obs: int, A: int, noise_std_type: str):
     return LogStdPolicy(num_obs, A, noise_std_type="log")
 
 
-def rollout(config: str, n: int, T: int, noise_std_type: str = "scalar"):
+def rollout(config: str, n: int, T: int, noise_std_type: str = "scalar", rnd: bool = False):
     from genesis_forge_amd.learner import ActorCriticMLP, RolloutStorage
     from genesis_forge_amd.tasks import BASELINE_CONFIGS
 
@@ -58,8 +70,7 @@ def rollout(config: str, n: int, T: int, noise_std_type: str = "scalar"):
     env.build()
     env.seed(1)
     obs, extras = env.reset()
-    groups = GAIT_GROUPS if config == "gait" else None
-    st = RolloutStorage(env, T, obs_groups=groups).attach()
+    st = RolloutStorage(env, T, obs_groups=obs_groups(config, rnd)).attach()
     st.begin(obs, extras)
     st.seed(2)
     A = env.action_space.shape[0]
@@ -82,7 +93,7 @@ def rollout(config: str, n: int, T: int, noise_std_type: str = "scalar"):
     return env, st, policy
 
 
-def synthetic(config: str, n: int, T: int, noise_std_type: str = "scalar"):
+def synthetic(config: str, n: int, T: int, noise_std_type: str = "scalar", rnd: bool = False):
     """A storage of random rows with the shapes of ``config`` and no env behind it (the dispatch-count runs: every launch of the
     process then belongs to the set-up or to an update)."""
     from types import SimpleNamespace
@@ -94,7 +105,7 @@ def synthetic(config: str, n: int, T: int, noise_std_type: str = "scalar"):
     mk = lambda name, w: SimpleNamespace(name=name, observation_space=SimpleNamespace(shape=(w,)), output="fresh", _history_len=1, _unrolled=False)
     mgrs = [mk("policy", obs_w)] + ([mk("critic", critic_w)] if critic_w else [])
     env = SimpleNamespace(num_envs=n, managers={"observation": mgrs}, backend=nat.get_backend())
-    st = RolloutStorage(env, T, obs_groups=GAIT_GROUPS if critic_w else None)
+    st = RolloutStorage(env, T, obs_groups=obs_groups("gait" if critic_w else "go2_cmd", rnd))
     st._ensure_policy_rows(A)
     g = torch.Generator(device="cuda").manual_seed(0)
     for t in [st.observations, *st.group_rows.values(), st.actions, st.values, st.advantages, st.returns, st.actions_log_prob, st.mu]:
@@ -147,18 +158,20 @@ def main():
     ap.add_argument("--synthetic", action="store_true", help="random storage rows, no env (dispatch counts under rocprofv3)")
     ap.add_argument("--noise-std-type", default="scalar", choices=["scalar", "log"], help="the policy's std parameter: std, or log_std")
     ap.add_argument("--symmetry", default="none", choices=["none", "augment", "mirror", "both"], help="rsl_rl's symmetry_cfg with the Go2 mirror")
+    ap.add_argument("--rnd", action="store_true", help="rsl_rl's rnd_cfg: every minibatch also trains the RND predictor")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_update.py measures on a ROCm GPU: none is visible")
     from genesis_forge_amd.learner import PPO
     from rsl_rl_ppo import RslRlPPO
+    from rsl_rl_rnd import RslRlRND, RslRlRndPPO
     from rsl_rl_symmetry import RslRlSymmetryPPO
 
     forms = args.forms.split(",")
     lines = []
     for spec in args.sizes.split(","):
         config, n = spec.split(":")
-        env, st, policy0 = (synthetic if args.synthetic else rollout)(config, int(n), args.steps, args.noise_std_type)
+        env, st, policy0 = (synthetic if args.synthetic else rollout)(config, int(n), args.steps, args.noise_std_type, args.rnd)
         init = copy.deepcopy(policy0.state_dict())
         algo_cfg = dict(ALGO)
         if args.symmetry != "none":
@@ -170,7 +183,13 @@ def main():
             for form in forms:
                 policy = copy.deepcopy(policy0)
                 policy.load_state_dict(init)
-                algo = PPO(policy, st, **algo_cfg) if form == "fused" else (RslRlSymmetryPPO if args.symmetry != "none" else RslRlPPO)(policy, st, **algo_cfg)
+                if form == "fused":
+                    algo = PPO(policy, st, **dict(algo_cfg, rnd_cfg=RND_CFG if args.rnd else None))
+                elif args.rnd:
+                    ref_rnd = RslRlRND(st.obs_width, **{k: v for k, v in RND_CFG.items() if k != "learning_rate"}).cuda()
+                    algo = RslRlRndPPO(policy, st, ref_rnd, rnd_learning_rate=RND_CFG["learning_rate"], **algo_cfg)
+                else:
+                    algo = (RslRlSymmetryPPO if args.symmetry != "none" else RslRlPPO)(policy, st, **algo_cfg)
                 gen = torch.Generator(device="cuda").manual_seed(rep)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -183,7 +202,7 @@ def main():
         mb = st.num_steps * st.env.num_envs // ALGO["num_mini_batches"]
         for form in forms:
             row = dict(config=config, num_envs=int(n), steps=args.steps, minibatch=mb, form=form, reps=args.reps,
-                       noise_std_type=args.noise_std_type, symmetry=args.symmetry,
+                       noise_std_type=args.noise_std_type, symmetry=args.symmetry, rnd=args.rnd,
                        best_ms=round(min(times[form]), 3) if times[form] else None,
                        median_ms=round(statistics.median(times[form]), 3) if times[form] else None,
                        losses=last[form][0], lr=last[form][1], device=torch.cuda.get_device_name(0))

@@ -84,6 +84,10 @@ GF_EXPORT int gf_sizeof(int which) {
         case 33: return (int)sizeof(GfMlpDistillArgs);
         case 34: return (int)sizeof(GfBcLossArgs);
         case 35: return (int)sizeof(GfRndRewardArgs);
+        case 36: return (int)sizeof(GfMlpRecurrentActArgs);
+        case 37: return (int)sizeof(GfRnnCell);
+        case 38: return (int)sizeof(GfTrajTableArgs);
+        case 39: return (int)sizeof(GfTrajGatherArgs);
         default: return -1;
     }
 }

@@ -1,4 +1,4 @@
-// gf_mlp.hip — gf_mlp_act (and gf_mlp_distill_act, gf_rnd_reward): the actor and critic MLPs of a collection step and gf_policy_act's sampling in one launch
+// gf_mlp.hip — gf_mlp_act (and gf_mlp_distill_act, gf_rnd_reward, gf_mlp_recurrent_act): the actor and critic MLPs of a collection step and gf_policy_act's sampling in one launch
 // (include/gf_step.h has the contract).  The first kernel of the library on the matrix cores: every other one is bandwidth- or
 // latency-bound, this one is 0.76 MFLOP per env.
 //
@@ -25,6 +25,7 @@
 // LDS: 65 664 B, registers <= 256: two workgroups per CU, so one's barriers, ELU and load latency hide behind the other's MFMAs.
 // gf_mlp_distill_act is the same tile walk with grid y = student / teacher (a distillation collection step): the student workgroup is
 // the actor path above, the teacher workgroup stores its outputs to two destinations and samples nothing.
+// gf_mlp_recurrent_act puts an LSTM / GRU cell between a net's input and its MLP (rnn_cell below): a second LDS buffer, one workgroup per CU.
 #include <initializer_list>
 
 #include "gf_launch.h"
@@ -108,12 +109,12 @@ __device__ __forceinline__ void mlp_multiply(const float* ap, float (&r)[NB][mlp
     }
 }
 
-// columns [k0, k1) of the layer's k loop, x holding column k at x[row][k - xk0]
+// columns [k0, k1) of the layer's k loop, x (an activation buffer of row stride kMlpXS) holding column k at x[row][k - xk0]
 template <int NB, bool VEC>
-__device__ __forceinline__ void mlp_k_loop(const MlpSmem& sm, const GF_GLOBAL float* W, const uint32_t (&rowoff)[NB], int K, int k0, int k1, int xk0, int li, int lh,
+__device__ __forceinline__ void mlp_k_loop(const float* x, const GF_GLOBAL float* W, const uint32_t (&rowoff)[NB], int K, int k0, int k1, int xk0, int li, int lh,
                                            f32x16 (&acc)[NB]) {
     constexpr int KC = mlp_kc(NB), H = KC / 2;
-    const float* ap = sm.x + li * kMlpXS + lh - xk0;
+    const float* ap = x + li * kMlpXS + lh - xk0;
     if constexpr (NB <= 2) {   // registers for two chunks: the one being multiplied and the one in flight, by turns
         float ra[NB][H], rb[NB][H];
         int k = k0;
@@ -135,6 +136,36 @@ __device__ __forceinline__ void mlp_k_loop(const MlpSmem& sm, const GF_GLOBAL fl
             mlp_load_chunk<NB, VEC>(W, rowoff, K, k, lh, r);
             mlp_multiply<NB>(ap + k, r, acc);
         }
+    }
+}
+
+// Columns [p0, p0 + cols) of the net's input from its segments into x[row][0 …], through the normaliser where `norm`: zeros past
+// num_envs and from `cols` up to `padded`.  The callers meet before and after.
+template <bool NORM>
+__device__ __forceinline__ void mlp_stage_input(MlpSmem& sm, const GfMlpNet& net, const bool norm, const int p0, const int cols, const int padded,
+                                                const int64_t row0, const int64_t N) {
+    for (int e = (int)threadIdx.x; e < kMlpRows * padded; e += kMlpBlock) {
+        const int row = e / padded, col = e - row * padded;
+        const int64_t n = row0 + row;
+        int k = p0 + col;
+        const bool in = n < N && col < cols;
+        const float* rows = net.inputs[0].rows;
+        int64_t off = 0;
+#pragma unroll
+        for (int s = 0; s < GF_MLP_MAX_INPUTS; ++s) {
+            const int w = s < net.num_inputs ? net.inputs[s].width : 0;
+            const bool hit = in && k >= 0 && k < w;
+            rows = hit ? net.inputs[s].rows : rows;
+            const int stride = net.inputs[s].row_stride ? net.inputs[s].row_stride : w;
+            off = hit ? n * stride + k : off;
+            k -= w;
+        }
+        float v = G(rows)[off];
+        if (NORM && norm) {   // rsl_rl EmpiricalNormalization.forward: one subtraction, one addition, one correctly rounded division
+            const int c = in ? p0 + col : 0;
+            v = (v - G(net.in_mean)[c]) / (G(net.in_std)[c] + net.in_eps);
+        }
+        sm.x[row * kMlpXS + col] = in ? v : 0.0f;
     }
 }
 
@@ -169,35 +200,12 @@ __device__ __forceinline__ void mlp_layer(MlpSmem& sm, const GfMlpNet& net, cons
     for (int p0 = 0; p0 < K; p0 += GF_MLP_MAX_HIDDEN) {
         const int cols = K - p0 < GF_MLP_MAX_HIDDEN ? K - p0 : GF_MLP_MAX_HIDDEN;
         if (first) {   // the input from its segments: zeros past num_envs and past K up to the chunk's end
-            const int padded = (cols + KC - 1) / KC * KC;
             if (p0) __syncthreads();   // (the previous pass is multiplied)
-            for (int e = (int)threadIdx.x; e < kMlpRows * padded; e += kMlpBlock) {
-                const int row = e / padded, col = e - row * padded;
-                const int64_t n = row0 + row;
-                int k = p0 + col;
-                const bool in = n < N && col < cols;
-                const float* rows = net.inputs[0].rows;
-                int64_t off = 0;
-#pragma unroll
-                for (int s = 0; s < GF_MLP_MAX_INPUTS; ++s) {
-                    const int w = s < net.num_inputs ? net.inputs[s].width : 0;
-                    const bool hit = in && k >= 0 && k < w;
-                    rows = hit ? net.inputs[s].rows : rows;
-                    const int stride = net.inputs[s].row_stride ? net.inputs[s].row_stride : w;
-                    off = hit ? n * stride + k : off;
-                    k -= w;
-                }
-                float v = G(rows)[off];
-                if (NORM && norm) {   // rsl_rl EmpiricalNormalization.forward: one subtraction, one addition, one correctly rounded division
-                    const int c = in ? p0 + col : 0;
-                    v = (v - G(net.in_mean)[c]) / (G(net.in_std)[c] + net.in_eps);
-                }
-                sm.x[row * kMlpXS + col] = in ? v : 0.0f;
-            }
+            mlp_stage_input<NORM>(sm, net, norm, p0, cols, (cols + KC - 1) / KC * KC, row0, N);
             __syncthreads();
         }
-        if (vec) mlp_k_loop<NB, true>(sm, W, rowoff, K, p0, p0 + cols, p0, li, lh, acc);
-        else mlp_k_loop<NB, false>(sm, W, rowoff, K, p0, p0 + cols, p0, li, lh, acc);
+        if (vec) mlp_k_loop<NB, true>(sm.x, W, rowoff, K, p0, p0 + cols, p0, li, lh, acc);
+        else mlp_k_loop<NB, false>(sm.x, W, rowoff, K, p0, p0 + cols, p0, li, lh, acc);
     }
     __syncthreads();   // every wave is done reading x
 
@@ -254,17 +262,11 @@ __device__ __forceinline__ void mlp_sample_row(const GfPolicyActArgs& p, const f
     else policy_act_row<false, LOG>(p, n, load_mean);
 }
 
-template <bool NORM, bool LOG>
-__global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArgs a, const int first_net, const int vec_rows) {
-    __shared__ MlpSmem sm;
-    const bool is_critic = (int)blockIdx.y + first_net == 1;
-    const GfMlpNet& net = is_critic ? a.critic : a.actor;
+// one lane per row finishes it from the outputs in x (K of them): the critic's value, or the actor's mean and gf_policy_act's row
+template <bool LOG>
+__device__ __forceinline__ void mlp_act_finish(const GfMlpActArgs& a, const MlpSmem& sm, const bool is_critic, const int K, const int64_t row0,
+                                               const int vec_rows) {
     const int64_t N = a.num_envs;
-    const int64_t row0 = (int64_t)blockIdx.x * kMlpRows;
-
-    const int K = mlp_forward<NORM>(sm, net, row0, N);
-
-    // one lane per row finishes it from the outputs in x
     const int r = (int)threadIdx.x;
     const int64_t n = row0 + r;
     if (r >= kMlpRows || n >= N) return;
@@ -300,6 +302,17 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArg
     p.values_out = nullptr;   // (the critic workgroup's)
     p.log_prob_out = a.log_prob_out;
     mlp_sample_row<LOG>(p, out, n, vec_rows);
+}
+
+template <bool NORM, bool LOG>
+__global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArgs a, const int first_net, const int vec_rows) {
+    __shared__ MlpSmem sm;
+    const bool is_critic = (int)blockIdx.y + first_net == 1;
+    const GfMlpNet& net = is_critic ? a.critic : a.actor;
+    const int64_t row0 = (int64_t)blockIdx.x * kMlpRows;
+
+    const int K = mlp_forward<NORM>(sm, net, row0, a.num_envs);
+    mlp_act_finish<LOG>(a, sm, is_critic, K, row0, vec_rows);
 }
 
 // gf_mlp_distill_act: grid y = 0 the student (gf_mlp_act's actor path: mean, sample, the storage row), y = 1 the teacher (its output
@@ -494,6 +507,184 @@ __global__ __launch_bounds__(kSumBlock) void rnd_scale_kernel(const GfRndRewardA
     rnd_finish_row(a, n, sd > 0.0f ? r / sd : r);   // rsl_rl: no eps in this division
 }
 
+// gf_mlp_recurrent_act: an LSTM / GRU cell in front of each MLP, in the launch of gf_mlp_act.  The cell is the layer code's tile walk
+// with the four accumulators of a wave holding the four gate columns of ONE 32-unit block (LSTM i, f, g, o; GRU n_x, r, z, n_h), so a
+// lane has every pre-activation of its hidden unit for 16 rows and the non-linear tail needs no exchange.  Wave w owns the unit
+// blocks w, w + 4, … in rounds (H <= 128: one round); per round the k loop runs over the input columns (x, staged through the
+// normaliser in 512-column passes as a first layer's) and then the hidden columns, from a SECOND activation buffer that holds the
+// tile's h (after the reset) for the whole cell — 2 x 65 664 = 131 328 B of LDS, one workgroup per CU.  (Not built: [x | h] as one k
+// range in the one buffer, which keeps two workgroups per CU but re-stages h with every pass and round and cannot hold an input of
+// 512 columns next to any h.)  h' and c' go to memory in place as a round ends — only this workgroup reads these rows, and it reads
+// h from LDS — and when the rounds are over the workgroup reads its h' back into x: the MLP's input, staged as a layer's output is.
+struct RnnSmem {
+    MlpSmem m;
+    float h[kMlpRows * kMlpXS];
+};
+
+__device__ __forceinline__ float rnn_sigmoid(float p) { return 1.0f / (1.0f + expf(-p)); }
+
+template <bool LSTM>
+__device__ __forceinline__ void rnn_cell(RnnSmem& sm, const GfMlpNet& net, const GfRnnCell& cell, const int K, const int64_t row0, const int64_t N) {
+    constexpr int NBX = LSTM ? 4 : 3;   // accumulators the input columns feed (GRU: n_x, r, z), and the hidden ones (GRU: r, z, n_h)
+    const int H = cell.hidden;
+    const int UB = (H + 31) >> 5;
+    const int rounds = (UB + kMlpWaves - 1) / kMlpWaves;
+    const int passes = (K + GF_MLP_MAX_HIDDEN - 1) / GF_MLP_MAX_HIDDEN;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+    const bool norm = net.in_mean != nullptr;
+    const bool vec_x = (K & 3) == 0 && (reinterpret_cast<uintptr_t>(cell.w_ih) & 15u) == 0;
+    const bool vec_h = (H & 3) == 0 && (reinterpret_cast<uintptr_t>(cell.w_hh) & 15u) == 0;
+    const GF_GLOBAL uint8_t* reset = cell.reset ? G(cell.reset) : nullptr;
+
+    // h after the reset -> LDS (zeros past num_envs and from H to the chunk's end) and h_save
+    const int hp = UB * 32;
+    for (int e = (int)threadIdx.x; e < kMlpRows * hp; e += kMlpBlock) {
+        const int row = e / hp, col = e - row * hp;
+        const int64_t n = row0 + row;
+        float v = 0.0f;
+        if (n < N && col < H) {
+            const bool rs = reset && reset[n] != 0;
+            v = rs ? 0.0f : G(cell.h)[n * H + col];
+            if (cell.h_save) G(cell.h_save)[n * H + col] = v;
+        }
+        sm.h[row * kMlpXS + col] = v;
+    }
+
+    for (int round = 0; round < rounds; ++round) {
+        const int ub = round * kMlpWaves + wave;
+        const bool active = ub < UB;   // (wave-uniform)
+        const int j = ub * 32 + li;
+        const bool real = active && j < H;
+        const int jj = real ? j : 0;
+
+        // gate g of unit j is row g · H + j of w_ih / w_hh; the accumulators in the order LSTM i f g o, GRU n_x r z n_h
+        f32x16 acc[4];
+        uint32_t rowx[NBX], rowh[NBX];   // (4 · 512 · 1 024 elements at most: 32 bits)
+        {
+            const GF_GLOBAL float* bi = G(cell.b_ih);
+            const GF_GLOBAL float* bh = G(cell.b_hh);
+            float b0[4];
+            if (LSTM) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    b0[g] = bi[g * H + jj] + bh[g * H + jj];
+                    rowx[g] = (uint32_t)(g * H + jj) * (uint32_t)K;
+                    rowh[g] = (uint32_t)(g * H + jj) * (uint32_t)H;
+                }
+            } else {
+                b0[0] = bi[2 * H + jj];
+                b0[1] = bi[jj] + bh[jj];
+                b0[2] = bi[H + jj] + bh[H + jj];
+                b0[3] = bh[2 * H + jj];
+                rowx[0] = (uint32_t)(2 * H + jj) * (uint32_t)K;
+                rowx[1] = (uint32_t)jj * (uint32_t)K;
+                rowx[2] = (uint32_t)(H + jj) * (uint32_t)K;
+                rowh[0] = (uint32_t)jj * (uint32_t)H;
+                rowh[1] = (uint32_t)(H + jj) * (uint32_t)H;
+                rowh[2] = (uint32_t)(2 * H + jj) * (uint32_t)H;
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[g][r] = real ? b0[g] : 0.0f;
+            }
+        }
+
+        // the input columns: x holds one pass at a time (a single pass stays for every round)
+        for (int p = 0; p < passes; ++p) {
+            const int p0 = p * GF_MLP_MAX_HIDDEN;
+            const int cols = K - p0 < GF_MLP_MAX_HIDDEN ? K - p0 : GF_MLP_MAX_HIDDEN;
+            if (round == 0 || passes > 1) {
+                if (round || p) __syncthreads();   // (what x held is multiplied)
+                mlp_stage_input<true>(sm.m, net, norm, p0, cols, (cols + 31) / 32 * 32, row0, N);
+                __syncthreads();   // (round 0, pass 0: h is staged too)
+            }
+            if (active) {
+                f32x16(&ax)[NBX] = reinterpret_cast<f32x16(&)[NBX]>(acc[0]);
+                if (vec_x) mlp_k_loop<NBX, true>(sm.m.x, G(cell.w_ih), rowx, K, p0, p0 + cols, p0, li, lh, ax);
+                else mlp_k_loop<NBX, false>(sm.m.x, G(cell.w_ih), rowx, K, p0, p0 + cols, p0, li, lh, ax);
+            }
+        }
+        if (!active) continue;
+        // the hidden columns, on the same chains (GRU: r, z and the second chain of n)
+        {
+            f32x16(&ah)[NBX] = reinterpret_cast<f32x16(&)[NBX]>(acc[LSTM ? 0 : 1]);
+            if (vec_h) mlp_k_loop<NBX, true>(sm.h, G(cell.w_hh), rowh, H, 0, H, 0, li, lh, ah);
+            else mlp_k_loop<NBX, false>(sm.h, G(cell.w_hh), rowh, H, 0, H, 0, li, lh, ah);
+        }
+
+        // the unit's tail, 16 rows per lane
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int64_t n = row0 + row;
+            if (!real || n >= N) continue;
+            const int64_t at = n * H + j;
+            float hn;
+            if (LSTM) {
+                const bool rs = reset && reset[n] != 0;
+                const float c0 = rs ? 0.0f : G(cell.c)[at];
+                if (cell.c_save) G(cell.c_save)[at] = c0;
+                const float ig = rnn_sigmoid(acc[0][r]), fg = rnn_sigmoid(acc[1][r]), gg = tanhf(acc[2][r]), og = rnn_sigmoid(acc[3][r]);
+                const float cn = __fadd_rn(__fmul_rn(fg, c0), __fmul_rn(ig, gg));
+                G(cell.c)[at] = cn;
+                hn = __fmul_rn(og, tanhf(cn));
+            } else {
+                const float h0 = sm.h[row * kMlpXS + j];
+                const float rg = rnn_sigmoid(acc[1][r]), zg = rnn_sigmoid(acc[2][r]);
+                const float ng = tanhf(__fadd_rn(acc[0][r], __fmul_rn(rg, acc[3][r])));
+                hn = __fadd_rn(__fmul_rn(1.0f - zg, ng), __fmul_rn(zg, h0));
+            }
+            G(cell.h)[at] = hn;
+        }
+    }
+    __syncthreads();   // x and h are read, h' is stored
+
+    // h' -> x as a layer's output: H columns, zeros up to the longest chunk the first Linear may read to, zero rows past num_envs
+    const int padded = (H + 127) / 128 * 128 < GF_MLP_MAX_HIDDEN ? (H + 127) / 128 * 128 : GF_MLP_MAX_HIDDEN;
+    for (int e = (int)threadIdx.x; e < kMlpRows * padded; e += kMlpBlock) {
+        const int row = e / padded, col = e - row * padded;
+        const int64_t n = row0 + row;
+        sm.m.x[row * kMlpXS + col] = n < N && col < H ? G(cell.h)[n * H + col] : 0.0f;
+    }
+    __syncthreads();
+}
+
+// (one instance: the normaliser and log_std are workgroup-uniform run-time tests, as in rnd_tile_kernel and mlp_distill_kernel)
+__global__ __launch_bounds__(kMlpBlock, 1) void mlp_recurrent_act_kernel(const GfMlpRecurrentActArgs ra, const int first_net, const int vec_rows) {
+    __shared__ RnnSmem sm;
+    const GfMlpActArgs& a = ra.act;
+    const bool is_critic = (int)blockIdx.y + first_net == 1;
+    const GfMlpNet& net = is_critic ? a.critic : a.actor;
+    const GfRnnCell& cell = is_critic ? ra.critic_cell : ra.actor_cell;
+    const int64_t N = a.num_envs;
+    const int64_t row0 = (int64_t)blockIdx.x * kMlpRows;
+
+    int K;
+    if (cell.type == GF_RNN_NONE) {
+        K = mlp_forward<true>(sm.m, net, row0, N);
+    } else {
+        K = 0;
+        for (int s = 0; s < net.num_inputs; ++s) K += net.inputs[s].width;
+        if (cell.type == GF_RNN_LSTM) rnn_cell<true>(sm, net, cell, K, row0, N);
+        else rnn_cell<false>(sm, net, cell, K, row0, N);
+        K = cell.hidden;
+        const int layers = net.num_layers;
+        for (int l = 0; l < layers; ++l) {
+            const GfMlpLayer& L = net.layers[l];
+            const int nb = (((L.out_width + 31) >> 5) + kMlpWaves - 1) / kMlpWaves;
+            const bool last = l == layers - 1;
+            if (nb == 1) mlp_layer<1, true>(sm.m, net, L, K, false, last, row0, N);
+            else if (nb == 2) mlp_layer<2, true>(sm.m, net, L, K, false, last, row0, N);
+            else if (nb == 3) mlp_layer<3, true>(sm.m, net, L, K, false, last, row0, N);
+            else mlp_layer<4, true>(sm.m, net, L, K, false, last, row0, N);
+            K = L.out_width;
+        }
+    }
+    if (a.std_is_log) mlp_act_finish<true>(a, sm.m, is_critic, K, row0, vec_rows);
+    else mlp_act_finish<false>(a, sm.m, is_critic, K, row0, vec_rows);
+}
+
 // GF_OK and the net's widths, or the refusal
 static int mlp_check_net(const GfMlpNet& net, bool critic, int* out_width) {
     if (net.num_layers < 0 || net.num_layers > GF_MLP_MAX_LAYERS) return GF_E_RANGE;
@@ -523,6 +714,44 @@ static int mlp_check_net(const GfMlpNet& net, bool critic, int* out_width) {
     return GF_OK;
 }
 
+// gf_mlp_act's refusals (gf_mlp_recurrent_act's too): GF_OK, the actor's output width and which nets are there
+static int mlp_act_check(const GfMlpActArgs& a, int* A, bool* has_actor, bool* has_critic) {
+    if (a.num_envs < 0 || (a.std_per_env != 0 && a.std_per_env != 1) || (a.std_is_log != 0 && a.std_is_log != 1)) return GF_E_RANGE;
+    int one = 0;
+    int rc = mlp_check_net(a.actor, false, A);
+    if (rc != GF_OK) return rc;
+    rc = mlp_check_net(a.critic, true, &one);
+    if (rc != GF_OK) return rc;
+    const bool actor = a.actor.num_layers > 0, critic = a.critic.num_layers > 0;
+    if (!actor && !critic) return GF_E_UNSUPPORTED;
+    if (actor) {
+        if (!a.mean && !a.actions) return GF_E_NULL;
+        if (a.actions && !a.std) return GF_E_NULL;
+        if (!a.actions && (a.actions_out || a.mu_out || a.sigma_out || a.log_prob_out)) return GF_E_NULL;
+    } else if (a.mean || a.actions || a.actions_out || a.mu_out || a.sigma_out || a.log_prob_out) {
+        return GF_E_NULL;
+    }
+    if (critic) {
+        if (!a.values && !a.values_out) return GF_E_NULL;
+    } else if (a.values || a.values_out) {
+        return GF_E_NULL;
+    }
+    *has_actor = actor;
+    *has_critic = critic;
+    return GF_OK;
+}
+
+// a net's cell: GF_OK or the refusal (`present`: the net is in the launch)
+static int rnn_check_cell(const GfRnnCell& c, bool present) {
+    if (c.type != GF_RNN_NONE && c.type != GF_RNN_LSTM && c.type != GF_RNN_GRU) return GF_E_RANGE;
+    if (c.type == GF_RNN_NONE) return c.h_save || c.c_save ? GF_E_NULL : GF_OK;
+    if (!present) return GF_E_RANGE;
+    if (c.hidden < 1 || c.hidden > GF_MLP_MAX_HIDDEN) return GF_E_RANGE;
+    if (!c.w_ih || !c.w_hh || !c.b_ih || !c.b_hh || !c.h) return GF_E_NULL;
+    if (c.type == GF_RNN_LSTM ? !c.c : (c.c || c.c_save)) return GF_E_NULL;
+    return GF_OK;
+}
+
 // the launch's row tiles, or -1 where they pass a grid's x range
 static int64_t mlp_tiles(int64_t num_envs) {
     const int64_t tiles = (num_envs + kMlpRows - 1) / kMlpRows;
@@ -540,26 +769,10 @@ static int mlp_vec_rows(std::initializer_list<const void*> rows, int A) {
 
 extern "C" __attribute__((visibility("default"))) int gf_mlp_act(const GfMlpActArgs* a, void* stream) {
     if (!a) return GF_E_NULL;
-    if (a->num_envs < 0 || (a->std_per_env != 0 && a->std_per_env != 1) || (a->std_is_log != 0 && a->std_is_log != 1)) return GF_E_RANGE;
-    int A = 0, one = 0;
-    int rc = gf::mlp_check_net(a->actor, false, &A);
+    int A = 0;
+    bool actor = false, critic = false;
+    const int rc = gf::mlp_act_check(*a, &A, &actor, &critic);
     if (rc != GF_OK) return rc;
-    rc = gf::mlp_check_net(a->critic, true, &one);
-    if (rc != GF_OK) return rc;
-    const bool actor = a->actor.num_layers > 0, critic = a->critic.num_layers > 0;
-    if (!actor && !critic) return GF_E_UNSUPPORTED;
-    if (actor) {
-        if (!a->mean && !a->actions) return GF_E_NULL;
-        if (a->actions && !a->std) return GF_E_NULL;
-        if (!a->actions && (a->actions_out || a->mu_out || a->sigma_out || a->log_prob_out)) return GF_E_NULL;
-    } else if (a->mean || a->actions || a->actions_out || a->mu_out || a->sigma_out || a->log_prob_out) {
-        return GF_E_NULL;
-    }
-    if (critic) {
-        if (!a->values && !a->values_out) return GF_E_NULL;
-    } else if (a->values || a->values_out) {
-        return GF_E_NULL;
-    }
     if (a->num_envs == 0) return GF_OK;
     const int64_t tiles = gf::mlp_tiles(a->num_envs);
     if (tiles < 0) return GF_E_RANGE;
@@ -576,6 +789,27 @@ extern "C" __attribute__((visibility("default"))) int gf_mlp_act(const GfMlpActA
         if (norm) gf::klaunch(gf::mlp_act_kernel<true, false>, grid, block, 0, s, *a, first_net, vec_rows);
         else gf::klaunch(gf::mlp_act_kernel<false, false>, grid, block, 0, s, *a, first_net, vec_rows);
     }
+    return gf::launch_status();
+}
+
+extern "C" __attribute__((visibility("default"))) int gf_mlp_recurrent_act(const GfMlpRecurrentActArgs* ra, void* stream) {
+    if (!ra) return GF_E_NULL;
+    const GfMlpActArgs* a = &ra->act;
+    int A = 0;
+    bool actor = false, critic = false;
+    int rc = gf::mlp_act_check(*a, &A, &actor, &critic);
+    if (rc != GF_OK) return rc;
+    rc = gf::rnn_check_cell(ra->actor_cell, actor);
+    if (rc != GF_OK) return rc;
+    rc = gf::rnn_check_cell(ra->critic_cell, critic);
+    if (rc != GF_OK) return rc;
+    if (ra->actor_cell.type == GF_RNN_NONE && ra->critic_cell.type == GF_RNN_NONE) return GF_E_UNSUPPORTED;   // gf_mlp_act's launch
+    if (a->num_envs == 0) return GF_OK;
+    const int64_t tiles = gf::mlp_tiles(a->num_envs);
+    if (tiles < 0) return GF_E_RANGE;
+    const int vec_rows = gf::mlp_vec_rows({a->noise, a->actions, a->actions_out, a->mu_out, a->sigma_out, a->std}, A);
+    const dim3 grid((unsigned)tiles, actor && critic ? 2u : 1u);
+    gf::klaunch(gf::mlp_recurrent_act_kernel, grid, dim3(gf::kMlpBlock), 0, (hipStream_t)stream, *ra, actor ? 0 : 1, vec_rows);
     return gf::launch_status();
 }
 

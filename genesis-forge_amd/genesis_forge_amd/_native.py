@@ -442,6 +442,47 @@ class GfMlpActArgs(C.Structure):
                 ("actions_out", P), ("mu_out", P), ("sigma_out", P), ("values_out", P), ("log_prob_out", P), ("std_is_log", C.c_int32), ("_pad", C.c_int32)]
 
 
+# the collection step of a recurrent policy (learner.RecurrentForward): gf_mlp_recurrent_act, not in ABI_STRUCTS either
+GF_SIZEOF_MLP_RECURRENT_ACT = 36
+GF_SIZEOF_RNN_CELL = 37
+GF_RNN_NONE = 0
+GF_RNN_LSTM = 1
+GF_RNN_GRU = 2
+
+
+class GfRnnCell(C.Structure):
+    _fields_ = [("type", C.c_int32), ("hidden", C.c_int32), ("w_ih", P), ("w_hh", P), ("b_ih", P), ("b_hh", P), ("h", P), ("c", P),
+                ("reset", P), ("h_save", P), ("c_save", P)]
+
+
+class GfMlpRecurrentActArgs(C.Structure):
+    _fields_ = [("act", GfMlpActArgs), ("actor_cell", GfRnnCell), ("critic_cell", GfRnnCell)]
+
+
+# the trajectory minibatches of a recurrent policy's update (learner.RolloutStorage.recurrent_mini_batch_generator)
+GF_SIZEOF_TRAJ_TABLE = 38
+GF_SIZEOF_TRAJ_GATHER = 39
+
+
+class GfTrajTableArgs(C.Structure):
+    _fields_ = [("num_steps", C.c_int32), ("num_envs", C.c_int32), ("dones", P), ("counts", P), ("offsets", P), ("table", P)]
+
+
+class GfTrajGroup(C.Structure):
+    _fields_ = [("num_inputs", C.c_int32), ("width", C.c_int32), ("inputs", GfMlpSegment * GF_MLP_MAX_INPUTS), ("mean", P), ("std", P),
+                ("eps", C.c_float), ("_pad", C.c_int32), ("dst", P)]
+
+
+class GfTrajState(C.Structure):
+    _fields_ = [("hidden", C.c_int32), ("_pad", C.c_int32), ("h_start", P), ("c_start", P), ("h0", P), ("c0", P)]
+
+
+class GfTrajGatherArgs(C.Structure):
+    _fields_ = [("num_steps", C.c_int32), ("num_envs", C.c_int32), ("first_traj", C.c_int32), ("num_traj", C.c_int32),
+                ("env_start", C.c_int32), ("num_mb_envs", C.c_int32), ("table_rows", C.c_int32), ("_pad", C.c_int32), ("table", P),
+                ("groups", GfTrajGroup * 2), ("states", GfTrajState * 2), ("masks", P), ("unpad_index", P)]
+
+
 # teacher–student distillation (learner.DistillForward / RolloutStorage.act_distill, learner.Distillation): gf_mlp_distill_act /
 # gf_bc_loss, not in ABI_STRUCTS either
 GF_SIZEOF_MLP_DISTILL = 33
@@ -748,12 +789,17 @@ class HipBackend(Backend):
                             ("gf_rollout_frame_write", GF_SIZEOF_ROLLOUT_FRAME, GfRolloutFrameArgs),
                             ("gf_mirror_rows", GF_SIZEOF_MIRROR_ROWS, GfMirrorRowsArgs), ("gf_mirror_loss", GF_SIZEOF_MIRROR_LOSS, GfMirrorLossArgs),
                             ("gf_mlp_distill_act", GF_SIZEOF_MLP_DISTILL, GfMlpDistillArgs), ("gf_bc_loss", GF_SIZEOF_BC_LOSS, GfBcLossArgs),
-                            ("gf_rnd_reward", GF_SIZEOF_RND_REWARD, GfRndRewardArgs)):
+                            ("gf_rnd_reward", GF_SIZEOF_RND_REWARD, GfRndRewardArgs),
+                            ("gf_mlp_recurrent_act", GF_SIZEOF_MLP_RECURRENT_ACT, GfMlpRecurrentActArgs),
+                            ("gf_traj_table", GF_SIZEOF_TRAJ_TABLE, GfTrajTableArgs), ("gf_traj_gather", GF_SIZEOF_TRAJ_GATHER, GfTrajGatherArgs)):
             n = self.lib.gf_sizeof(idx)
             if n != C.sizeof(st):
                 raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")
             getattr(self.lib, fn).restype = C.c_int
             getattr(self.lib, fn).argtypes = [C.POINTER(st), C.c_void_p]
+        n = self.lib.gf_sizeof(GF_SIZEOF_RNN_CELL)
+        if n != C.sizeof(GfRnnCell):
+            raise GfError(f"ABI drift: sizeof(GfRnnCell) is {n} in the library, {C.sizeof(GfRnnCell)} in the binding")
 
     def _stream(self) -> int:
         torch = self._torch
@@ -900,6 +946,9 @@ _LEARNER_ENTRIES = {
     "mlp_distill_act": "learner.DistillForward.act, learner.RolloutStorage.act_distill",
     "bc_loss": "learner.Distillation.update",
     "rnd_reward": "learner.RndForward.reward, learner.RolloutStorage.intrinsic_reward",
+    "mlp_recurrent_act": "learner.RecurrentForward",
+    "traj_table": "learner.RolloutStorage.recurrent_mini_batch_generator",
+    "traj_gather": "learner.RolloutStorage.recurrent_mini_batch_generator",
 }
 
 

@@ -81,6 +81,17 @@ class MiniBatch(NamedTuple):
     indices: torch.Tensor        # [mb] int64: transition (t, n) = divmod(index, N)
 
 
+class RecurrentMiniBatch(NamedTuple):
+    """One minibatch of trajectories (rsl_rl ``recurrent_mini_batch_generator``): the envs of a contiguous range, fresh tensors."""
+    obs: torch.Tensor            # [T, ntraj, W_policy group] padded with zeros, through the actor's normaliser
+    critic_obs: torch.Tensor     # [T, ntraj, W_critic group] (``obs`` itself when the two groups are the same)
+    masks: torch.Tensor          # [T, ntraj] bool: the real steps
+    hid_a: object                # the actor memory's initial state: h0 [1, ntraj, H], or (h0, c0) for an LSTM
+    hid_c: object                # the critic memory's
+    unpad_index: torch.Tensor    # [envs · T] int64: the policy's batch mode un-pads with it (index_select)
+    rows: MiniBatch              # the per-row fields, [T · envs, …] in (t, env) order; its obs / critic_obs are None
+
+
 _MB_FIELDS = ("actions", "values", "advantages", "returns", "actions_log_prob", "mu", "sigma")   # MiniBatch fields after the observations
 _LOG_SQRT_2PI = math.log(math.sqrt(2 * math.pi))   # the constant of torch's Normal.log_prob
 
@@ -577,6 +588,74 @@ class RolloutStorage:
         self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
         return actions
 
+    def act_recurrent(self, forward: "RecurrentForward", obs, critic_obs=None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``act_policy`` for a recurrent policy: ONE ``gf_mlp_recurrent_act`` launch normalises the observations, advances the actor's
+        and the critic's LSTM / GRU state by one step in place (rows flagged by ``forward.reset(dones)`` start from zeros), walks the two
+        MLPs from the new hidden states, samples and writes the policy's rows.  The row, the noise stream and seed, and the input rules
+        are ``act_policy``'s.  At the first step of a rollout (row 0) the launch also writes the state the rollout starts from, after
+        the reset, into ``rnn_start`` (``{"actor": (h, c), "critic": (h, c)}``, ``[N, H]`` each, ``c`` None for a GRU): a trajectory that
+        starts later starts behind a done, from zeros, so the rollout-start state is all an update needs (rsl_rl stores the state of
+        every step).  The cell and the MLPs are k-ascending f32 fma chains with the device libm's ``expf`` / ``tanhf`` (``gf_step.h``):
+        within f32 rounding of the module's torch step, not its bits.  Measured per collection step against ``act()`` on the module's
+        torch step (go2_cmd, 256 units, profiles/r26_recurrent.md): 3.5 x / 1.27 x / 1.10 x faster at 4 096 / 16 384 / 65 536 envs with
+        an LSTM, 4.1 x / 1.54 x / 1.34 x with a GRU — this is the call to use at every size measured.  Against the MLP policy's
+        ``act_policy`` a recurrent step still costs 2.2 x – 4.4 x: every 32-row tile streams the cell's weights again.
+        On a backend without the entry (the test-only CPU oracle) this is ``act`` on the module's torch step under ``no_grad``, and
+        ``noise`` is required."""
+        if not isinstance(forward, RecurrentForward):
+            raise ValueError("act_recurrent(forward, ...) takes a RecurrentForward")
+        n, dev = self.env.num_envs, self.device
+        segs = _segments(obs, "obs", n, dev, forward._reader("actor"))
+        csegs = _segments(obs if critic_obs is None else critic_obs, "obs (the critic's input)" if critic_obs is None else "critic_obs", n, dev,
+                          forward._reader("critic"))
+        A = forward.num_actions
+        std, is_log = getattr(forward.policy, forward._std_name), forward.std_is_log
+        first = self._act_row() == 0
+        fn = getattr(self.env.backend, "mlp_recurrent_act", None)
+        if fn is None:   # (the test-only oracle backend) the module's step
+            with torch.no_grad():
+                if first:
+                    self.keep_rnn_start(forward.policy)
+                return self.act(forward.policy.act_mean(_cat(segs)), std.detach(), forward.policy.evaluate(_cat(csegs)), noise, std_is_log=is_log)
+        _check_f32(std, "policy.log_std" if is_log else "policy.std", {(A,)}, dev)
+        if noise is not None:
+            _check_f32(noise, "noise", {(n, A)}, dev)
+        self._ensure_policy_rows(A)
+        save = None
+        if first:
+            save = {}
+            for name in ("actor", "critic"):
+                h, c = forward.state(name, n, dev)
+                save[name] = (torch.empty_like(h[0]), None if c is None else torch.empty_like(c[0]))
+            self.rnn_start = save
+        actions = torch.empty((n, A), device=dev, dtype=torch.float32)
+        t, stream, seed, env_offset = self._open_act()
+        ra = forward._fill(n, segs, csegs, save)
+        a = ra.act
+        a.std, a.std_per_env, a.std_is_log = std.data_ptr(), 0, 1 if is_log else 0
+        a.noise = None if noise is None else noise.data_ptr()
+        a.seed, a.stream, a.env_offset = seed, stream, env_offset
+        a.mean = a.values = None
+        a.actions = actions.data_ptr()
+        self._policy_row_ptrs(a, t)
+        self._keep_act = (segs, csegs, noise)
+        fn(ra)
+        self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
+        return actions
+
+    def keep_rnn_start(self, policy) -> None:
+        """Copy the hidden states ``policy.get_hidden_states()`` holds — the state the rollout starts from, zeros where a memory has
+        none yet — into ``rnn_start``: what a loop on the module's torch step calls before the first step of a rollout (``act_recurrent``
+        does it inside its launch)."""
+        n, dev = self.env.num_envs, self.device
+        self.rnn_start = {}
+        for name, memory, hs in zip(("actor", "critic"), (policy.memory_a, policy.memory_c), policy.get_hidden_states()):
+            if hs is None:
+                H = memory.rnn.hidden_size
+                hs = tuple(torch.zeros((1, n, H), device=dev) for _ in range(2 if isinstance(memory.rnn, torch.nn.LSTM) else 1))
+            h, c = (hs[0], hs[1]) if isinstance(hs, tuple) and len(hs) == 2 else ((hs[0] if isinstance(hs, tuple) else hs), None)
+            self.rnn_start[name] = (h[0].detach().clone(), None if c is None else c[0].detach().clone())
+
     # -- teacher–student distillation: the collection step and the update's batches ------------------------------------------------
     def _ensure_distill_rows(self, num_actions: int) -> None:
         T, n = self.num_steps, self.env.num_envs
@@ -840,6 +919,139 @@ class RolloutStorage:
             for i in range(num_mini_batches):
                 yield self._gather(indices[i * mb:(i + 1) * mb], *norms)
 
+    # -- trajectory minibatches (a recurrent policy's update) ----------------------------------------------------------------------------
+    def recurrent_mini_batch_generator(self, num_mini_batches: int, num_epochs: int = 1, norms=(None, None)) -> Iterator["RecurrentMiniBatch"]:
+        """rsl_rl's ``recurrent_mini_batch_generator``: the rollout cut into trajectories at the dones (``dones[T-1]`` counts as set),
+        enumerated env-major; minibatch ``i`` is the envs ``[i·N // num_mini_batches, (i+1)·N // num_mini_batches)`` — contiguous,
+        not shuffled, the same in every epoch — as padded ``[T, ntraj, W]`` observation sequences through ``norms`` (the actor's and
+        the critic's :class:`EmpiricalNormalization` or None; padding stays zero), their masks, the initial hidden states and the
+        int64 index the policy's batch mode un-pads with.  ``gf_traj_table`` runs once (and ONE host read fetches the
+        ``num_mini_batches + 1`` trajectory offsets); every minibatch is one ``gf_traj_gather`` and one ``gf_minibatch_gather`` (the
+        per-row fields, rows ``t·N + n`` in ``(t, env)`` order).
+
+        The initial state of a trajectory is the rollout-start state ``act_recurrent`` saved (``rnn_start``) where it starts at
+        ``t = 0``, zeros elsewhere — a later start lies behind a done; rsl_rl stores the state of every step to read the same values.
+        ``history="frames"`` storage is refused (``ValueError``).  On a backend without the entries (the test-only oracle) the same
+        batches come from rsl_rl's lines: ``nonzero``, ``torch.split``, ``pad_sequence``."""
+        if not self._returns_ready:
+            raise RuntimeError("recurrent_mini_batch_generator() reads returns and advantages: call compute_returns() first")
+        if self.frames:
+            raise ValueError('recurrent_mini_batch_generator: history="frames" storage is not supported (trajectories are gathered from observation rows)')
+        start = getattr(self, "rnn_start", None)
+        if not start:
+            raise RuntimeError("recurrent_mini_batch_generator() needs the rollout-start hidden states: collect with act_recurrent()")
+        M, num_epochs = int(num_mini_batches), int(num_epochs)
+        T, n = self.num_steps, self.env.num_envs
+        if M < 1 or M > n or num_epochs < 0:
+            raise ValueError(f"num_mini_batches must be 1 … num_envs ({n}) and num_epochs >= 0")
+        width = lambda group: sum(self._widths[m] for m in self.obs_groups[group])
+        norms = (_as_normalizer(norms[0], width("policy"), "obs_normalizer"), _as_normalizer(norms[1], width("critic"), "critic_obs_normalizer"))
+        bounds = [i * n // M for i in range(M + 1)]
+        if getattr(self.env.backend, "traj_table", None) is None:
+            return self._recurrent_batches_torch(bounds, num_epochs, norms, start)
+        dev = self.device
+        key = (T, n, M)
+        if getattr(self, "_traj_key", None) != key:
+            self._traj_counts = torch.empty(n, device=dev, dtype=torch.int32)
+            self._traj_offsets = torch.empty(n + 1, device=dev, dtype=torch.int32)
+            self._traj_table = torch.empty((T * n, 3), device=dev, dtype=torch.int32)
+            self._traj_bounds = torch.tensor(bounds, device=dev, dtype=torch.int64)
+            self._traj_rows = (torch.arange(T, device=dev) * n)[:, None] + torch.arange(n, device=dev)[None, :]   # [T, N]: row t·N + n
+            self._traj_key = key
+        a = nat.GfTrajTableArgs()
+        a.num_steps, a.num_envs, a.dones = T, n, self.dones.data_ptr()
+        a.counts, a.offsets, a.table = self._traj_counts.data_ptr(), self._traj_offsets.data_ptr(), self._traj_table.data_ptr()
+        self.env.backend.traj_table(a)
+        offs = self._traj_offsets.index_select(0, self._traj_bounds).tolist()   # the one host read
+        return self._recurrent_batches_hip(bounds, offs, num_epochs, norms, start)
+
+    def _recurrent_batches_hip(self, bounds, offs, num_epochs: int, norms, start) -> Iterator["RecurrentMiniBatch"]:
+        T, n, dev = self.num_steps, self.env.num_envs, self.device
+        rows = self._flat_rows()
+        policy, critic = self.obs_groups["policy"], self.obs_groups["critic"]
+        same = list(critic) == list(policy) and norms[1] is norms[0]
+        a = nat.GfTrajGatherArgs()
+        a.num_steps, a.num_envs, a.table, a.table_rows = T, n, self._traj_table.data_ptr(), offs[-1]
+        for g, names, norm in zip(a.groups, (policy, critic), norms):
+            g.num_inputs, g.width = len(names), sum(self._widths[k] for k in names)
+            for seg, k in zip(g.inputs, names):
+                seg.rows, seg.width, seg.row_stride = rows[k].data_ptr(), self._widths[k], rows[k].stride(0)
+            if norm is not None:
+                g.mean, g.std, g.eps = norm._mean.data_ptr(), norm._std.data_ptr(), norm.eps
+        if same:
+            a.groups[1].width = 0
+        for st, name in zip(a.states, ("actor", "critic")):
+            h, c = start[name]
+            st.hidden, st.h_start, st.c_start = h.shape[1], h.data_ptr(), None if c is None else c.data_ptr()
+        for _epoch in range(num_epochs):
+            for i in range(len(bounds) - 1):
+                e0, e1, J = bounds[i], bounds[i + 1], offs[i + 1] - offs[i]
+                a.first_traj, a.num_traj, a.env_start, a.num_mb_envs = offs[i], J, e0, e1 - e0
+                obs = torch.empty((T, J, a.groups[0].width), device=dev, dtype=torch.float32)
+                critic_obs = obs if same else torch.empty((T, J, a.groups[1].width), device=dev, dtype=torch.float32)
+                masks = torch.empty((T, J), device=dev, dtype=torch.bool)
+                index = torch.empty((e1 - e0) * T, device=dev, dtype=torch.int64)
+                a.groups[0].dst, a.groups[1].dst = obs.data_ptr(), None if same else critic_obs.data_ptr()
+                a.masks, a.unpad_index = masks.data_ptr(), index.data_ptr()
+                hid = []
+                for st, name in zip(a.states, ("actor", "critic")):
+                    h, c = start[name]
+                    h0 = torch.empty((1, J, h.shape[1]), device=dev, dtype=torch.float32)
+                    c0 = None if c is None else torch.empty_like(h0)
+                    st.h0, st.c0 = h0.data_ptr(), None if c0 is None else c0.data_ptr()
+                    hid.append(h0 if c0 is None else (h0, c0))
+                self.env.backend.traj_gather(a)
+                per = self._gather(self._traj_rows[:, e0:e1].reshape(-1), fields_only=True)
+                yield RecurrentMiniBatch(obs, critic_obs, masks, hid[0], hid[1], index, per)
+
+    def _recurrent_batches_torch(self, bounds, num_epochs: int, norms, start) -> Iterator["RecurrentMiniBatch"]:
+        """rsl_rl's lines (``split_and_pad_trajectories``, ``recurrent_mini_batch_generator``) on the stored rows."""
+        T, n = self.num_steps, self.env.num_envs
+        rows = self._flat_rows()
+
+        def group(names, norm):
+            x = rows[names[0]] if len(names) == 1 else torch.cat([rows[m] for m in names], dim=-1)
+            if norm is not None:
+                with torch.no_grad():
+                    x = norm(x)
+            return x.reshape(T, n, -1)
+
+        dones = self.dones.clone()
+        dones[-1] = True
+        flat_dones = dones.transpose(1, 0).reshape(-1, 1)
+        done_indices = torch.cat((flat_dones.new_tensor([-1], dtype=torch.int64), flat_dones.nonzero()[:, 0]))
+        trajectory_lengths = done_indices[1:] - done_indices[:-1]
+        lengths = trajectory_lengths.tolist()
+
+        def split_and_pad(tensor):
+            trajectories = torch.split(tensor.transpose(1, 0).flatten(0, 1), lengths)
+            trajectories = trajectories + (torch.zeros(tensor.shape[0], *tensor.shape[2:], device=tensor.device),)
+            return torch.nn.utils.rnn.pad_sequence(trajectories)[:, :-1]
+
+        policy, critic = self.obs_groups["policy"], self.obs_groups["critic"]
+        same = list(critic) == list(policy) and norms[1] is norms[0]
+        padded_obs = split_and_pad(group(policy, norms[0]))
+        padded_critic = padded_obs if same else split_and_pad(group(critic, norms[1]))
+        trajectory_masks = trajectory_lengths > torch.arange(0, T, device=dones.device).unsqueeze(1)
+        starts = done_indices[:-1] + 1                   # env-major flat index e·T + t of every trajectory's first step
+        env, t0 = starts // T, starts % T
+        per_env = torch.bincount(env, minlength=n).cumsum(0)
+        first = [0] + per_env.tolist()
+        tn = (torch.arange(T) * n)[:, None] + torch.arange(n)[None, :]
+        for _epoch in range(num_epochs):
+            for i in range(len(bounds) - 1):
+                e0, e1 = bounds[i], bounds[i + 1]
+                j0, j1 = first[e0], first[e1]
+                masks = trajectory_masks[:, j0:j1]
+                hid = []
+                for name in ("actor", "critic"):
+                    state = tuple(torch.where((t0[j0:j1] == 0)[:, None], s[env[j0:j1]], torch.zeros(())).unsqueeze(0).contiguous()
+                                  for s in start[name] if s is not None)
+                    hid.append(state if len(state) == 2 else state[0])
+                index = masks.transpose(1, 0).reshape(-1).nonzero()[:, 0]
+                per = self._gather(tn[:, e0:e1].reshape(-1).to(self.device), fields_only=True)
+                yield RecurrentMiniBatch(padded_obs[:, j0:j1], padded_critic[:, j0:j1], masks, hid[0], hid[1], index, per)
+
     def _flat(self) -> dict:
         """Every stored array as its ``[T·N, w]`` source rows (views); a frame-stored manager as its ``[(T+H)·N, O]`` frames, of which
         row ``t·N + n`` is the OLDEST frame of observation row ``t`` (its newer frames lie multiples of N rows further on)."""
@@ -856,7 +1068,9 @@ class RolloutStorage:
             rows[name] = F.view(F.shape[0] * n, F.shape[2])
         return rows
 
-    def _gather(self, idx: torch.Tensor, obs_norm=None, critic_norm=None) -> MiniBatch:
+    def _gather(self, idx: torch.Tensor, obs_norm=None, critic_norm=None, fields_only: bool = False) -> MiniBatch:
+        """``fields_only``: the per-row fields alone (``obs`` / ``critic_obs`` None) — a recurrent update reads its observations as
+        padded trajectories."""
         rows, per = self._flat()
         policy, critic = self.obs_groups["policy"], self.obs_groups["critic"]
         same = list(critic) == list(policy) and critic_norm is obs_norm
@@ -873,6 +1087,8 @@ class RolloutStorage:
                 with torch.no_grad():
                     return norm(x)
 
+            if fields_only:
+                return MiniBatch(None, None, *(per[k][idx] for k in _MB_FIELDS), idx)
             obs = cat(policy, obs_norm)
             return MiniBatch(obs, obs if same else cat(critic, critic_norm), *(per[k][idx] for k in _MB_FIELDS), idx)
         m = idx.shape[0]
@@ -889,8 +1105,8 @@ class RolloutStorage:
                 col += widths[k]
             return out
 
-        obs = group(policy, obs_norm)
-        critic_obs = obs if same else group(critic, critic_norm)
+        obs = None if fields_only else group(policy, obs_norm)
+        critic_obs = obs if same or fields_only else group(critic, critic_norm)
         outs = []
         for k in _MB_FIELDS:
             src = per[k]
@@ -1401,6 +1617,8 @@ class ActorCriticMLP(_ActionStd, torch.nn.Module):
     parameter starting at ``log(init_noise_std)`` in its place (no ``std`` parameter; rsl_rl's names, so checkpoints interchange),
     which keeps the std positive whatever step Adam takes.  ``action_std`` is the current std of either."""
 
+    is_recurrent = False
+
     def __init__(self, num_obs: int, num_actions: int, actor_hidden_dims: Sequence[int] = (512, 256, 128),
                  critic_hidden_dims: Sequence[int] = (512, 256, 128), init_noise_std: float = 1.0, num_critic_obs: Optional[int] = None,
                  actor_obs_normalization: bool = False, critic_obs_normalization: bool = False, noise_std_type: str = "scalar"):
@@ -1445,6 +1663,127 @@ class ActorCriticMLP(_ActionStd, torch.nn.Module):
             if isinstance(norm, EmpiricalNormalization) and norm.training:
                 pairs.append((norm, _segments(x, name, None, norm._mean.device, norm_width=norm.width)))
         _update_normalizers(pairs, self._scratch.args)
+
+
+class _Memory(torch.nn.Module):
+    """rsl_rl's ``Memory``: a one-layer, sequence-major ``nn.LSTM`` / ``nn.GRU`` (``rnn``) and its hidden state — ``h [1, N, H]``, for
+    an LSTM ``(h, c)`` — which is not part of the state dict."""
+
+    def __init__(self, input_size: int, rnn_type: str, hidden_size: int):
+        super().__init__()
+        cls = torch.nn.GRU if rnn_type == "gru" else torch.nn.LSTM
+        self.rnn = cls(input_size=input_size, hidden_size=hidden_size, num_layers=1)
+        self.hidden_states = None
+
+    def forward(self, x: torch.Tensor, masks=None, hidden_states=None, unpad_index=None) -> torch.Tensor:
+        if masks is not None:   # batch mode: a padded [T, ntraj, W] sequence from the given states; the stored state is untouched
+            if hidden_states is None:
+                raise ValueError("hidden states not passed to the memory module during a policy update")
+            out, _ = self.rnn(x, hidden_states)
+            return _unpad_trajectories(out, masks, unpad_index)
+        out, self.hidden_states = self.rnn(x.unsqueeze(0), self.hidden_states)   # step mode: [N, W] -> [1, N, H]
+        return out
+
+    def reset(self, dones=None) -> None:
+        if dones is None:
+            self.hidden_states = None   # (zeros again at the next step)
+        elif self.hidden_states is not None:
+            for s in self.hidden_states if isinstance(self.hidden_states, tuple) else (self.hidden_states,):
+                s[..., dones.to(torch.bool).reshape(-1), :] = 0.0
+
+
+class _StateHolder:
+    """A hidden state of its own over a memory's ``rnn`` (``RecurrentForward(own_state=True)``)."""
+
+    def __init__(self, rnn):
+        self.rnn, self.hidden_states = rnn, None
+
+    reset = _Memory.reset
+
+
+def _unpad_trajectories(out: torch.Tensor, masks: torch.Tensor, unpad_index=None) -> torch.Tensor:
+    """rsl_rl's ``unpad_trajectories``: the real steps of a padded ``[T, ntraj, H]`` batch, trajectory-major, back as ``[T, envs, H]``.
+    ``unpad_index`` (int64, the positions of the set mask elements in the flattened ``[ntraj, T]`` mask): the same rows through
+    ``index_select`` — no boolean indexing, so no host synchronisation."""
+    T, H = masks.shape[0], out.shape[-1]
+    flat = out.transpose(1, 0)
+    if unpad_index is None:
+        rows = flat[masks.transpose(1, 0)]
+    else:
+        rows = flat.reshape(-1, H).index_select(0, unpad_index)
+    return rows.view(-1, T, H).transpose(1, 0)
+
+
+_RECURRENT_POLICY_KEYS = _POLICY_KEYS + ("rnn_type", "rnn_hidden_dim", "rnn_num_layers")
+
+
+class ActorCriticRecurrent(_ActionStd, torch.nn.Module):
+    """rsl_rl's ``ActorCriticRecurrent``: a one-layer LSTM or GRU ``Memory`` in front of the actor MLP and another in front of the
+    critic MLP — ``obs -> normaliser -> rnn -> MLP`` (rsl_rl 3.x).  Modules and state-dict keys are rsl_rl's (``memory_a.rnn.*``,
+    ``memory_c.rnn.*``, ``actor.*``, ``critic.*``, ``std`` or ``log_std``), so checkpoints interchange; the hidden state is no part of it.
+
+    Step mode — ``act_mean(obs)`` / ``evaluate(obs)`` without ``masks`` — advances that net's hidden state (zeros at the first step)
+    by one step; ``reset(dones)`` zeroes the rows where ``dones`` is set (``None``: all), ``get_hidden_states()`` returns
+    ``(actor_state, critic_state)``.  Batch mode — ``masks=`` and ``hidden_states=`` given — runs the rnn over a padded
+    ``[T, ntraj, W]`` sequence from the given initial states and un-pads the outputs to ``[T, envs, H]`` in front of the MLP (with
+    ``unpad_index=`` through ``index_select``); the stored state is untouched.
+
+    ``rnn_num_layers`` other than 1, ``rnn_type`` other than ``"lstm"`` / ``"gru"`` and ``rnn_hidden_dim`` above 512 (the one-launch
+    step's limit, ``GF_MLP_MAX_HIDDEN``) raise ``ValueError`` naming the key."""
+
+    is_recurrent = True
+
+    def __init__(self, num_obs: int, num_actions: int, actor_hidden_dims: Sequence[int] = (512, 256, 128),
+                 critic_hidden_dims: Sequence[int] = (512, 256, 128), init_noise_std: float = 1.0, num_critic_obs: Optional[int] = None,
+                 actor_obs_normalization: bool = False, critic_obs_normalization: bool = False, noise_std_type: str = "scalar",
+                 rnn_type: str = "lstm", rnn_hidden_dim: int = 256, rnn_num_layers: int = 1):
+        super().__init__()
+        self._set_noise_std_type("ActorCriticRecurrent", noise_std_type)
+        if rnn_type not in ("lstm", "gru"):
+            raise ValueError(f"ActorCriticRecurrent: rnn_type={rnn_type!r} is not supported ('lstm' or 'gru')")
+        if int(rnn_num_layers) != 1:
+            raise ValueError(f"ActorCriticRecurrent: rnn_num_layers={rnn_num_layers} is not supported (only 1)")
+        if not 1 <= int(rnn_hidden_dim) <= nat.GF_MLP_MAX_HIDDEN:
+            raise ValueError(f"ActorCriticRecurrent: rnn_hidden_dim={rnn_hidden_dim} is not supported (1 to {nat.GF_MLP_MAX_HIDDEN})")
+        self.rnn_type, self.rnn_hidden_dim = rnn_type, int(rnn_hidden_dim)
+
+        num_critic_obs = num_obs if num_critic_obs is None else int(num_critic_obs)
+        self.memory_a = _Memory(num_obs, rnn_type, self.rnn_hidden_dim)
+        self.memory_c = _Memory(num_critic_obs, rnn_type, self.rnn_hidden_dim)
+        self.actor = _mlp([self.rnn_hidden_dim, *actor_hidden_dims, num_actions])
+        self.critic = _mlp([self.rnn_hidden_dim, *critic_hidden_dims, 1])
+        self._make_std(init_noise_std, num_actions)
+        self.actor_obs_normalizer = EmpiricalNormalization(num_obs) if actor_obs_normalization else torch.nn.Identity()
+        self.critic_obs_normalizer = EmpiricalNormalization(num_critic_obs) if critic_obs_normalization else torch.nn.Identity()
+        self._scratch = _NormScratch()
+
+    @classmethod
+    def from_train_cfg(cls, train_cfg: dict, num_obs: int, num_actions: int, num_critic_obs: Optional[int] = None) -> "ActorCriticRecurrent":
+        """As :meth:`ActorCriticMLP.from_train_cfg`, for ``policy.class_name = "ActorCriticRecurrent"`` with ``policy.rnn_type``,
+        ``rnn_hidden_dim`` and ``rnn_num_layers``."""
+        pol = _policy_cfg(train_cfg, "ActorCriticRecurrent", _RECURRENT_POLICY_KEYS, "ActorCriticRecurrent")
+        both = bool(train_cfg.get("empirical_normalization"))
+        return cls(num_obs, num_actions, tuple(pol.get("actor_hidden_dims", (512, 256, 128))), tuple(pol.get("critic_hidden_dims", (512, 256, 128))),
+                   float(pol.get("init_noise_std", 1.0)), num_critic_obs=num_critic_obs,
+                   actor_obs_normalization=both or bool(pol.get("actor_obs_normalization", False)),
+                   critic_obs_normalization=both or bool(pol.get("critic_obs_normalization", False)),
+                   noise_std_type=pol.get("noise_std_type", "scalar"), rnn_type=pol.get("rnn_type", "lstm"),
+                   rnn_hidden_dim=pol.get("rnn_hidden_dim", 256), rnn_num_layers=pol.get("rnn_num_layers", 1))
+
+    def act_mean(self, obs: torch.Tensor, masks=None, hidden_states=None, unpad_index=None) -> torch.Tensor:
+        return self.actor(self.memory_a(self.actor_obs_normalizer(obs), masks, hidden_states, unpad_index).squeeze(0))
+
+    def evaluate(self, obs: torch.Tensor, masks=None, hidden_states=None, unpad_index=None) -> torch.Tensor:
+        return self.critic(self.memory_c(self.critic_obs_normalizer(obs), masks, hidden_states, unpad_index).squeeze(0))
+
+    def get_hidden_states(self) -> tuple:
+        return self.memory_a.hidden_states, self.memory_c.hidden_states
+
+    def reset(self, dones=None) -> None:
+        self.memory_a.reset(dones)
+        self.memory_c.reset(dones)
+
+    update_normalization = ActorCriticMLP.update_normalization
 
 
 _STUDENT_TEACHER_KEYS = ("class_name", "activation", "student_hidden_dims", "teacher_hidden_dims", "init_noise_std", "noise_std_type",
@@ -1709,6 +2048,165 @@ class PolicyForward(_MlpForward):
     def value(self, critic_obs) -> torch.Tensor:
         """The critic's output ``[N, 1]`` (``policy.evaluate(critic_obs)``): one launch, a fresh tensor."""
         return self._one(critic_obs, "critic", self.policy.critic, lambda n, parts: self._fill(n, None, parts))
+
+
+class RecurrentForward(_MlpForward):
+    """A recurrent policy (:class:`ActorCriticRecurrent`, or rsl_rl's: ``memory_a.rnn`` / ``memory_c.rnn`` one-layer ``nn.LSTM`` or
+    ``nn.GRU``, ``actor`` / ``critic`` MLPs) as ``gf_mlp_recurrent_act`` reads it: normaliser, cell, MLP and the sampling in ONE launch
+    per step, weights read in place and looked up at every call (as :class:`PolicyForward`), the hidden state — the policy's own
+    ``memory_*.hidden_states`` tensors, created as zeros at the first step — read and advanced in place.
+
+    ``reset(dones)`` is rsl_rl's ``policy.reset(dones)`` without a launch: it keeps ``dones`` (a ``[N]`` bool or uint8 tensor, read
+    in place — the caller leaves it alone until both nets have stepped) as one pending flag row per net; the next launch of a net
+    reads zeros for the flagged rows of that net's state and the flag is consumed.  So after a rollout the bootstrap ``value()``
+    consumes the critic's pending reset and the first step of the next rollout the actor's, exactly the order rsl_rl's
+    ``compute_returns`` (``policy.evaluate(last_obs)`` advances the critic once more) leaves behind.  ``reset(None)`` forgets both states.
+
+    ``mean(obs)`` / ``value(critic_obs)``: an actor-only / critic-only launch that advances that net's state by one step — play-time
+    inference and the bootstrap value.  ``RolloutStorage.act_recurrent(forward, obs)``: the collection step.  On a backend without
+    the entry (the test-only CPU oracle) every call is the module's torch step under ``no_grad``.
+
+    ``own_state=True``: the forward steps hidden states of its own instead of the policy's memories' — a play-time policy next to a
+    training loop (``OnPolicyRunner.get_inference_policy``)."""
+
+    def __init__(self, policy, own_state: bool = False):
+        self.policy = policy
+        who = "RecurrentForward"
+        self.actor = _walk_mlp(getattr(policy, "actor", None), "actor", nat.GF_MLP_MAX_ACTIONS, who)
+        self.critic = _walk_mlp(getattr(policy, "critic", None), "critic", 1, who)
+        if self.actor is None or self.critic is None:
+            raise ValueError(f"{who}: the policy needs an actor and a critic")
+        self._memory = {"actor": getattr(policy, "memory_a", None), "critic": getattr(policy, "memory_c", None)}
+        if own_state:
+            self._memory = {name: _StateHolder(getattr(m, "rnn", None)) for name, m in self._memory.items()}
+        self._cell_type = {name: self._walk_rnn(m, "memory_a" if name == "actor" else "memory_c", getattr(self, name))
+                           for name, m in self._memory.items()}
+        self._normalizer("actor"), self._normalizer("critic")   # (refuses what the kernel cannot fold in)
+        std = self._read_std()
+        A = self.actor[-1][0].shape[0]
+        if std is None or not self._std_ok(std, A):
+            raise ValueError(f"{who}: policy.{self._std_name} must be a float32 [{A}] tensor")
+        self.num_actions = int(A)
+        self._args = nat.GfMlpRecurrentActArgs()
+        self._pending = {"actor": None, "critic": None}
+        self._keep = None
+
+    @staticmethod
+    def _walk_rnn(memory, name: str, layers) -> int:
+        """The cell type of ``policy.<name>.rnn``; ``ValueError`` naming what the kernel cannot run."""
+        who = f"RecurrentForward: policy.{name}.rnn"
+        rnn = getattr(memory, "rnn", None)
+        if not isinstance(rnn, (torch.nn.LSTM, torch.nn.GRU)):
+            raise ValueError(f"{who} must be an nn.LSTM or nn.GRU, not {type(rnn).__name__}")
+        if rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first or getattr(rnn, "proj_size", 0):
+            raise ValueError(f"{who} must have num_layers=1, bias=True, batch_first=False, no projection and one direction")
+        if not 1 <= rnn.hidden_size <= nat.GF_MLP_MAX_HIDDEN:
+            raise ValueError(f"{who} has hidden_size {rnn.hidden_size}; 1 to {nat.GF_MLP_MAX_HIDDEN}")
+        if rnn.input_size > nat.GF_MLP_MAX_INPUT_WIDTH:
+            raise ValueError(f"{who} reads {rnn.input_size} inputs; at most {nat.GF_MLP_MAX_INPUT_WIDTH}")
+        if int(layers[0][0].shape[1]) != rnn.hidden_size:
+            raise ValueError(f"{who} has hidden_size {rnn.hidden_size}; the MLP behind it reads {int(layers[0][0].shape[1])}")
+        for pn in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
+            p = getattr(rnn, pn)
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError(f"{who}.{pn} must be contiguous float32")
+        return nat.GF_RNN_LSTM if isinstance(rnn, torch.nn.LSTM) else nat.GF_RNN_GRU
+
+    def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
+        """The policy's current normaliser in front of the memory of net ``name``."""
+        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), int(self._memory[name].rnn.input_size),
+                              f"RecurrentForward: policy.{name}_obs_normalizer")
+
+    def _reader(self, name: str):
+        """What ``_segments`` checks an observation of net ``name`` against: the cell's input weights."""
+        return [(self._memory[name].rnn.weight_ih_l0, None)]
+
+    def state(self, name: str, n: int, dev) -> tuple:
+        """``(h, c)`` of net ``name`` (``c`` None for a GRU), ``[1, n, H]`` each: the memory's own tensors, zeros where it had none."""
+        m = self._memory[name]
+        H, lstm = m.rnn.hidden_size, self._cell_type[name] == nat.GF_RNN_LSTM
+        hs = m.hidden_states
+        parts = () if hs is None else (tuple(hs) if lstm else (hs,))
+        dev = torch.device(dev)
+        same_dev = lambda d: d.type == dev.type and (dev.index is None or d.index == dev.index)
+        ok = len(parts) == (2 if lstm else 1) and all(
+            s.shape == (1, n, H) and s.dtype == torch.float32 and s.is_contiguous() and same_dev(s.device) and not s.requires_grad for s in parts)
+        if hs is not None and not ok:
+            raise ValueError(f"RecurrentForward: the hidden state of the {name}'s memory is not [1, {n}, {H}] contiguous float32 on {dev}")
+        if hs is None:
+            parts = tuple(torch.zeros((1, n, H), device=dev, dtype=torch.float32) for _ in range(2 if lstm else 1))
+            m.hidden_states = parts if lstm else parts[0]
+        return parts[0], (parts[1] if lstm else None)
+
+    def reset(self, dones=None) -> None:
+        if dones is None or getattr(nat.get_backend(), "mlp_recurrent_act", None) is None:   # (None, or the test-only oracle backend)
+            for m in self._memory.values():
+                m.reset(dones)
+            if dones is None:
+                self._pending = {"actor": None, "critic": None}
+            return
+        if not isinstance(dones, torch.Tensor) or dones.dim() != 1 or dones.dtype not in (torch.bool, torch.uint8) or not dones.is_contiguous():
+            raise ValueError("RecurrentForward.reset(dones): dones must be a contiguous [N] bool or uint8 tensor")
+        flags = dones.view(torch.uint8)
+        for name, old in self._pending.items():
+            self._pending[name] = flags if old is None else (old | flags)
+
+    def _fill(self, n: int, actor_parts, critic_parts, save=None):
+        """The descriptor with the given nets (None: left out) pointed at the current weights, states and pending resets; ``save``:
+        ``{name: (h_save, c_save)}``.  The pending reset of every net in the launch is consumed."""
+        ra = self._args
+        ra.act.num_envs = n
+        keep = []
+        for name, net, cell, parts in (("actor", ra.act.actor, ra.actor_cell, actor_parts), ("critic", ra.act.critic, ra.critic_cell, critic_parts)):
+            _fill_net(net, getattr(self, name), parts, None if parts is None else self._normalizer(name))
+            cell.h_save = cell.c_save = cell.reset = None
+            if parts is None:
+                cell.type = nat.GF_RNN_NONE
+                continue
+            rnn = self._memory[name].rnn
+            h, c = self.state(name, n, parts[0].device)
+            flags = self._pending[name]
+            if flags is not None and (flags.shape[0] != n or flags.device != parts[0].device):
+                raise ValueError(f"RecurrentForward: the pending reset is [{flags.shape[0]}] on {flags.device}; the step has {n} rows on {parts[0].device}")
+            self._pending[name] = None
+            cell.type, cell.hidden = self._cell_type[name], rnn.hidden_size
+            cell.w_ih, cell.w_hh, cell.b_ih, cell.b_hh = (getattr(rnn, p).data_ptr() for p in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"))
+            cell.h, cell.c = h.data_ptr(), None if c is None else c.data_ptr()
+            cell.reset = None if flags is None else flags.data_ptr()
+            if save is not None and name in save:
+                hs, cs = save[name]
+                cell.h_save, cell.c_save = hs.data_ptr(), None if c is None else cs.data_ptr()
+            keep.append((parts, h, c, flags))
+        self._keep = keep
+        return ra
+
+    def _one(self, obs, name: str) -> torch.Tensor:
+        fn = getattr(nat.get_backend(), "mlp_recurrent_act", None)
+        parts = _segments(obs, "obs", None, None, self._reader(name))
+        if fn is None:   # (the test-only oracle backend) policy.act_mean / evaluate on this forward's state
+            with torch.no_grad():
+                norm, m = self._normalizer(name), self._memory[name]
+                x = _cat(parts)
+                out, m.hidden_states = m.rnn((x if norm is None else norm(x)).unsqueeze(0), m.hidden_states)
+                return getattr(self.policy, name)(out.squeeze(0))
+        n = int(parts[0].shape[0])
+        out = torch.empty((n, self.num_actions if name == "actor" else 1), device=parts[0].device, dtype=torch.float32)
+        ra = self._fill(n, parts if name == "actor" else None, parts if name == "critic" else None)
+        a = ra.act
+        a.std_is_log = a.std_per_env = 0
+        a.std = a.noise = a.actions = a.actions_out = a.mu_out = a.sigma_out = a.values_out = a.log_prob_out = None
+        a.mean, a.values = (None, out.data_ptr()) if name == "critic" else (out.data_ptr(), None)
+        self._keep_one = out
+        fn(ra)
+        return out
+
+    def mean(self, obs) -> torch.Tensor:
+        """The actor's output ``[N, A]`` for one more step of its memory (``policy.act_mean(obs)``): one launch, a fresh tensor."""
+        return self._one(obs, "actor")
+
+    def value(self, critic_obs) -> torch.Tensor:
+        """The critic's output ``[N, 1]`` for one more step of its memory (``policy.evaluate(critic_obs)``): one launch."""
+        return self._one(critic_obs, "critic")
 
 
 class DistillForward(_MlpForward):
@@ -2187,6 +2685,13 @@ class PPO(_FlatAdam):
     clipping, one rank.  ``update()`` returns the mean loss as ``"rnd"``.  A storage without that group, a missing
     ``num_outputs`` / ``predictor_hidden_dims`` / ``target_hidden_dims``, an unknown key, a bad ``weight_schedule``, another
     activation than ``"elu"`` or a multi-rank ``grad_sync`` raises ``ValueError`` naming ``rnd_cfg``.
+
+    A recurrent policy (``policy.is_recurrent``: :class:`ActorCriticRecurrent`) is updated on the trajectory minibatches of
+    ``storage.recurrent_mini_batch_generator`` — contiguous env ranges, not shuffled, ``generator`` unused: the memories run over the
+    padded sequences from the stored initial states in torch (BPTT is ``nn.LSTM`` / ``nn.GRU``'s), ``mu`` / ``value`` ``[T·envs, ·]``
+    go through the same ``gf_ppo_loss`` and ``gf_adam_step`` with the rnn parameters in the flat bucket; one more host read per
+    update (the trajectory offsets).  The rollout is collected with ``storage.act_recurrent`` (or ``storage.keep_rnn_start(policy)``
+    before a rollout on the module's torch step).  ``symmetry_cfg`` or ``rnd_cfg`` with such a policy raises ``ValueError`` naming the key.
     """
 
     def __init__(self, policy: "ActorCriticMLP", storage: RolloutStorage, grad_sync: Optional[GradientAllReduce] = None, **algorithm):
@@ -2221,6 +2726,10 @@ class PPO(_FlatAdam):
         if std is None or std.dim() != 1:
             raise ValueError("PPO needs a policy with act_mean(), evaluate() and a [A] std (or, with noise_std_type='log', log_std) parameter (ActorCriticMLP)")
         self.num_actions = int(std.numel())
+        self.recurrent = bool(getattr(policy, "is_recurrent", False))
+        for key, cfg_ in (("symmetry_cfg", symmetry_cfg), ("rnd_cfg", rnd_cfg)):
+            if self.recurrent and cfg_ is not None:
+                raise ValueError(f"PPO: {key} is not supported with a recurrent policy")
         self.symmetry = self._parse_symmetry(symmetry_cfg)   # None, or {"func", "augment", "mirror", "coeff"}
         self.rnd, rnd_lr = self._parse_rnd(rnd_cfg, grad_sync, std.device)   # None, or the RandomNetworkDistillation
         self.grad_sync = grad_sync if grad_sync is not None else GradientAllReduce(policy.parameters())
@@ -2341,7 +2850,13 @@ class PPO(_FlatAdam):
     def compute_returns(self, last_critic_obs: torch.Tensor) -> None:
         """rsl_rl ``PPO.compute_returns``: the critic's value of the bootstrap observation, then GAE over the storage.  The value is
         torch's forward (so results stay what they were); a loop that wants the one-launch forward passes
-        ``PolicyForward(policy).value(last_critic_obs)`` to ``storage.compute_returns`` itself."""
+        ``PolicyForward(policy).value(last_critic_obs)`` to ``storage.compute_returns`` itself.
+
+        With a recurrent policy this is rsl_rl's ``policy.evaluate(last_obs)`` in step mode: the critic's hidden state advances once
+        more — by the bootstrap observation, after the rollout's last reset — and the next rollout's first critic step goes on from
+        there, while the actor's state waits (with its last reset still to be applied) for the next rollout's first step.  A loop on
+        :class:`RecurrentForward` passes ``forward.value(last_critic_obs)`` to ``storage.compute_returns`` for the same step in one
+        launch: it consumes the critic's pending reset, the actor's stays pending."""
         with torch.no_grad():
             last_values = self.policy.evaluate(last_critic_obs)
         self.storage.compute_returns(last_values, gamma=self.gamma, lam=self.lam)
@@ -2352,7 +2867,10 @@ class PPO(_FlatAdam):
         host read of the update."""
         self._sums.zero_()
         norms = self._normalizers()
-        if self.symmetry is None:
+        if self.recurrent:
+            for batch in self.storage.recurrent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, norms):
+                self._minibatch_recurrent(batch)
+        elif self.symmetry is None:
             for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, generator=generator,
                                                            obs_normalizer=norms[0], critic_obs_normalizer=norms[1]):
                 self._minibatch(batch, norms)
@@ -2402,6 +2920,26 @@ class PPO(_FlatAdam):
             self._rnd_step(backend, b.indices)
 
     # -- one minibatch with a symmetry_cfg ---------------------------------------------------------------------------------------------
+    def _minibatch_recurrent(self, rb: RecurrentMiniBatch) -> None:
+        """One minibatch of trajectories: the memories run over the padded sequences from their initial states in torch (BPTT is
+        ``nn.LSTM`` / ``nn.GRU``'s), the un-padded outputs ``[T, envs, H]`` go through the MLPs, and ``mu`` / ``value`` ``[T·envs, ·]``
+        through the loss, clipping and Adam of ``_minibatch``.  The observations come normalised from the gather."""
+        sync, policy = self.grad_sync, self.policy
+        sync.zero_grad()
+        mu = policy.actor(policy.memory_a(rb.obs, rb.masks, rb.hid_a, rb.unpad_index))
+        value = policy.critic(policy.memory_c(rb.critic_obs, rb.masks, rb.hid_c, rb.unpad_index))
+        mu, value, b = mu.reshape(-1, mu.shape[-1]), value.reshape(-1, 1), rb.rows
+        backend = self.storage.env.backend
+        if getattr(backend, "ppo_loss", None) is not None:
+            gmu, gval = self._loss_hip(backend, mu, value, b)
+            torch.autograd.backward((mu, value), (gmu, gval.view_as(value)))
+        else:
+            self._loss_torch(mu, value, b)
+        self._reduce_kl()
+        sync.average()
+        sync.wait()
+        self._adam_step(backend)
+
     def _minibatch_symmetry(self, b: MiniBatch, norms=(None, None)) -> None:
         """One minibatch of ``_symmetry_batches`` (rsl_rl PPO.update with ``symmetry``).  ``norms``: the policy's normalisers —
         applied here, by ``gf_mirror_rows`` (or by the policy's own modules on a backend without it)."""

@@ -25,8 +25,8 @@ from typing import Callable, Optional
 import torch
 
 from . import gs
-from .learner import (ActorCriticMLP, DistillForward, Distillation, EpisodeStatistics, PolicyForward, PPO, RndForward, RolloutStorage,
-                      StudentTeacherMLP, _cat, _policy_std)
+from .learner import (ActorCriticMLP, ActorCriticRecurrent, DistillForward, Distillation, EpisodeStatistics, PolicyForward, PPO,
+                      RecurrentForward, RndForward, RolloutStorage, StudentTeacherMLP, _cat, _policy_std)
 from .wrappers import RslRlWrapper
 
 CHECKPOINT_VERSION = 1   # of the "genesis_forge_amd" block of a checkpoint file
@@ -70,8 +70,19 @@ class OnPolicyRunner:
     Attributes: ``alg`` (the ``PPO``; ``alg.policy``), ``current_learning_iteration``, ``log_dir``, ``git_status_repos`` (a plain list
     the reference assigns to; nothing reads it), ``last_log``.
 
-    Not here: multi-rank training, TensorBoard / W&B writers, recurrent policies, video handling, and the env's own state — as with
-    rsl_rl, a resumed run goes on from the env as it is."""
+    ``policy.class_name = "ActorCriticRecurrent"`` (rsl_rl's LSTM / GRU memory in front of the actor and the critic:
+    :class:`~.learner.ActorCriticRecurrent`, ``policy.rnn_type`` / ``rnn_hidden_dim`` / ``rnn_num_layers``): ``forward="hip"`` collects
+    with ``store.act_recurrent(fwd, …)`` — normaliser, cell, MLP, sampling and rows in one ``gf_mlp_recurrent_act`` launch, the hidden
+    state advanced in place — and resets the memories of finished episodes without a launch (``fwd.reset(dones)``: the next launch of
+    each net reads zeros there); ``"torch"`` steps the module and calls ``policy.reset(dones)``.  The bootstrap value advances the
+    critic's memory once more, as rsl_rl's ``compute_returns`` does.  The update runs ``PPO``'s trajectory minibatches.  Measured
+    per collection step (profiles/r26_recurrent.md, 256 units): ``"hip"`` is 3.5 x / 1.27 x / 1.10 x faster than ``"torch"`` at
+    4 096 / 16 384 / 65 536 envs with an LSTM, 4.1 x / 1.54 x / 1.34 x with a GRU — the one to use at every size measured.  A checkpoint carries rsl_rl's keys (``memory_a.rnn.*``, ``memory_c.rnn.*``, …) and, in this package's block, the
+    hidden states, so that a resumed run continues exactly; rsl_rl leaves them out and so does ``model_state_dict``.
+    ``get_inference_policy()`` then returns a callable that keeps a hidden state of its own and has ``.reset(dones=None)``.
+
+    Not here: multi-rank training, TensorBoard / W&B writers, video handling, and the env's own state — as with rsl_rl, a resumed run
+    goes on from the env as it is."""
 
     def __init__(self, env, train_cfg: dict, log_dir: Optional[str] = None, device=None, *, forward: str = "hip",
                  action_noise: Optional[torch.Generator] = None):
@@ -109,10 +120,16 @@ class OnPolicyRunner:
     def _build_algorithm(self, train_cfg: dict, base, store: RolloutStorage) -> None:
         """``self.alg`` (the policy inside it) and ``self._fwd``, the one-launch forward of ``forward="hip"``."""
         width = lambda group: sum(store._widths[m] for m in store.obs_groups[group])
-        policy = ActorCriticMLP.from_train_cfg(train_cfg, width("policy"), base.action_space.shape[0], num_critic_obs=width("critic"))
+        name = dict(train_cfg.get("policy", {})).get("class_name", "ActorCritic")
+        cls = ActorCriticRecurrent if name == "ActorCriticRecurrent" else ActorCriticMLP   # (any other name: from_train_cfg refuses it)
+        policy = cls.from_train_cfg(train_cfg, width("policy"), base.action_space.shape[0], num_critic_obs=width("critic"))
         policy = policy.to(self.device)
         self.alg = PPO(policy, store, **train_cfg["algorithm"])
-        self._fwd = PolicyForward(policy) if self.forward == "hip" else None
+        self._recurrent = policy.is_recurrent
+        if self._recurrent:
+            self._fwd = RecurrentForward(policy) if self.forward == "hip" else None
+        else:
+            self._fwd = PolicyForward(policy) if self.forward == "hip" else None
         self._rnd_fwd = RndForward(self.alg.rnd) if self.forward == "hip" and self.alg.rnd is not None else None
 
     # -- observations ---------------------------------------------------------------------------------------------------------------
@@ -142,10 +159,15 @@ class OnPolicyRunner:
         rnd = ppo.rnd
         for _ in range(self.num_steps_per_env):
             x, cx = self._inputs(obs, extras)
-            if self._fwd is not None:
+            row = store._act_row()
+            if self._fwd is not None and self._recurrent:
+                actions = store.act_recurrent(self._fwd, x, cx, noise=self._noise(n, A))
+            elif self._fwd is not None:
                 actions = store.act_policy(self._fwd, x, cx, noise=self._noise(n, A))
             else:
                 std, is_log = _policy_std(policy)   # (std, or log_std with std_is_log)
+                if self._recurrent and row == 0:
+                    store.keep_rnn_start(policy)
                 with torch.no_grad():
                     mean = policy.act_mean(_cat(x))
                     values = policy.evaluate(_cat(x if cx is None else cx))
@@ -158,6 +180,8 @@ class OnPolicyRunner:
                 rnd.update_normalization(rs)
                 store.intrinsic_reward(rnd if self._rnd_fwd is None else self._rnd_fwd, rs)
             store.process_env_step(truncated, gamma=ppo.gamma, episodes=stats)
+            if self._recurrent:   # rsl_rl PPO.process_env_step: policy.reset(dones)
+                (policy if self._fwd is None else self._fwd).reset(store.dones[row])
         return obs, extras
 
     def _returns(self, obs: torch.Tensor, extras: dict) -> None:
@@ -258,6 +282,8 @@ class OnPolicyRunner:
                                   "generator_state": self._generator.get_state(),
                                   "action_noise_state": None if self.action_noise is None else self.action_noise.get_state()},
         }
+        if getattr(self, "_recurrent", False):
+            saved["genesis_forge_amd"]["hidden_states"] = self._hidden_states()
         rnd = getattr(self.alg, "rnd", None)
         if rnd is not None:   # rsl_rl's two keys, and the schedule's counter in this package's block
             saved["rnd_state_dict"] = {k: v.detach().clone() for k, v in rnd.state_dict().items()}
@@ -308,7 +334,29 @@ class OnPolicyRunner:
             self._generator.set_state(ours["generator_state"].cpu())
             if self.action_noise is not None and ours.get("action_noise_state") is not None:
                 self.action_noise.set_state(ours["action_noise_state"].cpu())
+            if getattr(self, "_recurrent", False) and "hidden_states" in ours:
+                policy = self.alg.policy
+                for m, hs in zip((policy.memory_a, policy.memory_c), ours["hidden_states"]):
+                    to = lambda x: x.to(self.device).contiguous()
+                    m.hidden_states = None if hs is None else (tuple(to(x) for x in hs) if isinstance(hs, (tuple, list)) else to(hs))
+                if self._fwd is not None:
+                    self._fwd._pending = {"actor": None, "critic": None}
         return loaded.get("infos")
+
+    def _hidden_states(self) -> tuple:
+        """The memories' states as the next step will read them (copies; a pending reset of the one-launch forward applied)."""
+        out = []
+        for name, hs in zip(("actor", "critic"), self.alg.policy.get_hidden_states()):
+            if hs is None:
+                out.append(None)
+                continue
+            parts = [x.detach().clone() for x in (hs if isinstance(hs, tuple) else (hs,))]
+            flags = None if self._fwd is None else self._fwd._pending[name]
+            if flags is not None:
+                for x in parts:
+                    x[:, flags.to(torch.bool)] = 0.0
+            out.append(tuple(parts) if isinstance(hs, tuple) else parts[0])
+        return tuple(out)
 
     # -- inference ----------------------------------------------------------------------------------------------------------------------
     def get_inference_policy(self, device=None) -> Callable:
@@ -318,6 +366,8 @@ class OnPolicyRunner:
         self.eval_mode()
         if device is not None and torch.device(device).type != self.device.type:   # (moving the module would take its parameters out of PPO's flat buffer)
             raise ValueError(f"get_inference_policy: the policy lives on {self.device}; device={device!r} is not supported")
+        if getattr(self, "_recurrent", False):
+            return _RecurrentInference(RecurrentForward(self.alg.policy, own_state=True))
         if self._fwd is not None:
             return self._fwd.mean
         policy = self.alg.policy
@@ -337,6 +387,21 @@ class OnPolicyRunner:
         self.alg.policy.eval()
         if getattr(self.alg, "rnd", None) is not None:
             self.alg.rnd.eval()
+
+
+class _RecurrentInference:
+    """``policy(obs) -> [N, A]`` of a recurrent policy with a hidden state of its own: an actor-only ``gf_mlp_recurrent_act`` launch
+    per call (the module's torch step on a backend without it); ``reset(dones=None)`` zeroes the rows of finished episodes (``None``:
+    all) before the next call."""
+
+    def __init__(self, forward: RecurrentForward):
+        self._fwd = forward
+
+    def __call__(self, obs):
+        return self._fwd.mean(tuple(obs) if isinstance(obs, (list, tuple)) else obs)
+
+    def reset(self, dones=None) -> None:
+        self._fwd.reset(None if dones is None else dones.reshape(-1).to(torch.bool).clone())   # (a copy: the caller's tensor may change before the next call)
 
 
 class DistillationRunner(OnPolicyRunner):

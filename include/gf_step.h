@@ -1121,6 +1121,136 @@ typedef struct GfMlpActArgs {
 } GfMlpActArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * The collection step of a recurrent policy (rsl_rl ActorCriticRecurrent.act / evaluate inside PPO.act: a one-layer LSTM or GRU
+ * `Memory` in front of the actor MLP and another in front of the critic MLP).  In torch that is gf_mlp_act's 14 launches, two RNN
+ * calls on a sequence of length one and the hidden-state bookkeeping (the masked reset on `dones`, the copy of the state into the
+ * storage).  gf_mlp_recurrent_act is gf_mlp_act's launch with a cell between the input and the MLP of a net:
+ *     observations -> normaliser -> cell (h, c read; h', c' stored in place) -> h' -> MLP -> gf_mlp_act's outputs, word for word
+ * `act` is a gf_mlp_act descriptor; a net's segments (and in_mean / in_std) describe the CELL's input, of width `in` = the sum of the
+ * segment widths, and its layers[0] reads `hidden` columns.  A net whose cell has type GF_RNN_NONE is gf_mlp_act's net unchanged.
+ *
+ * The cell (torch.nn.LSTM / torch.nn.GRU with one layer, their tensors read in place; G = 4 gates i, f, g, o for LSTM, G = 3 gates
+ * r, z, n for GRU, gate g of unit j being row g · H + j):
+ *     h0, c0 = reset[n] != 0 ? 0 : h[n], c[n]                               (h_save / c_save, when given, receive h0 / c0)
+ *     LSTM:  p_g[j] = chain from (b_ih[gH + j] + b_hh[gH + j])  — one f32 addition — over k = 0 … in-1 of fma(x[n, k], w_ih[gH + j, k], ·),
+ *                     ascending, then over k = 0 … H-1 of fma(h0[k], w_hh[gH + j, k], ·), ascending: ONE chain per gate element;
+ *            c' = fl(fl(sig(p_f) · c0) + fl(sig(p_i) · tanh(p_g))),   h' = fl(sig(p_o) · tanh(c'))
+ *     GRU:   p_r, p_z as above;  n_x[j] = chain from b_ih[2H + j] over the input columns,  n_h[j] = chain from b_hh[2H + j] over the
+ *            hidden columns (two chains: r multiplies the second only);
+ *            n = tanh(fl(n_x + fl(sig(p_r) · n_h))),   h' = fl(fl(fl(1 - sig(p_z)) · n) + fl(sig(p_z) · h0))
+ *     sig(p) = 1.0f / (1.0f + expf(-p)) — one negation, the device libm's expf, one addition, one correctly rounded division;
+ *     tanh is the device libm's tanhf.  Every fl() is one f32 rounding (no contraction).
+ * h[n] and c[n] are then overwritten with h' and c' ([N, H], torch's [1, N, H] state viewed flat): a workgroup touches its own rows
+ * only, so in place is safe.  The MLP's first Linear reads h' as its input and the walk goes on as in gf_mlp_act: with the same h'
+ * handed to gf_mlp_act as a one-segment observation of width H and the same layers, mean, values, actions and every storage row are
+ * bit for bit gf_mlp_act's.  Row n's results depend on row n's inputs only — not on num_envs, the tile, or the other net.
+ *
+ * LDS: the tile's x pass and its h0 side by side, 2 × 65 664 B: one workgroup per CU (gf_mlp_act has two).  A wave keeps the four
+ * gate columns of one 32-unit block in its four accumulators; H > 128 takes (H / 32 + 3) / 4 rounds over the same staged x and h0.
+ *
+ * Refusals, before anything is launched: everything gf_mlp_act refuses for `act`, with its codes; GF_E_RANGE — a cell type outside
+ * GF_RNN_NONE … GF_RNN_GRU, `hidden` outside 1 … GF_MLP_MAX_HIDDEN, a cell on an absent net; GF_E_NULL — w_ih, w_hh, b_ih, b_hh or h
+ * missing, an LSTM without c, a GRU with c or c_save, h_save or c_save with GF_RNN_NONE; GF_E_UNSUPPORTED — both cells GF_RNN_NONE
+ * (gf_mlp_act is the call for that).  num_envs == 0 is a no-op.  No allocation, no copy, no synchronisation inside.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_RNN_NONE 0
+#define GF_RNN_LSTM 1
+#define GF_RNN_GRU 2
+
+typedef struct GfRnnCell {
+    int32_t type;               /* GF_RNN_NONE: the net has no cell; GF_RNN_LSTM; GF_RNN_GRU */
+    int32_t hidden;             /* H, 1 … GF_MLP_MAX_HIDDEN */
+    const float* w_ih;          /* [G * H, in] row-major: weight_ih_l0 read in place */
+    const float* w_hh;          /* [G * H, H]: weight_hh_l0 */
+    const float* b_ih;          /* [G * H] */
+    const float* b_hh;          /* [G * H] */
+    float* h;                   /* [N, H] in/out: the hidden state */
+    float* c;                   /* [N, H] in/out: the cell state (LSTM); NULL for GRU */
+    const uint8_t* reset;       /* [N] or NULL: a row with reset[n] != 0 reads zeros for h[n] / c[n] */
+    float* h_save;              /* [N, H] or NULL: out, the state the step started from (after the reset) */
+    float* c_save;              /* [N, H] or NULL (LSTM only) */
+} GfRnnCell;
+
+typedef struct GfMlpRecurrentActArgs {
+    GfMlpActArgs act;           /* gf_mlp_act's descriptor: a net with a cell reads `hidden` columns in layers[0] */
+    GfRnnCell actor_cell;
+    GfRnnCell critic_cell;
+} GfMlpRecurrentActArgs;
+
+/* ------------------------------------------------------------------------------------------
+ * The trajectory minibatches of a recurrent policy's update (rsl_rl split_and_pad_trajectories and
+ * RolloutStorage.recurrent_mini_batch_generator).  A rollout `[T, N]` is cut into trajectories at the dones — dones[T-1] counts as
+ * set — and enumerated env-major: env 0's in time order, then env 1's, …  A minibatch is a contiguous env range, so its
+ * trajectories are a contiguous range of that enumeration.
+ *
+ * gf_traj_table, once per update: counts[n] = the trajectories of env n, offsets[n] = their exclusive prefix sum (offsets[N] = the
+ * total), table[j] = (env, t0, len) of trajectory j, `[T · N, 3]` int32 of which the first offsets[N] rows are written.  One
+ * workgroup scans the envs 256 at a time (wave shuffle scan, wave totals through LDS, a carried total): deterministic, no atomics.
+ * Refusals: GF_E_NULL — args or a pointer; GF_E_RANGE — a negative size, T · N > (2^31 - 1) / 3.  T == 0 or N == 0 is a no-op.
+ *
+ * gf_traj_gather, one launch per minibatch = the trajectories [first_traj, first_traj + num_traj) of the envs
+ * [env_start, env_start + num_mb_envs):
+ *     groups[g].dst `[T, num_traj, W]`   row (s, j) = the group's observation of step t0_j + s of env_j for s < len_j — its segments side
+ *                                        by side (row (t, n) of a segment at rows + (t · N + n) · row_stride; 0: width), through the
+ *                                        normaliser where `mean` is given: (v - mean[k]) / (std[k] + eps), gf_minibatch_gather's
+ *                                        operations — and zeros from len_j on (padding is not normalised).  width == 0: no such group.
+ *     masks `[T, num_traj]` uint8        1 where s < len_j
+ *     unpad_index `[num_mb_envs · T]`    element (env - env_start) · T + t = j · T + (t - t0_j): where step t of that env sits in the
+ *                                        `[num_traj, T]`-flattened padded batch (index_select on it is rsl_rl's unpad_trajectories)
+ *     states[k].h0 / c0 `[num_traj, H]`  the rollout-start state h_start / c_start `[N, H]` of env_j where t0_j == 0, zeros elsewhere:
+ *                                        a trajectory that starts later starts behind a done.  hidden == 0: no such net; c0 NULL: a GRU.
+ * Refusals: GF_E_NULL — args, table, masks, unpad_index, a group's dst / segment, mean without std, h_start / h0, c0 without
+ * c_start, a pointer of an absent group or net; GF_E_RANGE — sizes < 1 (num_traj, first_traj, env_start, num_mb_envs < 0), an env
+ * range past num_envs, num_traj outside num_mb_envs … T · num_mb_envs, a trajectory range past table_rows, a segment count outside
+ * 1 … GF_MLP_MAX_INPUTS, segment widths that do not add up to `width`, width > GF_MLP_MAX_INPUT_WIDTH, hidden > GF_MLP_MAX_HIDDEN.
+ * num_traj == 0 is a no-op.  No allocation, no copy, no synchronisation inside either.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct GfTrajTableArgs {
+    int32_t num_steps;          /* T */
+    int32_t num_envs;           /* N */
+    const uint8_t* dones;       /* [T, N] */
+    int32_t* counts;            /* [N] out */
+    int32_t* offsets;           /* [N + 1] out */
+    int32_t* table;             /* [T * N, 3] out: (env, t0, len) */
+} GfTrajTableArgs;
+
+typedef struct GfTrajGroup {
+    int32_t num_inputs;         /* 1 … GF_MLP_MAX_INPUTS */
+    int32_t width;              /* W = the sum of the segment widths; 0: the group is absent */
+    GfMlpSegment inputs[GF_MLP_MAX_INPUTS];   /* [T * N, width] each */
+    const float* mean;          /* [W] or NULL */
+    const float* std;           /* [W] (required with mean) */
+    float eps;
+    int32_t _pad;
+    float* dst;                 /* [T, num_traj, W] out */
+} GfTrajGroup;
+
+typedef struct GfTrajState {
+    int32_t hidden;             /* H; 0: the net is absent */
+    int32_t _pad;
+    const float* h_start;       /* [N, H] the rollout-start state */
+    const float* c_start;       /* [N, H] (with c0) */
+    float* h0;                  /* [num_traj, H] out */
+    float* c0;                  /* [num_traj, H] out, or NULL */
+} GfTrajState;
+
+typedef struct GfTrajGatherArgs {
+    int32_t num_steps;          /* T */
+    int32_t num_envs;           /* N */
+    int32_t first_traj;
+    int32_t num_traj;
+    int32_t env_start;
+    int32_t num_mb_envs;
+    int32_t table_rows;         /* rows of `table` that gf_traj_table wrote (offsets[N]) */
+    int32_t _pad;
+    const int32_t* table;       /* gf_traj_table's */
+    GfTrajGroup groups[2];      /* the actor's and the critic's observation group */
+    GfTrajState states[2];      /* the actor's and the critic's memory */
+    uint8_t* masks;             /* [T, num_traj] out */
+    int64_t* unpad_index;       /* [num_mb_envs * T] out */
+} GfTrajGatherArgs;
+
+/* ------------------------------------------------------------------------------------------
  * The collection step of teacher–student distillation (rsl_rl Distillation.act: StudentTeacher.act on the deployable observations,
  * StudentTeacher.evaluate on the privileged ones).  The two MLPs have no data dependency, and at a few thousand envs one net leaves
  * half the device idle (N / GF_MLP_TILE_ROWS workgroups per net): gf_mlp_distill_act runs both in ONE launch, grid y = net, with
@@ -1347,7 +1477,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs, 31 GfMirrorRowsArgs, 32 GfMirrorLossArgs, 33 GfMlpDistillArgs, 34 GfBcLossArgs, 35 GfRndRewardArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs, 31 GfMirrorRowsArgs, 32 GfMirrorLossArgs, 33 GfMlpDistillArgs, 34 GfBcLossArgs, 35 GfRndRewardArgs, 36 GfMlpRecurrentActArgs, 37 GfRnnCell, 38 GfTrajTableArgs, 39 GfTrajGatherArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -1377,6 +1507,9 @@ int gf_ppo_loss(const GfPpoLossArgs* a, void* stream);           /* minibatch lo
 int gf_mirror_rows(const GfMirrorRowsArgs* a, void* stream);     /* originals + mirrored copies of up to four row fields, and the replicated per-row scalars, in one launch (rsl_rl PPO.update: data_augmentation_func, torch.cat, repeat) */
 int gf_mirror_loss(const GfMirrorLossArgs* a, void* stream);     /* symmetry loss and its gradient w.r.t. the mirrored rows' mu (rsl_rl PPO.update: MSELoss(mean_actions[mb:], mirrored mean_actions[:mb].detach()) and its backward) */
 int gf_mlp_act(const GfMlpActArgs* a, void* stream);             /* actor + critic MLP forward on the f32 matrix cores, then gf_policy_act's sampling and rows, in one launch (rsl_rl ActorCritic.act / evaluate inside PPO.act) */
+int gf_mlp_recurrent_act(const GfMlpRecurrentActArgs* a, void* stream); /* gf_mlp_act with an LSTM / GRU cell in front of each MLP, the hidden state read and advanced in place, in one launch (rsl_rl ActorCriticRecurrent.act / evaluate inside PPO.act) */
+int gf_traj_table(const GfTrajTableArgs* a, void* stream);       /* the trajectories of a rollout: per-env counts, their prefix sum and (env, t0, len), once per update (rsl_rl split_and_pad_trajectories) */
+int gf_traj_gather(const GfTrajGatherArgs* a, void* stream);     /* one minibatch of trajectories: padded normalised observations, masks, the un-pad index and the initial states in one launch (rsl_rl recurrent_mini_batch_generator) */
 int gf_mlp_distill_act(const GfMlpDistillArgs* a, void* stream); /* student + teacher MLP forward in one launch, the student sampled by gf_policy_act's row code (rsl_rl Distillation.act: StudentTeacher.act / evaluate) */
 int gf_bc_loss(const GfBcLossArgs* a, void* stream);             /* behaviour-cloning loss of one time step (mse / huber) and its gradient w.r.t. the student's mean (rsl_rl Distillation.update: loss_fn(actions, privileged_actions) and its backward) */
 int gf_rnd_reward(const GfRndRewardArgs* a, void* stream);       /* target + predictor MLP forward, their distance, the reward normaliser and the storage row's add in one launch (two with the normaliser updating) (rsl_rl RandomNetworkDistillation.get_intrinsic_reward inside PPO.process_env_step) */

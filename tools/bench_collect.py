@@ -24,9 +24,14 @@ both normalisers on): after env.step() every form updates the state normaliser a
 ``rsl_rl`` with the module's torch lines (``RandomNetworkDistillation.get_intrinsic_reward``: one host read per step), ``fused`` /
 ``fused_mlp`` with ``RolloutStorage.intrinsic_reward(RndForward(rnd), …)`` (gf_rnd_reward) — and one more line per size times the RND
 step ALONE in both forms, alternated in one process (``"form": "rnd_hip"`` / ``"rnd_torch"``).
+``--policy recurrent [--rnn-type lstm|gru] [--rnn-hidden-dim 256]``: an ``ActorCriticRecurrent`` policy; per size three loops in ONE
+process, their batches alternated: ``recurrent_hip`` (``RolloutStorage.act_recurrent``: normaliser, cell, MLP, sampling and rows in one
+gf_mlp_recurrent_act launch, ``RecurrentForward.reset(dones)`` without a launch), ``recurrent_torch`` (the module's step, ``act`` and
+``policy.reset(dones)``) and ``mlp_hip`` (the ``fused_mlp`` loop of the MLP policy), one JSON line each.
 ``collector()`` builds one such loop and times batches of it, for scripts that alternate several forms in one process.
     python tools/bench_collect.py [--sizes 4096,16384,65536] [--forms rsl_rl,fused,fused_mlp] [--steps 240] [--warmup 48] [--reps 5] [--normalize] [--noise-std-type scalar|log]
-                                  [--config go2_cmd|gait] [--history rows|frames] [--output fresh|window] [--rnd]"""
+                                  [--config go2_cmd|gait] [--history rows|frames] [--output fresh|window] [--rnd]
+                                  [--policy mlp|recurrent] [--rnn-type lstm|gru] [--rnn-hidden-dim 256]"""
 import argparse
 import json
 import os
@@ -39,7 +44,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "genesis-forge_amd"))
 import torch
 from genesis_forge_amd import gs, tasks
-from genesis_forge_amd.learner import (ActorCriticMLP, EpisodeStatistics, PolicyForward, RandomNetworkDistillation, RndForward, RolloutStorage,
+from genesis_forge_amd.learner import (ActorCriticMLP, ActorCriticRecurrent, EpisodeStatistics, RecurrentForward, PolicyForward, RandomNetworkDistillation, RndForward, RolloutStorage,
                                        _rnd_reward_torch)
 from genesis_forge_amd.managers import ObservationManager
 
@@ -87,7 +92,7 @@ class collector:
     """One collection loop: ``batch(steps)`` runs ``steps`` of it and returns µs per step (ending in a device synchronise)."""
 
     def __init__(self, n: int, form: str, normalize: bool = False, config: str = "go2_cmd", history: str = "rows", output: str = "fresh",
-                 noise_std_type: str = "scalar", rnd: bool = False):
+                 noise_std_type: str = "scalar", rnd: bool = False, rnn_type: str = "lstm", rnn_hidden_dim: int = 256):
         old, ObservationManager.default_output = ObservationManager.default_output, output
         try:   # (the managers are created by env.config(), i.e. inside build())
             env = tasks.BASELINE_CONFIGS[config][1](n)
@@ -101,7 +106,10 @@ class collector:
             groups["rnd_state"] = ["policy"]
         self.store = RolloutStorage(env, T, obs_groups=groups, history=history).attach()
         self.store.begin(*self.state)
-        self.step, self.stats, self.rewbuffer = _make_step(env, self.store, form, normalize, noise_std_type, rnd)
+        if form.startswith("recurrent"):
+            self.step, self.stats, self.rewbuffer = _make_recurrent_step(env, self.store, form, normalize, rnn_type, rnn_hidden_dim)
+        else:
+            self.step, self.stats, self.rewbuffer = _make_step(env, self.store, form, normalize, noise_std_type, rnd)
 
     def batch(self, steps: int) -> float:
         obs, extras = self.state
@@ -200,6 +208,58 @@ def _make_step(env, store, form: str, normalize: bool, noise_std_type: str = "sc
     return step, stats, rewbuffer
 
 
+def _make_recurrent_step(env, store, form: str, normalize: bool, rnn_type: str, hidden: int):
+    """``recurrent_hip`` / ``recurrent_torch``: one collection step of an ActorCriticRecurrent policy (the critic reads the policy group)."""
+    n, A = env.num_envs, env.action_space.shape[0]
+    torch.manual_seed(0)
+    policy = ActorCriticRecurrent(store.obs_width, A, actor_obs_normalization=normalize, critic_obs_normalization=normalize,
+                                  rnn_type=rnn_type, rnn_hidden_dim=hidden).to(gs.device)
+    stats, gamma = EpisodeStatistics(n), 0.99
+    if form == "recurrent_hip":
+        fwd = RecurrentForward(policy)
+
+        def step(obs, extras):
+            row = store._act_row()
+            actions = store.act_recurrent(fwd, obs)
+            obs, _rew, _term, trunc, extras = env.step(actions)
+            if normalize:
+                policy.update_normalization(obs)
+            store.process_env_step(trunc, gamma=gamma, episodes=stats)
+            fwd.reset(store.dones[row])
+            return obs, extras
+    else:
+
+        def step(obs, extras):
+            row = store._act_row()
+            actions = store.act(policy.act_mean(obs), policy.std, policy.evaluate(obs))
+            obs, _rew, _term, trunc, extras = env.step(actions)
+            if normalize:
+                policy.update_normalization(obs)
+            store.process_env_step(trunc, gamma=gamma, episodes=stats)
+            policy.reset(store.dones[row])
+            return obs, extras
+
+    return step, stats, None
+
+
+def run_recurrent(n: int, steps: int, warmup: int, reps: int, normalize: bool, rnn_type: str, hidden: int) -> list:
+    """The three loops of ``--policy recurrent`` in one process, batches alternated."""
+    forms = ("recurrent_hip", "recurrent_torch", "mlp_hip")
+    cs = {f: collector(n, "fused_mlp" if f == "mlp_hip" else f, normalize, rnn_type=rnn_type, rnn_hidden_dim=hidden) for f in forms}
+    for c in cs.values():
+        c.batch(warmup)
+    times = {f: [] for f in forms}
+    for _ in range(reps):
+        for f in forms:
+            times[f].append(cs[f].batch(steps))
+    out = [{"tool": "bench_collect", "policy": "recurrent", "rnn_type": rnn_type, "rnn_hidden_dim": hidden, "num_envs": n, "form": f,
+            "normalize": normalize, "steps": steps, "warmup": warmup, "reps": reps, "us_per_step_best": round(min(t), 2),
+            "us_per_step_median": round(statistics.median(t), 2), "us_per_step_all": [round(x, 2) for x in t]} for f, t in times.items()]
+    for c in cs.values():
+        c.store.detach()
+    return out
+
+
 def run(n: int, form: str, steps: int, warmup: int, reps: int, normalize: bool = False, config: str = "go2_cmd", history: str = "rows",
         output: str = "fresh", noise_std_type: str = "scalar", rnd: bool = False) -> dict:
     c = collector(n, form, normalize, config, history, output, noise_std_type, rnd)
@@ -264,6 +324,9 @@ def main() -> None:
     ap.add_argument("--output", default="fresh", choices=["fresh", "window"], help="what the ObservationManagers hand out")
     ap.add_argument("--noise-std-type", default="scalar", choices=["scalar", "log"], help="the policy's std parameter: std, or log_std")
     ap.add_argument("--rnd", action="store_true", help="random network distillation: the intrinsic reward joins every step; the RND step alone is timed too")
+    ap.add_argument("--policy", default="mlp", choices=["mlp", "recurrent"], help="recurrent: the one-launch recurrent step against the module's torch step and the MLP policy's loop")
+    ap.add_argument("--rnn-type", default="lstm", choices=["lstm", "gru"])
+    ap.add_argument("--rnn-hidden-dim", type=int, default=256)
     a = ap.parse_args()
     if a.output == "window" and a.history != "frames":
         raise SystemExit("--output window needs --history frames: a row storage copies contiguous observation rows")
@@ -271,6 +334,10 @@ def main() -> None:
         raise SystemExit("bench_collect.py times the collection loop on a ROCm GPU: no device visible")
     gs.set_device("cuda:0")
     for n in (int(x) for x in a.sizes.split(",")):
+        if a.policy == "recurrent":
+            for line in run_recurrent(n, a.steps, a.warmup, a.reps, a.normalize, a.rnn_type, a.rnn_hidden_dim):
+                print(json.dumps(line), flush=True)
+            continue
         for form in a.forms.split(","):
             if form not in ("rsl_rl", "fused", "fused_mlp"):
                 raise SystemExit(f"unknown form {form!r}")

@@ -5,6 +5,7 @@ PPO.update restated in torch (tests/rsl_rl_ppo.py: torch.optim.Adam, clip_grad_n
 usage: python tools/bench_update.py [--sizes go2_cmd:4096,go2_cmd:16384,go2_cmd:65536,gait:4096] [--steps 24] [--reps 7]
                                     [--forms rsl_rl,fused] [--out FILE] [--noise-std-type scalar|log]
                                     [--symmetry none|augment|mirror|both] [--rnd]
+                                    [--policy mlp|recurrent] [--rnn-type lstm|gru] [--rnn-hidden-dim 256]
 
 Per size: one rollout of T steps is collected with act / process_env_step by the reference policy (ELU MLPs 512-256-128, as
 examples/*/train.py) and its returns computed; then every rep runs each form once, alternating, from the same initial weights,
@@ -18,7 +19,10 @@ that differ only in ``--reps`` differ by exactly that many updates, which gives 
 ``--symmetry``: both forms get rsl_rl's ``symmetry_cfg`` with the Go2 left/right mirror (``go2_mirror``) — ``augment``: data
 augmentation, ``mirror``: the mirror loss, ``both``; the torch form is then tests/rsl_rl_symmetry.py.
 ``--rnd``: both forms get rsl_rl's ``rnd_cfg`` (``rnd_state`` = the policy observation, a 256-128 predictor and target with 16
-outputs, both normalisers on): every minibatch also trains the predictor; the torch form is then tests/rsl_rl_rnd.py."""
+outputs, both normalisers on): every minibatch also trains the predictor; the torch form is then tests/rsl_rl_rnd.py.
+``--policy recurrent [--rnn-type lstm|gru] [--rnn-hidden-dim 256]``: an ``ActorCriticRecurrent`` policy, its rollout collected with
+``act_recurrent``; ``fused`` is ``learner.PPO`` on the trajectory minibatches (gf_traj_table, gf_traj_gather), ``rsl_rl`` is
+tests/rsl_rl_recurrent.py (``split_and_pad_trajectories`` once per update, the per-step saved hidden states)."""
 import argparse
 import copy
 import json
@@ -93,6 +97,39 @@ def rollout(config: str, n: int, T: int, noise_std_type: str = "scalar", rnd: bo
     return env, st, policy
 
 
+def recurrent_rollout(config: str, n: int, T: int, rnn_type: str, hidden: int):
+    """A rollout of an ActorCriticRecurrent policy through act_recurrent, and rsl_rl's per-step saved hidden states next to it."""
+    from genesis_forge_amd.learner import ActorCriticRecurrent, RecurrentForward, RolloutStorage
+    from genesis_forge_amd.tasks import BASELINE_CONFIGS
+
+    env = BASELINE_CONFIGS[config][1](n)
+    env.build()
+    env.seed(1)
+    obs, extras = env.reset()
+    st = RolloutStorage(env, T).attach()
+    st.begin(obs, extras)
+    st.seed(2)
+    torch.manual_seed(0)
+    policy = ActorCriticRecurrent(st.obs_width, env.action_space.shape[0], rnn_type=rnn_type, rnn_hidden_dim=hidden).cuda()
+    fwd = RecurrentForward(policy)
+    saved, prev = {"actor": [], "critic": []}, None
+    for t in range(T):
+        for name in saved:
+            parts = [x.clone() for x in fwd.state(name, n, "cuda") if x is not None]
+            if prev is not None:
+                for x in parts:
+                    x[:, prev] = 0.0
+            saved[name].append(parts)
+        actions = st.act_recurrent(fwd, obs)
+        obs, _r, _te, tr, extras = env.step(actions)
+        st.process_env_step(tr)
+        prev = st.dones[t].clone()
+        fwd.reset(st.dones[t])
+    st.compute_returns(fwd.value(obs), gamma=ALGO["gamma"], lam=ALGO["lam"])
+    stack = lambda steps: tuple(torch.stack([s[i] for s in steps]) for i in range(len(steps[0])))
+    return env, st, policy, (stack(saved["actor"]), stack(saved["critic"]))
+
+
 def synthetic(config: str, n: int, T: int, noise_std_type: str = "scalar", rnd: bool = False):
     """A storage of random rows with the shapes of ``config`` and no env behind it (the dispatch-count runs: every launch of the
     process then belongs to the set-up or to an update)."""
@@ -148,6 +185,51 @@ def go2_mirror(st):
     return MirrorSymmetry(op, os_, *GO2_JOINT_MIRROR, critic_obs_perm=cp, critic_obs_sign=cs)
 
 
+def recurrent_update(config: str, n: int, args, forms) -> list:
+    """--policy recurrent: one size, the forms alternated per rep from the same initial weights."""
+    import rsl_rl_recurrent as R
+    from genesis_forge_amd.learner import PPO
+
+    env, st, policy0, (saved_a, saved_c) = recurrent_rollout(config, n, args.steps, args.rnn_type, args.rnn_hidden_dim)
+    init = copy.deepcopy(policy0.state_dict())
+    obs = st.observation_rows()[:args.steps]
+    A = env.action_space.shape[0]
+    times, last = {f: [] for f in forms}, {}
+    for rep in range(args.reps + 1):   # rep 0: warm-up
+        for form in forms:
+            if form == "fused":
+                policy = copy.deepcopy(policy0)
+                policy.load_state_dict(init)
+                policy.reset()
+                algo = PPO(policy, st, **ALGO)
+                update = algo.update
+            else:
+                policy = R.RslRlActorCriticRecurrent(st.obs_width, A, (512, 256, 128), (512, 256, 128), rnn_type=args.rnn_type,
+                                                     rnn_hidden_dim=args.rnn_hidden_dim).cuda()
+                policy.load_state_dict(init)
+                algo = R.RslRlRecurrentPPO(policy, st, **ALGO)
+                update = lambda: algo.update(obs, obs, saved_a, saved_c)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            losses = update()
+            torch.cuda.synchronize()
+            if rep:
+                times[form].append((time.perf_counter() - t0) * 1e3)
+            last[form] = (losses, algo.learning_rate)
+    rows = []
+    for form in forms:
+        row = dict(config=config, num_envs=n, steps=args.steps, form=form, reps=args.reps, policy="recurrent", rnn_type=args.rnn_type,
+                   rnn_hidden_dim=args.rnn_hidden_dim, trajectories=int(st.dones[:-1].sum()) + n,
+                   best_ms=round(min(times[form]), 3) if times[form] else None,
+                   median_ms=round(statistics.median(times[form]), 3) if times[form] else None,
+                   all_ms=[round(x, 3) for x in times[form]], losses=last[form][0], lr=last[form][1], device=torch.cuda.get_device_name(0))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    del env, st, policy0
+    torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="go2_cmd:4096,go2_cmd:16384,go2_cmd:65536,gait:4096")
@@ -159,6 +241,9 @@ def main():
     ap.add_argument("--noise-std-type", default="scalar", choices=["scalar", "log"], help="the policy's std parameter: std, or log_std")
     ap.add_argument("--symmetry", default="none", choices=["none", "augment", "mirror", "both"], help="rsl_rl's symmetry_cfg with the Go2 mirror")
     ap.add_argument("--rnd", action="store_true", help="rsl_rl's rnd_cfg: every minibatch also trains the RND predictor")
+    ap.add_argument("--policy", default="mlp", choices=["mlp", "recurrent"], help="recurrent: ActorCriticRecurrent on trajectory minibatches")
+    ap.add_argument("--rnn-type", default="lstm", choices=["lstm", "gru"])
+    ap.add_argument("--rnn-hidden-dim", type=int, default=256)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_update.py measures on a ROCm GPU: none is visible")
@@ -171,6 +256,9 @@ def main():
     lines = []
     for spec in args.sizes.split(","):
         config, n = spec.split(":")
+        if args.policy == "recurrent":
+            lines += recurrent_update(config, int(n), args, forms)
+            continue
         env, st, policy0 = (synthetic if args.synthetic else rollout)(config, int(n), args.steps, args.noise_std_type, args.rnd)
         init = copy.deepcopy(policy0.state_dict())
         algo_cfg = dict(ALGO)

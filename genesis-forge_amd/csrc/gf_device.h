@@ -108,8 +108,11 @@ __device__ __forceinline__ V3 rot_inv(const float4 q, const V3 v) {
     return o;
 }
 
-__device__ __forceinline__ float norm3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
-__device__ __forceinline__ float norm2(float x, float y) { return sqrtf(x * x + y * y); }
+// torch.norm(v, dim=-1) on CPU: the squares accumulate through fused multiply-adds in component order, so the
+// sum rounds twice (3-vector) or once (2-vector) less than plain products would.  An explicit fmaf fuses under -ffp-contract=off;
+// these two are the only fused operations of the step kernels.
+__device__ __forceinline__ float norm3(float x, float y, float z) { return sqrtf(fmaf(z, z, fmaf(y, y, x * x))); }
+__device__ __forceinline__ float norm2(float x, float y) { return sqrtf(fmaf(y, y, x * x)); }
 
 __device__ __forceinline__ V3 load3(const float* __restrict__ p, int64_t n) {
     const float* r = p + 3 * n;

@@ -65,5 +65,17 @@ def current_actions(env, action_manager=None) -> torch.Tensor:
 
 def contact_force(env, contact_manager) -> torch.Tensor:
     """Per-link contact force magnitude, shape (num_envs, num_links) (observations.py:182-193)."""
-    out = torch.norm(contact_manager.contacts[:, :, :], dim=-1)
+    # A direct call runs the observation kernel's own norm item (one launch): torch.norm on the device rounds differently from the
+    # CPU torch.norm the reference is pinned to (SURVEY.md Appendix B), so an eager norm here would not be the value a fused
+    # observation of the same item gives.
+    contacts = contact_manager.contacts
+    L = int(contacts.shape[1])
+    out = torch.empty((env.num_envs, L), device=gs.device, dtype=gs.tc_float)
+    a = nat.GfObservationArgs()
+    a.num_envs, a.num_items, a.obs_width, a.history_len = env.num_envs, 1, L, 1
+    a.contact[0].contacts, a.contact[0].num_links = contacts.data_ptr(), L
+    a.obs = out.data_ptr()
+    it = a.items[0]
+    it.op, it.width, it.i0, it.scale, it.noise = nat.GF_O_CONTACT_FORCE_NORM, L, 0, 1.0, 0.0
+    env.backend.call("observe", a, owner=None)
     return _tag(out, ("contact_norm", contact_manager))

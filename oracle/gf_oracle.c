@@ -95,8 +95,10 @@ static inline void rot_inv(const float* q, const float* v, float* o) {
     o[2] = (v[2] + w * t2) + (a * t1 - b * t0);
 }
 
-static inline float norm3(const float* v) { return sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
-static inline float norm2(float x, float y) { return sqrtf(x * x + y * y); }
+/* torch.norm(v, dim=-1) on CPU: the squares accumulate through fused multiply-adds in component order.
+ * libm's fmaf rounds once whether or not the build has an FMA instruction. */
+static inline float norm3(const float* v) { return sqrtf(fmaf(v[2], v[2], fmaf(v[1], v[1], v[0] * v[0]))); }
+static inline float norm2(float x, float y) { return sqrtf(fmaf(y, y, x * x)); }
 
 static inline void body_lin_vel(const GfEntityView* e, int64_t n, float* o) { rot_inv(e->quat + 4 * n, e->lin_vel + 3 * n, o); }
 static inline void body_ang_vel(const GfEntityView* e, int64_t n, float* o) { rot_inv(e->quat + 4 * n, e->ang_vel + 3 * n, o); }

@@ -12,7 +12,7 @@ order, which envs resample/reset, weights, op order — not torch's RNG stream.
 Usage: python tools/gen_golden.py                     rewrites the unit fixtures and the traj_go2_* trajectories
        python tools/gen_golden.py examples [key ...]  rewrites traj_ex_<key>.npz — the reference's own example files
                                                       (tests/example_cases.py: six examples at n = 8 + the multi-tile cases)
-       python tools/gen_golden.py entity_obs | contact_kernel   one unit fixture
+       python tools/gen_golden.py entity_obs | contact_kernel | mask_edges   one unit fixture
 """
 import math
 import os
@@ -638,6 +638,273 @@ def gen_orientation_sweep():
     print("orientation_sweep:", sum(m.size for m in masks), "cases,", int(sum(m.sum() for m in masks)), "fired")
 
 
+# ------------------------------------------------------------------------------------------------
+# mask_edges: every mask-valued decision at its boundary (tests/mask_edges_cases.py holds the env, the config and the block layout)
+# ------------------------------------------------------------------------------------------------
+def _ulps(x, k):
+    """float32 ``x`` moved by k representable values (k > 0: towards +inf)."""
+    x = np.float32(x)
+    for _ in range(abs(k)):
+        x = np.nextafter(x, np.float32(np.inf if k > 0 else -np.inf), dtype=np.float32)
+    return x
+
+
+def _oblique(rng, thr, n, dim):
+    """n random ``dim``-vectors whose exact length lies within ±4 ulp of float32(thr)."""
+    t32 = np.float32(thr)
+    sp = float(np.spacing(t32))
+    sp_below = float(t32) - float(np.nextafter(t32, np.float32(0.0), dtype=np.float32))
+    out = np.zeros((0, dim), dtype=np.float32)
+    while len(out) < n:
+        d = rng.standard_normal((2 * n, dim))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        # (aimed within one representable value of the threshold on either side — below a power of two they lie twice as dense —
+        # where the rounding of the sum of squares decides the comparison; the components' own rounding spreads them further)
+        k = rng.uniform(-1.0, 1.0, (2 * n, 1))
+        v = (d * (float(t32) + k * np.where(k > 0, sp, sp_below))).astype(np.float32)
+        exact = np.sqrt((v.astype(np.float64) ** 2).sum(axis=1))
+        out = np.concatenate([out, v[np.abs(exact - float(t32)) <= 4.0 * sp]])
+    return out[:n]
+
+
+def _codes(n):
+    """Placement codes (mask_edges_cases.link_index): the group of four rotates fastest, then the place in the group."""
+    i = np.arange(n)
+    return (4 * (i % 3) + (i // 3) % 4).astype(np.int8)
+
+
+def mask_edge_blocks(benign):
+    """name -> dict(thr, limit, variants, arrays): the inputs of every block, made from fixed seeds."""
+    import mask_edges_cases as mc
+
+    rng = np.random.RandomState(20260131)
+    blocks = {}
+    all_variants = list(range(len(mc.VARIANTS)))
+
+    def add(name, arrays, thr=5.0, limit=10.0, variants=None):
+        assert name not in blocks
+        n = {a.shape[0] for a in arrays.values()}
+        assert len(n) == 1 and n.pop() <= mc.N_ENVS, name
+        if "force" in arrays:   # up to MAX_FORCES forces per row, zero where a block places fewer
+            f = np.zeros((arrays["force"].shape[0], mc.MAX_FORCES, 3), dtype=np.float32)
+            f[:, : arrays["force"].shape[1]] = arrays["force"]
+            arrays = dict(arrays, force=f)
+        blocks[name] = dict(thr=thr, limit=limit, variants=all_variants if variants is None else variants, arrays=arrays)
+
+    def rep(key, n):
+        return np.repeat(benign[key][None], n, axis=0).copy()
+
+    # -- norm against a threshold, 3-vectors ---------------------------------------------------------------------------------------
+    for thr in mc.THRESHOLDS:
+        vs = [k for k, v in enumerate(mc.VARIANTS) if v["thr"] == thr]
+        t32 = np.float32(thr)
+        rows = []
+        for k in (-1, 0, 1):
+            for axis in range(3):
+                for sign in (1.0, -1.0):
+                    for _place in range(3):
+                        f = np.zeros(3, dtype=np.float32)
+                        f[axis] = np.float32(sign) * _ulps(t32, k)
+                        rows.append(f)
+        f = np.stack(rows)[:, None, :]
+        add(f"c3_{thr}_axis", {"force": f, "code": _codes(len(f))}, thr=thr, variants=vs)
+        f = _oblique(rng, thr, mc.N_ENVS, 3)[:, None, :]
+        add(f"c3_{thr}_oblique", {"force": f, "code": _codes(len(f))}, thr=thr, variants=vs)
+        # has_contact's count: 0, 1 or 2 links far over the threshold next to the probed one -> min_contacts - 1, min_contacts, min_contacts + 1
+        n = 3 * 64
+        f = np.zeros((n, 3, 3), dtype=np.float32)
+        f[:, 0] = _oblique(rng, thr, n, 3)
+        far = np.arange(n) // 64
+        f[far >= 1, 1, 0] = np.float32(3.0 * thr)
+        f[far >= 2, 2, 1] = np.float32(-3.0 * thr)
+        add(f"c3_{thr}_count", {"force": f, "code": _codes(n)}, thr=thr, variants=vs)
+        # the grace variant: episode_length = grace - 1, grace, grace + 1
+        f = _oblique(rng, thr, n, 3)[:, None, :]
+        ep = (mc.GRACE - 1 + np.arange(n) // 64).astype(np.int32)
+        add(f"c3_{thr}_grace", {"force": f, "code": _codes(n), "episode_length": ep}, thr=thr, variants=vs)
+
+    # -- norm against a threshold, 2-vectors (the xy command); a foot has just landed, so feet_air_time is non-zero where its mask is --
+    def landed(n):
+        cct, last = rep("cur_contact", n), rep("last_air", n)
+        cct[np.arange(n), np.arange(n) % 4] = np.float32(mc.DT)
+        last[np.arange(n), np.arange(n) % 4] = np.float32(0.45)
+        return {"cur_contact": cct, "last_air": last}
+
+    for cthr in mc.CMD_THRESHOLDS:
+        t32 = np.float32(cthr)
+        rows = []
+        for k in (-1, 0, 1):
+            for axis in range(2):
+                for sign in (1.0, -1.0):
+                    c = np.zeros(3, dtype=np.float32)
+                    c[axis] = np.float32(sign) * _ulps(t32, k)
+                    rows.append(c)
+        c = np.stack(rows)
+        add(f"cmd_{cthr}_axis", dict(landed(len(c)), command=c))
+        c = np.zeros((mc.N_ENVS, 3), dtype=np.float32)
+        c[:, :2] = _oblique(rng, cthr, mc.N_ENVS, 2)
+        add(f"cmd_{cthr}_oblique", dict(landed(len(c)), command=c))
+
+    # -- bad_orientation about oblique axes: the ±600-step sweep of orientation_sweep.npz, axis (cos φ, sin φ, 0) -------------------------
+    for ang in mc.LIMITS:
+        vs = [k for k, v in enumerate(mc.VARIANTS) if v["limit"] == ang]
+        thr = math.radians(ang) if ang < 82 else math.asin(0.99)
+        base = np.float32(min(thr, math.asin(0.99)))
+        tilt = base + np.arange(-600, 601, dtype=np.float64) * 2e-8
+        for phi in mc.AXES_DEG:
+            q = np.zeros((tilt.size, 4), dtype=np.float64)
+            q[:, 0] = np.cos(tilt / 2)
+            q[:, 1] = np.sin(tilt / 2) * math.cos(math.radians(phi))
+            q[:, 2] = np.sin(tilt / 2) * math.sin(math.radians(phi))
+            q32 = q.astype(np.float32)
+            add(f"tilt_{ang}_{phi}", {"quat": q32, "episode_length": np.full(len(q32), mc.GRACE + 1, dtype=np.int32)}, limit=ang, variants=vs)
+            if phi == 45.0:
+                add(f"tilt_{ang}_grace", {"quat": q32[::5].copy(), "episode_length": np.full(len(q32[::5]), mc.GRACE, dtype=np.int32)},
+                    limit=ang, variants=vs)
+
+    # -- scalar decisions ----------------------------------------------------------------------------------------------------------------
+    pos = rep("pos", 3)
+    pos[:, 2] = [_ulps(mc.MIN_HEIGHT, k) for k in (-1, 0, 1)]
+    add("height", {"pos": pos})
+    x_min, x_max, y_min, y_max = mc.BOUNDS   # the bounds the reference's way (terminations.py:126-128): Python doubles
+    edges = [(0, x_min + mc.BORDER_MARGIN), (0, x_max - mc.BORDER_MARGIN), (1, y_min + mc.BORDER_MARGIN), (1, y_max - mc.BORDER_MARGIN)]
+    pos = rep("pos", 12)
+    for e, (axis, bound) in enumerate(edges):
+        for k in (-1, 0, 1):
+            pos[3 * e + k + 1, axis] = _ulps(bound, k)
+    add("bounds", {"pos": pos})
+    mx = int(benign["max_episode_length"])
+    add("timeout", {"episode_length": np.array([mx - 1, mx, mx + 1], dtype=np.int32)})
+    # feet_air_time: current_contact_time around has_made_contact's two comparisons (> 0, < dt + 1e-8)
+    edge = np.float32(mc.DT + 1.0e-8)
+    vals = [np.float32(0.0), np.float32(1e-45), _ulps(mc.DT, -1), np.float32(mc.DT), _ulps(mc.DT, 1), _ulps(edge, -1), edge, _ulps(edge, 1)]
+    n = 4 * len(vals)
+    cct, last = rep("cur_contact", n), rep("last_air", n)
+    cct[np.arange(n), np.arange(n) % 4] = np.repeat(np.array(vals, dtype=np.float32), 4)
+    last[np.arange(n), np.arange(n) % 4] = np.float32(0.45)
+    add("air_contact_time", {"cur_contact": cct, "last_air": last})
+    # … last_air_time around the clamp (time_threshold_max - time_threshold), and below time_threshold (a negative term)
+    vals = [_ulps(mc.AIR_THRESHOLD_MAX, k) for k in range(-8, 9)] + [np.float32(0.0), np.float32(0.1), _ulps(mc.AIR_THRESHOLD, -1),
+                                                                    np.float32(mc.AIR_THRESHOLD), _ulps(mc.AIR_THRESHOLD, 1)]
+    n = 4 * len(vals)
+    cct, last = rep("cur_contact", n), rep("last_air", n)
+    cct[np.arange(n), np.arange(n) % 4] = np.float32(mc.DT)
+    last[np.arange(n), np.arange(n) % 4] = np.repeat(np.array(vals, dtype=np.float32), 4)
+    add("air_last_air_time", {"cur_contact": cct, "last_air": last})
+    return blocks
+
+
+def gen_mask_edges():
+    """tests/golden/mask_edges.npz: inputs and the reference's outputs of every block — per-term calls, one TerminationManager.step() +
+    RewardManager.step() of the mask-term config, the air-time arrays after the feet manager's air-time update."""
+    import types
+
+    import mask_edges_cases as mc
+    from genesis_forge import managers as ref_managers
+
+    api = types.SimpleNamespace(ManagedEnvironment=ref.ManagedEnvironment, managers=ref_managers, scene=my_scene, reset=reset, rewards=rewards,
+                                terminations=terminations, observations=observations)
+    envs = []
+    for k in range(len(mc.VARIANTS)):
+        env = mc.make_env(api, k)
+        env.build()
+        envs.append(env)
+    env0 = envs[0]
+    default = env0.action_manager.default_dofs_pos.numpy().astype(np.float32).reshape(-1)[:12].copy()
+    assert default[0] == 0.0
+    dof_pos = default.copy()
+    dof_pos[0] = 1.0   # sum |dof_pos - default| is exactly 1: stand_still's value is its mask
+    links_vel = np.zeros((env0.robot.n_links, 3), dtype=np.float32)
+    links_vel[:, 0] = 1.0   # every link moves at exactly 1: feet_slide's value is its count of feet in contact
+    f4 = lambda x: np.full(4, x, dtype=np.float32)
+    benign = dict(pos=np.array([0.0, 0.0, 0.4], np.float32), quat=np.array([1.0, 0.0, 0.0, 0.0], np.float32), lin_vel=np.zeros(3, np.float32),
+                  ang_vel=np.zeros(3, np.float32), dof_pos=dof_pos, dof_vel=np.zeros(12, np.float32), links_vel=links_vel,
+                  command=np.array([1.0, 0.0, 0.0], np.float32), episode_length=np.int32(500), max_episode_length=np.int32(1000),
+                  last_air=f4(mc.AIR_START["last_air"]), cur_air=f4(mc.AIR_START["cur_air"]), last_contact=f4(mc.AIR_START["last_contact"]),
+                  cur_contact=f4(mc.AIR_START["cur_contact"]))
+    blocks = mask_edge_blocks(benign)
+    names = list(blocks)
+    counts = [next(iter(blocks[b]["arrays"].values())).shape[0] for b in names]
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    R = int(sum(counts))
+    n_c3 = int(sum(c for b, c in zip(names, counts) if b.startswith("c3_")))
+    assert all(b.startswith("c3_") for b in names[: sum(b.startswith("c3_") for b in names)]), "the contact blocks come first (mgr_air covers them)"
+    V = len(mc.VARIANTS)
+    out = {"blocks": np.array(names), "n_envs": np.int64(mc.N_ENVS), "block_start": starts, "block_n": np.array(counts, dtype=np.int64),
+           "block_thr": np.array([blocks[b]["thr"] for b in names]), "block_limit": np.array([blocks[b]["limit"] for b in names]),
+           "block_variants": np.array([[k in blocks[b]["variants"] for k in range(V)] for b in names])}
+    out.update({f"benign_{k}": np.asarray(v) for k, v in benign.items()})
+    for k in mc.ROW_KEYS:
+        out[f"in_{k}"] = np.repeat(np.asarray(benign[k])[None], R, axis=0).copy()
+    out["in_force"], out["in_code"] = np.zeros((R, mc.MAX_FORCES, 3), dtype=np.float32), np.zeros(R, dtype=np.int8)
+    for b, s0, c in zip(names, starts, counts):
+        for k, v in blocks[b]["arrays"].items():
+            out[f"in_{k}"][s0:s0 + c] = v
+    out["mgr_terminated"], out["mgr_truncated"] = np.zeros((V, R), dtype=np.bool_), np.zeros((V, R), dtype=np.bool_)
+    out["mgr_reward"] = np.zeros((V, R), dtype=np.float32)
+    out["mgr_air"] = np.zeros((V, 4, n_c3, 4), dtype=np.float32)
+    to_t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    mask_rows, float_rows = {}, {}
+    out["call_force_norm"] = np.zeros((R, mc.MAX_FORCES), dtype=np.float32)
+    for b, s0, c in zip(names, starts, counts):
+        rows = slice(int(s0), int(s0) + c)
+        st = mc.block_state(out, rows)
+        mc.load_state(env0, st, to_t)
+        norms = {}
+        for term, (kind, val) in mc.call_terms(api, env0, blocks[b]["thr"], blocks[b]["limit"]).items():
+            v = val.detach().numpy()[:c]
+            if kind == "mask":
+                assert v.dtype == np.bool_ or np.all((v == 0) | (v == 1)), term
+                mask_rows.setdefault(term, np.zeros(R, dtype=np.bool_))[rows] = v != 0
+            elif kind == "float":
+                float_rows.setdefault(term, np.zeros(R, dtype=np.float32))[rows] = v
+            else:
+                norms[term] = v
+        # observations.contact_force is one norm per force vector: stored once, read where the largest link set had the forces placed —
+        # and every link set's own output must be that, laid out like its contacts (what the tests rebuild)
+        code, Lmax = out["in_code"][rows].astype(np.int64), max(mc.LINK_SETS)
+        at = mc.link_index(code, Lmax)
+        for j in range(mc.MAX_FORCES):
+            out["call_force_norm"][rows, j] = norms[f"obs_contact_force_L{Lmax}"][np.arange(c), (at + j) % Lmax]
+        for L in mc.LINK_SETS:
+            rebuilt = mc.expand_contacts(out["call_force_norm"][rows][:, :, None], code, L)[:, :, 0]
+            assert np.array_equal(rebuilt, norms[f"obs_contact_force_L{L}"]), (b, L)
+        for k in blocks[b]["variants"]:
+            env = envs[k]
+            mc.load_state(env, st, to_t)
+            env._extras = {env.extras_logging_key: {}}
+            term, trunc = env.termination_manager.step()
+            rew = env.reward_manager.step()
+            out["mgr_terminated"][k, rows], out["mgr_truncated"][k, rows] = term.numpy()[:c], trunc.numpy()[:c]
+            out["mgr_reward"][k, rows] = rew.detach().numpy()[:c]
+            if b.startswith("c3_"):   # ContactManager.step's is_contact (contact_manager.py:444-477) on the feet, threshold = the variant's
+                feet = env.cms[mc.FEET]
+                feet._calculate_air_time()
+                out["mgr_air"][k][:, rows] = np.stack([feet.last_air_time.numpy(), feet.current_air_time.numpy(), feet.last_contact_time.numpy(),
+                                                       feet.current_contact_time.numpy()])[:, :c]
+    out["call_mask_names"], out["call_mask"] = np.array(list(mask_rows)), np.stack(list(mask_rows.values()))
+    out["call_float_names"], out["call_float"] = np.array(list(float_rows)), np.stack(list(float_rows.values()))
+    # the sensitivity condition: rows where plain products summed left to right land on the other side of the recorded mask
+    fx = mc.Fixture(_DictNpz(out))
+    flips = {b: mc.sensitive_rows(fx, b) for b in names if b.endswith("_oblique")}
+    for b, f in flips.items():
+        assert f >= mc.MIN_SENSITIVE_ROWS, f"{b}: only {f} rows tell the two norm formulas apart"
+    path = os.path.join(GOLD, "mask_edges.npz")
+    out["in_quat_delta"] = mc.delta_rows(out.pop("in_quat"))   # (a sweep moves a few float32 steps per row: the differences compress 4x better)
+    np.savez_compressed(path, **out)
+    print("mask_edges:", len(blocks), "blocks,", R, "rows,", os.path.getsize(path), "bytes; rows the plain-product norm puts on the other side:", flips)
+
+
+class _DictNpz:
+    """A dict with the two things mask_edges_cases.Fixture asks of an NpzFile."""
+
+    def __init__(self, d):
+        self.d, self.files = d, list(d)
+
+    def __getitem__(self, k):
+        return self.d[k]
+
+
 def gen_action():
     n = 65
     out = {}
@@ -1000,6 +1267,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "contact_kernel":
         gen_contact_kernel()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "mask_edges":
+        gen_mask_edges()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "at_size":
         gen_at_size()

@@ -125,6 +125,7 @@ int contact_launch(const GfContactArgs* const* mgrs, int num, hipStream_t s) {
     k.force = a0->force; k.position = a0->position; k.links_quat = a0->links_quat; k.links_vel = a0->links_vel; k.links_pos = a0->links_pos;
     k.link_a = a0->link_a; k.link_b = a0->link_b;
     const int C = a0->num_contacts;
+    // (tests/test_contact_edges.py: _plan() restates this choice of E and thread count; its case table depends on it)
     // E envs per workgroup: the LDS holds their slot ids (packed pairs), masks and the relevant slots' contributions
     // (contact_lds_ints); about one (env, tracked link) pair per thread
     auto lds_bytes = [&](int e) { return (size_t)contact_lds_ints(e, C > 0 ? C : 1) * 4; };

@@ -12,7 +12,7 @@ order, which envs resample/reset, weights, op order — not torch's RNG stream.
 Usage: python tools/gen_golden.py                     rewrites the unit fixtures and the traj_go2_* trajectories
        python tools/gen_golden.py examples [key ...]  rewrites traj_ex_<key>.npz — the reference's own example files
                                                       (tests/example_cases.py: six examples at n = 8 + the multi-tile cases)
-       python tools/gen_golden.py entity_obs | contact_kernel | mask_edges   one unit fixture
+       python tools/gen_golden.py entity_obs | contact_kernel | contact_edges | mask_edges   one unit fixture
 """
 import math
 import os
@@ -1109,6 +1109,45 @@ def gen_contact_kernel():
     print("contact_kernel: ok, nonzero force rows per manager", [int((np.abs(data[f"m{m}_contacts"]).sum(-1) > 0).sum()) for m in range(3)])
 
 
+def gen_contact_edges():
+    """The reference's Taichi kernel (contact/kernel.py:5-90, executed from its own source on arrays, as check_ti_parallel does) on ONE
+    case with more than 64 contact slots per env — three occupancy-mask words in gf_contact_tile.h — that holds what the
+    contact_kernel fixture lacks: self-contacts (link_a == link_b == a tracked link), slots with exactly one side -1, slots with both
+    sides -1, and NaN / +-Inf force components, with and without a with-filter.  The kernel gets the forces as ContactManager hands
+    them over (contact_manager.py:399-403: non-finite components replaced by 0); the fixture keeps the raw ones."""
+    from genesis_forge.managers.contact.kernel import kernel_get_contact_forces
+
+    n, C, NL = 24, 130, 20
+    rng = np.random.RandomState(131)
+    targets, withs = [2, 5, 6, 9, 13, 19], [0, 5, 13, 7]
+    la = rng.randint(-1, NL, (n, C)).astype(np.int32)
+    lb = rng.randint(-1, NL, (n, C)).astype(np.int32)
+    empty = rng.uniform(size=(n, C)) < 0.4
+    la[empty], lb[empty] = -1, -1
+    self_c = rng.uniform(size=(n, C)) < 0.06   # self-contacts, of tracked and of untracked links
+    lb[self_c] = la[self_c]
+    for e, c, t in ((0, 0, 2), (1, 31, 5), (2, 32, 6), (3, 63, 9), (4, 64, 13), (5, 95, 19), (6, 96, 5), (7, 129, 13)):   # at the word boundaries too
+        la[e, c], lb[e, c] = t, t
+    f = (10.0 * rng.standard_normal((n, C, 3))).astype(np.float32)
+    for e, c, j, v, a, b in ((8, 5, 0, np.nan, 5, 13), (9, 70, 1, np.inf, 0, 2), (10, 129, 2, -np.inf, 13, 13), (11, 64, 0, np.nan, -1, 6)):
+        f[e, c, j], la[e, c], lb[e, c] = v, a, b
+    f[12, 3, 1], la[12, 3], lb[12, 3] = np.nan, -1, -1   # (a non-finite force in a slot nobody includes)
+    pos = rng.standard_normal((n, C, 3)).astype(np.float32)
+    q = rng.standard_normal((n, NL, 4)).astype(np.float32)
+    q /= np.linalg.norm(q, axis=-1, keepdims=True)
+    assert ((la == lb) & np.isin(la, targets)).sum() >= 8 and ((la < 0) ^ (lb < 0)).sum() > 100 and ((la < 0) & (lb < 0)).sum() > 100
+    clean = torch.nan_to_num(torch.from_numpy(f), nan=0.0, posinf=0.0, neginf=0.0)
+    data = dict(force=f, position=pos, link_a=la, link_b=lb, links_quat=q, targets=np.array(targets, np.int32), withs=np.array(withs, np.int32))
+    T = len(targets)
+    for filt in (0, 1):
+        out_f, out_p, cnt = torch.zeros(n, T, 3), torch.zeros(n, T, 3), torch.zeros(n, T)
+        kernel_get_contact_forces(clean, torch.from_numpy(pos), torch.from_numpy(la), torch.from_numpy(lb), torch.from_numpy(q),
+                                  torch.tensor(targets, dtype=torch.int32), torch.tensor(withs, dtype=torch.int32), out_f, out_p, cnt, filt)
+        data[f"f{filt}_contacts"], data[f"f{filt}_contact_positions"], data[f"f{filt}_counts"] = out_f.numpy().copy(), out_p.numpy().copy(), cnt.numpy().copy()
+    np.savez_compressed(os.path.join(GOLD, "contact_edges.npz"), **data)
+    print("contact_edges: ok, matched slots per link at most", [int(data[f"f{k}_counts"].max()) for k in (0, 1)])
+
+
 def gen_terrain():
     """TerrainManager on a 2x2 height-field terrain: get_terrain_height at in-range, edge and out-of-range points
     (terrain_manager.py:100-166), bounds / subterrain bounds (:281-343) and generate_random_positions with given draws (:168-248)."""
@@ -1268,6 +1307,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "contact_kernel":
         gen_contact_kernel()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "contact_edges":
+        gen_contact_edges()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "mask_edges":
         gen_mask_edges()
         sys.exit(0)
@@ -1287,6 +1329,7 @@ if __name__ == "__main__":
         sys.exit(0)
     gen_terrain()
     gen_contact_kernel()
+    gen_contact_edges()
     gen_entity_obs()
     run_trajectory("traj_go2_rough", n=16, steps=170, contacts=False, history=None, episode_s=1.5, variant="rough",
                    scene_kwargs=dict(ang_noise=0.4, lin_noise=0.05, seed=41, contact_prob=0.3, contact_force=30.0))

@@ -88,6 +88,7 @@ GF_EXPORT int gf_sizeof(int which) {
         case 37: return (int)sizeof(GfRnnCell);
         case 38: return (int)sizeof(GfTrajTableArgs);
         case 39: return (int)sizeof(GfTrajGatherArgs);
+        case 40: return (int)sizeof(GfMlpRecurrentDistillArgs);
         default: return -1;
     }
 }

@@ -26,6 +26,8 @@
 // gf_mlp_distill_act is the same tile walk with grid y = student / teacher (a distillation collection step): the student workgroup is
 // the actor path above, the teacher workgroup stores its outputs to two destinations and samples nothing.
 // gf_mlp_recurrent_act puts an LSTM / GRU cell between a net's input and its MLP (rnn_cell below): a second LDS buffer, one workgroup per CU.
+// gf_mlp_recurrent_distill_act (gf_mlp_rdistill.hip, which compiles this file's device functions with GF_BODIES_ONLY) is that walk on
+// gf_mlp_distill_act's grid, with its finish.
 #include <initializer_list>
 
 #include "gf_launch.h"
@@ -318,17 +320,11 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_act_kernel(const GfMlpActArg
 // gf_mlp_distill_act: grid y = 0 the student (gf_mlp_act's actor path: mean, sample, the storage row), y = 1 the teacher (its output
 // to two destinations).  LOG is a run-time, workgroup-uniform choice here — only the sampling lanes at the end differ, and two
 // instances (NORM) are what the launch needs.
-template <bool NORM>
-__global__ __launch_bounds__(kMlpBlock, 2) void mlp_distill_kernel(const GfMlpDistillArgs a, const int vec_rows) {
-    __shared__ MlpSmem sm;
-    const bool is_teacher = blockIdx.y == 1;
-    const GfMlpNet& net = is_teacher ? a.teacher : a.student;
+// one lane per row finishes it from the outputs in x (A of them): the teacher's output to its two destinations, or the student's mean
+// and gf_policy_act's row (gf_mlp_recurrent_distill_act's finish too: gf_mlp_rdistill.hip)
+__device__ __forceinline__ void mlp_distill_finish(const GfMlpDistillArgs& a, const MlpSmem& sm, const bool is_teacher, const int A, const int64_t row0,
+                                                   const int vec_rows) {
     const int64_t N = a.num_envs;
-    const int64_t row0 = (int64_t)blockIdx.x * kMlpRows;
-
-    const int A = mlp_forward<NORM>(sm, net, row0, N);
-
-    // one lane per row finishes it from the outputs in x
     const int r = (int)threadIdx.x;
     const int64_t n = row0 + r;
     if (r >= kMlpRows || n >= N) return;
@@ -369,6 +365,17 @@ __global__ __launch_bounds__(kMlpBlock, 2) void mlp_distill_kernel(const GfMlpDi
     else mlp_sample_row<false>(p, out, n, vec_rows);
 }
 
+template <bool NORM>
+__global__ __launch_bounds__(kMlpBlock, 2) void mlp_distill_kernel(const GfMlpDistillArgs a, const int vec_rows) {
+    __shared__ MlpSmem sm;
+    const bool is_teacher = blockIdx.y == 1;
+    const GfMlpNet& net = is_teacher ? a.teacher : a.student;
+    const int64_t row0 = (int64_t)blockIdx.x * kMlpRows;
+
+    const int A = mlp_forward<NORM>(sm, net, row0, a.num_envs);
+    mlp_distill_finish(a, sm, is_teacher, A, row0, vec_rows);
+}
+
 // gf_rnd_reward (rsl_rl RandomNetworkDistillation.get_intrinsic_reward): ONE workgroup walks the frozen target, stashes the tile's
 // E <= GF_MLP_MAX_ACTIONS outputs in a second LDS array, walks the predictor from the re-staged input, and lane r < 32 finishes row
 // r: ‖target − predictor‖₂, the weight, the storage row's add.  Chosen over grid y = net (gf_mlp_distill_act's shape) because the
@@ -393,6 +400,7 @@ __device__ __forceinline__ void rnd_finish_row(const GfRndRewardArgs& a, const i
     if (a.acc_intrinsic) G(a.acc_intrinsic)[n] = G(a.acc_intrinsic)[n] + (double)i;
 }
 
+#ifndef GF_BODIES_ONLY
 // (one instance, mlp_forward<true>: whether a net has a normaliser is its workgroup-uniform run-time test there; an instance
 // without it came out at 256 VGPRs with 64 B of scratch once the two walks and the row's end shared a kernel, this one at 249)
 __global__ __launch_bounds__(kMlpBlock, 2) void rnd_tile_kernel(const GfRndRewardArgs a, const int two_pass) {
@@ -506,6 +514,7 @@ __global__ __launch_bounds__(kSumBlock) void rnd_scale_kernel(const GfRndRewardA
     const float r = G(a.intrinsic)[n];
     rnd_finish_row(a, n, sd > 0.0f ? r / sd : r);   // rsl_rl: no eps in this division
 }
+#endif  // GF_BODIES_ONLY
 
 // gf_mlp_recurrent_act: an LSTM / GRU cell in front of each MLP, in the launch of gf_mlp_act.  The cell is the layer code's tile walk
 // with the four accumulators of a wave holding the four gate columns of ONE 32-unit block (LSTM i, f, g, o; GRU n_x, r, z, n_h), so a
@@ -650,6 +659,36 @@ __device__ __forceinline__ void rnn_cell(RnnSmem& sm, const GfMlpNet& net, const
     __syncthreads();
 }
 
+// every layer of `net` behind its cell on the tile's rows (a net without a cell: mlp_forward): the normaliser, the cell — state read,
+// reset, advanced and stored in place — and the MLP walk from h'; the last layer's outputs are left in x; returns their width.
+// gf_mlp_rdistill.hip's walk.  (mlp_recurrent_act_kernel keeps these lines in its own body: calling this function there allocated it
+// one more VGPR, 194 for 193 — profiles/r27_recurrent_distill.md.)
+__device__ __forceinline__ int rnn_forward(RnnSmem& sm, const GfMlpNet& net, const GfRnnCell& cell, const int64_t row0, const int64_t N) {
+    int K;
+    if (cell.type == GF_RNN_NONE) {
+        K = mlp_forward<true>(sm.m, net, row0, N);
+    } else {
+        K = 0;
+        for (int s = 0; s < net.num_inputs; ++s) K += net.inputs[s].width;
+        if (cell.type == GF_RNN_LSTM) rnn_cell<true>(sm, net, cell, K, row0, N);
+        else rnn_cell<false>(sm, net, cell, K, row0, N);
+        K = cell.hidden;
+        const int layers = net.num_layers;
+        for (int l = 0; l < layers; ++l) {
+            const GfMlpLayer& L = net.layers[l];
+            const int nb = (((L.out_width + 31) >> 5) + kMlpWaves - 1) / kMlpWaves;
+            const bool last = l == layers - 1;
+            if (nb == 1) mlp_layer<1, true>(sm.m, net, L, K, false, last, row0, N);
+            else if (nb == 2) mlp_layer<2, true>(sm.m, net, L, K, false, last, row0, N);
+            else if (nb == 3) mlp_layer<3, true>(sm.m, net, L, K, false, last, row0, N);
+            else mlp_layer<4, true>(sm.m, net, L, K, false, last, row0, N);
+            K = L.out_width;
+        }
+    }
+    return K;
+}
+
+#ifndef GF_BODIES_ONLY
 // (one instance: the normaliser and log_std are workgroup-uniform run-time tests, as in rnd_tile_kernel and mlp_distill_kernel)
 __global__ __launch_bounds__(kMlpBlock, 1) void mlp_recurrent_act_kernel(const GfMlpRecurrentActArgs ra, const int first_net, const int vec_rows) {
     __shared__ RnnSmem sm;
@@ -684,6 +723,7 @@ __global__ __launch_bounds__(kMlpBlock, 1) void mlp_recurrent_act_kernel(const G
     if (a.std_is_log) mlp_act_finish<true>(a, sm.m, is_critic, K, row0, vec_rows);
     else mlp_act_finish<false>(a, sm.m, is_critic, K, row0, vec_rows);
 }
+#endif  // GF_BODIES_ONLY
 
 // GF_OK and the net's widths, or the refusal
 static int mlp_check_net(const GfMlpNet& net, bool critic, int* out_width) {
@@ -714,6 +754,7 @@ static int mlp_check_net(const GfMlpNet& net, bool critic, int* out_width) {
     return GF_OK;
 }
 
+#ifndef GF_BODIES_ONLY
 // gf_mlp_act's refusals (gf_mlp_recurrent_act's too): GF_OK, the actor's output width and which nets are there
 static int mlp_act_check(const GfMlpActArgs& a, int* A, bool* has_actor, bool* has_critic) {
     if (a.num_envs < 0 || (a.std_per_env != 0 && a.std_per_env != 1) || (a.std_is_log != 0 && a.std_is_log != 1)) return GF_E_RANGE;
@@ -738,6 +779,21 @@ static int mlp_act_check(const GfMlpActArgs& a, int* A, bool* has_actor, bool* h
     }
     *has_actor = actor;
     *has_critic = critic;
+    return GF_OK;
+}
+#endif  // GF_BODIES_ONLY
+
+// gf_mlp_distill_act's refusals (gf_mlp_recurrent_distill_act's too): GF_OK and the output width of both nets
+static int mlp_distill_check(const GfMlpDistillArgs& a, int* A) {
+    if (a.num_envs < 0 || (a.std_is_log != 0 && a.std_is_log != 1)) return GF_E_RANGE;
+    int At = 0;
+    int rc = mlp_check_net(a.student, false, A);
+    if (rc != GF_OK) return rc;
+    rc = mlp_check_net(a.teacher, false, &At);
+    if (rc != GF_OK) return rc;
+    if (a.student.num_layers == 0 || a.teacher.num_layers == 0) return GF_E_UNSUPPORTED;
+    if (*A != At) return GF_E_RANGE;
+    if (!a.std || !a.actions || !a.teacher_actions) return GF_E_NULL;
     return GF_OK;
 }
 
@@ -767,6 +823,7 @@ static int mlp_vec_rows(std::initializer_list<const void*> rows, int A) {
 
 }  // namespace gf
 
+#ifndef GF_BODIES_ONLY
 extern "C" __attribute__((visibility("default"))) int gf_mlp_act(const GfMlpActArgs* a, void* stream) {
     if (!a) return GF_E_NULL;
     int A = 0;
@@ -815,15 +872,9 @@ extern "C" __attribute__((visibility("default"))) int gf_mlp_recurrent_act(const
 
 extern "C" __attribute__((visibility("default"))) int gf_mlp_distill_act(const GfMlpDistillArgs* a, void* stream) {
     if (!a) return GF_E_NULL;
-    if (a->num_envs < 0 || (a->std_is_log != 0 && a->std_is_log != 1)) return GF_E_RANGE;
-    int A = 0, At = 0;
-    int rc = gf::mlp_check_net(a->student, false, &A);
+    int A = 0;
+    const int rc = gf::mlp_distill_check(*a, &A);
     if (rc != GF_OK) return rc;
-    rc = gf::mlp_check_net(a->teacher, false, &At);
-    if (rc != GF_OK) return rc;
-    if (a->student.num_layers == 0 || a->teacher.num_layers == 0) return GF_E_UNSUPPORTED;
-    if (A != At) return GF_E_RANGE;
-    if (!a->std || !a->actions || !a->teacher_actions) return GF_E_NULL;
     if (a->num_envs == 0) return GF_OK;
     const int64_t tiles = gf::mlp_tiles(a->num_envs);
     if (tiles < 0) return GF_E_RANGE;
@@ -869,3 +920,4 @@ extern "C" __attribute__((visibility("default"))) int gf_rnd_reward(const GfRndR
     }
     return gf::launch_status();
 }
+#endif  // GF_BODIES_ONLY

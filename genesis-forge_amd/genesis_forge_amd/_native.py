@@ -503,6 +503,14 @@ class GfMlpDistillArgs(C.Structure):
                 ("actions_out", P), ("teacher_actions", P), ("teacher_actions_out", P)]
 
 
+# distillation with a recurrent student (learner.RecurrentDistillForward / RolloutStorage.act_distill_recurrent): gf_mlp_recurrent_distill_act
+GF_SIZEOF_MLP_RECURRENT_DISTILL = 40
+
+
+class GfMlpRecurrentDistillArgs(C.Structure):
+    _fields_ = [("act", GfMlpDistillArgs), ("student_cell", GfRnnCell), ("teacher_cell", GfRnnCell)]
+
+
 class GfBcLossArgs(C.Structure):
     _fields_ = [("num_rows", C.c_int64), ("num_actions", C.c_int32), ("loss_type", C.c_int32), ("mu", P), ("target", P), ("grad", P),
                 ("out", P), ("sums", P), ("workspace", P), ("workspace_bytes", C.c_int64)]
@@ -791,7 +799,8 @@ class HipBackend(Backend):
                             ("gf_mlp_distill_act", GF_SIZEOF_MLP_DISTILL, GfMlpDistillArgs), ("gf_bc_loss", GF_SIZEOF_BC_LOSS, GfBcLossArgs),
                             ("gf_rnd_reward", GF_SIZEOF_RND_REWARD, GfRndRewardArgs),
                             ("gf_mlp_recurrent_act", GF_SIZEOF_MLP_RECURRENT_ACT, GfMlpRecurrentActArgs),
-                            ("gf_traj_table", GF_SIZEOF_TRAJ_TABLE, GfTrajTableArgs), ("gf_traj_gather", GF_SIZEOF_TRAJ_GATHER, GfTrajGatherArgs)):
+                            ("gf_traj_table", GF_SIZEOF_TRAJ_TABLE, GfTrajTableArgs), ("gf_traj_gather", GF_SIZEOF_TRAJ_GATHER, GfTrajGatherArgs),
+                            ("gf_mlp_recurrent_distill_act", GF_SIZEOF_MLP_RECURRENT_DISTILL, GfMlpRecurrentDistillArgs)):
             n = self.lib.gf_sizeof(idx)
             if n != C.sizeof(st):
                 raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")
@@ -947,6 +956,7 @@ _LEARNER_ENTRIES = {
     "bc_loss": "learner.Distillation.update",
     "rnd_reward": "learner.RndForward.reward, learner.RolloutStorage.intrinsic_reward",
     "mlp_recurrent_act": "learner.RecurrentForward",
+    "mlp_recurrent_distill_act": "learner.RecurrentDistillForward.act, learner.RolloutStorage.act_distill_recurrent",
     "traj_table": "learner.RolloutStorage.recurrent_mini_batch_generator",
     "traj_gather": "learner.RolloutStorage.recurrent_mini_batch_generator",
 }

@@ -685,6 +685,43 @@ class RolloutStorage:
         self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
         return actions
 
+    def act_distill_recurrent(self, forward: "RecurrentDistillForward", obs, teacher_obs=None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``act_distill`` for a recurrent student (a :class:`RecurrentDistillForward`): ONE ``gf_mlp_recurrent_distill_act`` launch
+        normalises both observations, advances ``memory_s`` (and ``memory_t``, if the teacher has one) by one step in place — rows
+        flagged by ``forward.reset(dones)`` start from zeros — walks the two MLPs, samples and writes ``actions[t]`` and
+        ``privileged_actions[t]``.  At the first step of a rollout (row 0) the launch also writes the state the student starts the
+        rollout from, after the reset, into ``rnn_start["student"]`` (``(h, c)``, ``[N, H]`` each, ``c`` None for a GRU): what
+        ``Distillation.update`` replays the rollout from.  The teacher's start state is not kept: the update never steps the teacher.
+        On a backend without the entry (the test-only CPU oracle) this is the module's torch step, and ``noise`` is required."""
+        if not isinstance(forward, RecurrentDistillForward):
+            raise ValueError("act_distill_recurrent(forward, ...) takes a RecurrentDistillForward")
+        n, dev, A = self.env.num_envs, self.device, forward.num_actions
+        _segments(obs, "obs", n, dev, forward._reader("student"))   # (the storage's env count and device; act() checks the rest)
+        self._ensure_distill_rows(A)
+        save = None
+        if self._act_row() == 0:
+            H, lstm = forward._memory["student"].rnn.hidden_size, forward._cell_type["student"] == nat.GF_RNN_LSTM
+            save = {"student": (torch.empty((n, H), device=dev, dtype=torch.float32),
+                                torch.empty((n, H), device=dev, dtype=torch.float32) if lstm else None)}
+            self.rnn_start = save
+        t, stream, seed, env_offset = self._open_act()
+        actions, _teacher = forward.act(obs, teacher_obs, noise, seed=seed, stream=stream, env_offset=env_offset, actions_out=self.actions[t],
+                                        teacher_actions_out=self.privileged_actions[t], backend=self.env.backend, save=save)
+        self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
+        return actions
+
+    def keep_distill_rnn_start(self, policy) -> None:
+        """``rnn_start["student"]`` from ``policy.memory_s`` — the state the rollout starts from, zeros where the memory has none yet:
+        what a loop on the module's torch step calls before the first step of a rollout (``act_distill_recurrent`` does it inside its
+        launch)."""
+        n, dev, rnn = self.env.num_envs, self.device, policy.memory_s.rnn
+        hs = policy.memory_s.hidden_states
+        lstm = isinstance(rnn, torch.nn.LSTM)
+        if hs is None:
+            hs = tuple(torch.zeros((1, n, rnn.hidden_size), device=dev) for _ in range(2 if lstm else 1))
+        parts = tuple(hs) if isinstance(hs, tuple) else (hs,)
+        self.rnn_start = {"student": (parts[0][0].detach().clone(), parts[1][0].detach().clone() if lstm else None)}
+
     def _act_distill_rows(self, mean: torch.Tensor, std: torch.Tensor, teacher_actions: torch.Tensor, noise: Optional[torch.Tensor] = None,
                           std_is_log: bool = False) -> torch.Tensor:
         """``act_distill`` from the two networks' outputs (the torch forwards of ``DistillationRunner(forward="torch")``): ``act``'s
@@ -702,11 +739,12 @@ class RolloutStorage:
             self.privileged_actions[t].copy_(teacher_actions)
         return actions
 
-    def step_batches(self) -> Iterator[tuple]:
+    def step_batches(self, with_dones: bool = False) -> Iterator[tuple]:
         """rsl_rl's distillation ``generator()``: for ``t = 0 … T-1`` in time order ``(obs_t, privileged_actions[t])`` — the policy
         group's observation of transition ``t`` and the teacher's actions ``act_distill`` stored for it.  Views of the stored rows, no
         gather launch; a group of several managers is concatenated per step, a frame-stored manager goes through
-        ``observation_rows(name, t)``."""
+        ``observation_rows(name, t)``.  ``with_dones=True``: ``(obs_t, privileged_actions[t], dones[t])``, what a recurrent student's
+        update resets its state by."""
         if self.privileged_actions is None:
             raise RuntimeError("step_batches() reads the teacher's actions: collect the rollout with act_distill() first")
         names = self.obs_groups["policy"]
@@ -718,7 +756,10 @@ class RolloutStorage:
 
         for t in range(self.num_steps):
             obs = rows(names[0], t) if len(names) == 1 else torch.cat([rows(m, t) for m in names], dim=-1)
-            yield obs, self.privileged_actions[t]
+            if with_dones:
+                yield obs, self.privileged_actions[t], self.dones[t]
+            else:
+                yield obs, self.privileged_actions[t]
 
     def _act_torch(self, mean, std, values, noise, actions, t, std_is_log: bool = False) -> None:
         """``gf_policy_act``'s row in torch (the test-only oracle backend); ``values=None``: only the action row."""
@@ -1875,6 +1916,150 @@ class StudentTeacherMLP(_ActionStd, torch.nn.Module):
         return resumed
 
 
+_STUDENT_TEACHER_RECURRENT_KEYS = _STUDENT_TEACHER_KEYS + ("rnn_type", "rnn_hidden_dim", "rnn_num_layers", "teacher_recurrent")
+
+
+class StudentTeacherRecurrent(_ActionStd, torch.nn.Module):
+    """rsl_rl's ``StudentTeacherRecurrent``: a one-layer LSTM or GRU ``Memory`` (``memory_s``) in front of the trained ``student`` MLP
+    and, with ``teacher_recurrent=True``, another (``memory_t``) in front of the frozen ``teacher`` MLP — ``obs -> normaliser -> rnn ->
+    MLP``; without it the teacher is :class:`StudentTeacherMLP`'s.  Modules and state-dict keys are rsl_rl's (``memory_s.rnn.*``,
+    ``memory_t.rnn.*`` only with ``teacher_recurrent``, ``student.*``, ``teacher.*``, ``std`` or ``log_std``,
+    ``student_obs_normalizer.*`` / ``teacher_obs_normalizer.*``); the hidden states are no part of the state dict.  ``student`` reads
+    ``rnn_hidden_dim`` columns, and so does ``teacher`` when it is recurrent.  The teacher, ``memory_t`` and the teacher's normaliser
+    are frozen and stay in eval mode whatever ``train()`` is given.
+
+    ``act_mean(obs)`` advances ``memory_s`` by one step (zeros at the first) — with a graph when grad is enabled, which is what
+    :class:`Distillation` back-propagates through; ``evaluate(teacher_obs)`` runs under ``no_grad`` and advances ``memory_t`` if
+    there is one.  ``reset(dones)`` zeroes the rows of both states where ``dones`` is set, ``reset()`` forgets them,
+    ``reset(hidden_states=(student_state, teacher_state))`` installs the given ones; ``get_hidden_states()`` returns that pair (the
+    teacher's ``None`` without ``memory_t``); ``detach_hidden_states()`` cuts both from their graphs.
+
+    ``load_state_dict`` is rsl_rl's rule: a PPO checkpoint (``actor.*`` keys) fills the teacher, the teacher's normaliser and — with
+    ``teacher_recurrent`` — ``memory_t`` from ``memory_a.*``, and returns ``False``; a distillation checkpoint (``student.*`` keys)
+    loads whole and returns ``True``.  A recurrent PPO checkpoint into ``teacher_recurrent=False``, or a feed-forward one into
+    ``teacher_recurrent=True``, raises ``ValueError`` naming ``teacher_recurrent``.
+
+    ``rnn_num_layers`` other than 1, ``rnn_type`` other than ``"lstm"`` / ``"gru"`` and ``rnn_hidden_dim`` outside 1 … 512 raise
+    ``ValueError`` naming the key, as :class:`ActorCriticRecurrent`."""
+
+    is_recurrent = True
+
+    def __init__(self, num_student_obs: int, num_teacher_obs: int, num_actions: int, student_hidden_dims: Sequence[int] = (256, 256, 256),
+                 teacher_hidden_dims: Sequence[int] = (256, 256, 256), init_noise_std: float = 0.1, student_obs_normalization: bool = False,
+                 teacher_obs_normalization: bool = False, noise_std_type: str = "scalar", rnn_type: str = "lstm", rnn_hidden_dim: int = 256,
+                 rnn_num_layers: int = 1, teacher_recurrent: bool = False):
+        super().__init__()
+        who = "StudentTeacherRecurrent"
+        self._set_noise_std_type(who, noise_std_type)
+        if rnn_type not in ("lstm", "gru"):
+            raise ValueError(f"{who}: rnn_type={rnn_type!r} is not supported ('lstm' or 'gru')")
+        if int(rnn_num_layers) != 1:
+            raise ValueError(f"{who}: rnn_num_layers={rnn_num_layers} is not supported (only 1)")
+        if not 1 <= int(rnn_hidden_dim) <= nat.GF_MLP_MAX_HIDDEN:
+            raise ValueError(f"{who}: rnn_hidden_dim={rnn_hidden_dim} is not supported (1 to {nat.GF_MLP_MAX_HIDDEN})")
+        self.rnn_type, self.rnn_hidden_dim, self.teacher_recurrent = rnn_type, int(rnn_hidden_dim), bool(teacher_recurrent)
+        self.loaded_teacher = False
+
+        H = self.rnn_hidden_dim
+        self.memory_s = _Memory(int(num_student_obs), rnn_type, H)
+        self.student = _mlp([H, *student_hidden_dims, int(num_actions)])
+        if self.teacher_recurrent:
+            self.memory_t = _Memory(int(num_teacher_obs), rnn_type, H)
+        self.teacher = _mlp([H if self.teacher_recurrent else int(num_teacher_obs), *teacher_hidden_dims, int(num_actions)])
+        for m in self._frozen():
+            for p in m.parameters():
+                p.requires_grad_(False)
+        self._make_std(init_noise_std, num_actions)
+        self.student_obs_normalizer = EmpiricalNormalization(int(num_student_obs)) if student_obs_normalization else torch.nn.Identity()
+        self.teacher_obs_normalizer = EmpiricalNormalization(int(num_teacher_obs)) if teacher_obs_normalization else torch.nn.Identity()
+        self._scratch = _NormScratch()
+        self._freeze()
+
+    def _frozen(self) -> tuple:
+        """The teacher's modules, the normaliser (created last) included once it exists."""
+        mods = (self.teacher, self.memory_t) if self.teacher_recurrent else (self.teacher,)
+        norm = getattr(self, "teacher_obs_normalizer", None)
+        return mods if norm is None else mods + (norm,)
+
+    def _freeze(self) -> None:
+        for m in self._frozen():
+            m.eval()
+
+    @classmethod
+    def from_train_cfg(cls, train_cfg: dict, num_student_obs: int, num_teacher_obs: int, num_actions: int) -> "StudentTeacherRecurrent":
+        """As :meth:`StudentTeacherMLP.from_train_cfg`, for ``policy.class_name = "StudentTeacherRecurrent"`` with ``policy.rnn_type``,
+        ``rnn_hidden_dim``, ``rnn_num_layers`` and ``teacher_recurrent``."""
+        pol = _policy_cfg(train_cfg, "StudentTeacherRecurrent", _STUDENT_TEACHER_RECURRENT_KEYS, "StudentTeacherRecurrent")
+        return cls(num_student_obs, num_teacher_obs, num_actions, tuple(pol.get("student_hidden_dims", (256, 256, 256))),
+                   tuple(pol.get("teacher_hidden_dims", (256, 256, 256))), float(pol.get("init_noise_std", 0.1)),
+                   student_obs_normalization=bool(pol.get("student_obs_normalization", False)),
+                   teacher_obs_normalization=bool(pol.get("teacher_obs_normalization", False)),
+                   noise_std_type=pol.get("noise_std_type", "scalar"), rnn_type=pol.get("rnn_type", "lstm"),
+                   rnn_hidden_dim=pol.get("rnn_hidden_dim", 256), rnn_num_layers=pol.get("rnn_num_layers", 1),
+                   teacher_recurrent=bool(pol.get("teacher_recurrent", False)))
+
+    def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
+        """The student on one more step of ``memory_s`` (rsl_rl's ``act_inference``)."""
+        return self.student(self.memory_s(self.student_obs_normalizer(obs)).squeeze(0))
+
+    def evaluate(self, teacher_obs: torch.Tensor) -> torch.Tensor:
+        """The teacher's actions, under ``no_grad``; a recurrent teacher's ``memory_t`` advances by one step."""
+        with torch.no_grad():
+            x = self.teacher_obs_normalizer(teacher_obs)
+            return self.teacher(self.memory_t(x).squeeze(0) if self.teacher_recurrent else x)
+
+    def get_hidden_states(self) -> tuple:
+        return self.memory_s.hidden_states, self.memory_t.hidden_states if self.teacher_recurrent else None
+
+    def reset(self, dones=None, hidden_states=None) -> None:
+        memories = (self.memory_s, self.memory_t) if self.teacher_recurrent else (self.memory_s,)
+        if hidden_states is not None:
+            if dones is not None:
+                raise ValueError("StudentTeacherRecurrent.reset: dones and hidden_states cannot both be given")
+            for m, hs in zip(memories, hidden_states):
+                m.hidden_states = hs
+            return
+        for m in memories:
+            m.reset(dones)
+
+    def detach_hidden_states(self) -> None:
+        for m in (self.memory_s, self.memory_t) if self.teacher_recurrent else (self.memory_s,):
+            hs = m.hidden_states
+            if hs is not None:
+                m.hidden_states = tuple(x.detach() for x in hs) if isinstance(hs, tuple) else hs.detach()
+
+    update_normalization = StudentTeacherMLP.update_normalization
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        self._freeze()
+        return self
+
+    def load_state_dict(self, state_dict, strict: bool = True) -> bool:
+        who = "StudentTeacherRecurrent.load_state_dict"
+        if any(k.startswith("actor.") for k in state_dict):   # a PPO checkpoint: its actor (and memory_a) becomes the teacher
+            recurrent = any(k.startswith("memory_a.") for k in state_dict)
+            if recurrent != self.teacher_recurrent:
+                raise ValueError(f"{who}: the PPO checkpoint is {'recurrent' if recurrent else 'feed-forward'} (it has "
+                                 f"{'' if recurrent else 'no '}'memory_a.*' keys); this policy was built with teacher_recurrent={self.teacher_recurrent}")
+            sub = lambda prefix: {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+            self.teacher.load_state_dict(sub("actor."), strict=strict)
+            if recurrent:
+                self.memory_t.load_state_dict(sub("memory_a."), strict=strict)
+            norm = sub("actor_obs_normalizer.")
+            if norm and isinstance(self.teacher_obs_normalizer, EmpiricalNormalization):
+                self.teacher_obs_normalizer.load_state_dict(norm, strict=strict)
+            resumed = False
+        elif any(k.startswith("student.") for k in state_dict):
+            super().load_state_dict(state_dict, strict=strict)
+            resumed = True
+        else:
+            raise ValueError(f"{who}: the state dict has neither 'actor.*' keys (a PPO checkpoint) nor 'student.*' keys (a distillation checkpoint)")
+        self.loaded_teacher = True
+        self._freeze()
+        return resumed
+
+
 def _policy_std(policy):
     """``(parameter, is_log)``: ``policy.log_std`` where ``policy.noise_std_type == "log"`` (rsl_rl's attribute names: a foreign policy
     works too), ``policy.std`` otherwise; the parameter is None where the policy has none."""
@@ -2069,6 +2254,8 @@ class RecurrentForward(_MlpForward):
     ``own_state=True``: the forward steps hidden states of its own instead of the policy's memories' — a play-time policy next to a
     training loop (``OnPolicyRunner.get_inference_policy``)."""
 
+    _ENTRY = "mlp_recurrent_act"   # the backend's one-launch step; a backend without it takes the module's torch step
+
     def __init__(self, policy, own_state: bool = False):
         self.policy = policy
         who = "RecurrentForward"
@@ -2139,11 +2326,11 @@ class RecurrentForward(_MlpForward):
         return parts[0], (parts[1] if lstm else None)
 
     def reset(self, dones=None) -> None:
-        if dones is None or getattr(nat.get_backend(), "mlp_recurrent_act", None) is None:   # (None, or the test-only oracle backend)
+        if dones is None or getattr(nat.get_backend(), self._ENTRY, None) is None:   # (None, or the test-only oracle backend)
             for m in self._memory.values():
                 m.reset(dones)
             if dones is None:
-                self._pending = {"actor": None, "critic": None}
+                self._pending = dict.fromkeys(self._pending)
             return
         if not isinstance(dones, torch.Tensor) or dones.dim() != 1 or dones.dtype not in (torch.bool, torch.uint8) or not dones.is_contiguous():
             raise ValueError("RecurrentForward.reset(dones): dones must be a contiguous [N] bool or uint8 tensor")
@@ -2179,6 +2366,27 @@ class RecurrentForward(_MlpForward):
             keep.append((parts, h, c, flags))
         self._keep = keep
         return ra
+
+    def _fill_cell(self, name: str, cell, parts, n: int, save=None) -> tuple:
+        """Point ``cell`` at the memory of net ``name``: the current weights, the state (read and advanced in place), the pending
+        reset — consumed — and ``save[name] = (h_save, c_save)``.  Returns what must outlive the launch.  (:class:`RecurrentDistillForward`'s
+        form of the loop body above, which stays written out in ``_fill``: the recurrent PPO step's host path is left line for line
+        as it was — at 4 096 envs that step is host-bound.)"""
+        rnn = self._memory[name].rnn
+        h, c = self.state(name, n, parts[0].device)
+        flags = self._pending[name]
+        if flags is not None and (flags.shape[0] != n or flags.device != parts[0].device):
+            raise ValueError(f"RecurrentForward: the pending reset is [{flags.shape[0]}] on {flags.device}; the step has {n} rows on {parts[0].device}")
+        self._pending[name] = None
+        cell.type, cell.hidden = self._cell_type[name], rnn.hidden_size
+        cell.w_ih, cell.w_hh, cell.b_ih, cell.b_hh = (getattr(rnn, p).data_ptr() for p in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"))
+        cell.h, cell.c = h.data_ptr(), None if c is None else c.data_ptr()
+        cell.reset = None if flags is None else flags.data_ptr()
+        cell.h_save = cell.c_save = None
+        if save is not None and name in save:
+            hs, cs = save[name]
+            cell.h_save, cell.c_save = hs.data_ptr(), None if c is None else cs.data_ptr()
+        return (parts, h, c, flags)
 
     def _one(self, obs, name: str) -> torch.Tensor:
         fn = getattr(nat.get_backend(), "mlp_recurrent_act", None)
@@ -2291,6 +2499,159 @@ class DistillForward(_MlpForward):
         self._keep = (segs, tsegs, noise, actions_out, teacher_actions_out)
         fn(a)
         return actions, teacher
+
+
+class RecurrentDistillForward(RecurrentForward):
+    """A recurrent student and its teacher (:class:`StudentTeacherRecurrent`, or rsl_rl's: ``memory_s.rnn`` in front of ``student``,
+    optionally ``memory_t.rnn`` in front of ``teacher``) as ``gf_mlp_recurrent_distill_act`` reads them — :class:`DistillForward`'s
+    checks for the two nets and ``std``, :class:`RecurrentForward`'s for every memory, weights and normalisers looked up at every call.
+    The policy's own ``memory_s`` / ``memory_t`` state tensors (zeros at the first step) are read and advanced in place;
+    ``own_state=True`` steps states of its own instead (``DistillationRunner.get_inference_policy``).
+
+    ``reset(dones)``: one pending flag row per net with a memory, consumed by that net's next launch (:class:`RecurrentForward`'s
+    scheme); ``reset(None)`` forgets the states.  ``act(obs, teacher_obs, …)``: the collection step, ONE launch — both normalisers,
+    both cells, both MLPs, the student's sampling and the rows.  ``mean(obs)``: a student-only ``gf_mlp_recurrent_act`` launch that
+    advances ``memory_s`` — play-time inference.  On a backend without the entry (the test-only CPU oracle) every call is the module's
+    torch step under ``no_grad``, and ``noise`` is required."""
+
+    _ENTRY = "mlp_recurrent_distill_act"
+
+    def __init__(self, policy, own_state: bool = False):
+        self.policy = policy
+        who = "RecurrentDistillForward"
+        self.student = _walk_mlp(getattr(policy, "student", None), "student", nat.GF_MLP_MAX_ACTIONS, who)
+        self.teacher = _walk_mlp(getattr(policy, "teacher", None), "teacher", nat.GF_MLP_MAX_ACTIONS, who)
+        if self.student is None or self.teacher is None:
+            raise ValueError(f"{who}: the policy needs a student and a teacher")
+        A = int(self.student[-1][0].shape[0])
+        if int(self.teacher[-1][0].shape[0]) != A:
+            raise ValueError(f"{who}: policy.student has {A} outputs, policy.teacher {int(self.teacher[-1][0].shape[0])}")
+        self._memory = {"student": getattr(policy, "memory_s", None)}
+        if getattr(policy, "memory_t", None) is not None:
+            self._memory["teacher"] = policy.memory_t
+        if own_state:
+            self._memory = {name: _StateHolder(getattr(m, "rnn", None)) for name, m in self._memory.items()}
+        self._cell_type = {name: self._walk_rnn(m, "memory_s" if name == "student" else "memory_t", getattr(self, name))
+                           for name, m in self._memory.items()}
+        self._normalizer("student"), self._normalizer("teacher")   # (refuses what the kernel cannot fold in)
+        std = self._read_std()
+        if std is None or not self._std_ok(std, A):
+            raise ValueError(f"{who}: policy.{self._std_name} must be a float32 [{A}] tensor")
+        self.num_actions = A
+        self._args, self._mean_args = nat.GfMlpRecurrentDistillArgs(), nat.GfMlpRecurrentActArgs()
+        self._pending = dict.fromkeys(self._memory)
+        self._keep = None
+
+    def _reader(self, name: str):
+        """What ``_segments`` checks an observation of net ``name`` against: its cell's input weights, or its first layer."""
+        return [(self._memory[name].rnn.weight_ih_l0, None)] if name in self._memory else getattr(self, name)
+
+    def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
+        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), int(self._reader(name)[0][0].shape[1]),
+                              f"RecurrentDistillForward: policy.{name}_obs_normalizer")
+
+    def _fill_nets(self, n: int, nets, save=None) -> list:
+        """``nets``: ``(name, GfMlpNet, GfRnnCell, segments)`` each — pointed at the current weights, normaliser, state and pending
+        reset (consumed); a net without a memory gets ``GF_RNN_NONE``."""
+        keep = []
+        for name, net, cell, parts in nets:
+            _fill_net(net, getattr(self, name), parts, self._normalizer(name))
+            if name in self._memory:
+                keep.append(self._fill_cell(name, cell, parts, n, save))
+            else:
+                cell.type = nat.GF_RNN_NONE
+                cell.h_save = cell.c_save = cell.reset = None
+                keep.append(parts)
+        return keep
+
+    def _torch_step(self, name: str, x: torch.Tensor) -> torch.Tensor:
+        """Net ``name`` of the module on this forward's state (the policy's own unless ``own_state``), under ``no_grad``."""
+        norm = self._normalizer(name)
+        x = x if norm is None else norm(x)
+        if name in self._memory:
+            m = self._memory[name]
+            x, m.hidden_states = m.rnn(x.unsqueeze(0), m.hidden_states)
+            x = x.squeeze(0)
+        return getattr(self.policy, name)(x)
+
+    def mean(self, obs) -> torch.Tensor:
+        """The student's output ``[N, A]`` for one more step of its memory (``policy.act_mean(obs)``): one launch, a fresh tensor."""
+        parts = _segments(obs, "obs", None, None, self._reader("student"))
+        fn = getattr(nat.get_backend(), "mlp_recurrent_act", None)
+        if fn is None:   # (the test-only oracle backend)
+            with torch.no_grad():
+                return self._torch_step("student", _cat(parts))
+        n = int(parts[0].shape[0])
+        out = torch.empty((n, self.num_actions), device=parts[0].device, dtype=torch.float32)
+        ra = self._mean_args
+        a = ra.act
+        a.num_envs = n
+        a.critic.num_layers = 0
+        ra.critic_cell.type = nat.GF_RNN_NONE
+        self._keep = self._fill_nets(n, [("student", a.actor, ra.actor_cell, parts)])
+        a.std_is_log = a.std_per_env = 0
+        a.std = a.noise = a.actions = a.actions_out = a.mu_out = a.sigma_out = a.values = a.values_out = a.log_prob_out = None
+        a.mean = out.data_ptr()
+        fn(ra)
+        return out
+
+    def value(self, critic_obs):
+        raise ValueError("RecurrentDistillForward: a student–teacher policy has no critic")
+
+    def act(self, obs, teacher_obs=None, noise: Optional[torch.Tensor] = None, seed: int = 0, stream: int = 0, env_offset: int = 0,
+            actions_out: Optional[torch.Tensor] = None, teacher_actions_out: Optional[torch.Tensor] = None, backend=None, save=None):
+        """``(actions, teacher_actions)``, fresh ``[N, A]`` tensors, as :meth:`DistillForward.act` — with both memories advanced by one
+        step in place, in ONE ``gf_mlp_recurrent_distill_act`` launch.  ``save``: ``{"student": (h_save, c_save)}`` (``[N, H]`` each,
+        ``c_save`` None for a GRU; ``"teacher"`` likewise) receive the state the step started from, after the reset."""
+        segs = _segments(obs, "obs", None, None, self._reader("student"))
+        n, dev = int(segs[0].shape[0]), segs[0].device
+        tsegs = _segments(obs if teacher_obs is None else teacher_obs, "obs (the teacher's input)" if teacher_obs is None else "teacher_obs", n, dev,
+                          self._reader("teacher"))
+        A = self.num_actions
+        std = getattr(self.policy, self._std_name)
+        _check_f32(std, f"policy.{self._std_name}", {(A,)}, dev)
+        for t, name in ((noise, "noise"), (actions_out, "actions_out"), (teacher_actions_out, "teacher_actions_out")):
+            if t is not None:
+                _check_f32(t, name, {(n, A)}, dev)
+        backend = nat.get_backend() if backend is None else backend
+        fn = getattr(backend, self._ENTRY, None)
+        if fn is None:   # (the test-only oracle backend) the module's torch step, from the given draws
+            if noise is None:
+                raise RuntimeError("act() draws its noise in the HIP kernel: on a backend without gf_mlp_recurrent_distill_act pass noise=")
+            with torch.no_grad():
+                for name, dst in (save or {}).items():
+                    self._save_torch(name, n, dev, dst)
+                mean, teacher = self._torch_step("student", _cat(segs)), self._torch_step("teacher", _cat(tsegs)).clone()
+                actions, _sd = _sample_torch(mean, std, noise, self.std_is_log)
+                if actions_out is not None:
+                    actions_out.copy_(actions)
+                if teacher_actions_out is not None:
+                    teacher_actions_out.copy_(teacher)
+            return actions, teacher
+        actions = torch.empty((n, A), device=dev, dtype=torch.float32)
+        teacher = torch.empty((n, A), device=dev, dtype=torch.float32)
+        ra = self._args
+        a = ra.act
+        a.num_envs = n
+        keep = self._fill_nets(n, [("student", a.student, ra.student_cell, segs), ("teacher", a.teacher, ra.teacher_cell, tsegs)], save)
+        a.std, a.std_is_log = std.data_ptr(), 1 if self.std_is_log else 0
+        a.noise = None if noise is None else noise.data_ptr()
+        a.seed, a.stream, a.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(env_offset)
+        a.mean = None
+        a.actions, a.teacher_actions = actions.data_ptr(), teacher.data_ptr()
+        a.actions_out = None if actions_out is None else actions_out.data_ptr()
+        a.teacher_actions_out = None if teacher_actions_out is None else teacher_actions_out.data_ptr()
+        self._keep = (keep, noise, actions_out, teacher_actions_out, save)
+        fn(ra)
+        return actions, teacher
+
+    def _save_torch(self, name: str, n: int, dev, dst) -> None:
+        """``h_save`` / ``c_save`` of the torch step: the state of net ``name`` as the step will read it (zeros where there is none)."""
+        hs = self._memory[name].hidden_states
+        parts = () if hs is None else (tuple(hs) if isinstance(hs, tuple) else (hs,))
+        for i, d in enumerate(dst):
+            if d is not None:
+                d.copy_(parts[i][0]) if parts else d.zero_()
 
 
 def _rnd_reward_torch(rnd: "RandomNetworkDistillation", rnd_state: torch.Tensor, rewards=None, acc_extrinsic=None, acc_intrinsic=None) -> torch.Tensor:
@@ -3184,7 +3545,23 @@ class Distillation(_FlatAdam):
 
     ``optimizer_state_dict()`` is ``torch.optim.Adam``'s format over the student's parameters.  It is NOT interchangeable with
     rsl_rl's distillation checkpoints, whose Adam was built over every parameter of the policy (the teacher's and ``std`` take index
-    slots there); only the model state interchanges."""
+    slots there); only the model state interchanges.
+
+    A recurrent student (``policy.is_recurrent``: :class:`StudentTeacherRecurrent`, collected with ``act_distill_recurrent``) is
+    trained by truncated back-propagation through time.  The trained parameters are ``policy.student``'s and ``policy.memory_s``'s,
+    both in the flat buffer.  Per epoch the student's state is set to ``storage.rnn_start["student"]``, detached — rsl_rl's
+    ``last_hidden_states``: the state update k leaves behind is the one collection k + 1 starts from.  Per stored step, in time
+    order, ``policy.act_mean(obs_t)`` advances ``memory_s`` with a graph and ``gf_bc_loss`` writes the loss and its gradient w.r.t.
+    that step's mean into row ``cnt % gradient_length`` of a ``[gradient_length, N, A]`` buffer; every ``gradient_length`` steps ONE
+    ``torch.autograd.backward`` over the window's means and gradient rows back-propagates through time inside the window only, then
+    ``gf_adam_step``, the bucket is zeroed and the state detached; then the rows with ``dones[t]`` set restart from zeros (no
+    gradient crosses a done).  The pending tail runs under ``no_grad``, loss-only, and still advances the state.  After the last
+    epoch ``memory_s`` holds the replay's end state — the last ``dones`` applied, detached, contiguous — which the next collection
+    step advances in place.  Still one host read per update.  A ``history="frames"`` storage, or one without
+    ``rnn_start["student"]``, raises ``ValueError``.  Two deliberate deviations from rsl_rl: ``update()`` never touches the teacher's
+    memory, which keeps what the collection left (rsl_rl's per-epoch ``reset(hidden_states=…)`` rewinds it to the state before the
+    previous update); and ``max_grad_norm`` clips the norm over ALL trained parameters, ``memory_s``'s included, because
+    ``gf_adam_step`` takes one norm per bucket (rsl_rl clips ``student.parameters()`` only)."""
 
     def __init__(self, policy: "StudentTeacherMLP", storage: RolloutStorage, **algorithm):
         algorithm = dict(algorithm)
@@ -3208,32 +3585,38 @@ class Distillation(_FlatAdam):
         self.max_grad_norm = torch.finfo(torch.float32).max if cfg["max_grad_norm"] is None else float(cfg["max_grad_norm"])
         self.schedule, self.adaptive, self.desired_kl = "fixed", False, None
         self.num_actions = int(policy.student[-1].weight.shape[0])
-        self.grad_sync = GradientAllReduce(policy.student.parameters())   # (one rank: a bucket, never a collective)
+        self.recurrent = bool(getattr(policy, "is_recurrent", False))
+        if self.recurrent and not isinstance(getattr(getattr(policy, "memory_s", None), "rnn", None), (torch.nn.LSTM, torch.nn.GRU)):
+            raise ValueError("Distillation: a recurrent policy needs memory_s.rnn, an nn.LSTM or nn.GRU (StudentTeacherRecurrent)")
+        trained = list(policy.student.parameters()) + (list(policy.memory_s.parameters()) if self.recurrent else [])
+        self.grad_sync = GradientAllReduce(trained)   # (one rank: a bucket, never a collective)
         self._init_flat(float(cfg["learning_rate"]))
         dev = self.params.device
         self._out = torch.zeros(1, device=dev, dtype=torch.float32)
         self._sums = torch.zeros(1, device=dev, dtype=torch.float64)
         self._loss_args = nat.GfBcLossArgs()
-        self._grad = self._loss_ws = None
+        self._grad = self._loss_ws = self._grad_window = None
 
-    def _bc_hip(self, backend, mu: torch.Tensor, target: torch.Tensor, want_grad: bool = True) -> torch.Tensor:
+    def _bc_hip(self, backend, mu: torch.Tensor, target: torch.Tensor, want_grad: bool = True, grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``gf_bc_loss`` of one step; the gradient goes to ``grad`` (a contiguous ``[n, A]`` row of the caller's) or the module's own."""
         n, A = int(target.shape[0]), self.num_actions
         if tuple(mu.shape) != (n, A) or mu.dtype != torch.float32 or not mu.is_contiguous():
             raise ValueError(f"Distillation: the student's mean must be a contiguous float32 {(n, A)} tensor, not {tuple(mu.shape)} {mu.dtype}")
         if self._grad is None or tuple(self._grad.shape) != (n, A):
             self._grad = torch.empty((n, A), device=mu.device, dtype=torch.float32)
             self._loss_ws = torch.empty(max(1, nat.bc_loss_workspace_bytes(n) // 8), device=mu.device, dtype=torch.float64)
+        grad = self._grad if grad is None else grad
         a = self._loss_args
         a.num_rows, a.num_actions, a.loss_type = n, A, _BC_LOSS_TYPES[self.loss_type]
-        a.mu, a.target, a.grad = mu.data_ptr(), target.data_ptr(), self._grad.data_ptr() if want_grad else None
+        a.mu, a.target, a.grad = mu.data_ptr(), target.data_ptr(), grad.data_ptr() if want_grad else None
         a.out, a.sums = self._out.data_ptr(), self._sums.data_ptr()
         a.workspace, a.workspace_bytes = self._loss_ws.data_ptr(), self._loss_ws.numel() * 8
         self._keep = (mu, target)
         backend.bc_loss(a)
-        return self._grad
+        return grad
 
-    def _bc_torch(self, mu: torch.Tensor, target: torch.Tensor, backward: bool = True) -> None:
-        """rsl_rl's ``loss_fn(actions, privileged_actions)`` and its ``backward()``, which accumulates into the bucket."""
+    def _bc_torch(self, mu: torch.Tensor, target: torch.Tensor, backward: bool = True) -> torch.Tensor:
+        """rsl_rl's ``loss_fn(actions, privileged_actions)`` and its ``backward()``, which accumulates into the bucket; returns the loss."""
         fn = torch.nn.functional.mse_loss if self.loss_type == "mse" else torch.nn.functional.huber_loss
         loss = fn(mu, target)
         if backward:
@@ -3241,9 +3624,12 @@ class Distillation(_FlatAdam):
         with torch.no_grad():
             self._out[0] = loss.detach()
             self._sums[0] += loss.detach().to(torch.float64)
+        return loss
 
     def update(self) -> Dict[str, float]:
         """One distillation update over the stored rollout; returns ``{"behavior": mean loss per step}`` — its one host read."""
+        if self.recurrent:
+            return self._update_recurrent()
         sync, policy, backend = self.grad_sync, self.policy, self.storage.env.backend
         hip = getattr(backend, "bc_loss", None) is not None   # (else the test-only oracle backend: torch's loss, autograd, torch Adam)
         self._sums.zero_()
@@ -3271,4 +3657,63 @@ class Distillation(_FlatAdam):
                 if cnt % self.gradient_length == 0:
                     self._adam_step(backend)
                     sync.zero_grad()
+        return {"behavior": self._sums.tolist()[0] / cnt}
+
+    def _update_recurrent(self) -> Dict[str, float]:
+        """``update()`` for a recurrent student: truncated back-propagation through time, one backward per window (the class docstring)."""
+        sync, policy, store, backend = self.grad_sync, self.policy, self.storage, self.storage.env.backend
+        if store.history == "frames":
+            raise ValueError('Distillation: a recurrent student over a history="frames" storage is not supported')
+        start = (getattr(store, "rnn_start", None) or {}).get("student")
+        if start is None:
+            raise ValueError('Distillation: the storage has no rnn_start["student"] — collect the rollout with act_distill_recurrent() '
+                             "(or call keep_distill_rnn_start(policy) before its first step)")
+        hip = getattr(backend, "bc_loss", None) is not None   # (else the test-only oracle backend: torch's loss, autograd, torch Adam)
+        memory, L, lstm = policy.memory_s, self.gradient_length, isinstance(policy.memory_s.rnn, torch.nn.LSTM)
+        if hip:
+            shape = (L, store.env.num_envs, self.num_actions)
+            if self._grad_window is None or tuple(self._grad_window.shape) != shape:
+                self._grad_window = torch.empty(shape, device=self.params.device, dtype=torch.float32)
+        self._sums.zero_()
+        sync.zero_grad()
+        total = self.num_learning_epochs * store.num_steps
+        stepped = total - total % L   # the steps past it never reach an optimizer step: their loss is logged only
+        cnt, window, loss = 0, [], None
+
+        def states(fn) -> None:
+            hs = memory.hidden_states
+            memory.hidden_states = tuple(fn(x) for x in hs) if isinstance(hs, tuple) else fn(hs)
+
+        for _epoch in range(self.num_learning_epochs):
+            h0 = tuple(x.detach().unsqueeze(0) for x in start if x is not None)
+            memory.hidden_states = h0 if lstm else h0[0]
+            for obs, target, dones in store.step_batches(with_dones=True):
+                if cnt >= stepped:   # no graph, no gradient, no backward: the state still advances
+                    with torch.no_grad():
+                        mu = policy.act_mean(obs)
+                        if hip:
+                            self._bc_hip(backend, mu, target, want_grad=False)
+                        else:
+                            self._bc_torch(mu, target, backward=False)
+                else:
+                    mu = policy.act_mean(obs)
+                    if hip:
+                        self._bc_hip(backend, mu, target, grad=self._grad_window[cnt % L])
+                        window.append(mu)
+                    else:
+                        step_loss = self._bc_torch(mu, target, backward=False)
+                        loss = step_loss if loss is None else loss + step_loss
+                cnt += 1
+                if cnt <= stepped and cnt % L == 0:
+                    if hip:
+                        torch.autograd.backward(window, list(self._grad_window.unbind(0)))
+                    else:
+                        loss.backward()
+                    self._adam_step(backend)
+                    sync.zero_grad()
+                    states(lambda x: x.detach())
+                    window, loss = [], None
+                keep = dones.reshape(1, -1, 1)
+                states(lambda x: torch.where(keep, 0.0, x))   # a done row restarts from zeros: no gradient crosses it
+        states(lambda x: x.detach().contiguous())
         return {"behavior": self._sums.tolist()[0] / cnt}

@@ -26,7 +26,8 @@ import torch
 
 from . import gs
 from .learner import (ActorCriticMLP, ActorCriticRecurrent, DistillForward, Distillation, EpisodeStatistics, PolicyForward, PPO,
-                      RecurrentForward, RndForward, RolloutStorage, StudentTeacherMLP, _cat, _policy_std)
+                      RecurrentDistillForward, RecurrentForward, RndForward, RolloutStorage, StudentTeacherMLP, StudentTeacherRecurrent, _cat,
+                      _policy_std)
 from .wrappers import RslRlWrapper
 
 CHECKPOINT_VERSION = 1   # of the "genesis_forge_amd" block of a checkpoint file
@@ -116,6 +117,7 @@ class OnPolicyRunner:
         self._shared_critic = list(store.obs_groups["critic"]) == list(store.obs_groups["policy"])
 
     _NAME = "OnPolicyRunner"
+    _INFERENCE_FORWARD = RecurrentForward   # the forward a recurrent policy's get_inference_policy() steps a state of its own with
 
     def _build_algorithm(self, train_cfg: dict, base, store: RolloutStorage) -> None:
         """``self.alg`` (the policy inside it) and ``self._fwd``, the one-launch forward of ``forward="hip"``."""
@@ -335,23 +337,28 @@ class OnPolicyRunner:
             if self.action_noise is not None and ours.get("action_noise_state") is not None:
                 self.action_noise.set_state(ours["action_noise_state"].cpu())
             if getattr(self, "_recurrent", False) and "hidden_states" in ours:
-                policy = self.alg.policy
-                for m, hs in zip((policy.memory_a, policy.memory_c), ours["hidden_states"]):
+                for m, hs in zip(self._memories(), ours["hidden_states"]):
                     to = lambda x: x.to(self.device).contiguous()
                     m.hidden_states = None if hs is None else (tuple(to(x) for x in hs) if isinstance(hs, (tuple, list)) else to(hs))
                 if self._fwd is not None:
-                    self._fwd._pending = {"actor": None, "critic": None}
+                    self._fwd._pending = dict.fromkeys(self._fwd._pending)
         return loaded.get("infos")
+
+    _MEMORY_NAMES = (("actor", "memory_a"), ("critic", "memory_c"))   # (the forward's net name, the policy's memory) in get_hidden_states()'s order
+
+    def _memories(self) -> tuple:
+        """The policy's memory modules in ``get_hidden_states()``'s order (a net without one is left out, last)."""
+        return tuple(m for m in (getattr(self.alg.policy, attr, None) for _name, attr in self._MEMORY_NAMES) if m is not None)
 
     def _hidden_states(self) -> tuple:
         """The memories' states as the next step will read them (copies; a pending reset of the one-launch forward applied)."""
         out = []
-        for name, hs in zip(("actor", "critic"), self.alg.policy.get_hidden_states()):
+        for (name, _attr), hs in zip(self._MEMORY_NAMES, self.alg.policy.get_hidden_states()):
             if hs is None:
                 out.append(None)
                 continue
             parts = [x.detach().clone() for x in (hs if isinstance(hs, tuple) else (hs,))]
-            flags = None if self._fwd is None else self._fwd._pending[name]
+            flags = None if self._fwd is None else self._fwd._pending.get(name)
             if flags is not None:
                 for x in parts:
                     x[:, flags.to(torch.bool)] = 0.0
@@ -367,7 +374,7 @@ class OnPolicyRunner:
         if device is not None and torch.device(device).type != self.device.type:   # (moving the module would take its parameters out of PPO's flat buffer)
             raise ValueError(f"get_inference_policy: the policy lives on {self.device}; device={device!r} is not supported")
         if getattr(self, "_recurrent", False):
-            return _RecurrentInference(RecurrentForward(self.alg.policy, own_state=True))
+            return _RecurrentInference(self._INFERENCE_FORWARD(self.alg.policy, own_state=True))
         if self._fwd is not None:
             return self._fwd.mean
         policy = self.alg.policy
@@ -418,7 +425,15 @@ class DistillationRunner(OnPolicyRunner):
     ``gf_mlp_distill_act`` launch for the student, the teacher, the sampling and the two rows; ``forward="torch"``: the two torch
     forwards and ``gf_policy_act``) → ``env.step`` → ``policy.update_normalization`` → ``store.process_env_step(None, episodes=…)``,
     then ``Distillation.update()``.  The log record carries ``"behavior"`` in place of the three PPO losses.
-    ``get_inference_policy()`` is the student's mean."""
+    ``get_inference_policy()`` is the student's mean.
+
+    ``policy.class_name = "StudentTeacherRecurrent"`` (:class:`~.learner.StudentTeacherRecurrent`: ``policy.rnn_type`` /
+    ``rnn_hidden_dim`` / ``rnn_num_layers`` / ``teacher_recurrent``; a recurrent PPO checkpoint as the teacher needs
+    ``teacher_recurrent=True``): ``forward="hip"`` collects with ``store.act_distill_recurrent`` — ONE
+    ``gf_mlp_recurrent_distill_act`` launch — and resets the memories of finished episodes without a launch (``fwd.reset(dones)``);
+    ``"torch"`` steps the module and calls ``policy.reset(dones)``.  ``Distillation.update()`` then trains the student and its memory
+    by truncated back-propagation through time.  A checkpoint carries both hidden states in this package's block, so a resumed run
+    continues exactly; ``get_inference_policy()`` returns a callable with a hidden state of its own and ``.reset(dones=None)``."""
 
     _NAME = "DistillationRunner"
 
@@ -426,9 +441,18 @@ class DistillationRunner(OnPolicyRunner):
         if "teacher" not in store.obs_groups or not store.obs_groups["teacher"]:
             raise ValueError("DistillationRunner: train_cfg['obs_groups'] needs a 'teacher' group (the teacher's privileged observations)")
         width = lambda group: sum(store._widths[m] for m in store.obs_groups[group])
-        policy = StudentTeacherMLP.from_train_cfg(train_cfg, width("policy"), width("teacher"), base.action_space.shape[0]).to(self.device)
+        name = dict(train_cfg.get("policy", {})).get("class_name", "StudentTeacher")
+        cls = StudentTeacherRecurrent if name == "StudentTeacherRecurrent" else StudentTeacherMLP   # (any other name: from_train_cfg refuses it)
+        policy = cls.from_train_cfg(train_cfg, width("policy"), width("teacher"), base.action_space.shape[0]).to(self.device)
         self.alg = Distillation(policy, store, **train_cfg["algorithm"])
-        self._fwd = DistillForward(policy) if self.forward == "hip" else None
+        self._recurrent = bool(getattr(policy, "is_recurrent", False))
+        if self.forward != "hip":
+            self._fwd = None
+        else:
+            self._fwd = RecurrentDistillForward(policy) if self._recurrent else DistillForward(policy)
+
+    _MEMORY_NAMES = (("student", "memory_s"), ("teacher", "memory_t"))
+    _INFERENCE_FORWARD = RecurrentDistillForward
 
     def _collect(self, obs: torch.Tensor, extras: dict, stats: EpisodeStatistics):
         store, policy, env = self.storage, self.alg.policy, self.env
@@ -436,16 +460,23 @@ class DistillationRunner(OnPolicyRunner):
         groups = store.obs_groups
         for _ in range(self.num_steps_per_env):
             x, tx = self._group(groups["policy"], obs, extras), self._group(groups["teacher"], obs, extras)
-            if self._fwd is not None:
+            row = store._act_row()
+            if self._fwd is not None and self._recurrent:
+                actions = store.act_distill_recurrent(self._fwd, x, tx, noise=self._noise(n, A))
+            elif self._fwd is not None:
                 actions = store.act_distill(self._fwd, x, tx, noise=self._noise(n, A))
             else:
                 std, is_log = _policy_std(policy)
+                if self._recurrent and row == 0:
+                    store.keep_distill_rnn_start(policy)
                 with torch.no_grad():
                     mean, teacher = policy.act_mean(_cat(x)), policy.evaluate(_cat(tx))
                 actions = store._act_distill_rows(mean, std.detach(), teacher, noise=self._noise(n, A), std_is_log=is_log)
             obs, _rew, _terminated, _truncated, extras = env.step(actions)
             policy.update_normalization(self._group(groups["policy"], obs, extras))
             store.process_env_step(None, episodes=stats)
+            if self._recurrent:   # rsl_rl Distillation.process_env_step: policy.reset(dones)
+                (policy if self._fwd is None else self._fwd).reset(store.dones[row])
         return obs, extras
 
     def _returns(self, obs: torch.Tensor, extras: dict) -> None:

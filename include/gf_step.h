@@ -1290,6 +1290,31 @@ typedef struct GfMlpDistillArgs {
 } GfMlpDistillArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * The collection step of distillation with a recurrent student (rsl_rl Distillation.act on a StudentTeacherRecurrent: memory_s in
+ * front of the student MLP, optionally memory_t in front of the teacher MLP).  gf_mlp_recurrent_distill_act is gf_mlp_distill_act's
+ * launch — grid (tiles of GF_MLP_TILE_ROWS rows, 2), y = 0 the student, y = 1 the teacher — with gf_mlp_recurrent_act's walk per
+ * workgroup: normaliser -> cell (state read, reset where flagged, advanced and stored in place, h_save / c_save written) -> MLP ->
+ * gf_mlp_distill_act's finish (the student: mean, sampling, actions_out; the teacher: its output to both destinations).  The cell's
+ * arithmetic and gate layout are those documented above GfRnnCell, the LDS and occupancy those of gf_mlp_recurrent_act.  A net whose
+ * cell is GF_RNN_NONE is gf_mlp_distill_act's net unchanged.
+ *
+ * Bit for bit: the student's actions, mean, actions_out, h, c, h_save, c_save equal those of a gf_mlp_recurrent_act launch with
+ * `student` as the actor, student_cell as actor_cell, no critic and the same std / std_is_log / noise / seed / stream / env_offset
+ * (gf_mlp_act where student_cell is GF_RNN_NONE); teacher_actions, teacher_actions_out and the teacher's state equal the `mean` and
+ * state of such a launch with `teacher` as the actor.  Row n depends on row n only; rows past num_envs are never written.
+ *
+ * Refusals, before anything is launched: everything gf_mlp_distill_act refuses for `act` and everything gf_mlp_recurrent_act refuses
+ * per cell, with their codes; GF_E_UNSUPPORTED — both cells GF_RNN_NONE (gf_mlp_distill_act is the call for that).  num_envs == 0 is
+ * a no-op.  No allocation, no copy, no synchronisation inside.  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct GfMlpRecurrentDistillArgs {
+    GfMlpDistillArgs act;       /* gf_mlp_distill_act's descriptor; a net with a cell: its segments / in_mean / in_std describe the CELL's
+                                   input, its layers[0] reads `hidden` columns (as GfMlpRecurrentActArgs) */
+    GfRnnCell student_cell;
+    GfRnnCell teacher_cell;     /* GF_RNN_NONE: that net is gf_mlp_distill_act's net unchanged */
+} GfMlpRecurrentDistillArgs;
+
+/* ------------------------------------------------------------------------------------------
  * The curiosity bonus of a collection step (rsl_rl RandomNetworkDistillation.get_intrinsic_reward and the `rewards += intrinsic` of
  * PPO.process_env_step): a frozen random `target` MLP and a trained `predictor` MLP read the same rnd_state rows, the distance of
  * their outputs is the intrinsic reward.  rsl_rl spends about twenty small launches and one host read (`if std > 0`) on it;
@@ -1477,7 +1502,7 @@ int gf_abi_version(void);
  * links below 16 384 envs, more than 12 below 32 768); 0 keeps the two launches (A/B, tests), 2 folds whenever it is possible. */
 enum { GF_OPT_POST_VARIANT = 0, GF_OPT_PROFILE_STRIDE = 1, GF_OPT_GRAPH = 2, GF_OPT_CHAIN = 3, GF_OPT_FOLD_CONTACT = 4, GF_OPT_COUNT = 5 };
 int gf_set_option(int option, int value);
-int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs, 31 GfMirrorRowsArgs, 32 GfMirrorLossArgs, 33 GfMlpDistillArgs, 34 GfBcLossArgs, 35 GfRndRewardArgs, 36 GfMlpRecurrentActArgs, 37 GfRnnCell, 38 GfTrajTableArgs, 39 GfTrajGatherArgs): binding self-check */
+int gf_sizeof(int which);   /* sizeof of the ABI structs (0 = GfStepStats … 11 = GfObsItem, 12 GfTerrainView, 13 GfTerrainHeightArgs, 14 GfGaitArgs, 15 GfContactView, 16 GfCommandView, 17 GfPostRefs, 18 GfRolloutArgs, 19 GfHistoryUnrollArgs, 20 GfRolloutPolicyArgs, 21 GfGaeArgs, 22 GfCompactArgs, 23 GfMinibatchArgs, 24 GfPolicyActArgs, 25 GfEpisodeArgs, 26 GfPpoLossArgs, 27 GfAdamArgs, 28 GfMlpActArgs, 29 GfObsNormArgs, 30 GfRolloutFrameArgs, 31 GfMirrorRowsArgs, 32 GfMirrorLossArgs, 33 GfMlpDistillArgs, 34 GfBcLossArgs, 35 GfRndRewardArgs, 36 GfMlpRecurrentActArgs, 37 GfRnnCell, 38 GfTrajTableArgs, 39 GfTrajGatherArgs, 40 GfMlpRecurrentDistillArgs): binding self-check */
 const char* gf_build_info(void);
 const char* gf_error_string(int code);
 
@@ -1511,6 +1536,7 @@ int gf_mlp_recurrent_act(const GfMlpRecurrentActArgs* a, void* stream); /* gf_ml
 int gf_traj_table(const GfTrajTableArgs* a, void* stream);       /* the trajectories of a rollout: per-env counts, their prefix sum and (env, t0, len), once per update (rsl_rl split_and_pad_trajectories) */
 int gf_traj_gather(const GfTrajGatherArgs* a, void* stream);     /* one minibatch of trajectories: padded normalised observations, masks, the un-pad index and the initial states in one launch (rsl_rl recurrent_mini_batch_generator) */
 int gf_mlp_distill_act(const GfMlpDistillArgs* a, void* stream); /* student + teacher MLP forward in one launch, the student sampled by gf_policy_act's row code (rsl_rl Distillation.act: StudentTeacher.act / evaluate) */
+int gf_mlp_recurrent_distill_act(const GfMlpRecurrentDistillArgs* a, void* stream); /* gf_mlp_distill_act with an LSTM / GRU cell in front of the student's MLP, optionally the teacher's, the hidden states read and advanced in place, in one launch (rsl_rl Distillation.act on a StudentTeacherRecurrent) */
 int gf_bc_loss(const GfBcLossArgs* a, void* stream);             /* behaviour-cloning loss of one time step (mse / huber) and its gradient w.r.t. the student's mean (rsl_rl Distillation.update: loss_fn(actions, privileged_actions) and its backward) */
 int gf_rnd_reward(const GfRndRewardArgs* a, void* stream);       /* target + predictor MLP forward, their distance, the reward normaliser and the storage row's add in one launch (two with the normaliser updating) (rsl_rl RandomNetworkDistillation.get_intrinsic_reward inside PPO.process_env_step) */
 int gf_obs_norm_update(const GfObsNormArgs* a, void* stream);    /* running mean / var / std / count of up to two observation normalisers in two launches (rsl_rl EmpiricalNormalization.update) */

@@ -559,32 +559,43 @@ class RolloutStorage:
         ``noise`` is required."""
         if not isinstance(forward, PolicyForward):
             raise ValueError("act_policy(forward, ...) takes a PolicyForward")
-        n, dev = self.env.num_envs, self.device
         if forward.actor is None or forward.critic is None or forward.num_actions is None:
             raise ValueError("act_policy needs a policy with an actor, a critic and a [A] std (or log_std)")
-        segs = _segments(obs, "obs", n, dev, forward.actor)   # (a window-mode manager's strided view is read in place)
-        csegs = _segments(obs if critic_obs is None else critic_obs, "obs (the critic's input)" if critic_obs is None else "critic_obs", n, dev, forward.critic)
+        return self._act_actor_critic(forward, obs, critic_obs, noise)
+
+    def _act_actor_critic(self, forward, obs, critic_obs, noise) -> torch.Tensor:
+        """``act_policy`` and ``act_recurrent`` behind their refusals: the checks, the row, the descriptor of ``forward`` — a forward
+        with memories nests it as ``.act`` and has, at row 0, the state the rollout starts from saved into ``rnn_start`` — and the ONE
+        launch of the forward's entry; on a backend without it (the test-only oracle backend) ``act`` on the module's torch step."""
+        n, dev = self.env.num_envs, self.device
+        segs = _segments(obs, "obs", n, dev, forward._reader("actor"))   # (a window-mode manager's strided view is read in place)
+        csegs = _segments(obs if critic_obs is None else critic_obs, "obs (the critic's input)" if critic_obs is None else "critic_obs", n, dev,
+                          forward._reader("critic"))
         A = forward.num_actions
         std, is_log = getattr(forward.policy, forward._std_name), forward.std_is_log
-        fn = getattr(self.env.backend, "mlp_act", None)
-        if fn is None:   # (the test-only oracle backend) today's path, bit for bit
+        first = bool(forward._memory) and self._act_row() == 0
+        fn = getattr(self.env.backend, forward._ENTRY, None)
+        if fn is None:   # today's path, bit for bit
             with torch.no_grad():
+                if first:
+                    self.keep_rnn_start(forward.policy)
                 return self.act(forward.policy.act_mean(_cat(segs)), std.detach(), forward.policy.evaluate(_cat(csegs)), noise, std_is_log=is_log)
         _check_f32(std, "policy.log_std" if is_log else "policy.std", {(A,)}, dev)
         if noise is not None:
             _check_f32(noise, "noise", {(n, A)}, dev)
         self._ensure_policy_rows(A)
+        save = None
+        if first:   # (the launch writes them)
+            save = self.rnn_start = {name: _rnn_state_rows(m, n, dev, empty=True) for name, m in forward._memory.items()}
         actions = torch.empty((n, A), device=dev, dtype=torch.float32)
         t, stream, seed, env_offset = self._open_act()
-        a = forward._fill(n, segs, csegs)
-        a.std, a.std_per_env, a.std_is_log = std.data_ptr(), 0, 1 if is_log else 0
-        a.noise = None if noise is None else noise.data_ptr()
-        a.seed, a.stream, a.env_offset = seed, stream, env_offset
-        a.mean = a.values = None
-        a.actions = actions.data_ptr()
+        d = forward._fill(n, segs, csegs, save)
+        a = forward._args_parts[0]   # (d itself, or its .act where the descriptor is nested)
+        _fill_sampling(a, std, is_log, noise, seed, stream, env_offset, actions)
+        a.std_per_env, a.values = 0, None
         self._policy_row_ptrs(a, t)
         self._keep_act = (segs, csegs, noise)
-        fn(a)
+        fn(d)
         self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
         return actions
 
@@ -604,57 +615,14 @@ class RolloutStorage:
         ``noise`` is required."""
         if not isinstance(forward, RecurrentForward):
             raise ValueError("act_recurrent(forward, ...) takes a RecurrentForward")
-        n, dev = self.env.num_envs, self.device
-        segs = _segments(obs, "obs", n, dev, forward._reader("actor"))
-        csegs = _segments(obs if critic_obs is None else critic_obs, "obs (the critic's input)" if critic_obs is None else "critic_obs", n, dev,
-                          forward._reader("critic"))
-        A = forward.num_actions
-        std, is_log = getattr(forward.policy, forward._std_name), forward.std_is_log
-        first = self._act_row() == 0
-        fn = getattr(self.env.backend, "mlp_recurrent_act", None)
-        if fn is None:   # (the test-only oracle backend) the module's step
-            with torch.no_grad():
-                if first:
-                    self.keep_rnn_start(forward.policy)
-                return self.act(forward.policy.act_mean(_cat(segs)), std.detach(), forward.policy.evaluate(_cat(csegs)), noise, std_is_log=is_log)
-        _check_f32(std, "policy.log_std" if is_log else "policy.std", {(A,)}, dev)
-        if noise is not None:
-            _check_f32(noise, "noise", {(n, A)}, dev)
-        self._ensure_policy_rows(A)
-        save = None
-        if first:
-            save = {}
-            for name in ("actor", "critic"):
-                h, c = forward.state(name, n, dev)
-                save[name] = (torch.empty_like(h[0]), None if c is None else torch.empty_like(c[0]))
-            self.rnn_start = save
-        actions = torch.empty((n, A), device=dev, dtype=torch.float32)
-        t, stream, seed, env_offset = self._open_act()
-        ra = forward._fill(n, segs, csegs, save)
-        a = ra.act
-        a.std, a.std_per_env, a.std_is_log = std.data_ptr(), 0, 1 if is_log else 0
-        a.noise = None if noise is None else noise.data_ptr()
-        a.seed, a.stream, a.env_offset = seed, stream, env_offset
-        a.mean = a.values = None
-        a.actions = actions.data_ptr()
-        self._policy_row_ptrs(a, t)
-        self._keep_act = (segs, csegs, noise)
-        fn(ra)
-        self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
-        return actions
+        return self._act_actor_critic(forward, obs, critic_obs, noise)
 
     def keep_rnn_start(self, policy) -> None:
         """Copy the hidden states ``policy.get_hidden_states()`` holds — the state the rollout starts from, zeros where a memory has
         none yet — into ``rnn_start``: what a loop on the module's torch step calls before the first step of a rollout (``act_recurrent``
         does it inside its launch)."""
         n, dev = self.env.num_envs, self.device
-        self.rnn_start = {}
-        for name, memory, hs in zip(("actor", "critic"), (policy.memory_a, policy.memory_c), policy.get_hidden_states()):
-            if hs is None:
-                H = memory.rnn.hidden_size
-                hs = tuple(torch.zeros((1, n, H), device=dev) for _ in range(2 if isinstance(memory.rnn, torch.nn.LSTM) else 1))
-            h, c = (hs[0], hs[1]) if isinstance(hs, tuple) and len(hs) == 2 else ((hs[0] if isinstance(hs, tuple) else hs), None)
-            self.rnn_start[name] = (h[0].detach().clone(), None if c is None else c[0].detach().clone())
+        self.rnn_start = {name: _rnn_state_rows(m, n, dev) for name, m in (("actor", policy.memory_a), ("critic", policy.memory_c))}
 
     # -- teacher–student distillation: the collection step and the update's batches ------------------------------------------------
     def _ensure_distill_rows(self, num_actions: int) -> None:
@@ -676,12 +644,20 @@ class RolloutStorage:
         without the entry point (the test-only CPU oracle) the same values are computed in torch and ``noise`` is required."""
         if not isinstance(forward, DistillForward):
             raise ValueError("act_distill(forward, ...) takes a DistillForward")
+        return self._act_student_teacher(forward, obs, teacher_obs, noise)
+
+    def _act_student_teacher(self, forward, obs, teacher_obs, noise) -> torch.Tensor:
+        """``act_distill`` and ``act_distill_recurrent`` behind their refusals: the rows, ``forward.act`` with them as its second
+        destinations and — for a forward with memories, at row 0 — ``rnn_start["student"]`` as what the launch saves the state into."""
         n, dev, A = self.env.num_envs, self.device, forward.num_actions
-        _segments(obs, "obs", n, dev, forward.student)   # (the storage's env count and device; act() checks the rest)
+        _segments(obs, "obs", n, dev, forward._reader("student"))   # (the storage's env count and device; act() checks the rest)
         self._ensure_distill_rows(A)
+        save = None
+        if forward._memory and self._act_row() == 0:
+            save = self.rnn_start = {"student": _rnn_state_rows(forward._memory["student"], n, dev, empty=True)}
         t, stream, seed, env_offset = self._open_act()
         actions, _teacher = forward.act(obs, teacher_obs, noise, seed=seed, stream=stream, env_offset=env_offset, actions_out=self.actions[t],
-                                        teacher_actions_out=self.privileged_actions[t], backend=self.env.backend)
+                                        teacher_actions_out=self.privileged_actions[t], backend=self.env.backend, save=save)
         self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
         return actions
 
@@ -695,32 +671,13 @@ class RolloutStorage:
         On a backend without the entry (the test-only CPU oracle) this is the module's torch step, and ``noise`` is required."""
         if not isinstance(forward, RecurrentDistillForward):
             raise ValueError("act_distill_recurrent(forward, ...) takes a RecurrentDistillForward")
-        n, dev, A = self.env.num_envs, self.device, forward.num_actions
-        _segments(obs, "obs", n, dev, forward._reader("student"))   # (the storage's env count and device; act() checks the rest)
-        self._ensure_distill_rows(A)
-        save = None
-        if self._act_row() == 0:
-            H, lstm = forward._memory["student"].rnn.hidden_size, forward._cell_type["student"] == nat.GF_RNN_LSTM
-            save = {"student": (torch.empty((n, H), device=dev, dtype=torch.float32),
-                                torch.empty((n, H), device=dev, dtype=torch.float32) if lstm else None)}
-            self.rnn_start = save
-        t, stream, seed, env_offset = self._open_act()
-        actions, _teacher = forward.act(obs, teacher_obs, noise, seed=seed, stream=stream, env_offset=env_offset, actions_out=self.actions[t],
-                                        teacher_actions_out=self.privileged_actions[t], backend=self.env.backend, save=save)
-        self._pol_serial = self._serial + 1   # (the transition the next env.step() writes)
-        return actions
+        return self._act_student_teacher(forward, obs, teacher_obs, noise)
 
     def keep_distill_rnn_start(self, policy) -> None:
         """``rnn_start["student"]`` from ``policy.memory_s`` — the state the rollout starts from, zeros where the memory has none yet:
         what a loop on the module's torch step calls before the first step of a rollout (``act_distill_recurrent`` does it inside its
         launch)."""
-        n, dev, rnn = self.env.num_envs, self.device, policy.memory_s.rnn
-        hs = policy.memory_s.hidden_states
-        lstm = isinstance(rnn, torch.nn.LSTM)
-        if hs is None:
-            hs = tuple(torch.zeros((1, n, rnn.hidden_size), device=dev) for _ in range(2 if lstm else 1))
-        parts = tuple(hs) if isinstance(hs, tuple) else (hs,)
-        self.rnn_start = {"student": (parts[0][0].detach().clone(), parts[1][0].detach().clone() if lstm else None)}
+        self.rnn_start = {"student": _rnn_state_rows(policy.memory_s, self.env.num_envs, self.device)}
 
     def _act_distill_rows(self, mean: torch.Tensor, std: torch.Tensor, teacher_actions: torch.Tensor, noise: Optional[torch.Tensor] = None,
                           std_is_log: bool = False) -> torch.Tensor:
@@ -1328,6 +1285,19 @@ def _sample_torch(mean, std, noise, std_is_log: bool) -> tuple:
     return mean + sd * noise, sd
 
 
+def _rnn_state_rows(memory, n: int, dev, empty: bool = False) -> tuple:
+    """``(h, c)``, ``[n, H]`` each (``c`` None for a GRU): copies of the state ``memory`` (an ``rnn`` and its ``hidden_states``) holds —
+    ``h[0].clone()``, ``c[0].clone()`` — zeros where it has none yet; ``empty``: rows of that shape for a launch to write."""
+    rnn, hs = memory.rnn, memory.hidden_states
+    if empty:
+        row = lambda i: torch.empty((n, rnn.hidden_size), device=dev, dtype=torch.float32)
+    elif hs is None:
+        row = lambda i: torch.zeros((n, rnn.hidden_size), device=dev)
+    else:
+        row = lambda i: (hs[i] if isinstance(hs, tuple) else hs)[0].detach().clone()
+    return row(0), (row(1) if isinstance(rnn, torch.nn.LSTM) else None)
+
+
 def _segments(obs, name: str, n: Optional[int], dev, layers=None, norm_width: Optional[int] = None) -> tuple:
     """``obs`` as the tuple of ``[n, w]`` float32 segments that are read side by side (``act``'s rules: nothing is cast) — contiguous,
     or the strided view a window-mode ObservationManager handed out (``_rows_ok``).  The reader is the first layer of ``layers``
@@ -1647,6 +1617,32 @@ def _policy_cfg(train_cfg: dict, who: str, keys: tuple, class_name: str) -> dict
 
 _POLICY_KEYS = ("class_name", "activation", "actor_hidden_dims", "critic_hidden_dims", "init_noise_std", "noise_std_type",
                 "actor_obs_normalization", "critic_obs_normalization")
+_RNN_KEYS = ("rnn_type", "rnn_hidden_dim", "rnn_num_layers")
+
+
+def _actor_critic_kwargs(train_cfg: dict, pol: dict) -> dict:
+    """The constructor keywords ``ActorCriticMLP.from_train_cfg`` reads from a checked ``train_cfg["policy"]`` (``_POLICY_KEYS``)."""
+    both = bool(train_cfg.get("empirical_normalization"))
+    return dict(actor_hidden_dims=tuple(pol.get("actor_hidden_dims", (512, 256, 128))), critic_hidden_dims=tuple(pol.get("critic_hidden_dims", (512, 256, 128))),
+                init_noise_std=float(pol.get("init_noise_std", 1.0)),
+                actor_obs_normalization=both or bool(pol.get("actor_obs_normalization", False)),
+                critic_obs_normalization=both or bool(pol.get("critic_obs_normalization", False)),
+                noise_std_type=pol.get("noise_std_type", "scalar"))
+
+
+def _rnn_kwargs(pol: dict) -> dict:
+    """The three ``_RNN_KEYS`` of a recurrent policy's ``train_cfg["policy"]``, with rsl_rl's defaults."""
+    return dict(rnn_type=pol.get("rnn_type", "lstm"), rnn_hidden_dim=pol.get("rnn_hidden_dim", 256), rnn_num_layers=pol.get("rnn_num_layers", 1))
+
+
+def _check_rnn_args(who: str, rnn_type, rnn_hidden_dim, rnn_num_layers) -> None:
+    """What a recurrent policy's constructor refuses: ``ValueError`` (``who: key=…``) naming the key."""
+    if rnn_type not in ("lstm", "gru"):
+        raise ValueError(f"{who}: rnn_type={rnn_type!r} is not supported ('lstm' or 'gru')")
+    if int(rnn_num_layers) != 1:
+        raise ValueError(f"{who}: rnn_num_layers={rnn_num_layers} is not supported (only 1)")
+    if not 1 <= int(rnn_hidden_dim) <= nat.GF_MLP_MAX_HIDDEN:
+        raise ValueError(f"{who}: rnn_hidden_dim={rnn_hidden_dim} is not supported (1 to {nat.GF_MLP_MAX_HIDDEN})")
 
 
 class ActorCriticMLP(_ActionStd, torch.nn.Module):
@@ -1683,12 +1679,7 @@ class ActorCriticMLP(_ActionStd, torch.nn.Module):
         Anything that cannot be honoured — another activation than ``"elu"``, another ``noise_std_type`` than those two, an
         unknown policy key — raises ``ValueError`` naming the key."""
         pol = _policy_cfg(train_cfg, "ActorCriticMLP", _POLICY_KEYS, "ActorCritic")
-        both = bool(train_cfg.get("empirical_normalization"))
-        return cls(num_obs, num_actions, tuple(pol.get("actor_hidden_dims", (512, 256, 128))), tuple(pol.get("critic_hidden_dims", (512, 256, 128))),
-                   float(pol.get("init_noise_std", 1.0)), num_critic_obs=num_critic_obs,
-                   actor_obs_normalization=both or bool(pol.get("actor_obs_normalization", False)),
-                   critic_obs_normalization=both or bool(pol.get("critic_obs_normalization", False)),
-                   noise_std_type=pol.get("noise_std_type", "scalar"))
+        return cls(num_obs, num_actions, num_critic_obs=num_critic_obs, **_actor_critic_kwargs(train_cfg, pol))
 
     def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
         return self.actor(self.actor_obs_normalizer(obs))
@@ -1755,7 +1746,7 @@ def _unpad_trajectories(out: torch.Tensor, masks: torch.Tensor, unpad_index=None
     return rows.view(-1, T, H).transpose(1, 0)
 
 
-_RECURRENT_POLICY_KEYS = _POLICY_KEYS + ("rnn_type", "rnn_hidden_dim", "rnn_num_layers")
+_RECURRENT_POLICY_KEYS = _POLICY_KEYS + _RNN_KEYS
 
 
 class ActorCriticRecurrent(_ActionStd, torch.nn.Module):
@@ -1780,12 +1771,7 @@ class ActorCriticRecurrent(_ActionStd, torch.nn.Module):
                  rnn_type: str = "lstm", rnn_hidden_dim: int = 256, rnn_num_layers: int = 1):
         super().__init__()
         self._set_noise_std_type("ActorCriticRecurrent", noise_std_type)
-        if rnn_type not in ("lstm", "gru"):
-            raise ValueError(f"ActorCriticRecurrent: rnn_type={rnn_type!r} is not supported ('lstm' or 'gru')")
-        if int(rnn_num_layers) != 1:
-            raise ValueError(f"ActorCriticRecurrent: rnn_num_layers={rnn_num_layers} is not supported (only 1)")
-        if not 1 <= int(rnn_hidden_dim) <= nat.GF_MLP_MAX_HIDDEN:
-            raise ValueError(f"ActorCriticRecurrent: rnn_hidden_dim={rnn_hidden_dim} is not supported (1 to {nat.GF_MLP_MAX_HIDDEN})")
+        _check_rnn_args("ActorCriticRecurrent", rnn_type, rnn_hidden_dim, rnn_num_layers)
         self.rnn_type, self.rnn_hidden_dim = rnn_type, int(rnn_hidden_dim)
 
         num_critic_obs = num_obs if num_critic_obs is None else int(num_critic_obs)
@@ -1803,13 +1789,7 @@ class ActorCriticRecurrent(_ActionStd, torch.nn.Module):
         """As :meth:`ActorCriticMLP.from_train_cfg`, for ``policy.class_name = "ActorCriticRecurrent"`` with ``policy.rnn_type``,
         ``rnn_hidden_dim`` and ``rnn_num_layers``."""
         pol = _policy_cfg(train_cfg, "ActorCriticRecurrent", _RECURRENT_POLICY_KEYS, "ActorCriticRecurrent")
-        both = bool(train_cfg.get("empirical_normalization"))
-        return cls(num_obs, num_actions, tuple(pol.get("actor_hidden_dims", (512, 256, 128))), tuple(pol.get("critic_hidden_dims", (512, 256, 128))),
-                   float(pol.get("init_noise_std", 1.0)), num_critic_obs=num_critic_obs,
-                   actor_obs_normalization=both or bool(pol.get("actor_obs_normalization", False)),
-                   critic_obs_normalization=both or bool(pol.get("critic_obs_normalization", False)),
-                   noise_std_type=pol.get("noise_std_type", "scalar"), rnn_type=pol.get("rnn_type", "lstm"),
-                   rnn_hidden_dim=pol.get("rnn_hidden_dim", 256), rnn_num_layers=pol.get("rnn_num_layers", 1))
+        return cls(num_obs, num_actions, num_critic_obs=num_critic_obs, **_actor_critic_kwargs(train_cfg, pol), **_rnn_kwargs(pol))
 
     def act_mean(self, obs: torch.Tensor, masks=None, hidden_states=None, unpad_index=None) -> torch.Tensor:
         return self.actor(self.memory_a(self.actor_obs_normalizer(obs), masks, hidden_states, unpad_index).squeeze(0))
@@ -1831,7 +1811,83 @@ _STUDENT_TEACHER_KEYS = ("class_name", "activation", "student_hidden_dims", "tea
                          "student_obs_normalization", "teacher_obs_normalization")
 
 
-class StudentTeacherMLP(_ActionStd, torch.nn.Module):
+def _student_teacher_kwargs(pol: dict) -> dict:
+    """The constructor keywords ``StudentTeacherMLP.from_train_cfg`` reads from a checked ``train_cfg["policy"]`` (``_STUDENT_TEACHER_KEYS``)."""
+    return dict(student_hidden_dims=tuple(pol.get("student_hidden_dims", (256, 256, 256))),
+                teacher_hidden_dims=tuple(pol.get("teacher_hidden_dims", (256, 256, 256))), init_noise_std=float(pol.get("init_noise_std", 0.1)),
+                student_obs_normalization=bool(pol.get("student_obs_normalization", False)),
+                teacher_obs_normalization=bool(pol.get("teacher_obs_normalization", False)),
+                noise_std_type=pol.get("noise_std_type", "scalar"))
+
+
+class _StudentTeacher(_ActionStd, torch.nn.Module):
+    """What :class:`StudentTeacherMLP` and :class:`StudentTeacherRecurrent` share: the frozen teacher side — ``teacher``, ``memory_t``
+    where ``teacher_recurrent``, ``teacher_obs_normalizer`` — which stays in eval mode whatever ``train()`` is given, the student's
+    normaliser update and rsl_rl's ``load_state_dict`` rule.  The feed-forward class is the case without memories."""
+
+    is_recurrent = False
+    teacher_recurrent = False
+
+    def _finish(self, num_student_obs, num_teacher_obs, num_actions, init_noise_std, student_obs_normalization, teacher_obs_normalization) -> None:
+        """What a constructor does once its nets (and memories) exist, in this order: the teacher side's parameters frozen, the std,
+        the two normalisers, the teacher side in eval mode."""
+        for m in self._frozen():
+            for p in m.parameters():
+                p.requires_grad_(False)
+        self._make_std(init_noise_std, num_actions)
+        self.student_obs_normalizer = EmpiricalNormalization(int(num_student_obs)) if student_obs_normalization else torch.nn.Identity()
+        self.teacher_obs_normalizer = EmpiricalNormalization(int(num_teacher_obs)) if teacher_obs_normalization else torch.nn.Identity()
+        self._scratch = _NormScratch()
+        self._freeze()
+
+    def _frozen(self) -> tuple:
+        """The teacher's modules, the normaliser (created last) included once it exists."""
+        mods = (self.teacher, self.memory_t) if self.teacher_recurrent else (self.teacher,)
+        norm = getattr(self, "teacher_obs_normalizer", None)
+        return mods if norm is None else mods + (norm,)
+
+    def _freeze(self) -> None:
+        for m in self._frozen():
+            m.eval()
+
+    def update_normalization(self, obs) -> None:
+        """The student's normaliser sees this step's observations (a ``[N, W]`` tensor or up to four segments); the teacher's is
+        frozen with the teacher."""
+        norm = self.student_obs_normalizer
+        if isinstance(norm, EmpiricalNormalization) and norm.training:
+            _update_normalizers([(norm, _segments(obs, "obs", None, norm._mean.device, norm_width=norm.width))], self._scratch.args)
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        self._freeze()
+        return self
+
+    def load_state_dict(self, state_dict, strict: bool = True) -> bool:
+        who = f"{type(self).__name__}.load_state_dict"
+        if any(k.startswith("actor.") for k in state_dict):   # a PPO checkpoint: its actor (and memory_a) becomes the teacher
+            recurrent = any(k.startswith("memory_a.") for k in state_dict)
+            if self.is_recurrent and recurrent != self.teacher_recurrent:   # (the feed-forward class reads only the keys it knows)
+                raise ValueError(f"{who}: the PPO checkpoint is {'recurrent' if recurrent else 'feed-forward'} (it has "
+                                 f"{'' if recurrent else 'no '}'memory_a.*' keys); this policy was built with teacher_recurrent={self.teacher_recurrent}")
+            sub = lambda prefix: {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+            self.teacher.load_state_dict(sub("actor."), strict=strict)
+            if self.teacher_recurrent:
+                self.memory_t.load_state_dict(sub("memory_a."), strict=strict)
+            norm = sub("actor_obs_normalizer.")
+            if norm and isinstance(self.teacher_obs_normalizer, EmpiricalNormalization):
+                self.teacher_obs_normalizer.load_state_dict(norm, strict=strict)
+            resumed = False
+        elif any(k.startswith("student.") for k in state_dict):
+            super().load_state_dict(state_dict, strict=strict)
+            resumed = True
+        else:
+            raise ValueError(f"{who}: the state dict has neither 'actor.*' keys (a PPO checkpoint) nor 'student.*' keys (a distillation checkpoint)")
+        self.loaded_teacher = True
+        self._freeze()
+        return resumed
+
+
+class StudentTeacherMLP(_StudentTeacher):
     """rsl_rl's ``StudentTeacher`` (feed-forward): a ``student`` that reads the deployable observations and is trained, and a frozen
     ``teacher`` that reads the privileged ones and labels every step.  Both are ``nn.Sequential`` of ``Linear`` with ``ELU`` between;
     ``std`` (or ``log_std`` with ``noise_std_type="log"``) is the exploration noise of the student's actions during collection;
@@ -1853,14 +1909,7 @@ class StudentTeacherMLP(_ActionStd, torch.nn.Module):
 
         self.student = _mlp([int(num_student_obs), *student_hidden_dims, int(num_actions)])
         self.teacher = _mlp([int(num_teacher_obs), *teacher_hidden_dims, int(num_actions)])
-        for p in self.teacher.parameters():
-            p.requires_grad_(False)
-        self._make_std(init_noise_std, num_actions)
-        self.student_obs_normalizer = EmpiricalNormalization(int(num_student_obs)) if student_obs_normalization else torch.nn.Identity()
-        self.teacher_obs_normalizer = EmpiricalNormalization(int(num_teacher_obs)) if teacher_obs_normalization else torch.nn.Identity()
-        self._scratch = _NormScratch()
-        self.teacher.eval()
-        self.teacher_obs_normalizer.eval()
+        self._finish(num_student_obs, num_teacher_obs, num_actions, init_noise_std, student_obs_normalization, teacher_obs_normalization)
 
     @classmethod
     def from_train_cfg(cls, train_cfg: dict, num_student_obs: int, num_teacher_obs: int, num_actions: int) -> "StudentTeacherMLP":
@@ -1869,11 +1918,7 @@ class StudentTeacherMLP(_ActionStd, torch.nn.Module):
         unknown policy key, another activation than ``"elu"``, another class name than ``"StudentTeacher"`` — raises ``ValueError``
         naming the key."""
         pol = _policy_cfg(train_cfg, "StudentTeacherMLP", _STUDENT_TEACHER_KEYS, "StudentTeacher")
-        return cls(num_student_obs, num_teacher_obs, num_actions, tuple(pol.get("student_hidden_dims", (256, 256, 256))),
-                   tuple(pol.get("teacher_hidden_dims", (256, 256, 256))), float(pol.get("init_noise_std", 0.1)),
-                   student_obs_normalization=bool(pol.get("student_obs_normalization", False)),
-                   teacher_obs_normalization=bool(pol.get("teacher_obs_normalization", False)),
-                   noise_std_type=pol.get("noise_std_type", "scalar"))
+        return cls(num_student_obs, num_teacher_obs, num_actions, **_student_teacher_kwargs(pol))
 
     def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
         """The student on its normalised input (rsl_rl's ``act_inference``)."""
@@ -1884,42 +1929,11 @@ class StudentTeacherMLP(_ActionStd, torch.nn.Module):
         with torch.no_grad():
             return self.teacher(self.teacher_obs_normalizer(teacher_obs))
 
-    def update_normalization(self, obs) -> None:
-        """The student's normaliser sees this step's observations (a ``[N, W]`` tensor or up to four segments); the teacher's is
-        frozen with the teacher."""
-        norm = self.student_obs_normalizer
-        if isinstance(norm, EmpiricalNormalization) and norm.training:
-            _update_normalizers([(norm, _segments(obs, "obs", None, norm._mean.device, norm_width=norm.width))], self._scratch.args)
 
-    def train(self, mode: bool = True):
-        super().train(mode)
-        self.teacher.eval()
-        self.teacher_obs_normalizer.eval()
-        return self
-
-    def load_state_dict(self, state_dict, strict: bool = True) -> bool:
-        if any(k.startswith("actor.") for k in state_dict):   # a PPO checkpoint: its actor becomes the teacher
-            self.teacher.load_state_dict({k[len("actor."):]: v for k, v in state_dict.items() if k.startswith("actor.")}, strict=strict)
-            norm = {k[len("actor_obs_normalizer."):]: v for k, v in state_dict.items() if k.startswith("actor_obs_normalizer.")}
-            if norm and isinstance(self.teacher_obs_normalizer, EmpiricalNormalization):
-                self.teacher_obs_normalizer.load_state_dict(norm, strict=strict)
-            resumed = False
-        elif any(k.startswith("student.") for k in state_dict):
-            super().load_state_dict(state_dict, strict=strict)
-            resumed = True
-        else:
-            raise ValueError("StudentTeacherMLP.load_state_dict: the state dict has neither 'actor.*' keys (a PPO checkpoint) nor "
-                             "'student.*' keys (a distillation checkpoint)")
-        self.loaded_teacher = True
-        self.teacher.eval()
-        self.teacher_obs_normalizer.eval()
-        return resumed
+_STUDENT_TEACHER_RECURRENT_KEYS = _STUDENT_TEACHER_KEYS + _RNN_KEYS + ("teacher_recurrent",)
 
 
-_STUDENT_TEACHER_RECURRENT_KEYS = _STUDENT_TEACHER_KEYS + ("rnn_type", "rnn_hidden_dim", "rnn_num_layers", "teacher_recurrent")
-
-
-class StudentTeacherRecurrent(_ActionStd, torch.nn.Module):
+class StudentTeacherRecurrent(_StudentTeacher):
     """rsl_rl's ``StudentTeacherRecurrent``: a one-layer LSTM or GRU ``Memory`` (``memory_s``) in front of the trained ``student`` MLP
     and, with ``teacher_recurrent=True``, another (``memory_t``) in front of the frozen ``teacher`` MLP — ``obs -> normaliser -> rnn ->
     MLP``; without it the teacher is :class:`StudentTeacherMLP`'s.  Modules and state-dict keys are rsl_rl's (``memory_s.rnn.*``,
@@ -1951,12 +1965,7 @@ class StudentTeacherRecurrent(_ActionStd, torch.nn.Module):
         super().__init__()
         who = "StudentTeacherRecurrent"
         self._set_noise_std_type(who, noise_std_type)
-        if rnn_type not in ("lstm", "gru"):
-            raise ValueError(f"{who}: rnn_type={rnn_type!r} is not supported ('lstm' or 'gru')")
-        if int(rnn_num_layers) != 1:
-            raise ValueError(f"{who}: rnn_num_layers={rnn_num_layers} is not supported (only 1)")
-        if not 1 <= int(rnn_hidden_dim) <= nat.GF_MLP_MAX_HIDDEN:
-            raise ValueError(f"{who}: rnn_hidden_dim={rnn_hidden_dim} is not supported (1 to {nat.GF_MLP_MAX_HIDDEN})")
+        _check_rnn_args(who, rnn_type, rnn_hidden_dim, rnn_num_layers)
         self.rnn_type, self.rnn_hidden_dim, self.teacher_recurrent = rnn_type, int(rnn_hidden_dim), bool(teacher_recurrent)
         self.loaded_teacher = False
 
@@ -1966,36 +1975,14 @@ class StudentTeacherRecurrent(_ActionStd, torch.nn.Module):
         if self.teacher_recurrent:
             self.memory_t = _Memory(int(num_teacher_obs), rnn_type, H)
         self.teacher = _mlp([H if self.teacher_recurrent else int(num_teacher_obs), *teacher_hidden_dims, int(num_actions)])
-        for m in self._frozen():
-            for p in m.parameters():
-                p.requires_grad_(False)
-        self._make_std(init_noise_std, num_actions)
-        self.student_obs_normalizer = EmpiricalNormalization(int(num_student_obs)) if student_obs_normalization else torch.nn.Identity()
-        self.teacher_obs_normalizer = EmpiricalNormalization(int(num_teacher_obs)) if teacher_obs_normalization else torch.nn.Identity()
-        self._scratch = _NormScratch()
-        self._freeze()
-
-    def _frozen(self) -> tuple:
-        """The teacher's modules, the normaliser (created last) included once it exists."""
-        mods = (self.teacher, self.memory_t) if self.teacher_recurrent else (self.teacher,)
-        norm = getattr(self, "teacher_obs_normalizer", None)
-        return mods if norm is None else mods + (norm,)
-
-    def _freeze(self) -> None:
-        for m in self._frozen():
-            m.eval()
+        self._finish(num_student_obs, num_teacher_obs, num_actions, init_noise_std, student_obs_normalization, teacher_obs_normalization)
 
     @classmethod
     def from_train_cfg(cls, train_cfg: dict, num_student_obs: int, num_teacher_obs: int, num_actions: int) -> "StudentTeacherRecurrent":
         """As :meth:`StudentTeacherMLP.from_train_cfg`, for ``policy.class_name = "StudentTeacherRecurrent"`` with ``policy.rnn_type``,
         ``rnn_hidden_dim``, ``rnn_num_layers`` and ``teacher_recurrent``."""
         pol = _policy_cfg(train_cfg, "StudentTeacherRecurrent", _STUDENT_TEACHER_RECURRENT_KEYS, "StudentTeacherRecurrent")
-        return cls(num_student_obs, num_teacher_obs, num_actions, tuple(pol.get("student_hidden_dims", (256, 256, 256))),
-                   tuple(pol.get("teacher_hidden_dims", (256, 256, 256))), float(pol.get("init_noise_std", 0.1)),
-                   student_obs_normalization=bool(pol.get("student_obs_normalization", False)),
-                   teacher_obs_normalization=bool(pol.get("teacher_obs_normalization", False)),
-                   noise_std_type=pol.get("noise_std_type", "scalar"), rnn_type=pol.get("rnn_type", "lstm"),
-                   rnn_hidden_dim=pol.get("rnn_hidden_dim", 256), rnn_num_layers=pol.get("rnn_num_layers", 1),
+        return cls(num_student_obs, num_teacher_obs, num_actions, **_student_teacher_kwargs(pol), **_rnn_kwargs(pol),
                    teacher_recurrent=bool(pol.get("teacher_recurrent", False)))
 
     def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
@@ -2027,37 +2014,6 @@ class StudentTeacherRecurrent(_ActionStd, torch.nn.Module):
             hs = m.hidden_states
             if hs is not None:
                 m.hidden_states = tuple(x.detach() for x in hs) if isinstance(hs, tuple) else hs.detach()
-
-    update_normalization = StudentTeacherMLP.update_normalization
-
-    def train(self, mode: bool = True):
-        super().train(mode)
-        self._freeze()
-        return self
-
-    def load_state_dict(self, state_dict, strict: bool = True) -> bool:
-        who = "StudentTeacherRecurrent.load_state_dict"
-        if any(k.startswith("actor.") for k in state_dict):   # a PPO checkpoint: its actor (and memory_a) becomes the teacher
-            recurrent = any(k.startswith("memory_a.") for k in state_dict)
-            if recurrent != self.teacher_recurrent:
-                raise ValueError(f"{who}: the PPO checkpoint is {'recurrent' if recurrent else 'feed-forward'} (it has "
-                                 f"{'' if recurrent else 'no '}'memory_a.*' keys); this policy was built with teacher_recurrent={self.teacher_recurrent}")
-            sub = lambda prefix: {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
-            self.teacher.load_state_dict(sub("actor."), strict=strict)
-            if recurrent:
-                self.memory_t.load_state_dict(sub("memory_a."), strict=strict)
-            norm = sub("actor_obs_normalizer.")
-            if norm and isinstance(self.teacher_obs_normalizer, EmpiricalNormalization):
-                self.teacher_obs_normalizer.load_state_dict(norm, strict=strict)
-            resumed = False
-        elif any(k.startswith("student.") for k in state_dict):
-            super().load_state_dict(state_dict, strict=strict)
-            resumed = True
-        else:
-            raise ValueError(f"{who}: the state dict has neither 'actor.*' keys (a PPO checkpoint) nor 'student.*' keys (a distillation checkpoint)")
-        self.loaded_teacher = True
-        self._freeze()
-        return resumed
 
 
 def _policy_std(policy):
@@ -2129,53 +2085,185 @@ def _fill_net(net, layers, parts, norm=None) -> None:
         lay.weight, lay.bias, lay.out_width = w.data_ptr(), b.data_ptr(), w.shape[0]
 
 
+def _fill_sampling(a, std, std_is_log: bool, noise, seed: int, stream: int, env_offset: int, actions) -> None:
+    """The sampling fields a GfMlpActArgs and a GfMlpDistillArgs share by name: the ``[A]`` std (or log_std), the given draws or the
+    Philox key of the kernel's own, and the fresh ``[N, A]`` tensor the sample goes to.  ``mean`` is not kept."""
+    a.std, a.std_is_log = std.data_ptr(), 1 if std_is_log else 0
+    a.noise = None if noise is None else noise.data_ptr()
+    a.seed, a.stream, a.env_offset = seed, stream, env_offset
+    a.mean = None
+    a.actions = actions.data_ptr()
+
+
+def _walk_rnn(memory, name: str, layers) -> int:
+    """The cell type of ``policy.<name>.rnn``; ``ValueError`` naming what the kernel cannot run."""
+    who = f"RecurrentForward: policy.{name}.rnn"
+    rnn = getattr(memory, "rnn", None)
+    if not isinstance(rnn, (torch.nn.LSTM, torch.nn.GRU)):
+        raise ValueError(f"{who} must be an nn.LSTM or nn.GRU, not {type(rnn).__name__}")
+    if rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first or getattr(rnn, "proj_size", 0):
+        raise ValueError(f"{who} must have num_layers=1, bias=True, batch_first=False, no projection and one direction")
+    if not 1 <= rnn.hidden_size <= nat.GF_MLP_MAX_HIDDEN:
+        raise ValueError(f"{who} has hidden_size {rnn.hidden_size}; 1 to {nat.GF_MLP_MAX_HIDDEN}")
+    if rnn.input_size > nat.GF_MLP_MAX_INPUT_WIDTH:
+        raise ValueError(f"{who} reads {rnn.input_size} inputs; at most {nat.GF_MLP_MAX_INPUT_WIDTH}")
+    if int(layers[0][0].shape[1]) != rnn.hidden_size:
+        raise ValueError(f"{who} has hidden_size {rnn.hidden_size}; the MLP behind it reads {int(layers[0][0].shape[1])}")
+    for pn in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
+        p = getattr(rnn, pn)
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise ValueError(f"{who}.{pn} must be contiguous float32")
+    return nat.GF_RNN_LSTM if isinstance(rnn, torch.nn.LSTM) else nat.GF_RNN_GRU
+
+
 class _MlpForward:
-    """What :class:`PolicyForward` and :class:`DistillForward` share.  The host class keeps ``policy`` and, per net name, the
-    ``[(weight, bias)]`` list ``_walk_mlp`` returned (or None) as the attribute of that name."""
+    """What the four forwards share.  A forward keeps ``policy``, per net name the ``[(weight, bias)]`` list ``_walk_mlp`` returned
+    (or None) as the attribute of that name, and ``_memory``: ``{net name: memory}`` for the nets with an rnn in front (a
+    :class:`RecurrentForward`; empty otherwise).  The descriptors come in two families — actor–critic (GfMlpActArgs) and
+    student–teacher (GfMlpDistillArgs) — each bare, or, for a forward with memories, nested as ``.act`` beside one GfRnnCell per net."""
+
+    _memory: dict = {}
+
+    def _setup(self, policy, who: str, nets, missing: str, both: bool = True, memories=(), own_state: bool = False, same_width: bool = False) -> None:
+        """A constructor's checks, under the class name ``who``: walk the two ``nets`` (``(name, most outputs)`` each) — ``both``
+        required, or at least one, ``missing`` says which — ``same_width`` outputs, the ``memories`` (``(net name, attribute of the
+        policy)`` each; ``own_state``: a state of this forward's own over their rnn), the normalisers, the ``[A]`` std (required with
+        ``both``).  Sets ``num_actions`` (None without an actor or a std)."""
+        self.policy, self._who = policy, who
+        for name, max_out in nets:
+            setattr(self, name, _walk_mlp(getattr(policy, name, None), name, max_out, who))
+        (a, _), (b, _) = nets
+        first, second = getattr(self, a), getattr(self, b)
+        if (first is None or second is None) if both else (first is None and second is None):
+            raise ValueError(f"{who}: {missing}")
+        if same_width and int(second[-1][0].shape[0]) != int(first[-1][0].shape[0]):
+            raise ValueError(f"{who}: policy.{a} has {int(first[-1][0].shape[0])} outputs, policy.{b} {int(second[-1][0].shape[0])}")
+        if memories:
+            self._memory = {name: getattr(policy, attr, None) for name, attr in memories}
+            if own_state:
+                self._memory = {name: _StateHolder(getattr(m, "rnn", None)) for name, m in self._memory.items()}
+            self._cell_type = {name: _walk_rnn(self._memory[name], attr, getattr(self, name)) for name, attr in memories}
+        self._pending = dict.fromkeys(self._memory)
+        self._keep = None
+        # what reads a net's observation: its cell's input weights, or its first layer (the Parameter objects, as the layers' are)
+        self._readers = {name: [(self._memory[name].rnn.weight_ih_l0, None)] if name in self._memory else getattr(self, name) for name, _ in nets}
+        self._in_width = {name: int(r[0][0].shape[1]) for name, r in self._readers.items() if r is not None}
+        for name, _ in nets:
+            self._normalizer(name)   # (refuses what the kernel cannot fold in)
+        std, is_log = _policy_std(policy)   # the type is fixed here; the parameter itself is looked up per call
+        self.std_is_log, self._std_name = is_log, "log_std" if is_log else "std"
+        self.num_actions = None
+        if first is not None and (both or std is not None):
+            A = int(first[-1][0].shape[0])
+            if std is None or std.dtype != torch.float32 or tuple(std.shape) != (A,):
+                raise ValueError(f"{who}: policy.{self._std_name} must be a float32 [{A}] tensor" + ("" if both else f", not {std.dtype} {tuple(std.shape)}"))
+            self.num_actions = A
 
     def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
-        """The policy's current normaliser in front of net ``name`` (None: the net reads its input as it is)."""
-        layers = getattr(self, name)
-        if layers is None:
+        """The policy's current normaliser in front of net ``name`` — of its memory, where it has one (None: the input is read as it is)."""
+        width = self._in_width.get(name)   # the cell's input_size, or the first layer's (None: the policy has no such net)
+        if width is None:
             return None
-        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), int(layers[0][0].shape[1]),
-                              f"{type(self).__name__}: policy.{name}_obs_normalizer")
+        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), width, f"{self._who}: policy.{name}_obs_normalizer")
 
-    def _read_std(self):
-        """Fix the std's type (the parameter itself is looked up per call) and return the parameter, None where the policy has none."""
-        std, is_log = _policy_std(self.policy)
-        self.std_is_log, self._std_name = is_log, "log_std" if is_log else "std"
-        return std
+    def _reader(self, name: str):
+        """What ``_segments`` checks an observation of net ``name`` against: its cell's input weights, or its first layer."""
+        return self._readers[name]
 
-    @staticmethod
-    def _std_ok(std, A: int) -> bool:
-        return std.dtype == torch.float32 and tuple(std.shape) == (A,)
+    def _descriptors(self, cls, one_cls=None) -> None:
+        """``_args``: the collection step's descriptor; ``_one_args``: the actor–critic one of ``_one`` (``one_cls`` None: the same).
+        Beside each, its parts looked up once (ctypes builds a new view at every attribute read): ``(the act part, {field: (its
+        GfMlpNet, its GfRnnCell or None)})``."""
+        def parts(d):
+            a = d.act if self._memory else d
+            return a, {f: (getattr(a, f), getattr(d, f + "_cell") if self._memory else None) for f, t in a._fields_ if t is nat.GfMlpNet}
 
-    def _one(self, obs, name: str, torch_fn, fill) -> torch.Tensor:
-        """The output of net ``name`` alone for ``obs``: one ``gf_mlp_act`` launch on the descriptor ``fill(n, segments)`` returns, a
-        fresh tensor."""
+        self._args = cls()
+        self._args_parts = parts(self._args)
+        self._one_args = self._args if one_cls is None else one_cls()
+        self._one_parts = self._args_parts if one_cls is None else parts(self._one_args)
+
+    def _fill_desc(self, d_parts, n: int, slots, save=None):
+        """A descriptor of either family (its ``_descriptors`` parts) for ``n`` rows; ``slots``: ``(field of the descriptor, net name,
+        segments)`` twice — the net pointed at the current weights, normaliser and segments and, in a nested descriptor, its cell at
+        the memory (``_fill_cell``; GF_RNN_NONE without one); segments None: that net is left out of the launch.  Returns the ``act``
+        part."""
+        a, nets = d_parts
+        a.num_envs = n
+        keep = []
+        for slot, name, parts in slots:
+            net, cell = nets[slot]
+            if parts is None:
+                net.num_layers = 0
+            else:
+                _fill_net(net, getattr(self, name), parts, self._normalizer(name))
+            if cell is not None:
+                if parts is not None and name in self._memory:
+                    keep.append(self._fill_cell(name, cell, parts, n, save))
+                    continue
+                cell.type = nat.GF_RNN_NONE
+                cell.h_save = cell.c_save = cell.reset = None
+            keep.append(parts)
+        self._keep = keep
+        return a
+
+    def _torch_step(self, name: str, x: torch.Tensor) -> torch.Tensor:
+        """Net ``name`` of the module in torch on this forward's state (the policy's own unless ``own_state``), under ``no_grad``: the
+        test-only oracle backend's path."""
+        norm = self._normalizer(name)
+        x = x if norm is None else norm(x)
+        m = self._memory.get(name)
+        if m is not None:
+            x, m.hidden_states = m.rnn(x.unsqueeze(0), m.hidden_states)
+            x = x.squeeze(0)
+        return getattr(self.policy, name)(x)
+
+    def _one(self, obs, name: str) -> torch.Tensor:
+        """The output of net ``name`` alone for ``obs`` (one more step of its memory, where it has one), a fresh tensor: one
+        ``gf_mlp_act`` / ``gf_mlp_recurrent_act`` launch on the actor–critic descriptor ``_one_args``, with the net in the critic's
+        slot if it is the critic and in the actor's otherwise, the other slot left out and nothing sampled."""
         layers = getattr(self, name)
         if layers is None:
-            raise ValueError(f"{type(self).__name__}: the policy has no {name}")
-        parts = _segments(obs, "obs", None, None, layers)
-        fn = getattr(nat.get_backend(), "mlp_act", None)
+            raise ValueError(f"{self._who}: the policy has no {name}")
+        parts = _segments(obs, "obs", None, None, self._reader(name))
+        fn = getattr(nat.get_backend(), "mlp_recurrent_act" if self._memory else "mlp_act", None)
         if fn is None:   # (the test-only oracle backend)
-            norm = self._normalizer(name)
             with torch.no_grad():
-                x = _cat(parts)
-                return torch_fn(x if norm is None else norm(x))
+                return self._torch_step(name, _cat(parts))
         n = int(parts[0].shape[0])
         out = torch.empty((n, int(layers[-1][0].shape[0])), device=parts[0].device, dtype=torch.float32)
-        a = fill(n, parts)
-        a.std_is_log = 0
+        slot, other = ("critic", "actor") if name == "critic" else ("actor", "critic")
+        a = self._fill_desc(self._one_parts, n, ((slot, name, parts), (other, None, None)))
+        a.std_is_log = a.std_per_env = 0
         a.std = a.noise = a.actions = a.actions_out = a.mu_out = a.sigma_out = a.values_out = a.log_prob_out = None
         a.mean, a.values = (None, out.data_ptr()) if name == "critic" else (out.data_ptr(), None)
-        self._keep_one = (parts, out)
-        fn(a)
+        self._keep_one = out
+        fn(self._one_args)
         return out
 
 
-class PolicyForward(_MlpForward):
+class _ActorCriticForward(_MlpForward):
+    """What :class:`PolicyForward` and :class:`RecurrentForward` share: ``_args`` is the actor–critic descriptor of the collection step,
+    and of ``mean`` / ``value``."""
+
+    def _fill(self, n: int, actor_parts, critic_parts, save=None):
+        """The descriptor with the given nets (None: left out) pointed at the current weights and inputs — and, where they have a
+        memory, at its state and pending reset, which is consumed; ``save``: ``{name: (h_save, c_save)}``."""
+        self._fill_desc(self._args_parts, n, (("actor", "actor", actor_parts), ("critic", "critic", critic_parts)), save)
+        return self._args
+
+    def mean(self, obs) -> torch.Tensor:
+        """The actor's output ``[N, A]`` (``policy.act_mean(obs)``, one more step of its memory where it has one): one launch, a fresh
+        tensor."""
+        return self._one(obs, "actor")
+
+    def value(self, critic_obs) -> torch.Tensor:
+        """The critic's output ``[N, 1]`` (``policy.evaluate(critic_obs)``, one more step of its memory where it has one): one launch,
+        a fresh tensor."""
+        return self._one(critic_obs, "critic")
+
+
+class PolicyForward(_ActorCriticForward):
     """The actor and critic of a policy as ``gf_mlp_act`` reads them: one launch per forward pass, weights read in place.
 
     ``policy.actor`` / ``policy.critic`` (either may be missing or ``None``) must be ``nn.Sequential`` of ``Linear`` layers with
@@ -2192,50 +2280,20 @@ class PolicyForward(_MlpForward):
     ``RolloutStorage.act_policy(forward, obs)``: the collection step.  An observation is a ``[N, W]`` tensor or a sequence of up to
     four whose widths add up to the first layer's input (an observation group's members, no ``torch.cat``)."""
 
+    _ENTRY = "mlp_act"   # the backend's one-launch step
+
     def __init__(self, policy):
-        self.policy = policy
-        self.actor = self._walk(getattr(policy, "actor", None), "actor", nat.GF_MLP_MAX_ACTIONS)
-        self.critic = self._walk(getattr(policy, "critic", None), "critic", 1)
-        if self.actor is None and self.critic is None:
-            raise ValueError("PolicyForward: the policy has neither an actor nor a critic")
-        self._normalizer("actor"), self._normalizer("critic")   # (refuses what the kernel cannot fold in)
-        std = self._read_std()
-        self.num_actions = None
-        if self.actor is not None and std is not None:
-            A = self.actor[-1][0].shape[0]
-            if not self._std_ok(std, A):
-                raise ValueError(f"PolicyForward: policy.{self._std_name} must be a float32 [{A}] tensor, not {std.dtype} {tuple(std.shape)}")
-            self.num_actions = int(A)
-        self._args = nat.GfMlpActArgs()
+        self._setup(policy, "PolicyForward", (("actor", nat.GF_MLP_MAX_ACTIONS), ("critic", 1)), "the policy has neither an actor nor a critic", both=False)
+        self._descriptors(nat.GfMlpActArgs)
 
     def std_param(self):
         """``(policy.std, False)`` or, for a ``noise_std_type="log"`` policy, ``(policy.log_std, True)`` — the parameter is looked up at
         every call, the type was read at construction."""
         return getattr(self.policy, self._std_name, None), self.std_is_log
 
-    @staticmethod
-    def _walk(net, name: str, max_out: int):
-        """[(weight, bias)] of the net's Linear layers (the Parameter objects: their storage may be re-seated later), or None."""
-        return _walk_mlp(net, name, max_out)
-
-    def _fill(self, n: int, actor_parts, critic_parts):
-        """The descriptor with both nets pointed at the current weights and the given inputs (None: that net is left out)."""
-        a = self._args
-        a.num_envs = n
-        _fill_net(a.actor, self.actor, actor_parts, self._normalizer("actor"))
-        _fill_net(a.critic, self.critic, critic_parts, self._normalizer("critic"))
-        return a
-
-    def mean(self, obs) -> torch.Tensor:
-        """The actor's output ``[N, A]`` (``policy.act_mean(obs)``): one launch, a fresh tensor."""
-        return self._one(obs, "actor", self.policy.actor, lambda n, parts: self._fill(n, parts, None))
-
-    def value(self, critic_obs) -> torch.Tensor:
-        """The critic's output ``[N, 1]`` (``policy.evaluate(critic_obs)``): one launch, a fresh tensor."""
-        return self._one(critic_obs, "critic", self.policy.critic, lambda n, parts: self._fill(n, None, parts))
 
 
-class RecurrentForward(_MlpForward):
+class RecurrentForward(_ActorCriticForward):
     """A recurrent policy (:class:`ActorCriticRecurrent`, or rsl_rl's: ``memory_a.rnn`` / ``memory_c.rnn`` one-layer ``nn.LSTM`` or
     ``nn.GRU``, ``actor`` / ``critic`` MLPs) as ``gf_mlp_recurrent_act`` reads it: normaliser, cell, MLP and the sampling in ONE launch
     per step, weights read in place and looked up at every call (as :class:`PolicyForward`), the hidden state — the policy's own
@@ -2257,56 +2315,9 @@ class RecurrentForward(_MlpForward):
     _ENTRY = "mlp_recurrent_act"   # the backend's one-launch step; a backend without it takes the module's torch step
 
     def __init__(self, policy, own_state: bool = False):
-        self.policy = policy
-        who = "RecurrentForward"
-        self.actor = _walk_mlp(getattr(policy, "actor", None), "actor", nat.GF_MLP_MAX_ACTIONS, who)
-        self.critic = _walk_mlp(getattr(policy, "critic", None), "critic", 1, who)
-        if self.actor is None or self.critic is None:
-            raise ValueError(f"{who}: the policy needs an actor and a critic")
-        self._memory = {"actor": getattr(policy, "memory_a", None), "critic": getattr(policy, "memory_c", None)}
-        if own_state:
-            self._memory = {name: _StateHolder(getattr(m, "rnn", None)) for name, m in self._memory.items()}
-        self._cell_type = {name: self._walk_rnn(m, "memory_a" if name == "actor" else "memory_c", getattr(self, name))
-                           for name, m in self._memory.items()}
-        self._normalizer("actor"), self._normalizer("critic")   # (refuses what the kernel cannot fold in)
-        std = self._read_std()
-        A = self.actor[-1][0].shape[0]
-        if std is None or not self._std_ok(std, A):
-            raise ValueError(f"{who}: policy.{self._std_name} must be a float32 [{A}] tensor")
-        self.num_actions = int(A)
-        self._args = nat.GfMlpRecurrentActArgs()
-        self._pending = {"actor": None, "critic": None}
-        self._keep = None
-
-    @staticmethod
-    def _walk_rnn(memory, name: str, layers) -> int:
-        """The cell type of ``policy.<name>.rnn``; ``ValueError`` naming what the kernel cannot run."""
-        who = f"RecurrentForward: policy.{name}.rnn"
-        rnn = getattr(memory, "rnn", None)
-        if not isinstance(rnn, (torch.nn.LSTM, torch.nn.GRU)):
-            raise ValueError(f"{who} must be an nn.LSTM or nn.GRU, not {type(rnn).__name__}")
-        if rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first or getattr(rnn, "proj_size", 0):
-            raise ValueError(f"{who} must have num_layers=1, bias=True, batch_first=False, no projection and one direction")
-        if not 1 <= rnn.hidden_size <= nat.GF_MLP_MAX_HIDDEN:
-            raise ValueError(f"{who} has hidden_size {rnn.hidden_size}; 1 to {nat.GF_MLP_MAX_HIDDEN}")
-        if rnn.input_size > nat.GF_MLP_MAX_INPUT_WIDTH:
-            raise ValueError(f"{who} reads {rnn.input_size} inputs; at most {nat.GF_MLP_MAX_INPUT_WIDTH}")
-        if int(layers[0][0].shape[1]) != rnn.hidden_size:
-            raise ValueError(f"{who} has hidden_size {rnn.hidden_size}; the MLP behind it reads {int(layers[0][0].shape[1])}")
-        for pn in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
-            p = getattr(rnn, pn)
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise ValueError(f"{who}.{pn} must be contiguous float32")
-        return nat.GF_RNN_LSTM if isinstance(rnn, torch.nn.LSTM) else nat.GF_RNN_GRU
-
-    def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
-        """The policy's current normaliser in front of the memory of net ``name``."""
-        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), int(self._memory[name].rnn.input_size),
-                              f"RecurrentForward: policy.{name}_obs_normalizer")
-
-    def _reader(self, name: str):
-        """What ``_segments`` checks an observation of net ``name`` against: the cell's input weights."""
-        return [(self._memory[name].rnn.weight_ih_l0, None)]
+        self._setup(policy, "RecurrentForward", (("actor", nat.GF_MLP_MAX_ACTIONS), ("critic", 1)), "the policy needs an actor and a critic",
+                    memories=(("actor", "memory_a"), ("critic", "memory_c")), own_state=own_state)
+        self._descriptors(nat.GfMlpRecurrentActArgs)
 
     def state(self, name: str, n: int, dev) -> tuple:
         """``(h, c)`` of net ``name`` (``c`` None for a GRU), ``[1, n, H]`` each: the memory's own tensors, zeros where it had none."""
@@ -2338,40 +2349,9 @@ class RecurrentForward(_MlpForward):
         for name, old in self._pending.items():
             self._pending[name] = flags if old is None else (old | flags)
 
-    def _fill(self, n: int, actor_parts, critic_parts, save=None):
-        """The descriptor with the given nets (None: left out) pointed at the current weights, states and pending resets; ``save``:
-        ``{name: (h_save, c_save)}``.  The pending reset of every net in the launch is consumed."""
-        ra = self._args
-        ra.act.num_envs = n
-        keep = []
-        for name, net, cell, parts in (("actor", ra.act.actor, ra.actor_cell, actor_parts), ("critic", ra.act.critic, ra.critic_cell, critic_parts)):
-            _fill_net(net, getattr(self, name), parts, None if parts is None else self._normalizer(name))
-            cell.h_save = cell.c_save = cell.reset = None
-            if parts is None:
-                cell.type = nat.GF_RNN_NONE
-                continue
-            rnn = self._memory[name].rnn
-            h, c = self.state(name, n, parts[0].device)
-            flags = self._pending[name]
-            if flags is not None and (flags.shape[0] != n or flags.device != parts[0].device):
-                raise ValueError(f"RecurrentForward: the pending reset is [{flags.shape[0]}] on {flags.device}; the step has {n} rows on {parts[0].device}")
-            self._pending[name] = None
-            cell.type, cell.hidden = self._cell_type[name], rnn.hidden_size
-            cell.w_ih, cell.w_hh, cell.b_ih, cell.b_hh = (getattr(rnn, p).data_ptr() for p in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"))
-            cell.h, cell.c = h.data_ptr(), None if c is None else c.data_ptr()
-            cell.reset = None if flags is None else flags.data_ptr()
-            if save is not None and name in save:
-                hs, cs = save[name]
-                cell.h_save, cell.c_save = hs.data_ptr(), None if c is None else cs.data_ptr()
-            keep.append((parts, h, c, flags))
-        self._keep = keep
-        return ra
-
     def _fill_cell(self, name: str, cell, parts, n: int, save=None) -> tuple:
         """Point ``cell`` at the memory of net ``name``: the current weights, the state (read and advanced in place), the pending
-        reset — consumed — and ``save[name] = (h_save, c_save)``.  Returns what must outlive the launch.  (:class:`RecurrentDistillForward`'s
-        form of the loop body above, which stays written out in ``_fill``: the recurrent PPO step's host path is left line for line
-        as it was — at 4 096 envs that step is host-bound.)"""
+        reset — consumed — and ``save[name] = (h_save, c_save)``.  Returns what must outlive the launch."""
         rnn = self._memory[name].rnn
         h, c = self.state(name, n, parts[0].device)
         flags = self._pending[name]
@@ -2388,82 +2368,34 @@ class RecurrentForward(_MlpForward):
             cell.h_save, cell.c_save = hs.data_ptr(), None if c is None else cs.data_ptr()
         return (parts, h, c, flags)
 
-    def _one(self, obs, name: str) -> torch.Tensor:
-        fn = getattr(nat.get_backend(), "mlp_recurrent_act", None)
-        parts = _segments(obs, "obs", None, None, self._reader(name))
-        if fn is None:   # (the test-only oracle backend) policy.act_mean / evaluate on this forward's state
-            with torch.no_grad():
-                norm, m = self._normalizer(name), self._memory[name]
-                x = _cat(parts)
-                out, m.hidden_states = m.rnn((x if norm is None else norm(x)).unsqueeze(0), m.hidden_states)
-                return getattr(self.policy, name)(out.squeeze(0))
-        n = int(parts[0].shape[0])
-        out = torch.empty((n, self.num_actions if name == "actor" else 1), device=parts[0].device, dtype=torch.float32)
-        ra = self._fill(n, parts if name == "actor" else None, parts if name == "critic" else None)
-        a = ra.act
-        a.std_is_log = a.std_per_env = 0
-        a.std = a.noise = a.actions = a.actions_out = a.mu_out = a.sigma_out = a.values_out = a.log_prob_out = None
-        a.mean, a.values = (None, out.data_ptr()) if name == "critic" else (out.data_ptr(), None)
-        self._keep_one = out
-        fn(ra)
-        return out
+
+class _DistillAct:
+    """The student–teacher half of :class:`DistillForward` and :class:`RecurrentDistillForward`: ``_args`` is the student–teacher
+    descriptor of the collection step, ``_one_args`` an actor–critic one with the student in the actor's slot for ``mean``."""
+
+    def _setup_distill(self, policy, who: str, memories=(), own_state: bool = False) -> None:
+        self._setup(policy, who, (("student", nat.GF_MLP_MAX_ACTIONS), ("teacher", nat.GF_MLP_MAX_ACTIONS)), "the policy needs a student and a teacher",
+                    memories=memories, own_state=own_state, same_width=True)
+        self._descriptors(*((nat.GfMlpRecurrentDistillArgs, nat.GfMlpRecurrentActArgs) if memories else (nat.GfMlpDistillArgs, nat.GfMlpActArgs)))
 
     def mean(self, obs) -> torch.Tensor:
-        """The actor's output ``[N, A]`` for one more step of its memory (``policy.act_mean(obs)``): one launch, a fresh tensor."""
-        return self._one(obs, "actor")
-
-    def value(self, critic_obs) -> torch.Tensor:
-        """The critic's output ``[N, 1]`` for one more step of its memory (``policy.evaluate(critic_obs)``): one launch."""
-        return self._one(critic_obs, "critic")
-
-
-class DistillForward(_MlpForward):
-    """The student and the teacher of a policy (``policy.student`` / ``policy.teacher``, a :class:`StudentTeacherMLP` or anything of
-    that shape) as ``gf_mlp_distill_act`` reads them — the counterpart of :class:`PolicyForward`, under its rules: the structure is
-    checked once, the weight addresses and the normalisers (``policy.student_obs_normalizer`` / ``teacher_obs_normalizer``) are looked
-    up at every call.  Both nets are required and must have the same output width; ``policy.std`` (``log_std``) must be ``[A]``.
-
-    ``mean(obs)``: the student's mean — play-time inference, one ``gf_mlp_act`` launch.  ``act(obs, teacher_obs)``: the collection
-    step, ONE ``gf_mlp_distill_act`` launch; ``RolloutStorage.act_distill`` calls it with its rows as the second destinations."""
-
-    def __init__(self, policy):
-        self.policy = policy
-        self.student = _walk_mlp(getattr(policy, "student", None), "student", nat.GF_MLP_MAX_ACTIONS, "DistillForward")
-        self.teacher = _walk_mlp(getattr(policy, "teacher", None), "teacher", nat.GF_MLP_MAX_ACTIONS, "DistillForward")
-        if self.student is None or self.teacher is None:
-            raise ValueError("DistillForward: the policy needs a student and a teacher")
-        A = int(self.student[-1][0].shape[0])
-        if int(self.teacher[-1][0].shape[0]) != A:
-            raise ValueError(f"DistillForward: policy.student has {A} outputs, policy.teacher {int(self.teacher[-1][0].shape[0])}")
-        self._normalizer("student"), self._normalizer("teacher")   # (refuses what the kernel cannot fold in)
-        std = self._read_std()
-        if std is None or not self._std_ok(std, A):
-            raise ValueError(f"DistillForward: policy.{self._std_name} must be a float32 [{A}] tensor")
-        self.num_actions = A
-        self._args, self._mean_args = nat.GfMlpDistillArgs(), nat.GfMlpActArgs()
-
-    def mean(self, obs) -> torch.Tensor:
-        """The student's output ``[N, A]`` (``policy.act_mean(obs)``): one launch, a fresh tensor."""
-        return self._one(obs, "student", self.policy.student, self._fill_mean)
-
-    def _fill_mean(self, n: int, parts):
-        a = self._mean_args
-        a.num_envs = n
-        _fill_net(a.actor, self.student, parts, self._normalizer("student"))
-        a.critic.num_layers = 0
-        return a
+        """The student's output ``[N, A]`` (``policy.act_mean(obs)``, one more step of its memory where it has one): one launch, a
+        fresh tensor."""
+        return self._one(obs, "student")
 
     def act(self, obs, teacher_obs=None, noise: Optional[torch.Tensor] = None, seed: int = 0, stream: int = 0, env_offset: int = 0,
-            actions_out: Optional[torch.Tensor] = None, teacher_actions_out: Optional[torch.Tensor] = None, backend=None):
+            actions_out: Optional[torch.Tensor] = None, teacher_actions_out: Optional[torch.Tensor] = None, backend=None, save=None):
         """``(actions, teacher_actions)``, fresh ``[N, A]`` tensors: ``Normal(student(obs), std).sample()`` and ``teacher(teacher_obs)``
-        (``teacher_obs=None``: the teacher reads ``obs``) in ONE ``gf_mlp_distill_act`` launch; ``actions_out`` / ``teacher_actions_out``:
-        contiguous ``[N, A]`` rows that receive the same values from the same launch.  ``noise`` / ``seed`` / ``stream`` /
-        ``env_offset``: as ``gf_policy_act``'s.  On a backend without the entry point (the test-only CPU oracle) the same expression
-        runs in torch and ``noise`` is required."""
-        segs = _segments(obs, "obs", None, None, self.student)
+        (``teacher_obs=None``: the teacher reads ``obs``) in ONE launch of the forward's entry — ``gf_mlp_distill_act``, or, with both
+        memories advanced by one step in place, ``gf_mlp_recurrent_distill_act``; ``actions_out`` / ``teacher_actions_out``: contiguous
+        ``[N, A]`` rows that receive the same values from the same launch.  ``noise`` / ``seed`` / ``stream`` / ``env_offset``: as
+        ``gf_policy_act``'s.  ``save`` (a forward with memories): ``{"student": (h_save, c_save)}`` (``[N, H]`` each, ``c_save`` None
+        for a GRU; ``"teacher"`` likewise) receive the state the step started from, after the reset.  On a backend without the entry
+        point (the test-only CPU oracle) the same expression runs in torch on the module's step and ``noise`` is required."""
+        segs = _segments(obs, "obs", None, None, self._reader("student"))
         n, dev = int(segs[0].shape[0]), segs[0].device
         tsegs = _segments(obs if teacher_obs is None else teacher_obs, "obs (the teacher's input)" if teacher_obs is None else "teacher_obs", n, dev,
-                          self.teacher)
+                          self._reader("teacher"))
         A = self.num_actions
         std = getattr(self.policy, self._std_name)
         _check_f32(std, f"policy.{self._std_name}", {(A,)}, dev)
@@ -2471,12 +2403,14 @@ class DistillForward(_MlpForward):
             if t is not None:
                 _check_f32(t, name, {(n, A)}, dev)
         backend = nat.get_backend() if backend is None else backend
-        fn = getattr(backend, "mlp_distill_act", None)
+        fn = getattr(backend, self._ENTRY, None)
         if fn is None:   # (the test-only oracle backend) the same expression in torch, from the given draws
             if noise is None:
-                raise RuntimeError("act() draws its noise in the HIP kernel: on a backend without gf_mlp_distill_act pass noise=")
+                raise RuntimeError(f"act() draws its noise in the HIP kernel: on a backend without gf_{self._ENTRY} pass noise=")
             with torch.no_grad():
-                mean, teacher = self.policy.act_mean(_cat(segs)), self.policy.evaluate(_cat(tsegs)).clone()
+                for name, dst in (save or {}).items():
+                    self._save_torch(name, dst)
+                mean, teacher = self._torch_step("student", _cat(segs)), self._torch_step("teacher", _cat(tsegs)).clone()
                 actions, _sd = _sample_torch(mean, std, noise, self.std_is_log)
                 if actions_out is not None:
                     actions_out.copy_(actions)
@@ -2485,23 +2419,40 @@ class DistillForward(_MlpForward):
             return actions, teacher
         actions = torch.empty((n, A), device=dev, dtype=torch.float32)
         teacher = torch.empty((n, A), device=dev, dtype=torch.float32)
-        a = self._args
-        a.num_envs = n
-        _fill_net(a.student, self.student, segs, self._normalizer("student"))
-        _fill_net(a.teacher, self.teacher, tsegs, self._normalizer("teacher"))
-        a.std, a.std_is_log = std.data_ptr(), 1 if self.std_is_log else 0
-        a.noise = None if noise is None else noise.data_ptr()
-        a.seed, a.stream, a.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(env_offset)
-        a.mean = None
-        a.actions, a.teacher_actions = actions.data_ptr(), teacher.data_ptr()
+        a = self._fill_desc(self._args_parts, n, (("student", "student", segs), ("teacher", "teacher", tsegs)), save)
+        _fill_sampling(a, std, self.std_is_log, noise, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(env_offset), actions)
+        a.teacher_actions = teacher.data_ptr()
         a.actions_out = None if actions_out is None else actions_out.data_ptr()
         a.teacher_actions_out = None if teacher_actions_out is None else teacher_actions_out.data_ptr()
-        self._keep = (segs, tsegs, noise, actions_out, teacher_actions_out)
-        fn(a)
+        self._keep = (self._keep, noise, actions_out, teacher_actions_out, save)
+        fn(self._args)
         return actions, teacher
 
+    def _save_torch(self, name: str, dst) -> None:
+        """``h_save`` / ``c_save`` of the torch step: the state of net ``name`` as the step will read it (zeros where there is none)."""
+        hs = self._memory[name].hidden_states
+        parts = () if hs is None else (tuple(hs) if isinstance(hs, tuple) else (hs,))
+        for i, d in enumerate(dst):
+            if d is not None:
+                d.copy_(parts[i][0]) if parts else d.zero_()
 
-class RecurrentDistillForward(RecurrentForward):
+
+class DistillForward(_DistillAct, _MlpForward):
+    """The student and the teacher of a policy (``policy.student`` / ``policy.teacher``, a :class:`StudentTeacherMLP` or anything of
+    that shape) as ``gf_mlp_distill_act`` reads them — the counterpart of :class:`PolicyForward`, under its rules: the structure is
+    checked once, the weight addresses and the normalisers (``policy.student_obs_normalizer`` / ``teacher_obs_normalizer``) are looked
+    up at every call.  Both nets are required and must have the same output width; ``policy.std`` (``log_std``) must be ``[A]``.
+
+    ``mean(obs)``: the student's mean — play-time inference, one ``gf_mlp_act`` launch.  ``act(obs, teacher_obs)``: the collection
+    step, ONE ``gf_mlp_distill_act`` launch; ``RolloutStorage.act_distill`` calls it with its rows as the second destinations."""
+
+    _ENTRY = "mlp_distill_act"
+
+    def __init__(self, policy):
+        self._setup_distill(policy, "DistillForward")
+
+
+class RecurrentDistillForward(_DistillAct, RecurrentForward):
     """A recurrent student and its teacher (:class:`StudentTeacherRecurrent`, or rsl_rl's: ``memory_s.rnn`` in front of ``student``,
     optionally ``memory_t.rnn`` in front of ``teacher``) as ``gf_mlp_recurrent_distill_act`` reads them — :class:`DistillForward`'s
     checks for the two nets and ``std``, :class:`RecurrentForward`'s for every memory, weights and normalisers looked up at every call.
@@ -2517,141 +2468,11 @@ class RecurrentDistillForward(RecurrentForward):
     _ENTRY = "mlp_recurrent_distill_act"
 
     def __init__(self, policy, own_state: bool = False):
-        self.policy = policy
-        who = "RecurrentDistillForward"
-        self.student = _walk_mlp(getattr(policy, "student", None), "student", nat.GF_MLP_MAX_ACTIONS, who)
-        self.teacher = _walk_mlp(getattr(policy, "teacher", None), "teacher", nat.GF_MLP_MAX_ACTIONS, who)
-        if self.student is None or self.teacher is None:
-            raise ValueError(f"{who}: the policy needs a student and a teacher")
-        A = int(self.student[-1][0].shape[0])
-        if int(self.teacher[-1][0].shape[0]) != A:
-            raise ValueError(f"{who}: policy.student has {A} outputs, policy.teacher {int(self.teacher[-1][0].shape[0])}")
-        self._memory = {"student": getattr(policy, "memory_s", None)}
-        if getattr(policy, "memory_t", None) is not None:
-            self._memory["teacher"] = policy.memory_t
-        if own_state:
-            self._memory = {name: _StateHolder(getattr(m, "rnn", None)) for name, m in self._memory.items()}
-        self._cell_type = {name: self._walk_rnn(m, "memory_s" if name == "student" else "memory_t", getattr(self, name))
-                           for name, m in self._memory.items()}
-        self._normalizer("student"), self._normalizer("teacher")   # (refuses what the kernel cannot fold in)
-        std = self._read_std()
-        if std is None or not self._std_ok(std, A):
-            raise ValueError(f"{who}: policy.{self._std_name} must be a float32 [{A}] tensor")
-        self.num_actions = A
-        self._args, self._mean_args = nat.GfMlpRecurrentDistillArgs(), nat.GfMlpRecurrentActArgs()
-        self._pending = dict.fromkeys(self._memory)
-        self._keep = None
-
-    def _reader(self, name: str):
-        """What ``_segments`` checks an observation of net ``name`` against: its cell's input weights, or its first layer."""
-        return [(self._memory[name].rnn.weight_ih_l0, None)] if name in self._memory else getattr(self, name)
-
-    def _normalizer(self, name: str) -> Optional["EmpiricalNormalization"]:
-        return _as_normalizer(getattr(self.policy, name + "_obs_normalizer", None), int(self._reader(name)[0][0].shape[1]),
-                              f"RecurrentDistillForward: policy.{name}_obs_normalizer")
-
-    def _fill_nets(self, n: int, nets, save=None) -> list:
-        """``nets``: ``(name, GfMlpNet, GfRnnCell, segments)`` each — pointed at the current weights, normaliser, state and pending
-        reset (consumed); a net without a memory gets ``GF_RNN_NONE``."""
-        keep = []
-        for name, net, cell, parts in nets:
-            _fill_net(net, getattr(self, name), parts, self._normalizer(name))
-            if name in self._memory:
-                keep.append(self._fill_cell(name, cell, parts, n, save))
-            else:
-                cell.type = nat.GF_RNN_NONE
-                cell.h_save = cell.c_save = cell.reset = None
-                keep.append(parts)
-        return keep
-
-    def _torch_step(self, name: str, x: torch.Tensor) -> torch.Tensor:
-        """Net ``name`` of the module on this forward's state (the policy's own unless ``own_state``), under ``no_grad``."""
-        norm = self._normalizer(name)
-        x = x if norm is None else norm(x)
-        if name in self._memory:
-            m = self._memory[name]
-            x, m.hidden_states = m.rnn(x.unsqueeze(0), m.hidden_states)
-            x = x.squeeze(0)
-        return getattr(self.policy, name)(x)
-
-    def mean(self, obs) -> torch.Tensor:
-        """The student's output ``[N, A]`` for one more step of its memory (``policy.act_mean(obs)``): one launch, a fresh tensor."""
-        parts = _segments(obs, "obs", None, None, self._reader("student"))
-        fn = getattr(nat.get_backend(), "mlp_recurrent_act", None)
-        if fn is None:   # (the test-only oracle backend)
-            with torch.no_grad():
-                return self._torch_step("student", _cat(parts))
-        n = int(parts[0].shape[0])
-        out = torch.empty((n, self.num_actions), device=parts[0].device, dtype=torch.float32)
-        ra = self._mean_args
-        a = ra.act
-        a.num_envs = n
-        a.critic.num_layers = 0
-        ra.critic_cell.type = nat.GF_RNN_NONE
-        self._keep = self._fill_nets(n, [("student", a.actor, ra.actor_cell, parts)])
-        a.std_is_log = a.std_per_env = 0
-        a.std = a.noise = a.actions = a.actions_out = a.mu_out = a.sigma_out = a.values = a.values_out = a.log_prob_out = None
-        a.mean = out.data_ptr()
-        fn(ra)
-        return out
+        memories = (("student", "memory_s"), ("teacher", "memory_t")) if getattr(policy, "memory_t", None) is not None else (("student", "memory_s"),)
+        self._setup_distill(policy, "RecurrentDistillForward", memories, own_state)
 
     def value(self, critic_obs):
         raise ValueError("RecurrentDistillForward: a student–teacher policy has no critic")
-
-    def act(self, obs, teacher_obs=None, noise: Optional[torch.Tensor] = None, seed: int = 0, stream: int = 0, env_offset: int = 0,
-            actions_out: Optional[torch.Tensor] = None, teacher_actions_out: Optional[torch.Tensor] = None, backend=None, save=None):
-        """``(actions, teacher_actions)``, fresh ``[N, A]`` tensors, as :meth:`DistillForward.act` — with both memories advanced by one
-        step in place, in ONE ``gf_mlp_recurrent_distill_act`` launch.  ``save``: ``{"student": (h_save, c_save)}`` (``[N, H]`` each,
-        ``c_save`` None for a GRU; ``"teacher"`` likewise) receive the state the step started from, after the reset."""
-        segs = _segments(obs, "obs", None, None, self._reader("student"))
-        n, dev = int(segs[0].shape[0]), segs[0].device
-        tsegs = _segments(obs if teacher_obs is None else teacher_obs, "obs (the teacher's input)" if teacher_obs is None else "teacher_obs", n, dev,
-                          self._reader("teacher"))
-        A = self.num_actions
-        std = getattr(self.policy, self._std_name)
-        _check_f32(std, f"policy.{self._std_name}", {(A,)}, dev)
-        for t, name in ((noise, "noise"), (actions_out, "actions_out"), (teacher_actions_out, "teacher_actions_out")):
-            if t is not None:
-                _check_f32(t, name, {(n, A)}, dev)
-        backend = nat.get_backend() if backend is None else backend
-        fn = getattr(backend, self._ENTRY, None)
-        if fn is None:   # (the test-only oracle backend) the module's torch step, from the given draws
-            if noise is None:
-                raise RuntimeError("act() draws its noise in the HIP kernel: on a backend without gf_mlp_recurrent_distill_act pass noise=")
-            with torch.no_grad():
-                for name, dst in (save or {}).items():
-                    self._save_torch(name, n, dev, dst)
-                mean, teacher = self._torch_step("student", _cat(segs)), self._torch_step("teacher", _cat(tsegs)).clone()
-                actions, _sd = _sample_torch(mean, std, noise, self.std_is_log)
-                if actions_out is not None:
-                    actions_out.copy_(actions)
-                if teacher_actions_out is not None:
-                    teacher_actions_out.copy_(teacher)
-            return actions, teacher
-        actions = torch.empty((n, A), device=dev, dtype=torch.float32)
-        teacher = torch.empty((n, A), device=dev, dtype=torch.float32)
-        ra = self._args
-        a = ra.act
-        a.num_envs = n
-        keep = self._fill_nets(n, [("student", a.student, ra.student_cell, segs), ("teacher", a.teacher, ra.teacher_cell, tsegs)], save)
-        a.std, a.std_is_log = std.data_ptr(), 1 if self.std_is_log else 0
-        a.noise = None if noise is None else noise.data_ptr()
-        a.seed, a.stream, a.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(env_offset)
-        a.mean = None
-        a.actions, a.teacher_actions = actions.data_ptr(), teacher.data_ptr()
-        a.actions_out = None if actions_out is None else actions_out.data_ptr()
-        a.teacher_actions_out = None if teacher_actions_out is None else teacher_actions_out.data_ptr()
-        self._keep = (keep, noise, actions_out, teacher_actions_out, save)
-        fn(ra)
-        return actions, teacher
-
-    def _save_torch(self, name: str, n: int, dev, dst) -> None:
-        """``h_save`` / ``c_save`` of the torch step: the state of net ``name`` as the step will read it (zeros where there is none)."""
-        hs = self._memory[name].hidden_states
-        parts = () if hs is None else (tuple(hs) if isinstance(hs, tuple) else (hs,))
-        for i, d in enumerate(dst):
-            if d is not None:
-                d.copy_(parts[i][0]) if parts else d.zero_()
 
 
 def _rnd_reward_torch(rnd: "RandomNetworkDistillation", rnd_state: torch.Tensor, rewards=None, acc_extrinsic=None, acc_intrinsic=None) -> torch.Tensor:

@@ -9,7 +9,9 @@ and their optional pointers are NULL.
 * gf_adam_step against clip_grad_norm_ + torch.optim.Adam(foreach=True) on one flat parameter, two steps, at the chunk edges, at
   257 norm partials and past 2^20 elements, where the norm kernel's workgroups read a second chunk each.
 * gf_gae against rsl_rl's compute_returns loop (bit for bit) on T around its 12-step load batches and N around the workgroup
-  size, with rows that are never / always / sometimes done; the same grid on the CPU oracle's twin."""
+  size, with rows that are never / always / sometimes done; the same grid on the CPU oracle's twin.
+* gf_bc_loss and gf_mirror_loss at 256, 257 and 513 workgroup records, where the lanes of finalize_mean_loss stride, and at A = 1,
+  with the assertions and float64 bounds of tests/test_distillation.py and tests/test_symmetry.py."""
 import functools
 import math
 
@@ -356,3 +358,110 @@ def test_gae_normalize_tails_and_misaligned_advantages(hip_backend, T, N, offset
 @pytest.mark.parametrize("offset", [0, 1])
 def test_gae_oracle_tails_and_misaligned_advantages(oracle_backend, T, N, offset):
     _check_gae(oracle_backend, "cpu", T, N, "random", offset=offset)
+
+
+# ---- finalize_mean_loss (gf_reduce.h): the record stride of gf_bc_loss and gf_mirror_loss ------------------------------------------------
+# One workgroup of 256 lanes sums ceil(rows / 256) records with a lane stride: 256 records — every lane one; 257 — lane 0 two;
+# 513 — lane 0 three, every other lane two.
+MEAN_LOSS_ROWS = [65536, 65537, 131073]
+MEAN_LOSS_LANES = 256
+
+
+def _records_per_lane(rows):
+    nb = -(-rows // MEAN_LOSS_LANES)
+    return nb, [len(range(lane, nb, MEAN_LOSS_LANES)) for lane in (0, 1, MEAN_LOSS_LANES - 1)]
+
+
+def test_mean_loss_rows_reach_the_record_stride():
+    assert [_records_per_lane(r) for r in MEAN_LOSS_ROWS] == [(256, [1, 1, 1]), (257, [2, 1, 1]), (513, [3, 2, 2])]
+    assert _records_per_lane(513) == (3, [1, 1, 0]), "where the suite stopped before: three records, no lane strides"
+
+
+@functools.lru_cache(maxsize=1)
+def _mean_loss_inputs(rows, A):
+    """mu, target (CPU float32) with |d| exactly 1, just inside and just outside in the first elements, as test_bc_loss_and_gradient."""
+    g = torch.Generator().manual_seed(rows + A)
+    mu, target = torch.randn(rows, A, generator=g), torch.randn(rows, A, generator=g) * 1.5
+    one = torch.tensor(1.0)
+    edge = [1.0, -1.0, float(torch.nextafter(one, one * 0)), -float(torch.nextafter(one, one * 0)), float(torch.nextafter(one, one * 2)),
+            -float(torch.nextafter(one, one * 2))]
+    target.view(-1)[:len(edge)] = 0.0
+    mu.view(-1)[:len(edge)] = torch.tensor(edge)
+    assert (mu - target).view(-1)[:len(edge)].tolist() == edge
+    return mu, target
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("A", [1, 3])
+@pytest.mark.parametrize("rows", MEAN_LOSS_ROWS)
+def test_bc_loss_record_stride(hip_backend, rows, A):
+    """test_bc_loss_and_gradient's assertions and bounds (neither derivation depends on the row count: the sum is double) where the
+    finalize lanes stride; every row is in every check."""
+    from test_distillation import _bc_loss
+    from test_symmetry import _mirror_loss
+
+    perm, sign = torch.arange(A, dtype=torch.int32, device="cuda"), torch.ones(A, device="cuda")
+    mu, target = (x.cuda() for x in _mean_loss_inputs(rows, A))
+    d64 = mu.double() - target.double()
+    for loss_type in (0, 1):
+        if loss_type == 0:
+            loss64, grad64 = float((d64 * d64).mean()), 2.0 * d64 / (rows * A)
+        else:
+            e = torch.where(d64.abs() < 1, 0.5 * d64 * d64, d64.abs() - 0.5)
+            loss64, grad64 = float(e.mean()), d64.clamp(-1, 1) / (rows * A)
+            ref = torch.nn.functional.huber_loss(mu.double(), target.double())
+            assert abs(float(ref) - loss64) <= 1e-13 * loss64, "the float64 reference is torch's huber_loss"
+        grad = torch.full((rows, A), 7.0, device="cuda")
+        sums = torch.tensor([1.5], dtype=torch.float64, device="cuda")
+        out = _bc_loss(hip_backend, mu, target, loss_type, grad, sums)
+        e_loss = abs(float(out[0]) - loss64) / loss64
+        e_grad = float(((grad.double() - grad64).abs() / grad64.abs().clamp_min(1e-300)).max())
+        print(f"    A={A} rows={rows} type={loss_type}: loss rel err {e_loss:.3e}, grad rel err {e_grad:.3e} (bounds {4 * U:.3e})")
+        assert e_loss <= 4 * U, f"loss {float(out[0])} vs {loss64}"
+        assert bool(((grad.double() - grad64).abs() <= 4 * U * grad64.abs()).all()), f"gradient: max rel err {e_grad}"
+        assert float(sums[0]) == 1.5 + float(out[0]), "the running sum takes the float32 loss"
+        if loss_type == 0:
+            zero = torch.zeros(rows, A, device="cuda")
+            mir = _mirror_loss(hip_backend, mu, target, perm, sign, 1.0, zero)
+            assert torch.equal(mir, out) and torch.equal(zero, grad), "mse is gf_mirror_loss's operation order"
+        again = torch.full((rows, A), -3.0, device="cuda")   # written, not added; bitwise reproducible; loss only writes out / sums
+        assert torch.equal(_bc_loss(hip_backend, mu, target, loss_type, again), out) and torch.equal(again, grad)
+        assert torch.equal(_bc_loss(hip_backend, mu, target, loss_type, None, sums), out)
+        assert float(sums[0]) == (1.5 + float(out[0])) + float(out[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("A", [1, 3])
+@pytest.mark.parametrize("rows", MEAN_LOSS_ROWS)
+def test_mirror_loss_record_stride(hip_backend, rows, A):
+    """test_mirror_loss_and_gradient_against_float64's assertions and bounds where the finalize lanes stride.  A = 3: a 2-cycle, a fixed
+    point and both signs; A = 1 has the one permutation, with sign -1."""
+    from test_symmetry import _mirror_loss
+
+    perm, sign = ([1, 0, 2], [-1.0, -1.0, 1.0]) if A == 3 else ([0], [-1.0])
+    assert (perm != list(range(A)) or A == 1) and (len(set(sign)) == 2 or A == 1)
+    p, s = torch.tensor(perm, dtype=torch.int32, device="cuda"), torch.tensor(sign, dtype=torch.float32, device="cuda")
+    coeff = 0.75   # (exact in float32)
+    g = torch.Generator().manual_seed(rows + A)
+    mm, mo = torch.randn(rows, A, generator=g).cuda(), torch.randn(rows, A, generator=g).cuda()
+    d64 = mm.double() - s.double() * mo.double()[:, p.long()]
+    loss64, grad64 = float((d64 * d64).mean()), coeff * 2.0 * d64 / (rows * A)
+    zero = torch.zeros(rows, A, device="cuda")
+    sums = torch.tensor([1.5], dtype=torch.float64, device="cuda")
+    out = _mirror_loss(hip_backend, mm, mo, p, s, coeff, zero, sums)
+    e_loss = abs(float(out[0]) - loss64) / loss64
+    e_grad = float(((zero.double() - grad64).abs() / grad64.abs().clamp_min(1e-300)).max())
+    print(f"    A={A} rows={rows}: loss rel err {e_loss:.3e} (bound {4 * U:.3e}), grad rel err {e_grad:.3e} (bound {4 * U:.3e})")
+    assert e_loss <= 4 * U, f"loss {float(out[0])} vs {loss64}"
+    assert bool(((zero.double() - grad64).abs() <= 4 * U * grad64.abs()).all()), f"gradient: max rel err {e_grad}"
+    assert float(sums[0]) == 1.5 + float(out[0]), "the running sum takes the float32 loss"
+    base = torch.randn(rows, A, generator=g).cuda()   # added into a non-zero buffer, not stored
+    buf = base.clone()
+    again = _mirror_loss(hip_backend, mm, mo, p, s, coeff, buf)
+    assert torch.equal(buf, base + zero) and torch.equal(again, out), "bitwise reproducible, and an addition"
+    assert torch.equal(_mirror_loss(hip_backend, mm, mo, p, s, coeff, None), out)
+    keep = base.clone()
+    keep[0, 0] = -0.0
+    bits = keep.view(torch.int32).clone()
+    assert torch.equal(_mirror_loss(hip_backend, mm, mo, p, s, 0.0, keep), out)
+    assert torch.equal(keep.view(torch.int32), bits)

@@ -553,6 +553,17 @@ class GfObsNormArgs(C.Structure):
     _fields_ = [("num_rows", C.c_int64), ("num_sets", C.c_int32), ("_pad", C.c_int32), ("sets", GfObsNormSet * GF_OBS_NORM_MAX_SETS)]
 
 
+# the terrain height scan (managers.HeightScanner.scan): gf_height_scan — additive like gf_obs_norm_update, not in ABI_STRUCTS
+GF_HEIGHT_SCAN_MAX_POINTS = 1024
+GF_HEIGHT_SCAN_TILE_ENVS = 16
+
+
+class GfHeightScanArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("pos", P), ("quat", P), ("pattern", P), ("out", P), ("points_out", P), ("pos_stride", C.c_int64),
+                ("quat_stride", C.c_int64), ("out_stride", C.c_int64), ("terrain", GfTerrainView), ("num_points", C.c_int32),
+                ("align", C.c_int32), ("relative", C.c_int32), ("offset", C.c_float), ("clip_lo", C.c_float), ("clip_hi", C.c_float)]
+
+
 # the newest frame of a history observation into a frame-major rollout storage (learner.RolloutStorage(history="frames")):
 # gf_rollout_frame_write, issued by the storage behind the step's rollout_write — not a phase, not in ABI_STRUCTS either
 GF_SIZEOF_ROLLOUT_FRAME = 30
@@ -806,6 +817,12 @@ class HipBackend(Backend):
                 raise GfError(f"ABI drift: sizeof({st.__name__}) is {n} in the library, {C.sizeof(st)} in the binding")
             getattr(self.lib, fn).restype = C.c_int
             getattr(self.lib, fn).argtypes = [C.POINTER(st), C.c_void_p]
+        # the terrain height scan (managers.HeightScanner): an additive entry that reports its descriptor's size itself
+        n = self.lib.gf_height_scan_sizeof()
+        if n != C.sizeof(GfHeightScanArgs):
+            raise GfError(f"ABI drift: sizeof(GfHeightScanArgs) is {n} in the library, {C.sizeof(GfHeightScanArgs)} in the binding")
+        self.lib.gf_height_scan.restype = C.c_int
+        self.lib.gf_height_scan.argtypes = [C.POINTER(GfHeightScanArgs), C.c_void_p]
         n = self.lib.gf_sizeof(GF_SIZEOF_RNN_CELL)
         if n != C.sizeof(GfRnnCell):
             raise GfError(f"ABI drift: sizeof(GfRnnCell) is {n} in the library, {C.sizeof(GfRnnCell)} in the binding")
@@ -935,6 +952,13 @@ class HipBackend(Backend):
         if rc != 0:
             self._raise("profile_end", rc)
         return tot.value, cnt.value
+
+    def height_scan(self, args) -> None:
+        """gf_height_scan on the current stream (managers.HeightScanner.scan).  Only this backend has it: a backend without the method
+        makes the scanner compose the scan from torch ops and ``get_terrain_height``."""
+        rc = self.lib.gf_height_scan(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("height_scan", rc)
 
     def build_info(self) -> str:
         return self.lib.gf_build_info().decode()

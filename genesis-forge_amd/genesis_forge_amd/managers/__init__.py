@@ -6,6 +6,7 @@ from .command import CommandManager, VelocityCommandManager
 from .gait_command import GaitCommandManager
 from .contact import ContactManager
 from .terrain_manager import TerrainManager
+from .height_scanner import HeightScanner
 from .entity_manager import EntityManager
 from .observation_manager import ObservationManager
 from .config import MdpFnClass, ResetMdpFnClass
@@ -13,5 +14,5 @@ from .config import MdpFnClass, ResetMdpFnClass
 __all__ = [
     "BaseManager", "RewardManager", "TerminationManager", "CommandManager", "VelocityCommandManager", "GaitCommandManager",
     "BaseActionManager", "PositionActionManager", "PositionWithinLimitsActionManager", "ContactManager",
-    "TerrainManager", "EntityManager", "ObservationManager", "MdpFnClass", "ResetMdpFnClass",
+    "TerrainManager", "HeightScanner", "EntityManager", "ObservationManager", "MdpFnClass", "ResetMdpFnClass",
 ]

@@ -79,3 +79,10 @@ def contact_force(env, contact_manager) -> torch.Tensor:
     it.op, it.width, it.i0, it.scale, it.noise = nat.GF_O_CONTACT_FORCE_NORM, L, 0, 1.0, 0.0
     env.backend.call("observe", a, owner=None)
     return _tag(out, ("contact_norm", contact_manager))
+
+
+def height_scan(env, scanner) -> torch.Tensor:
+    """The terrain heights around the base, shape (num_envs, scanner.num_points): ``scanner.scan()`` (managers/height_scanner.py — one
+    ``gf_height_scan`` launch into the scanner's persistent buffer).  Untagged: ObservationManager evaluates it as an EXTERNAL item
+    each step and applies the item's ``scale`` / ``noise`` like any other; the reference has no counterpart."""
+    return scanner.scan()

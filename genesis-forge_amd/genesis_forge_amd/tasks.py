@@ -421,14 +421,19 @@ class HumanoidGaitLikeEnv(ManagedEnvironment):
 class Go2RoughTerrainEnv(ManagedEnvironment):
     """BASELINE config 3 (cf. examples/rough_terrain/environment.py:87-287): Go2 on a height-field terrain, TerrainManager,
     random terrain spawn with random yaw on reset, out_of_bounds termination, two contact managers, 9 reward terms — plus
-    (``height_reward=True``) ``base_height(terrain_manager=…)`` so the in-kernel height lookup is on the path."""
+    (``height_reward=True``) ``base_height(terrain_manager=…)`` so the in-kernel height lookup is on the path.
+    ``height_scan`` (a dict of ``HeightScanner`` keyword arguments; ``{}`` is the default 17 x 11 grid) adds ``self.height_scanner``
+    and a second ObservationManager, ``"critic"``: the policy's items plus the terrain heights around the base — the privileged input of
+    an asymmetric critic (``RolloutStorage(env, T, obs_groups={"policy": ["policy"], "critic": ["critic"]})``) or of a teacher.
+    ``None`` (the default) builds what the reference's example builds: a blind policy."""
 
     def __init__(self, num_envs=1, dt=1 / 50, max_episode_length_s=20, scene_kwargs=None, height_reward=True, rotation="default",
-                 terrain_kwargs=None, cmd_resample_s=5.0):
+                 terrain_kwargs=None, cmd_resample_s=5.0, height_scan=None):
         super().__init__(num_envs=num_envs, dt=dt, max_episode_length_sec=max_episode_length_s, max_episode_random_scaling=0.1)
         kw = dict(scene_kwargs or {})
         kw.setdefault("max_collision_pairs", 12)
         self._height_reward, self._rotation, self._cmd_resample_s = height_reward, rotation, cmd_resample_s
+        self._height_scan = None if height_scan is None else dict(height_scan)
         self.scene = new_scene(dt=self.dt, substeps=2, **kw)
         tk = dict(pos=(-12, -12, 0), n_subterrains=(1, 1), subterrain_size=(24, 24), vertical_scale=0.001,
                   subterrain_types=[["random_uniform_terrain"]],
@@ -478,7 +483,7 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
             "bad_orientation": {"fn": terminations.bad_orientation,
                                 "params": {"limit_angle": 30.0, "entity_manager": self.robot_manager, "grace_steps": 20}},
         })
-        self.observation_manager = ObservationManager(self, cfg={
+        policy_items = lambda: {
             "velocity_cmd": {"fn": self.velocity_command.observation},
             "angle_velocity": {"fn": lambda env: self.robot_manager.get_angular_velocity()},
             "linear_velocity": {"fn": lambda env: self.robot_manager.get_linear_velocity()},
@@ -486,7 +491,14 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
             "dof_position": {"fn": lambda env: self.action_manager.get_dofs_position()},
             "dof_velocity": {"fn": lambda env: self.action_manager.get_dofs_velocity(), "scale": 0.05},
             "actions": {"fn": lambda env: self.action_manager.get_actions()},
-        })
+        }
+        self.observation_manager = ObservationManager(self, cfg=policy_items())
+        if self._height_scan is not None:
+            from genesis_forge_amd.managers import HeightScanner
+
+            self.height_scanner = HeightScanner(self, self.terrain_manager, entity_manager=self.robot_manager, **self._height_scan)
+            self.critic_manager = ObservationManager(self, name="critic", cfg=dict(
+                policy_items(), height_scan={"fn": observations.height_scan, "params": {"scanner": self.height_scanner}}))
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

@@ -1482,6 +1482,49 @@ typedef struct GfHistoryUnrollArgs {
 } GfHistoryUnrollArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * Terrain height scan (managers/height_scanner.py; legged_gym's `measured_heights`, Isaac Lab's `height_scan`): the terrain
+ * height at P points around each env's base, P body-frame offsets (x forward, y left) shared by every env and turned by the
+ * base's yaw.  One launch writes out[n, p] for n < num_envs, p < num_points.  Per element, in f32 with one rounding per operation:
+ *     c  = 1 - 2*(qy*qy + qz*qz)        s = 2*(qw*qz + qx*qy)              (the yaw's cosine and sine times cos(pitch))
+ *     nrm = sqrt(c*c + s*s)
+ *     (cy, sy) = nrm < 1e-6f ? (1, 0) : (c / nrm, s / nrm)                 (align = 0: (1, 0), `quat` is never read)
+ *     px = bx + (cy*ox - sy*oy)         py = by + (sy*ox + cy*oy)
+ *     h  = the height GfTerrainHeightArgs documents, at (px, py)           (the same device function: the same bits)
+ *     v  = relative ? (bz - offset) - h : h
+ *     out = min(max(v, clip_lo), clip_hi)                                  (a NaN stays a NaN, as torch.clamp)
+ * c, s, nrm, cy, sy and bz - offset are computed once per env.  A 256-lane workgroup owns a tile of GF_HEIGHT_SCAN_TILE_ENVS envs: it
+ * stages the pattern and the tile's frames (bx, by, bz - offset, cy, sy) in LDS, then walks the tile's elements with consecutive
+ * lanes on consecutive p.  Stores are 16 bytes per lane where `out` is 16-byte aligned and either dense (out_stride == P: a
+ * tile's rows are one contiguous run) or made of whole quads (P and out_stride multiples of 4); one float per lane otherwise.
+ * The four taps are plain loads (the field is shared by every env and stays in L1 / L2).  No atomics, nothing between workgroups.
+ * Refusals, before anything is launched: GF_E_NULL — args, out, pos, pattern, quat with align = 1; GF_E_RANGE — num_envs < 0 (or
+ * more than 2^31 - 1 tiles), num_points outside 1 … GF_HEIGHT_SCAN_MAX_POINTS, pos_stride < 3, quat_stride < 4 (with a quat),
+ * out_stride < num_points, align / relative outside {0, 1}, clip_lo > clip_hi, a height field with rows < 1 or cols < 1.
+ * num_envs == 0 is a no-op.  Runs under GF_PHASE_TERRAIN for gf_profile_begin.  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_HEIGHT_SCAN_MAX_POINTS 1024
+#define GF_HEIGHT_SCAN_TILE_ENVS 16     /* envs per workgroup */
+
+typedef struct GfHeightScanArgs {
+    int64_t num_envs;
+    const float* pos;          /* row n at pos + n * pos_stride: x, y, z of the base */
+    const float* quat;         /* row n at quat + n * quat_stride: w, x, y, z; may be NULL with align = 0 */
+    const float* pattern;      /* [P, 2] body-frame offsets */
+    float* out;                /* row n at out + n * out_stride, P floats */
+    float* points_out;         /* optional [N, P, 2] dense: the world sample points (px, py); NULL: not written */
+    int64_t pos_stride;        /* in floats, >= 3 */
+    int64_t quat_stride;       /* in floats, >= 4 */
+    int64_t out_stride;        /* in floats, >= P */
+    GfTerrainView terrain;
+    int32_t num_points;        /* P: 1 … GF_HEIGHT_SCAN_MAX_POINTS */
+    int32_t align;             /* 0 = world axes, 1 = the base's yaw */
+    int32_t relative;          /* 0 = terrain height, 1 = (bz - offset) - terrain height */
+    float offset;
+    float clip_lo;             /* -inf … */
+    float clip_hi;             /* … +inf allowed */
+} GfHeightScanArgs;
+
+/* ------------------------------------------------------------------------------------------
  * Entry points.  `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream).
  * ---------------------------------------------------------------------------------------- */
 int gf_abi_version(void);
@@ -1518,6 +1561,8 @@ int gf_masked_reset(const GfResetArgs* a, void* stream);          /* replaces ma
 int gf_observe(const GfObservationArgs* a, void* stream);         /* replaces observation_manager.py:218-256 */
 int gf_entity_rotate(const GfRotateArgs* a, void* stream);        /* replaces entity_manager.py:130-146 */
 int gf_terrain_height(const GfTerrainHeightArgs* a, void* stream);/* replaces terrain_manager.py:100-166 */
+int gf_height_scan(const GfHeightScanArgs* a, void* stream);     /* the terrain height at P points around every base, yaw-aligned, in one launch (legged_gym measured_heights, Isaac Lab height_scan) */
+int gf_height_scan_sizeof(void);                                 /* sizeof(GfHeightScanArgs): the binding's self-check for this additive entry (gf_sizeof's table ends at 40) */
 int gf_synth_scene_step(const GfSynthSceneArgs* a, void* stream); /* stands in for scene.step() (managed_env.py:292) */
 int gf_rollout_write(const GfRolloutArgs* a, void* stream);       /* replaces the RolloutStorage copy_ launches of the RL library (examples/simple/train.py:125-129) */
 int gf_rollout_frame_write(const GfRolloutFrameArgs* a, void* stream);   /* the newest frame of up to four history observations into a frame-major rollout storage, one launch */

@@ -10,10 +10,11 @@ reference's operator interface.  ``install_as_genesis_forge()`` registers it und
 from .genesis_env import GenesisEnv, EnvMode
 from .managed_env import ManagedEnvironment
 from .managers.height_scanner import HeightScanner
+from .managers.ray_caster import RayCaster
 from .runner import DistillationRunner, OnPolicyRunner
 from .symmetry import MirrorSymmetry
 
-__all__ = ["GenesisEnv", "ManagedEnvironment", "EnvMode", "OnPolicyRunner", "DistillationRunner", "MirrorSymmetry", "HeightScanner", "install_as_genesis_forge"]
+__all__ = ["GenesisEnv", "ManagedEnvironment", "EnvMode", "OnPolicyRunner", "DistillationRunner", "MirrorSymmetry", "HeightScanner", "RayCaster", "install_as_genesis_forge"]
 __version__ = "0.1.0"
 
 

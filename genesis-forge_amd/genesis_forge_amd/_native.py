@@ -564,6 +564,19 @@ class GfHeightScanArgs(C.Structure):
                 ("align", C.c_int32), ("relative", C.c_int32), ("offset", C.c_float), ("clip_lo", C.c_float), ("clip_hi", C.c_float)]
 
 
+# the terrain ray cast (managers.RayCaster.cast): gf_ray_cast — additive like gf_height_scan, not in ABI_STRUCTS
+GF_RAY_CAST_MAX_RAYS = 2048
+GF_RAY_CAST_TILE_ENVS = 8
+GF_RAY_ALIGN_WORLD, GF_RAY_ALIGN_YAW, GF_RAY_ALIGN_BASE = 0, 1, 2
+GF_RAY_MODE_DISTANCE, GF_RAY_MODE_DEPTH = 0, 1
+
+
+class GfRayCastArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("pos", P), ("quat", P), ("pattern", P), ("out", P), ("hits_out", P), ("pos_stride", C.c_int64),
+                ("quat_stride", C.c_int64), ("out_stride", C.c_int64), ("terrain", GfTerrainView), ("num_rays", C.c_int32),
+                ("align", C.c_int32), ("mode", C.c_int32), ("axis", C.c_float * 3), ("max_range", C.c_float), ("miss_value", C.c_float)]
+
+
 # the newest frame of a history observation into a frame-major rollout storage (learner.RolloutStorage(history="frames")):
 # gf_rollout_frame_write, issued by the storage behind the step's rollout_write — not a phase, not in ABI_STRUCTS either
 GF_SIZEOF_ROLLOUT_FRAME = 30
@@ -823,6 +836,12 @@ class HipBackend(Backend):
             raise GfError(f"ABI drift: sizeof(GfHeightScanArgs) is {n} in the library, {C.sizeof(GfHeightScanArgs)} in the binding")
         self.lib.gf_height_scan.restype = C.c_int
         self.lib.gf_height_scan.argtypes = [C.POINTER(GfHeightScanArgs), C.c_void_p]
+        # the terrain ray cast (managers.RayCaster): additive in the same way
+        n = self.lib.gf_ray_cast_sizeof()
+        if n != C.sizeof(GfRayCastArgs):
+            raise GfError(f"ABI drift: sizeof(GfRayCastArgs) is {n} in the library, {C.sizeof(GfRayCastArgs)} in the binding")
+        self.lib.gf_ray_cast.restype = C.c_int
+        self.lib.gf_ray_cast.argtypes = [C.POINTER(GfRayCastArgs), C.c_void_p]
         n = self.lib.gf_sizeof(GF_SIZEOF_RNN_CELL)
         if n != C.sizeof(GfRnnCell):
             raise GfError(f"ABI drift: sizeof(GfRnnCell) is {n} in the library, {C.sizeof(GfRnnCell)} in the binding")
@@ -959,6 +978,13 @@ class HipBackend(Backend):
         rc = self.lib.gf_height_scan(C.byref(args), self._stream())
         if rc != 0:
             self._raise("height_scan", rc)
+
+    def ray_cast(self, args) -> None:
+        """gf_ray_cast on the current stream (managers.RayCaster.cast).  Only this backend has it: a backend without the method makes
+        the caster run the same float32 sequence as torch ops."""
+        rc = self.lib.gf_ray_cast(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("ray_cast", rc)
 
     def build_info(self) -> str:
         return self.lib.gf_build_info().decode()

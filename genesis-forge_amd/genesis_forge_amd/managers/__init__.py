@@ -7,6 +7,7 @@ from .gait_command import GaitCommandManager
 from .contact import ContactManager
 from .terrain_manager import TerrainManager
 from .height_scanner import HeightScanner
+from .ray_caster import RayCaster
 from .entity_manager import EntityManager
 from .observation_manager import ObservationManager
 from .config import MdpFnClass, ResetMdpFnClass
@@ -14,5 +15,5 @@ from .config import MdpFnClass, ResetMdpFnClass
 __all__ = [
     "BaseManager", "RewardManager", "TerminationManager", "CommandManager", "VelocityCommandManager", "GaitCommandManager",
     "BaseActionManager", "PositionActionManager", "PositionWithinLimitsActionManager", "ContactManager",
-    "TerrainManager", "HeightScanner", "EntityManager", "ObservationManager", "MdpFnClass", "ResetMdpFnClass",
+    "TerrainManager", "HeightScanner", "RayCaster", "EntityManager", "ObservationManager", "MdpFnClass", "ResetMdpFnClass",
 ]

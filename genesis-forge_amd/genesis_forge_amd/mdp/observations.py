@@ -86,3 +86,10 @@ def height_scan(env, scanner) -> torch.Tensor:
     ``gf_height_scan`` launch into the scanner's persistent buffer).  Untagged: ObservationManager evaluates it as an EXTERNAL item
     each step and applies the item's ``scale`` / ``noise`` like any other; the reference has no counterpart."""
     return scanner.scan()
+
+
+def ray_cast(env, caster) -> torch.Tensor:
+    """The distances (or depths) of a sensor's rays against the terrain, shape (num_envs, caster.num_rays): ``caster.cast()``
+    (managers/ray_caster.py — one ``gf_ray_cast`` launch into the caster's persistent buffer).  Untagged like ``height_scan``: an
+    EXTERNAL item, evaluated each step, with the item's ``scale`` / ``noise`` applied like any other."""
+    return caster.cast()

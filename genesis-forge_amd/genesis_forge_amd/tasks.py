@@ -425,15 +425,23 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
     ``height_scan`` (a dict of ``HeightScanner`` keyword arguments; ``{}`` is the default 17 x 11 grid) adds ``self.height_scanner``
     and a second ObservationManager, ``"critic"``: the policy's items plus the terrain heights around the base — the privileged input of
     an asymmetric critic (``RolloutStorage(env, T, obs_groups={"policy": ["policy"], "critic": ["critic"]})``) or of a teacher.
-    ``None`` (the default) builds what the reference's example builds: a blind policy."""
+    ``None`` (the default) builds what the reference's example builds: a blind policy.
+    ``depth_camera`` (a dict of ``RayCaster`` keyword arguments; ``{}`` is a 16 x 12 pinhole at 87 degrees horizontal, mounted at the
+    front of the trunk and pitched 30 degrees down, 4 m range, depth output) adds ``self.depth_camera`` and an ObservationManager
+    ``"depth"`` that holds that one item: what a deployable student sees
+    (``obs_groups={"policy": ["policy", "depth"], "teacher": ["critic"]}``).  ``None`` builds the managers above and nothing else."""
+
+    #: the default sensor of ``depth_camera={}``
+    DEPTH_CAMERA = dict(offset_pos=(0.3, 0.0, 0.05), offset_euler=(0.0, 30.0, 0.0), align="base", max_range=4.0, output="depth")
 
     def __init__(self, num_envs=1, dt=1 / 50, max_episode_length_s=20, scene_kwargs=None, height_reward=True, rotation="default",
-                 terrain_kwargs=None, cmd_resample_s=5.0, height_scan=None):
+                 terrain_kwargs=None, cmd_resample_s=5.0, height_scan=None, depth_camera=None):
         super().__init__(num_envs=num_envs, dt=dt, max_episode_length_sec=max_episode_length_s, max_episode_random_scaling=0.1)
         kw = dict(scene_kwargs or {})
         kw.setdefault("max_collision_pairs", 12)
         self._height_reward, self._rotation, self._cmd_resample_s = height_reward, rotation, cmd_resample_s
         self._height_scan = None if height_scan is None else dict(height_scan)
+        self._depth_camera = None if depth_camera is None else dict(depth_camera)
         self.scene = new_scene(dt=self.dt, substeps=2, **kw)
         tk = dict(pos=(-12, -12, 0), n_subterrains=(1, 1), subterrain_size=(24, 24), vertical_scale=0.001,
                   subterrain_types=[["random_uniform_terrain"]],
@@ -499,6 +507,16 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
             self.height_scanner = HeightScanner(self, self.terrain_manager, entity_manager=self.robot_manager, **self._height_scan)
             self.critic_manager = ObservationManager(self, name="critic", cfg=dict(
                 policy_items(), height_scan={"fn": observations.height_scan, "params": {"scanner": self.height_scanner}}))
+        if self._depth_camera is not None:
+            from genesis_forge_amd.managers import RayCaster
+            from genesis_forge_amd.managers.ray_caster import pinhole_pattern
+
+            kw = dict(self.DEPTH_CAMERA, **self._depth_camera)
+            if kw.get("pattern") is None:
+                kw["pattern"] = pinhole_pattern(16, 12, 87.0)
+            self.depth_camera = RayCaster(self, self.terrain_manager, entity_manager=self.robot_manager, **kw)
+            self.depth_manager = ObservationManager(self, name="depth", cfg={
+                "depth": {"fn": observations.ray_cast, "params": {"caster": self.depth_camera}}})
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

@@ -1525,6 +1525,85 @@ typedef struct GfHeightScanArgs {
 } GfHeightScanArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * Terrain ray cast (managers/ray_caster.py; Isaac Lab's RayCaster and its camera, the depth images of the parkour papers): R rays
+ * per env against the terrain surface, in one launch.  `pattern` is [R, 6], shared by every env: a body-frame start offset p and a
+ * UNIT direction e per ray (the host normalises in f64 and rounds once; the kernel never normalises).
+ *
+ * Surface.  Inside the field's rectangle [x_min, x_min + x_span] x [y_min, y_min + y_span] it is S(x, y), the bilinear interpolant
+ * of the cell's four corners at grid coordinates gx = (x - x_min) * sx, gy = (y - y_min) * sy with sx = (float)(cols - 1) / x_span,
+ * sy = (float)(rows - 1) / y_span.  Outside the rectangle there is no surface: a ray passes (the border clamp of the height
+ * sampler is NOT extended).  height_field == NULL: the plane z = origin_z everywhere.
+ * Result.  t* = the smallest t in [0, max_range] whose point lies in the rectangle with oz + t*dz <= S; none: the ray misses.
+ * out[n, r] = t* (mode 0, distance) or t* * ((ex*ax + ey*ay) + ez*az) (mode 1, depth along the body-frame optical axis `axis`);
+ * a miss writes miss_value (any float).  hits_out[n, r] = o + te*d with te = t* for a hit, max_range for a miss.
+ *
+ * In f32, one rounding per operation (never fused), `x ? a : b` selects written out so that a NaN takes the same side everywhere:
+ *   frame, once per env —
+ *     align 2 (base): the rotation matrix of the quaternion as given (not normalised)
+ *       r00 = 1 - 2*(qy*qy + qz*qz)   r01 = 2*(qx*qy - qw*qz)        r02 = 2*(qx*qz + qw*qy)
+ *       r10 = 2*(qw*qz + qx*qy)       r11 = 1 - 2*(qx*qx + qz*qz)    r12 = 2*(qy*qz - qw*qx)
+ *       r20 = 2*(qx*qz - qw*qy)       r21 = 2*(qy*qz + qw*qx)        r22 = 1 - 2*(qx*qx + qy*qy)
+ *     align 1 (yaw): (cy, sy) exactly as the height scan computes them (c = r00, s = r10 above); rows (cy, -sy, 0), (sy, cy, 0), (0, 0, 1)
+ *     align 0 (world): the identity; `quat` is never read
+ *   ray —
+ *     ox = bx + ((r00*px + r01*py) + r02*pz)   (oy, oz with rows 1, 2)      dx = (r00*ex + r01*ey) + r02*ez   (dy, dz likewise)
+ *   plane (no height field) —
+ *     C = oz - origin_z;  C <= 0: hit, t* = 0;  else dz < 0 and tt = C / (-dz) <= max_range: hit, t* = tt;  else miss
+ *   field —
+ *     gx0 = (ox - x_min)*sx   du = dx*sx   idu = 1/du        (y: gy0, dv, idv with y_min, sy)       fw = (float)(cols-1), fh likewise
+ *     slab: t0 = 0, t1 = max_range; per axis, if du != 0: ta = (-gx0)*idu, tb = (fw - gx0)*idu, lo = ta < tb ? ta : tb,
+ *       hi = ta < tb ? tb : ta, if (lo > t0) t0 = lo, if (hi < t1) t1 = hi; if du == 0 the ray needs 0 <= gx0 <= fw.  Miss unless t0 <= t1.
+ *     entry: tin = t0; gin = gx0 + tin*du; ix = (int)floor(gin), minus 1 if du < 0 and gin == floor(gin) (a start on a grid line
+ *       heading in the negative direction belongs to the cell behind the line); ix clamped to 0 … cols-2.  iy likewise.
+ *     walk, at most (cols-1) + (rows-1) + 1 cells:
+ *       tnx = du != 0 ? ((float)(ix + (du > 0)) - gx0)*idu : +inf        tny likewise        tn = tnx < tny ? tnx : tny
+ *       tout = tn < t1 ? tn : t1;  tout = tout > tin ? tout : tin;  smax = tout - tin
+ *       u0 = (gx0 + tin*du) - (float)ix, clamped to [0, 1] (< 0 first, then > 1)       v0 likewise       zin = oz + tin*dz
+ *       h00 = f[iy][ix]  h10 = f[iy][ix+1]  h01 = f[iy+1][ix]  h11 = f[iy+1][ix+1]
+ *       a = h10 - h00    b = h01 - h00    k = (h00 - h10) - (h01 - h11)
+ *       C = zin - (((h00 + a*u0) + b*v0) + (k*u0)*v0)
+ *       B = dz - ((a*du + b*dv) + k*(u0*dv + v0*du))
+ *       A = -((k*du)*dv)                                   (the gap along the ray inside the cell is C + B*s + A*s*s, s = t - tin)
+ *       C <= 0: hit at t* = tin (an origin under the surface gives 0).  Otherwise s = +inf and
+ *         A == 0: if B < 0, s = C / (-B)
+ *         A != 0: disc = B*B - (4*A)*C; if disc >= 0: sq = sqrt(disc), q = -0.5*(B + (B < 0 ? -sq : sq)), r1 = q / A, r2 = C / q,
+ *                 if (r1 >= 0 && r1 < s) s = r1, if (r2 >= 0 && r2 < s) s = r2           (the cancellation-free pair of roots)
+ *       s <= smax: hit at t* = tin + s.  Otherwise, unless tn < t1, the ray ended: miss.  Else step: if (tnx <= tn) ix += sign(du),
+ *       if (tny <= tn) iy += sign(dv) (a tie steps both; one index always steps, also when rounding put tn at or before tin); an
+ *       index outside 0 … cols-2 / 0 … rows-2: miss; tin = tout.
+ * A 256-lane workgroup owns a tile of GF_RAY_CAST_TILE_ENVS envs: the frames (origin and nine matrix entries) and the pattern are
+ * staged in LDS, consecutive lanes take consecutive rays, stores are 16 bytes wide under the height scan's rule (out 16-byte aligned
+ * and dense, or num_rays and out_stride multiples of 4).  The taps are plain loads.  No atomics, nothing between workgroups.
+ * Refusals, before anything is launched: GF_E_NULL — args, out, pos, pattern, quat with align != 0; GF_E_RANGE — num_envs < 0 (or
+ * more than 2^31 - 1 tiles), num_rays outside 1 … GF_RAY_CAST_MAX_RAYS, pos_stride < 3, quat_stride < 4 (with a quat),
+ * out_stride < num_rays, align outside {0, 1, 2}, mode outside {0, 1}, max_range negative or not finite, a height field with
+ * rows < 2 or cols < 2.  num_envs == 0 is a no-op.  Runs under GF_PHASE_TERRAIN for gf_profile_begin.  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_RAY_CAST_MAX_RAYS 2048       /* a 64 x 32 image */
+#define GF_RAY_CAST_TILE_ENVS 8         /* envs per workgroup */
+enum { GF_RAY_ALIGN_WORLD = 0, GF_RAY_ALIGN_YAW = 1, GF_RAY_ALIGN_BASE = 2 };
+enum { GF_RAY_MODE_DISTANCE = 0, GF_RAY_MODE_DEPTH = 1 };
+
+typedef struct GfRayCastArgs {
+    int64_t num_envs;
+    const float* pos;          /* row n at pos + n * pos_stride: x, y, z of the base */
+    const float* quat;         /* row n at quat + n * quat_stride: w, x, y, z; may be NULL with align = 0 */
+    const float* pattern;      /* [R, 6]: px, py, pz, ex, ey, ez */
+    float* out;                /* row n at out + n * out_stride, R floats */
+    float* hits_out;           /* optional [N, R, 3] dense: the world hit points; NULL: not written */
+    int64_t pos_stride;        /* in floats, >= 3 */
+    int64_t quat_stride;       /* in floats, >= 4 */
+    int64_t out_stride;        /* in floats, >= R */
+    GfTerrainView terrain;
+    int32_t num_rays;          /* R: 1 … GF_RAY_CAST_MAX_RAYS */
+    int32_t align;             /* GF_RAY_ALIGN_* */
+    int32_t mode;              /* GF_RAY_MODE_* */
+    float axis[3];             /* the optical axis in the body frame (mode 1) */
+    float max_range;           /* finite, >= 0 */
+    float miss_value;
+} GfRayCastArgs;
+
+/* ------------------------------------------------------------------------------------------
  * Entry points.  `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream).
  * ---------------------------------------------------------------------------------------- */
 int gf_abi_version(void);
@@ -1563,6 +1642,8 @@ int gf_entity_rotate(const GfRotateArgs* a, void* stream);        /* replaces en
 int gf_terrain_height(const GfTerrainHeightArgs* a, void* stream);/* replaces terrain_manager.py:100-166 */
 int gf_height_scan(const GfHeightScanArgs* a, void* stream);     /* the terrain height at P points around every base, yaw-aligned, in one launch (legged_gym measured_heights, Isaac Lab height_scan) */
 int gf_height_scan_sizeof(void);                                 /* sizeof(GfHeightScanArgs): the binding's self-check for this additive entry (gf_sizeof's table ends at 40) */
+int gf_ray_cast(const GfRayCastArgs* a, void* stream);           /* R rays per env against the terrain surface, exact cell walk, in one launch (Isaac Lab RayCaster / depth camera) */
+int gf_ray_cast_sizeof(void);                                    /* sizeof(GfRayCastArgs): the binding's self-check for this additive entry */
 int gf_synth_scene_step(const GfSynthSceneArgs* a, void* stream); /* stands in for scene.step() (managed_env.py:292) */
 int gf_rollout_write(const GfRolloutArgs* a, void* stream);       /* replaces the RolloutStorage copy_ launches of the RL library (examples/simple/train.py:125-129) */
 int gf_rollout_frame_write(const GfRolloutFrameArgs* a, void* stream);   /* the newest frame of up to four history observations into a frame-major rollout storage, one launch */

@@ -333,6 +333,9 @@ int reset_prep(const GfResetArgs* a) {
     if (a->env_actions && !a->env_last_actions) return GF_E_NULL;
     if (a->scene_dof_pos && !a->default_dof_pos) return GF_E_NULL;
     if (a->spawn_mode && a->terrain.height_field && (a->terrain.rows < 1 || a->terrain.cols < 1)) return GF_E_RANGE;
+    // reset_body moves a quaternion as one float4
+    if (a->scene_quat && (reinterpret_cast<uintptr_t>(a->scene_quat) & 15u)) return GF_E_UNSUPPORTED;
+    if (a->scene_quat && a->quat_stash && (reinterpret_cast<uintptr_t>(a->quat_stash) & 15u)) return GF_E_UNSUPPORTED;
     return GF_OK;
 }
 }  // namespace gf

@@ -402,8 +402,9 @@ typedef struct GfResetArgs {
     float dof_noise_scale;
     const float* dof_draws;     /* [N,D] U[0,1) or NULL → Philox (only read when noise_scale != 0) */
     float* scene_pos;           /* [N,3] ← reset_pos    (mdp.reset.position) */
-    float* scene_quat;          /* [N,4] ← reset_quat   */
-    float* quat_stash;          /* [N,4] optional: receives the pre-reset quat of every reset env (see GfObservationArgs.stale_quat) */
+    float* scene_quat;          /* [N,4] ← reset_quat; 16-byte aligned (a row moves as one unit), else GF_E_UNSUPPORTED */
+    float* quat_stash;          /* [N,4] optional: receives the pre-reset quat of every reset env (see GfObservationArgs.stale_quat);
+                                   16-byte aligned when scene_quat is set, else GF_E_UNSUPPORTED */
     float* scene_lin_vel;       /* [N,3] ← 0 when zero_velocity */
     float* scene_ang_vel;       /* [N,3] ← 0 when zero_velocity */
     float reset_pos[3];

@@ -727,6 +727,7 @@ GFO_EXPORT int gfo_gait_step(const GfGaitArgs* a) {
     if (a->num_gaits < 1 || a->num_gaits > GF_MAX_GAITS) return GF_E_RANGE;
     if (a->mode == GF_CMD_STEP && (a->resample_steps <= 0 || !a->episode_length)) return a->episode_length ? GF_E_RANGE : GF_E_NULL;
     if (a->mode == GF_CMD_MASKED && !a->mask) return GF_E_NULL;
+    if ((uintptr_t)a->state & 15u) return GF_E_UNSUPPORTED; /* the library moves a row as four 16-byte units */
     const int64_t N = a->num_envs;
     for (int64_t n = 0; n < N; ++n) {
         float* r = a->state + n * GF_GAIT_ROW;
@@ -782,6 +783,9 @@ GFO_EXPORT int gfo_masked_reset(const GfResetArgs* a) {
     if (a->num_contact < 0 || a->num_contact > GF_MAX_CONTACT_VIEWS) return GF_E_RANGE;
     if (a->env_actions && !a->env_last_actions) return GF_E_NULL;
     if (a->scene_dof_pos && !a->default_dof_pos) return GF_E_NULL;
+    /* the library reads and writes a quaternion as one 16-byte unit */
+    if (a->scene_quat && ((uintptr_t)a->scene_quat & 15u)) return GF_E_UNSUPPORTED;
+    if (a->scene_quat && a->quat_stash && ((uintptr_t)a->quat_stash & 15u)) return GF_E_UNSUPPORTED;
     int count = 0;
     for (int64_t n = 0; n < N; ++n) {
         if (!(a->mask[n] || (a->mask2 && a->mask2[n]))) continue;

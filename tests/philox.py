@@ -42,6 +42,29 @@ def uniform(seed: int, stream: int, n_env: int, n_col: int) -> np.ndarray:
     return np.ascontiguousarray(out[:, :n_col])
 
 
+def block_uniform(seed: int, stream: int, env_ids, block: int) -> np.ndarray:
+    """[len(env_ids), 4] float32 U[0,1): the four words of the block with counter (env id, block, stream), for the GLOBAL env ids
+    given (uint32; the caller adds its shard's ``env_offset`` and wraps modulo 2^32)."""
+    env = np.asarray(env_ids, dtype=np.uint32).reshape(-1)
+    x = philox4x32_10(env, np.uint32(block), np.uint32(stream & 0xFFFFFFFF), np.uint32((stream >> 32) & 0xFFFFFFFF),
+                      seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    w = np.stack(x, axis=1)
+    return (w >> np.uint32(8)).astype(np.float32) * np.float32(5.9604644775390625e-8)
+
+
+def uniform_ids(seed: int, stream: int, env_ids, n_col: int, first_col: int = 0) -> np.ndarray:
+    """[len(env_ids), n_col] float32 U[0,1): element (k, c) == philox_uniform(seed, stream, env_ids[k], first_col + c) of the C/HIP
+    code.  ``uniform(seed, stream, n, c)`` is ``uniform_ids(seed, stream, arange(n), c)``."""
+    env = np.asarray(env_ids, dtype=np.uint32).reshape(-1)
+    cols = np.arange(first_col, first_col + n_col)
+    out = np.empty((env.size, n_col), dtype=np.float32)
+    for blk in np.unique(cols >> 2):
+        u = block_uniform(seed, stream, env, int(blk))
+        sel = (cols >> 2) == blk
+        out[:, sel] = u[:, cols[sel] & 3]
+    return out
+
+
 def draws(seed: int, step: int, kind: int, n_env: int, n_col: int) -> np.ndarray:
     """Parity-mode draws for (step, kind): kind 0 = command.step, 1 = command.reset, 2 = episode length, 3 = observation noise."""
     return uniform(seed, (int(kind) << 40) | int(step), n_env, n_col)

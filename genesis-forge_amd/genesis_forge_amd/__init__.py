@@ -11,10 +11,11 @@ from .genesis_env import GenesisEnv, EnvMode
 from .managed_env import ManagedEnvironment
 from .managers.height_scanner import HeightScanner
 from .managers.ray_caster import RayCaster
+from .managers.terrain_curriculum import TerrainCurriculum
 from .runner import DistillationRunner, OnPolicyRunner
 from .symmetry import MirrorSymmetry
 
-__all__ = ["GenesisEnv", "ManagedEnvironment", "EnvMode", "OnPolicyRunner", "DistillationRunner", "MirrorSymmetry", "HeightScanner", "RayCaster", "install_as_genesis_forge"]
+__all__ = ["GenesisEnv", "ManagedEnvironment", "EnvMode", "OnPolicyRunner", "DistillationRunner", "MirrorSymmetry", "HeightScanner", "RayCaster", "TerrainCurriculum", "install_as_genesis_forge"]
 __version__ = "0.1.0"
 
 

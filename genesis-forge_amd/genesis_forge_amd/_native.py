@@ -577,6 +577,21 @@ class GfRayCastArgs(C.Structure):
                 ("align", C.c_int32), ("mode", C.c_int32), ("axis", C.c_float * 3), ("max_range", C.c_float), ("miss_value", C.c_float)]
 
 
+# the terrain curriculum (managers.TerrainCurriculum.respawn): gf_terrain_curriculum — additive like gf_height_scan, not in ABI_STRUCTS
+GF_TERRAIN_CURRICULUM_BLOCK_ENVS = 256
+
+
+class GfTerrainCurriculumArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("mask", P), ("mask2", P), ("pos_in", P), ("pos_out", P), ("quat_out", P), ("quat_stash", P),
+                ("lin_vel", P), ("ang_vel", P), ("dof_vel", P), ("spawn_xy", P), ("level", P), ("type", P), ("speed_ref", P), ("counts", P),
+                ("draws", P), ("command", GfCommandView), ("seed", C.c_uint64), ("stream", C.c_uint64), ("env_offset", C.c_uint32),
+                ("num_dofs", C.c_int32), ("num_levels", C.c_int32), ("num_types", C.c_int32), ("level_axis", C.c_int32), ("update", C.c_int32),
+                ("set_quat", C.c_int32), ("zero_velocity", C.c_int32), ("spawn_rot_mask", C.c_int32), ("promote_distance", C.c_float),
+                ("demote_time", C.c_float), ("demote_distance", C.c_float), ("spawn_x_min", C.c_float), ("spawn_x_span", C.c_float),
+                ("spawn_y_min", C.c_float), ("spawn_y_span", C.c_float), ("cell_dx", C.c_float), ("cell_dy", C.c_float),
+                ("height_offset", C.c_float), ("spawn_rot_lo", C.c_float * 3), ("spawn_rot_hi", C.c_float * 3), ("terrain", GfTerrainView)]
+
+
 # the newest frame of a history observation into a frame-major rollout storage (learner.RolloutStorage(history="frames")):
 # gf_rollout_frame_write, issued by the storage behind the step's rollout_write — not a phase, not in ABI_STRUCTS either
 GF_SIZEOF_ROLLOUT_FRAME = 30
@@ -842,6 +857,12 @@ class HipBackend(Backend):
             raise GfError(f"ABI drift: sizeof(GfRayCastArgs) is {n} in the library, {C.sizeof(GfRayCastArgs)} in the binding")
         self.lib.gf_ray_cast.restype = C.c_int
         self.lib.gf_ray_cast.argtypes = [C.POINTER(GfRayCastArgs), C.c_void_p]
+        # the terrain curriculum (managers.TerrainCurriculum): additive in the same way
+        n = self.lib.gf_terrain_curriculum_sizeof()
+        if n != C.sizeof(GfTerrainCurriculumArgs):
+            raise GfError(f"ABI drift: sizeof(GfTerrainCurriculumArgs) is {n} in the library, {C.sizeof(GfTerrainCurriculumArgs)} in the binding")
+        self.lib.gf_terrain_curriculum.restype = C.c_int
+        self.lib.gf_terrain_curriculum.argtypes = [C.POINTER(GfTerrainCurriculumArgs), C.c_void_p]
         n = self.lib.gf_sizeof(GF_SIZEOF_RNN_CELL)
         if n != C.sizeof(GfRnnCell):
             raise GfError(f"ABI drift: sizeof(GfRnnCell) is {n} in the library, {C.sizeof(GfRnnCell)} in the binding")
@@ -985,6 +1006,13 @@ class HipBackend(Backend):
         rc = self.lib.gf_ray_cast(C.byref(args), self._stream())
         if rc != 0:
             self._raise("ray_cast", rc)
+
+    def terrain_curriculum(self, args) -> None:
+        """gf_terrain_curriculum on the current stream (managers.TerrainCurriculum.respawn).  Only this backend has it: a backend
+        without the method makes the curriculum run the same float32 sequence as torch ops."""
+        rc = self.lib.gf_terrain_curriculum(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("terrain_curriculum", rc)
 
     def build_info(self) -> str:
         return self.lib.gf_build_info().decode()

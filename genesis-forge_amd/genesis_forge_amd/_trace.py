@@ -488,7 +488,7 @@ class StepTrace:
         ``resample_command``) is walked phase by phase — and the observation descriptors must be ones a recording may freeze."""
         env = self.env
         _, indexed = env._reset_partition()
-        if indexed:
+        if indexed or env._reset_masked_list():   # (a mask-driven launch of a manager's own does not go through backend.call either)
             return False
         if any(not om._traceable() for om in env.managers["observation"]):
             return False
@@ -892,7 +892,8 @@ def traceable(env, tail_python: bool = False) -> bool:
         if id(om) not in user_obs and not om._traceable():
             return False
     for em in env.managers["entity"]:
-        if not em.enabled or not em._can_fuse_reset():
+        # (its reset a section of the masked reset, or a mask-driven launch of its own behind it: ManagedEnvironment._reset_masked_list)
+        if not em.enabled or not (em._can_fuse_reset() or em._mask_only_reset()):
             return False
     if not am._can_fuse_reset():
         return False

@@ -429,7 +429,7 @@ class ManagedEnvironment(GenesisEnv):
         hit = self._partition_cache
         if hit is not None and hit[0] == self._trace_epoch:
             return hit[1], hit[2]
-        fused, indexed = [], []
+        fused, indexed, masked = [], [], []
         for m in self._all_managers():
             if not _most_derived_reset_is_ours(m):
                 indexed.append(m)
@@ -437,13 +437,27 @@ class ManagedEnvironment(GenesisEnv):
                 fused.append(m)
             elif type(m).reset is BaseManager.reset:
                 pass  # no-op reset (termination / observation managers)
+            elif getattr(m, "_mask_only_reset", lambda: False)():
+                masked.append(m)  # a launch of its own driven by the masks (EntityManager._masked_reset): see _reset_masked_list
             else:
                 indexed.append(m)
-        self._partition_cache = (self._trace_epoch, fused, indexed)
+        self._partition_cache = (self._trace_epoch, fused, indexed, masked)
         return fused, indexed
+
+    def _reset_masked_list(self) -> list:
+        """The third part of the partition: managers whose reset is neither a section of gf_masked_reset nor in need of an index list —
+        a mask-driven launch of their own behind the fused one (an EntityManager whose only on_reset entry is
+        ``mdp.reset.terrain_curriculum_position``)."""
+        self._reset_partition()
+        return self._partition_cache[3]
+
+    def _masked_resets(self, masked: list, mask: torch.Tensor, mask2: Optional[torch.Tensor], update: bool, replayed: bool = False) -> None:
+        for m in masked:
+            m._masked_reset(mask, mask2, update, replayed)
 
     def _reset_with_mask(self, mask: torch.Tensor, mask2: Optional[torch.Tensor], ids) -> None:
         fused, indexed = self._reset_partition()
+        masked = self._reset_masked_list()   # (taken now: a setter check during the push below drops the partition cache)
         a = self._reset_args  # persistent descriptor: a recorded step replays it in place
         C.memset(C.byref(a), 0, C.sizeof(a))
         ad = self._adapter
@@ -465,6 +479,20 @@ class ManagedEnvironment(GenesisEnv):
                 ad.push_done(mask, mask2)
             elif not isinstance(ids, torch.Tensor) or ids.numel() > 0:
                 ad.push(torch.as_tensor(ids, device=gs.device, dtype=torch.long))
+        if masked:
+            # behind the fused launch and the fused managers' own masked launches (the command has been resampled: the terrain
+            # curriculum records the command the new episode starts with), in front of the managers that need an index list.
+            # Levels move only in the in-step reset of finished episodes
+            rec = self.backend.tracer
+            if ids is None and rec is not None and rec.part is None and not rec.tail_python:
+                # while the step is being recorded: a Python piece between native phases (as _indexed_reset below) — it makes its own
+                # launch with this step's masks and takes its Philox stream from the env's counter, in the replayed step as here
+                from .managers._program import call_untraced
+                update = self._in_step   # (frozen into the recorded piece: a replayed step does not set the flag, and only in-step resets are recorded)
+                rec.python(lambda self=self, masked=list(masked), mask=mask, mask2=mask2, update=update: self._masked_resets(masked, mask, mask2, update, replayed=True))
+                call_untraced(self, lambda: self._masked_resets(masked, mask, mask2, update))
+            else:
+                self._masked_resets(masked, mask, mask2, self._in_step)
         if indexed:
             rec = self.backend.tracer
             if ids is None and rec is not None and rec.part is None and not rec.tail_python:

@@ -8,6 +8,7 @@ from .contact import ContactManager
 from .terrain_manager import TerrainManager
 from .height_scanner import HeightScanner
 from .ray_caster import RayCaster
+from .terrain_curriculum import TerrainCurriculum
 from .entity_manager import EntityManager
 from .observation_manager import ObservationManager
 from .config import MdpFnClass, ResetMdpFnClass
@@ -15,5 +16,5 @@ from .config import MdpFnClass, ResetMdpFnClass
 __all__ = [
     "BaseManager", "RewardManager", "TerminationManager", "CommandManager", "VelocityCommandManager", "GaitCommandManager",
     "BaseActionManager", "PositionActionManager", "PositionWithinLimitsActionManager", "ContactManager",
-    "TerrainManager", "HeightScanner", "RayCaster", "EntityManager", "ObservationManager", "MdpFnClass", "ResetMdpFnClass",
+    "TerrainManager", "HeightScanner", "RayCaster", "TerrainCurriculum", "EntityManager", "ObservationManager", "MdpFnClass", "ResetMdpFnClass",
 ]

@@ -151,6 +151,32 @@ class EntityManager(BaseManager):
                 self._stash_always = True  # a recorded step replays the same descriptor (quat_stash stays set)
             self._stash_armed = False
 
+    # -- mask-driven reset behind the fused launch ---------------------------------------------------------------
+    def _mask_only_reset(self) -> bool:
+        """True when the only on_reset entry is ``mdp.reset.terrain_curriculum_position`` on an entity with masked setters: the reset
+        is not a section of the masked reset, but it needs no index list either — one launch of its own, driven by the step's masks
+        (``ManagedEnvironment._reset_with_mask`` calls ``_masked_reset`` behind the fused launch)."""
+        if not hasattr(self.entity, "gf_masked_base"):
+            return False
+        from ..mdp import reset as reset_mdp
+        items = list(self.on_reset.values())
+        return len(items) == 1 and isinstance(items[0].fn, reset_mdp.terrain_curriculum_position)
+
+    def _masked_reset(self, mask, mask2, update: bool, replayed: bool = False) -> None:
+        """The reset of a ``_mask_only_reset`` manager for the envs flagged in ``mask`` / ``mask2``.  ``replayed``: called from a
+        recorded step, where the views cache has already been invalidated for this reset (``_after_masked_reset_traced``); in the
+        ordinary step that happens behind this call."""
+        if not self.enabled:
+            return
+        (cfg,) = self.on_reset.values()
+        ent = self.entity
+        pos, quat, lin, ang = ent.gf_masked_base()
+        dof_vel = ent.gf_masked_dofs(None)[1] if hasattr(ent, "gf_masked_dofs") else None
+        if cfg.fn.respawn(mask, mask2, update, pos, pos, quat, self._stash, lin, ang, dof_vel, **cfg.params):
+            # the stale-orientation rule of the fused spawn (see stale()): this tick's observations rotate by the stashed quaternions
+            self._stale_masks = (mask, mask2)
+            self._stale_tick = self.env._tick + (0 if replayed else 1)
+
     def _masked_base(self, cfg):
         """The base-state tensors the masked reset writes.  Synthetic scene: the scene's own buffers.  Genesis-shaped scene: this
         tick's snapshot, plus the write-back of the reset rows through ``set_pos`` / ``set_quat`` by index list, in the order

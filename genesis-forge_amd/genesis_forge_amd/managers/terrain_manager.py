@@ -37,6 +37,7 @@ class TerrainManager(BaseManager):
         self._size = (0.0, 0.0)
         self._subterrain_size = None
         self._subterrain_bounds: dict[str, tuple] = {}
+        self._grid: Optional[tuple] = None                             # (nx, ny) of a terrain made of sub-terrains
         self._height_field: torch.Tensor | None = None                 # [H (y), W (x)] metres
         self._explicit_bounds = bounds is not None
         N = env.num_envs
@@ -80,6 +81,7 @@ class TerrainManager(BaseManager):
             self._bounds = bounds
         if n_sub is not None:
             self._subterrain_size = tuple(morph.subterrain_size)
+            self._grid = (int(n_sub[0]), int(n_sub[1]))
             self._subterrain_bounds = {}
             for ix in range(n_sub[0]):
                 for iy in range(n_sub[1]):
@@ -138,6 +140,27 @@ class TerrainManager(BaseManager):
             bounds = self._subterrain_bounds[subterrain]
         (x_origin, _x_max, y_origin, _y_max) = bounds
         (x_size, y_size) = size
+        buffer_x = (x_size - x_size * usable_ratio) / 2
+        buffer_y = (y_size - y_size * usable_ratio) / 2
+        return (x_origin + buffer_x, x_origin + x_size - buffer_x, y_origin + buffer_y, y_origin + y_size - buffer_y)
+
+    def subterrain_grid(self) -> Optional[tuple]:
+        """``(nx, ny, size_x, size_y)`` of a terrain made of sub-terrains, ``None`` for any other terrain."""
+        if self._grid is None or self._subterrain_size is None:
+            return None
+        return (self._grid[0], self._grid[1], float(self._subterrain_size[0]), float(self._subterrain_size[1]))
+
+    def cell_usable_area(self, ix: int, iy: int, usable_ratio: float = 0.5) -> tuple[float, float, float, float]:
+        """:meth:`usable_area` of the sub-terrain at grid index ``(ix, iy)`` — by index, so a grid whose rows repeat a type name (which
+        ``_subterrain_bounds`` folds into one entry) addresses every cell.  Same double arithmetic, in the same order."""
+        grid = self.subterrain_grid()
+        if grid is None:
+            raise ValueError("the terrain has no sub-terrain grid")
+        nx, ny, x_size, y_size = grid
+        if not (0 <= int(ix) < nx and 0 <= int(iy) < ny):
+            raise ValueError(f"cell ({ix}, {iy}) is outside the {nx} x {ny} grid")
+        x_origin = self._origin[0] + int(ix) * self._subterrain_size[0]
+        y_origin = self._origin[1] + int(iy) * self._subterrain_size[1]
         buffer_x = (x_size - x_size * usable_ratio) / 2
         buffer_y = (y_size - y_size * usable_ratio) / 2
         return (x_origin + buffer_x, x_origin + x_size - buffer_x, y_origin + buffer_y, y_origin + y_size - buffer_y)

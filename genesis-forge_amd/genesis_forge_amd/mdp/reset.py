@@ -111,6 +111,83 @@ class randomize_terrain_position(ResetMdpFnClass):
             entity.set_quat(self._quat_buffer[envs_idx], envs_idx=envs_idx, zero_velocity=zero_velocity)
 
 
+class terrain_curriculum_position(ResetMdpFnClass):
+    """Respawn in the env's own terrain cell, moving terrain levels first when the reset ends an episode
+    (``managers.TerrainCurriculum``; legged_gym's ``_update_terrain_curriculum``, Isaac Lab's ``terrain_levels_vel``).
+    ``params = {"curriculum": TerrainCurriculum, "height_offset": float, "rotation": {"z": (lo, hi), …} | None, "zero_velocity": bool}``
+    with ``randomize_terrain_position``'s meaning of the last three.
+
+    Whichever way it is reached it is ONE ``gf_terrain_curriculum`` launch driven by a mask.  Levels move (``update``) only in the
+    in-step reset of finished episodes (``env._in_step``): the first ``reset()`` and resets a training script calls between steps
+    respawn the envs in the cell they have.
+
+    * In the step of an env whose EntityManager has this function as its only ``on_reset`` entry, on an entity with masked setters, the
+      manager is called with the step's termination masks (``EntityManager._masked_reset``): no index list, no host read, and the
+      step stays a recorded one.  Observations of the reset tick rotate by the pre-reset quaternion, as after the fused spawn.
+    * Called with an index list — the public signature — the list becomes a mask (``env._ids_to_mask``).  On an entity with masked
+      setters the launch writes the scene's buffers; otherwise it writes staging rows that reach the simulator through ``set_pos`` /
+      ``set_quat`` by index list, in ``randomize_terrain_position.__call__``'s order."""
+
+    def __init__(self, env, entity, curriculum, height_offset: float = 0.1e-3, rotation: dict | None = {"z": (0, 2 * math.pi)},
+                 zero_velocity: bool = True):
+        from ..managers.terrain_curriculum import TerrainCurriculum
+
+        if not isinstance(curriculum, TerrainCurriculum):
+            raise ValueError("curriculum must be a managers.TerrainCurriculum")
+        self._check(height_offset, rotation)
+        self.env = env
+        self._curriculum = curriculum
+        self._stage = None
+
+    @staticmethod
+    def _check(height_offset, rotation) -> None:
+        if not math.isfinite(float(height_offset)):
+            raise ValueError(f"height_offset must be finite, got {height_offset}")
+        if rotation is not None:
+            if not isinstance(rotation, dict) or any(k not in ("x", "y", "z") for k in rotation):
+                raise ValueError("rotation must be None or a dict with keys among 'x', 'y', 'z'")
+            for v in rotation.values():
+                if isinstance(v, tuple) and (len(v) != 2 or not all(math.isfinite(float(b)) for b in v)):
+                    raise ValueError(f"a rotation range must be a finite (lo, hi) pair, got {v}")
+
+    def build(self):
+        self._curriculum.build()   # (entity managers are built behind the terrain manager; a terrain without a grid is refused here)
+
+    def respawn(self, mask, mask2, update: bool, pos_in, pos_out, quat, stash, lin_vel, ang_vel, dof_vel, curriculum,
+                height_offset: float = 0.1e-3, rotation: dict | None = {"z": (0, 2 * math.pi)}, zero_velocity: bool = True):
+        """The launch.  Returns True when it wrote quaternions (``rotation`` is not None)."""
+        from ..managers.terrain_curriculum import rotation_ranges
+
+        self._check(height_offset, rotation)
+        rot = rotation_ranges(rotation)
+        draws = self.env.take_draws("curriculum")
+        curriculum.respawn(mask, mask2, pos_in, pos_out, quat_out=quat if rot is not None else None, quat_stash=stash, lin_vel=lin_vel,
+                           ang_vel=ang_vel, dof_vel=dof_vel, update=update, height_offset=height_offset, rotation=rot,
+                           zero_velocity=zero_velocity, draws=draws)
+        return rot is not None
+
+    def __call__(self, env, entity, envs_idx, curriculum, height_offset: float = 0.1e-3,
+                 rotation: dict | None = {"z": (0, 2 * math.pi)}, zero_velocity: bool = True):
+        mask = env._ids_to_mask(envs_idx)
+        update = bool(env._in_step)
+        if hasattr(entity, "gf_masked_base"):
+            pos, quat, lin, ang = entity.gf_masked_base()
+            dof_vel = entity.gf_masked_dofs(None)[1] if hasattr(entity, "gf_masked_dofs") else None
+            self.respawn(mask, None, update, pos, pos, quat, None, lin, ang, dof_vel, curriculum, height_offset, rotation, zero_velocity)
+            return
+        N = env.num_envs
+        if self._stage is None:
+            self._stage = (torch.zeros(N, 3, device=gs.device, dtype=gs.tc_float), torch.zeros(N, 4, device=gs.device, dtype=gs.tc_float))
+        pos_in = entity.get_pos().to(gs.tc_float).contiguous()
+        spos, squat = self._stage
+        with_quat = self.respawn(mask, None, update, pos_in, spos, squat, None, None, None, None, curriculum, height_offset, rotation,
+                                 zero_velocity)
+        ids = slice(None) if envs_idx is None else torch.as_tensor(envs_idx, device=gs.device, dtype=torch.long)
+        entity.set_pos(spos[ids], envs_idx=envs_idx, zero_velocity=zero_velocity)
+        if with_quat:
+            entity.set_quat(squat[ids], envs_idx=envs_idx, zero_velocity=zero_velocity)
+
+
 class randomize_link_mass_shift(ResetMdpFnClass):
     """Mass shift of the links whose name matches ``link_name`` (reference: mdp/reset.py:229-284) — a pure call into Genesis'
     ``set_mass_shift`` at reset time, nothing per env to compute (out of the hot path).

@@ -252,10 +252,18 @@ class OnPolicyRunner:
         """One record per iteration (the runner's own host reads are all here).  ``collection_time`` is the host's time to enqueue the
         rollout and ``learn_time`` ends at the update's one host read, which waits for the device: their sum is the iteration's."""
         steps = self.num_steps_per_env * self.storage.env.num_envs
+        std = self.alg.policy.action_std.mean()
+        curriculum = getattr(self.storage.env, "terrain_curriculum", None)
+        if curriculum is None or curriculum.levels is None:
+            std, level = float(std), None
+        else:   # the mean terrain level rides in the read of the action std: one value more, not a read of its own
+            std, level = torch.stack([std.detach().to(torch.float32), curriculum.mean_level().to(std.device)]).tolist()
         record = {"iteration": it, **self._loss_record(losses),
-                  "learning_rate": self.alg.learning_rate, "mean_action_std": float(self.alg.policy.action_std.mean()),
+                  "learning_rate": self.alg.learning_rate, "mean_action_std": std,
                   "mean_reward": stats.mean_reward(), "mean_episode_length": stats.mean_episode_length(),
                   "steps_per_second": steps / max(collection_s + learn_s, 1e-9), "collection_time": collection_s, "learn_time": learn_s}
+        if level is not None:      # (only for an env with a TerrainCurriculum: records without one keep their keys)
+            record["Curriculum/terrain_level"] = level
         if "symmetry" in losses:   # (only with algorithm.symmetry_cfg: records without one keep their keys)
             record["symmetry"] = losses["symmetry"]
         if "rnd" in losses:        # (only with algorithm.rnd_cfg)

@@ -418,6 +418,28 @@ class HumanoidGaitLikeEnv(ManagedEnvironment):
         })
 
 
+def graded_height_field(n_subterrains, cell_size, horizontal_scale: float, vertical_scale: float, max_height: float, level_axis: int = 0,
+                        seed: int = 2024):
+    """A deterministic integer height field (Genesis' layout: ``[nx * rows, ny * cols]`` height steps, metres = value *
+    ``vertical_scale``) for a grid of ``n_subterrains`` cells: blocky random roughness (1 m blocks) whose amplitude in a cell of level
+    ``l`` is ``max_height * (l + 1) / num_levels`` — level 0 the gentlest, the top level ``max_height``."""
+    import numpy as np
+
+    nx, ny = int(n_subterrains[0]), int(n_subterrains[1])
+    rows, cols = int(cell_size[0] / horizontal_scale + 1e-9), int(cell_size[1] / horizontal_scale + 1e-9)
+    levels = nx if level_axis == 0 else ny
+    blk = max(1, int(round(1.0 / horizontal_scale)))
+    rng = np.random.RandomState(seed)
+    hf = np.zeros((nx * rows, ny * cols), dtype=np.int16)
+    for i in range(nx):
+        for j in range(ny):
+            level = i if level_axis == 0 else j
+            top = int(round(max_height * (level + 1) / levels / vertical_scale))
+            coarse = rng.randint(0, top + 1, size=((rows + blk - 1) // blk, (cols + blk - 1) // blk))
+            hf[i * rows:(i + 1) * rows, j * cols:(j + 1) * cols] = np.kron(coarse, np.ones((blk, blk), dtype=np.int64))[:rows, :cols]
+    return hf
+
+
 class Go2RoughTerrainEnv(ManagedEnvironment):
     """BASELINE config 3 (cf. examples/rough_terrain/environment.py:87-287): Go2 on a height-field terrain, TerrainManager,
     random terrain spawn with random yaw on reset, out_of_bounds termination, two contact managers, 9 reward terms — plus
@@ -429,14 +451,21 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
     ``depth_camera`` (a dict of ``RayCaster`` keyword arguments; ``{}`` is a 16 x 12 pinhole at 87 degrees horizontal, mounted at the
     front of the trunk and pitched 30 degrees down, 4 m range, depth output) adds ``self.depth_camera`` and an ObservationManager
     ``"depth"`` that holds that one item: what a deployable student sees
-    (``obs_groups={"policy": ["policy", "depth"], "teacher": ["critic"]}``).  ``None`` builds the managers above and nothing else."""
+    (``obs_groups={"policy": ["policy", "depth"], "teacher": ["critic"]}``).  ``None`` builds the managers above and nothing else.
+    ``curriculum`` (a dict: ``num_levels`` (5), ``num_types`` (2), ``cell_size`` ((8, 8) metres), ``max_height`` (0.1 m, the roughness of the
+    top level) and ``TerrainCurriculum`` keyword arguments) makes the terrain a ``num_levels x num_types`` grid of cells whose roughness
+    grows with the level index — an explicit deterministic height field (``graded_height_field``) — adds ``self.terrain_curriculum`` and
+    replaces the one-rectangle spawn by ``mdp.reset.terrain_curriculum_position``: every env respawns in its own cell and moves a level up
+    or down with the distance it walked.  ``None`` (the default) builds exactly what it built before.  It composes with ``height_scan``
+    and ``depth_camera``."""
 
     #: the default sensor of ``depth_camera={}``
     DEPTH_CAMERA = dict(offset_pos=(0.3, 0.0, 0.05), offset_euler=(0.0, 30.0, 0.0), align="base", max_range=4.0, output="depth")
 
     def __init__(self, num_envs=1, dt=1 / 50, max_episode_length_s=20, scene_kwargs=None, height_reward=True, rotation="default",
-                 terrain_kwargs=None, cmd_resample_s=5.0, height_scan=None, depth_camera=None):
+                 terrain_kwargs=None, cmd_resample_s=5.0, height_scan=None, depth_camera=None, curriculum=None):
         super().__init__(num_envs=num_envs, dt=dt, max_episode_length_sec=max_episode_length_s, max_episode_random_scaling=0.1)
+        self._curriculum = None if curriculum is None else dict(curriculum)
         kw = dict(scene_kwargs or {})
         kw.setdefault("max_collision_pairs", 12)
         self._height_reward, self._rotation, self._cmd_resample_s = height_reward, rotation, cmd_resample_s
@@ -446,7 +475,25 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
         tk = dict(pos=(-12, -12, 0), n_subterrains=(1, 1), subterrain_size=(24, 24), vertical_scale=0.001,
                   subterrain_types=[["random_uniform_terrain"]],
                   subterrain_parameters={"random_uniform_terrain": {"min_height": 0.0, "max_height": 0.1, "step": 0.05, "downsampled_scale": 0.25}})
-        tk.update(terrain_kwargs or {})
+        if self._curriculum is not None:
+            cur = self._curriculum
+            levels, types = int(cur.pop("num_levels", 5)), int(cur.pop("num_types", 2))
+            cell = tuple(float(v) for v in cur.pop("cell_size", (8.0, 8.0)))
+            max_height = float(cur.pop("max_height", 0.1))
+            if levels < 1 or types < 1 or len(cell) != 2 or min(cell) <= 0.0 or max_height < 0.0:
+                raise ValueError("curriculum needs num_levels >= 1, num_types >= 1, a positive cell_size (x, y) and max_height >= 0")
+            if cur.get("level_axis", "x") not in ("x", "y"):
+                raise ValueError("level_axis must be 'x' or 'y'")
+            n_sub = (levels, types) if cur.get("level_axis", "x") == "x" else (types, levels)
+            tk.update(pos=(-n_sub[0] * cell[0] / 2, -n_sub[1] * cell[1] / 2, 0), n_subterrains=n_sub, subterrain_size=cell,
+                      subterrain_types=[["random_uniform_terrain"] * n_sub[1] for _ in range(n_sub[0])])
+            tk.update(terrain_kwargs or {})
+            if tk.get("height_field") is None:
+                # explicit: the stand-in scene's generator keys its parameters by type name, and every cell here has the same type
+                tk["height_field"] = graded_height_field(n_sub, cell, tk.get("horizontal_scale", 0.25), tk["vertical_scale"], max_height,
+                                                         level_axis=0 if cur.get("level_axis", "x") == "x" else 1)
+        else:
+            tk.update(terrain_kwargs or {})
         self.terrain = self.scene.add_entity(morph=morphs.Terrain(**tk))
         self.robot = self.scene.add_entity(morphs.URDF(file="urdf/go2/urdf/go2.urdf", pos=INITIAL_BODY_POSITION, quat=INITIAL_QUAT))
 
@@ -454,18 +501,27 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
         from genesis_forge_amd.managers import TerrainManager
 
         self.terrain_manager = TerrainManager(self)
-        params = {"height_offset": 0.4, "terrain_manager": self.terrain_manager}
+        make_command = lambda: VelocityCommandManager(
+            self, range={"lin_vel_x": [-1.0, 1.0], "lin_vel_y": [-1.0, 1.0], "ang_vel_z": [-0.5, 0.5]}, standing_probability=0.05,
+            resample_time_sec=self._cmd_resample_s)
+        if self._curriculum is not None:
+            from genesis_forge_amd.managers import TerrainCurriculum
+
+            self.velocity_command = make_command()   # (the curriculum reads the command an episode starts with)
+            self.terrain_curriculum = TerrainCurriculum(self, self.terrain_manager, command_manager=self.velocity_command, **self._curriculum)
+            spawn, params = reset.terrain_curriculum_position, {"height_offset": 0.4, "curriculum": self.terrain_curriculum}
+        else:
+            spawn, params = reset.randomize_terrain_position, {"height_offset": 0.4, "terrain_manager": self.terrain_manager}
         if self._rotation != "default":
             params["rotation"] = self._rotation
-        self.robot_manager = EntityManager(self, entity_attr="robot", on_reset={"position": {"fn": reset.randomize_terrain_position, "params": params}})
+        self.robot_manager = EntityManager(self, entity_attr="robot", on_reset={"position": {"fn": spawn, "params": params}})
         self.action_manager = PositionActionManager(
             self, joint_names=["FL_.*_joint", "FR_.*_joint", "RL_.*_joint", "RR_.*_joint"],
             default_pos={".*_hip_joint": 0.0, "FL_thigh_joint": 0.8, "FR_thigh_joint": 0.8, "RL_thigh_joint": 1.0, "RR_thigh_joint": 1.0,
                          ".*_calf_joint": -1.5},
             scale=0.25, use_default_offset=True, pd_kp=20, pd_kv=0.5, max_force=23.5)
-        self.velocity_command = VelocityCommandManager(
-            self, range={"lin_vel_x": [-1.0, 1.0], "lin_vel_y": [-1.0, 1.0], "ang_vel_z": [-0.5, 0.5]}, standing_probability=0.05,
-            resample_time_sec=self._cmd_resample_s)
+        if self._curriculum is None:
+            self.velocity_command = make_command()
         self.foot_contact_manager = ContactManager(self, link_names=[".*_calf"], track_air_time=True, air_time_contact_threshold=5.0)
         self.undesired_contacts = ContactManager(self, link_names=[".*_thigh", "base"])
         rcfg = {

@@ -1605,6 +1605,81 @@ typedef struct GfRayCastArgs {
 } GfRayCastArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * Terrain curriculum (managers/terrain_curriculum.py, mdp.reset.terrain_curriculum_position; legged_gym's
+ * _update_terrain_curriculum, Isaac Lab's terrain_levels_vel): the terrain is a grid of cells, difficulty growing along one axis;
+ * every env owns a (level, type) cell and respawns inside it.  One launch does the whole reset of the base for the flagged envs —
+ * level change, draws, position with the terrain height, orientation, velocities, bookkeeping.  For env n with
+ * mask[n] || (mask2 && mask2[n]), in f32 with one rounding per operation, in this order:
+ *   1. dx = pos_in[3n] - spawn_xy[2n], dy likewise; dist = sqrt(dx*dx + dy*dy)            (the distance walked since the spawn)
+ *   2. only if update != 0:  up = dist > promote_distance  (strict);  thr = speed_ref ? speed_ref[n] * demote_time : demote_distance;
+ *      down = !up && dist < thr;  l = level[n] + up - down.       With update == 0: l = level[n], and steps 1 and 4 are skipped.
+ *   3. draws u[0..5] = (x, y, rot x, rot y, rot z, level): row n of the dense `draws` [N, 6], or, with draws == NULL, Philox with
+ *      counter n + env_offset of `stream`: block GF_SPAWN_BLOCK gives (u0, u1, u4, u5), block GF_SPAWN_BLOCK + 1 gives (u2, u3) and is
+ *      computed only when spawn_rot_mask & 3 (else u2 = u3 = 0) — the spawn draws of GfResetArgs, plus the fourth word of the first
+ *      block, which that layout leaves unused.
+ *   4. l >= num_levels: l = min((int)(u5 * (float)num_levels), num_levels - 1), counted as a wrap.  Then l < 0: l = 0.
+ *   5. (ix, iy) = level_axis == 0 ? (l, type[n]) : (type[n], l)
+ *   6. x = (u0 * spawn_x_span + spawn_x_min) + (float)ix * cell_dx;  y likewise with u1, iy, cell_dy.  spawn_* is the usable rectangle
+ *      of cell (0, 0), computed by the host in double and stored as f32.  z = the height GfTerrainHeightArgs documents at (x, y)
+ *      (the same device function: the same bits) + height_offset.
+ *   7. set_quat: angle k = bit k of spawn_rot_mask ? u[2 + k] * (spawn_rot_hi[k] - spawn_rot_lo[k]) + spawn_rot_lo[k] : 0, the
+ *      quaternion by the deterministic xyz_to_quat of GfResetArgs' spawn.
+ *   8. writes: pos_out[n]; quat_out[n] if set_quat (the old quat_out[n] goes to quat_stash[n] first when quat_stash is given); zeros
+ *      to lin_vel, ang_vel, dof_vel [N, num_dofs] where non-NULL and zero_velocity is set; spawn_xy[n] = (x, y); level[n] = l;
+ *      if command.command: speed_ref[n] = sqrt(cx*cx + cy*cy) of the command's first two columns (stored after step 2 read the old
+ *      value); counts[0..2] += promoted (up), demoted (down, also when the floor of step 4 kept the level), wrapped.
+ * An env that is not flagged has nothing of its own written.  pos_in and pos_out may be the same buffer (a lane reads its row
+ * before it writes it).  A lane owns an env; a wave without a flagged lane leaves after the ballot; the counters are one vector
+ * atomicAdd per wave and counter; no LDS, nothing between workgroups.  A workgroup holds GF_TERRAIN_CURRICULUM_BLOCK_ENVS envs.
+ * Refusals, before any HIP call: GF_E_NULL — args, mask, pos_in, pos_out, spawn_xy, level, type, counts, quat_out with set_quat,
+ * speed_ref with a command; GF_E_RANGE — num_envs < 0 (or more than 2^31 - 1 workgroups), num_levels < 1, num_types < 1,
+ * num_dofs < 0, level_axis / update / set_quat outside {0, 1}, promote_distance / demote_time / demote_distance negative or not
+ * finite, a height field with rows < 1 or cols < 1, a command with width < 2 (or 0 < stride < width); GF_E_UNSUPPORTED — quat_out
+ * or quat_stash not 16-byte aligned (a row moves as one unit).  num_envs == 0 is a no-op.  Runs under GF_PHASE_TERRAIN for
+ * gf_profile_begin.  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_TERRAIN_CURRICULUM_BLOCK_ENVS 256   /* envs per workgroup (four waves) */
+
+typedef struct GfTerrainCurriculumArgs {
+    int64_t num_envs;
+    const uint8_t* mask;       /* [N] one byte per env */
+    const uint8_t* mask2;      /* [N] or NULL: OR-ed with mask */
+    const float* pos_in;       /* [N,3] the base position the episode ended at */
+    float* pos_out;            /* [N,3] the spawn position; may be pos_in */
+    float* quat_out;           /* [N,4] 16-byte aligned; may be NULL with set_quat = 0 */
+    float* quat_stash;         /* [N,4] 16-byte aligned or NULL: receives the pre-reset quat_out rows */
+    float* lin_vel;            /* [N,3] or NULL */
+    float* ang_vel;            /* [N,3] or NULL */
+    float* dof_vel;            /* [N,num_dofs] or NULL */
+    float* spawn_xy;           /* [N,2] where each env last spawned: read, then rewritten */
+    int32_t* level;            /* [N] read, then rewritten */
+    const int32_t* type;       /* [N] */
+    float* speed_ref;          /* [N] or NULL (then demote_distance is the threshold) */
+    int32_t* counts;           /* [3] promoted, demoted, wrapped: added to */
+    const float* draws;        /* [N,6] U[0,1) or NULL -> Philox */
+    GfCommandView command;     /* .command NULL: speed_ref is not rewritten */
+    uint64_t seed;
+    uint64_t stream;
+    uint32_t env_offset;
+    int32_t num_dofs;
+    int32_t num_levels;
+    int32_t num_types;
+    int32_t level_axis;        /* 0: levels along x, types along y; 1: the other way round */
+    int32_t update;            /* 0: respawn in the current cell; 1: move levels first */
+    int32_t set_quat;
+    int32_t zero_velocity;
+    int32_t spawn_rot_mask;
+    float promote_distance;
+    float demote_time;
+    float demote_distance;
+    float spawn_x_min, spawn_x_span, spawn_y_min, spawn_y_span;   /* the usable rectangle of cell (0, 0) */
+    float cell_dx, cell_dy;    /* the cell pitch */
+    float height_offset;
+    float spawn_rot_lo[3], spawn_rot_hi[3];
+    GfTerrainView terrain;
+} GfTerrainCurriculumArgs;
+
+/* ------------------------------------------------------------------------------------------
  * Entry points.  `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream).
  * ---------------------------------------------------------------------------------------- */
 int gf_abi_version(void);
@@ -1645,6 +1720,8 @@ int gf_height_scan(const GfHeightScanArgs* a, void* stream);     /* the terrain 
 int gf_height_scan_sizeof(void);                                 /* sizeof(GfHeightScanArgs): the binding's self-check for this additive entry (gf_sizeof's table ends at 40) */
 int gf_ray_cast(const GfRayCastArgs* a, void* stream);           /* R rays per env against the terrain surface, exact cell walk, in one launch (Isaac Lab RayCaster / depth camera) */
 int gf_ray_cast_sizeof(void);                                    /* sizeof(GfRayCastArgs): the binding's self-check for this additive entry */
+int gf_terrain_curriculum(const GfTerrainCurriculumArgs* a, void* stream);   /* promote / demote / respawn of the flagged envs in their terrain cells, in one launch (legged_gym _update_terrain_curriculum, Isaac Lab terrain_levels_vel) */
+int gf_terrain_curriculum_sizeof(void);                          /* sizeof(GfTerrainCurriculumArgs): the binding's self-check for this additive entry */
 int gf_synth_scene_step(const GfSynthSceneArgs* a, void* stream); /* stands in for scene.step() (managed_env.py:292) */
 int gf_rollout_write(const GfRolloutArgs* a, void* stream);       /* replaces the RolloutStorage copy_ launches of the RL library (examples/simple/train.py:125-129) */
 int gf_rollout_frame_write(const GfRolloutFrameArgs* a, void* stream);   /* the newest frame of up to four history observations into a frame-major rollout storage, one launch */

@@ -5,7 +5,7 @@
 // of them in flight per lane, every source row read from memory once — then walks the tile's destination chunks: the copy is the
 // chunk itself, the mirror gathers its four elements from the row in LDS through perm (a random LDS read costs a bank conflict at
 // worst) and multiplies by sign; with a normaliser both go through (v - mean[j]) / (std[j] + eps) at the destination column j.
-// tile = min(kMirMaxTileRows, GF_MIRROR_MAX_WIDTH / width) rows: 64 rows of a 48-wide observation, 7 of a 1 024-wide one.  The last
+// tile = min(kMirMaxTileRows, GF_MIRROR_MAX_WIDTH / width) rows: 64 rows of a 48-wide observation, 8 of a 1 024-wide one.  The last
 // grid row (y = num_fields) replicates the per-row scalars, 1 024 elements per workgroup.  Algorithmic traffic per row and field:
 // R 4·w, W 8·w bytes (4·w without dst_copy); the tables stay in cache.
 //

@@ -453,7 +453,7 @@ WIDTHS = [1, 3, 4, 5, 48, 235, 1024]
 @pytest.mark.parametrize("w", WIDTHS)
 def test_mirror_rows_is_torch_indexing_bit_for_bit(hip_backend, w):
     """Every row count x identity / reversal / random involution at this width: widths 4, 48 and 1 024 take the 16-byte path, the others
-    the element path; 257 rows of width 1 024 are 37 workgroups of 7 rows, 65 rows of width 48 two of 64."""
+    the element path; 257 rows of width 1 024 are 33 workgroups of 8 rows, 65 rows of width 48 two of 64."""
     g = torch.Generator().manual_seed(w)
     for rows in ROWS:
         x = torch.randn(rows, w, generator=g).cuda()

@@ -592,6 +592,18 @@ class GfTerrainCurriculumArgs(C.Structure):
                 ("height_offset", C.c_float), ("spawn_rot_lo", C.c_float * 3), ("spawn_rot_hi", C.c_float * 3), ("terrain", GfTerrainView)]
 
 
+# the random pushes (managers.PushDisturbance.step): gf_push — additive in the same way, not in ABI_STRUCTS
+GF_PUSH_BLOCK_ENVS = 256
+GF_PUSH_SEED_TAG = 0x9D15B0057ED5EEDB   # the kernel keys the push draws with seed ^ this tag (gf_step.h)
+
+
+class GfPushArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("mask", P), ("mask2", P), ("due", P), ("lin_vel", P), ("ang_vel", P), ("fired", P), ("counts", P),
+                ("draws", P), ("seed", C.c_uint64), ("step", C.c_uint32), ("env_offset", C.c_uint32), ("interval_lo", C.c_int32),
+                ("interval_hi", C.c_int32), ("mode", C.c_int32), ("comp_mask", C.c_int32), ("global_timer", C.c_int32), ("lo", C.c_float * 6),
+                ("hi", C.c_float * 6), ("scale", C.c_float)]
+
+
 # the newest frame of a history observation into a frame-major rollout storage (learner.RolloutStorage(history="frames")):
 # gf_rollout_frame_write, issued by the storage behind the step's rollout_write — not a phase, not in ABI_STRUCTS either
 GF_SIZEOF_ROLLOUT_FRAME = 30
@@ -863,6 +875,12 @@ class HipBackend(Backend):
             raise GfError(f"ABI drift: sizeof(GfTerrainCurriculumArgs) is {n} in the library, {C.sizeof(GfTerrainCurriculumArgs)} in the binding")
         self.lib.gf_terrain_curriculum.restype = C.c_int
         self.lib.gf_terrain_curriculum.argtypes = [C.POINTER(GfTerrainCurriculumArgs), C.c_void_p]
+        # the random pushes (managers.PushDisturbance): additive in the same way
+        n = self.lib.gf_push_sizeof()
+        if n != C.sizeof(GfPushArgs):
+            raise GfError(f"ABI drift: sizeof(GfPushArgs) is {n} in the library, {C.sizeof(GfPushArgs)} in the binding")
+        self.lib.gf_push.restype = C.c_int
+        self.lib.gf_push.argtypes = [C.POINTER(GfPushArgs), C.c_void_p]
         n = self.lib.gf_sizeof(GF_SIZEOF_RNN_CELL)
         if n != C.sizeof(GfRnnCell):
             raise GfError(f"ABI drift: sizeof(GfRnnCell) is {n} in the library, {C.sizeof(GfRnnCell)} in the binding")
@@ -1013,6 +1031,13 @@ class HipBackend(Backend):
         rc = self.lib.gf_terrain_curriculum(C.byref(args), self._stream())
         if rc != 0:
             self._raise("terrain_curriculum", rc)
+
+    def push(self, args) -> None:
+        """gf_push on the current stream (managers.PushDisturbance.step).  Only this backend has it: a backend without the method
+        makes the disturbance run the same float32 sequence as torch ops."""
+        rc = self.lib.gf_push(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("push", rc)
 
     def build_info(self) -> str:
         return self.lib.gf_build_info().decode()

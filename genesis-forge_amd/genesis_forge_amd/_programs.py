@@ -305,6 +305,9 @@ class _DryRunBackend(nat.HipBackend):
     def replay_step(self, replay, actions_ptr: int, params, num_params: int) -> None:
         pass
 
+    def push(self, args) -> None:   # (PushDisturbance launches outside the step: the tensors here are host memory)
+        pass
+
     def event_create(self):
         return None
 

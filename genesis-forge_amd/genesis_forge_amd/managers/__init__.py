@@ -9,6 +9,7 @@ from .terrain_manager import TerrainManager
 from .height_scanner import HeightScanner
 from .ray_caster import RayCaster
 from .terrain_curriculum import TerrainCurriculum
+from .push import PushDisturbance
 from .entity_manager import EntityManager
 from .observation_manager import ObservationManager
 from .config import MdpFnClass, ResetMdpFnClass
@@ -16,5 +17,5 @@ from .config import MdpFnClass, ResetMdpFnClass
 __all__ = [
     "BaseManager", "RewardManager", "TerminationManager", "CommandManager", "VelocityCommandManager", "GaitCommandManager",
     "BaseActionManager", "PositionActionManager", "PositionWithinLimitsActionManager", "ContactManager",
-    "TerrainManager", "HeightScanner", "RayCaster", "TerrainCurriculum", "EntityManager", "ObservationManager", "MdpFnClass", "ResetMdpFnClass",
+    "TerrainManager", "HeightScanner", "RayCaster", "TerrainCurriculum", "PushDisturbance", "EntityManager", "ObservationManager", "MdpFnClass", "ResetMdpFnClass",
 ]

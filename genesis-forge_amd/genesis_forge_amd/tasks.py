@@ -457,15 +457,20 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
     grows with the level index — an explicit deterministic height field (``graded_height_field``) — adds ``self.terrain_curriculum`` and
     replaces the one-rectangle spawn by ``mdp.reset.terrain_curriculum_position``: every env respawns in its own cell and moves a level up
     or down with the distance it walked.  ``None`` (the default) builds exactly what it built before.  It composes with ``height_scan``
-    and ``depth_camera``."""
+    and ``depth_camera``.
+    ``push`` (a dict of ``PushDisturbance`` keyword arguments; ``{}`` kicks x and y with up to 0.5 m/s every 10 to 15 s) adds ``self.push``
+    and a ``step()`` that runs it behind the step with the step's done masks: one more launch, the step inside stays the recorded one.
+    ``None`` (the default): the step is the parent class's."""
 
     #: the default sensor of ``depth_camera={}``
     DEPTH_CAMERA = dict(offset_pos=(0.3, 0.0, 0.05), offset_euler=(0.0, 30.0, 0.0), align="base", max_range=4.0, output="depth")
 
     def __init__(self, num_envs=1, dt=1 / 50, max_episode_length_s=20, scene_kwargs=None, height_reward=True, rotation="default",
-                 terrain_kwargs=None, cmd_resample_s=5.0, height_scan=None, depth_camera=None, curriculum=None):
+                 terrain_kwargs=None, cmd_resample_s=5.0, height_scan=None, depth_camera=None, curriculum=None, push=None):
         super().__init__(num_envs=num_envs, dt=dt, max_episode_length_sec=max_episode_length_s, max_episode_random_scaling=0.1)
         self._curriculum = None if curriculum is None else dict(curriculum)
+        self._push = None if push is None else dict(push)
+        self.push = None
         kw = dict(scene_kwargs or {})
         kw.setdefault("max_collision_pairs", 12)
         self._height_reward, self._rotation, self._cmd_resample_s = height_reward, rotation, cmd_resample_s
@@ -573,6 +578,22 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
             self.depth_camera = RayCaster(self, self.terrain_manager, entity_manager=self.robot_manager, **kw)
             self.depth_manager = ObservationManager(self, name="depth", cfg={
                 "depth": {"fn": observations.ray_cast, "params": {"caster": self.depth_camera}}})
+        if self._push is not None:
+            from genesis_forge_amd.managers import PushDisturbance
+
+            self.push = PushDisturbance(self, entity_manager=self.robot_manager, **self._push)
+
+    def build(self):
+        super().build()
+        if self.push is not None:
+            self.push.build()
+
+    def step(self, actions):
+        """The step, then the pushes with the step's done masks (code around ``super().step()``: the step inside is recorded as ever)."""
+        out = super().step(actions)
+        if self.push is not None:
+            self.push.step(out[2], out[3])
+        return out
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

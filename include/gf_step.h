@@ -1680,6 +1680,61 @@ typedef struct GfTerrainCurriculumArgs {
 } GfTerrainCurriculumArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * Random pushes (managers/push.py; legged_gym's push_robots / _push_robots, Isaac Lab's push_by_setting_velocity as an `interval`
+ * event): every few seconds the base gets a random velocity.  One launch keeps the per-env interval timers and gives the kick.
+ * The state is due[n], the value of `step` (the push's own call counter, uint32, wrapping) at which env n is pushed next — an
+ * absolute step, not a countdown, so that a launch in which nothing happens writes nothing but `fired`.  For env n, in this order
+ * (f32 with one rounding per operation, nothing contracted; integer sums modulo 2^32):
+ *   1. done = !global_timer && ((mask && mask[n]) || (mask2 && mask2[n]))         (this step's terminated / truncated masks)
+ *   2. fire = !done && (int32)(step - (uint32)due[n]) >= 0                         (wrap-safe: true for up to 2^31 - 1 steps past due)
+ *   3. if done || fire:  W = interval_hi - interval_lo + 1;
+ *      due[n] = (int32)(step + interval_lo + min((int)(u3 * (float)W), W - 1))
+ *   4. if fire, for every component j with bit j of comp_mask set (0..2: lin_vel x, y, z; 3..5: ang_vel x, y, z):
+ *      v = (u_j * (hi[j] - lo[j]) + lo[j]) * scale;  mode 0: vel[j] = v;  mode 1: vel[j] = vel[j] + v.
+ *      A component whose bit is clear is neither read nor written.
+ *   5. fired[n] = fire (where fired is given: written for EVERY env); counts[0] += the number of envs that fired.
+ * An env that finished its episode in this step is not pushed: it gets a fresh timer (Isaac Lab's per-env interval rule).  With
+ * global_timer the masks are not looked at (they may be NULL) and every env is pushed in the same steps (legged_gym).
+ * Draws: row n of the dense `draws` [N, 7] = (u0 … u6) (parity mode; with global_timer the caller puts the same u3 into every row),
+ * or, with draws == NULL, Philox4x32-10 keyed by seed ^ GF_PUSH_SEED_TAG — a key of its own, so no counter of any other phase can
+ * coincide — with counter (n + env_offset, block, step, 0), words to floats by u24_to_unit: block 0 gives (u0, u1, u2, u3), block 1
+ * gives (u4, u5, u6, -) and is computed only when comp_mask & 0x38.  With global_timer u3 is the fourth word of the block with
+ * counter (0xFFFFFFFF, 0, step, 0) instead: the same for every env, on every rank.
+ * A lane owns an env; a wave in which no lane is done or fires leaves after the ballot, having written its `fired` bytes — with
+ * intervals of hundreds of steps that is what almost every wave does; counts takes one vector atomicAdd per wave; no LDS, nothing
+ * between workgroups.  A workgroup holds GF_PUSH_BLOCK_ENVS envs.
+ * Refusals, before any HIP call: GF_E_NULL — args, due, lin_vel, counts, ang_vel with comp_mask & 0x38; GF_E_RANGE — num_envs < 0
+ * (or more than 2^31 - 1 workgroups), not 1 <= interval_lo <= interval_hi, interval_hi - interval_lo + 1 > 2^24 (u3 has 24 bits),
+ * mode / global_timer outside {0, 1}, comp_mask outside 0 … 63, a lo[j], hi[j] or scale that is not finite, hi[j] < lo[j] on an
+ * enabled component.  num_envs == 0 is a no-op.  Runs under GF_PHASE_TERRAIN for gf_profile_begin (the rough-terrain task's other
+ * additive entries do).  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_PUSH_BLOCK_ENVS 256                     /* envs per workgroup (four waves) */
+#define GF_PUSH_SEED_TAG 0x9D15B0057ED5EEDBull     /* XOR-ed into the seed of the push draws: a key of its own */
+
+typedef struct GfPushArgs {
+    int64_t num_envs;
+    const uint8_t* mask;       /* [N] one byte per env, or NULL */
+    const uint8_t* mask2;      /* [N] or NULL: OR-ed with mask */
+    int32_t* due;              /* [N] the step at which the env is pushed next: read, rewritten where done or fired */
+    float* lin_vel;            /* [N,3] */
+    float* ang_vel;            /* [N,3]; may be NULL when comp_mask & 0x38 == 0 */
+    uint8_t* fired;            /* [N] or NULL: 1 where pushed, 0 elsewhere */
+    int32_t* counts;           /* [1] pushes: added to */
+    const float* draws;        /* [N,7] U[0,1) or NULL -> Philox */
+    uint64_t seed;             /* Philox key = seed ^ GF_PUSH_SEED_TAG */
+    uint32_t step;             /* the push's own call counter */
+    uint32_t env_offset;
+    int32_t interval_lo;       /* steps, 1 <= interval_lo <= interval_hi */
+    int32_t interval_hi;
+    int32_t mode;              /* 0: set the enabled components; 1: add to them */
+    int32_t comp_mask;         /* bits 0..2: lin x, y, z; bits 3..5: ang x, y, z */
+    int32_t global_timer;      /* 0: per-env timers; 1: one interval draw for every env, masks ignored */
+    float lo[6], hi[6];        /* the range of each component */
+    float scale;               /* multiplies every drawn velocity (a magnitude curriculum) */
+} GfPushArgs;
+
+/* ------------------------------------------------------------------------------------------
  * Entry points.  `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream).
  * ---------------------------------------------------------------------------------------- */
 int gf_abi_version(void);
@@ -1722,6 +1777,8 @@ int gf_ray_cast(const GfRayCastArgs* a, void* stream);           /* R rays per e
 int gf_ray_cast_sizeof(void);                                    /* sizeof(GfRayCastArgs): the binding's self-check for this additive entry */
 int gf_terrain_curriculum(const GfTerrainCurriculumArgs* a, void* stream);   /* promote / demote / respawn of the flagged envs in their terrain cells, in one launch (legged_gym _update_terrain_curriculum, Isaac Lab terrain_levels_vel) */
 int gf_terrain_curriculum_sizeof(void);                          /* sizeof(GfTerrainCurriculumArgs): the binding's self-check for this additive entry */
+int gf_push(const GfPushArgs* a, void* stream);                  /* per-env interval timers and the random velocity kick of the envs that are due, in one launch (legged_gym _push_robots, Isaac Lab push_by_setting_velocity) */
+int gf_push_sizeof(void);                                        /* sizeof(GfPushArgs): the binding's self-check for this additive entry */
 int gf_synth_scene_step(const GfSynthSceneArgs* a, void* stream); /* stands in for scene.step() (managed_env.py:292) */
 int gf_rollout_write(const GfRolloutArgs* a, void* stream);       /* replaces the RolloutStorage copy_ launches of the RL library (examples/simple/train.py:125-129) */
 int gf_rollout_frame_write(const GfRolloutFrameArgs* a, void* stream);   /* the newest frame of up to four history observations into a frame-major rollout storage, one launch */

@@ -13,10 +13,12 @@ from .managers.height_scanner import HeightScanner
 from .managers.ray_caster import RayCaster
 from .managers.terrain_curriculum import TerrainCurriculum
 from .managers.push import PushDisturbance
+from .managers.action_delay import ActuatorDelay
+from .managers.action import DelayedPositionActionManager
 from .runner import DistillationRunner, OnPolicyRunner
 from .symmetry import MirrorSymmetry
 
-__all__ = ["GenesisEnv", "ManagedEnvironment", "EnvMode", "OnPolicyRunner", "DistillationRunner", "MirrorSymmetry", "HeightScanner", "RayCaster", "TerrainCurriculum", "PushDisturbance", "install_as_genesis_forge"]
+__all__ = ["GenesisEnv", "ManagedEnvironment", "EnvMode", "OnPolicyRunner", "DistillationRunner", "MirrorSymmetry", "HeightScanner", "RayCaster", "TerrainCurriculum", "PushDisturbance", "ActuatorDelay", "DelayedPositionActionManager", "install_as_genesis_forge"]
 __version__ = "0.1.0"
 
 

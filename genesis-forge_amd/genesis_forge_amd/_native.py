@@ -604,6 +604,17 @@ class GfPushArgs(C.Structure):
                 ("hi", C.c_float * 6), ("scale", C.c_float)]
 
 
+# actuator latency (managers.ActuatorDelay.step): gf_action_delay — additive in the same way, not in ABI_STRUCTS
+GF_ACTION_DELAY_MAX_SLOTS = 64
+GF_ACTION_DELAY_SEED_TAG = 0xAC7DE1A7C0FFEE5D   # the kernel keys the lag draws with seed ^ this tag (gf_step.h)
+
+
+class GfActionDelayArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("in_", P), ("out", P), ("ring", P), ("lag", P), ("episode_length", P), ("mask", P), ("mask2", P),
+                ("draws", P), ("seed", C.c_uint64), ("step", C.c_uint32), ("env_offset", C.c_uint32), ("num_dofs", C.c_int32),
+                ("slots", C.c_int32), ("head", C.c_int32), ("lag_lo", C.c_int32), ("lag_hi", C.c_int32), ("prime_all", C.c_int32)]
+
+
 # the newest frame of a history observation into a frame-major rollout storage (learner.RolloutStorage(history="frames")):
 # gf_rollout_frame_write, issued by the storage behind the step's rollout_write — not a phase, not in ABI_STRUCTS either
 GF_SIZEOF_ROLLOUT_FRAME = 30
@@ -881,6 +892,12 @@ class HipBackend(Backend):
             raise GfError(f"ABI drift: sizeof(GfPushArgs) is {n} in the library, {C.sizeof(GfPushArgs)} in the binding")
         self.lib.gf_push.restype = C.c_int
         self.lib.gf_push.argtypes = [C.POINTER(GfPushArgs), C.c_void_p]
+        # actuator latency (managers.ActuatorDelay): additive in the same way
+        n = self.lib.gf_action_delay_sizeof()
+        if n != C.sizeof(GfActionDelayArgs):
+            raise GfError(f"ABI drift: sizeof(GfActionDelayArgs) is {n} in the library, {C.sizeof(GfActionDelayArgs)} in the binding")
+        self.lib.gf_action_delay.restype = C.c_int
+        self.lib.gf_action_delay.argtypes = [C.POINTER(GfActionDelayArgs), C.c_void_p]
         n = self.lib.gf_sizeof(GF_SIZEOF_RNN_CELL)
         if n != C.sizeof(GfRnnCell):
             raise GfError(f"ABI drift: sizeof(GfRnnCell) is {n} in the library, {C.sizeof(GfRnnCell)} in the binding")
@@ -1038,6 +1055,13 @@ class HipBackend(Backend):
         rc = self.lib.gf_push(C.byref(args), self._stream())
         if rc != 0:
             self._raise("push", rc)
+
+    def action_delay(self, args) -> None:
+        """gf_action_delay on the current stream (managers.ActuatorDelay.step).  Only this backend has it: a backend without the
+        method makes the delay run the same sequence as torch ops."""
+        rc = self.lib.gf_action_delay(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("action_delay", rc)
 
     def build_info(self) -> str:
         return self.lib.gf_build_info().decode()

@@ -308,6 +308,9 @@ class _DryRunBackend(nat.HipBackend):
     def push(self, args) -> None:   # (PushDisturbance launches outside the step: the tensors here are host memory)
         pass
 
+    def action_delay(self, args) -> None:   # (ActuatorDelay launches from a Python phase of the step: the tensors here are host memory)
+        pass
+
     def event_create(self):
         return None
 

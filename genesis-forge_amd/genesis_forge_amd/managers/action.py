@@ -41,7 +41,7 @@ def _ensure_dof_pattern(value):
 
 class BaseActionManager(BaseManager):
     """Base for managers that handle actions (action/base.py:9-102).  ``delay_step`` is accepted and, as in
-    the reference (quirk q3: the FIFO is never primed), has no effect."""
+    the reference (quirk q3: the FIFO is never primed), has no effect.  ``DelayedPositionActionManager`` is the manager that delays."""
 
     def __init__(self, env, delay_step: int = 0):
         super().__init__(env, type="action")
@@ -277,6 +277,16 @@ class PositionActionManager(BaseActionManager):
 
     def _process(self, actions: torch.Tensor, _fuse_env: bool = False) -> torch.Tensor:
         """The native Phase A launch: scale / offset / clip (or the joint-limit map), NaN / Inf flags, targets to the actuators."""
+        self._compute(actions, _fuse_env)
+        return self._send(self._actions)
+
+    def _send(self, targets: torch.Tensor) -> torch.Tensor:
+        """Set target positions (position_action_manager.py:417).  Returns the manager's processed actions."""
+        self.env.robot.control_dofs_position(targets, self.dofs_idx)
+        return self._actions
+
+    def _compute(self, actions: torch.Tensor, _fuse_env: bool = False) -> None:
+        """The launch itself: the processed targets are in ``self._actions`` behind it; nothing has been sent."""
         env = self.env
         if actions.dtype != torch.float32 or not actions.is_contiguous():
             actions = actions.to(torch.float32).contiguous()
@@ -299,9 +309,6 @@ class PositionActionManager(BaseActionManager):
         env.backend.call("action_step", a, owner=self)
         if not self._quiet_action_errors:
             self._watch_flags()
-        # Set target positions (position_action_manager.py:417)
-        env.robot.control_dofs_position(self._actions, self.dofs_idx)
-        return self._actions
 
     def handle_actions(self, actions: torch.Tensor) -> torch.Tensor:
         """position_action_manager.py:389-419: actions → position targets, sent to the actuators.  A subclass that overrides it is
@@ -432,3 +439,56 @@ class PositionWithinLimitsActionManager(PositionActionManager):
         self._scale = ((upper - lower) * 0.5).unsqueeze(0).expand(self.env.num_envs, -1)
         self._k_offset = ((upper + lower) * 0.5).contiguous()
         self._k_scale = ((upper - lower) * 0.5).contiguous()
+
+
+class DelayedPositionActionManager(PositionActionManager):
+    """A ``PositionActionManager`` whose targets reach the actuators through a randomised per-env latency (Isaac Lab's
+    ``DelayedPDActuator``; managers/action_delay.py has the mechanism).  The constructor takes the parent's arguments plus ``lag_steps``
+    ``(lo, hi)`` — the lag of an episode, in control steps, uniform over lo … hi — and ``max_lag`` (default ``hi``; what
+    ``delay.set_lag_range`` may widen to later).
+
+    The delay lives in the actuator: ``env.actions`` / ``env.last_actions`` (and so ``action_rate_l2``) are the policy's raw actions,
+    ``get_actions()`` / ``.actions`` the undelayed processed targets — what the policy commanded and what it can know on a real
+    robot —, and ``applied_actions`` the delayed buffer the actuators track.  ``delay.lag`` is the privileged per-env lag.
+
+    It overrides ``handle_actions()``, the reference's extension point, so a recorded step runs it as user code at the place of the
+    action phase, behind the env's bookkeeping launch: ``episode_length`` is 1 in the first step of an episode, which is how the
+    delay finds the fresh envs without an index list — there is no ``reset()`` override.  A reset called between steps hands its mask
+    to the next launch; ``env.reset()`` of everything therefore primes every env, whatever is written to ``episode_length`` afterwards."""
+
+    def __init__(self, env, *args, lag_steps=(0, 2), max_lag: Optional[int] = None, **kwargs):
+        from .action_delay import check_lags
+
+        self._lag_cfg = check_lags(lag_steps, max_lag)   # (first: a refused construction registers nothing with the env)
+        super().__init__(env, *args, **kwargs)
+        self.delay = None
+        self._fresh_mask: Optional[torch.Tensor] = None
+
+    def build(self):
+        from .action_delay import ActuatorDelay
+
+        super().build()
+        lo, hi, max_lag = self._lag_cfg
+        self.delay = ActuatorDelay(self.env, self.num_actions, lag_steps=(lo, hi), max_lag=max_lag)
+        self.delay.build()
+
+    @property
+    def applied_actions(self) -> torch.Tensor:
+        """The delayed targets the actuators track (``[N, D]``, the same tensor every step; zeros before the first step)."""
+        if self.delay is None:
+            return torch.zeros((self.env.num_envs, self.num_actions))
+        return self.delay.out
+
+    def handle_actions(self, actions: torch.Tensor) -> torch.Tensor:
+        """Process as the parent does, delay, send the delayed targets — once."""
+        self._compute(actions, False)
+        mask, self._fresh_mask = self._fresh_mask, None
+        return self._send(self.delay.step(self._actions, mask))
+
+    def _after_fused_reset(self, mask, mask2) -> None:
+        super()._after_fused_reset(mask, mask2)
+        if not self.env._in_step and self.delay is not None:
+            # a reset between steps: its envs are fresh in the next launch even if their episode_length is written to afterwards
+            # (an in-step reset needs nothing: episode_length is 1 when the delay next runs)
+            m = mask if mask2 is None else (mask | mask2)
+            self._fresh_mask = m if self._fresh_mask is None else (self._fresh_mask | m)

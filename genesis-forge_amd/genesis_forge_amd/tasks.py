@@ -460,17 +460,23 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
     and ``depth_camera``.
     ``push`` (a dict of ``PushDisturbance`` keyword arguments; ``{}`` kicks x and y with up to 0.5 m/s every 10 to 15 s) adds ``self.push``
     and a ``step()`` that runs it behind the step with the step's done masks: one more launch, the step inside stays the recorded one.
-    ``None`` (the default): the step is the parent class's."""
+    ``None`` (the default): the step is the parent class's.
+    ``action_delay`` (a dict of ``lag_steps`` / ``max_lag``; ``{}`` is ``lag_steps=(0, 2)``) builds a ``DelayedPositionActionManager`` in
+    place of the ``PositionActionManager``: the targets reach the actuators a per-env, per-episode number of control steps late, and
+    ``self.action_delay`` is its ``ActuatorDelay``.  The action phase of the step then is the bookkeeping launch, the manager's code, the
+    process launch and the delay launch; the rest of the step stays recorded.  ``None`` (the default) builds exactly what it built before."""
 
     #: the default sensor of ``depth_camera={}``
     DEPTH_CAMERA = dict(offset_pos=(0.3, 0.0, 0.05), offset_euler=(0.0, 30.0, 0.0), align="base", max_range=4.0, output="depth")
 
     def __init__(self, num_envs=1, dt=1 / 50, max_episode_length_s=20, scene_kwargs=None, height_reward=True, rotation="default",
-                 terrain_kwargs=None, cmd_resample_s=5.0, height_scan=None, depth_camera=None, curriculum=None, push=None):
+                 terrain_kwargs=None, cmd_resample_s=5.0, height_scan=None, depth_camera=None, curriculum=None, push=None, action_delay=None):
         super().__init__(num_envs=num_envs, dt=dt, max_episode_length_sec=max_episode_length_s, max_episode_random_scaling=0.1)
         self._curriculum = None if curriculum is None else dict(curriculum)
         self._push = None if push is None else dict(push)
         self.push = None
+        self._action_delay = None if action_delay is None else dict(action_delay)
+        self.action_delay = None
         kw = dict(scene_kwargs or {})
         kw.setdefault("max_collision_pairs", 12)
         self._height_reward, self._rotation, self._cmd_resample_s = height_reward, rotation, cmd_resample_s
@@ -520,11 +526,16 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
         if self._rotation != "default":
             params["rotation"] = self._rotation
         self.robot_manager = EntityManager(self, entity_attr="robot", on_reset={"position": {"fn": spawn, "params": params}})
-        self.action_manager = PositionActionManager(
+        make_actions, delay_kw = PositionActionManager, {}
+        if self._action_delay is not None:
+            from genesis_forge_amd.managers import DelayedPositionActionManager
+
+            make_actions, delay_kw = DelayedPositionActionManager, dict({"lag_steps": (0, 2)}, **self._action_delay)
+        self.action_manager = make_actions(
             self, joint_names=["FL_.*_joint", "FR_.*_joint", "RL_.*_joint", "RR_.*_joint"],
             default_pos={".*_hip_joint": 0.0, "FL_thigh_joint": 0.8, "FR_thigh_joint": 0.8, "RL_thigh_joint": 1.0, "RR_thigh_joint": 1.0,
                          ".*_calf_joint": -1.5},
-            scale=0.25, use_default_offset=True, pd_kp=20, pd_kv=0.5, max_force=23.5)
+            scale=0.25, use_default_offset=True, pd_kp=20, pd_kv=0.5, max_force=23.5, **delay_kw)
         if self._curriculum is None:
             self.velocity_command = make_command()
         self.foot_contact_manager = ContactManager(self, link_names=[".*_calf"], track_air_time=True, air_time_contact_threshold=5.0)
@@ -585,6 +596,8 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
 
     def build(self):
         super().build()
+        if self._action_delay is not None:
+            self.action_delay = self.action_manager.delay
         if self.push is not None:
             self.push.build()
 

@@ -1735,6 +1735,59 @@ typedef struct GfPushArgs {
 } GfPushArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * Actuator latency (managers/action_delay.py; Isaac Lab's DelayedPDActuator with its per-env DelayBuffer, the "action lag" buffer of
+ * the legged_gym forks): the position targets a policy commands reach the actuators lag[n] control steps late, and the lag is drawn
+ * per env and per episode.  One launch writes this step's targets into a ring of `slots` = L steps, hands out the targets of
+ * lag[n] steps ago and re-draws the lag and primes the ring of every env whose episode has just begun.
+ * ring is [L, N, D], slot-major: the write to slot `head` is one coalesced stream, a lagged read a contiguous D-row of another slot.
+ * `head` is the slot this call writes; the host advances it by one modulo L per call (it is not derived from the wrapping call
+ * counter `step`: L need not divide 2^32).  For env n, in this order:
+ *   1. fresh = prime_all || (episode_length && episode_length[n] <= 1) || (mask && mask[n]) || (mask2 && mask2[n])
+ *      (episode_length is the env's counter AFTER this step's increment: 1 in the first step of an episode, 0 where a reset ran and
+ *      no step has; every input of the test is read-only in the launch, so all lanes that own a part of the env decide alike)
+ *   2. fresh:  u = draws ? draws[n] : u24_to_unit(x word of Philox4x32-10, counter (n + env_offset, 0, step, 0),
+ *                                                  key seed ^ GF_ACTION_DELAY_SEED_TAG);
+ *              W = lag_hi - lag_lo + 1;  lag[n] = lag_lo + min((int)(u * (float)W), W - 1)        (one f32 product, truncated)
+ *   3. fresh:  ring[s, n, :] = in[n, :] for every s in 0 … L-1;  out[n, :] = in[n, :]
+ *      (Isaac Lab's rule: a cleared buffer is filled with the first value pushed, so a new episode sees its own command until the
+ *      history exists.  A lane that does not write lag[n] computes the draw again; it never reads lag[n] back.)
+ *   4. otherwise:  ring[head, n, :] = in[n, :];  l = lag[n];
+ *              out[n, :] = l == 0 ? in[n, :] : ring[(head + L - l) % L, n, :]                     (never the slot just written)
+ *      lag[n] is not written, nor is any slot but `head`.  A lag[n] outside 0 … L-1 (state the launch did not write) reads as 0.
+ *   5. Values move as bits: a NaN or Inf of `in` arrives in `out` lag[n] steps later with the same bit pattern.
+ * The [N, D] streams move as 16-byte words, one per lane, when D % 4 == 0 and in / out / ring are 16-byte aligned (a word is then
+ * four DOFs of one env), element by element otherwise; no LDS, nothing between lanes.  Traffic of an ordinary step: 16 D bytes per
+ * env (in, the slot written, the slot read, out) + 4 of lag + the freshness bytes.
+ * Refusals, before any HIP call: GF_E_NULL — args, in, out, ring, lag; GF_E_RANGE — num_envs < 0 (or more than 2^31 - 1
+ * workgroups), num_dofs <= 0, slots outside 1 … GF_ACTION_DELAY_MAX_SLOTS, head outside 0 … slots-1, not
+ * 0 <= lag_lo <= lag_hi <= slots-1, prime_all outside {0, 1}.  num_envs == 0 is a no-op.  Runs under GF_PHASE_TERRAIN for
+ * gf_profile_begin (the rough-terrain task's other additive entries do).  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_ACTION_DELAY_MAX_SLOTS 64                       /* the ring's capacity: the largest lag is 63 steps */
+#define GF_ACTION_DELAY_SEED_TAG 0xAC7DE1A7C0FFEE5Dull     /* XOR-ed into the seed of the lag draws: a key of its own */
+
+typedef struct GfActionDelayArgs {
+    int64_t num_envs;
+    const float* in;           /* [N,D] this step's targets */
+    float* out;                /* [N,D] the targets the actuators get */
+    float* ring;               /* [L,N,D] slot-major history */
+    int32_t* lag;              /* [N] steps of delay: read, rewritten where fresh */
+    const int32_t* episode_length;   /* [N] or NULL: fresh where <= 1 */
+    const uint8_t* mask;       /* [N] one byte per env, or NULL: fresh where set */
+    const uint8_t* mask2;      /* [N] or NULL: OR-ed with mask */
+    const float* draws;        /* [N] U[0,1) or NULL -> Philox */
+    uint64_t seed;             /* Philox key = seed ^ GF_ACTION_DELAY_SEED_TAG */
+    uint32_t step;             /* the delay's own call counter */
+    uint32_t env_offset;
+    int32_t num_dofs;          /* D */
+    int32_t slots;             /* L = the largest lag + 1 */
+    int32_t head;              /* the slot this call writes */
+    int32_t lag_lo;            /* 0 <= lag_lo <= lag_hi <= slots - 1 */
+    int32_t lag_hi;
+    int32_t prime_all;         /* 1: every env is fresh (the first call, a reset of everything) */
+} GfActionDelayArgs;
+
+/* ------------------------------------------------------------------------------------------
  * Entry points.  `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream).
  * ---------------------------------------------------------------------------------------- */
 int gf_abi_version(void);
@@ -1779,6 +1832,8 @@ int gf_terrain_curriculum(const GfTerrainCurriculumArgs* a, void* stream);   /* 
 int gf_terrain_curriculum_sizeof(void);                          /* sizeof(GfTerrainCurriculumArgs): the binding's self-check for this additive entry */
 int gf_push(const GfPushArgs* a, void* stream);                  /* per-env interval timers and the random velocity kick of the envs that are due, in one launch (legged_gym _push_robots, Isaac Lab push_by_setting_velocity) */
 int gf_push_sizeof(void);                                        /* sizeof(GfPushArgs): the binding's self-check for this additive entry */
+int gf_action_delay(const GfActionDelayArgs* a, void* stream);  /* per-env delayed position targets: ring write, lagged read, re-draw and priming of the fresh envs, in one launch (Isaac Lab DelayedPDActuator, legged_gym action lag) */
+int gf_action_delay_sizeof(void);                                /* sizeof(GfActionDelayArgs): the binding's self-check for this additive entry */
 int gf_synth_scene_step(const GfSynthSceneArgs* a, void* stream); /* stands in for scene.step() (managed_env.py:292) */
 int gf_rollout_write(const GfRolloutArgs* a, void* stream);       /* replaces the RolloutStorage copy_ launches of the RL library (examples/simple/train.py:125-129) */
 int gf_rollout_frame_write(const GfRolloutFrameArgs* a, void* stream);   /* the newest frame of up to four history observations into a frame-major rollout storage, one launch */

@@ -708,7 +708,10 @@ static int post_launch(const GfPostArgs& packed, hipStream_t s, const PostProgra
 #ifdef GF_STAMPS
     GfPostArgs stamped = packed;
     stamped.stamps = gf_debug_stamps;
-    stamped.stamp_block = (uint32_t)(packed.num_envs / 64 / 2);
+    const uint32_t stamp_tiles = (uint32_t)env_grid(packed.num_envs);
+    stamped.stamp_stride = stamp_tiles / kStampSlots > 0 ? stamp_tiles / kStampSlots : 1u;
+    const char* const rs = getenv("GF_ROLE_SHIFT");   // (read per launch)
+    stamped.role_shift = rs && *rs >= '0' && *rs <= '9' && atoi(rs) <= 15 ? atoi(rs) : -1;
     const GfPostArgs& a = stamped;
 #else
     const GfPostArgs& a = packed;

@@ -6,20 +6,35 @@
 #include "gf_terms.h"
 #include "gf_contact_tile.h"
 
-// Diagnostic build only (tools/stamp_post.hip, -DGF_STAMPS): lane 0 of every wave of one workgroup records the 100 MHz
-// wall clock at the phase boundaries into a buffer of its own, stamps[16*wave + i]; no product build contains a stamp.
-// (ws_block: the workgroup's tile id in post_ws_body — blockIdx.x less the upkeep workgroups of a tick program.)
+// Diagnostic build only (tools/stamp_config.py, -DGF_STAMPS): lane 0 of every wave of up to kStampSlots workgroups spread over the grid
+// (tile = slot · stamp_stride) records the 100 MHz wall clock at the phase boundaries into a buffer of its own,
+// stamps[(4·slot + role)·16 + i], and once (GF_WHERE) where the hardware put it: behind the clock rows, two words per (slot, role) —
+// the HW_ID register (wave, SIMD, CU, shader array, shader engine) and the XCC_ID register, with the wave's index in its workgroup in
+// the upper half of the second word.  No product build contains a stamp.
+// (ws_block: the workgroup's tile id in post_ws_body — blockIdx.x less the upkeep workgroups of a tick program; `wave`: the role.)
 #ifdef GF_STAMPS
 extern "C" unsigned long long* gf_debug_stamps;  // host variable set by the tool
+constexpr int kStampSlots = 16;
+constexpr int kStampWords = kStampSlots * 4 * 16 + kStampSlots * 4 * 2;
+#define GF_STAMPED() (a.stamps && ws_block % a.stamp_stride == 0 && ws_block / a.stamp_stride < (unsigned)kStampSlots && (threadIdx.x & 63) == 0)
 #define GF_WSTAMP(i)                                                                                         \
     do {                                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
-        if (a.stamps && ws_block == a.stamp_block && (threadIdx.x & 63) == 0)                              \
-            a.stamps[16 * wave + i] = __builtin_amdgcn_s_memrealtime();                                      \
+        if (GF_STAMPED())                                                                                    \
+            a.stamps[(4 * (ws_block / a.stamp_stride) + wave) * 16 + i] = __builtin_amdgcn_s_memrealtime();  \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
+    } while (0)
+#define GF_WHERE()                                                                                           \
+    do {                                                                                                     \
+        if (GF_STAMPED()) {                                                                                  \
+            unsigned long long* const w_ = a.stamps + kStampSlots * 4 * 16 + (4 * (ws_block / a.stamp_stride) + wave) * 2; \
+            w_[0] = __builtin_amdgcn_s_getreg(4 | (31 << 11));    /* HW_REG_HW_ID, all 32 bits */              \
+            w_[1] = (unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) | ((unsigned long long)hw_wave << 32);   /* HW_REG_XCC_ID */ \
+        }                                                                                                    \
     } while (0)
 #else
 #define GF_WSTAMP(i)
+#define GF_WHERE()
 #endif
 
 namespace gf {
@@ -165,7 +180,8 @@ struct alignas(16) GfPostArgs {
     PostContact cfold;
 #ifdef GF_STAMPS
     unsigned long long* stamps;
-    uint32_t stamp_block;
+    uint32_t stamp_stride;   // >= 1: tile slot · stamp_stride is stamped, slot < kStampSlots
+    int32_t role_shift;      // GF_ROLE_SHIFT = 0 … 15: a program that may (ws_rotates) runs role (wave + (tile >> role_shift)) & 3; -1: role = wave
 #endif
 };
 static_assert(sizeof(GfPostArgs) <= 4096, "GfPostArgs must fit the 4 KB kernarg segment");

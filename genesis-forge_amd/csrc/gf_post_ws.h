@@ -233,6 +233,16 @@ __host__ __device__ constexpr bool ws_hands_over() {
 template <class P>
 __host__ __device__ constexpr int ws_hand_floats() { return H_STREAMS * kEnvBlock * 4 * P::DV + HB_FIELDS * kEnvBlock + 4 * P::DV; }   // streams, base rows, zero row
 
+#ifdef GF_STAMPS
+// Diagnostic build only: may the roles of program P be rotated over the hardware waves (role = (wave + (tile >> role_shift)) & 3)?  The
+// static programs the tick covers; checked bit for bit against role = wave with programs 1 and 2 (profiles/r33_role_balance.md).
+template <class P>
+__host__ __device__ constexpr bool ws_rotates() {
+    if constexpr (P::kStatic) return !ws_prog_folds<P>() && ws_pre_rows<P>() == 0 && ws_obs_norm_rows<P>() == 0 && P::n_gait == 0;
+    else return false;
+}
+#endif
+
 // The kernel's body.  tick_act / tick_scene / tick_upkeep are read by a WithTick program only (the descriptors of the step's action and
 // scene ops and the number of leading statistics-upkeep workgroups, as in action_scene_tile_kernel); every other program passes nothing.
 template <class P>
@@ -272,9 +282,22 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
     float* lds_norm = lds_pre + kPreRows * kEnvBlock;        // [kNormRows][64]: contact-force norms of observation items (wave 3, before the barrier)
     float* tile = lds_norm + kNormRows * kEnvBlock;          // [64][O+1]
 
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    // `wave` is the ROLE of this wave everywhere below: its index in the workgroup.  (The diagnostic build can rotate the roles over the
+    // hardware waves from tile to tile, GF_ROLE_SHIFT: the experiment of profiles/r33_role_balance.md; no product build does.)
+    const int hw_wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+#ifdef GF_STAMPS
+    const int wave = ws_rotates<P>() && a.role_shift >= 0 ? (hw_wave + (int)((ws_block >> (a.role_shift & 15)) & 3u)) & 3 : hw_wave;
+#else
+    const int wave = hw_wave;
+#endif
     GF_WSTAMP(1);
+    GF_WHERE();
     const int lane = threadIdx.x & (GF_WAVE - 1);
+#ifdef GF_STAMPS
+    const int role_tid = ws_rotates<P>() ? wave * GF_WAVE + lane : (int)threadIdx.x;   // the lane's index in the tile's work
+#else
+    const int role_tid = threadIdx.x;   // the lane's index in the tile's work
+#endif
     const int64_t N = UNI(a.num_envs);
     const int64_t tile_id = ws_block;
     const int64_t n0 = tile_id * kEnvBlock;
@@ -326,6 +349,34 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
     float* const hand_base = lds_aux + H_STREAMS * kEnvBlock * 4 * DV;     // [HB_FIELDS][64]
     float4* const hand_zero = reinterpret_cast<float4*>(hand_base + HB_FIELDS * kEnvBlock);   // [DV]: the row of an array the launch does not need
     int hand_env = lane;   // the env of the tile whose handed rows this lane reads
+    // Early requests (a static program that hands over): what the roles read of arrays NO tick writes is asked for here, in front of the
+    // tick's own loads, so that it travels with them instead of as a round trip of its own behind the tick's barrier — the reward
+    // role its episode-sum rows (LDS-DMA into rows nobody writes before the fold), the default joint row and the env's episode seconds,
+    // the control role max_episode_length, the DOF role the default joint row.  The same loads of the same addresses, only sooner; the
+    // reward role's old command view and the control role's command rows stay behind the tick (three registers across the tick cost
+    // the sixth wave per SIMD).
+    constexpr bool kEarly = kHand && P::kStatic;
+    float4 early_def[kEarly ? R : 1];
+    float early_secs = 0.f;
+    int early_max_len = 0;
+    if constexpr (kEarly) {
+        if (wave == 1) {
+            if (logging) {
+                static_for<P::n_rew>([&](auto K) GF_INLINE_LAMBDA {
+                    constexpr int k_ = decltype(K)::value;
+                    __builtin_amdgcn_global_load_lds(k_sums + (int64_t)karg.rterms[k_].row * N + n, lds_sums + k_ * kEnvBlock, 4, 0, 0);
+                });
+            }
+            row_load<DV>(early_def, gsel((needs & PN_DOFDEV) != 0, UNI(a.default_dof_pos), 0u), D);
+            const float* k_secs = UNI(a.episode_seconds);
+            early_secs = *gsel(has_reward && k_secs != nullptr, k_secs, e);
+        } else if (wave == 0) {
+            early_max_len = *gsel((needs & PN_MAXLEN) != 0, UNI(a.max_episode_length), e);
+        } else if (wave == 2) {
+            const float* k_def = UNI(a.default_dof_pos);
+            row_load<DV>(early_def, gsel(k_def != nullptr, k_def, 0u), D);
+        }
+    }
     if constexpr (kTick) {
         static_assert(kSynthTileBlock == kWsBlock && 3 * 3 * kEnvBlock <= X_FIELDS * kEnvBlock, "the tick's workgroup and LDS fit the kernel's");
         const GfSynthSceneArgs& sc = *tick_scene;
@@ -334,11 +385,11 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
         SynthBase ticked;   // (the body's out-parameter, unused here: what the roles need of it goes through the sink, inside wave 0's branch)
         if constexpr (kHand) {
             static_assert(kPreRows == 0 && kNormRows == 0, "the handed rows run from the scratch rows into the observation tile");
-            synth_tick_tile<DV, kEnvBlock, true>(sc, *tick_act, n0, rows, s3, ticked, TickHand<DV, kEnvBlock>{hand_rows, hand_base});
+            synth_tick_tile<DV, kEnvBlock, true>(sc, *tick_act, n0, rows, role_tid, s3, ticked, TickHand<DV, kEnvBlock>{hand_rows, hand_base});
             hand_env = lane < rows ? lane : rows - 1;
-            if (threadIdx.x < DV) hand_zero[threadIdx.x] = z4;
+            if (role_tid < DV) hand_zero[role_tid] = z4;
         } else {
-            synth_tick_tile<DV, kEnvBlock, true>(sc, *tick_act, n0, rows, s3, ticked);
+            synth_tick_tile<DV, kEnvBlock, true>(sc, *tick_act, n0, rows, role_tid, s3, ticked);
         }
         GF_WSTAMP(12);
         __syncthreads();
@@ -542,7 +593,9 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
             lin = V3{lp[0], lp[1], lp[2]}; ang = V3{ap[0], ap[1], ap[2]};
             ep_len = *gsel((needs & PN_EPLEN) != 0, UNI(a.episode_length), e);
         }
-        const int max_len = *gsel((needs & PN_MAXLEN) != 0, UNI(a.max_episode_length), e);
+        int max_len;
+        if constexpr (kEarly) max_len = early_max_len;
+        else max_len = *gsel((needs & PN_MAXLEN) != 0, UNI(a.max_episode_length), e);
 #pragma unroll
         for (int c = 0; c < GF_POST_MAX_CMD; ++c) {
             const bool on = c < n_cmd;
@@ -703,7 +756,7 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
         xch[X_DIRTY * kEnvBlock + lane] = (float)((cmd_dirty[0] ? 1 : 0) | (cmd_dirty[1] ? 2 : 0));
     } else if (wave == 1) {
         // ---- reward: loads + per-row reductions ------------------------------------------------------------------------------
-        if (logging) {
+        if (logging && !kEarly) {
             if constexpr (P::kStatic) {
                 static_for<P::n_rew>([&](auto K) GF_INLINE_LAMBDA {
                     constexpr int k_ = decltype(K)::value;
@@ -718,7 +771,12 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
         float4 r_def[R];
         V3 pos;
         if constexpr (kHand) {
-            row_load<DV>(r_def, p3, D);
+            if constexpr (kEarly) {
+#pragma unroll
+                for (int c = 0; c < DV; ++c) r_def[c] = early_def[c];
+            } else {
+                row_load<DV>(r_def, p3, D);
+            }
             hand_row(r_a, (needs & PN_DOFDEV) != 0, H_DOFPOS); hand_row(r_b, (needs & PN_ACTRATE) != 0, H_ACTIONS); hand_row(r_c, (needs & PN_ACTRATE) != 0, H_LAST);
             pos = hand_v3((needs & PN_POS) != 0, HB_POS);
         } else {
@@ -745,7 +803,9 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
             wang = V3{ap[0], ap[1], ap[2]};
         }
         const float* k_secs = UNI(a.episode_seconds);
-        const float secs_in = *gsel(has_reward && k_secs != nullptr, k_secs, e);
+        float secs_in;
+        if constexpr (kEarly) secs_in = early_secs;
+        else secs_in = *gsel(has_reward && k_secs != nullptr, k_secs, e);
         float dof_dev = 0.f, act_rate = 0.f, cmd0[3];
         {   // command view 0 as it is BEFORE this step's resample (its new values are stored only after the second barrier)
             const float* v0 = UNI(a.command[0].command);
@@ -830,7 +890,12 @@ __device__ __forceinline__ void post_ws_body(const GfPostArgs& karg, const GfAct
             const GF_GLOBAL float* p1 = gsel((needs & PN_DOFVEL) != 0, UNI(a.dof_vel), ro);
             row_load<DV>(r_a, p0, D); row_load<DV>(r_b, p1, D);
         }
-        row_load<DV>(r_c, p2, D);
+        if constexpr (kEarly) {
+#pragma unroll
+            for (int c = 0; c < DV; ++c) r_c[c] = early_def[c];
+        } else {
+            row_load<DV>(r_c, p2, D);
+        }
         GF_WSTAMP(9);
         if constexpr (kPreRows > 0) {   // the memory-only reward terms (see reward_op_memory_only), parked for the fold
             RewardRegs rp;   // (parked rows exist only in a program with reward terms, which matches only a launch that has the reward manager)

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(kSynthTileBlock) void synth_scene_tile_kernel(const
     const int64_t n0 = (int64_t)blockIdx.x * GF_WAVE;
     const int rows = (int)((int64_t)a.num_envs - n0 < GF_WAVE ? (int64_t)a.num_envs - n0 : GF_WAVE);
     SynthBase b;
-    synth_tick_tile<DV, GF_WAVE>(a, GfActionArgs{}, n0, rows, s3, b);
+    synth_tick_tile<DV, GF_WAVE>(a, GfActionArgs{}, n0, rows, (int)threadIdx.x, s3, b);
 }
 
 // The action phase and the tick of a recorded step in ONE launch (gf_run_ops folds an action op directly in front of a scene op):
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kSynthTileBlock) void action_scene_tile_kernel(cons
     const int64_t n0 = (int64_t)(blockIdx.x - upkeep) * GF_WAVE;
     const int rows = (int)((int64_t)a.num_envs - n0 < GF_WAVE ? (int64_t)a.num_envs - n0 : GF_WAVE);
     SynthBase b;
-    synth_tick_tile<DV, GF_WAVE, true>(a, act, n0, rows, s3, b);
+    synth_tick_tile<DV, GF_WAVE, true>(a, act, n0, rows, (int)threadIdx.x, s3, b);
 }
 
 // Per-link outputs (orientation, velocity, position of scene link l of env n; flat index gid = n·NL + l) from the base state the
@@ -213,7 +213,7 @@ __device__ __forceinline__ void synth_tile_body(const GfSynthSceneArgs& a, const
     const int rows = (int)((int64_t)a.num_envs - n0 < TE ? (int64_t)a.num_envs - n0 : TE);
     const int tid = threadIdx.x;
     SynthBase b;
-    if constexpr (SPLIT) synth_tick_tile<DV, TE, FOLD>(a, act, n0, rows, s3, b);
+    if constexpr (SPLIT) synth_tick_tile<DV, TE, FOLD>(a, act, n0, rows, tid, s3, b);
     else if (tid < rows) synth_state_body<DV>(a, n0 + tid, b);
     if (tid < rows) {
         float* r = s_base[tid];

@@ -248,10 +248,11 @@ __device__ __forceinline__ void synth_base_tile(const GfSynthSceneArgs& a, const
 
 // The tick of tile [n0, n0 + rows) by a whole workgroup (see above): wave 0 returns the base state of env n0 + lane in `b`.
 // (`act` is read only with FOLD; `sink`: see SynthNoSink)
+// `tid` is the lane's index in the tile's work, 0 … 255: threadIdx.x in the scene kernels; role · 64 + lane in a post-physics program
+// that rotates its roles over the hardware waves (ws_rotates, gf_post_ws.h) — nothing below reads threadIdx.x itself.
 template <int DV, int TE, bool FOLD = false, class Sink = SynthNoSink>
-__device__ __forceinline__ void synth_tick_tile(const GfSynthSceneArgs& a, const GfActionArgs& act, const int64_t n0, const int rows,
+__device__ __forceinline__ void synth_tick_tile(const GfSynthSceneArgs& a, const GfActionArgs& act, const int64_t n0, const int rows, const int tid,
                                                 float (&s3)[3][TE * 3], SynthBase& b, const Sink& sink = Sink{}) {
-    const int tid = threadIdx.x;
     if (tid >= GF_WAVE) synth_dof_tile<DV, TE, FOLD>(a, act, n0, rows, tid - GF_WAVE, sink);
     else synth_base_tile<TE, FOLD>(a, act, n0, rows, tid, s3, b, sink);
 }

@@ -5,6 +5,11 @@ tools/_stamps/; no product build contains a stamp) while the env steps on the re
 
     python tools/stamp_config.py build                    # here or on the GPU box: hipcc, ~1 min (again after any change under csrc/ or include/)
     python tools/stamp_config.py run gait_8192 [steps]    # on the GPU box
+
+Up to 16 workgroups spread over the grid are stamped.  The phase table is the middle workgroup's; the placement report behind it says,
+from the HW_ID / XCC_ID registers every stamped wave records, which role ran on which SIMD of which CU and how long each role was
+busy and idle between the tick's barrier and the role barrier.  GF_ROLE_SHIFT=s (0 ... 15; this build only) rotates the roles of the
+static programs the tick covers by (tile >> s) & 3 — profiles/r33_role_balance.md.
 """
 import ctypes as C
 import os
@@ -16,6 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "genesis-forge_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "_stamps")
 LIB = os.path.join(OUT, "libgf_step_stamps.so")
+SLOTS, STAMP_WORDS = 16, 16 * 4 * 16 + 16 * 4 * 2   # kStampSlots, kStampWords of csrc/gf_post_args.h
+ROLES = ["control", "reward", "obs-rows", "obs-misc"]
 NAMES = ["args staged", "pre-barrier done", "past barrier A", "role stores", "obs starts", "tile built", "past barrier B", "end"]
 
 
@@ -39,6 +46,60 @@ def build():
     print("built", LIB)
 
 
+class Placement:
+    """Where the hardware put the waves of the stamped workgroups (GF_WHERE: HW_ID and XCC_ID of every wave, read with s_getreg) and what
+    each role did between the tick's barrier (stamp 13; a launch without a tick: its first stamp) and the role barrier (stamp 3):
+    busy = up to the end of its pre-barrier block (stamp 2), idle = from there to the barrier's far side."""
+
+    def __init__(self):
+        self.cu = {}                                   # (xcc, se, sh, cu) -> {"n": launches, "simd": [role][simd] count, "busy": [role], "idle": [role]}
+        self.wave_simd = [[0] * 4 for _ in range(4)]   # [index of the wave in its workgroup][SIMD]
+        self.role_simd = [[0] * 4 for _ in range(4)]   # [role][SIMD]
+        self.same_simd = [0] * 5                       # workgroups whose four waves sit on k distinct SIMDs
+        self.tiles = {}                                # slot -> (tile, set of CUs it ran on)
+
+    def add(self, h, slots, stride):
+        base = SLOTS * 4 * 16
+        for s in range(slots):
+            simds = set()
+            key = None
+            for role in range(4):
+                hw, x = h[base + (4 * s + role) * 2], h[base + (4 * s + role) * 2 + 1]
+                simd, cu, sh, se, xcc, wave = (hw >> 4) & 3, (hw >> 8) & 15, (hw >> 12) & 1, (hw >> 13) & 7, x & 15, (x >> 32) & 3
+                key = (xcc, se, sh, cu)
+                c = self.cu.setdefault(key, {"n": 0, "simd": [[0] * 4 for _ in range(4)], "busy": [0.0] * 4, "idle": [0.0] * 4})
+                c["simd"][role][simd] += 1
+                st = h[64 * s + 16 * role: 64 * s + 16 * role + 16]
+                start = st[13] if st[13] else st[1]
+                c["busy"][role] += (st[2] - start) / 100.0
+                c["idle"][role] += (st[3] - st[2]) / 100.0
+                self.wave_simd[wave][simd] += 1
+                self.role_simd[role][simd] += 1
+                simds.add(simd)
+            self.cu[key]["n"] += 1
+            self.same_simd[len(simds)] += 1
+            self.tiles.setdefault(s, (s * stride, set()))[1].add(key)
+
+    def report(self):
+        print("  placement of the stamped workgroups (tile: CUs it ran on, as XCC.SE.SH.CU)")
+        for s, (tile, cus) in sorted(self.tiles.items()):
+            print(f"    slot {s:2d} tile {tile:5d}: " + " ".join("%d.%d.%d.%d" % k for k in sorted(cus)))
+        print("  waves of one workgroup on 1 / 2 / 3 / 4 distinct SIMDs: " + " / ".join(str(v) for v in self.same_simd[1:]))
+        for title, m, names in (("index of the wave in its workgroup", self.wave_simd, ["wave %d" % i for i in range(4)]), ("role", self.role_simd, ROLES)):
+            print(f"  {title} x SIMD 0 1 2 3 (counts over every stamped workgroup and launch)")
+            for i in range(4):
+                print(f"    {names[i]:>9s}: " + " ".join(f"{v:7d}" for v in m[i]))
+        print("  per CU seen: launches | per role: SIMD counts 0/1/2/3, busy and idle us between the tick's barrier and the role barrier")
+        for key, c in sorted(self.cu.items()):
+            n = max(1, c["n"])
+            cells = [f"{ROLES[r]} {'/'.join(str(v) for v in c['simd'][r])} busy {c['busy'][r] / n:.2f} idle {c['idle'][r] / n:.2f}" for r in range(4)]
+            print("    %d.%d.%d.%d n=%d | " % (*key, c["n"]) + " | ".join(cells))
+        nn = sum(c["n"] for c in self.cu.values())
+        if nn:
+            print("  all stamped workgroups, mean us: " + " | ".join(
+                f"{ROLES[r]} busy {sum(c['busy'][r] for c in self.cu.values()) / nn:.2f} idle {sum(c['idle'][r] for c in self.cu.values()) / nn:.2f}" for r in range(4)))
+
+
 def run(config, steps):
     os.environ["GF_JIT"] = "off"   # a plugin is compiled against the product GfPostArgs layout
     sys.path.insert(0, os.path.join(ROOT, "genesis-forge_amd"))
@@ -55,22 +116,29 @@ def run(config, steps):
     env.seed(1)
     env.reset()
     lib = _native.get_backend().lib
-    stamps = torch.zeros(64, dtype=torch.int64, device="cuda")
+    stamps = torch.zeros(STAMP_WORDS, dtype=torch.int64, device="cuda")
     D = env.action_space.shape[0]
     acts = [torch.randn(n, D, device="cuda") for _ in range(4)]
     for i in range(20):
         env.step(acts[i % 4])
     assert env._trace is not None, "not recorded"
     C.c_void_p.in_dll(lib, "gf_debug_stamps").value = stamps.data_ptr()
+    tiles = (n + 63) // 64
+    stride = max(1, tiles // SLOTS)
+    slots = min(SLOTS, (tiles + stride - 1) // stride)
+    mid = min(SLOTS - 1, tiles // 2 // stride)
     acc = torch.zeros(4, 16, dtype=torch.float64)
+    where = Placement()
     for i in range(steps):
         env.step(acts[i % 4])
         torch.cuda.synchronize()
-        h = stamps.cpu()
-        t0 = min(int(h[16 * w + 1]) for w in range(4))
+        h = stamps.cpu().tolist()
+        t0 = min(h[64 * mid + 16 * w + 1] for w in range(4))
         for w in range(4):
             for k in range(1, 16):
-                acc[w, k] += (int(h[16 * w + k]) - t0) / 100.0
+                if h[64 * mid + 16 * w + k]:   # (a stamp this launch does not take stays 0)
+                    acc[w, k] += (h[64 * mid + 16 * w + k] - t0) / 100.0
+        where.add(h, slots, stride)
     acc /= steps
     print(f"{config}: {n} envs, fused={env._trace.post_refs is not None}, mean of {steps} launches, us since the first wave had its args (middle workgroup)")
     print("          " + " ".join(f"{s:>17s}" for s in NAMES))
@@ -83,6 +151,8 @@ def run(config, steps):
     print("  (a step folded into one launch, post_ws_kernel_tick, has no contact phase: tick of the tile done | past the tick's barrier | 0 | 0)")
     for w in range(4):
         print(f"  wave {w}: " + " ".join(f"{float(acc[w, k]):17.2f}" for k in range(12, 16)))
+    print(f"  (rows are ROLES: role = wave unless GF_ROLE_SHIFT rotates them; GF_ROLE_SHIFT={os.environ.get('GF_ROLE_SHIFT', 'unset')})")
+    where.report()
 
 
 if __name__ == "__main__":

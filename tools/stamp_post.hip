@@ -180,7 +180,12 @@ int main(int argc, char** argv) {
         if (rc == 0) time_loop("gf_post_physics_step", iters, 566.0 * Nd, [&] { chk(gf_post_physics_step(&pr, 0), "post"); });
     }
     {
-        unsigned long long* st = dalloc<unsigned long long>(64);
+        // the stamped build's buffer (csrc/gf_post_args.h): 16 slots x 4 roles x 16 clock words, then 2 placement words per (slot, role);
+        // tile = slot * stride, stride = max(1, tiles / 16) — this tool prints the middle workgroup's slot
+        constexpr int kStampWords = 16 * 4 * 16 + 16 * 4 * 2;
+        const int tiles = (N + 63) / 64, stride = tiles / 16 > 0 ? tiles / 16 : 1;
+        const int mid = tiles / 2 / stride < 16 ? tiles / 2 / stride : 15;
+        unsigned long long* st = dalloc<unsigned long long>(kStampWords);
         gf_debug_stamps = st;
       for (int variant = 1; variant <= 2; ++variant) {
         gf_set_option(GF_OPT_POST_VARIANT, variant);
@@ -189,8 +194,9 @@ int main(int argc, char** argv) {
         for (int rep = 0; rep < 3; ++rep) {
             for (int i = 0; i < 50; ++i) chk(gf_post_physics_step(&pr, 0), "post");
             CK(hipDeviceSynchronize());
-            unsigned long long h[64];
-            CK(hipMemcpy(h, st, sizeof(h), hipMemcpyDeviceToHost));
+            unsigned long long all[kStampWords];
+            CK(hipMemcpy(all, st, sizeof(all), hipMemcpyDeviceToHost));
+            const unsigned long long* h = all + 64 * mid;
             unsigned long long t0 = ~0ull;
             for (int w = 0; w < 4; ++w) t0 = h[16 * w + 1] < t0 ? h[16 * w + 1] : t0;
             printf("ws stamps (us since first wave had its args; staged | pre-barrier done | past barrier A | role stores | state writer | tile built | past barrier B | end)\n");

@@ -686,13 +686,24 @@ static char g_dyn_name[kDynMax][64];
 static std::atomic<int> g_dyn_count{0};
 static std::mutex g_dyn_mutex;
 
+constexpr size_t kPostLaunchLdsMax = 160 * 1024;   // hipDeviceProp_t::sharedMemPerBlock of an MI355X: what a plain launch takes
+static int post_omax(const GfPostArgs& a) {         // the widest single frame of the launch's observation managers
+    int omax = 0;
+    for (int m = 0; m < a.n_obs; ++m) omax = a.obs[m].width > omax ? a.obs[m].width : omax;
+    return omax;
+}
+
 static const PostProgram& select_program(const GfPostArgs& a) {
     if (g_options[GF_OPT_POST_VARIANT] >= 2) {
         for (const PostProgram& p : kBuiltin)
             if (p.matches(&a)) return p;
+        // A program compiled at run time parks one LDS row per link of every contact-force-norm item on top of the tile (two managers of
+        // 255 norm columns: 510 rows, 128 KiB): one that would ask for more than a workgroup has is passed over, and the interpreter —
+        // whose request is bounded for every descriptor pack() admits (post_lds_bytes) — runs the step.  The built-in programs' matchers
+        // pin their widths.
         const int n = g_dyn_count.load();
         for (int i = 0; i < n; ++i)
-            if (g_dyn[i].matches(&a)) return g_dyn[i];
+            if (g_dyn[i].matches(&a) && g_dyn[i].lds_bytes(post_omax(a), a.n_gait) <= kPostLaunchLdsMax) return g_dyn[i];
     }
     return interp_program(a.num_dofs);
 }
@@ -703,6 +714,22 @@ struct TickLaunch {
     const GfSynthSceneArgs* scene;
     int upkeep;
 };
+// The dynamic LDS of one launch of program `p` on the packed descriptor `a`.  post_launch() hands it to the launch as it is — no
+// attribute is set on the kernel: gfx950 takes up to kPostLaunchLdsMax per workgroup from a plain launch (measured,
+// profiles/post_capacity.md).  The largest request a descriptor pack() admits is the 32-DOF interpreter at a 255-wide frame with a
+// gait manager: sizeof(GfPostArgs) + (37 + 16 + 32 + 256) rows of 64 floats, about 89 KiB; the static_assert below holds the bound
+// for every interpreter row, tick variants included (tests/test_post_capacity.py asserts the same through gf_post_interp_lds_bytes).
+static size_t post_lds_bytes(const GfPostArgs& a, const PostProgram& p, bool tick) {
+    const int omax = post_omax(a);
+    // a folded contact phase stages the tile's slot ids in the LDS the later phases use (behind the interpreter's descriptor copy)
+    const size_t fold_lds = a.cfold.num_mgr > 0 ? fold_lds_bytes(a.cfold.num_contacts) + (p.keeps_args_in_lds ? sizeof(GfPostArgs) : 0) : 0;
+    const size_t own_lds = (tick && p.tick_lds_bytes ? p.tick_lds_bytes : p.lds_bytes)(omax, a.n_gait);
+    return own_lds > fold_lds ? own_lds : fold_lds;
+}
+static_assert(sizeof(GfPostArgs) + (size_t)(x_fields(1) + kPostMaxReward + kPostAuxRows + GF_MAX_OBS_WIDTH) * kEnvBlock * sizeof(float) <= kPostLaunchLdsMax &&
+              sizeof(GfPostArgs) + (size_t)(x_fields(1) + kPostMaxReward) * kEnvBlock * sizeof(float) + (size_t)ws_hand_floats<Interp<8, false>>() * sizeof(float) <= kPostLaunchLdsMax,
+              "the widest frame pack() admits (GF_MAX_OBS_WIDTH - 1 columns + the tile's pad column) at 32 DOF fits a workgroup's LDS");
+
 // launches the post-physics kernel of program `p`; with `tick`, its tick variant (p.tick_kernel, the caller has looked)
 static int post_launch(const GfPostArgs& packed, hipStream_t s, const PostProgram& p, const TickLaunch* tick = nullptr) {
 #ifdef GF_STAMPS
@@ -716,12 +743,7 @@ static int post_launch(const GfPostArgs& packed, hipStream_t s, const PostProgra
 #else
     const GfPostArgs& a = packed;
 #endif
-    int omax = 0;
-    for (int m = 0; m < a.n_obs; ++m) omax = a.obs[m].width > omax ? a.obs[m].width : omax;
-    // a folded contact phase stages the tile's slot ids in the LDS the later phases use (behind the interpreter's descriptor copy)
-    const size_t fold_lds = a.cfold.num_mgr > 0 ? fold_lds_bytes(a.cfold.num_contacts) + (p.keeps_args_in_lds ? sizeof(GfPostArgs) : 0) : 0;
-    const size_t own_lds = (tick ? p.tick_lds_bytes : p.lds_bytes)(omax, a.n_gait);
-    const size_t lds = own_lds > fold_lds ? own_lds : fold_lds;
+    const size_t lds = post_lds_bytes(a, p, tick != nullptr);
     const dim3 grid(env_grid(a.num_envs) + (unsigned)(tick ? tick->upkeep : 0)), block(kWsBlock);
     const void* const kernel = tick ? p.tick_kernel : p.kernel;
     void* kargs[4] = {const_cast<GfPostArgs*>(&a), nullptr, nullptr, nullptr};   // (post_ws_kernel reads the first only)
@@ -848,6 +870,23 @@ extern "C" __attribute__((visibility("default"))) int gf_post_physics_describe(c
     int n = snprintf(buf, (size_t)cap, "program %d (%s): ", p.id, p.name);
     if (n < cap) gf::describe_program(pk.a, buf + n, cap - n);
     return GF_OK;
+}
+
+// Host-only, like gf_post_physics_check: the dynamic LDS post_launch() would ask for on these descriptors (the program selected under
+// the current GF_OPT_POST_VARIANT; `tick`: its tick variant where it has one), without a folded contact phase.
+extern "C" __attribute__((visibility("default"))) int gf_post_physics_lds_bytes(const GfPostRefs* r, int tick, long* bytes_out) {
+    if (!bytes_out) return GF_E_NULL;
+    gf::Packer pk;
+    const int rc = gf::pack(r, pk);
+    if (rc) return rc;
+    *bytes_out = (long)gf::post_lds_bytes(pk.a, gf::select_program(pk.a), tick != 0);
+    return GF_OK;
+}
+
+// … and of the table interpreter's row for `num_dofs` at a single-frame width `omax` (the capacity bound: no descriptor needed)
+extern "C" __attribute__((visibility("default"))) long gf_post_interp_lds_bytes(int num_dofs, int omax, int n_gait, int tick) {
+    const gf::PostProgram& p = gf::interp_program(num_dofs);
+    return (long)(tick && p.tick_lds_bytes ? p.tick_lds_bytes : p.lds_bytes)(omax, n_gait);
 }
 
 // steps gf_run_ops ran as one launch since the library was loaded (tests: the fold took place)

@@ -830,6 +830,10 @@ class HipBackend(Backend):
         self.lib.gf_post_physics_step_contacts.argtypes = [C.POINTER(GfPostRefs), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
         self.lib.gf_post_physics_describe.restype = C.c_int
         self.lib.gf_post_physics_describe.argtypes = [C.POINTER(GfPostRefs), C.c_char_p, C.c_int]
+        self.lib.gf_post_physics_lds_bytes.restype = C.c_int
+        self.lib.gf_post_physics_lds_bytes.argtypes = [C.POINTER(GfPostRefs), C.c_int, C.POINTER(C.c_long)]
+        self.lib.gf_post_interp_lds_bytes.restype = C.c_long
+        self.lib.gf_post_interp_lds_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         self.lib.gf_post_physics_needs.restype = C.c_int
         self.lib.gf_post_physics_needs.argtypes = [C.POINTER(GfPostRefs), C.POINTER(C.c_uint32)]
         self.lib.gf_post_program_register.restype = C.c_int
@@ -964,6 +968,14 @@ class HipBackend(Backend):
         if rc != 0:
             self._raise("post_physics_describe", rc)
         return buf.value.decode()
+
+    def post_lds_bytes(self, refs, tick: bool = False) -> int:
+        """The dynamic LDS the fused launch of this combination asks for, in bytes.  Host-only."""
+        n = C.c_long(0)
+        rc = self.lib.gf_post_physics_lds_bytes(C.byref(refs), 1 if tick else 0, C.byref(n))
+        if rc != 0:
+            self._raise("post_physics_lds_bytes", rc)
+        return int(n.value)
 
     def post_needs(self, refs) -> int:
         """The GF_POST_NEEDS_* word of this combination's fused launch: which state arrays it reads.  Host-only."""

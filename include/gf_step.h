@@ -1934,6 +1934,11 @@ int gf_post_physics_step_contacts(const GfPostRefs* r, const GfContactArgs* cons
  * gf_post_physics_step would launch (id 0 = table interpreter, >0 = a static program compiled for exactly this
  * structure) and the signature in the notation of csrc/gf_post_programs.h.  Host-only, no GPU needed. */
 int gf_post_physics_describe(const GfPostRefs* r, char* buf, int cap);
+/* The dynamic LDS, in bytes, the fused launch of this combination asks for (the program gf_post_physics_describe names; tick != 0:
+ * its variant with the scene tick as prologue, where it has one; without a folded contact phase), and the same for the table
+ * interpreter of a DOF count at a single-frame observation width, which bounds every admitted descriptor.  Host-only, no GPU needed. */
+int gf_post_physics_lds_bytes(const GfPostRefs* r, int tick, long* bytes_out);
+long gf_post_interp_lds_bytes(int num_dofs, int obs_width, int num_gait, int tick);
 /* Which state arrays the fused launch of this combination reads, as packed: a word of GF_POST_NEEDS_* bits.  An array whose bit is
  * off is never read — a role that would take its rows sees zeros.  Host-only, no GPU needed. */
 enum { GF_POST_NEEDS_POS = 1, GF_POST_NEEDS_QUAT = 2, GF_POST_NEEDS_LIN = 4, GF_POST_NEEDS_ANG = 8, GF_POST_NEEDS_DOFPOS = 16,

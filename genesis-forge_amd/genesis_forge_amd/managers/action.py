@@ -10,6 +10,7 @@ What became one kernel: NaN/Inf scan, ``a*scale+offset``, ``clamp``, and — whe
 from __future__ import annotations
 
 import re
+import weakref
 from typing import Any, Callable, Optional, TypeVar
 
 import numpy as np
@@ -25,9 +26,22 @@ DofValue = Any  # scalar or {joint-name regex: value}
 
 
 def _tag(t: torch.Tensor, src) -> torch.Tensor:
-    """Provenance tag read by ObservationManager.build() to fuse getter lambdas (see observation_manager.py)."""
-    t._gf_src = src
+    """Provenance tag read by ObservationManager.build() to fuse getter lambdas (see observation_manager.py): ``(kind, owner)`` with
+    the owner held WEAKLY (``tag_source`` resolves it).  The tagged tensors are the managers' persistent buffers: a strong reference
+    would close a cycle tensor → manager → env → tensor through the tensor's attribute dict, which the garbage collector cannot see
+    while anything else (a view, a clone's base) shares the tensor — the env and every device / pinned buffer it owns were then never
+    released."""
+    t._gf_src = (src[0], weakref.ref(src[1]))
     return t
+
+
+def tag_source(t):
+    """``(kind, owner)`` of a tensor tagged by ``_tag``, or None (untagged, or the owner is gone)."""
+    src = getattr(t, "_gf_src", None)
+    if src is None:
+        return None
+    owner = src[1]()
+    return None if owner is None else (src[0], owner)
 
 
 def _ensure_dof_pattern(value):

@@ -57,6 +57,7 @@ from .. import _native as nat
 from .. import gs
 from ..spaces import Box
 from ._program import _Slots, _col, call_untraced
+from .action import tag_source
 from .base import BaseManager, LiveAttr
 from .config import ObservationConfigItem
 
@@ -197,7 +198,7 @@ class ObservationManager(BaseManager):
             cfg.build()
             assert callable(cfg.fn), f"Observation function {name} is not callable"
             value = self._call_item(name, cfg)
-            src = getattr(value, "_gf_src", None) if self._fused else None
+            src = tag_source(value) if self._fused else None
             w = int(value.shape[-1]) if value.dim() > 1 else 1
             self._plan.append((name, cfg, src, w))
             width += w

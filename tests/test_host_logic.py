@@ -389,6 +389,34 @@ def test_returned_observations_are_the_callers_own(oracle_backend, history, trac
         assert torch.equal(a, b), "an in-place edit of a returned observation leaked into a later observation"
 
 
+@pytest.mark.parametrize("trace", [False, True])
+def test_a_dropped_env_is_released(oracle_backend, trace):
+    """An env nobody holds any more goes away with its managers and buffers at the next garbage collection.  The observation
+    getters tag the managers' persistent tensors with their owner (managers/action.py:_tag); a strong reference there is a cycle
+    through a tensor's attribute dict, which the collector does not follow while the tensor is shared: every env that had ever
+    observed stayed alive, with its device buffers and its 64 pinned statistics slots, until the process ran out of mappings."""
+    import gc
+    import weakref
+
+    def run():
+        env = Go2CommandDirectionEnv(num_envs=70, max_episode_length_s=1, cmd_resample_s=0.3, contacts=True, history=2,
+                                     scene_kwargs=dict(ang_noise=0.3, seed=3))
+        env.trace_enabled = trace
+        env.build()
+        env.seed(9)
+        env.reset()
+        g = torch.Generator().manual_seed(1)
+        for _ in range(6):
+            out = env.step(torch.randn(70, 12, generator=g))
+            dict(out[4]["episode"])
+        assert (env._trace is not None) == trace
+        return [weakref.ref(x) for x in (env, env.stats, env.action_manager, env.observation_manager, env.episode_length)]
+
+    refs = run()
+    gc.collect()
+    assert [r() for r in refs] == [None] * len(refs)
+
+
 def test_static_observation_output_is_opt_in(oracle_backend):
     """output="static": the returned tensor is one of `static_slots` persistent buffers (no copy); the default is "fresh"."""
     from genesis_forge_amd.managers import ObservationManager

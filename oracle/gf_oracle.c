@@ -661,6 +661,7 @@ static int check_reward_inputs(const GfRewardArgs* a) {
     if (term && !a->terminated) return GF_E_NULL;
     if (dofs && (!a->dof_pos || !a->default_dof_pos || a->num_dofs <= 0)) return GF_E_NULL;
     if (acts && (!a->actions || !a->last_actions || a->num_dofs <= 0)) return GF_E_NULL;
+    if (quat && ((uintptr_t)a->entity.quat & 15u)) return GF_E_UNSUPPORTED; /* the library loads a quaternion as one 16-byte unit */
     return GF_OK;
 }
 

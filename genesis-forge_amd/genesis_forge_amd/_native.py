@@ -615,6 +615,49 @@ class GfActionDelayArgs(C.Structure):
                 ("slots", C.c_int32), ("head", C.c_int32), ("lag_lo", C.c_int32), ("lag_hi", C.c_int32), ("prime_all", C.c_int32)]
 
 
+# the conv depth encoder of a distillation student (learner.ConvEncoder.encode): gf_conv_encode — additive in the same way, not in ABI_STRUCTS
+GF_CONV_MAX_LAYERS = 3
+GF_CONV_MAX_CHANNELS = 64
+GF_CONV_MAX_KERNEL = 7
+GF_CONV_MAX_STRIDE = 3
+GF_CONV_MAX_LATENT = 512
+GF_CONV_MAX_TILE_ENVS = 32
+GF_CONV_LDS_BYTES = 65536
+
+
+class GfConvLayer(C.Structure):
+    _fields_ = [("weight", P), ("bias", P), ("out_channels", C.c_int32), ("kernel", C.c_int32), ("stride", C.c_int32), ("padding", C.c_int32)]
+
+
+class GfConvEncodeArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("image", P), ("image_stride", C.c_int64), ("out", P), ("num_inputs", C.c_int32),
+                ("num_layers", C.c_int32), ("inputs", GfMlpSegment * GF_MLP_MAX_INPUTS), ("in_mean", P), ("in_std", P), ("in_eps", C.c_float),
+                ("channels", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("layers", GfConvLayer * GF_CONV_MAX_LAYERS),
+                ("head_weight", P), ("head_bias", P), ("latent_dim", C.c_int32), ("_pad", C.c_int32)]
+
+
+def conv_plan(args: "GfConvEncodeArgs") -> Optional[tuple]:
+    """gf_conv_plan: ``(tile_envs, lds_bytes, flat)`` of the launch ``gf_conv_encode`` would make for the shapes in ``args`` (no pointer
+    is looked at), or None where it refuses them.  Host-only: the library loads without a GPU."""
+    global _plan_lib
+    if _plan_lib is None:
+        path = lib_path()
+        if not os.path.exists(path):
+            raise GfError(f"{path} not found: build the HIP library first (make -C genesis-forge_amd/csrc)")
+        _plan_lib = C.CDLL(path)
+        if _plan_lib.gf_conv_encode_sizeof() != C.sizeof(GfConvEncodeArgs):
+            raise GfError(f"ABI drift: sizeof(GfConvEncodeArgs) is {_plan_lib.gf_conv_encode_sizeof()} in the library, {C.sizeof(GfConvEncodeArgs)} in the binding")
+        _plan_lib.gf_conv_plan.restype = C.c_int
+        _plan_lib.gf_conv_plan.argtypes = [C.POINTER(GfConvEncodeArgs), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    t, lds, flat = C.c_int(0), C.c_int(0), C.c_int(0)
+    if _plan_lib.gf_conv_plan(C.byref(args), C.byref(t), C.byref(lds), C.byref(flat)) != 0:
+        return None
+    return t.value, lds.value, flat.value
+
+
+_plan_lib = None
+
+
 # the newest frame of a history observation into a frame-major rollout storage (learner.RolloutStorage(history="frames")):
 # gf_rollout_frame_write, issued by the storage behind the step's rollout_write — not a phase, not in ABI_STRUCTS either
 GF_SIZEOF_ROLLOUT_FRAME = 30
@@ -902,6 +945,12 @@ class HipBackend(Backend):
             raise GfError(f"ABI drift: sizeof(GfActionDelayArgs) is {n} in the library, {C.sizeof(GfActionDelayArgs)} in the binding")
         self.lib.gf_action_delay.restype = C.c_int
         self.lib.gf_action_delay.argtypes = [C.POINTER(GfActionDelayArgs), C.c_void_p]
+        # the conv depth encoder (learner.ConvEncoder): additive in the same way
+        n = self.lib.gf_conv_encode_sizeof()
+        if n != C.sizeof(GfConvEncodeArgs):
+            raise GfError(f"ABI drift: sizeof(GfConvEncodeArgs) is {n} in the library, {C.sizeof(GfConvEncodeArgs)} in the binding")
+        self.lib.gf_conv_encode.restype = C.c_int
+        self.lib.gf_conv_encode.argtypes = [C.POINTER(GfConvEncodeArgs), C.c_void_p]
         n = self.lib.gf_sizeof(GF_SIZEOF_RNN_CELL)
         if n != C.sizeof(GfRnnCell):
             raise GfError(f"ABI drift: sizeof(GfRnnCell) is {n} in the library, {C.sizeof(GfRnnCell)} in the binding")
@@ -1092,6 +1141,7 @@ _LEARNER_ENTRIES = {
     "mirror_loss": "learner.PPO.update with a symmetry_cfg",
     "mlp_act": "learner.PolicyForward, learner.RolloutStorage.act_policy",
     "mlp_distill_act": "learner.DistillForward.act, learner.RolloutStorage.act_distill",
+    "conv_encode": "learner.ConvEncoder.encode, learner.DistillForward.act with a student_encoder",
     "bc_loss": "learner.Distillation.update",
     "rnd_reward": "learner.RndForward.reward, learner.RolloutStorage.intrinsic_reward",
     "mlp_recurrent_act": "learner.RecurrentForward",

@@ -650,7 +650,10 @@ class RolloutStorage:
         """``act_distill`` and ``act_distill_recurrent`` behind their refusals: the rows, ``forward.act`` with them as its second
         destinations and — for a forward with memories, at row 0 — ``rnn_start["student"]`` as what the launch saves the state into."""
         n, dev, A = self.env.num_envs, self.device, forward.num_actions
-        _segments(obs, "obs", n, dev, forward._reader("student"))   # (the storage's env count and device; act() checks the rest)
+        if getattr(forward, "_encoder", None) is None:
+            _segments(obs, "obs", n, dev, forward._reader("student"))   # (the storage's env count and device; act() checks the rest)
+        else:
+            forward.policy.split_student_obs(obs, n, dev)
         self._ensure_distill_rows(A)
         save = None
         if forward._memory and self._act_row() == 0:
@@ -1457,6 +1460,167 @@ def _mlp(sizes) -> torch.nn.Sequential:
     return torch.nn.Sequential(*layers)
 
 
+class ConvPlan(NamedTuple):
+    """How ``gf_conv_encode`` tiles an encoder: ``tile_envs`` envs per workgroup, the launch's LDS bytes, the head's input width."""
+    tile_envs: int
+    lds_bytes: int
+    flat: int
+
+
+class _ConvScratch:
+    """The native descriptor of a :class:`ConvEncoder`'s ``gf_conv_encode`` calls and what its last launch reads: call-to-call
+    scratch, so a copy or a pickle of the module starts with a fresh one (as ``_NormScratch``)."""
+
+    def __init__(self):
+        self.args = nat.GfConvEncodeArgs()
+        self.keep = None
+
+    def __deepcopy__(self, memo):
+        return _ConvScratch()
+
+    def __reduce__(self):
+        return (_ConvScratch, ())
+
+
+def _strided_rows(x, name: str, n: Optional[int], dev, width: Optional[int] = None) -> None:
+    """What ``gf_conv_encode`` reads in place: a float32 ``[n, w]`` tensor with unit column stride and rows at least ``w`` apart —
+    contiguous, or the leading / trailing columns of a wider block.  The launch follows at once, so any such view is taken."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError(f"{name} must be a [N, W] tensor")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, not {x.dtype}")
+    if (n is not None and int(x.shape[0]) != n) or (width is not None and int(x.shape[1]) != width):
+        raise ValueError(f"{name} has shape {tuple(x.shape)}; expected ({'N' if n is None else n}, {'W' if width is None else width})")
+    if dev is not None and x.device != dev:
+        raise ValueError(f"{name} lives on {x.device}, not on {dev}")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise ValueError(f"{name} must have unit column stride and rows at least its width apart")
+
+
+class ConvEncoder(torch.nn.Module):
+    """The depth encoder in front of a distillation student: ``conv`` — an ``nn.Sequential`` of one to three ``Conv2d`` (square kernel,
+    stride, zero padding; no dilation, groups, pooling or norm layer) each followed by ``ELU`` — then ``flatten`` in torch's
+    ``[C, H, W]`` order and ``head = Linear(flat, latent_dim)`` with no activation behind it: the latent feeds the student's first
+    ``Linear`` like any observation.  ``kernel_size`` / ``stride`` / ``padding``: one int for every layer, or one per layer.
+    Parameters are plain torch parameters in torch's layouts; the kernel reads them in place.
+
+    ``forward(image)`` — ``[n, C·H·W]`` or ``[n, C, H, W]`` — is the torch path, differentiable: what the update trains through.
+    ``encode(image, obs=None, normalizer=None, out=None)`` is the collection step's path, ONE ``gf_conv_encode`` launch under
+    ``no_grad``: ``out[n] = [normalizer(obs[n]) | forward(image[n])]``, the student MLP's complete input row.  ``plan`` is the
+    launch's tile (:class:`ConvPlan`).
+
+    Limits, checked here (``ValueError`` naming the argument): 1 to 3 conv layers, ``C`` and ``channels[i]`` <= 64, kernels 1 to 7,
+    strides 1 to 3, ``padding < kernel``, every layer's output at least 1 x 1, ``latent_dim`` 1 to 512, and the activations of one
+    env must fit the kernel's LDS tile."""
+
+    def __init__(self, image_shape, channels: Sequence[int] = (16, 32), kernel_size=3, stride=1, padding=0, latent_dim: int = 64):
+        super().__init__()
+        who = "ConvEncoder"
+        try:
+            shape = tuple(int(x) for x in image_shape)
+        except TypeError:
+            shape = ()
+        if len(shape) != 3 or min(shape) < 1 or shape[0] > nat.GF_CONV_MAX_CHANNELS:
+            raise ValueError(f"{who}: image_shape={image_shape!r} must be (C, H, W) with 1 <= C <= {nat.GF_CONV_MAX_CHANNELS} and H, W >= 1")
+        channels = tuple(int(c) for c in channels)
+        n = len(channels)
+        if not 1 <= n <= nat.GF_CONV_MAX_LAYERS or any(not 1 <= c <= nat.GF_CONV_MAX_CHANNELS for c in channels):
+            raise ValueError(f"{who}: channels={channels!r} must be 1 to {nat.GF_CONV_MAX_LAYERS} conv layers of 1 to {nat.GF_CONV_MAX_CHANNELS} channels")
+
+        def per_layer(v, name):
+            v = tuple(int(x) for x in v) if isinstance(v, (list, tuple)) else (int(v),) * n
+            if len(v) != n:
+                raise ValueError(f"{who}: {name} has {len(v)} entries for {n} conv layers")
+            return v
+
+        ks, ss, ps = per_layer(kernel_size, "kernel_size"), per_layer(stride, "stride"), per_layer(padding, "padding")
+        if any(not 1 <= k <= nat.GF_CONV_MAX_KERNEL for k in ks):
+            raise ValueError(f"{who}: kernel_size={kernel_size!r} must be 1 to {nat.GF_CONV_MAX_KERNEL} (square kernels)")
+        if any(not 1 <= s <= nat.GF_CONV_MAX_STRIDE for s in ss):
+            raise ValueError(f"{who}: stride={stride!r} must be 1 to {nat.GF_CONV_MAX_STRIDE}")
+        if any(not 0 <= p < k for p, k in zip(ps, ks)):
+            raise ValueError(f"{who}: padding={padding!r} must be >= 0 and smaller than the layer's kernel")
+        if not 1 <= int(latent_dim) <= nat.GF_CONV_MAX_LATENT:
+            raise ValueError(f"{who}: latent_dim={latent_dim!r} must be 1 to {nat.GF_CONV_MAX_LATENT}")
+        c, h, w = shape
+        mods = []
+        for i, (co, k, s, p) in enumerate(zip(channels, ks, ss, ps)):
+            if h + 2 * p < k or w + 2 * p < k:
+                raise ValueError(f"{who}: kernel_size={k} of conv layer {i} is larger than its padded {h} x {w} input: the output would be empty")
+            mods += [torch.nn.Conv2d(c, co, k, stride=s, padding=p), torch.nn.ELU()]
+            c, h, w = co, (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+        self.image_shape, self.image_size, self.latent_dim = shape, shape[0] * shape[1] * shape[2], int(latent_dim)
+        self.conv = torch.nn.Sequential(*mods)
+        self.flatten = torch.nn.Flatten(1)
+        self.head = torch.nn.Linear(c * h * w, self.latent_dim)
+        plan = nat.conv_plan(self._shapes(nat.GfConvEncodeArgs()))
+        if plan is None:
+            raise ValueError(f"{who}: image_shape={shape!r} with channels={channels!r}: the activations of one env do not fit the kernel's "
+                             f"{nat.GF_CONV_LDS_BYTES}-byte LDS tile")
+        self.plan = ConvPlan(*plan)
+        self._scratch = _ConvScratch()
+
+    def _shapes(self, a):
+        """The shape fields of a descriptor (what ``gf_conv_plan`` reads)."""
+        convs = self.conv[0::2]
+        a.num_layers, a.latent_dim = len(convs), self.latent_dim
+        a.channels, a.height, a.width = self.image_shape
+        for lay, m in zip(a.layers, convs):
+            lay.out_channels, lay.kernel, lay.stride, lay.padding = m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0]
+        return a
+
+    def forward(self, image: torch.Tensor) -> torch.Tensor:
+        return self.head(self.flatten(self.conv(image.reshape(-1, *self.image_shape))))
+
+    def encode(self, image: torch.Tensor, obs=None, normalizer=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``out[n] = [normalizer(obs[n]) | forward(image[n])]`` in ONE ``gf_conv_encode`` launch, under ``no_grad``.  ``image``:
+        ``[N, C·H·W]`` float32 rows with unit column stride — a tensor of its own (``[N, C, H, W]`` contiguous too) or the trailing
+        columns of a wider block; ``obs``: ``None``, a ``[N, W]`` tensor or up to four side by side (under the same rule);
+        ``normalizer``: ``None`` / ``nn.Identity`` or the :class:`EmpiricalNormalization` of those columns; ``out``: a contiguous
+        ``[N, W1 + latent_dim]`` tensor (a fresh one if None).  A backend without the entry point raises: there is no other path."""
+        S, L = self.image_size, self.latent_dim
+        if isinstance(image, torch.Tensor) and image.dim() == 4 and image.is_contiguous():
+            image = image.reshape(image.shape[0], -1)
+        dev = self.head.weight.device
+        _strided_rows(image, "image", None, dev, S)
+        n = int(image.shape[0])
+        parts = () if obs is None else (obs,) if isinstance(obs, torch.Tensor) else tuple(obs)
+        if len(parts) > nat.GF_MLP_MAX_INPUTS:
+            raise ValueError(f"obs must be a tensor or a sequence of at most {nat.GF_MLP_MAX_INPUTS} tensors")
+        for i, x in enumerate(parts):
+            _strided_rows(x, f"obs[{i}]" if len(parts) > 1 else "obs", n, dev)
+        W1 = sum(int(x.shape[1]) for x in parts)
+        norm = _as_normalizer(normalizer, W1, "ConvEncoder.encode: normalizer") if W1 else None
+        if norm is not None and norm._mean.device != dev:
+            raise ValueError(f"the encoder lives on {dev}, the normaliser on {norm._mean.device}")
+        if out is None:
+            out = torch.empty((n, W1 + L), device=dev, dtype=torch.float32)
+        else:
+            _check_f32(out, "out", {(n, W1 + L)}, dev)
+        fn = getattr(nat.get_backend(), "conv_encode", None)
+        if fn is None:
+            raise RuntimeError("ConvEncoder.encode is the gf_conv_encode launch: this backend has no such entry (forward() is the torch path)")
+        a = self._shapes(self._scratch.args)
+        a.num_envs, a.image, a.out = n, image.data_ptr(), out.data_ptr()
+        a.image_stride = 0 if n < 2 or image.stride(0) == S else image.stride(0)
+        a.num_inputs = len(parts)
+        for seg, x in zip(a.inputs, parts):
+            seg.rows, seg.width, seg.row_stride = x.data_ptr(), x.shape[1], 0 if n < 2 or x.stride(0) == x.shape[1] else x.stride(0)
+        if norm is None:
+            a.in_mean = a.in_std = None
+        else:
+            a.in_mean, a.in_std, a.in_eps = norm._mean.data_ptr(), norm._std.data_ptr(), norm.eps
+        for lay, m in zip(a.layers, self.conv[0::2]):
+            for p in (m.weight, m.bias):
+                if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
+                    raise ValueError("ConvEncoder.encode: the conv parameters must be contiguous float32 on one device")
+            lay.weight, lay.bias = m.weight.data_ptr(), m.bias.data_ptr()
+        a.head_weight, a.head_bias = self.head.weight.data_ptr(), self.head.bias.data_ptr()
+        self._scratch.keep = (image, parts, out, norm)
+        fn(a)
+        return out
+
+
 class EmpiricalDiscountedVariationNormalization(torch.nn.Module):
     """rsl_rl's ``EmpiricalDiscountedVariationNormalization``: a reward is divided by the running std of a per-env discounted sum of
     the rewards seen so far.  ``emp_norm`` is an :class:`EmpiricalNormalization` of width 1 (its buffers are the state dict);
@@ -1603,6 +1767,9 @@ def _policy_cfg(train_cfg: dict, who: str, keys: tuple, class_name: str) -> dict
     """``train_cfg["policy"]`` for ``who.from_train_cfg``; ``ValueError`` naming the key for an unknown one, another activation than
     ``"elu"``, another ``noise_std_type`` than ``"scalar"`` / ``"log"`` or another ``class_name`` than the one given."""
     pol = dict(train_cfg.get("policy", {}))
+    if "student_encoder" in pol and "student_encoder" not in keys:
+        raise ValueError(f"{who}: policy.student_encoder is not supported: a ConvEncoder goes in front of a StudentTeacherMLP's student only "
+                         "(not a recurrent student, not an actor-critic)")
     bad = sorted(k for k in pol if k not in keys)
     if bad:
         raise ValueError(f"{who}: unsupported policy keys {bad}")
@@ -1811,6 +1978,21 @@ _STUDENT_TEACHER_KEYS = ("class_name", "activation", "student_hidden_dims", "tea
                          "student_obs_normalization", "teacher_obs_normalization")
 
 
+_STUDENT_ENCODER_KEYS = ("image_shape", "channels", "kernel_size", "stride", "padding", "latent_dim")
+
+
+def _student_encoder(pol: dict) -> Optional["ConvEncoder"]:
+    """The :class:`ConvEncoder` of ``policy.student_encoder`` (``_STUDENT_ENCODER_KEYS``; ``image_shape`` is required), or None
+    without the key; an unknown key raises ``ValueError``."""
+    cfg = pol.get("student_encoder")
+    if cfg is None:
+        return None
+    bad = sorted(k for k in cfg if k not in _STUDENT_ENCODER_KEYS)
+    if bad or "image_shape" not in cfg:
+        raise ValueError(f"StudentTeacherMLP: policy.student_encoder needs image_shape and takes {list(_STUDENT_ENCODER_KEYS)}; unsupported keys {bad}")
+    return ConvEncoder(**cfg)
+
+
 def _student_teacher_kwargs(pol: dict) -> dict:
     """The constructor keywords ``StudentTeacherMLP.from_train_cfg`` reads from a checked ``train_cfg["policy"]`` (``_STUDENT_TEACHER_KEYS``)."""
     return dict(student_hidden_dims=tuple(pol.get("student_hidden_dims", (256, 256, 256))),
@@ -1855,6 +2037,8 @@ class _StudentTeacher(_ActionStd, torch.nn.Module):
         frozen with the teacher."""
         norm = self.student_obs_normalizer
         if isinstance(norm, EmpiricalNormalization) and norm.training:
+            if getattr(self, "student_encoder", None) is not None:   # the 1-D columns only; a slice of a wider block is copied
+                obs = tuple(x if _rows_ok(x) else x.contiguous() for x in self.split_student_obs(obs)[0])
             _update_normalizers([(norm, _segments(obs, "obs", None, norm._mean.device, norm_width=norm.width))], self._scratch.args)
 
     def train(self, mode: bool = True):
@@ -1902,14 +2086,22 @@ class StudentTeacherMLP(_StudentTeacher):
 
     def __init__(self, num_student_obs: int, num_teacher_obs: int, num_actions: int, student_hidden_dims: Sequence[int] = (256, 256, 256),
                  teacher_hidden_dims: Sequence[int] = (256, 256, 256), init_noise_std: float = 0.1, student_obs_normalization: bool = False,
-                 teacher_obs_normalization: bool = False, noise_std_type: str = "scalar"):
+                 teacher_obs_normalization: bool = False, noise_std_type: str = "scalar", student_encoder: Optional["ConvEncoder"] = None):
         super().__init__()
         self._set_noise_std_type("StudentTeacherMLP", noise_std_type)
         self.loaded_teacher = False
+        if student_encoder is not None and not isinstance(student_encoder, ConvEncoder):
+            raise ValueError(f"StudentTeacherMLP: student_encoder must be a ConvEncoder, not {type(student_encoder).__name__}")
+        if int(num_student_obs) < (0 if student_encoder is not None else 1):
+            raise ValueError(f"StudentTeacherMLP: num_student_obs={num_student_obs} (it counts the 1-D columns; 0 only with a student_encoder)")
+        self.num_student_obs = int(num_student_obs)
+        self.student_encoder = student_encoder
+        latent = 0 if student_encoder is None else student_encoder.latent_dim
 
-        self.student = _mlp([int(num_student_obs), *student_hidden_dims, int(num_actions)])
+        self.student = _mlp([self.num_student_obs + latent, *student_hidden_dims, int(num_actions)])
         self.teacher = _mlp([int(num_teacher_obs), *teacher_hidden_dims, int(num_actions)])
-        self._finish(num_student_obs, num_teacher_obs, num_actions, init_noise_std, student_obs_normalization, teacher_obs_normalization)
+        self._finish(num_student_obs, num_teacher_obs, num_actions, init_noise_std, student_obs_normalization and self.num_student_obs > 0,
+                     teacher_obs_normalization)
 
     @classmethod
     def from_train_cfg(cls, train_cfg: dict, num_student_obs: int, num_teacher_obs: int, num_actions: int) -> "StudentTeacherMLP":
@@ -1917,12 +2109,41 @@ class StudentTeacherMLP(_StudentTeacher):
         ``noise_std_type`` / ``student_obs_normalization`` / ``teacher_obs_normalization``.  Anything that cannot be honoured — an
         unknown policy key, another activation than ``"elu"``, another class name than ``"StudentTeacher"`` — raises ``ValueError``
         naming the key."""
-        pol = _policy_cfg(train_cfg, "StudentTeacherMLP", _STUDENT_TEACHER_KEYS, "StudentTeacher")
-        return cls(num_student_obs, num_teacher_obs, num_actions, **_student_teacher_kwargs(pol))
+        pol = _policy_cfg(train_cfg, "StudentTeacherMLP", _STUDENT_TEACHER_KEYS + ("student_encoder",), "StudentTeacher")
+        return cls(num_student_obs, num_teacher_obs, num_actions, student_encoder=_student_encoder(pol), **_student_teacher_kwargs(pol))
+
+    def split_student_obs(self, obs, n: Optional[int] = None, dev=None) -> tuple:
+        """A student observation of a policy with a ``student_encoder`` — one ``[N, num_student_obs + C·H·W]`` tensor or up to four
+        segments side by side — as ``(the 1-D segments, the image)``: views, nothing is copied.  The image is the trailing ``C·H·W``
+        columns and must lie whole inside the last segment: ``ValueError`` otherwise."""
+        S = self.student_encoder.image_size
+        parts = (obs,) if isinstance(obs, torch.Tensor) else tuple(obs) if isinstance(obs, (list, tuple)) else ()
+        if not parts or len(parts) > nat.GF_MLP_MAX_INPUTS:
+            raise ValueError(f"obs must be a tensor or a sequence of 1 to {nat.GF_MLP_MAX_INPUTS} tensors")
+        for i, x in enumerate(parts):
+            _strided_rows(x, f"obs[{i}]" if len(parts) > 1 else "obs", n, dev)
+            n = int(x.shape[0])
+        widths = [int(x.shape[1]) for x in parts]
+        if sum(widths) != self.num_student_obs + S:
+            raise ValueError(f"obs is {' + '.join(map(str, widths))} wide; the student reads {self.num_student_obs} columns and a {S}-column image")
+        if widths[-1] < S:
+            raise ValueError(f"the image ({S} columns) must lie whole inside the last segment of obs, which is {widths[-1]} wide: it is split "
+                             "across segments")
+        last = parts[-1]
+        rest = () if widths[-1] == S else (last[:, :widths[-1] - S],)
+        return parts[:-1] + rest, last[:, widths[-1] - S:]
 
     def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
-        """The student on its normalised input (rsl_rl's ``act_inference``)."""
-        return self.student(self.student_obs_normalizer(obs))
+        """The student on its normalised input (rsl_rl's ``act_inference``).  With a ``student_encoder``: the torch composition
+        ``student(cat(normaliser(obs1d), encoder(image)))``, differentiable."""
+        enc = self.student_encoder
+        if enc is None:
+            return self.student(self.student_obs_normalizer(obs))
+        W1 = self.num_student_obs
+        if obs.shape[-1] != W1 + enc.image_size:
+            raise ValueError(f"obs is {obs.shape[-1]} wide; the student reads {W1} columns and a {enc.image_size}-column image")
+        latent = enc(obs[..., W1:])
+        return self.student(torch.cat((self.student_obs_normalizer(obs[..., :W1]), latent), dim=-1) if W1 else latent)
 
     def evaluate(self, teacher_obs: torch.Tensor) -> torch.Tensor:
         """The teacher's actions, under ``no_grad``."""
@@ -1961,9 +2182,11 @@ class StudentTeacherRecurrent(_StudentTeacher):
     def __init__(self, num_student_obs: int, num_teacher_obs: int, num_actions: int, student_hidden_dims: Sequence[int] = (256, 256, 256),
                  teacher_hidden_dims: Sequence[int] = (256, 256, 256), init_noise_std: float = 0.1, student_obs_normalization: bool = False,
                  teacher_obs_normalization: bool = False, noise_std_type: str = "scalar", rnn_type: str = "lstm", rnn_hidden_dim: int = 256,
-                 rnn_num_layers: int = 1, teacher_recurrent: bool = False):
+                 rnn_num_layers: int = 1, teacher_recurrent: bool = False, student_encoder=None):
         super().__init__()
         who = "StudentTeacherRecurrent"
+        if student_encoder is not None:
+            raise ValueError(f"{who}: student_encoder is not supported: a ConvEncoder goes in front of a StudentTeacherMLP's student only")
         self._set_noise_std_type(who, noise_std_type)
         _check_rnn_args(who, rnn_type, rnn_hidden_dim, rnn_num_layers)
         self.rnn_type, self.rnn_hidden_dim, self.teacher_recurrent = rnn_type, int(rnn_hidden_dim), bool(teacher_recurrent)
@@ -2444,12 +2667,50 @@ class DistillForward(_DistillAct, _MlpForward):
     up at every call.  Both nets are required and must have the same output width; ``policy.std`` (``log_std``) must be ``[A]``.
 
     ``mean(obs)``: the student's mean — play-time inference, one ``gf_mlp_act`` launch.  ``act(obs, teacher_obs)``: the collection
-    step, ONE ``gf_mlp_distill_act`` launch; ``RolloutStorage.act_distill`` calls it with its rows as the second destinations."""
+    step, ONE ``gf_mlp_distill_act`` launch; ``RolloutStorage.act_distill`` calls it with its rows as the second destinations.
+
+    With ``policy.student_encoder`` (a :class:`ConvEncoder`; the student's observation is ``[1-D columns | image]``, one tensor or
+    segments with the image whole inside the last one) a step is TWO launches: ``gf_conv_encode`` writes the normalised 1-D columns
+    and the image's latent into a persistent ``[N, W1 + L]`` row buffer, then the unchanged ``gf_mlp_distill_act`` reads that buffer
+    as the student's one segment, with no normaliser.  On a backend without the entry points the row is the torch composition."""
 
     _ENTRY = "mlp_distill_act"
 
     def __init__(self, policy):
+        self._encoder = getattr(policy, "student_encoder", None)
+        if self._encoder is not None and not (isinstance(self._encoder, ConvEncoder) and hasattr(policy, "split_student_obs")):
+            raise ValueError("DistillForward: policy.student_encoder must be a ConvEncoder on a StudentTeacherMLP")
+        self._row = None
         self._setup_distill(policy, "DistillForward")
+        if self._encoder is not None:   # (refuses a normaliser that does not cover exactly the 1-D columns)
+            _as_normalizer(getattr(policy, "student_obs_normalizer", None), policy.num_student_obs, "DistillForward: policy.student_obs_normalizer")
+
+    def _normalizer(self, name: str):
+        if name == "student" and self._encoder is not None:
+            return None   # (the encoder's launch normalises the 1-D columns as it writes the row)
+        return super()._normalizer(name)
+
+    def _student_row(self, obs, n: Optional[int] = None, dev=None) -> torch.Tensor:
+        """The student MLP's input rows ``[N, W1 + L]`` for ``obs``: ``gf_conv_encode`` into the persistent buffer."""
+        policy, enc = self.policy, self._encoder
+        parts, image = policy.split_student_obs(obs, n, dev)
+        n, W = int(image.shape[0]), policy.num_student_obs + enc.latent_dim
+        norm = _as_normalizer(policy.student_obs_normalizer, policy.num_student_obs, "DistillForward: policy.student_obs_normalizer") if parts else None
+        if getattr(nat.get_backend(), "conv_encode", None) is None:   # (the test-only oracle backend)
+            with torch.no_grad():
+                latent = enc(image)
+                return torch.cat((policy.student_obs_normalizer(_cat(parts)), latent), dim=-1) if parts else latent
+        if self._row is None or tuple(self._row.shape) != (n, W) or self._row.device != image.device:
+            self._row = torch.empty((n, W), device=image.device, dtype=torch.float32)
+        return enc.encode(image, parts or None, norm, out=self._row)
+
+    def mean(self, obs) -> torch.Tensor:
+        return super().mean(obs if self._encoder is None else self._student_row(obs))
+
+    def act(self, obs, teacher_obs=None, *args, **kwargs):
+        if self._encoder is not None:
+            obs, teacher_obs = self._student_row(obs), (obs if teacher_obs is None else teacher_obs)
+        return super().act(obs, teacher_obs, *args, **kwargs)
 
 
 class RecurrentDistillForward(_DistillAct, RecurrentForward):
@@ -2468,6 +2729,8 @@ class RecurrentDistillForward(_DistillAct, RecurrentForward):
     _ENTRY = "mlp_recurrent_distill_act"
 
     def __init__(self, policy, own_state: bool = False):
+        if getattr(policy, "student_encoder", None) is not None:
+            raise ValueError("RecurrentDistillForward: policy.student_encoder is not supported: a ConvEncoder goes in front of a feed-forward student only")
         memories = (("student", "memory_s"), ("teacher", "memory_t")) if getattr(policy, "memory_t", None) is not None else (("student", "memory_s"),)
         self._setup_distill(policy, "RecurrentDistillForward", memories, own_state)
 
@@ -2878,6 +3141,8 @@ class PPO(_FlatAdam):
 
     def __init__(self, policy: "ActorCriticMLP", storage: RolloutStorage, grad_sync: Optional[GradientAllReduce] = None, **algorithm):
         algorithm = dict(algorithm)
+        if getattr(policy, "student_encoder", None) is not None:
+            raise ValueError("PPO: a policy with a student_encoder is not supported: a ConvEncoder belongs to a distillation student (Distillation)")
         algorithm.pop("class_name", None)
         symmetry_cfg = algorithm.pop("symmetry_cfg", None)
         rnd_cfg = algorithm.pop("rnd_cfg", None)
@@ -3409,7 +3674,11 @@ class Distillation(_FlatAdam):
         self.recurrent = bool(getattr(policy, "is_recurrent", False))
         if self.recurrent and not isinstance(getattr(getattr(policy, "memory_s", None), "rnn", None), (torch.nn.LSTM, torch.nn.GRU)):
             raise ValueError("Distillation: a recurrent policy needs memory_s.rnn, an nn.LSTM or nn.GRU (StudentTeacherRecurrent)")
-        trained = list(policy.student.parameters()) + (list(policy.memory_s.parameters()) if self.recurrent else [])
+        encoder = getattr(policy, "student_encoder", None)
+        if encoder is not None and self.recurrent:
+            raise ValueError("Distillation: a student_encoder in front of a recurrent student is not supported")
+        trained = (list(policy.student.parameters()) + (list(policy.memory_s.parameters()) if self.recurrent else []) +
+                   (list(encoder.parameters()) if encoder is not None else []))
         self.grad_sync = GradientAllReduce(trained)   # (one rank: a bucket, never a collective)
         self._init_flat(float(cfg["learning_rate"]))
         dev = self.params.device

@@ -435,6 +435,11 @@ class DistillationRunner(OnPolicyRunner):
     then ``Distillation.update()``.  The log record carries ``"behavior"`` in place of the three PPO losses.
     ``get_inference_policy()`` is the student's mean.
 
+    ``policy.student_encoder = {image_shape, channels, kernel_size, stride, padding, latent_dim}`` puts a
+    :class:`~.learner.ConvEncoder` in front of the student: the ``"policy"`` group is then ``[1-D columns | image]`` with the image
+    as its trailing ``C·H·W`` columns (whole inside the group's last manager), ``forward="hip"`` collects with ``gf_conv_encode`` +
+    ``gf_mlp_distill_act``, ``"torch"`` with the module's composition, and the update trains the encoder with the student.
+
     ``policy.class_name = "StudentTeacherRecurrent"`` (:class:`~.learner.StudentTeacherRecurrent`: ``policy.rnn_type`` /
     ``rnn_hidden_dim`` / ``rnn_num_layers`` / ``teacher_recurrent``; a recurrent PPO checkpoint as the teacher needs
     ``teacher_recurrent=True``): ``forward="hip"`` collects with ``store.act_distill_recurrent`` — ONE
@@ -451,7 +456,17 @@ class DistillationRunner(OnPolicyRunner):
         width = lambda group: sum(store._widths[m] for m in store.obs_groups[group])
         name = dict(train_cfg.get("policy", {})).get("class_name", "StudentTeacher")
         cls = StudentTeacherRecurrent if name == "StudentTeacherRecurrent" else StudentTeacherMLP   # (any other name: from_train_cfg refuses it)
-        policy = cls.from_train_cfg(train_cfg, width("policy"), width("teacher"), base.action_space.shape[0]).to(self.device)
+        student_w = width("policy")
+        enc_cfg = dict(train_cfg.get("policy", {})).get("student_encoder")
+        if enc_cfg is not None and cls is StudentTeacherMLP:   # the policy group is [1-D columns | image]: num_student_obs counts the former
+            image = 1
+            for d in tuple(enc_cfg.get("image_shape", ())):
+                image *= int(d)
+            if student_w < image:
+                raise ValueError(f"DistillationRunner: policy.student_encoder.image_shape={enc_cfg.get('image_shape')!r} is {image} columns; "
+                                 f"the 'policy' observation group is only {student_w} wide")
+            student_w -= image
+        policy = cls.from_train_cfg(train_cfg, student_w, width("teacher"), base.action_space.shape[0]).to(self.device)
         self.alg = Distillation(policy, store, **train_cfg["algorithm"])
         self._recurrent = bool(getattr(policy, "is_recurrent", False))
         if self.forward != "hip":

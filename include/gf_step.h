@@ -1788,7 +1788,63 @@ typedef struct GfActionDelayArgs {
 } GfActionDelayArgs;
 
 /* ------------------------------------------------------------------------------------------
- * Entry points.  `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream).
+ * gf_conv_encode: the convolutional depth encoder in front of a distillation student (learner.ConvEncoder) in ONE launch.  For
+ * every env n
+ *     out[n, 0 : W1]      = the 1-D observation columns (up to GF_MLP_MAX_INPUTS segments side by side, as gf_mlp_act reads them),
+ *                           through the normaliser where in_mean is given: (v - mean[k]) / (std[k] + eps), gf_mlp_act's staging arithmetic
+ *     out[n, W1 : W1 + L] = head(flatten(conv(image[n])))
+ * conv = 1 … GF_CONV_MAX_LAYERS of Conv2d (square kernel, stride, zero padding; no dilation, groups, pooling or norm) each followed by
+ * ELU; flatten in torch's [C, H, W] order; head = Linear(flat, L) without an activation.  Weights are torch's parameters read in place:
+ * Conv2d.weight [Cout, Cin, k, k] as a row-major [Cout, K] matrix, K = Cin·k·k.  `out` is the complete input row of the student MLP:
+ * the gf_mlp_distill_act launch that follows reads it as one segment with no normaliser.
+ * A workgroup owns a tile of T envs (gf_conv_plan: the largest T <= 32 whose activations fit in GF_CONV_LDS_BYTES); the image and every
+ * intermediate activation stay in LDS, every layer is an implicit GEMM on the f32 matrix cores, each output element one k-ascending
+ * fma chain started from its bias: the bits do not depend on N, T or the launch.
+ * GF_E_RANGE — num_envs < 0, a layer count outside 1 … GF_CONV_MAX_LAYERS, channels outside 1 … GF_CONV_MAX_CHANNELS, a kernel outside
+ * 1 … GF_CONV_MAX_KERNEL, a stride outside 1 … GF_CONV_MAX_STRIDE, padding >= kernel, a layer output smaller than 1 x 1, latent_dim
+ * outside 1 … GF_CONV_MAX_LATENT, a segment count outside 0 … GF_MLP_MAX_INPUTS, a width < 1, a non-zero stride smaller than its width,
+ * W1 > GF_MLP_MAX_INPUT_WIDTH, activations of one env that do not fit; GF_E_NULL — image, out, a weight or a bias missing, in_mean without in_std.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_CONV_MAX_LAYERS 3
+#define GF_CONV_MAX_CHANNELS 64
+#define GF_CONV_MAX_KERNEL 7
+#define GF_CONV_MAX_STRIDE 3
+#define GF_CONV_MAX_LATENT 512
+#define GF_CONV_MAX_TILE_ENVS 32       /* the head is one 32-row block */
+#define GF_CONV_LDS_BYTES 65536        /* a workgroup's budget: two workgroups per CU */
+
+typedef struct GfConvLayer {
+    const float* weight;        /* [out_channels, in_channels, kernel, kernel], torch.nn.Conv2d.weight read in place */
+    const float* bias;          /* [out_channels] */
+    int32_t out_channels;       /* 1 … GF_CONV_MAX_CHANNELS */
+    int32_t kernel;             /* 1 … GF_CONV_MAX_KERNEL */
+    int32_t stride;             /* 1 … GF_CONV_MAX_STRIDE */
+    int32_t padding;            /* 0 … kernel - 1, zeros */
+} GfConvLayer;
+
+typedef struct GfConvEncodeArgs {
+    int64_t num_envs;           /* N >= 0; 0: nothing is launched */
+    const float* image;         /* row n at image + n * image_stride: channels * height * width floats, [C, H, W] order */
+    int64_t image_stride;       /* floats from a row to the next; 0: channels * height * width */
+    float* out;                 /* [N, W1 + latent_dim], contiguous rows */
+    int32_t num_inputs;         /* 0 … GF_MLP_MAX_INPUTS 1-D segments; 0: W1 = 0, the image only */
+    int32_t num_layers;         /* 1 … GF_CONV_MAX_LAYERS */
+    GfMlpSegment inputs[GF_MLP_MAX_INPUTS];
+    const float* in_mean;       /* [W1] normaliser mean over the 1-D columns, or NULL: they are copied as they are */
+    const float* in_std;        /* [W1] (required with in_mean) */
+    float in_eps;               /* added to in_std */
+    int32_t channels;           /* C, 1 … GF_CONV_MAX_CHANNELS */
+    int32_t height;             /* H */
+    int32_t width;              /* W */
+    GfConvLayer layers[GF_CONV_MAX_LAYERS];
+    const float* head_weight;   /* [latent_dim, flat] row-major, torch.nn.Linear.weight read in place */
+    const float* head_bias;     /* [latent_dim] */
+    int32_t latent_dim;         /* L, 1 … GF_CONV_MAX_LATENT */
+    int32_t _pad;
+} GfConvEncodeArgs;
+
+/* ------------------------------------------------------------------------------------------
+ * Entry points. `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream).
  * ---------------------------------------------------------------------------------------- */
 int gf_abi_version(void);
 /* library-wide tuning switches (process global).  GF_OPT_POST_VARIANT selects the fused post-physics kernel:
@@ -1834,6 +1890,9 @@ int gf_push(const GfPushArgs* a, void* stream);                  /* per-env inte
 int gf_push_sizeof(void);                                        /* sizeof(GfPushArgs): the binding's self-check for this additive entry */
 int gf_action_delay(const GfActionDelayArgs* a, void* stream);  /* per-env delayed position targets: ring write, lagged read, re-draw and priming of the fresh envs, in one launch (Isaac Lab DelayedPDActuator, legged_gym action lag) */
 int gf_action_delay_sizeof(void);                                /* sizeof(GfActionDelayArgs): the binding's self-check for this additive entry */
+int gf_conv_encode(const GfConvEncodeArgs* a, void* stream);   /* the 1-D observation columns (normalised) and the conv encoder's latent of the image into the student MLP's input row, in one launch (learner.ConvEncoder.encode; the depth encoder of a distillation student) */
+int gf_conv_encode_sizeof(void);                                 /* sizeof(GfConvEncodeArgs): the binding's self-check for this additive entry */
+int gf_conv_plan(const GfConvEncodeArgs* a, int* tile_envs_out, int* lds_bytes_out, int* flat_out);   /* gf_conv_encode's refusals (pointers are not looked at) and its tile: T envs per workgroup, the launch's LDS bytes, the head's input width.  Host-only, no GPU needed. */
 int gf_synth_scene_step(const GfSynthSceneArgs* a, void* stream); /* stands in for scene.step() (managed_env.py:292) */
 int gf_rollout_write(const GfRolloutArgs* a, void* stream);       /* replaces the RolloutStorage copy_ launches of the RL library (examples/simple/train.py:125-129) */
 int gf_rollout_frame_write(const GfRolloutFrameArgs* a, void* stream);   /* the newest frame of up to four history observations into a frame-major rollout storage, one launch */

@@ -2,7 +2,7 @@
 
 usage: python tools/bench_distill.py [--sizes 4096,16384,65536] [--steps 24] [--gradient-length 15] [--reps 7] [--calls 50]
                                      [--parts collect,update] [--out FILE]
-                                     [--policy mlp|recurrent] [--rnn-type lstm|gru] [--teacher-recurrent]
+                                     [--policy mlp|recurrent] [--rnn-type lstm|gru] [--teacher-recurrent] [--encoder]
 
 The student reads a 5-frame history of the 48-wide go2_cmd observation (240 columns), the teacher the newest frame and 187 terrain
 heights (235 columns); both are the reference's 512-256-128 ELU MLPs with 12 actions.  Inputs are random rows — no env: every launch
@@ -28,7 +28,18 @@ collect
   torch                   the module's torch step (act_mean + evaluate), gf_policy_act for the sample and a copy_ of the teacher's actions
 update (2 % of the stored steps are dones)
   fused                   learner.Distillation.update: one backward per window of ``gradient_length`` steps, gf_bc_loss + gf_adam_step
-  restated                tests/rsl_rl_distillation_recurrent.py (torch.optim.Adam, an .item() per step)"""
+  restated                tests/rsl_rl_distillation_recurrent.py (torch.optim.Adam, an .item() per step)
+
+``--encoder`` (a depth student: 48 proprioceptive columns and a 16 x 12 or 32 x 24 depth image through a ConvEncoder — 16-32 channels,
+kernel 3, stride 2, latent 64 — in front of the 512-256-128 student; the observation is the two segments (proprio, depth)) times, per
+camera, the same two parts; its lines carry ``camera`` and the slowest rep:
+collect
+  conv_encode     gf_conv_encode + gf_mlp_distill_act (learner.DistillForward.act on the policy with its student_encoder)
+  torch_encoder   the module's torch forward and a torch.cat for the row, then the same gf_mlp_distill_act
+  torch           policy.act_mean + policy.evaluate in torch, gf_policy_act for the sample and a copy_ of the teacher's actions
+update
+  fused           learner.Distillation.update, the encoder's parameters in the flat bucket
+  restated        tests/rsl_rl_distillation.py over the same policy"""
 import argparse
 import copy
 import json
@@ -145,6 +156,95 @@ def update_forms(n: int, T: int, gradient_length: int):
         out["rsl_rl"] = RslRlDistillation(ref_policy, st, **cfg).update()
 
     return {"fused": fused, "rsl_rl": rsl_rl}, out
+
+
+ENC_PROPRIO, ENC_CAMERAS = 48, ((12, 16), (24, 32))
+
+
+def _encoder_policy(cam):
+    from genesis_forge_amd.learner import ConvEncoder, StudentTeacherMLP
+
+    torch.manual_seed(0)
+    enc = ConvEncoder((1, *cam), (16, 32), kernel_size=3, stride=2, padding=0, latent_dim=64)
+    return StudentTeacherMLP(ENC_PROPRIO, TEACHER_W, A, HIDDEN, HIDDEN, student_encoder=enc).cuda()
+
+
+def encoder_collect_forms(n: int, cam):
+    from genesis_forge_amd import _native as nat
+    from genesis_forge_amd.learner import DistillForward, StudentTeacherMLP
+
+    backend = nat.get_backend()
+    policy = _encoder_policy(cam)
+    enc = policy.student_encoder
+    fwd = DistillForward(policy)
+    plain = StudentTeacherMLP(ENC_PROPRIO + enc.latent_dim, TEACHER_W, A, HIDDEN, HIDDEN).cuda()   # the same nets behind a row that is already encoded
+    plain.student, plain.teacher, plain.std = policy.student, policy.teacher, policy.std
+    plain_fwd = DistillForward(plain)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    proprio, depth = torch.randn(n, ENC_PROPRIO, device="cuda", generator=g), torch.rand(n, cam[0] * cam[1], device="cuda", generator=g)
+    tobs = torch.randn(n, TEACHER_W, device="cuda", generator=g)
+    whole = torch.cat((proprio, depth), dim=1)
+    row_a, row_t = torch.zeros(n, A, device="cuda"), torch.zeros(n, A, device="cuda")
+    actions = torch.empty(n, A, device="cuda")
+    stream = [0]
+
+    def conv_encode():
+        stream[0] += 1
+        return fwd.act((proprio, depth), tobs, seed=3, stream=stream[0], actions_out=row_a, teacher_actions_out=row_t, backend=backend)
+
+    def torch_encoder():
+        stream[0] += 1
+        with torch.no_grad():
+            row = torch.cat((proprio, enc(depth)), dim=1)
+        return plain_fwd.act(row, tobs, seed=3, stream=stream[0], actions_out=row_a, teacher_actions_out=row_t, backend=backend)
+
+    pa = nat.GfPolicyActArgs()
+    pa.num_envs, pa.num_actions, pa.seed = n, A, 3
+    pa.std, pa.actions, pa.actions_out = policy.std.data_ptr(), actions.data_ptr(), row_a.data_ptr()
+
+    def torch_forward():
+        stream[0] += 1
+        with torch.no_grad():
+            mean, teacher = policy.act_mean(whole), policy.evaluate(tobs)
+        pa.mean, pa.stream = mean.data_ptr(), stream[0]
+        backend.policy_act(pa)
+        row_t.copy_(teacher)
+
+    return {"conv_encode": conv_encode, "torch_encoder": torch_encoder, "torch": torch_forward}
+
+
+def encoder_update_forms(n: int, T: int, gradient_length: int, cam):
+    from genesis_forge_amd import _native as nat
+    from genesis_forge_amd.learner import Distillation, RolloutStorage
+    from rsl_rl_distillation import RslRlDistillation
+
+    width = ENC_PROPRIO + cam[0] * cam[1]
+    mk = lambda name, w: SimpleNamespace(name=name, observation_space=SimpleNamespace(shape=(w,)), output="fresh", _history_len=1, _unrolled=False)
+    env = SimpleNamespace(num_envs=n, managers={"observation": [mk("policy", width)]}, backend=nat.get_backend())
+    st = RolloutStorage(env, T, obs_groups={"policy": ["policy"]})
+    st._ensure_distill_rows(A)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for t in (st.observations, st.privileged_actions):
+        t.copy_(torch.randn(t.shape, device="cuda", generator=g))
+    policy = _encoder_policy(cam)
+    ref_policy = copy.deepcopy(policy)
+    cfg = dict(num_learning_epochs=1, gradient_length=gradient_length, learning_rate=1e-3, max_grad_norm=None, loss_type="mse")
+    alg = Distillation(policy, st, **cfg)
+    start, ref_start = alg.params.clone(), copy.deepcopy(ref_policy.state_dict())
+    out = {}
+
+    def fused():
+        alg.params.copy_(start)   # the initial weights and a fresh optimizer state, without a host read
+        alg.exp_avg.zero_(), alg.exp_avg_sq.zero_(), alg._state.zero_()
+        alg._state_lr[0] = cfg["learning_rate"]
+        alg._calls = 0
+        out["fused"] = alg.update()
+
+    def restated():
+        ref_policy.load_state_dict(ref_start)
+        out["restated"] = RslRlDistillation(ref_policy, st, **cfg).update()
+
+    return {"fused": fused, "restated": restated}, out
 
 
 def _recurrent_policy(rnn_type: str, teacher_recurrent: bool):
@@ -274,23 +374,42 @@ def main():
     ap.add_argument("--policy", default="mlp", choices=("mlp", "recurrent"))
     ap.add_argument("--rnn-type", default="lstm", choices=("lstm", "gru"))
     ap.add_argument("--teacher-recurrent", action="store_true")
+    ap.add_argument("--encoder", action="store_true")
     args = ap.parse_args()
     recurrent = args.policy == "recurrent"
-    tag = {"policy": "recurrent", "rnn_type": args.rnn_type, "teacher_recurrent": args.teacher_recurrent} if recurrent else {}
-    spread = lambda worst, scale, unit: {f"max_{unit}": worst * scale} if recurrent else {}
+    if recurrent and args.encoder:
+        ap.error("--encoder goes with --policy mlp")
     from genesis_forge_amd import gs
 
     gs.set_device("cuda:0")
     lines = []
+    for cam in (ENC_CAMERAS if args.encoder else (None,)):
+        _run(args, recurrent, cam, lines)
+    if args.out:
+        with open(args.out, "w") as f:
+            for l in lines:
+                f.write(json.dumps(l) + "\n")
+
+
+def _run(args, recurrent: bool, cam, lines: list) -> None:
+    tag = {"policy": "recurrent", "rnn_type": args.rnn_type, "teacher_recurrent": args.teacher_recurrent} if recurrent else {}
+    if cam is not None:
+        tag = {"policy": "encoder", "camera": f"{cam[1]}x{cam[0]}"}
+    spread = lambda worst, scale, unit: {f"max_{unit}": worst * scale} if tag else {}
     for n in (int(x) for x in args.sizes.split(",")):
         if "collect" in args.parts.split(","):
-            forms = recurrent_collect_forms(n, args.rnn_type, args.teacher_recurrent) if recurrent else collect_forms(n)
+            if cam is not None:
+                forms = encoder_collect_forms(n, cam)
+            else:
+                forms = recurrent_collect_forms(n, args.rnn_type, args.teacher_recurrent) if recurrent else collect_forms(n)
             for form, (best, med, worst) in run_forms(forms, args.reps, args.calls).items():
                 lines.append({"part": "collect", "envs": n, **tag, "form": form, "best_us_per_step": best * 1e6, "median_us_per_step": med * 1e6,
                               **spread(worst, 1e6, "us_per_step")})
                 print(json.dumps(lines[-1]), flush=True)
         if "update" in args.parts.split(","):
-            if recurrent:
+            if cam is not None:
+                forms, out = encoder_update_forms(n, args.steps, args.gradient_length, cam)
+            elif recurrent:
                 forms, out = recurrent_update_forms(n, args.steps, args.gradient_length, args.rnn_type, args.teacher_recurrent)
             else:
                 forms, out = update_forms(n, args.steps, args.gradient_length)
@@ -299,10 +418,6 @@ def main():
                               "best_ms_per_update": best * 1e3, "median_ms_per_update": med * 1e3, **spread(worst, 1e3, "ms_per_update"),
                               "behavior": out[form]["behavior"]})
                 print(json.dumps(lines[-1]), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            for l in lines:
-                f.write(json.dumps(l) + "\n")
 
 
 if __name__ == "__main__":

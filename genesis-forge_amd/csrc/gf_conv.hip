@@ -223,6 +223,7 @@ __device__ __forceinline__ void conv_head(const GfConvEncodeArgs& a, const ConvP
     }
 }
 
+#ifndef GF_CONV_BODIES_ONLY   // (gf_conv_banded.hip compiles the device functions above)
 __global__ __launch_bounds__(kMlpBlock, 2) void conv_encode_kernel(const GfConvEncodeArgs a, const ConvPlan p) {
     extern __shared__ float conv_smem[];
     uint32_t* tab = reinterpret_cast<uint32_t*>(conv_smem);
@@ -362,8 +363,11 @@ static int conv_plan(const GfConvEncodeArgs& a, ConvPlan* p) {
     return GF_OK;
 }
 
+#endif  // GF_CONV_BODIES_ONLY
+
 }  // namespace gf
 
+#ifndef GF_CONV_BODIES_ONLY
 extern "C" __attribute__((visibility("default"))) int gf_conv_encode_sizeof(void) { return (int)sizeof(GfConvEncodeArgs); }
 
 extern "C" __attribute__((visibility("default"))) int gf_conv_plan(const GfConvEncodeArgs* a, int* tile_envs_out, int* lds_bytes_out, int* flat_out) {
@@ -394,3 +398,4 @@ extern "C" __attribute__((visibility("default"))) int gf_conv_encode(const GfCon
     gf::klaunch(gf::conv_encode_kernel, dim3((unsigned)tiles), dim3(gf::kMlpBlock), (size_t)p.lds_bytes, (hipStream_t)stream, *a, p);
     return gf::launch_status();
 }
+#endif  // GF_CONV_BODIES_ONLY

@@ -655,7 +655,34 @@ def conv_plan(args: "GfConvEncodeArgs") -> Optional[tuple]:
     return t.value, lds.value, flat.value
 
 
+# its row-banded form (learner.ConvEncoder(form="banded").encode): gf_conv_encode_banded — additive in the same way
+class GfConvBandedArgs(C.Structure):
+    _fields_ = [("enc", GfConvEncodeArgs), ("feat", P), ("band_rows", C.c_int32), ("tile_envs", C.c_int32)]
+
+
+def conv_banded_plan(args: "GfConvBandedArgs") -> Optional[tuple]:
+    """gf_conv_banded_plan: ``(tile_envs, band_rows, num_bands, lds_bytes, flat)`` of the launches ``gf_conv_encode_banded`` would make
+    for the shapes in ``args`` (``band_rows`` / ``tile_envs`` of 0: the plan's choice; no pointer is looked at), or None where it
+    refuses them.  Host-only, as ``conv_plan``."""
+    global _banded_plan_lib
+    if _banded_plan_lib is None:
+        path = lib_path()
+        if not os.path.exists(path):
+            raise GfError(f"{path} not found: build the HIP library first (make -C genesis-forge_amd/csrc)")
+        lib = C.CDLL(path)
+        if lib.gf_conv_encode_banded_sizeof() != C.sizeof(GfConvBandedArgs):
+            raise GfError(f"ABI drift: sizeof(GfConvBandedArgs) is {lib.gf_conv_encode_banded_sizeof()} in the library, {C.sizeof(GfConvBandedArgs)} in the binding")
+        lib.gf_conv_banded_plan.restype = C.c_int
+        lib.gf_conv_banded_plan.argtypes = [C.POINTER(GfConvBandedArgs)] + [C.POINTER(C.c_int)] * 5
+        _banded_plan_lib = lib
+    out = [C.c_int(0) for _ in range(5)]
+    if _banded_plan_lib.gf_conv_banded_plan(C.byref(args), *(C.byref(x) for x in out)) != 0:
+        return None
+    return tuple(x.value for x in out)
+
+
 _plan_lib = None
+_banded_plan_lib = None
 
 
 # the newest frame of a history observation into a frame-major rollout storage (learner.RolloutStorage(history="frames")):
@@ -951,6 +978,11 @@ class HipBackend(Backend):
             raise GfError(f"ABI drift: sizeof(GfConvEncodeArgs) is {n} in the library, {C.sizeof(GfConvEncodeArgs)} in the binding")
         self.lib.gf_conv_encode.restype = C.c_int
         self.lib.gf_conv_encode.argtypes = [C.POINTER(GfConvEncodeArgs), C.c_void_p]
+        n = self.lib.gf_conv_encode_banded_sizeof()
+        if n != C.sizeof(GfConvBandedArgs):
+            raise GfError(f"ABI drift: sizeof(GfConvBandedArgs) is {n} in the library, {C.sizeof(GfConvBandedArgs)} in the binding")
+        self.lib.gf_conv_encode_banded.restype = C.c_int
+        self.lib.gf_conv_encode_banded.argtypes = [C.POINTER(GfConvBandedArgs), C.c_void_p]
         n = self.lib.gf_sizeof(GF_SIZEOF_RNN_CELL)
         if n != C.sizeof(GfRnnCell):
             raise GfError(f"ABI drift: sizeof(GfRnnCell) is {n} in the library, {C.sizeof(GfRnnCell)} in the binding")
@@ -1142,6 +1174,7 @@ _LEARNER_ENTRIES = {
     "mlp_act": "learner.PolicyForward, learner.RolloutStorage.act_policy",
     "mlp_distill_act": "learner.DistillForward.act, learner.RolloutStorage.act_distill",
     "conv_encode": "learner.ConvEncoder.encode, learner.DistillForward.act with a student_encoder",
+    "conv_encode_banded": 'learner.ConvEncoder(form="banded").encode',
     "bc_loss": "learner.Distillation.update",
     "rnd_reward": "learner.RndForward.reward, learner.RolloutStorage.intrinsic_reward",
     "mlp_recurrent_act": "learner.RecurrentForward",

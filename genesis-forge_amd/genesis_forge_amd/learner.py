@@ -1467,19 +1467,32 @@ class ConvPlan(NamedTuple):
     flat: int
 
 
-class _ConvScratch:
-    """The native descriptor of a :class:`ConvEncoder`'s ``gf_conv_encode`` calls and what its last launch reads: call-to-call
-    scratch, so a copy or a pickle of the module starts with a fresh one (as ``_NormScratch``)."""
+class ConvBandedPlan(NamedTuple):
+    """How ``gf_conv_encode_banded`` splits an encoder: :class:`ConvPlan`'s fields for its first launch, then ``band_rows`` rows of
+    the last conv layer's output per workgroup and ``num_bands`` such bands over its height."""
+    tile_envs: int
+    lds_bytes: int
+    flat: int
+    band_rows: int
+    num_bands: int
 
-    def __init__(self):
-        self.args = nat.GfConvEncodeArgs()
+
+class _ConvScratch:
+    """The native descriptor of a :class:`ConvEncoder`'s ``gf_conv_encode`` / ``gf_conv_encode_banded`` calls, what its last launch
+    reads and, banded, the ``feat`` buffer between the two launches: call-to-call scratch, so a copy or a pickle of the module
+    starts with a fresh one (as ``_NormScratch``)."""
+
+    def __init__(self, banded: bool = False):
+        self.banded = banded
+        self.args = nat.GfConvBandedArgs() if banded else nat.GfConvEncodeArgs()
         self.keep = None
+        self.feat = None
 
     def __deepcopy__(self, memo):
-        return _ConvScratch()
+        return _ConvScratch(self.banded)
 
     def __reduce__(self):
-        return (_ConvScratch, ())
+        return (_ConvScratch, (self.banded,))
 
 
 def _strided_rows(x, name: str, n: Optional[int], dev, width: Optional[int] = None) -> None:
@@ -1509,13 +1522,24 @@ class ConvEncoder(torch.nn.Module):
     ``no_grad``: ``out[n] = [normalizer(obs[n]) | forward(image[n])]``, the student MLP's complete input row.  ``plan`` is the
     launch's tile (:class:`ConvPlan`).
 
+    ``form="banded"`` is the kernel's second form, ``gf_conv_encode_banded``, for cameras whose activations do not fit the LDS tile
+    (58 x 87, 64 x 64) or leave it a few envs: TWO launches — the conv layers in bands of ``band_rows`` output rows of the last layer
+    (None: whole images where one env fits, else the tallest band that does), then the head over 32-env blocks out of a persistent
+    ``[N, flat]`` buffer the module owns.  ``plan`` is then a :class:`ConvBandedPlan`.  The row is ``form="tile"``'s bit for bit
+    wherever both serve the shape; ``tile_envs`` forces the envs per workgroup as ``band_rows`` forces the band (tests).
+
     Limits, checked here (``ValueError`` naming the argument): 1 to 3 conv layers, ``C`` and ``channels[i]`` <= 64, kernels 1 to 7,
     strides 1 to 3, ``padding < kernel``, every layer's output at least 1 x 1, ``latent_dim`` 1 to 512, and the activations of one
-    env must fit the kernel's LDS tile."""
+    env must fit the kernel's LDS tile (``form="tile"``) or a one-row band of one env must (``form="banded"``)."""
 
-    def __init__(self, image_shape, channels: Sequence[int] = (16, 32), kernel_size=3, stride=1, padding=0, latent_dim: int = 64):
+    def __init__(self, image_shape, channels: Sequence[int] = (16, 32), kernel_size=3, stride=1, padding=0, latent_dim: int = 64,
+                 form: str = "tile", band_rows: Optional[int] = None, tile_envs: Optional[int] = None):
         super().__init__()
         who = "ConvEncoder"
+        if form not in ("tile", "banded"):
+            raise ValueError(f"{who}: form={form!r} must be 'tile' or 'banded'")
+        if form == "tile" and (band_rows is not None or tile_envs is not None):
+            raise ValueError(f"{who}: band_rows / tile_envs belong to form='banded'")
         try:
             shape = tuple(int(x) for x in image_shape)
         except TypeError:
@@ -1553,12 +1577,27 @@ class ConvEncoder(torch.nn.Module):
         self.conv = torch.nn.Sequential(*mods)
         self.flatten = torch.nn.Flatten(1)
         self.head = torch.nn.Linear(c * h * w, self.latent_dim)
-        plan = nat.conv_plan(self._shapes(nat.GfConvEncodeArgs()))
-        if plan is None:
-            raise ValueError(f"{who}: image_shape={shape!r} with channels={channels!r}: the activations of one env do not fit the kernel's "
-                             f"{nat.GF_CONV_LDS_BYTES}-byte LDS tile")
-        self.plan = ConvPlan(*plan)
-        self._scratch = _ConvScratch()
+        self.form = form
+        if form == "banded":
+            a = nat.GfConvBandedArgs()
+            self._shapes(a.enc)
+            a.band_rows, a.tile_envs = int(band_rows or 0), int(tile_envs or 0)
+            plan = None if a.band_rows < 0 or a.tile_envs < 0 else nat.conv_banded_plan(a)
+            if plan is None and (band_rows or tile_envs):
+                raise ValueError(f"{who}: band_rows={band_rows!r} / tile_envs={tile_envs!r} of image_shape={shape!r}: bands of 1 to {h} rows and "
+                                 f"tiles of 1 to {nat.GF_CONV_MAX_TILE_ENVS} envs that fit {nat.GF_CONV_LDS_BYTES} bytes of LDS")
+            if plan is None:
+                raise ValueError(f"{who}: image_shape={shape!r} with channels={channels!r}: a one-row band of one env does not fit the "
+                                 f"kernel's {nat.GF_CONV_LDS_BYTES}-byte LDS tile")
+            t, r, bands, lds, flat = plan
+            self.plan = ConvBandedPlan(t, lds, flat, r, bands)
+        else:
+            plan = nat.conv_plan(self._shapes(nat.GfConvEncodeArgs()))
+            if plan is None:
+                raise ValueError(f"{who}: image_shape={shape!r} with channels={channels!r}: the activations of one env do not fit the kernel's "
+                                 f"{nat.GF_CONV_LDS_BYTES}-byte LDS tile")
+            self.plan = ConvPlan(*plan)
+        self._scratch = _ConvScratch(form == "banded")
 
     def _shapes(self, a):
         """The shape fields of a descriptor (what ``gf_conv_plan`` reads)."""
@@ -1573,7 +1612,8 @@ class ConvEncoder(torch.nn.Module):
         return self.head(self.flatten(self.conv(image.reshape(-1, *self.image_shape))))
 
     def encode(self, image: torch.Tensor, obs=None, normalizer=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``out[n] = [normalizer(obs[n]) | forward(image[n])]`` in ONE ``gf_conv_encode`` launch, under ``no_grad``.  ``image``:
+        """``out[n] = [normalizer(obs[n]) | forward(image[n])]`` in ONE ``gf_conv_encode`` launch (``form="banded"``: the two of
+        ``gf_conv_encode_banded``), under ``no_grad``.  ``image``:
         ``[N, C·H·W]`` float32 rows with unit column stride — a tensor of its own (``[N, C, H, W]`` contiguous too) or the trailing
         columns of a wider block; ``obs``: ``None``, a ``[N, W]`` tensor or up to four side by side (under the same rule);
         ``normalizer``: ``None`` / ``nn.Identity`` or the :class:`EmpiricalNormalization` of those columns; ``out``: a contiguous
@@ -1597,10 +1637,11 @@ class ConvEncoder(torch.nn.Module):
             out = torch.empty((n, W1 + L), device=dev, dtype=torch.float32)
         else:
             _check_f32(out, "out", {(n, W1 + L)}, dev)
-        fn = getattr(nat.get_backend(), "conv_encode", None)
+        banded = self.form == "banded"
+        fn = getattr(nat.get_backend(), "conv_encode_banded" if banded else "conv_encode", None)
         if fn is None:
             raise RuntimeError("ConvEncoder.encode is the gf_conv_encode launch: this backend has no such entry (forward() is the torch path)")
-        a = self._shapes(self._scratch.args)
+        a = self._shapes(self._scratch.args.enc if banded else self._scratch.args)
         a.num_envs, a.image, a.out = n, image.data_ptr(), out.data_ptr()
         a.image_stride = 0 if n < 2 or image.stride(0) == S else image.stride(0)
         a.num_inputs = len(parts)
@@ -1617,7 +1658,15 @@ class ConvEncoder(torch.nn.Module):
             lay.weight, lay.bias = m.weight.data_ptr(), m.bias.data_ptr()
         a.head_weight, a.head_bias = self.head.weight.data_ptr(), self.head.bias.data_ptr()
         self._scratch.keep = (image, parts, out, norm)
-        fn(a)
+        if banded:   # the buffer between the two launches: persistent, grown on demand
+            feat = self._scratch.feat
+            if feat is None or feat.device != dev or feat.numel() < n * self.plan.flat:
+                feat = self._scratch.feat = torch.empty(max(n, 1) * self.plan.flat, device=dev, dtype=torch.float32)
+            b = self._scratch.args
+            b.feat, b.band_rows, b.tile_envs = feat.data_ptr(), self.plan.band_rows, self.plan.tile_envs
+            fn(b)
+        else:
+            fn(a)
         return out
 
 
@@ -1978,7 +2027,7 @@ _STUDENT_TEACHER_KEYS = ("class_name", "activation", "student_hidden_dims", "tea
                          "student_obs_normalization", "teacher_obs_normalization")
 
 
-_STUDENT_ENCODER_KEYS = ("image_shape", "channels", "kernel_size", "stride", "padding", "latent_dim")
+_STUDENT_ENCODER_KEYS = ("image_shape", "channels", "kernel_size", "stride", "padding", "latent_dim", "form", "band_rows")
 
 
 def _student_encoder(pol: dict) -> Optional["ConvEncoder"]:

@@ -2130,6 +2130,33 @@ enum { GF_PHASE_ACTION = 0, GF_PHASE_CONTACT, GF_PHASE_TERMINATION, GF_PHASE_REW
 int gf_profile_begin(int phase, int max_samples);     /* start recording event pairs for `phase` */
 int gf_profile_end(double* total_ms, int* samples);    /* sync events, return Σ elapsed + count, free them */
 
+/* ------------------------------------------------------------------------------------------
+ * gf_conv_encode_banded: gf_conv_encode's row for images whose activations do not fit one LDS tile, and for tiles of a few envs —
+ * the same `out`, bit for bit wherever gf_conv_encode serves the shape, in TWO launches.
+ *   A  a workgroup owns (a tile of T envs, a band of R consecutive output rows of the LAST conv layer).  Walking the layers backwards
+ *      gives the rows of every activation the band needs — layer input rows [oy0·s − p, (oy1 − 1)·s − p + k) clipped to the
+ *      activation; neighbouring bands recompute the halo rows of the intermediate layers — and only those rows live in LDS.  The layers
+ *      are gf_conv_encode's implicit GEMMs; rows above row 0 and below H are padding, zeros selected.  The band's last activation goes to
+ *      `feat[n, flat]` at torch's [C, H, W] flatten offsets; the workgroups of band 0 write the normalised 1-D columns.
+ *   B  out[n, W1 + j] = head_bias[j] + Σ_k feat[n, k] · head_weight[j, k] over full 32-env row blocks, `feat` streamed through LDS in k
+ *      slabs, k ascending, no split: the head's weights are read once per 32 envs whatever T is.
+ * An output element is one k-ascending fma chain started from its bias in both launches: the bits do not depend on N, T, R or the launch.
+ * gf_conv_banded_plan picks (T, R) within GF_CONV_LDS_BYTES: whole images (R = the last layer's height) with the largest T <= 32 that
+ * fits; R shrinks only where not even one env fits.  band_rows / tile_envs: 0 = the plan's value, otherwise forced.
+ * GF_E_RANGE — gf_conv_encode's shape refusals (but for the tile), a forced band_rows outside 1 … the last layer's height, a forced
+ * tile_envs outside 1 … GF_CONV_MAX_TILE_ENVS, forced values that do not fit, a one-row band of one env that does not fit;
+ * GF_E_NULL — as gf_conv_encode, or feat missing.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct GfConvBandedArgs {
+    GfConvEncodeArgs enc;       /* gf_conv_encode's descriptor, field for field */
+    float* feat;                /* [N, flat] scratch, contiguous rows: written by launch A, read by launch B */
+    int32_t band_rows;          /* R; 0: the plan's */
+    int32_t tile_envs;          /* T; 0: the plan's */
+} GfConvBandedArgs;
+int gf_conv_encode_banded(const GfConvBandedArgs* a, void* stream);   /* gf_conv_encode's row in two launches: the conv layers in row bands, then the head over 32-env blocks (learner.ConvEncoder(form="banded").encode) */
+int gf_conv_encode_banded_sizeof(void);                                /* sizeof(GfConvBandedArgs): the binding's self-check for this additive entry */
+int gf_conv_banded_plan(const GfConvBandedArgs* a, int* tile_envs_out, int* band_rows_out, int* num_bands_out, int* lds_bytes_out, int* flat_out);   /* gf_conv_encode_banded's refusals (pointers are not looked at) and its plan.  Host-only, no GPU needed. */
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 
 usage: python tools/bench_distill.py [--sizes 4096,16384,65536] [--steps 24] [--gradient-length 15] [--reps 7] [--calls 50]
                                      [--parts collect,update] [--out FILE]
-                                     [--policy mlp|recurrent] [--rnn-type lstm|gru] [--teacher-recurrent] [--encoder]
+                                     [--policy mlp|recurrent] [--rnn-type lstm|gru] [--teacher-recurrent]
+                                     [--encoder [--encoder-form tile|banded|both] [--cameras 16x12,32x24,87x58]]
 
 The student reads a 5-frame history of the 48-wide go2_cmd observation (240 columns), the teacher the newest frame and 187 terrain
 heights (235 columns); both are the reference's 512-256-128 ELU MLPs with 12 actions.  Inputs are random rows — no env: every launch
@@ -31,10 +32,13 @@ update (2 % of the stored steps are dones)
   restated                tests/rsl_rl_distillation_recurrent.py (torch.optim.Adam, an .item() per step)
 
 ``--encoder`` (a depth student: 48 proprioceptive columns and a 16 x 12 or 32 x 24 depth image through a ConvEncoder — 16-32 channels,
-kernel 3, stride 2, latent 64 — in front of the 512-256-128 student; the observation is the two segments (proprio, depth)) times, per
-camera, the same two parts; its lines carry ``camera`` and the slowest rep:
+kernel 3, stride 2, latent 64 — or the 87 x 58 parkour camera with kernels 5 and 3, in front of the 512-256-128 student; the observation
+is the two segments (proprio, depth); ``--cameras 32x24,87x58`` selects) times, per camera, the same two parts; its lines carry
+``camera`` and the slowest rep.  ``--encoder-form tile|banded|both`` picks the ConvEncoder form(s) of the collect part (a form that
+refuses the camera is left out; `both` alternates them inside a repetition):
 collect
   conv_encode     gf_conv_encode + gf_mlp_distill_act (learner.DistillForward.act on the policy with its student_encoder)
+  conv_encode_banded   the same with form="banded": gf_conv_encode_banded's two launches + gf_mlp_distill_act
   torch_encoder   the module's torch forward and a torch.cat for the row, then the same gf_mlp_distill_act
   torch           policy.act_mean + policy.evaluate in torch, gf_policy_act for the sample and a copy_ of the teacher's actions
 update
@@ -158,25 +162,32 @@ def update_forms(n: int, T: int, gradient_length: int):
     return {"fused": fused, "rsl_rl": rsl_rl}, out
 
 
-ENC_PROPRIO, ENC_CAMERAS = 48, ((12, 16), (24, 32))
+ENC_PROPRIO, ENC_CAMERAS = 48, ((12, 16), (24, 32), (58, 87))   # (58 x 87, the parkour depth camera: kernels 5 and 3, form="banded" only)
 
 
-def _encoder_policy(cam):
+def _encoder_policy(cam, form="tile"):
+    """The policy with its encoder in `form` (the same weights in either), or None where that form refuses the camera."""
     from genesis_forge_amd.learner import ConvEncoder, StudentTeacherMLP
 
     torch.manual_seed(0)
-    enc = ConvEncoder((1, *cam), (16, 32), kernel_size=3, stride=2, padding=0, latent_dim=64)
+    try:
+        enc = ConvEncoder((1, *cam), (16, 32), kernel_size=(5, 3) if cam[0] > 32 else 3, stride=2, padding=0, latent_dim=64, form=form)
+    except ValueError:
+        return None
     return StudentTeacherMLP(ENC_PROPRIO, TEACHER_W, A, HIDDEN, HIDDEN, student_encoder=enc).cuda()
 
 
-def encoder_collect_forms(n: int, cam):
+def encoder_collect_forms(n: int, cam, encoder_form="tile"):
     from genesis_forge_amd import _native as nat
     from genesis_forge_amd.learner import DistillForward, StudentTeacherMLP
 
     backend = nat.get_backend()
-    policy = _encoder_policy(cam)
+    hip = {form: _encoder_policy(cam, form) for form in (("tile", "banded") if encoder_form == "both" else (encoder_form,))}
+    hip = {form: DistillForward(p) for form, p in hip.items() if p is not None}
+    policy = next(iter(hip.values())).policy if hip else _encoder_policy(cam, "banded")
+    for form, f in hip.items():
+        print(f"# camera {cam[1]}x{cam[0]} form {form}: {f.policy.student_encoder.plan}", flush=True)
     enc = policy.student_encoder
-    fwd = DistillForward(policy)
     plain = StudentTeacherMLP(ENC_PROPRIO + enc.latent_dim, TEACHER_W, A, HIDDEN, HIDDEN).cuda()   # the same nets behind a row that is already encoded
     plain.student, plain.teacher, plain.std = policy.student, policy.teacher, policy.std
     plain_fwd = DistillForward(plain)
@@ -188,9 +199,11 @@ def encoder_collect_forms(n: int, cam):
     actions = torch.empty(n, A, device="cuda")
     stream = [0]
 
-    def conv_encode():
-        stream[0] += 1
-        return fwd.act((proprio, depth), tobs, seed=3, stream=stream[0], actions_out=row_a, teacher_actions_out=row_t, backend=backend)
+    def conv_encode(fwd):
+        def run():
+            stream[0] += 1
+            return fwd.act((proprio, depth), tobs, seed=3, stream=stream[0], actions_out=row_a, teacher_actions_out=row_t, backend=backend)
+        return run
 
     def torch_encoder():
         stream[0] += 1
@@ -210,7 +223,8 @@ def encoder_collect_forms(n: int, cam):
         backend.policy_act(pa)
         row_t.copy_(teacher)
 
-    return {"conv_encode": conv_encode, "torch_encoder": torch_encoder, "torch": torch_forward}
+    names = {"tile": "conv_encode", "banded": "conv_encode_banded"}
+    return {**{names[form]: conv_encode(f) for form, f in hip.items()}, "torch_encoder": torch_encoder, "torch": torch_forward}
 
 
 def encoder_update_forms(n: int, T: int, gradient_length: int, cam):
@@ -226,7 +240,7 @@ def encoder_update_forms(n: int, T: int, gradient_length: int, cam):
     g = torch.Generator(device="cuda").manual_seed(0)
     for t in (st.observations, st.privileged_actions):
         t.copy_(torch.randn(t.shape, device="cuda", generator=g))
-    policy = _encoder_policy(cam)
+    policy = _encoder_policy(cam) or _encoder_policy(cam, "banded")   # (the update is the torch path either way)
     ref_policy = copy.deepcopy(policy)
     cfg = dict(num_learning_epochs=1, gradient_length=gradient_length, learning_rate=1e-3, max_grad_norm=None, loss_type="mse")
     alg = Distillation(policy, st, **cfg)
@@ -375,6 +389,8 @@ def main():
     ap.add_argument("--rnn-type", default="lstm", choices=("lstm", "gru"))
     ap.add_argument("--teacher-recurrent", action="store_true")
     ap.add_argument("--encoder", action="store_true")
+    ap.add_argument("--encoder-form", default="tile", choices=("tile", "banded", "both"), help="the ConvEncoder form(s) of the collect part")
+    ap.add_argument("--cameras", default=None, help="with --encoder: WxH,… out of 16x12,32x24,87x58 (default: all)")
     args = ap.parse_args()
     recurrent = args.policy == "recurrent"
     if recurrent and args.encoder:
@@ -383,7 +399,8 @@ def main():
 
     gs.set_device("cuda:0")
     lines = []
-    for cam in (ENC_CAMERAS if args.encoder else (None,)):
+    cams = [c for c in ENC_CAMERAS if args.cameras is None or f"{c[1]}x{c[0]}" in args.cameras.split(",")]
+    for cam in (cams if args.encoder else (None,)):
         _run(args, recurrent, cam, lines)
     if args.out:
         with open(args.out, "w") as f:
@@ -399,7 +416,7 @@ def _run(args, recurrent: bool, cam, lines: list) -> None:
     for n in (int(x) for x in args.sizes.split(",")):
         if "collect" in args.parts.split(","):
             if cam is not None:
-                forms = encoder_collect_forms(n, cam)
+                forms = encoder_collect_forms(n, cam, args.encoder_form)
             else:
                 forms = recurrent_collect_forms(n, args.rnn_type, args.teacher_recurrent) if recurrent else collect_forms(n)
             for form, (best, med, worst) in run_forms(forms, args.reps, args.calls).items():

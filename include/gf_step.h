@@ -1803,7 +1803,10 @@ typedef struct GfActionDelayArgs {
  * GF_E_RANGE — num_envs < 0, a layer count outside 1 … GF_CONV_MAX_LAYERS, channels outside 1 … GF_CONV_MAX_CHANNELS, a kernel outside
  * 1 … GF_CONV_MAX_KERNEL, a stride outside 1 … GF_CONV_MAX_STRIDE, padding >= kernel, a layer output smaller than 1 x 1, latent_dim
  * outside 1 … GF_CONV_MAX_LATENT, a segment count outside 0 … GF_MLP_MAX_INPUTS, a width < 1, a non-zero stride smaller than its width,
- * W1 > GF_MLP_MAX_INPUT_WIDTH, activations of one env that do not fit; GF_E_NULL — image, out, a weight or a bias missing, in_mean without in_std.
+ * W1 > GF_MLP_MAX_INPUT_WIDTH, a height or width outside 1 … 4096, a non-zero image_stride smaller than channels · height · width,
+ * activations of one env that do not fit; GF_E_NULL — image, out, a weight or a bias (a layer's or the head's) or a segment's rows
+ * missing, in_mean without in_std.  The order: the shape, then the pointers, then num_envs == 0 — an empty call with a bad shape is
+ * GF_E_RANGE, with a missing pointer GF_E_NULL, otherwise GF_OK with nothing launched; a refused call writes nothing.
  * ---------------------------------------------------------------------------------------- */
 #define GF_CONV_MAX_LAYERS 3
 #define GF_CONV_MAX_CHANNELS 64
@@ -2145,7 +2148,7 @@ int gf_profile_end(double* total_ms, int* samples);    /* sync events, return Σ
  * fits; R shrinks only where not even one env fits.  band_rows / tile_envs: 0 = the plan's value, otherwise forced.
  * GF_E_RANGE — gf_conv_encode's shape refusals (but for the tile), a forced band_rows outside 1 … the last layer's height, a forced
  * tile_envs outside 1 … GF_CONV_MAX_TILE_ENVS, forced values that do not fit, a one-row band of one env that does not fit;
- * GF_E_NULL — as gf_conv_encode, or feat missing.
+ * GF_E_NULL — as gf_conv_encode, or feat missing.  The same order: the shape and the plan, then the pointers, then num_envs == 0.
  * ---------------------------------------------------------------------------------------- */
 typedef struct GfConvBandedArgs {
     GfConvEncodeArgs enc;       /* gf_conv_encode's descriptor, field for field */

@@ -681,8 +681,54 @@ def conv_banded_plan(args: "GfConvBandedArgs") -> Optional[tuple]:
     return tuple(x.value for x in out)
 
 
+# its backward (learner.ConvEncoder(backward="hip").encode_train): gf_conv_encode_backward — additive in the same way
+GF_CONV_BWD_LDS_BYTES = 65536
+GF_CONV_BWD_GROUPS = 512
+GF_CONV_BWD_MAX_GROUPS = 4096
+
+
+class GfConvBackwardArgs(C.Structure):
+    _fields_ = [("enc", GfConvEncodeArgs), ("grad_latent", P), ("grad_row_stride", C.c_int64), ("grad_weight", P * GF_CONV_MAX_LAYERS),
+                ("grad_bias", P * GF_CONV_MAX_LAYERS), ("grad_head_weight", P), ("grad_head_bias", P), ("workspace", P),
+                ("workspace_bytes", C.c_int64), ("tile_envs", C.c_int32), ("groups", C.c_int32)]
+
+
+def _backward_lib():
+    global _backward_plan_lib
+    if _backward_plan_lib is None:
+        path = lib_path()
+        if not os.path.exists(path):
+            raise GfError(f"{path} not found: build the HIP library first (make -C genesis-forge_amd/csrc)")
+        lib = C.CDLL(path)
+        if lib.gf_conv_backward_sizeof() != C.sizeof(GfConvBackwardArgs):
+            raise GfError(f"ABI drift: sizeof(GfConvBackwardArgs) is {lib.gf_conv_backward_sizeof()} in the library, {C.sizeof(GfConvBackwardArgs)} in the binding")
+        lib.gf_conv_backward_plan.restype = C.c_int
+        lib.gf_conv_backward_plan.argtypes = [C.POINTER(GfConvBackwardArgs)] + [C.POINTER(C.c_int)] * 4
+        lib.gf_conv_backward_workspace_bytes.restype = C.c_int64
+        lib.gf_conv_backward_workspace_bytes.argtypes = [C.POINTER(GfConvBackwardArgs)]
+        _backward_plan_lib = lib
+    return _backward_plan_lib
+
+
+def conv_backward_plan(args: "GfConvBackwardArgs") -> Optional[tuple]:
+    """gf_conv_backward_plan: ``(tile_envs, groups, lds_bytes, flat)`` of the launches ``gf_conv_encode_backward`` would make for the
+    shapes and ``num_envs`` in ``args`` (``tile_envs`` / ``groups`` of 0: the plan's choice; no pointer is looked at), or None where
+    it refuses them.  Host-only, as ``conv_plan``."""
+    out = [C.c_int(0) for _ in range(4)]
+    if _backward_lib().gf_conv_backward_plan(C.byref(args), *(C.byref(x) for x in out)) != 0:
+        return None
+    return tuple(x.value for x in out)
+
+
+def conv_backward_workspace_bytes(args: "GfConvBackwardArgs") -> int:
+    """gf_conv_backward_workspace_bytes: the workspace ``gf_conv_encode_backward`` needs for ``args.enc.num_envs`` envs (a negative
+    status where the plan refuses the shapes).  Host-only."""
+    return int(_backward_lib().gf_conv_backward_workspace_bytes(C.byref(args)))
+
+
 _plan_lib = None
 _banded_plan_lib = None
+_backward_plan_lib = None
 
 
 # the newest frame of a history observation into a frame-major rollout storage (learner.RolloutStorage(history="frames")):
@@ -983,6 +1029,11 @@ class HipBackend(Backend):
             raise GfError(f"ABI drift: sizeof(GfConvBandedArgs) is {n} in the library, {C.sizeof(GfConvBandedArgs)} in the binding")
         self.lib.gf_conv_encode_banded.restype = C.c_int
         self.lib.gf_conv_encode_banded.argtypes = [C.POINTER(GfConvBandedArgs), C.c_void_p]
+        n = self.lib.gf_conv_backward_sizeof()
+        if n != C.sizeof(GfConvBackwardArgs):
+            raise GfError(f"ABI drift: sizeof(GfConvBackwardArgs) is {n} in the library, {C.sizeof(GfConvBackwardArgs)} in the binding")
+        self.lib.gf_conv_encode_backward.restype = C.c_int
+        self.lib.gf_conv_encode_backward.argtypes = [C.POINTER(GfConvBackwardArgs), C.c_void_p]
         n = self.lib.gf_sizeof(GF_SIZEOF_RNN_CELL)
         if n != C.sizeof(GfRnnCell):
             raise GfError(f"ABI drift: sizeof(GfRnnCell) is {n} in the library, {C.sizeof(GfRnnCell)} in the binding")
@@ -1175,6 +1226,7 @@ _LEARNER_ENTRIES = {
     "mlp_distill_act": "learner.DistillForward.act, learner.RolloutStorage.act_distill",
     "conv_encode": "learner.ConvEncoder.encode, learner.DistillForward.act with a student_encoder",
     "conv_encode_banded": 'learner.ConvEncoder(form="banded").encode',
+    "conv_encode_backward": 'learner.ConvEncoder(backward="hip").encode_train: the backward of its row',
     "bc_loss": "learner.Distillation.update",
     "rnd_reward": "learner.RndForward.reward, learner.RolloutStorage.intrinsic_reward",
     "mlp_recurrent_act": "learner.RecurrentForward",

@@ -59,6 +59,7 @@ import contextlib
 import ctypes as C
 import math
 import statistics
+import warnings
 from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequence
 
 import torch
@@ -1477,6 +1478,14 @@ class ConvBandedPlan(NamedTuple):
     num_bands: int
 
 
+class ConvBackwardPlan(NamedTuple):
+    """How ``gf_conv_encode_backward`` tiles an encoder: ``tile_envs`` envs per tile, at most ``groups`` persistent workgroups walking
+    the tiles, the tile launch's LDS bytes."""
+    tile_envs: int
+    groups: int
+    lds_bytes: int
+
+
 class _ConvScratch:
     """The native descriptor of a :class:`ConvEncoder`'s ``gf_conv_encode`` / ``gf_conv_encode_banded`` calls, what its last launch
     reads and, banded, the ``feat`` buffer between the two launches: call-to-call scratch, so a copy or a pickle of the module
@@ -1487,12 +1496,34 @@ class _ConvScratch:
         self.args = nat.GfConvBandedArgs() if banded else nat.GfConvEncodeArgs()
         self.keep = None
         self.feat = None
+        # backward="hip": gf_conv_encode_backward's descriptor and its workspace (one tensor, grown on demand)
+        self.bwd = nat.GfConvBackwardArgs()
+        self.workspace = self.bwd_keep = None
 
     def __deepcopy__(self, memo):
         return _ConvScratch(self.banded)
 
     def __reduce__(self):
         return (_ConvScratch, (self.banded,))
+
+
+class _ConvEncodeRow(torch.autograd.Function):
+    """``ConvEncoder.encode_train``'s row: forward is the ``gf_conv_encode`` launch, backward ``gf_conv_encode_backward`` — the gradient
+    of every conv and head parameter from the latent columns of the row's gradient.  The image, the 1-D columns and the normaliser get
+    no gradient.  ``params`` are the encoder's parameters (conv weight, bias, …, head weight, bias): inputs, so autograd accumulates."""
+
+    @staticmethod
+    def forward(ctx, enc, image, obs, normalizer, *params):
+        row = enc.encode(image, obs, normalizer)
+        ctx.enc, ctx.w1 = enc, int(row.shape[1]) - enc.latent_dim
+        ctx.save_for_backward(image)
+        return row
+
+    @staticmethod
+    def backward(ctx, grad_row):
+        (image,) = ctx.saved_tensors
+        grads = ctx.enc._backward_hip(image, grad_row, ctx.w1)
+        return (None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:]))
 
 
 def _strided_rows(x, name: str, n: Optional[int], dev, width: Optional[int] = None) -> None:
@@ -1528,16 +1559,25 @@ class ConvEncoder(torch.nn.Module):
     ``[N, flat]`` buffer the module owns.  ``plan`` is then a :class:`ConvBandedPlan`.  The row is ``form="tile"``'s bit for bit
     wherever both serve the shape; ``tile_envs`` forces the envs per workgroup as ``band_rows`` forces the band (tests).
 
+    ``backward="hip"`` (independent of ``form``; the default ``"torch"`` changes nothing) trains the encoder without torch's conv
+    kernels: ``encode_train(image, obs=None, normalizer=None)`` is ``encode``'s row from the same launch, with a ``grad_fn`` whose
+    backward is ``gf_conv_encode_backward`` — the gradients of every conv and head parameter from the row's latent columns,
+    recomputed per tile in LDS, nothing saved by the forward; the image and the 1-D columns get no gradient.
+    ``StudentTeacherMLP.act_mean`` uses it when grad is enabled.  ``backward_plan`` is a :class:`ConvBackwardPlan`.  Every activation
+    of one env must fit the backward's LDS tile at once: the 87 x 58 camera does not (there is no banded backward).
+
     Limits, checked here (``ValueError`` naming the argument): 1 to 3 conv layers, ``C`` and ``channels[i]`` <= 64, kernels 1 to 7,
     strides 1 to 3, ``padding < kernel``, every layer's output at least 1 x 1, ``latent_dim`` 1 to 512, and the activations of one
     env must fit the kernel's LDS tile (``form="tile"``) or a one-row band of one env must (``form="banded"``)."""
 
     def __init__(self, image_shape, channels: Sequence[int] = (16, 32), kernel_size=3, stride=1, padding=0, latent_dim: int = 64,
-                 form: str = "tile", band_rows: Optional[int] = None, tile_envs: Optional[int] = None):
+                 form: str = "tile", band_rows: Optional[int] = None, tile_envs: Optional[int] = None, backward: str = "torch"):
         super().__init__()
         who = "ConvEncoder"
         if form not in ("tile", "banded"):
             raise ValueError(f"{who}: form={form!r} must be 'tile' or 'banded'")
+        if backward not in ("torch", "hip"):
+            raise ValueError(f"{who}: backward={backward!r} must be 'torch' or 'hip'")
         if form == "tile" and (band_rows is not None or tile_envs is not None):
             raise ValueError(f"{who}: band_rows / tile_envs belong to form='banded'")
         try:
@@ -1597,6 +1637,16 @@ class ConvEncoder(torch.nn.Module):
                 raise ValueError(f"{who}: image_shape={shape!r} with channels={channels!r}: the activations of one env do not fit the kernel's "
                                  f"{nat.GF_CONV_LDS_BYTES}-byte LDS tile")
             self.plan = ConvPlan(*plan)
+        self.backward, self.backward_plan = backward, None
+        if backward == "hip":
+            b = nat.GfConvBackwardArgs()
+            self._shapes(b.enc)
+            plan = nat.conv_backward_plan(b)
+            if plan is None:
+                raise ValueError(f"{who}: backward='hip' with image_shape={shape!r} and channels={channels!r}: every activation of one env "
+                                 f"must fit the backward kernel's {nat.GF_CONV_BWD_LDS_BYTES}-byte LDS tile, and there is no banded backward; "
+                                 "train this encoder with backward='torch'")
+            self.backward_plan = ConvBackwardPlan(*plan[:3])
         self._scratch = _ConvScratch(form == "banded")
 
     def _shapes(self, a):
@@ -1668,6 +1718,62 @@ class ConvEncoder(torch.nn.Module):
         else:
             fn(a)
         return out
+
+    def encode_train(self, image: torch.Tensor, obs=None, normalizer=None) -> torch.Tensor:
+        """``encode``'s row — the same launch, so ``torch.equal`` to it — carrying a ``grad_fn`` whose backward runs
+        ``gf_conv_encode_backward`` (``backward="hip"``).  On CPU tensors or a backend without that entry: the torch composition
+        ``cat(normalizer(obs), forward(image))``."""
+        if self.backward != "hip":
+            raise RuntimeError("ConvEncoder.encode_train belongs to backward='hip' (forward() is what backward='torch' trains through)")
+        hip = isinstance(image, torch.Tensor) and image.is_cuda and getattr(nat.get_backend(), "conv_encode_backward", None) is not None
+        if not hip:
+            parts = () if obs is None else (obs,) if isinstance(obs, torch.Tensor) else tuple(obs)
+            cols = torch.cat(parts, dim=1) if parts else None
+            norm = _as_normalizer(normalizer, 0 if cols is None else int(cols.shape[1]), "ConvEncoder.encode_train: normalizer") if parts else None
+            latent = self.forward(image)
+            return latent if cols is None else torch.cat((cols if norm is None else norm(cols), latent), dim=1)
+        if image.dim() == 4 and image.is_contiguous():
+            image = image.reshape(image.shape[0], -1)
+        params = [q for m in self.conv[0::2] for q in (m.weight, m.bias)] + [self.head.weight, self.head.bias]
+        return _ConvEncodeRow.apply(self, image, obs, normalizer, *params)
+
+    def _backward_hip(self, image: torch.Tensor, grad_row: torch.Tensor, w1: int, tile_envs: int = 0, groups: int = 0) -> list:
+        """``gf_conv_encode_backward`` of ``grad_row[:, w1:]`` for the rows of ``image``: the parameters' gradients (conv weight, bias,
+        …, head weight, bias), views of ONE fresh tensor per call: a backward over several rows of this encoder gets gradients that
+        do not alias each other (the engine sums them), and autograd may keep them.  Only the kernel's workspace is the module's.
+        ``tile_envs`` / ``groups`` force the launch's tile and persistent workgroups (tests); 0: the plan's."""
+        sc, dev, n, L = self._scratch, self.head.weight.device, int(image.shape[0]), self.latent_dim
+        if grad_row.dtype != torch.float32 or grad_row.dim() != 2 or grad_row.stride(1) != 1 or (n > 1 and grad_row.stride(0) < w1 + L):
+            grad_row = grad_row.to(torch.float32).contiguous()
+        b = sc.bwd
+        a = self._shapes(b.enc)
+        a.num_envs, a.image = n, image.data_ptr()
+        a.image_stride = 0 if n < 2 or image.stride(0) == self.image_size else image.stride(0)
+        a.num_inputs, a.out = 0, None
+        convs = list(self.conv[0::2])
+        params = [q for m in convs for q in (m.weight, m.bias)] + [self.head.weight, self.head.bias]
+        for lay, m in zip(a.layers, convs):
+            lay.weight, lay.bias = m.weight.data_ptr(), m.bias.data_ptr()
+        a.head_weight, a.head_bias = self.head.weight.data_ptr(), self.head.bias.data_ptr()
+        b.tile_envs, b.groups = tile_envs, groups
+        need = nat.conv_backward_workspace_bytes(b)
+        if need < 0:
+            raise RuntimeError(f"gf_conv_backward_workspace_bytes refused the encoder's shapes (status {need})")
+        total = sum(q.numel() for q in params)
+        if sc.workspace is None or sc.workspace.device != dev or sc.workspace.numel() < need // 4:
+            sc.workspace = torch.empty(need // 4 + 1, device=dev, dtype=torch.float32)
+        block, grads, at = torch.empty(total, device=dev, dtype=torch.float32), [], 0
+        for q in params:
+            grads.append(block[at:at + q.numel()].view(q.shape))
+            at += q.numel()
+        b.grad_latent, b.grad_row_stride = grad_row.data_ptr() + 4 * w1, 0 if n < 2 else grad_row.stride(0)
+        for l in range(len(convs)):
+            b.grad_weight[l], b.grad_bias[l] = grads[2 * l].data_ptr(), grads[2 * l + 1].data_ptr()
+        b.grad_head_weight, b.grad_head_bias = grads[-2].data_ptr(), grads[-1].data_ptr()
+        b.workspace, b.workspace_bytes = sc.workspace.data_ptr(), need
+        sc.bwd_keep = (image, grad_row, block)
+        nat.get_backend().conv_encode_backward(b)
+        return grads
 
 
 class EmpiricalDiscountedVariationNormalization(torch.nn.Module):
@@ -2027,7 +2133,7 @@ _STUDENT_TEACHER_KEYS = ("class_name", "activation", "student_hidden_dims", "tea
                          "student_obs_normalization", "teacher_obs_normalization")
 
 
-_STUDENT_ENCODER_KEYS = ("image_shape", "channels", "kernel_size", "stride", "padding", "latent_dim", "form", "band_rows")
+_STUDENT_ENCODER_KEYS = ("image_shape", "channels", "kernel_size", "stride", "padding", "latent_dim", "form", "band_rows", "backward")
 
 
 def _student_encoder(pol: dict) -> Optional["ConvEncoder"]:
@@ -2184,13 +2290,26 @@ class StudentTeacherMLP(_StudentTeacher):
 
     def act_mean(self, obs: torch.Tensor) -> torch.Tensor:
         """The student on its normalised input (rsl_rl's ``act_inference``).  With a ``student_encoder``: the torch composition
-        ``student(cat(normaliser(obs1d), encoder(image)))``, differentiable."""
+        ``student(cat(normaliser(obs1d), encoder(image)))``, differentiable — or, with a ``backward="hip"`` encoder on the HIP backend,
+        the student on ``encode_train``'s row (``encode``'s under ``no_grad``): no torch conv kernel, forward or backward.  The HIP
+        path takes what the launch reads in place — a 2-D float32 CUDA ``obs`` with unit column stride (what ``step_batches`` yields);
+        any other ``obs`` (CPU, another dtype, more dimensions, strided columns) goes through the torch composition, torch's conv
+        kernels included, with a ``RuntimeWarning`` once per policy."""
         enc = self.student_encoder
         if enc is None:
             return self.student(self.student_obs_normalizer(obs))
         W1 = self.num_student_obs
         if obs.shape[-1] != W1 + enc.image_size:
             raise ValueError(f"obs is {obs.shape[-1]} wide; the student reads {W1} columns and a {enc.image_size}-column image")
+        if (enc.backward == "hip" and obs.is_cuda and obs.dim() == 2 and obs.dtype == torch.float32 and obs.stride(1) == 1
+                and getattr(nat.get_backend(), "conv_encode_backward", None) is not None):
+            parts, image = self.split_student_obs(obs)
+            row = (enc.encode_train if torch.is_grad_enabled() else enc.encode)(image, parts or None, self.student_obs_normalizer)
+            return self.student(row)
+        if enc.backward == "hip" and obs.is_cuda and not getattr(self, "_warned_torch_encoder", False):
+            self._warned_torch_encoder = True
+            warnings.warn("StudentTeacherMLP.act_mean: the backward='hip' encoder runs through torch for this obs "
+                          f"(shape {tuple(obs.shape)}, {obs.dtype}, strides {obs.stride()}): it reads 2-D float32 rows with unit column stride", RuntimeWarning)
         latent = enc(obs[..., W1:])
         return self.student(torch.cat((self.student_obs_normalizer(obs[..., :W1]), latent), dim=-1) if W1 else latent)
 

@@ -2160,6 +2160,63 @@ int gf_conv_encode_banded(const GfConvBandedArgs* a, void* stream);   /* gf_conv
 int gf_conv_encode_banded_sizeof(void);                                /* sizeof(GfConvBandedArgs): the binding's self-check for this additive entry */
 int gf_conv_banded_plan(const GfConvBandedArgs* a, int* tile_envs_out, int* band_rows_out, int* num_bands_out, int* lds_bytes_out, int* flat_out);   /* gf_conv_encode_banded's refusals (pointers are not looked at) and its plan.  Host-only, no GPU needed. */
 
+/* ------------------------------------------------------------------------------------------
+ * gf_conv_encode_backward: the gradients of gf_conv_encode's parameters from the gradient of its latent — what torch autograd computes
+ * for   latent = F.linear(flatten(F.elu(F.conv2d(…F.elu(F.conv2d(image, W0, b0))…))), Wh, bh);  latent.backward(grad_latent)
+ * — in THREE launches, nothing saved by the forward.  No gradient of the image or of the 1-D columns; `enc.out`, `enc.inputs` and the
+ * normaliser are not read.  The gradients are WRITTEN, not accumulated.
+ *   A  a persistent grid of G workgroups; workgroup g walks the tiles g, g + G, … of T envs in order.  Per tile it recomputes every
+ *      activation into LDS with gf_conv_encode's device functions (the same bits), keeps ALL of them, writes the last one to the
+ *      workspace's `feat[n, flat]`, and walks back: head dgrad  d_feat[env][k] = Σ_j g[env][j] · Wh[j][k];  per layer, last to first,
+ *      d_pre = d_act · (a > 0 ? 1 : a + 1) from the stored output a (in place of a),  wgrad  dW[co][k] = Σ_rows d_pre[row][co] · im2col[row][k]
+ *      (the bias gradient, column K of the layer's block, is the channel's d_pre summed in double),  and for layers 2 and 3 the dgrad in gather form
+ *      d_act[env][ci][iy][ix] = Σ_(co,dy,dx) d_pre[env][co][(iy + p − dy) / s][(ix + p − dx) / s] · W[co][ci][dy][dx]  (zero where the
+ *      division leaves a remainder or the position is outside).  All three are v_mfma_f32_32x32x2_f32 GEMMs; tails are selected zeros.
+ *      A workgroup adds each tile's [Cout, K + 1] blocks into ITS slice of the workspace (the same lane owns an element every tile);
+ *      the slice is float32: the sum over a workgroup's ⌈tiles / G⌉ tiles is a float32 chain, only the sum over slices (C) is double.
+ *   B  the head's weight gradient  dWh[j][k] = Σ_n g[n][j] · feat[n][k]  (+ the bias as column `flat`, whose feat value is 1): a
+ *      workgroup owns a slab of 128 k columns and one of S contiguous env ranges, keeps its accumulators in registers over the whole
+ *      range (K of the MFMA is the env index) and writes one [latent, flat + 1] partial per range.
+ *   C  every gradient element: its G slices (S partials) summed in ascending order in double, rounded once to float32.
+ * No float atomics: the same arguments give the same bits on every launch.
+ * Workspace, in floats from `workspace` (gf_conv_backward_workspace_bytes): feat [N · flat, rounded up to 4] | conv slices
+ * [min(G, tiles)][Σ_l Cout_l · (K_l + 1)], layer by layer | head partials [S][latent][flat + 1];  S = ⌈N / per⌉ with
+ * per = ⌈N / min(128, ⌈N / 128⌉)⌉ rounded up to even.
+ * gf_conv_backward_plan: T = the largest tile <= GF_CONV_MAX_TILE_ENVS with
+ *   4 · (2 · tab + 128 + T · (Σ_i (size_i | 1) + (latent | 1))) <= GF_CONV_BWD_LDS_BYTES,
+ * size_i the image and every layer's output, tab = the largest of K_l + 1 and (l >= 1) Cout_l · k_l² rounded up to 32; these are the
+ * launch's LDS bytes.  G = min(GF_CONV_BWD_GROUPS, tiles).  tile_envs / groups: 0 = the plan's value, otherwise forced (a forced G is
+ * still capped by the tile count).
+ * Order: GF_E_NULL for a NULL descriptor;  GF_E_RANGE — gf_conv_encode's shape refusals with their codes, one env's backward that
+ * does not fit GF_CONV_BWD_LDS_BYTES, a forced tile_envs outside 1 … GF_CONV_MAX_TILE_ENVS or that does not fit, a forced groups
+ * outside 1 … GF_CONV_BWD_MAX_GROUPS;  GF_E_NULL — image, a layer's or the head's weight or bias, grad_latent, a gradient pointer or
+ * (num_envs > 0) the workspace missing;  GF_E_RANGE — a grad_row_stride below latent_dim (0 means latent_dim), workspace_bytes below
+ * gf_conv_backward_workspace_bytes;  then num_envs == 0 writes zero gradients (launch C alone).  Nothing is launched before the last check.
+ * ---------------------------------------------------------------------------------------- */
+#ifndef GF_CONV_BWD_LDS_BYTES
+#define GF_CONV_BWD_LDS_BYTES 65536    /* a workgroup's budget in launch A: two workgroups per CU, as the forward (profiles/r35_conv_backward.md) */
+#endif
+#define GF_CONV_BWD_GROUPS 512         /* persistent workgroups of launch A: two on each of the MI355X's 256 CUs */
+#define GF_CONV_BWD_MAX_GROUPS 4096
+
+typedef struct GfConvBackwardArgs {
+    GfConvEncodeArgs enc;       /* gf_conv_encode's descriptor: shapes, image / image_stride, parameter pointers */
+    const float* grad_latent;   /* [N, latent] rows grad_row_stride apart (the autograd gradient of the row, W1 columns in) */
+    int64_t grad_row_stride;    /* 0: latent_dim */
+    float* grad_weight[GF_CONV_MAX_LAYERS];   /* [Cout, Cin, k, k] per layer, written */
+    float* grad_bias[GF_CONV_MAX_LAYERS];     /* [Cout] per layer, written */
+    float* grad_head_weight;    /* [latent, flat], written */
+    float* grad_head_bias;      /* [latent], written */
+    void* workspace;            /* gf_conv_backward_workspace_bytes, 4-byte aligned; may hold anything */
+    int64_t workspace_bytes;
+    int32_t tile_envs;          /* T; 0: the plan's */
+    int32_t groups;             /* G; 0: the plan's */
+} GfConvBackwardArgs;
+int gf_conv_encode_backward(const GfConvBackwardArgs* a, void* stream);   /* the conv encoder's parameter gradients from the latent's gradient: recompute per tile, MFMA dgrad / wgrad, fixed-order double reduce (learner.ConvEncoder(backward="hip").encode_train) */
+int gf_conv_backward_sizeof(void);                                          /* sizeof(GfConvBackwardArgs): the binding's self-check for this additive entry */
+int gf_conv_backward_plan(const GfConvBackwardArgs* a, int* tile_envs_out, int* groups_out, int* lds_bytes_out, int* flat_out);   /* gf_conv_encode_backward's shape and plan refusals (pointers are not looked at) and its plan for a->num_envs (groups: GF_CONV_BWD_GROUPS at num_envs == 0).  Host-only, no GPU needed. */
+int64_t gf_conv_backward_workspace_bytes(const GfConvBackwardArgs* a);     /* the workspace gf_conv_encode_backward needs for a->num_envs, or a negative GF_E_* where the plan refuses.  Host-only. */
+
 #ifdef __cplusplus
 }
 #endif

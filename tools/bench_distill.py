@@ -3,7 +3,7 @@
 usage: python tools/bench_distill.py [--sizes 4096,16384,65536] [--steps 24] [--gradient-length 15] [--reps 7] [--calls 50]
                                      [--parts collect,update] [--out FILE]
                                      [--policy mlp|recurrent] [--rnn-type lstm|gru] [--teacher-recurrent]
-                                     [--encoder [--encoder-form tile|banded|both] [--cameras 16x12,32x24,87x58]]
+                                     [--encoder [--encoder-form tile|banded|both] [--cameras 16x12,32x24,87x58] [--encoder-backward torch|hip]]
 
 The student reads a 5-frame history of the 48-wide go2_cmd observation (240 columns), the teacher the newest frame and 187 terrain
 heights (235 columns); both are the reference's 512-256-128 ELU MLPs with 12 actions.  Inputs are random rows — no env: every launch
@@ -43,7 +43,10 @@ collect
   torch           policy.act_mean + policy.evaluate in torch, gf_policy_act for the sample and a copy_ of the teacher's actions
 update
   fused           learner.Distillation.update, the encoder's parameters in the flat bucket
-  restated        tests/rsl_rl_distillation.py over the same policy"""
+  restated        tests/rsl_rl_distillation.py over the same policy
+  fused_hip       with ``--encoder-backward hip``: the same update over a ConvEncoder(backward="hip") of the same weights — the row by
+                  gf_conv_encode, the encoder's gradients by gf_conv_encode_backward — alternating with the two above in every
+                  repetition (a camera the backward refuses is left out)"""
 import argparse
 import copy
 import json
@@ -165,13 +168,14 @@ def update_forms(n: int, T: int, gradient_length: int):
 ENC_PROPRIO, ENC_CAMERAS = 48, ((12, 16), (24, 32), (58, 87))   # (58 x 87, the parkour depth camera: kernels 5 and 3, form="banded" only)
 
 
-def _encoder_policy(cam, form="tile"):
-    """The policy with its encoder in `form` (the same weights in either), or None where that form refuses the camera."""
+def _encoder_policy(cam, form="tile", backward="torch"):
+    """The policy with its encoder in `form` (the same weights in either), or None where that form (or backward) refuses the camera."""
     from genesis_forge_amd.learner import ConvEncoder, StudentTeacherMLP
 
     torch.manual_seed(0)
     try:
-        enc = ConvEncoder((1, *cam), (16, 32), kernel_size=(5, 3) if cam[0] > 32 else 3, stride=2, padding=0, latent_dim=64, form=form)
+        enc = ConvEncoder((1, *cam), (16, 32), kernel_size=(5, 3) if cam[0] > 32 else 3, stride=2, padding=0, latent_dim=64, form=form,
+                          backward=backward)
     except ValueError:
         return None
     return StudentTeacherMLP(ENC_PROPRIO, TEACHER_W, A, HIDDEN, HIDDEN, student_encoder=enc).cuda()
@@ -227,7 +231,7 @@ def encoder_collect_forms(n: int, cam, encoder_form="tile"):
     return {**{names[form]: conv_encode(f) for form, f in hip.items()}, "torch_encoder": torch_encoder, "torch": torch_forward}
 
 
-def encoder_update_forms(n: int, T: int, gradient_length: int, cam):
+def encoder_update_forms(n: int, T: int, gradient_length: int, cam, backward="torch"):
     from genesis_forge_amd import _native as nat
     from genesis_forge_amd.learner import Distillation, RolloutStorage
     from rsl_rl_distillation import RslRlDistillation
@@ -258,7 +262,21 @@ def encoder_update_forms(n: int, T: int, gradient_length: int, cam):
         ref_policy.load_state_dict(ref_start)
         out["restated"] = RslRlDistillation(ref_policy, st, **cfg).update()
 
-    return {"fused": fused, "restated": restated}, out
+    forms = {"fused": fused, "restated": restated}
+    hip_policy = _encoder_policy(cam, backward="hip") if backward == "hip" else None
+    if hip_policy is not None:
+        print(f"# camera {cam[1]}x{cam[0]} backward hip: {hip_policy.student_encoder.backward_plan}", flush=True)
+        hip_alg = Distillation(hip_policy, st, **cfg)
+
+        def fused_hip():
+            hip_alg.params.copy_(start)
+            hip_alg.exp_avg.zero_(), hip_alg.exp_avg_sq.zero_(), hip_alg._state.zero_()
+            hip_alg._state_lr[0] = cfg["learning_rate"]
+            hip_alg._calls = 0
+            out["fused_hip"] = hip_alg.update()
+
+        forms = {"fused": fused, "fused_hip": fused_hip, "restated": restated}
+    return forms, out
 
 
 def _recurrent_policy(rnn_type: str, teacher_recurrent: bool):
@@ -390,6 +408,8 @@ def main():
     ap.add_argument("--teacher-recurrent", action="store_true")
     ap.add_argument("--encoder", action="store_true")
     ap.add_argument("--encoder-form", default="tile", choices=("tile", "banded", "both"), help="the ConvEncoder form(s) of the collect part")
+    ap.add_argument("--encoder-backward", default="torch", choices=("torch", "hip"),
+                    help="with --encoder: hip adds the update over a ConvEncoder(backward='hip'), alternating with the torch form")
     ap.add_argument("--cameras", default=None, help="with --encoder: WxH,… out of 16x12,32x24,87x58 (default: all)")
     args = ap.parse_args()
     recurrent = args.policy == "recurrent"
@@ -425,7 +445,7 @@ def _run(args, recurrent: bool, cam, lines: list) -> None:
                 print(json.dumps(lines[-1]), flush=True)
         if "update" in args.parts.split(","):
             if cam is not None:
-                forms, out = encoder_update_forms(n, args.steps, args.gradient_length, cam)
+                forms, out = encoder_update_forms(n, args.steps, args.gradient_length, cam, args.encoder_backward)
             elif recurrent:
                 forms, out = recurrent_update_forms(n, args.steps, args.gradient_length, args.rnn_type, args.teacher_recurrent)
             else:

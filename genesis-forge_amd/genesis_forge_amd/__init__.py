@@ -14,12 +14,13 @@ from .managers.ray_caster import RayCaster
 from .managers.terrain_curriculum import TerrainCurriculum
 from .managers.push import PushDisturbance
 from .managers.action_delay import ActuatorDelay
+from .managers.depth_camera import DepthCamera
 from .managers.action import DelayedPositionActionManager
 from .learner import ConvEncoder
 from .runner import DistillationRunner, OnPolicyRunner
 from .symmetry import MirrorSymmetry
 
-__all__ = ["GenesisEnv", "ManagedEnvironment", "EnvMode", "OnPolicyRunner", "DistillationRunner", "MirrorSymmetry", "HeightScanner", "RayCaster", "TerrainCurriculum", "PushDisturbance", "ActuatorDelay", "DelayedPositionActionManager", "ConvEncoder", "install_as_genesis_forge"]
+__all__ = ["GenesisEnv", "ManagedEnvironment", "EnvMode", "OnPolicyRunner", "DistillationRunner", "MirrorSymmetry", "HeightScanner", "RayCaster", "TerrainCurriculum", "PushDisturbance", "ActuatorDelay", "DepthCamera", "DelayedPositionActionManager", "ConvEncoder", "install_as_genesis_forge"]
 __version__ = "0.1.0"
 
 

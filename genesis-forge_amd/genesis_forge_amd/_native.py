@@ -615,6 +615,22 @@ class GfActionDelayArgs(C.Structure):
                 ("slots", C.c_int32), ("head", C.c_int32), ("lag_lo", C.c_int32), ("lag_hi", C.c_int32), ("prime_all", C.c_int32)]
 
 
+# the depth camera model (managers.DepthCamera.step): gf_depth_camera — additive in the same way, not in ABI_STRUCTS
+GF_DEPTH_CAMERA_SPAN_ENVS = 16
+GF_DEPTH_CAMERA_MAX_SLOTS = 16
+GF_DEPTH_CAMERA_SEED_TAG = 0xDE97CA3E5A11F0A3   # the kernel keys the camera's draws with seed ^ this tag (gf_step.h)
+
+
+class GfDepthCameraArgs(C.Structure):
+    _fields_ = [("num_envs", C.c_int64), ("pos", P), ("quat", P), ("pattern", P), ("episode_length", P), ("ring", P), ("head", P), ("lag", P),
+                ("image", P), ("due_out", P), ("pos_stride", C.c_int64), ("quat_stride", C.c_int64), ("terrain", GfTerrainView),
+                ("seed", C.c_uint64), ("tick", C.c_uint32), ("env_offset", C.c_uint32), ("num_rays", C.c_int32), ("align", C.c_int32),
+                ("mode", C.c_int32), ("interval", C.c_int32), ("staggered", C.c_int32), ("stack", C.c_int32), ("slots", C.c_int32),
+                ("latency_lo", C.c_int32), ("latency_hi", C.c_int32), ("normalize", C.c_int32), ("axis", C.c_float * 3),
+                ("max_range", C.c_float), ("miss_value", C.c_float), ("near_clip", C.c_float), ("far_clip", C.c_float), ("noise", C.c_float),
+                ("dropout", C.c_float), ("dropout_value", C.c_float), ("inv_span", C.c_float)]
+
+
 # the conv depth encoder of a distillation student (learner.ConvEncoder.encode): gf_conv_encode — additive in the same way, not in ABI_STRUCTS
 GF_CONV_MAX_LAYERS = 3
 GF_CONV_MAX_CHANNELS = 64
@@ -1018,6 +1034,12 @@ class HipBackend(Backend):
             raise GfError(f"ABI drift: sizeof(GfActionDelayArgs) is {n} in the library, {C.sizeof(GfActionDelayArgs)} in the binding")
         self.lib.gf_action_delay.restype = C.c_int
         self.lib.gf_action_delay.argtypes = [C.POINTER(GfActionDelayArgs), C.c_void_p]
+        # the depth camera model (managers.DepthCamera): additive in the same way
+        n = self.lib.gf_depth_camera_sizeof()
+        if n != C.sizeof(GfDepthCameraArgs):
+            raise GfError(f"ABI drift: sizeof(GfDepthCameraArgs) is {n} in the library, {C.sizeof(GfDepthCameraArgs)} in the binding")
+        self.lib.gf_depth_camera.restype = C.c_int
+        self.lib.gf_depth_camera.argtypes = [C.POINTER(GfDepthCameraArgs), C.c_void_p]
         # the conv depth encoder (learner.ConvEncoder): additive in the same way
         n = self.lib.gf_conv_encode_sizeof()
         if n != C.sizeof(GfConvEncodeArgs):
@@ -1206,6 +1228,13 @@ class HipBackend(Backend):
         rc = self.lib.gf_action_delay(C.byref(args), self._stream())
         if rc != 0:
             self._raise("action_delay", rc)
+
+    def depth_camera(self, args) -> None:
+        """gf_depth_camera on the current stream (managers.DepthCamera.step).  Only this backend has it: a backend without the
+        method makes the camera run the same sequence as torch ops around ``RayCaster.cast``."""
+        rc = self.lib.gf_depth_camera(C.byref(args), self._stream())
+        if rc != 0:
+            self._raise("depth_camera", rc)
 
     def build_info(self) -> str:
         return self.lib.gf_build_info().decode()

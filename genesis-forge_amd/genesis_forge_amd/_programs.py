@@ -311,6 +311,9 @@ class _DryRunBackend(nat.HipBackend):
     def action_delay(self, args) -> None:   # (ActuatorDelay launches from a Python phase of the step: the tensors here are host memory)
         pass
 
+    def depth_camera(self, args) -> None:   # (DepthCamera launches outside the step: the tensors here are host memory)
+        pass
+
     def event_create(self):
         return None
 

@@ -11,6 +11,7 @@ from .ray_caster import RayCaster
 from .terrain_curriculum import TerrainCurriculum
 from .push import PushDisturbance
 from .action_delay import ActuatorDelay
+from .depth_camera import DepthCamera
 from .entity_manager import EntityManager
 from .observation_manager import ObservationManager
 from .config import MdpFnClass, ResetMdpFnClass
@@ -18,5 +19,5 @@ from .config import MdpFnClass, ResetMdpFnClass
 __all__ = [
     "BaseManager", "RewardManager", "TerminationManager", "CommandManager", "VelocityCommandManager", "GaitCommandManager",
     "BaseActionManager", "PositionActionManager", "PositionWithinLimitsActionManager", "DelayedPositionActionManager", "ActuatorDelay", "ContactManager",
-    "TerrainManager", "HeightScanner", "RayCaster", "TerrainCurriculum", "PushDisturbance", "EntityManager", "ObservationManager", "MdpFnClass", "ResetMdpFnClass",
+    "TerrainManager", "HeightScanner", "RayCaster", "TerrainCurriculum", "PushDisturbance", "DepthCamera", "EntityManager", "ObservationManager", "MdpFnClass", "ResetMdpFnClass",
 ]

@@ -93,3 +93,10 @@ def ray_cast(env, caster) -> torch.Tensor:
     (managers/ray_caster.py — one ``gf_ray_cast`` launch into the caster's persistent buffer).  Untagged like ``height_scan``: an
     EXTERNAL item, evaluated each step, with the item's ``scale`` / ``noise`` applied like any other."""
     return caster.cast()
+
+
+def depth_camera(env, camera) -> torch.Tensor:
+    """The image of a camera model, shape (num_envs, camera.stack · num_rays): ``camera.image`` (managers/depth_camera.py), as the
+    camera's last ``step()`` left it — the env runs that launch behind the step; nothing is cast here.  Untagged like ``ray_cast``:
+    an EXTERNAL item, evaluated each step, with the item's ``scale`` / ``noise`` applied like any other."""
+    return camera.image

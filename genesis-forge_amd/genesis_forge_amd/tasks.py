@@ -452,6 +452,12 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
     front of the trunk and pitched 30 degrees down, 4 m range, depth output) adds ``self.depth_camera`` and an ObservationManager
     ``"depth"`` that holds that one item: what a deployable student sees
     (``obs_groups={"policy": ["policy", "depth"], "teacher": ["critic"]}``).  ``None`` builds the managers above and nothing else.
+    A ``"model"`` key in that dict (a dict of ``DepthCamera`` keyword arguments; ``{}`` is one frame per 5 steps, staggered) puts a
+    camera model on the sensor: ``self.depth_sensor`` is the ``DepthCamera``, ``step()`` runs it behind the step — one more launch that
+    casts only the envs whose frame is due, the step inside stays the recorded one — and the ``"depth"`` item hands out
+    ``depth_sensor.image`` (frame rate, latency, clip, noise, holes, ``stack`` frames as channels) without casting again.  A student's
+    observation ``(proprio_block, env.depth_sensor.image)`` with ``ConvEncoder(image_shape=(stack, H, W), …)`` needs no further change.
+    Without ``"model"`` the sensor is what it was: a cast per observation.
     ``curriculum`` (a dict: ``num_levels`` (5), ``num_types`` (2), ``cell_size`` ((8, 8) metres), ``max_height`` (0.1 m, the roughness of the
     top level) and ``TerrainCurriculum`` keyword arguments) makes the terrain a ``num_levels x num_types`` grid of cells whose roughness
     grows with the level index — an explicit deterministic height field (``graded_height_field``) — adds ``self.terrain_curriculum`` and
@@ -482,6 +488,10 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
         self._height_reward, self._rotation, self._cmd_resample_s = height_reward, rotation, cmd_resample_s
         self._height_scan = None if height_scan is None else dict(height_scan)
         self._depth_camera = None if depth_camera is None else dict(depth_camera)
+        self._depth_model = None if self._depth_camera is None or self._depth_camera.get("model") is None else dict(self._depth_camera["model"])
+        if self._depth_camera is not None:
+            self._depth_camera.pop("model", None)
+        self.depth_sensor = None
         self.scene = new_scene(dt=self.dt, substeps=2, **kw)
         tk = dict(pos=(-12, -12, 0), n_subterrains=(1, 1), subterrain_size=(24, 24), vertical_scale=0.001,
                   subterrain_types=[["random_uniform_terrain"]],
@@ -587,8 +597,17 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
             if kw.get("pattern") is None:
                 kw["pattern"] = pinhole_pattern(16, 12, 87.0)
             self.depth_camera = RayCaster(self, self.terrain_manager, entity_manager=self.robot_manager, **kw)
-            self.depth_manager = ObservationManager(self, name="depth", cfg={
-                "depth": {"fn": observations.ray_cast, "params": {"caster": self.depth_camera}}})
+            item = {"fn": observations.ray_cast, "params": {"caster": self.depth_camera}}
+            if self._depth_model is not None:
+                from genesis_forge_amd.managers import DepthCamera
+
+                self.depth_sensor = DepthCamera(self.depth_camera, **self._depth_model)
+                width = self.depth_sensor.stack * self.depth_camera.num_rays
+                if width > 255:
+                    raise ValueError(f"the camera model's image has stack x rays = {width} columns, an observation frame holds at most 255: "
+                                     "feed the policy from env.depth_sensor.image instead of the 'depth' observation")
+                item = {"fn": observations.depth_camera, "params": {"camera": self.depth_sensor}}
+            self.depth_manager = ObservationManager(self, name="depth", cfg={"depth": item})
         if self._push is not None:
             from genesis_forge_amd.managers import PushDisturbance
 
@@ -600,12 +619,17 @@ class Go2RoughTerrainEnv(ManagedEnvironment):
             self.action_delay = self.action_manager.delay
         if self.push is not None:
             self.push.build()
+        if self.depth_sensor is not None:
+            self.depth_sensor.build()
 
     def step(self, actions):
-        """The step, then the pushes with the step's done masks (code around ``super().step()``: the step inside is recorded as ever)."""
+        """The step, then the pushes with the step's done masks and the camera model's frame (code around ``super().step()``: the step
+        inside is recorded as ever)."""
         out = super().step(actions)
         if self.push is not None:
             self.push.step(out[2], out[3])
+        if self.depth_sensor is not None:
+            self.depth_sensor.step()
         return out
 
 

@@ -1788,6 +1788,85 @@ typedef struct GfActionDelayArgs {
 } GfActionDelayArgs;
 
 /* ------------------------------------------------------------------------------------------
+ * Depth camera model (managers/depth_camera.py; the update_period of Isaac Lab's sensors, the one-frame-per-5-steps cameras of
+ * Extreme-Parkour-style training): a sensor delivers a frame every `interval` control steps, a frame or two late, clipped to its
+ * range, with noise and holes, and the policy sees the last `stack` frames as channels.  One launch per control step casts ONLY the
+ * envs whose frame is due and keeps, per env, a ring of S = `slots` frames:
+ *   ring  [S, N, R] f32, slot-major            head [N] i32: the slot of the newest frame            lag [N] i32: frames of latency
+ *   image [N, stack*R] f32, newest channel first: image[n, c, :] is the frame lag[n] + c captures ago
+ * For env n (n the LOCAL index), with `tick` the camera's own call counter (uint32, wrapping):
+ *   1. fresh = episode_length[n] <= 1                                   (gf_action_delay's rule: the env's counter after the step)
+ *   2. phase = staggered ? n % interval : 0;   due = fresh || (uint32)(tick + phase) % interval == 0;   due_out[n] = due (if given)
+ *   3. not due: nothing else of env n is read or written — no ring slot, no head, no lag, no image row, no pose.
+ *   4. fresh: u = u24_to_unit(x word of Philox4x32-10, counter (n + env_offset, 0, tick, 1), key seed ^ GF_DEPTH_CAMERA_SEED_TAG);
+ *             W = latency_hi - latency_lo + 1;  lag[n] = latency_lo + min((int)(u * (float)W), W - 1)   (gf_action_delay's draw rule)
+ *      otherwise l = lag[n]; an l outside 0 … S - stack (state the launch did not write) reads as 0.
+ *   5. h = head[n], read as 0 when outside 0 … S-1;  h = (h + 1) % S;  head[n] = h.
+ *   6. every ray r: d = what gf_ray_cast gives for (n, r) with the same pose, pattern, align, mode, axis, max_range, miss_value
+ *      and terrain (the same device functions: the same bits).  Then, in f32, one rounding per operation:
+ *        if noise != 0 or dropout != 0:  (u0, u1) = u24_to_unit of the x and y words of the block with counter (n + env_offset, r, tick, 0)
+ *        if noise != 0:   v = d + noise * (2*u0 - 1)         else v = d
+ *        v = v < near ? near : v;   v = v > far ? far : v                         (a NaN passes)
+ *        if dropout != 0 and u1 < dropout:   v = dropout_value
+ *        if normalize:    v = (v - near) * inv_span - 0.5    (inv_span = 1 / (far - near), formed by the host in double, rounded once)
+ *   7. fresh: ring[s, n, :] = v for EVERY slot s and image[n, c, :] = v for every channel c: an episode never sees another's frames.
+ *      otherwise: ring[h, n, :] = v;  image[n, c, :] = (l + c == 0) ? v : ring[(h - l - c) mod S, n, :]  for c < stack — slots that
+ *      earlier launches wrote (1 <= l + c <= S - 1 there): the launch never reads what it writes.
+ * A 256-lane workgroup owns a span of GF_DEPTH_CAMERA_SPAN_ENVS envs.  Its first wave evaluates the span's due flags and compacts the
+ * due envs into an LDS list by ballot and prefix count; a workgroup without a due env returns there.  Otherwise it stages the pattern
+ * and the frames of the due envs only and walks ndue * R elements in flat order, consecutive lanes on consecutive rays, so every lane
+ * is busy whichever envs are due.  Values are stored from registers, 16 bytes wide when num_rays % 4 == 0 and ring and image are
+ * 16-byte aligned (every row of every slot and channel then is), one float at a time otherwise.  No atomics, nothing between workgroups.
+ * Refusals, before anything is launched: GF_E_NULL — args, pos, pattern, ring, head, lag, image, episode_length, quat with
+ * align != 0; GF_E_RANGE — everything gf_ray_cast refuses (num_envs < 0 or more than 2^31 - 1 workgroups, num_rays, pos_stride,
+ * quat_stride, align, mode, max_range, a field under 2 x 2), interval < 1, stack < 1, not 0 <= latency_lo <= latency_hi,
+ * slots < latency_hi + stack or slots > GF_DEPTH_CAMERA_MAX_SLOTS, staggered / normalize outside {0, 1}, near or far not finite or
+ * near >= far, dropout outside 0 … 1, noise negative or not finite.  num_envs == 0 is a no-op (after the checks, before any HIP
+ * call).  Runs under GF_PHASE_TERRAIN for gf_profile_begin.  Not a phase of the step.
+ * ---------------------------------------------------------------------------------------- */
+#define GF_DEPTH_CAMERA_SPAN_ENVS 16                       /* envs per workgroup (at most 64: one ballot); profiles/r36_depth_camera.md */
+#define GF_DEPTH_CAMERA_MAX_SLOTS 16                       /* the ring's capacity: latency_hi + stack <= 16 */
+#define GF_DEPTH_CAMERA_SEED_TAG 0xDE97CA3E5A11F0A3ull     /* XOR-ed into the seed of the camera's draws: a key of its own */
+
+typedef struct GfDepthCameraArgs {
+    int64_t num_envs;
+    const float* pos;          /* row n at pos + n * pos_stride: x, y, z of the base */
+    const float* quat;         /* row n at quat + n * quat_stride: w, x, y, z; may be NULL with align = 0 */
+    const float* pattern;      /* [R, 6]: px, py, pz, ex, ey, ez */
+    const int32_t* episode_length;   /* [N]: fresh where <= 1 */
+    float* ring;               /* [S, N, R] slot-major */
+    int32_t* head;             /* [N] the slot of the newest frame: read, advanced where due */
+    int32_t* lag;              /* [N] frames of latency: rewritten where fresh */
+    float* image;              /* [N, stack * R] dense, newest channel first */
+    uint8_t* due_out;          /* [N] or NULL: 1 where the env was cast in this launch, 0 elsewhere */
+    int64_t pos_stride;        /* in floats, >= 3 */
+    int64_t quat_stride;       /* in floats, >= 4 */
+    GfTerrainView terrain;
+    uint64_t seed;             /* Philox key = seed ^ GF_DEPTH_CAMERA_SEED_TAG */
+    uint32_t tick;             /* the camera's own call counter */
+    uint32_t env_offset;
+    int32_t num_rays;          /* R: 1 … GF_RAY_CAST_MAX_RAYS */
+    int32_t align;             /* GF_RAY_ALIGN_* */
+    int32_t mode;              /* GF_RAY_MODE_* */
+    int32_t interval;          /* control steps between two frames, >= 1 */
+    int32_t staggered;         /* 1: phase n % interval; 0: every env in the same steps */
+    int32_t stack;             /* channels of image, >= 1 */
+    int32_t slots;             /* S >= latency_hi + stack */
+    int32_t latency_lo;        /* 0 <= latency_lo <= latency_hi, in frames */
+    int32_t latency_hi;
+    int32_t normalize;         /* 1: image in [-0.5, 0.5] */
+    float axis[3];             /* the optical axis in the body frame (mode 1) */
+    float max_range;           /* finite, >= 0 */
+    float miss_value;
+    float near_clip;           /* finite, < far_clip */
+    float far_clip;
+    float noise;               /* half-width of the uniform noise in metres, finite, >= 0 */
+    float dropout;             /* probability of a hole, 0 … 1 */
+    float dropout_value;       /* what a hole reads */
+    float inv_span;            /* 1 / (far_clip - near_clip) */
+} GfDepthCameraArgs;
+
+/* ------------------------------------------------------------------------------------------
  * gf_conv_encode: the convolutional depth encoder in front of a distillation student (learner.ConvEncoder) in ONE launch.  For
  * every env n
  *     out[n, 0 : W1]      = the 1-D observation columns (up to GF_MLP_MAX_INPUTS segments side by side, as gf_mlp_act reads them),
@@ -1893,6 +1972,8 @@ int gf_push(const GfPushArgs* a, void* stream);                  /* per-env inte
 int gf_push_sizeof(void);                                        /* sizeof(GfPushArgs): the binding's self-check for this additive entry */
 int gf_action_delay(const GfActionDelayArgs* a, void* stream);  /* per-env delayed position targets: ring write, lagged read, re-draw and priming of the fresh envs, in one launch (Isaac Lab DelayedPDActuator, legged_gym action lag) */
 int gf_action_delay_sizeof(void);                                /* sizeof(GfActionDelayArgs): the binding's self-check for this additive entry */
+int gf_depth_camera(const GfDepthCameraArgs* a, void* stream);  /* a depth camera's frame rate, latency, noise and frame stack: only the envs whose frame is due are cast, in one launch (Isaac Lab update_period, Extreme-Parkour depth buffer) */
+int gf_depth_camera_sizeof(void);                                /* sizeof(GfDepthCameraArgs): the binding's self-check for this additive entry */
 int gf_conv_encode(const GfConvEncodeArgs* a, void* stream);   /* the 1-D observation columns (normalised) and the conv encoder's latent of the image into the student MLP's input row, in one launch (learner.ConvEncoder.encode; the depth encoder of a distillation student) */
 int gf_conv_encode_sizeof(void);                                 /* sizeof(GfConvEncodeArgs): the binding's self-check for this additive entry */
 int gf_conv_plan(const GfConvEncodeArgs* a, int* tile_envs_out, int* lds_bytes_out, int* flat_out);   /* gf_conv_encode's refusals (pointers are not looked at) and its tile: T envs per workgroup, the launch's LDS bytes, the head's input width.  Host-only, no GPU needed. */
